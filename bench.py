@@ -22,6 +22,18 @@ the oracle (oracle/hm_oracle.c, the C restatement pinned against HM) on this box
 workload; `cpu_baseline_reference` is HM's own decoder (oracle/_ref/TAppDecoder, when the build container shipped it) on an
 HM-encoded 2160p Main10 stream, HM's own per-picture decode time -- reported baselines, not targets.
 
+A plain run (no `--full`) does only what the headline needs: set-up, `--warmup` untimed steps, `--steps` timed steps, the
+outputs when `--dump-outputs` is given, and the line with `metric`, `value`, `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` (plus the run's configuration).  `--full` adds everything else: `roofline`, `kernels` and the other per-kernel
+figures (runs of their own with hipEvents), the one-stream repeat, the measured copy bandwidth, the host-inclusive path,
+`kernels_bi` and the CPU baselines; for `--workload decode` the hash-check-off / host-thread passes, host parsing alone and HM's
+decoder; for `--workload gop` the per-kernel times.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step left in the device pictures, as a caller would
+download them (hmgpu_picture_download): one fixed, seeded sample of sample positions per plane, the same for every picture,
+as float32 DIR/pic<k>_{y,cb,cr}.npy (about 60 MB in all, under 64 MB; whole planes when they fit).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
 `--gpus N` (N > 1) without a torch.distributed environment starts the N ranks itself (`python -m torch.distributed.run`, as a child
 process, before anything touches the GPU) and relays rank 0's line; under an external launcher WORLD_SIZE must equal N.
 """
@@ -37,6 +49,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+DUMP_MAX_VALUES = 15000000     # --dump-outputs: float32 values over all files (60 MB of data + the .npy headers)
 
 
 def algorithmic_bytes(p):
@@ -109,9 +122,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-inclusive", action="store_true", help="skip the host-inclusive (staging included) measurement of the default workload")
     ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-kernel times and roofline, "
+                    "copy bandwidth, host-inclusive path, B-picture MC kernels, CPU baselines (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's pictures (a seeded sample of each plane) as float32 DIR/*.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.workload == "decode":
+        ap.error("--dump-outputs: the decode workload hands its pictures to the application inside the timed passes; not supported")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             return launch_ranks(args.gpus)
@@ -135,7 +156,13 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    copy_gbps = measured_copy_bandwidth(local_rank) if world == 1 else None
+    if world == 1 and args.full:
+        copy_gbps = measured_copy_bandwidth(local_rank)
+    else:
+        # the device is opened through torch's HIP runtime before hmgpu_create, as the copy measurement did for every run before it
+        # moved behind --full: the timed replay measured up to ~1 % faster so than with hmgpu_create opening the device itself
+        torch.empty(1, device="cuda:%d" % local_rank)
+        copy_gbps = None
 
     import libhm_amd
     from libhm_amd import abi
@@ -178,8 +205,10 @@ def main():
     # two distinct parsed pictures, staged alternately into nb device pictures with their own buffers
     # every picture of the batch predicts from its OWN reference pictures (no flattering reuse of one reference in cache)
     metas = [synth.make_picture(w, h, bd, seed=0x484D3136 + 7 * rank + i, bi=bool(args.bi), ref_handles=([0], [1]), **kw) for i in range(2)]
-    host_incl = wl == "full" and world == 1 and not args.no_host_inclusive and 4 * nb <= 64
-    seq = abi.make_seq(w, h, bd, bd, log2_ctu=6, max_pictures=(4 if host_incl else 3) * nb)
+    # (the picture pool is sized for the host-inclusive leg whether it runs or not: the timed replay sees the same device layout)
+    host_pool = wl == "full" and world == 1 and not args.no_host_inclusive and 4 * nb <= 64
+    host_incl = host_pool and args.full
+    seq = abi.make_seq(w, h, bd, bd, log2_ctu=6, max_pictures=(4 if host_pool else 3) * nb)
     ctx = libhm_amd.Context(seq, device=local_rank)
     ref_planes = [synth.noise_planes(w, h, bd, 100 + rank), synth.blocky_planes(w, h, bd, 200 + rank)]
     pics, refs_of = [], []
@@ -207,6 +236,16 @@ def main():
     # barrier + sync on both sides, MAX over ranks (libhm_amd/dist.py)
     elapsed = hdist.timed_region(dist, lambda: ctx.replay(pics, ALL, args.steps), ctx.sync,
                                  device=("cuda:%d" % local_rank) if dist is not None else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, pics, args.dump_outputs)
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, wl, w, h, nb, world, elapsed, t_stage)), flush=True)
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # the same steps on ONE stream (kernel after kernel: what the per-kernel times below add up to)
     ms_one_stream = None
@@ -234,9 +273,8 @@ def main():
         hi = host_inclusive(ctx, metas, pics, refs_of, nb, w, h, args)
 
     if rank == 0:
-        luma_px = w * h
-        total_px = world * nb * args.steps * luma_px
-        value = total_px / elapsed / 1e6
+        out = headline(args, wl, w, h, nb, world, elapsed, t_stage)
+        value = world * nb * args.steps * w * h / elapsed / 1e6
         bytes_pp = [algorithmic_bytes(m) for m in metas]
         kernels = {}
         dom, dom_t = None, -1.0
@@ -272,25 +310,11 @@ def main():
                 "frac": kernels[dom]["frac"], "traffic": traffic, "traffic_source": traffic_source,
                 "algorithmic_bytes_per_launch": int(kernels[dom]["alg_MB"] * 1e6)}
         dev_ms = sum(k["avg_ms"] for k in kernels.values())
-        out = {
-            "metric": "decoded Mpixels/s (luma), 2160p Main10 reconstruction + loop filters" if wl == "full" else
-                      "Mpixels/s (luma) through the '%s' stage set (SURVEY 8d sub-benchmark)" % wl, "value": round(value, 1),
-            "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "int16 samples / int32 accumulate", "data": "synthetic",
-            "config": {"workload": "%dx%d Main10 %s pictures, pre-parsed CTU metadata: %s, "
-                                   "batch of %d independent pictures per step, inputs resident in HBM" %
-                                   (w, h, "B (bi-pred)" if args.bi else "lowdelay_P",
-                                    {"full": "prep+MC+dequant/IT/recon+deblock+SAO", "idct": "prep+MC+dequant/IT/recon, 32x32 luma / 16x16 chroma TUs, stress levels",
-                                     "mc": "prep+MC+dequant/IT/recon", "mc_bi": "prep+MC+dequant/IT/recon",
-                                     "intra": "all-intra pictures: prep+intra prediction/dequant/IT/recon (CTU-row wavefront)+deblock+SAO", "filter": "prep+MC+dequant/IT/recon+deblock+SAO, 25% intra CUs (Bs 2 edges)"}[wl], nb),
-                       "sub_benchmark": wl, "streams": args.streams,
-                       "pictures_per_step": nb, "parallelism": "frame-parallel, 1 process per GPU, no data-path collective"},
+        out.update({
             "roofline": roof, "kernels": kernels, "device_ms_per_step_sum_of_kernels": round(dev_ms, 4),
             "hbm_GBps_whole_step_algorithmic": round(sum(sum(b[k] for k in kernels) for b in [bytes_pp[i % 2] for i in range(nb)])
                                                     / (elapsed / args.steps) / 1e9, 1),
-            "staging_s_for_batch_incl_first_run": round(t_stage, 3),
-        }
+        })
         if ms_one_stream is not None:
             out["ms_per_step_one_stream"] = round(ms_one_stream, 4)
         if copy_gbps is not None:
@@ -314,6 +338,46 @@ def main():
         ctx.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def headline(args, wl, w, h, nb, world, elapsed, t_stage):
+    """the fields of the line a plain run prints (`--full` adds to them)"""
+    value = world * nb * args.steps * w * h / elapsed / 1e6
+    return {
+        "metric": "decoded Mpixels/s (luma), 2160p Main10 reconstruction + loop filters" if wl == "full" else
+                  "Mpixels/s (luma) through the '%s' stage set (SURVEY 8d sub-benchmark)" % wl, "value": round(value, 1),
+        "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int16 samples / int32 accumulate", "data": "synthetic",
+        "config": {"workload": "%dx%d Main10 %s pictures, pre-parsed CTU metadata: %s, "
+                               "batch of %d independent pictures per step, inputs resident in HBM" %
+                               (w, h, "B (bi-pred)" if args.bi else "lowdelay_P",
+                                {"full": "prep+MC+dequant/IT/recon+deblock+SAO", "idct": "prep+MC+dequant/IT/recon, 32x32 luma / 16x16 chroma TUs, stress levels",
+                                 "mc": "prep+MC+dequant/IT/recon", "mc_bi": "prep+MC+dequant/IT/recon",
+                                 "intra": "all-intra pictures: prep+intra prediction/dequant/IT/recon (CTU-row wavefront)+deblock+SAO", "filter": "prep+MC+dequant/IT/recon+deblock+SAO, 25% intra CUs (Bs 2 edges)"}[wl], nb),
+                   "sub_benchmark": wl, "streams": args.streams,
+                   "pictures_per_step": nb, "parallelism": "frame-parallel, 1 process per GPU, no data-path collective"},
+        "staging_s_for_batch_incl_first_run": round(t_stage, 3),
+    }
+
+
+def dump_outputs(ctx, pics, out_dir):
+    """--dump-outputs: the planes of every picture in `pics` as a caller downloads them, float32 DIR/pic<k>_{y,cb,cr}.npy.  Planes are
+    sampled when the batch does not fit DUMP_MAX_VALUES: one seeded set of positions per plane (sorted flat indices), the same for
+    every picture, so that equal arguments give equal files"""
+    os.makedirs(out_dir, exist_ok=True)
+    total, idx = None, [None] * 3
+    for k, pic in enumerate(pics):
+        planes = ctx.download(pic)
+        if total is None:
+            total = len(pics) * sum(p.size for p in planes)
+            for c, p in enumerate(planes):
+                n = p.size * DUMP_MAX_VALUES // total
+                if n < p.size:
+                    idx[c] = np.sort(np.random.RandomState(0x0D0E + c).choice(p.size, n, replace=False))
+        for c, p in enumerate(planes):
+            v = p.ravel() if idx[c] is None else p.ravel()[idx[c]]
+            np.save(os.path.join(out_dir, "pic%02d_%s.npy" % (k, ("y", "cb", "cr")[c])), v.astype(np.float32))
 
 
 def mc_bi_kernels(w, h, bd, nb, rank, local_rank, args):
@@ -459,11 +523,15 @@ def gop_main(args, hdist, dist, rank, world, local_rank, copy_gbps):
         for _ in range(args.steps):
             run.step()
     elapsed = hdist.timed_region(dist, steps, ctx.sync, device=("cuda:%d" % local_rank) if dist is not None else None)
-    ctx.set_profiling(True)
-    ctx.stats(reset=True)
-    run.step()
-    st = ctx.stats(reset=True)
-    ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, [run.handle_of[gp] for gp in run.mine], args.dump_outputs)
+    st = None
+    if args.full:
+        ctx.set_profiling(True)
+        ctx.stats(reset=True)
+        run.step()
+        st = ctx.stats(reset=True)
+        ctx.set_profiling(False)
     # every rank says what it moved: a scaling run is self-evidencing (which backend carried the pictures, how many ranks, how many bytes)
     my_sends = sum(len(s[3]) for lvl in run.plan for s in lvl["sends"] if s[2] == rank)
     my_recvs = sum(1 for lvl in run.plan for s in lvl["sends"] if rank in s[3])
@@ -483,9 +551,10 @@ def gop_main(args, hdist, dist, rank, world, local_rank, copy_gbps):
                        "sub_benchmark": "gop", "pictures_per_step": 8 * world, "dependency_levels": len(plan),
                        "parallelism": "frame-parallel, 1 process per GPU, RCCL send/recv of finished reference pictures",
                        "transfers_per_step": sends, "bytes_per_transfer": region},
-            "kernels_rank0_ms_per_step": {k: round(ms, 4) for k, (ms, n) in st["kernels"].items() if n},
             "staging_s": round(t_stage, 3),
         }
+        if st is not None:
+            out["kernels_rank0_ms_per_step"] = {k: round(ms, 4) for k, (ms, n) in st["kernels"].items() if n}
         if copy_gbps is not None:
             out["hbm_copy_GBps_measured"] = copy_gbps
         print(json.dumps(out), flush=True)
@@ -559,18 +628,20 @@ def decode_main(args, hdist, dist, rank, world, local_rank):
             raise SystemExit("decode: %d pictures disagree with their hash SEI in the timed passes" % bad_now)
         # the warm-up passes leave pictures in the decoder that the first timed pass puts out: count what actually came out
         return t, state["pixels"], state["pictures"]
-    elapsed_off, pixels_off, pictures_off = timed(False)
+    if args.full:
+        elapsed_off, pixels_off, pictures_off = timed(False)
     # check on: the MD5 chains run on the device (hmgpu_picture_hash_begin: no download for the check, no hash threads; libhmdec's default).
     # The chains of the last pictures finish after the last picture is out -- a GPU lane runs an MD5 chain ~8x slower than a host core --
     # that tail is reported separately.  Beside it: the check on the decoder's hash threads (round 2's form).
     elapsed, pixels_timed, pictures_timed = timed(True, device_md5=True)
     batches_timed, tail_dev = timed.batches, timed.tail_s
-    elapsed_host, _, pictures_host = timed(True, device_md5=False)
-    # host parsing alone (no device work): what bounds the decoder today
-    t0 = time.perf_counter()
-    with hmdec.Decoder(parse_only=True, threads=args.threads) as d:
-        d.decode_stream(data)
-    t_parse = time.perf_counter() - t0
+    if args.full:
+        elapsed_host, _, pictures_host = timed(True, device_md5=False)
+        # host parsing alone (no device work): what bounds the decoder today
+        t0 = time.perf_counter()
+        with hmdec.Decoder(parse_only=True, threads=args.threads) as d:
+            d.decode_stream(data)
+        t_parse = time.perf_counter() - t0
     if rank == 0:
         w, h = info["size"]
         out = {
@@ -583,17 +654,18 @@ def decode_main(args, hdist, dist, rank, world, local_rank):
                        "sub_benchmark": "decode", "parser_threads": args.threads, "pictures_per_step": npic, "parallelism": "replicas, 1 process per GPU"},
             "fps": round(world * pictures_timed / elapsed, 2),
             "hash_sei_check": "on in the timed passes (MD5 of every picture, chains on the device: one lane per plane, batches of up to 32 pictures)",
-            "fps_hash_check_off": round(world * pictures_off / elapsed_off, 2),
-            "fps_hash_check_on_host_threads": round(world * pictures_host / elapsed_host, 2),
             "device_md5_tail_s": round(tail_dev, 3),
             "device_batches_per_step": round(batches_timed / max(1, args.steps + max(1, args.warmup)), 2),
-            "host_parse_only_Mpixels_s": round(pixels / t_parse / 1e6, 1),
-            "host_parse_only_Mbit_s": round(len(data) * 8 / t_parse / 1e6, 1),
             "hash_sei_verified_pictures": npic,
             "roofline": None,        # host-bound (CABAC parsing); the device kernels are measured by the default workload
         }
+        if args.full:
+            out["fps_hash_check_off"] = round(world * pictures_off / elapsed_off, 2)
+            out["fps_hash_check_on_host_threads"] = round(world * pictures_host / elapsed_host, 2)
+            out["host_parse_only_Mpixels_s"] = round(pixels / t_parse / 1e6, 1)
+            out["host_parse_only_Mbit_s"] = round(len(data) * 8 / t_parse / 1e6, 1)
         ref_dec = os.path.join(here, "oracle", "_ref", "TAppDecoder")
-        if not args.no_cpu_baseline and os.path.exists(ref_dec):
+        if args.full and not args.no_cpu_baseline and os.path.exists(ref_dec):
             best = 1e9
             for _ in range(2):
                 t0 = time.perf_counter()

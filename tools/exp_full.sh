@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 cp libhm_amd/libhmgpu.so /tmp/libhmgpu_base.so
 for v in "$@"; do
   if [ $v = base ]; then cp /tmp/libhmgpu_base.so libhm_amd/libhmgpu.so; else cp libhm_amd/variants/$v/libhmgpu.so libhm_amd/libhmgpu.so; fi
-  python3 bench.py --steps 30 --no-cpu-baseline --no-host-inclusive > $out/$v.json 2> $out/$v.err
+  python3 bench.py --full --steps 30 --no-cpu-baseline --no-host-inclusive > $out/$v.json 2> $out/$v.err
   python3 - $out/$v.json $v <<'PY'
 import json,sys
 try:

@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 cp libhm_amd/libhmgpu.so /tmp/libhmgpu_base.so
 for v in "$@"; do
   if [ $v = base ]; then cp /tmp/libhmgpu_base.so libhm_amd/libhmgpu.so; else cp libhm_amd/variants/$v/libhmgpu.so libhm_amd/libhmgpu.so; fi
-  python3 bench.py --no-cpu-baseline > $out/${v}_full.json 2> $out/${v}_full.err
-  python3 bench.py --workload intra --batch 1 --steps 5 --warmup 1 --profile-steps 2 --no-cpu-baseline > $out/${v}_intra.json 2> $out/${v}_intra.err
+  python3 bench.py --full --no-cpu-baseline > $out/${v}_full.json 2> $out/${v}_full.err
+  python3 bench.py --full --workload intra --batch 1 --steps 5 --warmup 1 --profile-steps 2 --no-cpu-baseline > $out/${v}_intra.json 2> $out/${v}_intra.err
   python3 - $out/${v}_full.json $out/${v}_intra.json $v <<'PY'
 import json,sys
 try:

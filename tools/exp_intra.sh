@@ -8,7 +8,7 @@ cp libhm_amd/libhmgpu.so /tmp/libhmgpu_base.so
 for v in "$@"; do
   if [ $v = base ]; then cp /tmp/libhmgpu_base.so libhm_amd/libhmgpu.so; else cp libhm_amd/variants/$v/libhmgpu.so libhm_amd/libhmgpu.so; fi
   for b in 1 16; do
-    timeout -k 10 200 python3 bench.py --workload intra --batch $b --steps 5 --warmup 1 --profile-steps 2 --no-cpu-baseline > $out/${v}_$b.json 2> $out/${v}_$b.err
+    timeout -k 10 200 python3 bench.py --full --workload intra --batch $b --steps 5 --warmup 1 --profile-steps 2 --no-cpu-baseline > $out/${v}_$b.json 2> $out/${v}_$b.err
     python3 - $out/${v}_$b.json ${v}_$b <<'PY'
 import json,sys
 try:

@@ -8,6 +8,6 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 cp libhm_amd/libhmgpu.so /tmp/libhmgpu_base.so
 cp libhm_amd/variants/tm/libhmgpu.so libhm_amd/libhmgpu.so
-timeout -k 10 200 python3 bench.py $args --steps 1 --warmup 1 --profile-steps 0 --no-cpu-baseline --no-host-inclusive > $out/tm.out 2> $out/tm.err
+timeout -k 10 200 python3 bench.py --full $args --steps 1 --warmup 1 --profile-steps 0 --no-cpu-baseline --no-host-inclusive > $out/tm.out 2> $out/tm.err
 cp /tmp/libhmgpu_base.so libhm_amd/libhmgpu.so
 grep -c "^TM" $out/tm.out

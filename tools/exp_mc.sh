@@ -4,7 +4,7 @@ tag=$1
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-run() { name=$1; shift; python3 bench.py --workload mc "$@" --steps 10 --no-cpu-baseline > $out/$name.json 2> $out/$name.err; python3 - $out/$name.json $name <<'PY'
+run() { name=$1; shift; python3 bench.py --full --workload mc "$@" --steps 10 --no-cpu-baseline > $out/$name.json 2> $out/$name.err; python3 - $out/$name.json $name <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))
 k=d["kernels"]

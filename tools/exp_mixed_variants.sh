@@ -8,7 +8,7 @@ cp libhm_amd/libhmgpu.so /tmp/libhmgpu_base.so
 for v in "$@"; do
   if [ $v = base ]; then cp /tmp/libhmgpu_base.so libhm_amd/libhmgpu.so; else cp libhm_amd/variants/$v/libhmgpu.so libhm_amd/libhmgpu.so; fi
   for f in 0.05 0.1 0.25; do
-    timeout -k 10 200 python3 bench.py --intra-frac $f --steps 10 --no-cpu-baseline --no-host-inclusive > $out/${v}_$f.json 2> $out/${v}_$f.err
+    timeout -k 10 200 python3 bench.py --full --intra-frac $f --steps 10 --no-cpu-baseline --no-host-inclusive > $out/${v}_$f.json 2> $out/${v}_$f.err
     python3 -c "
 import json; d=json.load(open('$out/${v}_$f.json')); print('$v intra-frac $f', d['value'], 'Mpx/s', 'intra=%.3f ms' % d['kernels']['intra']['avg_ms'], flush=True)"
   done

@@ -44,7 +44,7 @@ if json_out:
         if k in BENCH_NAME and "FETCH_SIZE" in v and "WRITE_SIZE" in v:
             out[BENCH_NAME[k]] = {"FETCH_SIZE_KiB": v["FETCH_SIZE"], "WRITE_SIZE_KiB": v["WRITE_SIZE"],
                                   "traffic_bytes": int((2 * v["FETCH_SIZE"] + v["WRITE_SIZE"]) * 1024)}
-    json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `python3 bench.py --steps 2 --warmup 1 "
+    json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `python3 bench.py --full --steps 2 --warmup 1 "
                          "--profile-steps 1 --no-cpu-baseline`; per launch = largest dispatch (batch of 16 pictures); "
                          "traffic = (2*FETCH_SIZE + WRITE_SIZE) KiB, the gfx950 correction of MI355X_MICROARCH.md",
                "csrc_sha16": csrc_digest(), "kernels": out}, open(json_out, "w"), indent=1)
