@@ -77,10 +77,14 @@ unsigned long long hmdec_transfer_bytes(libHMDec_context* ctx);
  * CTB row behind the picture it takes temporal motion vectors from); pictures come out in the same order, later.  Before the first NAL unit. */
 void hmdec_set_threads(libHMDec_context* ctx, int n);
 void hmdec_set_parse_only(libHMDec_context* ctx, int on);                     /* no device work: parser output only (planes unavailable) */
+/* before the first NAL unit: 4:0:0 / 4:2:0 pictures are packed (hmgpu_pack_input, into page-locked memory) and handed over through
+ * hmgpu_decompress_pictures_packed; other pictures, and a picture the packer refuses, take the array path.  Off by default. */
+void hmdec_set_packed_input(libHMDec_context* ctx, int on);
 int hmdec_hash_mismatches(libHMDec_context* ctx);                             /* pictures whose reconstruction disagreed with the hash SEI */
 int hmdec_pictures_decoded(libHMDec_context* ctx);
 void hmdec_set_device_md5(libHMDec_context* ctx, int on);                     /* MD5 hash SEIs checked on the device (hmgpu_picture_hash_begin) (the default;
                                                                                   HMDEC_DEVICE_MD5=0 or 0 here: on the decoder's hash threads) */
+int hmdec_packed_pictures(libHMDec_context* ctx);                             /* pictures handed to the device as packed inputs so far */
 int hmdec_device_batches(libHMDec_context* ctx);                              /* calls of hmgpu_decompress_pictures so far (pictures retired together share one) */
 const char* hmdec_last_error(libHMDec_context* ctx);
 libHMDec_picture* hmdec_last_decoded_picture(libHMDec_context* ctx);          /* the picture finished most recently, decoding order */

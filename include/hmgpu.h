@@ -323,6 +323,72 @@ hmgpu_status hmgpu_staging_share(hmgpu_ctx* owner, hmgpu_staging* staging, hmgpu
 hmgpu_status hmgpu_pack_levels(const hmgpu_seq_params* seq, const hmgpu_ctu_meta* meta, const hmgpu_coeffs* dense,
                                int16_t* const out_level[3], uint32_t* const out_start[3]);
 
+/* ------------------------------------------------------------------------------------------------ packed input
+ * A picture's inputs in few bytes: per-partition arrays hold values that are constant over a CU, PU or TU (every CU and TU covers a
+ * contiguous range of HM's z-scan), and most levels are zero.  The packed form stores the metadata as runs and the levels sparsely, in
+ * ONE contiguous, self-describing blob; hmgpu_decompress_pictures_packed copies the blob in one DMA and expands it on the device into
+ * exactly the arrays and compact levels the other entry points stage -- everything downstream is the same.  A P picture of 2160p moves
+ * about 5.6 MB instead of 19 MB (DESIGN.md "Packed input").
+ *
+ * Envelope: whole pictures, chroma_format 0 (4:0:0) or 1 (4:2:0); other formats give HMGPU_EUNSUPPORTED.  PCM samples stay in the
+ * caller's arrays (hmgpu_packed_job.pcm_sample), as with staging blocks.  Cross-component prediction weights are not carried (4:4:4).
+ *
+ * Layout (little endian, every section 16-byte aligned, the blob itself at least 4-byte aligned):
+ *   header: uint32 magic 0x4B504D48 ("HMPK"), version 1, num_ctus, parts_per_ctu, groups (bit g: run group g is present; 0-2 always),
+ *           bytes (of the whole blob), 2 reserved; then {offset, size} in bytes of 19 sections; padded to 192 bytes
+ *   section 0: [num_ctus] uint32  slice_idx | tile_idx << 16
+ *   sections 1 + 3g, 2 + 3g, 3 + 3g, for the run groups g = 0 CU (depth, part_size, pred_mode, qp, transquant_bypass, ipcm, 0, 0),
+ *           1 TU (tr_idx, cbf[0..2], transform_skip[0..2], 0), 2 list 0 (mv[0] hor, ver as int16, ref_idx[0], 0, 0, 0), 3 list 1 (the same),
+ *           4 intra (intra_dir[0], intra_dir[1], 0 x 6): [num_ctus + 1] uint32 run starts (CTU a has runs start[a] .. start[a+1] - 1, at
+ *           least one), [runs] uint16 run ends (the z-index one past the run's last partition: strictly ascending inside a CTU, the last
+ *           one = parts_per_ctu), [runs] 8-byte tuples as listed.  A group left out has three empty sections: list 1 then reads as
+ *           mv 0 / ref_idx -1 everywhere (a picture without B slices), the intra modes as absent (intra CUs are left untouched, as when
+ *           meta->intra_dir is NULL).
+ *   section 16: [3][num_ctus + 1] uint32  the compact form's CTU starts (hmgpu_coeffs.ctu_level_start), per component
+ *   section 17: [num_ctus][3] {uint32 offset in 4-byte units into section 18, uint32 mode}: mode 0x80000000 = the CTU's piece of the
+ *           component is stored raw (its int16 levels, padded to 4 bytes), else mode = the number of pairs: that many uint16 positions in
+ *           the piece (strictly ascending, padded to 4 bytes) followed by as many int16 values (padded); all other levels are zero
+ *   section 18: the pieces
+ * hmgpu_pack_input writes the smaller of the two forms of every piece and zeroes all padding: the blob depends on the input alone, and
+ * dense and compact levels give the same bytes. */
+typedef struct hmgpu_packed_job {
+  hmgpu_pic pic;
+  int32_t num_slices;
+  const hmgpu_slice_params* const* slices;
+  const void* blob;                 /* page-locked (hmgpu_host_alloc) for a true asynchronous copy */
+  size_t bytes;
+  const int16_t* pcm_sample[3];     /* as hmgpu_coeffs.pcm_sample: needed only if the picture has PCM CUs */
+} hmgpu_packed_job;
+
+/* where hmgpu_unpack_input writes HM's arrays: the fields of hmgpu_ctu_meta (same order, same layout), writable; NULL = not wanted */
+typedef struct hmgpu_ctu_meta_out {
+  uint8_t* depth; int8_t* part_size; int8_t* pred_mode; int8_t* qp; uint8_t* tr_idx;
+  uint8_t* cbf[3]; uint8_t* transform_skip[3];
+  int16_t* mv[2]; int8_t* ref_idx[2];
+  uint8_t* intra_dir[2];
+  uint8_t* transquant_bypass; uint8_t* ipcm;
+  uint16_t* slice_idx; uint16_t* tile_idx;
+  int8_t* ccp_alpha[2];             /* (not carried by the packed form: left untouched) */
+} hmgpu_ctu_meta_out;
+
+/* worst-case blob size for the geometry of `seq` (a different tuple in every partition, every level non-zero); 0 for bad parameters */
+size_t       hmgpu_packed_max_bytes(const hmgpu_seq_params* seq);
+/* HM's arrays (levels dense, or compact with ctu_level_start) -> the blob at `out` (capacity bytes, 4-byte aligned); *bytes = its size */
+hmgpu_status hmgpu_pack_input(const hmgpu_seq_params* seq, const hmgpu_ctu_meta* meta, const hmgpu_coeffs* coeffs, void* out, size_t capacity,
+                              size_t* bytes);
+/* host reference expansion and validator: checks the whole blob (HMGPU_EINVAL if anything is out of place) and writes every non-NULL
+ * array of *meta ([num_ctus][parts] as in hmgpu_ctu_meta; meta may be NULL) and the compact levels / CTU starts (out_level / out_start
+ * may be NULL, or hold NULL entries; out_level[c] needs out_start[c][num_ctus] elements) */
+hmgpu_status hmgpu_unpack_input(const hmgpu_seq_params* seq, const void* blob, size_t bytes, const hmgpu_ctu_meta_out* meta,
+                                int16_t* const out_level[3], uint32_t* const out_start[3]);
+/* hmgpu_decompress_pictures with packed inputs (n <= 16): every blob is validated in full before anything is enqueued -- the checks of
+ * hmgpu_unpack_input, the blobs of a call on threads of their own; a malformed one gives HMGPU_EINVAL -- then copied in one DMA on the
+ * copy stream and expanded by one kernel launch for the whole call.  The blob must stay untouched until hmgpu_packed_wait(ctx, blob) or
+ * hmgpu_sync() has returned. */
+hmgpu_status hmgpu_decompress_pictures_packed(hmgpu_ctx* ctx, int32_t n, const hmgpu_packed_job* jobs);
+/* blocks until the copy of the last hmgpu_decompress_pictures_packed call that read `blob` has been made (at once for a blob no call has read) */
+hmgpu_status hmgpu_packed_wait(hmgpu_ctx* ctx, const void* blob);
+
 /* ------------------------------------------------------------------------------------------------ call 2
  * Replaces TDecGop::filterPicture (TDecGop.cpp:157-217): TComLoopFilter::loopFilterPic (all vertical edges, then
  * all horizontal edges), then reconstructBlkSAOParams + SAOProcess.  Uses the metadata of every CTU handed to

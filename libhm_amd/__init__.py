@@ -91,6 +91,18 @@ def lib():
         L.hmgpu_staging_free.argtypes = [C.c_void_p, C.c_void_p]
         L.hmgpu_staging_free.restype = None
         L.hmgpu_pack_levels.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.CtuMeta), C.POINTER(abi.Coeffs), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.hmgpu_packed_max_bytes.argtypes = [C.POINTER(abi.SeqParams)]
+        L.hmgpu_packed_max_bytes.restype = C.c_size_t
+        L.hmgpu_pack_input.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.CtuMeta), C.POINTER(abi.Coeffs), C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]
+        L.hmgpu_unpack_input.argtypes = [C.POINTER(abi.SeqParams), C.c_void_p, C.c_size_t, C.POINTER(abi.CtuMetaOut), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p)]
+        L.hmgpu_decompress_pictures_packed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.PackedJob)]
+        L.hmgpu_packed_wait.argtypes = [C.c_void_p, C.c_void_p]
+        L.hmgpu_host_alloc.argtypes = [C.c_size_t]
+        L.hmgpu_host_alloc.restype = C.c_void_p
+        L.hmgpu_host_free.argtypes = [C.c_void_p]
+        L.hmgpu_host_free.restype = None
         L.hmgpu_replay.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         L.hmgpu_replay_batch.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]
         L.hmgpu_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -120,6 +132,73 @@ def pack_levels(seq, meta, coeffs):
     for k in range(3):
         out.struct.ctu_level_start[k] = out.starts[k].ctypes.data
     return out
+
+
+def packed_max_bytes(seq):
+    """worst-case size of a packed picture input (hmgpu_packed_max_bytes)"""
+    return int(lib().hmgpu_packed_max_bytes(C.byref(seq)))
+
+
+def pack_input(seq, meta, coeffs, out=None):
+    """HM's arrays (MetaHolder; CoeffHolder with dense levels, or with compact ones as pack_levels returns) -> the packed input
+    (hmgpu_pack_input: host code).  out: a uint8 array of at least packed_max_bytes(seq) (e.g. page-locked memory) to pack into;
+    returns the blob as a uint8 array (a view of `out` when given).  Raises HmgpuError on a bad status."""
+    cap = packed_max_bytes(seq)
+    if out is None:
+        out = np.zeros(cap + 16, dtype=np.uint8)
+        out = out[(-out.ctypes.data) % 16:][:cap]           # (16-byte aligned)
+    n = C.c_size_t(0)
+    st = lib().hmgpu_pack_input(C.byref(seq), C.byref(meta.struct), C.byref(coeffs.struct), out.ctypes.data, out.nbytes, C.byref(n))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_pack_input")
+    return out[:n.value]
+
+
+def unpack_input_status(seq, blob, meta_arrays=None, levels=None, starts=None):
+    """hmgpu_unpack_input on a uint8 array; returns the status (no exception): the validator"""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    if blob.ctypes.data % 4:                                 # (the contract asks for a 4-byte aligned blob)
+        b = np.zeros(blob.nbytes + 4, dtype=np.uint8)
+        b = b[(-b.ctypes.data) % 4:][:blob.nbytes]
+        b[:] = blob
+        blob = b
+    m = abi.MetaHolder(meta_arrays or {})
+    out = abi.CtuMetaOut.from_buffer_copy(m.struct)
+    lv = (C.c_void_p * 3)(*[None if levels is None else levels[k].ctypes.data for k in range(3)])
+    stt = (C.c_void_p * 3)(*[None if starts is None else starts[k].ctypes.data for k in range(3)])
+    return int(lib().hmgpu_unpack_input(C.byref(seq), blob.ctypes.data, blob.nbytes, C.byref(out), lv, stt))
+
+
+def unpack_input(seq, blob):
+    """the host reference expansion (hmgpu_unpack_input): returns (meta arrays by abi.META_ARRAYS name, compact levels [3], CTU starts [3])"""
+    n, parts, ctu = abi.num_ctus(seq), abi.parts_per_ctu(seq), 1 << seq.log2_ctu_size
+    arrays = {}
+    for name, dt in abi.META_ARRAYS:
+        if name in ("ccp_u", "ccp_v"):
+            continue
+        shape = (n,) if name in ("slice_idx", "tile_idx") else ((n, parts * 2) if name in ("mv0", "mv1") else (n, parts))
+        arrays[name] = np.zeros(shape, dtype=dt)
+    levels = [np.zeros(n * ctu * ctu >> (2 if k else 0), dtype=np.int16) for k in range(3)]
+    starts = [np.zeros(n + 1, dtype=np.uint32) for _ in range(3)]
+    st = unpack_input_status(seq, blob, arrays, levels, starts)
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_unpack_input")
+    return arrays, [levels[k][:int(starts[k][n])] for k in range(3)], starts
+
+
+class PinnedBuffer:
+    """page-locked host memory (hmgpu_host_alloc) as a uint8 array; .free() gives it back"""
+
+    def __init__(self, nbytes):
+        self.ptr = lib().hmgpu_host_alloc(nbytes)
+        if not self.ptr:
+            raise HmgpuError(abi.HMGPU_ENOMEM, "hmgpu_host_alloc")
+        self.array = np.ctypeslib.as_array(C.cast(self.ptr, C.POINTER(C.c_uint8)), shape=(nbytes,))
+
+    def free(self):
+        if self.ptr:
+            lib().hmgpu_host_free(self.ptr)
+            self.ptr, self.array = None, None
 
 
 class Context:
@@ -272,6 +351,31 @@ class Context:
     def decompress_pictures(self, jobs):
         arr = jobs if isinstance(jobs, C.Array) else self.picture_jobs(jobs)
         self._chk(lib().hmgpu_decompress_pictures(self._h, len(arr), arr), "hmgpu_decompress_pictures")
+
+    @staticmethod
+    def packed_jobs(jobs):
+        """jobs: [(pic, [slice_params, ...], blob (uint8 array from pack_input), pcm (three int16 arrays) or None), ...] -> the C array"""
+        arr = (abi.PackedJob * len(jobs))()
+        arr._keep = [jobs]
+        for i, job in enumerate(jobs):
+            pic, slices, blob = job[:3]
+            pcm = job[3] if len(job) > 3 else None
+            sl = (C.POINTER(abi.SliceParams) * len(slices))(*[C.pointer(s) for s in slices])
+            arr._keep.append(sl)
+            arr[i].pic, arr[i].num_slices, arr[i].slices = pic, len(slices), sl
+            arr[i].blob, arr[i].bytes = blob.ctypes.data, blob.nbytes
+            if pcm is not None:
+                for k in range(3):
+                    arr[i].pcm_sample[k] = pcm[k].ctypes.data
+        return arr
+
+    def decompress_pictures_packed(self, jobs):
+        """hmgpu_decompress_pictures with packed inputs (see packed_jobs)"""
+        arr = jobs if isinstance(jobs, C.Array) else self.packed_jobs(jobs)
+        self._chk(lib().hmgpu_decompress_pictures_packed(self._h, len(arr), arr), "hmgpu_decompress_pictures_packed")
+
+    def packed_wait(self, blob):
+        self._chk(lib().hmgpu_packed_wait(self._h, blob.ctypes.data), "hmgpu_packed_wait")
 
     def filter_pictures(self, jobs):
         arr = jobs if isinstance(jobs, C.Array) else self.filter_jobs(jobs)

@@ -49,6 +49,10 @@ class CtuMeta(C.Structure):
                 ("ccp_alpha", C.c_void_p * 2)]
 
 
+class CtuMetaOut(CtuMeta):
+    """hmgpu_ctu_meta_out: hmgpu_ctu_meta's fields, writable (hmgpu_unpack_input); same layout"""
+
+
 class Coeffs(C.Structure):
     _fields_ = [("level", C.c_void_p * 3), ("pcm_sample", C.c_void_p * 3), ("ctu_level_start", C.c_void_p * 3)]
 
@@ -65,6 +69,11 @@ class PicParams(C.Structure):
 class PictureJob(C.Structure):
     _fields_ = [("pic", C.c_int32), ("num_slices", C.c_int32), ("slices", C.POINTER(C.POINTER(SliceParams))),
                 ("meta", C.POINTER(CtuMeta)), ("coeffs", C.POINTER(Coeffs))]
+
+
+class PackedJob(C.Structure):
+    _fields_ = [("pic", C.c_int32), ("num_slices", C.c_int32), ("slices", C.POINTER(C.POINTER(SliceParams))),
+                ("blob", C.c_void_p), ("bytes", C.c_size_t), ("pcm_sample", C.c_void_p * 3)]
 
 
 class FilterJob(C.Structure):

@@ -5,6 +5,7 @@
 // once every traversal runs on the device: copy arrays, launch kernels, keep per-picture state.  The only serial
 // host computation is reconstructBlkSAOParams' merge resolution (a dependent chain over CTUs, 3 x num_ctus items).
 #include "hmgpu_dev.h"
+#include "packed_format.h"
 
 #include <algorithm>
 #include <chrono>
@@ -13,15 +14,17 @@
 #include <cstring>
 #include <cstdlib>
 #include <new>
+#include <thread>
+#include <unordered_map>
 #include <vector>
 
 using namespace hmgpu;
 
 namespace {
 
-enum { K_PREP = 0, K_MC_LUMA, K_MC_CHROMA, K_ITX, K_DBK_VER, K_DBK_HOR, K_SAO, K_EXTEND, K_H2D, K_INTRA, K_FILTER, K_RES11 };
+enum { K_PREP = 0, K_MC_LUMA, K_MC_CHROMA, K_ITX, K_DBK_VER, K_DBK_HOR, K_SAO, K_EXTEND, K_H2D, K_INTRA, K_FILTER, K_UNPACK };
 const char* const kKernelNames[HMGPU_NUM_KERNELS] = {"prep", "mc_luma", "mc_chroma", "itx", "deblock_ver", "deblock_hor", "sao",
-                                                     "extend_border", "h2d_stage", "intra", "filter_fused", ""};
+                                                     "extend_border", "h2d_stage", "intra", "filter_fused", "unpack"};
 
 struct SliceCall { int first_ctu, num_ctus, slice_idx; bool intra, wp, cells, bi, islice; };   // intra: the range holds intra CUs the device reconstructs; islice: mostly intra CUs;
                                                                                     // cells: it holds PUs that cut an 8x8 luma tile (k_mc_cells.hip); bi: B slices
@@ -39,6 +42,7 @@ struct Picture {
   void* coef = nullptr;
   void* pcm = nullptr;                  // PCM sample buffers, allocated when the first PCM CU shows up
   void* ccp = nullptr;                  // cross-component prediction weights (4:4:4), allocated with the first picture that carries them
+  void* blob = nullptr;                 // device copy of a packed input (hmgpu_decompress_pictures_packed), allocated when first used
   void* derived = nullptr;              // blk, tu lists, counters, sao params, slices
   uint8_t* sl_table = nullptr;          // device: expanded scaling-list matrices (inside `derived`)
   uint32_t* coef_start = nullptr;       // device: [3][num_ctus + 1] CTU starts of compact levels (inside `derived`)
@@ -86,6 +90,8 @@ struct hmgpu_ctx {
   uint64_t copy_seq = 0, use_seq = 0;
   std::vector<hmgpu_staging*> stagings;
   std::vector<hmgpu_staging*> shared_stagings;   // blocks of other contexts (hmgpu_staging_share): recognised, not owned
+  // packed blobs and the staging pass that last copied them (hmgpu_packed_wait); entries whose copy is known to be done are dropped
+  std::unordered_map<const void*, uint64_t> packed_reads;
   // Small host structures (descriptors, slice table entries, resolved SAO parameters) travel through a ring of page-locked memory: an
   // asynchronous copy from pageable memory makes the runtime stage the bytes itself, 20-100 us of the calling thread per copy (the resolved
   // SAO parameters of a picture: 0.18 ms; sixteen pictures per call spent 7 of their 7.7 ms on the host that way, round 4).  Eight segments; a
@@ -365,6 +371,8 @@ void free_picture(Picture& p) {
   if (p.pcm) hipFree(p.pcm);                       // (the planes belong to the context's slab)
   if (p.ccp) hipFree(p.ccp);
   p.ccp = nullptr;
+  if (p.blob) hipFree(p.blob);
+  p.blob = nullptr;
   if (p.meta) hipFree(p.meta);
   if (p.coef) hipFree(p.coef);
   if (p.derived) hipFree(p.derived);
@@ -1191,6 +1199,47 @@ static const hmgpu_staging* staging_of(const hmgpu_ctx* c, const hmgpu_ctu_meta*
   return nullptr;
 }
 
+// what every way of staging a CTU range ends with: PCM samples, the picture's descriptor, and the record of the call (which kernels run)
+static hmgpu_status finish_stage(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx, const std::vector<int>& slices, bool any_wp,
+                                 const int16_t* const pcm_sample[3], bool any_pcm, bool any_bypass, int32_t first_ctu, int32_t num_ctus,
+                                 size_t n_intra, bool cells, hipStream_t hs, SliceCall* call_out) {
+  Picture& p = c->pics[cur];
+  const size_t pn = (size_t)num_ctus * c->parts;
+  {
+    if (any_pcm) {
+      size_t bytes = 0;
+      for (int k = 0; k < 3; k++) bytes += align_up(c->coef_elems[k] * sizeof(int16_t), 256);
+      if (!p.pcm) {
+        HIP_TRY(c, hipMalloc(&p.pcm, bytes));
+        Carver cp(p.pcm);
+        for (int k = 0; k < 3; k++) p.dev.pcm[k] = cp.take<int16_t>(c->coef_elems[k]);
+      }
+      for (int k = 0; k < 3; k++) {
+        const size_t per = (size_t)(c->ctu * c->ctu) >> (k ? c->csx + c->csy : 0);
+        HIP_TRY(c, hipMemcpyAsync((void*)(p.dev.pcm[k] + first_ctu * per), pcm_sample[k] + first_ctu * per, (size_t)num_ctus * per * 2,
+                                  hipMemcpyHostToDevice, hs));
+      }
+      p.dev.pcm_shift[0] = c->seq.bit_depth_luma - c->seq.pcm_bit_depth_luma;
+      p.dev.pcm_shift[1] = p.dev.pcm_shift[2] = c->seq.bit_depth_chroma - c->seq.pcm_bit_depth_chroma;
+    }
+    if (any_bypass || (any_pcm && c->seq.pcm_loop_filter_disable)) p.dev.any_nofilt = 1;
+    HIP_TRY(c, h2d_small(c, c->d_pics + cur, &p.dev, sizeof(PicDev), hs));
+  }
+  // a range decoded again (picture buffer reused without release/acquire) replaces the earlier record
+  p.calls.erase(std::remove_if(p.calls.begin(), p.calls.end(), [&](const SliceCall& o) {
+                  return o.first_ctu < first_ctu + num_ctus && first_ctu < o.first_ctu + o.num_ctus; }), p.calls.end());
+  const bool has_intra = p.dev.has_intra_dir && n_intra != 0;
+  bool any_b = false, any_i = false;
+  for (int si : slices) { any_b |= p.slices[si].slice_type == HMGPU_B_SLICE; any_i |= p.slices[si].slice_type == HMGPU_I_SLICE; }
+  // I slices, or a range at least half intra, take the intra kernel that stages whole CTUs
+  if (has_intra && !any_i) any_i = 2 * n_intra >= pn;
+  SliceCall call = {first_ctu, num_ctus, slice_idx, has_intra, any_wp, cells, any_b, any_i};
+  p.calls.push_back(call);
+  p.extended = false;
+  *call_out = call;
+  return HMGPU_OK;
+}
+
 // HM arrays of a CTU range to the device (on stream hs) and the record of the call.  `slices` lists the slice table entries whose
 // reference pictures the range may read; slice_idx is the one a missing meta->slice_idx array stands for.
 static hmgpu_status stage_inputs(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx, const std::vector<int>& slices, bool any_wp,
@@ -1292,29 +1341,6 @@ static hmgpu_status stage_inputs(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx,
       p.dev.ccp[k] = (const int8_t*)p.ccp + k * np;
     }
   }
-  {
-    if (any_pcm) {
-      size_t bytes = 0;
-      for (int k = 0; k < 3; k++) bytes += align_up(c->coef_elems[k] * sizeof(int16_t), 256);
-      if (!p.pcm) {
-        HIP_TRY(c, hipMalloc(&p.pcm, bytes));
-        Carver cp(p.pcm);
-        for (int k = 0; k < 3; k++) p.dev.pcm[k] = cp.take<int16_t>(c->coef_elems[k]);
-      }
-      for (int k = 0; k < 3; k++) {
-        const size_t per = (size_t)(c->ctu * c->ctu) >> (k ? c->csx + c->csy : 0);
-        HIP_TRY(c, hipMemcpyAsync((void*)(p.dev.pcm[k] + first_ctu * per), co->pcm_sample[k] + first_ctu * per, (size_t)num_ctus * per * 2,
-                                  hipMemcpyHostToDevice, hs));
-      }
-      p.dev.pcm_shift[0] = c->seq.bit_depth_luma - c->seq.pcm_bit_depth_luma;
-      p.dev.pcm_shift[1] = p.dev.pcm_shift[2] = c->seq.bit_depth_chroma - c->seq.pcm_bit_depth_chroma;
-    }
-    if (any_bypass || (any_pcm && c->seq.pcm_loop_filter_disable)) p.dev.any_nofilt = 1;
-    HIP_TRY(c, h2d_small(c, c->d_pics + cur, &p.dev, sizeof(PicDev), hs));
-  }
-  // a range decoded again (picture buffer reused without release/acquire) replaces the earlier record
-  p.calls.erase(std::remove_if(p.calls.begin(), p.calls.end(), [&](const SliceCall& o) {
-                  return o.first_ctu < first_ctu + num_ctus && first_ctu < o.first_ctu + o.num_ctus; }), p.calls.end());
   // The caller's arrays are at hand: ONE pass over three of them (branch-free, so that the compiler vectorises it: ~1.5 MB per 2160p picture)
   // says whether the range holds intra CUs at all and how many (which intra kernel, if any: launch_intra) and whether it holds PUs that cut
   // an 8x8 luma tile -- 2NxN / Nx2N (/ NxN) parts of 8x8 CUs, the 4- and 12-sample parts of AMP in 16x16 CUs -- (the cells kernels).
@@ -1342,17 +1368,8 @@ static hmgpu_status stage_inputs(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx,
       n_intra += cnt; cells_u |= cel;
     }
   }
-  const bool has_intra = p.dev.has_intra_dir && n_intra != 0;
-  const bool cells = cells_u != 0;
-  bool any_b = false, any_i = false;
-  for (int si : slices) { any_b |= p.slices[si].slice_type == HMGPU_B_SLICE; any_i |= p.slices[si].slice_type == HMGPU_I_SLICE; }
-  // I slices, or a range at least half intra, take the intra kernel that stages whole CTUs
-  if (has_intra && !any_i) any_i = 2 * n_intra >= pn;
-  SliceCall call = {first_ctu, num_ctus, slice_idx, has_intra, any_wp, cells, any_b, any_i};
-  p.calls.push_back(call);
-  p.extended = false;
-  *call_out = call;
-  return HMGPU_OK;
+  return finish_stage(c, cur, slice_idx, slices, any_wp, co->pcm_sample, any_pcm, any_bypass, first_ctu, num_ctus, n_intra, cells_u != 0, hs,
+                      call_out);
 }
 
 // reference pictures named by the slice table entries `slices` of picture `cur`: their borders must be extended before the kernels read them
@@ -1606,6 +1623,127 @@ hmgpu_status hmgpu_decompress_pictures(hmgpu_ctx* c, int32_t n, const hmgpu_pict
   if (st == HMGPU_OK) st = run_recon(c, b, any_intra, any_wp, any_cells, any_bi, any_islice);
   mark_use(c, b);
   return st;
+}
+
+// ---- packed input (include/hmgpu.h "packed input"): validated here, copied in one DMA, expanded by k_unpack.hip
+static hmgpu_status stage_packed(hmgpu_ctx* c, const hmgpu_packed_job& j, const packed::Summary& sm, const std::vector<int>& slices,
+                                 bool any_wp, hipStream_t hs, SliceCall* call_out) {
+  Picture& p = c->pics[j.pic];
+  if (!p.blob) HIP_TRY(c, hipMalloc(&p.blob, hmgpu_packed_max_bytes(&c->seq)));
+  HIP_TRY(c, hipMemcpyAsync(p.blob, j.blob, j.bytes, hipMemcpyHostToDevice, hs));
+  // what stage_inputs derives from the arrays, from the runs (packed::validate): the same values, so that the same kernels are chosen
+  p.dev.has_intra_dir = (sm.groups >> packed::G_INTRA) & 1;
+  for (int k = 0; k < 3; k++) p.dev.coef_start[k] = p.coef_start + (size_t)k * (c->num_ctus + 1);
+  p.flags_staged = sm.flags_used;           // (the expansion writes the transform-skip / lossless / PCM flags of every partition)
+  p.h_slice_idx.resize(c->num_ctus);
+  p.h_tile_idx.resize(c->num_ctus);
+  for (int a = 0; a < c->num_ctus; a++) { p.h_slice_idx[a] = (uint16_t)(sm.ctu[a] & 0xffff); p.h_tile_idx[a] = (uint16_t)(sm.ctu[a] >> 16); }
+  p.dev.ccp[0] = p.dev.ccp[1] = nullptr;
+  return finish_stage(c, j.pic, 0, slices, any_wp, j.pcm_sample, sm.any_pcm, sm.any_bypass, 0, c->num_ctus, sm.n_intra, sm.cells, hs, call_out);
+}
+
+hmgpu_status hmgpu_decompress_pictures_packed(hmgpu_ctx* c, int32_t n, const hmgpu_packed_job* jobs) {
+  if (!c || !jobs || n < 1 || n > kMaxBatch) return HMGPU_EINVAL;
+  if (c->seq.chroma_format > 1) return HMGPU_EUNSUPPORTED;
+  c->host_calls++;
+  std::vector<packed::Summary> sums(n);
+  { HostTimer tv(c, 0);
+  // every blob is checked before anything is enqueued: the device expansion trusts what passed
+  for (int i = 0; i < n; i++) {
+    const hmgpu_packed_job& j = jobs[i];
+    if (!valid_pic(c, j.pic) || !j.slices || j.num_slices < 1 || j.num_slices > HMGPU_MAX_SLICES || !j.blob) return HMGPU_EINVAL;
+    for (int k = 0; k < i; k++) if (jobs[k].pic == j.pic) return HMGPU_EINVAL;
+    for (int s2 = 0; s2 < j.num_slices; s2++)
+      for (int l = 0; l < 2 && j.slices[s2]; l++)
+        for (int r = 0; r < j.slices[s2]->num_ref_idx[l] && r < HMGPU_MAX_REF; r++)
+          for (int k = 0; k < n; k++) if (j.slices[s2]->ref_pic[l][r] == jobs[k].pic) return HMGPU_EINVAL;
+  }
+  // every blob in full (the walk over the level positions included: ~1.1 M of them per 2160p picture, a few tenths of a millisecond),
+  // the blobs of a call side by side on threads of their own
+  {
+    std::vector<hmgpu_status> vs(n, HMGPU_OK);
+    std::vector<std::thread> th;
+    for (int i = 1; i < n; i++) {
+      auto check = [&, i] { vs[i] = packed::validate(&c->seq, jobs[i].blob, jobs[i].bytes, &sums[i], true); };
+      try { th.emplace_back(check); } catch (...) { check(); }      // (no thread to be had: on this one)
+    }
+    vs[0] = packed::validate(&c->seq, jobs[0].blob, jobs[0].bytes, &sums[0], true);
+    for (std::thread& t : th) t.join();
+    for (int i = 0; i < n; i++) if (vs[i] != HMGPU_OK) return vs[i];
+  }
+  for (int i = 0; i < n; i++) {
+    const hmgpu_packed_job& j = jobs[i];
+    const packed::Summary& sm = sums[i];
+    if (sm.max_slice >= (uint32_t)j.num_slices) return HMGPU_EINVAL;
+    if (sm.any_pcm && (!j.pcm_sample[0] || !j.pcm_sample[1] || !j.pcm_sample[2] || !((sm.groups >> packed::G_INTRA) & 1))) return HMGPU_EINVAL;
+    if (sm.any_pcm && (c->seq.pcm_bit_depth_luma < 1 || c->seq.pcm_bit_depth_luma > c->seq.bit_depth_luma ||
+                       c->seq.pcm_bit_depth_chroma < 1 || c->seq.pcm_bit_depth_chroma > c->seq.bit_depth_chroma)) return HMGPU_EINVAL;
+  }
+  }
+  hipSetDevice(c->device);
+  Batch b; memset(&b, 0, sizeof(b));
+  b.n = n;
+  UnpackArgs ua; memset(&ua, 0, sizeof(ua));
+  ua.n = n;
+  bool any_intra = false, any_wp = false, any_cells = false, any_bi = false, any_islice = false;
+  hmgpu_status st = HMGPU_OK;
+  std::vector<std::vector<int>> all(n);
+  {
+    ProfScope ps(c, K_H2D);
+    for (int i = 0; i < n && st == HMGPU_OK; i++) {
+      const hmgpu_packed_job& j = jobs[i];
+      Picture& p = c->pics[j.pic];
+      const hipStream_t hs = (i & 1) ? c->copy_stream2 : c->copy_stream;
+      wait_for_last_use(c, p, hs);
+      if (p.sao_applied) { p.sao_applied = false; p.dev.sao_applied = 0; for (int k = 0; k < 3; k++) c->h_finals[j.pic].p[k] = p.dev.rec[k];
+                           HIP_TRY(c, h2d_small(c, c->d_finals + j.pic, &c->h_finals[j.pic], sizeof(PlaneSet), hs)); }
+      bool wp = false;
+      { HostTimer ts(c, 1);
+      for (int k = 0; k < j.num_slices && st == HMGPU_OK; k++) {
+        st = register_slice(c, j.pic, k, j.slices[k], hs);
+        all[i].push_back(k);
+        wp |= j.slices[k] && j.slices[k]->weighted_pred != 0;
+      }
+      }
+      SliceCall call;
+      HostTimer ti(c, 2);
+      if (st == HMGPU_OK) st = stage_packed(c, j, sums[i], all[i], wp, hs, &call);
+      if (st != HMGPU_OK) break;
+      b.pic[i] = j.pic; b.first_ctu[i] = 0; b.num_ctus[i] = c->num_ctus;
+      ua.pic[i] = j.pic; ua.blob[i] = (const char*)p.blob;
+      any_intra |= call.intra; any_wp |= call.wp; any_cells |= call.cells; any_bi |= call.bi; any_islice |= call.islice;
+    }
+    if (n > 1) {
+      (void)hipEventRecord(c->copy_join, c->copy_stream2);
+      (void)hipStreamWaitEvent(c->copy_stream, c->copy_join, 0);
+    }
+    if (st != HMGPU_OK) return st;
+    c->copy_seq++;
+    // the oldest pass the event ring still stands for: once its event has passed, every copy of that pass and before it is done
+    if (c->copy_seq > 8 && hipEventQuery(c->copy_ev[(c->copy_seq - 7) % 8]) == hipSuccess)
+      for (auto it = c->packed_reads.begin(); it != c->packed_reads.end();) it = it->second <= c->copy_seq - 7 ? c->packed_reads.erase(it) : std::next(it);
+    for (int i = 0; i < n; i++) c->packed_reads[jobs[i].blob] = c->copy_seq;
+    HIP_TRY(c, hipEventRecord(c->copy_ev[c->copy_seq % 8], c->copy_stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_ev[c->copy_seq % 8], 0));
+  }
+  HostTimer tr(c, 3);
+  { ProfScope ps(c, K_UNPACK); launch_unpack_input(c->d_pics, ua, c->num_ctus, c->stream); }
+  HIP_TRY(c, hipGetLastError());
+  for (int i = 0; i < n && st == HMGPU_OK; i++) st = extend_refs_of(c, jobs[i].pic, all[i]);
+  if (st == HMGPU_OK) st = run_recon(c, b, any_intra, any_wp, any_cells, any_bi, any_islice);
+  mark_use(c, b);
+  return st;
+}
+
+hmgpu_status hmgpu_packed_wait(hmgpu_ctx* c, const void* blob) {
+  if (!c || !blob) return HMGPU_EINVAL;
+  const auto it = c->packed_reads.find(blob);
+  if (it == c->packed_reads.end()) return HMGPU_OK;           // never read, or its copy is known to be done
+  hipSetDevice(c->device);
+  // (the ring of copy events holds the last 8 passes; an older pass is behind the newest event)
+  const uint64_t seq = c->copy_seq - it->second < 8 ? it->second : c->copy_seq;
+  if (hipEventSynchronize(c->copy_ev[seq % 8]) != hipSuccess) return HMGPU_EDEVICE;
+  return HMGPU_OK;
 }
 
 hmgpu_status hmgpu_filter_pictures(hmgpu_ctx* c, int32_t n, const hmgpu_filter_job* jobs) {

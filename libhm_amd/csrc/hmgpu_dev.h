@@ -270,6 +270,13 @@ __host__ inline int xcd_grid(int n, int nb) {
 }
 
 // ---- launchers (one per kernel family; defined in the .hip files) ---------------------------------------------------
+// packed picture input (k_unpack.hip): the device copy of every picture's blob, validated on the host
+struct UnpackArgs {
+  int32_t n;
+  int32_t pic[kMaxBatch];
+  const char* blob[kMaxBatch];
+};
+void launch_unpack_input(const PicDev* pics, const UnpackArgs& ua, int num_ctus, hipStream_t s);
 void launch_prep(const PicDev* pics, const Batch& b, int max_ctus, int parts, bool intra, bool write_blk, int fmt, hipStream_t s);
 // npics = entries of the finals table (device pictures of the context, <= kMaxPics)
 // bi: the batch holds B slices (the variants that run the H and V passes once per list)

@@ -829,6 +829,8 @@ void Decoder::flush_batch() {
   std::vector<hmgpu_coeffs> coefs(n);
   std::vector<std::vector<const hmgpu_slice_params*>> slices(n);
   std::vector<hmgpu_picture_job> jobs(n);
+  std::vector<hmgpu_packed_job> pjobs(n);
+  std::vector<char> packed(n, 0);
   std::vector<hmgpu_pic_params> pps(n);
   std::vector<hmgpu_filter_job> fjobs(n);
   bool resync = false;
@@ -871,6 +873,25 @@ void Decoder::flush_batch() {
     for (auto& s : p->slices) slices[i].push_back(&s->params);
     jobs[i].pic = p->handle; jobs[i].num_slices = (int32_t)slices[i].size(); jobs[i].slices = slices[i].data();
     jobs[i].meta = &m; jobs[i].coeffs = &co;
+    if (packed_input_ && p->chroma_format <= 1) {
+      // the packed form: the arrays above packed into the picture's own page-locked blob (once its last copy has been made)
+      if (!p->blob) {
+        p->blob_cap = hmgpu_packed_max_bytes(&seq_);
+        p->blob = hmgpu_host_alloc(p->blob_cap);
+        if (!p->blob) throw std::runtime_error("hmdec: hmgpu_host_alloc failed for a packed input");
+      } else if (p->blob_ctx) {
+        const hmgpu_status st = hmgpu_packed_wait(p->blob_ctx, p->blob);
+        if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_packed_wait: ") + hmgpu_status_string(st));
+      }
+      size_t bytes = 0;
+      if (hmgpu_pack_input(&seq_, &m, &co, p->blob, p->blob_cap, &bytes) == HMGPU_OK) {   // (else: the array path)
+        packed[i] = true;
+        hmgpu_packed_job& pj = pjobs[i];
+        pj.pic = p->handle; pj.num_slices = jobs[i].num_slices; pj.slices = jobs[i].slices;
+        pj.blob = p->blob; pj.bytes = bytes;
+        for (int c = 0; c < 3; c++) pj.pcm_sample[c] = co.pcm_sample[c];
+      }
+    }
     memset(&pps[i], 0, sizeof(pps[i]));
     pps[i].lf_across_tiles = p->lf_across_tiles;
     pps[i].sao_enabled = p->sao_enabled;
@@ -896,6 +917,7 @@ void Decoder::flush_batch() {
   }
   for (size_t d = 0; d < nd; d++) {
     std::vector<hmgpu_picture_job> dj;
+    std::vector<hmgpu_packed_job> dp;
     std::vector<hmgpu_filter_job> df;
     for (size_t i = 0; i < n; i++) {
       if (where[i] != (int)d) continue;
@@ -908,12 +930,20 @@ void Decoder::flush_batch() {
             if (ts != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_picture_transfer: ") + hmgpu_status_string(ts));
             r->present |= 1u << d;
           }
-      dj.push_back(jobs[i]);
+      if (packed[i]) { dp.push_back(pjobs[i]); pics[i]->blob_ctx = gpus_[d]; packed_pictures_++; }
+      else dj.push_back(jobs[i]);
       df.push_back(fjobs[i]);
     }
-    if (dj.empty()) continue;
-    hmgpu_status st = hmgpu_decompress_pictures(gpus_[d], (int32_t)dj.size(), dj.data());
-    if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_decompress_pictures: ") + hmgpu_status_string(st));
+    if (df.empty()) continue;
+    hmgpu_status st = HMGPU_OK;
+    if (!dj.empty()) {
+      st = hmgpu_decompress_pictures(gpus_[d], (int32_t)dj.size(), dj.data());
+      if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_decompress_pictures: ") + hmgpu_status_string(st));
+    }
+    if (!dp.empty()) {
+      st = hmgpu_decompress_pictures_packed(gpus_[d], (int32_t)dp.size(), dp.data());
+      if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_decompress_pictures_packed: ") + hmgpu_status_string(st));
+    }
     if (resync) (void)hmgpu_sync(gpus_[d]);                  // (the dense stand-in of a damaged picture is not page-locked staging: let its copies finish)
     st = hmgpu_filter_pictures(gpus_[d], (int32_t)df.size(), df.data());
     if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_filter_pictures: ") + hmgpu_status_string(st));

@@ -24,7 +24,8 @@ class Decoder {
   Decoder();
   ~Decoder();
   // configuration (before the first NAL unit)
-  void set_parse_only(bool v) { parse_only_ = v; }        // no device: metadata only (host-side tests)
+  void set_parse_only(bool v) { parse_only_ = v; }
+  void set_packed_input(bool v) { packed_input_ = v; }    // 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmgpu_pack_input)        // no device: metadata only (host-side tests)
   void set_check_hash(bool v) { check_hash_ = v; }
   void set_device(int ordinal) { device_ = ordinal; devices_.assign(1, ordinal); }
   // Several device contexts (one per GPU; the same ordinal twice gives two contexts on one GPU): the pictures retired together -- the B
@@ -56,6 +57,7 @@ class Decoder {
   int hash_mismatches() { drain_hash_jobs(); return hash_mismatches_.load(); }   // (waits for the MD5 checks still running on the hash threads)
   int pictures_decoded() const { return pictures_decoded_; }
   int device_batches() const { return (int)batches_submitted_; }
+  int packed_pictures() const { return (int)packed_pictures_; }
   void set_device_md5(bool on) { device_md5_ = on; }        // MD5 hash SEIs are checked on the device instead of on the hash threads
   const std::string& last_error() const { return last_error_; }
   void set_error(const std::string& s) { last_error_ = s; }
@@ -136,6 +138,8 @@ class Decoder {
   bool device_md5_ = !(getenv("HMDEC_DEVICE_MD5") != nullptr && getenv("HMDEC_DEVICE_MD5")[0] == '0');   // default on
   std::vector<PicData*> batch_;                            // pictures retired and not yet submitted: mutually independent
   uint64_t batches_submitted_ = 0;
+  uint64_t packed_pictures_ = 0;
+  bool packed_input_ = false;
   std::string last_error_;
   std::string deferred_error_;                            // parse error of a picture that left the pipeline while another unit was pushed
   bool push_unit(const uint8_t* data, size_t len, int max_temporal_layer, int* nal_type_out);

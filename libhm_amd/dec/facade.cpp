@@ -295,10 +295,12 @@ int hmdec_num_devices(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*
 unsigned long long hmdec_transfer_bytes(libHMDec_context* ctx) { return ctx ? (unsigned long long)static_cast<Wrapper*>(ctx)->dec.transfer_bytes() : 0ull; }
 void hmdec_set_threads(libHMDec_context* ctx, int n) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_threads(n); }
 void hmdec_set_parse_only(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_parse_only(on != 0); }
+void hmdec_set_packed_input(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_packed_input(on != 0); }
 int hmdec_hash_mismatches(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.hash_mismatches() : -1; }
 int hmdec_pictures_decoded(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.pictures_decoded() : -1; }
 void hmdec_set_device_md5(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_device_md5(on != 0); }
 int hmdec_device_batches(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.device_batches() : -1; }
+int hmdec_packed_pictures(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.packed_pictures() : -1; }
 const char* hmdec_last_error(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.last_error().c_str() : ""; }
 libHMDec_picture* hmdec_last_decoded_picture(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.last_decoded() : nullptr; }
 

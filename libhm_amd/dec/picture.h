@@ -110,6 +110,10 @@ struct PicData {
   hmgpu_staging* stg = nullptr;
   hmgpu_ctu_meta stg_meta;
   hmgpu_coeffs stg_co;
+  // packed input (Decoder::set_packed_input): the picture's inputs packed into page-locked memory, and the context whose copy read it last
+  void* blob = nullptr;
+  size_t blob_cap = 0;
+  hmgpu_ctx* blob_ctx = nullptr;
   HostVec<hmgpu_sao_param> sao;      // [num_ctbs][3]
   std::vector<std::unique_ptr<SliceInfo>> slices;
   // picture state (8.3)
@@ -146,9 +150,18 @@ struct PicData {
   ~PicData() { release_staging(); }
   void release_staging() {
     if (stg) { hmgpu_staging_free(stg_ctx, stg); stg = nullptr; stg_ctx = nullptr; }
+    release_blob();
+  }
+  // (before the contexts go away: the copy out of the blob may still be under way)
+  void release_blob() {
+    if (!blob) return;
+    if (blob_ctx) (void)hmgpu_packed_wait(blob_ctx, blob);
+    hmgpu_host_free(blob);
+    blob = nullptr; blob_cap = 0; blob_ctx = nullptr;
   }
   // the device context goes away while the application still holds the picture: the views become copies
   void detach_from_device() {
+    release_blob();
     if (!stg) return;
     for (auto* v : {&depth, &tr_idx, &cbf[0], &cbf[1], &cbf[2], &ts[0], &ts[1], &ts[2], &intra_dir[0], &intra_dir[1], &bypass, &ipcm}) v->detach();
     for (auto* v : {&part_size, &pred_mode, &qp, &ref_idx[0], &ref_idx[1]}) v->detach();

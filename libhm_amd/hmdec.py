@@ -43,6 +43,8 @@ def lib():
         L.hmdec_transfer_bytes.argtypes = [C.c_void_p]
         L.hmdec_transfer_bytes.restype = C.c_ulonglong
         L.hmdec_set_parse_only.argtypes = [C.c_void_p, C.c_int]
+        L.hmdec_set_packed_input.argtypes = [C.c_void_p, C.c_int]
+        L.hmdec_packed_pictures.argtypes = [C.c_void_p]
         L.hmdec_set_threads.argtypes = [C.c_void_p, C.c_int]
         L.hmdec_hash_mismatches.argtypes = [C.c_void_p]
         L.hmdec_pictures_decoded.argtypes = [C.c_void_p]
@@ -177,8 +179,10 @@ class Picture:
 
 
 class Decoder:
-    def __init__(self, parse_only=False, device=0, check_hash=True, max_temporal_layer=-1, threads=1, device_md5=None, devices=None):
-        """devices: GPU ordinals of several device contexts (hmdec_set_devices; the same ordinal twice = two contexts on one GPU)"""
+    def __init__(self, parse_only=False, device=0, check_hash=True, max_temporal_layer=-1, threads=1, device_md5=None, devices=None,
+                 packed_input=False):
+        """devices: GPU ordinals of several device contexts (hmdec_set_devices; the same ordinal twice = two contexts on one GPU).
+        packed_input: 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmdec_set_packed_input)"""
         self.ctx = lib().libHMDec_new_decoder()
         if not self.ctx:
             raise MemoryError("libHMDec_new_decoder")
@@ -187,6 +191,7 @@ class Decoder:
         if devices:
             lib().hmdec_set_devices(self.ctx, (C.c_int * len(devices))(*devices), len(devices))
         lib().hmdec_set_threads(self.ctx, threads)
+        lib().hmdec_set_packed_input(self.ctx, 1 if packed_input else 0)
         lib().libHMDec_set_SEI_Check(self.ctx, check_hash)
         lib().libHMDec_set_max_temporal_layer(self.ctx, max_temporal_layer)
         if device_md5 is not None:                 # MD5 hash SEIs checked on the device (default: the decoder's hash threads / HMDEC_DEVICE_MD5)
@@ -235,6 +240,11 @@ class Decoder:
     @property
     def pictures_decoded(self):
         return lib().hmdec_pictures_decoded(self.ctx)
+
+    @property
+    def packed_pictures(self):
+        """pictures handed to the device as packed inputs so far"""
+        return lib().hmdec_packed_pictures(self.ctx)
 
     @property
     def device_batches(self):
