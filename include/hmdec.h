@@ -80,6 +80,22 @@ void hmdec_set_parse_only(libHMDec_context* ctx, int on);                     /*
 /* before the first NAL unit: 4:0:0 / 4:2:0 pictures are packed (hmgpu_pack_input, into page-locked memory) and handed over through
  * hmgpu_decompress_pictures_packed; other pictures, and a picture the packer refuses, take the array path.  Off by default. */
 void hmdec_set_packed_input(libHMDec_context* ctx, int on);
+/* Device output (before the first NAL unit, off by default): libHMDec_get_picture no longer downloads the planes of the pictures it
+ * puts out; libHMDEC_get_image_plane and hmdec_picture_array("plane*") download them when first asked.  hmdec_picture_export converts
+ * a picture into caller device memory (hmgpu_picture_export on the context that holds it; returns an hmgpu_status).  It is valid from
+ * libHMDec_get_picture until the next libHMDec_push_nal_unit; a picture of a sequence that has ended (its context is gone) gives
+ * HMGPU_EINVAL.  hmdec_download_bytes: plane bytes copied device -> host so far, for any reason (output, host hash checks). */
+#ifndef HMGPU_H
+typedef struct hmgpu_export_desc hmgpu_export_desc;
+#endif
+void hmdec_set_device_output(libHMDec_context* ctx, int on);
+int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
+                         const int64_t pitch_bytes[3], int on_stream, void* stream);
+unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
+int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
+/* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,
+ * transfer_characteristics, matrix_coefficients, video_format */
+int hmdec_picture_colour(libHMDec_picture* pic, int32_t out[5]);
 int hmdec_hash_mismatches(libHMDec_context* ctx);                             /* pictures whose reconstruction disagreed with the hash SEI */
 int hmdec_pictures_decoded(libHMDec_context* ctx);
 void hmdec_set_device_md5(libHMDec_context* ctx, int on);                     /* MD5 hash SEIs checked on the device (hmgpu_picture_hash_begin) (the default;

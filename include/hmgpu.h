@@ -255,6 +255,51 @@ hmgpu_status hmgpu_picture_commit_received(hmgpu_ctx* ctx, hmgpu_pic pic);
 /* the context's HIP stream (a hipStream_t), for callers that order their own device work against the library's */
 void* hmgpu_stream(hmgpu_ctx* ctx);
 
+/* ------------------------------------------------------------------------------------------------ device export
+ * A finished picture converted on the device straight into caller-owned device memory.  Three layouts:
+ *   HMGPU_EXPORT_PLANAR      Y, Cb, Cr at the picture's chroma format (Y only for 4:0:0) -- what TAppDecoder -d N -o writes
+ *   HMGPU_EXPORT_SEMIPLANAR  Y + one interleaved CbCr plane (NV12 / NV16 / NV24; P010 / P016 with msb_aligned) (Y only for 4:0:0)
+ *   HMGPU_EXPORT_RGB         three planes R, G, B (CHW), full range 0 .. 2^bit_depth - 1
+ * Bit depth of the YUV layouts (and of matrix 0), per channel type, HM 16.0 TVideoIOYuv::write with CLIP_TO_709_RANGE 0
+ * (TVideoIOYuv.cpp:70-87): s = out - coding depth; s >= 0: v << s; s < 0: Clip3(0, 2^out - 1, (v + (1 << (-s - 1))) >> -s).
+ * 2-byte samples are LSB-aligned, or shifted left by 16 - out when msb_aligned.  The crop window is in luma samples and must cover
+ * whole chroma samples (else HMGPU_EINVAL).  RGB: the chroma sample of luma (x, y) is (x >> csx, y >> csy); 4:0:0 uses
+ * Cb = Cr = 1 << (bdC - 1); `matrix` takes the VUI matrix_coefficients codes 1 (BT.709), 5 / 6 (BT.601), 9 (BT.2020 non-constant
+ * luminance) -- H.273's Kr / Kb equations, limited or full range (full_range) -- and 0 (identity / GBR: G = Y, B = Cb, R = Cr, then
+ * the bit-depth rule; 4:4:4 only); any other code gives HMGPU_EUNSUPPORTED.  The integers the kernel uses are derived on the host
+ * in double precision (rounded half away from zero) and published in hmgpu_export_plan.coef:
+ *   coef[0] S (shift)      coef[1] 1 << (S - 1)     coef[2] Y offset      coef[3] chroma offset (1 << (bdC - 1))
+ *   coef[4] cY             coef[5] cR<-Cr           coef[6] cG<-Cb        coef[7] cG<-Cr        coef[8] cB<-Cb
+ *   coef[9] 2^bit_depth - 1                         coef[10] 1: identity (matrix 0)            coef[11..15] 0
+ *   t = cY * (Y - coef[2]) + coef[1];  u = Cb - coef[3];  v = Cr - coef[3]
+ *   R = Clip3(0, coef[9], (t + cR<-Cr * v) >> S)   G = Clip3(0, coef[9], (t + cG<-Cb * u + cG<-Cr * v) >> S)   B = Clip3(0, coef[9], (t + cB<-Cb * u) >> S)
+ * in 32-bit integers: S is the largest shift (<= 30) for which no sum can overflow for any sample of the coding bit depths. */
+enum { HMGPU_EXPORT_PLANAR = 0, HMGPU_EXPORT_SEMIPLANAR = 1, HMGPU_EXPORT_RGB = 2 };
+typedef struct hmgpu_export_desc {
+  int32_t layout;              /* HMGPU_EXPORT_* */
+  int32_t bit_depth[2];        /* output depth luma / chroma (RGB: [0] for all three; 8..16); 0 = the coding bit depth */
+  int32_t bytes_per_sample;    /* 1 (bit depth <= 8) or 2 */
+  int32_t msb_aligned;         /* 2-byte samples only: shifted left by 16 - bit depth (P010 / P016) */
+  int32_t crop[4];             /* left, right, top, bottom, luma samples */
+  int32_t matrix, full_range;  /* RGB only: VUI matrix_coefficients, video_full_range_flag of the input */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_export_desc;
+typedef struct hmgpu_export_plan {
+  int32_t planes;              /* planes written: 1 .. 3 */
+  int32_t width[3], height[3]; /* per plane, in samples (semi-planar CbCr: in CbCr pairs) */
+  int32_t row_bytes[3];        /* bytes of one row: the least pitch */
+  int32_t coef[16];            /* RGB: see above; else 0 */
+} hmgpu_export_plan;
+/* validates a descriptor against a sequence and reports what an export writes; host code, no device needed */
+hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, hmgpu_export_plan* out);
+/* Enqueues the conversion of picture `pic` into dst[k] (device memory of the context's GPU, rows pitch_bytes[k] apart) and returns
+ * without waiting.  on_stream 0: on the context's stream; 1: on `stream`, a hipStream_t of the context's device (0: the null
+ * stream; another device's stream gives HMGPU_EINVAL).  Either way the kernel runs after all work enqueued for the picture and after
+ * everything already on `stream`, and every later operation of the context waits for it.  Everything is validated before anything
+ * is enqueued. */
+hmgpu_status hmgpu_picture_export(hmgpu_ctx* ctx, hmgpu_pic pic, const hmgpu_export_desc* desc, void* const dst[3],
+                                  const int64_t pitch_bytes[3], int32_t on_stream, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->
  * TDecCu::decompressCU (TDecSlice.cpp:334, TDecCu.cpp:142,373) for the CTUs [first_ctu, first_ctu+num_ctus) of

@@ -79,6 +79,9 @@ def lib():
         L.hmgpu_picture_transfer.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.hmgpu_transfer_bytes.argtypes = [C.c_void_p]
         L.hmgpu_transfer_bytes.restype = C.c_uint64
+        L.hmgpu_export_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportPlan)]
+        L.hmgpu_picture_export.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                           C.c_int32, C.c_void_p]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -132,6 +135,15 @@ def pack_levels(seq, meta, coeffs):
     for k in range(3):
         out.struct.ctu_level_start[k] = out.starts[k].ctypes.data
     return out
+
+
+def export_plan(seq, desc):
+    """what an export with `desc` writes for pictures of `seq` (hmgpu_export_plan_for: host code, no GPU)"""
+    plan = abi.ExportPlan()
+    st = lib().hmgpu_export_plan_for(C.byref(seq), C.byref(desc), C.byref(plan))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_export_plan_for")
+    return plan
 
 
 def packed_max_bytes(seq):
@@ -265,6 +277,19 @@ class Context:
         strides = (C.c_int32 * 3)(*[p.shape[1] for p in planes])
         self._chk(lib().hmgpu_picture_download(self._h, pic, ptrs, strides), "hmgpu_picture_download")
         return planes
+
+    def export_into(self, pic, desc, ptrs, pitches, on_stream=0, stream=0):
+        """hmgpu_picture_export into device memory the caller owns: ptrs / pitches (bytes) per plane"""
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        self._chk(lib().hmgpu_picture_export(self._h, pic, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmgpu_picture_export")
+
+    def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True):
+        """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
+        (on_stream) or on the context's own"""
+        from . import export
+        return export.export_tensors(lambda desc, ptrs, pitches, st: self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st),
+                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

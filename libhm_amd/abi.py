@@ -85,6 +85,31 @@ class Stats(C.Structure):
                 ("intra_partitions", C.c_uint64), ("inter_partitions", C.c_uint64), ("coded_tus", (C.c_uint64 * 3) * 4)]
 
 
+EXPORT_PLANAR, EXPORT_SEMIPLANAR, EXPORT_RGB = 0, 1, 2
+
+
+class ExportDesc(C.Structure):
+    _fields_ = [("layout", C.c_int32), ("bit_depth", C.c_int32 * 2), ("bytes_per_sample", C.c_int32), ("msb_aligned", C.c_int32),
+                ("crop", C.c_int32 * 4), ("matrix", C.c_int32), ("full_range", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class ExportPlan(C.Structure):
+    _fields_ = [("planes", C.c_int32), ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("row_bytes", C.c_int32 * 3),
+                ("coef", C.c_int32 * 16)]
+
+
+def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
+    d = ExportDesc()
+    d.layout = layout
+    bd = (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
+    d.bit_depth[0], d.bit_depth[1] = bd
+    d.bytes_per_sample, d.msb_aligned = bytes_per_sample, int(msb_aligned)
+    for i in range(4):
+        d.crop[i] = crop[i]
+    d.matrix, d.full_range = matrix, int(full_range)
+    return d
+
+
 # ------------------------------------------------------------------------------------------------ helpers
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p).value

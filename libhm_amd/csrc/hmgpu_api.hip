@@ -120,6 +120,7 @@ struct hmgpu_ctx {
   uint32_t* hash_host = nullptr;         // page-locked: the same
   uint64_t hash_seq = 0, hash_launched = 0, hash_launches = 0;
   hipEvent_t xfer_ev[2] = {};            // hmgpu_picture_transfer: source ready / copy done
+  hipEvent_t exp_ev[2] = {};             // hmgpu_picture_export on a caller's stream: picture ready / export done (created when first used)
   uint64_t xfer_bytes = 0;
   uint32_t* dl_fault = nullptr;        // [32] page-locked: the picture's fault word (k_intra's bounded spin) as it stood behind the copies of ticket t
   std::vector<int> touched;            // pictures the entry point under way has enqueued work on, in any role (commit_use)
@@ -737,6 +738,7 @@ void hmgpu_destroy(hmgpu_ctx* c) {
   }
   if (c->hash_dev) (void)hipFree(c->hash_dev);
   for (int k = 0; k < 2; k++) if (c->xfer_ev[k]) hipEventDestroy(c->xfer_ev[k]);
+  for (int k = 0; k < 2; k++) if (c->exp_ev[k]) hipEventDestroy(c->exp_ev[k]);
   if (c->hash_host) (void)hipHostFree(c->hash_host);
   for (int k = 0; k < 2; k++) if (c->lane_ev[k]) hipEventDestroy(c->lane_ev[k]);
   delete c;
@@ -1123,6 +1125,151 @@ hmgpu_status hmgpu_picture_transfer(hmgpu_ctx* src, hmgpu_pic src_pic, hmgpu_ctx
 uint64_t hmgpu_transfer_bytes(const hmgpu_ctx* c) { return c ? c->xfer_bytes : 0; }
 
 void* hmgpu_stream(hmgpu_ctx* c) { return c ? (void*)c->stream : nullptr; }
+
+// ------------------------------------------------------------------------------------------------ device export (k_export.hip)
+static long long round_half_away(double v) { return v < 0 ? -(long long)std::floor(-v + 0.5) : (long long)std::floor(v + 0.5); }
+
+// H.273 Kr / Kb of the matrix_coefficients codes the export takes (Table 4): false for any other code
+static bool matrix_kr_kb(int matrix, double* kr, double* kb) {
+  switch (matrix) {
+    case 1: *kr = 0.2126; *kb = 0.0722; return true;            // BT.709
+    case 5: case 6: *kr = 0.299; *kb = 0.114; return true;      // BT.601 (625 / 525)
+    case 9: *kr = 0.2627; *kb = 0.0593; return true;            // BT.2020 non-constant luminance
+    default: return false;
+  }
+}
+
+hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, hmgpu_export_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const int fmt = seq->chroma_format, bdY = seq->bit_depth_luma, bdC = seq->bit_depth_chroma;
+  if (fmt < 0 || fmt > 3 || bdY < 8 || bdY > 12 || bdC < 8 || bdC > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
+  if (d->layout < HMGPU_EXPORT_PLANAR || d->layout > HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (d->bytes_per_sample != 1 && d->bytes_per_sample != 2) return HMGPU_EINVAL;
+  if ((d->msb_aligned != 0 && d->msb_aligned != 1) || (d->msb_aligned && d->bytes_per_sample != 2)) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB, mono = fmt == 0;
+  const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
+  const int ob[2] = {d->bit_depth[0] ? d->bit_depth[0] : bdY, rgb ? (d->bit_depth[0] ? d->bit_depth[0] : bdY) : (d->bit_depth[1] ? d->bit_depth[1] : bdC)};
+  const int lo = rgb ? 8 : 1;
+  for (int t = 0; t < (mono && !rgb ? 1 : 2); t++)
+    if (ob[t] < lo || ob[t] > 16 || (d->bytes_per_sample == 1 && ob[t] > 8)) return HMGPU_EINVAL;
+  const int* cr = d->crop;
+  if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+  const int W = seq->width - cr[0] - cr[1], H = seq->height - cr[2] - cr[3];
+  if (W <= 0 || H <= 0) return HMGPU_EINVAL;
+  if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  const int B = d->bytes_per_sample;
+  if (rgb) {
+    if (d->full_range != 0 && d->full_range != 1) return HMGPU_EINVAL;
+    double kr = 0, kb = 0;
+    if (d->matrix == 0) {
+      if (fmt != 3) return HMGPU_EINVAL;                         // identity: 4:4:4 only
+    } else if (!matrix_kr_kb(d->matrix, &kr, &kb)) {
+      return HMGPU_EUNSUPPORTED;
+    }
+    out->planes = 3;
+    for (int k = 0; k < 3; k++) { out->width[k] = W; out->height[k] = H; out->row_bytes[k] = W * B; }
+    const int M = (1 << ob[0]) - 1;
+    out->coef[9] = M;
+    if (d->matrix == 0) { out->coef[10] = 1; return HMGPU_OK; }
+    const double kg = 1.0 - kr - kb;
+    const int yo = d->full_range ? 0 : 16 << (bdY - 8), co = 1 << (bdC - 1);
+    const double ys = d->full_range ? (double)((1 << bdY) - 1) : (double)(219 << (bdY - 8));
+    const double cs = d->full_range ? (double)((1 << bdC) - 1) : (double)(224 << (bdC - 8));
+    const double r[5] = {M / ys, M * 2.0 * (1.0 - kr) / cs, -M * 2.0 * kb * (1.0 - kb) / kg / cs, -M * 2.0 * kr * (1.0 - kr) / kg / cs, M * 2.0 * (1.0 - kb) / cs};
+    const long long maxdy = std::max(yo, (1 << bdY) - 1 - yo), maxdc = co;
+    for (int S = 30; S >= 1; S--) {
+      long long c[5];
+      for (int i = 0; i < 5; i++) c[i] = round_half_away(r[i] * (double)(1LL << S));
+      const long long t = std::llabs(c[0]) * maxdy + (1LL << (S - 1));
+      const long long bound = std::max({t + std::llabs(c[1]) * maxdc, t + (std::llabs(c[2]) + std::llabs(c[3])) * maxdc, t + std::llabs(c[4]) * maxdc});
+      if (bound > INT32_MAX) continue;
+      out->coef[0] = S; out->coef[1] = 1 << (S - 1); out->coef[2] = yo; out->coef[3] = co;
+      for (int i = 0; i < 5; i++) out->coef[4 + i] = (int32_t)c[i];
+      return HMGPU_OK;
+    }
+    return HMGPU_EUNSUPPORTED;
+  }
+  out->planes = mono ? 1 : d->layout == HMGPU_EXPORT_PLANAR ? 3 : 2;
+  out->width[0] = W; out->height[0] = H; out->row_bytes[0] = W * B;
+  for (int k = 1; k < out->planes; k++) {
+    out->width[k] = W >> csx; out->height[k] = H >> csy;
+    out->row_bytes[k] = (d->layout == HMGPU_EXPORT_PLANAR ? 1 : 2) * out->width[k] * B;
+  }
+  return HMGPU_OK;
+}
+
+// true if [p, p + bytes) lies inside one device allocation of `device`
+static bool device_span_ok(const void* p, size_t bytes, int device) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (at.type != hipMemoryTypeDevice || at.device != device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+  return q >= b && q - b + bytes <= size;
+}
+
+hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
+                                  int32_t on_stream, void* stream) {
+  if (!c || !valid_pic(c, pic) || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  { const hmgpu_status st = hmgpu_export_plan_for(&c->seq, d, &plan); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  const int B = d->bytes_per_sample;
+  bool vec = (d->crop[0] & 3) == 0;
+  for (int k = 0; k < plan.planes; k++) {
+    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k], c->device)) return HMGPU_EINVAL;
+    vec = vec && ((uintptr_t)dst[k] % (4 * B)) == 0 && pitch_bytes[k] % (4 * B) == 0;
+  }
+  hipStream_t hs = c->stream;
+  if (on_stream) {
+    hs = (hipStream_t)stream;
+    if (hs) {
+      hipDevice_t dev = -1;
+      if (hipStreamGetDevice(hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
+      if ((int)dev != c->device) return HMGPU_EINVAL;
+    }
+    for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
+  }
+  const Picture& p = c->pics[pic];
+  int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+  ExportArgs a;
+  memset(&a, 0, sizeof(a));
+  const int x0 = d->crop[0], y0 = d->crop[2];
+  a.y = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
+  a.c = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+  a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
+  a.layout = d->layout; a.bytes = B; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+  a.w = plan.width[0]; a.h = plan.height[0];
+  a.cw = (plan.width[0]) >> c->csx; a.ch = plan.height[0] >> c->csy;
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
+  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
+  const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
+  const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
+  a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
+  a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
+  a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
+  a.vec = vec ? 1 : 0;
+  for (int k = 0; k < 3; k++) { a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr; a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0; }
+  memcpy(a.coef, plan.coef, sizeof(a.coef));
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                 // behind everything enqueued for the picture ...
+    HIP_TRY(c, hipStreamWaitEvent(hs, c->exp_ev[0], 0));                 // ... and behind what is already on the caller's stream
+  }
+  launch_export(a, hs);
+  HIP_TRY(c, hipGetLastError());
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
+  }
+  touch(c, pic);
+  commit_use(c);
+  return HMGPU_OK;
+}
 
 // slice table entry of one slice (validation, SliceDev, scaling lists): the part of a slice call that does not depend on CTUs
 static hmgpu_status register_slice(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx, const hmgpu_slice_params* sl, hipStream_t hs) {

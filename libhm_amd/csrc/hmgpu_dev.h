@@ -296,6 +296,21 @@ struct Md5Batch { int32_t n, pad_; const uint8_t* msg[128]; unsigned long long b
 void launch_md5(const Md5Batch& job, hipStream_t s);
 void launch_crc(const int16_t* src, int pitch, int step, int w, int h, int bd, uint32_t* rows, uint32_t* out, hipStream_t s);
 void launch_intra(const PicDev* pics, const Batch& b, const int32_t* order, int num_ctus, bool lean, hipStream_t s);   // lean: no I slices in the call
+// device export of a finished picture (k_export.hip, hmgpu_picture_export): everything by value, validated on the host
+struct ExportArgs {
+  const int16_t* y;                // luma sample (crop left, crop top)
+  const int16_t* c;                // Cb of chroma sample (crop left >> csx, crop top >> csy) in the pair plane (Cr one element on)
+  int32_t pitch_y, pitch_c;        // int16 elements
+  int32_t layout, bytes, mono, csx, csy;
+  int32_t w, h, cw, ch;            // output luma / chroma size (chroma rows follow the luma rows in the grid, YUV layouts)
+  int32_t sh[2], maxv[2];          // bit-depth rule per channel type: out - coding depth, 2^out - 1
+  int32_t msb[2];                  // container shift per channel type (msb_aligned: 16 - out)
+  int32_t vec;                     // every group of 4 samples may use vector loads and stores (alignment of crop, dst and pitches)
+  uint8_t* dst[3];
+  int64_t pitch[3];                // bytes
+  int32_t coef[16];                // hmgpu_export_plan.coef
+};
+void launch_export(const ExportArgs& a, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

@@ -483,6 +483,9 @@ void Decoder::start_picture(const SliceHeader& sh) {
   cur_->pcm_lf_disable = sps_->pcm && sps_->pcm_loop_filter_disabled;
   cur_->strong_intra = sps_->strong_intra_smoothing;
   cur_->range_ext_flags = sps_->range_ext_flags();
+  cur_->colour[0] = sps_->video_full_range; cur_->colour[1] = sps_->colour_primaries; cur_->colour[2] = sps_->transfer_characteristics;
+  cur_->colour[3] = sps_->matrix_coefficients; cur_->colour[4] = sps_->video_format;
+  cur_->owner = this;
   cur_->num_comps = sps_->chroma_format_idc == 0 ? 1 : 3;
   cur_->sao_offset_shift[0] = pps_->sao_offset_shift[0]; cur_->sao_offset_shift[1] = pps_->sao_offset_shift[1];
   cur_->lf_across_tiles = pps_->lf_across_tiles;
@@ -948,7 +951,7 @@ void Decoder::flush_batch() {
     st = hmgpu_filter_pictures(gpus_[d], (int32_t)df.size(), df.data());
     if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_filter_pictures: ") + hmgpu_status_string(st));
   }
-  for (size_t i = 0; i < n; i++) { pics[i]->home = where[i]; pics[i]->present = 1u << where[i]; }
+  for (size_t i = 0; i < n; i++) { pics[i]->home = where[i]; pics[i]->present = 1u << where[i]; pics[i]->on_device = true; }
   ++submitted_seq_;
   batches_submitted_++;
   for (PicData* p : pics) p->submit_seq = submitted_seq_;
@@ -959,6 +962,7 @@ bool Decoder::fetch_planes(PicData* pic) {
   if (!gpu_ || !pic) return false;
   if (pic->planes_valid) return true;
   flush_batch();
+  if (!pic->on_device) return false;                     // (device output: its context went away with the sequence)
   if (const uint64_t t = pic->dl_ticket.load()) {        // begun for the hash check: wait for it instead of copying again
     if (hmgpu_download_wait(ctx_of(pic), t) != HMGPU_OK) return false;
     pic->planes_valid = true;
@@ -971,9 +975,23 @@ bool Decoder::fetch_planes(PicData* pic) {
   const int32_t strides[3] = {pic->width, pic->width >> pic->csx, pic->width >> pic->csx};
   const uint64_t seq = submitted_seq_;
   if (hmgpu_picture_download(ctx_of(pic), pic->handle, planes, strides) != HMGPU_OK) return false;
+  download_bytes_ += 2 * (pic->plane[0].size() + pic->plane[1].size() + pic->plane[2].size());
   if (gpus_.size() == 1) synced_seq_ = seq;  // a download returns after everything enqueued before it (on that context)
   pic->planes_valid = true;
   return true;
+}
+
+bool Decoder::deliver(PicData* pic) {
+  if (!device_output_) return fetch_planes(pic);
+  if (gpu_) flush_batch();                               // (the picture's device work is enqueued before anybody exports it)
+  return true;
+}
+
+hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream) {
+  if (!gpu_ || !pic || pic->owner != this) return HMGPU_EINVAL;
+  flush_batch();
+  if (!pic->on_device || !pic->decoded) return HMGPU_EINVAL;
+  return hmgpu_picture_export(ctx_of(pic), pic->handle, desc, dst, pitch_bytes, on_stream, stream);
 }
 
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row
@@ -1081,6 +1099,7 @@ void Decoder::check_hash(PicData* pic) {
         const int32_t strides[3] = {pic->width, pic->width >> pic->csx, pic->width >> pic->csx};
         uint64_t t = 0;
         if (hmgpu_picture_download_begin(ctx_of(pic), pic->handle, planes, strides, &t) != HMGPU_OK) return;
+        download_bytes_ += 2 * (pic->plane[0].size() + pic->plane[1].size() + pic->plane[2].size());
         pic->dl_ticket.store(t);
       }
       pic->users.fetch_add(pic->num_comps);

@@ -27,6 +27,9 @@ class Decoder {
   void set_parse_only(bool v) { parse_only_ = v; }
   void set_packed_input(bool v) { packed_input_ = v; }    // 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmgpu_pack_input)        // no device: metadata only (host-side tests)
   void set_check_hash(bool v) { check_hash_ = v; }
+  // device output: pictures put out stay on the device (hmgpu_picture_export); their planes are downloaded only when asked for
+  void set_device_output(bool v) { device_output_ = v; }
+  bool device_output() const { return device_output_; }
   void set_device(int ordinal) { device_ = ordinal; devices_.assign(1, ordinal); }
   // Several device contexts (one per GPU; the same ordinal twice gives two contexts on one GPU): the pictures retired together -- the B
   // pictures of one temporal level, TDecTop.cpp:672 per picture -- are placed round-robin on them, each reference picture is copied once to
@@ -62,6 +65,10 @@ class Decoder {
   const std::string& last_error() const { return last_error_; }
   void set_error(const std::string& s) { last_error_ = s; }
   bool fetch_planes(PicData* pic);                        // device -> host planes of a finished picture (no-op when parse-only)
+  bool deliver(PicData* pic);                             // a picture handed to the application: planes downloaded, or (device output) its work submitted
+  hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream);
+  int device_of(const PicData* pic) const { return pic && pic->on_device && pic->owner == this ? devices_[pic->home] : -1; }
+  uint64_t download_bytes() const { return download_bytes_; }
   int last_display_poc = -(1 << 30);
 
  private:
@@ -140,6 +147,8 @@ class Decoder {
   uint64_t batches_submitted_ = 0;
   uint64_t packed_pictures_ = 0;
   bool packed_input_ = false;
+  bool device_output_ = false;
+  std::atomic<uint64_t> download_bytes_{0};                // plane bytes copied device -> host
   std::string last_error_;
   std::string deferred_error_;                            // parse error of a picture that left the pipeline while another unit was pushed
   bool push_unit(const uint8_t* data, size_t len, int max_temporal_layer, int* nal_type_out);

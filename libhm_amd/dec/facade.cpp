@@ -21,6 +21,10 @@ struct Wrapper {
 int g_bit_depth[2] = {8, 8};           // HM keeps the bit depths in globals (g_bitDepth); the getter has no context argument
 
 PicData* as_pic(libHMDec_picture* p) { return static_cast<PicData*>(p); }
+// device output: the planes of a picture come down when somebody first reads them
+void fetch_lazily(PicData* p) {
+  if (!p->planes_valid && p->owner) static_cast<Decoder*>(p->owner)->fetch_planes(p);
+}
 }  // namespace
 
 extern "C" {
@@ -109,7 +113,7 @@ libHMDec_picture* libHMDec_get_picture(libHMDec_context* ctx) {
   if (!w) return nullptr;
   if (w->dec.threaded()) {
     PicData* q = w->dec.pop_output();
-    if (q) w->dec.fetch_planes(q);
+    if (q) w->dec.deliver(q);
     return q;
   }
   PicData* p = w->dec.next_output(w->flush_output);
@@ -123,7 +127,7 @@ libHMDec_picture* libHMDec_get_picture(libHMDec_context* ctx) {
     }
     return nullptr;
   }
-  w->dec.fetch_planes(p);              // the samples leave the device when the application asks for the picture
+  w->dec.deliver(p);                   // the samples leave the device when the application asks for the picture (device output: later, if at all)
   return p;
 }
 
@@ -142,6 +146,7 @@ int libHMDEC_get_picture_stride(libHMDec_picture* pic, libHMDec_ColorComponent c
 short* libHMDEC_get_image_plane(libHMDec_picture* pic, libHMDec_ColorComponent c) {
   if (!pic || c < LIBHMDEC_LUMA || c > LIBHMDEC_CHROMA_V) return nullptr;
   PicData* p = as_pic(pic);
+  fetch_lazily(p);
   if (!p->planes_valid) return nullptr;
   if (c != LIBHMDEC_LUMA && p->num_comps == 1) return nullptr;        // monochrome: HM allocates no chroma buffers (TComPicYuv::create)
   return p->plane[c].data();
@@ -295,6 +300,22 @@ int hmdec_num_devices(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*
 unsigned long long hmdec_transfer_bytes(libHMDec_context* ctx) { return ctx ? (unsigned long long)static_cast<Wrapper*>(ctx)->dec.transfer_bytes() : 0ull; }
 void hmdec_set_threads(libHMDec_context* ctx, int n) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_threads(n); }
 void hmdec_set_parse_only(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_parse_only(on != 0); }
+void hmdec_set_device_output(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_device_output(on != 0); }
+unsigned long long hmdec_download_bytes(libHMDec_context* ctx) { return ctx ? (unsigned long long)static_cast<Wrapper*>(ctx)->dec.download_bytes() : 0ull; }
+int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3],
+                         int on_stream, void* stream) {
+  if (!ctx || !pic) return HMGPU_EINVAL;
+  return static_cast<Wrapper*>(ctx)->dec.export_picture(as_pic(pic), desc, dst, pitch_bytes, on_stream, stream);
+}
+int hmdec_picture_device(libHMDec_picture* pic) {
+  if (!pic || !as_pic(pic)->owner) return -1;
+  return static_cast<const Decoder*>(as_pic(pic)->owner)->device_of(as_pic(pic));
+}
+int hmdec_picture_colour(libHMDec_picture* pic, int32_t out[5]) {
+  if (!pic || !out) return 1;
+  for (int i = 0; i < 5; i++) out[i] = as_pic(pic)->colour[i];
+  return 0;
+}
 void hmdec_set_packed_input(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_packed_input(on != 0); }
 int hmdec_hash_mismatches(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.hash_mismatches() : -1; }
 int hmdec_pictures_decoded(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.pictures_decoded() : -1; }
@@ -332,6 +353,7 @@ int hmdec_picture_array(libHMDec_picture* pic, const char* name, const void** da
   if (n.compare(0, 5, "coeff") == 0 && idx(5) >= 0 && idx(5) < 3) return give(p.coeff[idx(5)].data(), p.coeff[idx(5)].size() * 2);
   if (n.compare(0, 3, "pcm") == 0 && idx(3) >= 0 && idx(3) < 3) return give(p.pcm[idx(3)].data(), p.pcm[idx(3)].size() * 2);
   if (n.compare(0, 3, "ccp") == 0 && idx(3) >= 0 && idx(3) < 2 && !p.ccp[idx(3)].empty()) return give(p.ccp[idx(3)].data(), p.ccp[idx(3)].size());
+  if (n.compare(0, 5, "plane") == 0) fetch_lazily(&p);
   if (n.compare(0, 5, "plane") == 0 && idx(5) >= 0 && idx(5) < 3 && p.planes_valid) return give(p.plane[idx(5)].data(), p.plane[idx(5)].size() * 2);
   return 1;
 }

@@ -211,11 +211,15 @@ static void skip_hrd(BitReader& br, bool common, int max_sub_layers_minus1) {
   }
 }
 
-// E.2.1 vui_parameters(): nothing of it is needed for reconstruction
-static void skip_vui(BitReader& br, int max_sub_layers_minus1) {
+// E.2.1 vui_parameters(): nothing of it is needed for reconstruction; the colour description is kept for the device export
+static void parse_vui(BitReader& br, int max_sub_layers_minus1, Sps& s) {
   if (br.flag()) { if (br.u(8) == 255) { br.u(16); br.u(16); } }
   if (br.flag()) br.u(1);
-  if (br.flag()) { br.u(3); br.u(1); if (br.flag()) { br.u(8); br.u(8); br.u(8); } }
+  if ((s.video_signal_type_present = br.flag())) {
+    s.video_format = br.u(3);
+    s.video_full_range = br.u(1) != 0;
+    if (br.flag()) { s.colour_primaries = br.u(8); s.transfer_characteristics = br.u(8); s.matrix_coefficients = br.u(8); }
+  }
   if (br.flag()) { br.ue(); br.ue(); }
   br.u(1); br.u(1); br.u(1);
   if (br.flag()) { br.ue(); br.ue(); br.ue(); br.ue(); }
@@ -306,7 +310,7 @@ std::shared_ptr<Sps> parse_sps(BitReader& br) {
   }
   s.temporal_mvp = br.flag();
   s.strong_intra_smoothing = br.flag();
-  if (br.flag()) skip_vui(br, msl1);
+  if (br.flag()) parse_vui(br, msl1, s);
   if (br.flag()) {                       // sps_extension_present_flag: range extension flag first (HM 16.0: TDecCAVLC.cpp:758-800)
     const bool range_ext = br.flag();
     br.u(7);

@@ -53,6 +53,9 @@ struct Sps {
   int num_long_term_ref_pics_sps = 0, lt_ref_pic_poc_lsb_sps[32] = {0};
   bool used_by_curr_pic_lt_sps[32] = {false};
   bool temporal_mvp = false, strong_intra_smoothing = false;
+  // VUI colour description (E.2.1); absent fields take the E.3.1 defaults: video_format 5, limited range, 2 = unspecified
+  bool video_signal_type_present = false, video_full_range = false;
+  int video_format = 5, colour_primaries = 2, transfer_characteristics = 2, matrix_coefficients = 2;
   // sps_range_extension() (HM 16.0: TDecCAVLC.cpp:778-786); tools the device path lacks are refused while parsing
   bool rext_rotation = false, rext_ts_context = false, rext_implicit_rdpcm = false, rext_explicit_rdpcm = false;
   bool rext_persistent_rice = false, rext_intra_smoothing_disabled = false, rext_high_precision_offsets = false;

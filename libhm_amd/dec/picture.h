@@ -136,7 +136,10 @@ struct PicData {
   int home = 0;                      // the context that decoded the picture (Decoder::gpus_) ...
   uint32_t present = 0;              // ... and the contexts that hold its finished samples (bit k: gpus_[k])
   uint64_t submit_seq = 0;           // device submission that last read these arrays
+  int colour[5] = {0, 2, 2, 2, 5};    // VUI of the active SPS: video_full_range_flag, colour_primaries, transfer_characteristics, matrix_coefficients, video_format
   // output side
+  void* owner = nullptr;             // the hmdec::Decoder whose buffer this is (lazy plane download in device-output mode)
+  bool on_device = false;            // submitted, and its device context still exists: the samples can be exported or downloaded
   bool planes_valid = false;
   std::atomic<uint64_t> dl_ticket{0};   // a download of the planes is under way (hmgpu_picture_download_begin): planes_valid once it has been waited for
   HostVec<int16_t> plane[3];
@@ -161,6 +164,7 @@ struct PicData {
   }
   // the device context goes away while the application still holds the picture: the views become copies
   void detach_from_device() {
+    on_device = false;
     release_blob();
     if (!stg) return;
     for (auto* v : {&depth, &tr_idx, &cbf[0], &cbf[1], &cbf[2], &ts[0], &ts[1], &ts[2], &intra_dir[0], &intra_dir[1], &bypass, &ipcm}) v->detach();
@@ -216,7 +220,7 @@ struct PicData {
     std::fill(slice_addr.begin(), slice_addr.end(), -1);
     slices.clear();
     slices.reserve(HMGPU_MAX_SLICES);   // entries are added while a parser thread reads earlier ones: the storage must not move
-    has_pcm = has_bypass = decoded = filtered = planes_valid = false;
+    has_pcm = has_bypass = decoded = filtered = planes_valid = on_device = false;
     level_cursor[0] = level_cursor[1] = level_cursor[2] = 0;
     hash_mismatch = false;
     dl_ticket = 0;

@@ -65,6 +65,13 @@ def lib():
         L.hmdec_picture_hash_sei.argtypes = [C.c_void_p, C.c_void_p]
         L.hmdec_picture_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_picture_conformance_window.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.hmdec_set_device_output.argtypes = [C.c_void_p, C.c_int]
+        L.hmdec_download_bytes.argtypes = [C.c_void_p]
+        L.hmdec_download_bytes.restype = C.c_ulonglong
+        L.hmdec_picture_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.ExportDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                           C.c_int, C.c_void_p]
+        L.hmdec_picture_device.argtypes = [C.c_void_p]
+        L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
         _lib = L
     return _lib
@@ -107,8 +114,9 @@ _DTYPES = {"depth": np.uint8, "part_size": np.int8, "pred_mode": np.int8, "qp": 
 class Picture:
     """a decoded picture handle (valid until the decoder reuses the buffer)"""
 
-    def __init__(self, handle):
+    def __init__(self, handle, ctx=None):
         self.h = handle
+        self.ctx = ctx                            # the decoder (libHMDec_context) the picture came from: export() needs it
 
     @property
     def poc(self):
@@ -177,12 +185,56 @@ class Picture:
         m = lib().hmdec_picture_hash_sei(self.h, d)
         return m, bytes(d)
 
+    @property
+    def device(self):
+        """GPU ordinal that holds the picture's samples (hmdec_picture_device), -1: none"""
+        return lib().hmdec_picture_device(self.h)
+
+    def colour(self):
+        """VUI colour description: dict of full_range, primaries, transfer, matrix, video_format (E.3.1 defaults when absent)"""
+        v = (C.c_int32 * 5)()
+        lib().hmdec_picture_colour(self.h, v)
+        return dict(zip(("full_range", "primaries", "transfer", "matrix", "video_format"), (int(x) for x in v)))
+
+    def export_into(self, desc, ptrs, pitches, on_stream=1, stream=0):
+        """hmdec_picture_export into device memory the caller owns"""
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        st = lib().hmdec_picture_export(self.ctx, self.h, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None))
+        if st != 0:
+            from . import HmgpuError
+            raise HmgpuError(st, "hmdec_picture_export")
+
+    def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False):
+        """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
+        RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
+        crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
+        VUI (the colour policy of libhm_amd.export).  Valid until the next push into the decoder."""
+        from . import export
+        if self.ctx is None:
+            raise RuntimeError("Picture.export: the picture does not know its decoder")
+        g = self.geometry()
+        seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
+        seq.chroma_format = g["chroma_format"]
+        if crop == "conformance":
+            crop = self.conformance_window()
+        elif crop is None:
+            crop = (0, 0, 0, 0)
+        col = self.colour()
+        matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
+        dev = self.device
+        if dev < 0:
+            raise RuntimeError("Picture.export: the picture is not on a device (parse-only, or its sequence has ended)")
+        return export.export_tensors(lambda desc, ptrs, pitches, st: self.export_into(desc, ptrs, pitches, 1, st),
+                                     seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned)
+
 
 class Decoder:
     def __init__(self, parse_only=False, device=0, check_hash=True, max_temporal_layer=-1, threads=1, device_md5=None, devices=None,
-                 packed_input=False):
+                 packed_input=False, device_output=False):
         """devices: GPU ordinals of several device contexts (hmdec_set_devices; the same ordinal twice = two contexts on one GPU).
-        packed_input: 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmdec_set_packed_input)"""
+        packed_input: 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmdec_set_packed_input).
+        device_output: pictures put out stay on the device (hmdec_set_device_output): Picture.export, planes downloaded lazily"""
         self.ctx = lib().libHMDec_new_decoder()
         if not self.ctx:
             raise MemoryError("libHMDec_new_decoder")
@@ -192,6 +244,7 @@ class Decoder:
             lib().hmdec_set_devices(self.ctx, (C.c_int * len(devices))(*devices), len(devices))
         lib().hmdec_set_threads(self.ctx, threads)
         lib().hmdec_set_packed_input(self.ctx, 1 if packed_input else 0)
+        lib().hmdec_set_device_output(self.ctx, 1 if device_output else 0)
         lib().libHMDec_set_SEI_Check(self.ctx, check_hash)
         lib().libHMDec_set_max_temporal_layer(self.ctx, max_temporal_layer)
         if device_md5 is not None:                 # MD5 hash SEIs checked on the device (default: the decoder's hash threads / HMDEC_DEVICE_MD5)
@@ -219,7 +272,7 @@ class Decoder:
 
     def get_picture(self):
         h = lib().libHMDec_get_picture(self.ctx)
-        return Picture(h) if h else None
+        return Picture(h, self.ctx) if h else None
 
     def internal_info(self, pic, kind):
         """libHMDEC_get_internal_info as a list of (x, y, w, h, value, value2)"""
@@ -231,7 +284,7 @@ class Decoder:
 
     def last_decoded(self):
         h = lib().hmdec_last_decoded_picture(self.ctx)
-        return Picture(h) if h else None
+        return Picture(h, self.ctx) if h else None
 
     @property
     def hash_mismatches(self):
@@ -258,6 +311,11 @@ class Decoder:
     def transfer_bytes(self):
         return int(lib().hmdec_transfer_bytes(self.ctx))
 
+    @property
+    def download_bytes(self):
+        """plane bytes copied device -> host so far (hmdec_download_bytes)"""
+        return int(lib().hmdec_download_bytes(self.ctx))
+
     def decode_stream(self, stream, on_decoded=None, on_output=None):
         """libHM's documented loop (libHMDecoder.h:36-77) over an Annex B stream"""
         nals = split_nal_units(stream)
@@ -276,5 +334,22 @@ class Decoder:
                             break
                         if on_output:
                             on_output(p)
+                if not new_pic:
+                    break
+
+    def frames(self, stream, **export_kw):
+        """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
+        of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's."""
+        nals = split_nal_units(stream)
+        for i, nal in enumerate(nals):
+            eof = i == len(nals) - 1
+            while True:
+                new_pic, check = self.push(nal, eof)
+                if check:
+                    while True:
+                        p = self.get_picture()
+                        if p is None:
+                            break
+                        yield p.poc, p.export(**export_kw)
                 if not new_pic:
                     break
