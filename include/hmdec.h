@@ -87,10 +87,14 @@ void hmdec_set_packed_input(libHMDec_context* ctx, int on);
  * HMGPU_EINVAL.  hmdec_download_bytes: plane bytes copied device -> host so far, for any reason (output, host hash checks). */
 #ifndef HMGPU_H
 typedef struct hmgpu_export_desc hmgpu_export_desc;
+typedef struct hmgpu_export_scale hmgpu_export_scale;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
                          const int64_t pitch_bytes[3], int on_stream, void* stream);
+/* the same with scaling (hmgpu_picture_export_scaled), under the same rules */
+int hmdec_picture_export_scaled(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

@@ -299,6 +299,55 @@ hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_expo
  * is enqueued. */
 hmgpu_status hmgpu_picture_export(hmgpu_ctx* ctx, hmgpu_pic pic, const hmgpu_export_desc* desc, void* const dst[3],
                                   const int64_t pitch_bytes[3], int32_t on_stream, void* stream);
+/* Scaled export: the unscaled export of the same descriptor resized to scale->width x scale->height.
+ *   s = what hmgpu_picture_export writes for `desc` (crop window, layout, matrix, output depth D), before the msb_aligned shift
+ *   each output plane is resampled separably, horizontally first, from its own cropped source plane; only samples inside the crop
+ *   window contribute.  RGB: three width x height planes (chroma replicated to the luma grid before the matrix, as unscaled).
+ *   PLANAR / SEMIPLANAR: Y width x height, Cb and Cr (width >> csx) x (height >> csy), each from its cropped plane with half-sample
+ *   centres (align_corners=False); width / height must be whole chroma samples (else HMGPU_EINVAL).  4:0:0: Y only (YUV layouts).
+ * One table per plane class (0: luma / RGB planes, 1: chroma planes) and axis (0: horizontal, 1: vertical): for output index i the
+ * first source index first[i] (in the cropped plane), count[i] taps and int16 weights w[i][0 .. count[i]) in Q14 summing to 16384.
+ * The host derives them in double precision from the weights torch uses (in = source size, out = output size, scale = in / out):
+ *   HMGPU_SCALE_NEAREST   mode="nearest-exact": one tap at min(floor((2i + 1) * in / (2 * out)), in - 1), computed exactly in
+ *                         integers (torch forms (i + 0.5) * scale with a float32 scale and can land one below where that product
+ *                         is a whole number: an exact tie)
+ *   HMGPU_SCALE_BILINEAR  mode="bilinear", antialias=True, align_corners=False: PIL's triangle, support 1 widened by scale when scale > 1
+ *   HMGPU_SCALE_BICUBIC   mode="bicubic", antialias=True, align_corners=False: Keys' cubic with a = -0.5, support 2 widened the same way
+ *                         (centre (i + 0.5) * scale; taps int(centre - support + 0.5) .. int(centre + support + 0.5) - 1, clamped to
+ *                         the plane, weight f((j - centre + 0.5) / max(scale, 1)), normalised to sum 1)
+ *   HMGPU_SCALE_AREA      mode="area" (adaptive average): taps floor(i * in / out) .. ceil((i + 1) * in / out) - 1, equal weights
+ * Q14 by largest remainders: each weight times 16384 is rounded down, then the weights with the largest remainders (the lower index
+ * first on a tie) gain one unit each until the row sums to 16384, so every weight is within one unit of its exact value; zero weights
+ * at either end are dropped.  At equal size every table is the identity, so a scaled export at the crop's own size equals the unscaled one.
+ * Integer arithmetic, 32-bit, E = 16 - D fractional bits kept between the passes (hmgpu_export_plan.coef[11]), D the output depth of the
+ * plane (RGB: bit_depth[0]), except that E is one value per export: for the YUV layouts with different luma and chroma output depths
+ * E = 16 - max(D luma, D chroma), while each plane is clipped to its own D:
+ *   t = (sum_j wx[j] * s[y][first + j] + (1 << (13 - E))) >> (14 - E)          per source row y
+ *   o = Clip3(0, 2^D - 1, (sum_k wy[k] * t[first + k] + (1 << (13 + E))) >> (14 + E)), then << (16 - D) when msb_aligned
+ * (>> is an arithmetic shift: bicubic weights are negative in places).  Limits: per axis and plane class, in <= 32 * out (a 32x
+ * reduction) and out <= 8 * in (an 8x enlargement), and at most 16384 output samples per side; outside them HMGPU_EUNSUPPORTED.
+ * Within them no sum overflows for any input at any D of 8 .. 16 (the largest row sums of positive and of negative weights bound
+ * every sum; the host evaluates that bound for the tables of each shape and refuses, HMGPU_EUNSUPPORTED, one that would overflow).  The plan is that of the unscaled export with every plane's size replaced and
+ * coef[11] E, coef[12] / coef[13] the widest horizontal / vertical table (taps); coef[0..10] keep their RGB meaning. */
+enum { HMGPU_SCALE_NEAREST = 0, HMGPU_SCALE_BILINEAR = 1, HMGPU_SCALE_BICUBIC = 2, HMGPU_SCALE_AREA = 3 };
+typedef struct hmgpu_export_scale {
+  int32_t width, height;       /* output size in luma samples (RGB: of every plane) */
+  int32_t filter;              /* HMGPU_SCALE_* */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_export_scale;
+/* validates and reports what a scaled export writes; host code, no device needed */
+hmgpu_status hmgpu_export_scaled_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          hmgpu_export_plan* out);
+/* the integers of one table (chroma 0 / 1: plane class, axis 0 / 1: horizontal / vertical), host code: first[out], count[out],
+ * weights[out][max_taps] (row i zero beyond count[i]); max_taps below the widest table gives HMGPU_EINVAL.  A 4:0:0 sequence, or
+ * the RGB layout, has no chroma class (HMGPU_EINVAL). */
+hmgpu_status hmgpu_export_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                     int32_t chroma, int32_t axis, int32_t max_taps, int32_t* first, int32_t* count, int16_t* weights);
+/* hmgpu_picture_export with scaling: the same validation (destination spans, the stream's device) and the same stream ordering; the
+ * tables live in device memory of the context, cached per shape (a repeated shape enqueues no copy; a slot is reused only after the
+ * last export that read it has finished). */
+hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* ctx, hmgpu_pic pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->

@@ -82,6 +82,12 @@ def lib():
         L.hmgpu_export_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportPlan)]
         L.hmgpu_picture_export.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                            C.c_int32, C.c_void_p]
+        L.hmgpu_export_scaled_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportPlan)]
+        L.hmgpu_export_scale_taps.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale), C.c_int32,
+                                              C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]
+        L.hmgpu_picture_export_scaled.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -144,6 +150,33 @@ def export_plan(seq, desc):
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_plan_for")
     return plan
+
+
+def export_scaled_plan(seq, desc, scale):
+    """what a scaled export writes (hmgpu_export_scaled_plan_for: host code, no GPU)"""
+    plan = abi.ExportPlan()
+    st = lib().hmgpu_export_scaled_plan_for(C.byref(seq), C.byref(desc), C.byref(scale), C.byref(plan))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_export_scaled_plan_for")
+    return plan
+
+
+def export_scale_taps(seq, desc, scale, chroma, axis):
+    """one resampling table of a scaled export (hmgpu_export_scale_taps): (first, count, weights [out, taps]) as numpy arrays"""
+    plan = export_scaled_plan(seq, desc, scale)
+    taps = max(1, plan.coef[12 + axis])
+    n = (scale.width, scale.height)[axis]
+    if chroma:
+        fmt = seq.chroma_format
+        n >>= (0 if fmt == 3 else 1) if axis == 0 else (1 if fmt in (0, 1) else 0)
+    first, count = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    w = np.zeros((n, taps), np.int16)
+    st = lib().hmgpu_export_scale_taps(C.byref(seq), C.byref(desc), C.byref(scale), chroma, axis, taps, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       w.ctypes.data_as(C.POINTER(C.c_int16)))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_export_scale_taps")
+    return first, count, w
 
 
 def packed_max_bytes(seq):
@@ -278,18 +311,24 @@ class Context:
         self._chk(lib().hmgpu_picture_download(self._h, pic, ptrs, strides), "hmgpu_picture_download")
         return planes
 
-    def export_into(self, pic, desc, ptrs, pitches, on_stream=0, stream=0):
-        """hmgpu_picture_export into device memory the caller owns: ptrs / pitches (bytes) per plane"""
+    def export_into(self, pic, desc, ptrs, pitches, on_stream=0, stream=0, scale=None):
+        """hmgpu_picture_export (scale: an abi.ExportScale, hmgpu_picture_export_scaled) into device memory the caller owns:
+        ptrs / pitches (bytes) per plane"""
         p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
         q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        self._chk(lib().hmgpu_picture_export(self._h, pic, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmgpu_picture_export")
+        if scale is None:
+            self._chk(lib().hmgpu_picture_export(self._h, pic, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmgpu_picture_export")
+        else:
+            self._chk(lib().hmgpu_picture_export_scaled(self._h, pic, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None)),
+                      "hmgpu_picture_export_scaled")
 
-    def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True):
+    def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
+               size=None, filter="bilinear", out=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
-        (on_stream) or on the context's own"""
+        (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it"""
         from . import export
-        return export.export_tensors(lambda desc, ptrs, pitches, st: self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st),
-                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream)
+        return export.export_tensors(lambda desc, scale, ptrs, pitches, st: self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st, scale),
+                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter, out)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

@@ -98,6 +98,19 @@ class ExportPlan(C.Structure):
                 ("coef", C.c_int32 * 16)]
 
 
+SCALE_NEAREST, SCALE_BILINEAR, SCALE_BICUBIC, SCALE_AREA = 0, 1, 2, 3
+
+
+class ExportScale(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def make_export_scale(width, height, filter=SCALE_BILINEAR):
+    s = ExportScale()
+    s.width, s.height, s.filter = width, height, filter
+    return s
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

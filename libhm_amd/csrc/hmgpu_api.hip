@@ -13,6 +13,11 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <cmath>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <tuple>
 #include <new>
 #include <thread>
 #include <unordered_map>
@@ -121,6 +126,20 @@ struct hmgpu_ctx {
   uint64_t hash_seq = 0, hash_launched = 0, hash_launches = 0;
   hipEvent_t xfer_ev[2] = {};            // hmgpu_picture_transfer: source ready / copy done
   hipEvent_t exp_ev[2] = {};             // hmgpu_picture_export on a caller's stream: picture ready / export done (created when first used)
+  // hmgpu_picture_export_scaled: resampling tables in device memory, one slot per export shape, least recently used slot reused
+  struct ScaleSlot {
+    int32_t key[8] = {};                 // crop[4], output width / height, filter, RGB
+    bool valid = false, pending = false; // pending: `done` stands for an export that read the slot
+    uint64_t used = 0;
+    char* dev = nullptr;                 // the tables (ScaleTable)
+    char* host = nullptr;                // page-locked: the same bytes on their way over
+    size_t cap = 0;
+    hipEvent_t done = nullptr;           // recorded behind the last export that read the slot
+    ScaleClass cls[2];
+  };
+  static constexpr int kScaleSlots = 8;
+  ScaleSlot scale_slot[kScaleSlots];
+  uint64_t scale_tick = 0;
   uint64_t xfer_bytes = 0;
   uint32_t* dl_fault = nullptr;        // [32] page-locked: the picture's fault word (k_intra's bounded spin) as it stood behind the copies of ticket t
   std::vector<int> touched;            // pictures the entry point under way has enqueued work on, in any role (commit_use)
@@ -739,6 +758,11 @@ void hmgpu_destroy(hmgpu_ctx* c) {
   if (c->hash_dev) (void)hipFree(c->hash_dev);
   for (int k = 0; k < 2; k++) if (c->xfer_ev[k]) hipEventDestroy(c->xfer_ev[k]);
   for (int k = 0; k < 2; k++) if (c->exp_ev[k]) hipEventDestroy(c->exp_ev[k]);
+  for (auto& sl : c->scale_slot) {
+    if (sl.done) hipEventDestroy(sl.done);
+    if (sl.dev) (void)hipFree(sl.dev);
+    if (sl.host) (void)hipHostFree(sl.host);
+  }
   if (c->hash_host) (void)hipHostFree(c->hash_host);
   for (int k = 0; k < 2; k++) if (c->lane_ev[k]) hipEventDestroy(c->lane_ev[k]);
   delete c;
@@ -1212,6 +1236,51 @@ static bool device_span_ok(const void* p, size_t bytes, int device) {
   return q >= b && q - b + bytes <= size;
 }
 
+// every plane's destination inside one allocation of the context's device; vec is cleared unless every plane may take 4-sample stores
+static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& plan, int B, void* const dst[3], const int64_t pitch_bytes[3],
+                                  bool* vec) {
+  for (int k = 0; k < plan.planes; k++) {
+    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k], c->device)) return HMGPU_EINVAL;
+    *vec = *vec && ((uintptr_t)dst[k] % (4 * B)) == 0 && pitch_bytes[k] % (4 * B) == 0;
+  }
+  return HMGPU_OK;
+}
+
+// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device
+static hmgpu_status export_stream(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
+  *hs = c->stream;
+  if (!on_stream) return HMGPU_OK;
+  *hs = (hipStream_t)stream;
+  if (*hs) {
+    hipDevice_t dev = -1;
+    if (hipStreamGetDevice(*hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
+    if ((int)dev != c->device) return HMGPU_EINVAL;
+  }
+  for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
+  return HMGPU_OK;
+}
+
+static hmgpu_status export_begin(hmgpu_ctx* c, int32_t on_stream, hipStream_t hs) {
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                 // behind everything enqueued for the picture ...
+    HIP_TRY(c, hipStreamWaitEvent(hs, c->exp_ev[0], 0));                 // ... and behind what is already on the caller's stream
+  }
+  return HMGPU_OK;
+}
+
+// after the export's launch
+static hmgpu_status export_end(hmgpu_ctx* c, hmgpu_pic pic, int32_t on_stream, hipStream_t hs) {
+  HIP_TRY(c, hipGetLastError());
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
+  }
+  touch(c, pic);
+  commit_use(c);
+  return HMGPU_OK;
+}
+
 hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
                                   int32_t on_stream, void* stream) {
   if (!c || !valid_pic(c, pic) || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
@@ -1220,21 +1289,9 @@ hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_expor
   hipSetDevice(c->device);
   const int B = d->bytes_per_sample;
   bool vec = (d->crop[0] & 3) == 0;
-  for (int k = 0; k < plan.planes; k++) {
-    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    if (!device_span_ok(dst[k], (size_t)pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k], c->device)) return HMGPU_EINVAL;
-    vec = vec && ((uintptr_t)dst[k] % (4 * B)) == 0 && pitch_bytes[k] % (4 * B) == 0;
-  }
+  { const hmgpu_status st = export_dst_ok(c, plan, B, dst, pitch_bytes, &vec); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
-  if (on_stream) {
-    hs = (hipStream_t)stream;
-    if (hs) {
-      hipDevice_t dev = -1;
-      if (hipStreamGetDevice(hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
-      if ((int)dev != c->device) return HMGPU_EINVAL;
-    }
-    for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
-  }
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const Picture& p = c->pics[pic];
   int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
   ExportArgs a;
@@ -1256,19 +1313,355 @@ hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_expor
   a.vec = vec ? 1 : 0;
   for (int k = 0; k < 3; k++) { a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr; a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0; }
   memcpy(a.coef, plan.coef, sizeof(a.coef));
-  if (on_stream) {
-    HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                 // behind everything enqueued for the picture ...
-    HIP_TRY(c, hipStreamWaitEvent(hs, c->exp_ev[0], 0));                 // ... and behind what is already on the caller's stream
-  }
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
   launch_export(a, hs);
-  HIP_TRY(c, hipGetLastError());
-  if (on_stream) {
-    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
+  return export_end(c, pic, on_stream, hs);
+}
+
+// ------------------------------------------------------------------------------------------------ scaled export (k_export_scale.hip)
+namespace {
+
+// one resampling table: `in` source samples to `out` outputs (include/hmgpu.h "scaled export")
+struct ScaleTab {
+  int taps = 0;                        // widest row
+  std::vector<int32_t> first, count;
+  std::vector<int16_t> w;              // [out][taps]
+  long long pos = 0, neg = 0;          // the largest sum of the positive / of the magnitudes of the negative weights of a row
+};
+
+double scale_filter(int filter, double x) {
+  x = std::fabs(x);
+  if (filter == HMGPU_SCALE_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  const double a = -0.5;                                         // Keys, as PIL and torch's antialiased bicubic
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+  if (x < 2.0) return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a;
+  return 0.0;
+}
+
+std::shared_ptr<const ScaleTab> build_scale_tab(int in, int out, int filter) {
+  auto t = std::make_shared<ScaleTab>();
+  std::vector<std::vector<int>> rows((size_t)out);
+  t->first.resize((size_t)out);
+  t->count.resize((size_t)out);
+  std::vector<double> w;
+  for (int i = 0; i < out; i++) {
+    int lo = 0;
+    w.clear();
+    if (filter == HMGPU_SCALE_NEAREST) {                         // nearest-exact, the source index exact (no rounding at ties)
+      lo = (int)std::min((2LL * i + 1) * in / (2LL * out), (long long)in - 1);
+      w.push_back(1.0);
+    } else if (filter == HMGPU_SCALE_AREA) {                     // adaptive average pooling
+      lo = (int)((long long)i * in / out);
+      const int hi = (int)(((long long)(i + 1) * in + out - 1) / out);
+      w.assign((size_t)(hi - lo), 1.0 / (hi - lo));
+    } else {                                                     // torch's antialiased interpolation (PIL's weights)
+      const double scale = (double)in / out, support = (filter == HMGPU_SCALE_BILINEAR ? 1.0 : 2.0) * (scale >= 1.0 ? scale : 1.0);
+      const double centre = scale * (i + 0.5), inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+      lo = (int)std::max((long long)(centre - support + 0.5), 0LL);
+      const int hi = (int)std::min((long long)(centre + support + 0.5), (long long)in);
+      double total = 0;
+      for (int j = lo; j < hi; j++) { w.push_back(scale_filter(filter, (j - centre + 0.5) * inv)); total += w.back(); }
+      if (total != 0.0) for (double& v : w) v /= total;
+    }
+    // Q14 by largest remainders: every weight rounded down, then one unit each to the largest remainders (lower index first on a tie)
+    // until the row sums to 16384, so that every weight is within one unit of its exact value
+    std::vector<int>& q = rows[(size_t)i];
+    std::vector<std::pair<double, int>> rem;
+    int sum = 0;
+    for (size_t j = 0; j < w.size(); j++) {
+      const double v = w[j] * 16384.0, f = std::floor(v);
+      q.push_back((int)f);
+      sum += q.back();
+      rem.emplace_back(-(v - f), (int)j);
+    }
+    std::sort(rem.begin(), rem.end());
+    for (int u = 0; u < 16384 - sum; u++) q[(size_t)rem[(size_t)u % rem.size()].second] += 1;
+    size_t b = 0, e = q.size();
+    while (q[b] == 0) b++;
+    while (q[e - 1] == 0) e--;
+    q = std::vector<int>(q.begin() + (ptrdiff_t)b, q.begin() + (ptrdiff_t)e);
+    t->first[(size_t)i] = lo + (int)b;
+    t->count[(size_t)i] = (int)q.size();
+    t->taps = std::max(t->taps, (int)q.size());
+    long long p = 0, n = 0;
+    for (int v : q) (v > 0 ? p : n) += std::llabs(v);
+    t->pos = std::max(t->pos, p);
+    t->neg = std::max(t->neg, n);
   }
-  touch(c, pic);
-  commit_use(c);
+  t->w.assign((size_t)out * t->taps, 0);
+  for (int i = 0; i < out; i++)
+    for (size_t j = 0; j < rows[(size_t)i].size(); j++) t->w[(size_t)i * t->taps + j] = (int16_t)rows[(size_t)i][j];
+  return t;
+}
+
+// process-wide: the tables of recent shapes (a plan or an export of a repeated shape derives nothing)
+std::shared_ptr<const ScaleTab> scale_tab(int in, int out, int filter) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, std::shared_ptr<const ScaleTab>> tabs;
+  const auto key = std::make_tuple(in, out, filter);
+  {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = tabs.find(key);
+    if (it != tabs.end()) return it->second;
+  }
+  auto t = build_scale_tab(in, out, filter);
+  std::lock_guard<std::mutex> g(mu);
+  if (tabs.size() >= 64) tabs.clear();
+  tabs[key] = t;
+  return t;
+}
+
+// everything a scaled export of one shape needs on the host: the plan, per plane class its tables
+struct ScaleShape {
+  int classes = 1;                                              // 2: YUV with chroma
+  int in[2][2] = {}, out[2][2] = {};                             // [class][axis]
+  std::shared_ptr<const ScaleTab> tab[2][2];
+  int depth[2] = {8, 8};                                         // output depth per class
+};
+
+// t = (h + 2^(13-E)) >> (14-E), o = (sum wy t + 2^(13+E)) >> (14+E): no 32-bit sum overflows for samples 0 .. 2^D - 1
+bool scale_sums_fit(const ScaleTab& x, const ScaleTab& y, int D, int E) {
+  const long long V = (1LL << D) - 1, r1 = 1LL << (13 - E), r2 = 1LL << (13 + E);
+  const long long hmax = x.pos * V + r1, hmin = -x.neg * V + r1;
+  if (hmax > INT32_MAX || hmin < INT32_MIN) return false;
+  const long long tmax = hmax >> (14 - E), tmin = hmin >> (14 - E);       // (arithmetic shifts: floor)
+  const long long vmax = y.pos * tmax + y.neg * std::max(-tmin, 0LL) + r2;
+  const long long vmin = -(y.pos * std::max(-tmin, 0LL) + y.neg * tmax) + r2;
+  return vmax <= INT32_MAX && vmin >= INT32_MIN;
+}
+
+hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, hmgpu_export_plan* out,
+                         ScaleShape* shape) {
+  if (!seq || !d || !sc || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+  if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+  hmgpu_export_plan base;
+  { const hmgpu_status st = hmgpu_export_plan_for(seq, d, &base); if (st != HMGPU_OK) return st; }
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB, chroma = !rgb && base.planes > 1;
+  const int fmt = seq->chroma_format, csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
+  if (chroma && ((sc->width & ((1 << csx) - 1)) || (sc->height & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  ScaleShape s;
+  s.classes = chroma ? 2 : 1;
+  const int W = base.width[0], H = base.height[0];
+  const int bdY = seq->bit_depth_luma, bdC = seq->bit_depth_chroma;
+  s.depth[0] = d->bit_depth[0] ? d->bit_depth[0] : bdY;
+  s.depth[1] = d->bit_depth[1] ? d->bit_depth[1] : bdC;
+  for (int k = 0; k < s.classes; k++) {
+    const int sx = k ? csx : 0, sy = k ? csy : 0;
+    s.in[k][0] = W >> sx; s.in[k][1] = H >> sy;
+    s.out[k][0] = sc->width >> sx; s.out[k][1] = sc->height >> sy;
+    for (int ax = 0; ax < 2; ax++) {
+      const long long i = s.in[k][ax], o = s.out[k][ax];
+      if (o > 16384 || i > 32 * o || o > 8 * i) return HMGPU_EUNSUPPORTED;
+    }
+  }
+  const int D = rgb ? s.depth[0] : chroma ? std::max(s.depth[0], s.depth[1]) : s.depth[0];
+  const int E = 16 - D;
+  int taps[2] = {0, 0};
+  for (int k = 0; k < s.classes; k++) {
+    for (int ax = 0; ax < 2; ax++) {
+      s.tab[k][ax] = scale_tab(s.in[k][ax], s.out[k][ax], sc->filter);
+      taps[ax] = std::max(taps[ax], s.tab[k][ax]->taps);
+    }
+    if (!scale_sums_fit(*s.tab[k][0], *s.tab[k][1], rgb ? s.depth[0] : s.depth[k], E)) return HMGPU_EUNSUPPORTED;
+  }
+  *out = base;
+  for (int p = 0; p < out->planes; p++) {
+    const int k = rgb || p == 0 ? 0 : 1;
+    const int w = k ? sc->width >> csx : sc->width, h = k ? sc->height >> csy : sc->height;
+    out->row_bytes[p] = out->row_bytes[p] / out->width[p] * w;
+    out->width[p] = w; out->height[p] = h;
+  }
+  out->coef[11] = E; out->coef[12] = taps[0]; out->coef[13] = taps[1];
+  if (shape) *shape = s;
   return HMGPU_OK;
+}
+
+}  // namespace
+
+hmgpu_status hmgpu_export_scaled_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          hmgpu_export_plan* out) {
+  return scaled_plan(seq, d, sc, out, nullptr);
+}
+
+hmgpu_status hmgpu_export_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, int32_t chroma,
+                                     int32_t axis, int32_t max_taps, int32_t* first, int32_t* count, int16_t* weights) {
+  if (!first || !count || !weights || (chroma != 0 && chroma != 1) || (axis != 0 && axis != 1)) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  ScaleShape s;
+  { const hmgpu_status st = scaled_plan(seq, d, sc, &plan, &s); if (st != HMGPU_OK) return st; }
+  if (chroma >= s.classes) return HMGPU_EINVAL;
+  const ScaleTab& t = *s.tab[chroma][axis];
+  if (max_taps < t.taps) return HMGPU_EINVAL;
+  const int n = s.out[chroma][axis];
+  memcpy(first, t.first.data(), sizeof(int32_t) * (size_t)n);
+  memcpy(count, t.count.data(), sizeof(int32_t) * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    memset(weights + (size_t)i * max_taps, 0, sizeof(int16_t) * (size_t)max_taps);
+    memcpy(weights + (size_t)i * max_taps, t.w.data() + (size_t)i * t.taps, sizeof(int16_t) * (size_t)t.taps);
+  }
+  return HMGPU_OK;
+}
+
+namespace {
+
+// tile of one plane class (ScaleClass): wide enough to share source samples, small enough to give the GPU work for every CU, and the
+// LDS of a pass (C channels: 16-bit staged samples + 32-bit horizontal sums) within kScaleLdsBytes
+struct ScaleTiles { int tw, th, rows, cap, tiles_x, tiles_y; std::vector<int32_t> span[2]; };
+
+std::vector<int32_t> scale_spans(const ScaleTab& t, int n, int tile) {
+  std::vector<int32_t> sp;
+  for (int i0 = 0; i0 < n; i0 += tile) {
+    int lo = INT32_MAX, hi = 0;
+    for (int i = i0; i < std::min(n, i0 + tile); i++) { lo = std::min(lo, t.first[(size_t)i]); hi = std::max(hi, t.first[(size_t)i] + t.count[(size_t)i]); }
+    sp.push_back(lo); sp.push_back(hi);
+  }
+  return sp;
+}
+
+ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int outh, int x0, int C) {
+  const int G = C == 2 ? 4 : 8;
+  ScaleTiles z;
+  z.tw = 128;
+  while (z.tw > 4 && z.tw / 2 >= outw) z.tw /= 2;
+  z.th = 1024 / z.tw;
+  while (z.th > 1 && z.th / 2 >= outh) z.th /= 2;
+  auto blocks = [&]() { return (long long)((outw + z.tw - 1) / z.tw) * ((outh + z.th - 1) / z.th); };
+  while (blocks() < 1024 && z.tw * z.th > 64) {      // (large reductions: small tiles, or a few workgroups would do all the work)
+    if (z.th >= z.tw / 4 && z.th > 2) z.th /= 2;
+    else if (z.tw > 16) z.tw /= 2;
+    else break;
+  }
+  for (;;) {
+    z.span[0] = scale_spans(tx, outw, z.tw);
+    z.cap = 0;
+    for (size_t i = 0; i < z.span[0].size(); i += 2) {
+      const int a = (x0 + z.span[0][i]) & ~(G - 1), b = (x0 + z.span[0][i + 1] + G - 1) & ~(G - 1);
+      z.cap = std::max(z.cap, b - a);
+    }
+    z.cap = (z.cap + 7) & ~7;
+    z.rows = std::min(1024 / z.tw, kScaleLdsBytes / (C * (2 * z.cap + 4 * z.tw)));
+    if ((z.rows >= 4 || z.tw <= 16) && z.rows >= 1) break;
+    z.tw /= 2;
+  }
+  z.span[1] = scale_spans(ty, outh, z.th);
+  z.tiles_x = (outw + z.tw - 1) / z.tw;
+  z.tiles_y = (outh + z.th - 1) / z.th;
+  return z;
+}
+
+// the slot that holds the tables of `key`: found, or filled (least recently used slot) with a copy enqueued on hs
+hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s, bool rgb, int x0c[2], hipStream_t hs, hmgpu_ctx::ScaleSlot** out) {
+  hmgpu_ctx::ScaleSlot* slot = nullptr;
+  for (auto& sl : c->scale_slot)
+    if (sl.valid && !memcmp(sl.key, key, sizeof(sl.key))) { slot = &sl; break; }
+  if (!slot) {
+    slot = &c->scale_slot[0];
+    for (auto& sl : c->scale_slot) {
+      if (!sl.valid) { slot = &sl; break; }
+      if (sl.used < slot->used) slot = &sl;
+    }
+    if (slot->pending) HIP_TRY(c, hipEventSynchronize(slot->done));   // an export in flight still reads it
+    slot->valid = slot->pending = false;
+    // layout: per class and axis first, count, span, weights (tap-major), each 256-byte aligned
+    ScaleTiles z[2];
+    size_t off[2][2][4], bytes = 0;
+    for (int k = 0; k < s.classes; k++) {
+      const int C = rgb ? 3 : k ? 2 : 1;
+      z[k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], x0c[k], C);
+      for (int ax = 0; ax < 2; ax++) {
+        const size_t n = (size_t)s.out[k][ax], sizes[4] = {4 * n, 4 * n, 4 * z[k].span[ax].size(), 2 * n * (size_t)s.tab[k][ax]->taps};
+        for (int f = 0; f < 4; f++) { off[k][ax][f] = bytes; bytes += align_up(sizes[f], 256); }
+      }
+    }
+    if (bytes > slot->cap) {
+      if (slot->dev) HIP_TRY(c, hipFree(slot->dev));
+      if (slot->host) HIP_TRY(c, hipHostFree(slot->host));
+      slot->dev = slot->host = nullptr;
+      slot->cap = 0;
+      HIP_TRY(c, hipMalloc(&slot->dev, bytes));
+      HIP_TRY(c, hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
+      slot->cap = bytes;
+    }
+    if (!slot->done) HIP_TRY(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    for (int k = 0; k < s.classes; k++) {
+      ScaleClass& cl = slot->cls[k];
+      memset(&cl, 0, sizeof(cl));
+      for (int ax = 0; ax < 2; ax++) {
+        const ScaleTab& t = *s.tab[k][ax];
+        const int n = s.out[k][ax];
+        memcpy(slot->host + off[k][ax][0], t.first.data(), 4 * (size_t)n);
+        memcpy(slot->host + off[k][ax][1], t.count.data(), 4 * (size_t)n);
+        memcpy(slot->host + off[k][ax][2], z[k].span[ax].data(), 4 * z[k].span[ax].size());
+        int16_t* w = reinterpret_cast<int16_t*>(slot->host + off[k][ax][3]);
+        for (int j = 0; j < t.taps; j++)
+          for (int i = 0; i < n; i++) w[(size_t)j * n + i] = t.w[(size_t)i * t.taps + j];
+        ScaleTable& d = ax ? cl.ty : cl.tx;
+        d.first = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][0]);
+        d.count = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][1]);
+        d.span = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][2]);
+        d.w = reinterpret_cast<const int16_t*>(slot->dev + off[k][ax][3]);
+        d.n = n;
+      }
+      cl.tw = z[k].tw; cl.th = z[k].th; cl.rows = z[k].rows; cl.span_cap = z[k].cap;
+      cl.tiles_x = z[k].tiles_x; cl.blocks = z[k].tiles_x * z[k].tiles_y;
+    }
+    HIP_TRY(c, hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, hs));
+    memcpy(slot->key, key, sizeof(slot->key));
+    slot->valid = true;
+  }
+  slot->used = ++c->scale_tick;
+  *out = slot;
+  return HMGPU_OK;
+}
+
+}  // namespace
+
+hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
+  if (!c || !valid_pic(c, pic) || !d || !sc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  ScaleShape s;
+  { const hmgpu_status st = scaled_plan(&c->seq, d, sc, &plan, &s); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  const int B = d->bytes_per_sample;
+  bool vec = true;
+  { const hmgpu_status st = export_dst_ok(c, plan, B, dst, pitch_bytes, &vec); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
+  const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, rgb ? 1 : 0};
+  int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
+  hmgpu_ctx::ScaleSlot* slot = nullptr;
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, hs, &slot); if (st != HMGPU_OK) return st; }
+  const Picture& p = c->pics[pic];
+  int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+  ScaleArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < s.classes; k++) {
+    a.cls[k] = slot->cls[k];
+    a.cls[k].src = src[k];
+    a.cls[k].pitch = c->pitch[k];
+    a.cls[k].x0 = x0c[k];
+    a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
+  }
+  a.c = src[1]; a.pitch_c = c->pitch[1];
+  a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
+  const int obY = s.depth[0], obC = rgb ? obY : s.depth[1];
+  a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
+  a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
+  a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
+  a.e = plan.coef[11];
+  a.vec = vec ? 1 : 0;
+  for (int k = 0; k < 3; k++) { a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr; a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0; }
+  memcpy(a.coef, plan.coef, sizeof(a.coef));
+  launch_export_scaled(a, d->layout, B, hs);
+  HIP_TRY(c, hipEventRecord(slot->done, hs));
+  slot->pending = true;
+  return export_end(c, pic, on_stream, hs);
 }
 
 // slice table entry of one slice (validation, SliceDev, scaling lists): the part of a slice call that does not depend on CTUs

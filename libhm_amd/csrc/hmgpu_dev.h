@@ -311,6 +311,40 @@ struct ExportArgs {
   int32_t coef[16];                // hmgpu_export_plan.coef
 };
 void launch_export(const ExportArgs& a, hipStream_t s);
+// scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
+// memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
+// tap-major (w[tap * n + i], zero beyond count[i])
+struct ScaleTable {
+  const int32_t* first;
+  const int32_t* count;
+  const int32_t* span;
+  const int16_t* w;
+  int32_t n;                       // output samples along the axis
+};
+constexpr int kScaleLdsBytes = 40960;   // LDS of one workgroup: four share a CU
+struct ScaleClass {                // one plane class: 0 = luma (YUV) or RGB, 1 = the chroma pair (YUV)
+  ScaleTable tx, ty;
+  int32_t tw, th;                  // tile: output columns (4 .. 128, a power of two) x output rows, tw / 4 * th <= 256
+  int32_t rows;                    // source rows per pass through LDS (<= 1024 / tw)
+  int32_t span_cap;                // LDS samples per row and channel: the widest source span of a tile in 16-byte groups
+  int32_t tiles_x, blocks;         // tiles per row, workgroups of the class
+  int32_t x0, y0;                  // crop origin in the class's plane (samples)
+  const int16_t* src;              // sample (0, 0) of the class's plane (chroma: Cb in the pair plane)
+  int32_t pitch;                   // int16 elements
+};
+struct ScaleArgs {
+  ScaleClass cls[2];
+  const int16_t* c;                // RGB: chroma sample (0, 0) (Cb) in the pair plane, rows pitch_c apart
+  int32_t pitch_c;
+  int32_t mono, csx, csy;
+  int32_t sh[2], maxv[2], msb[2];  // bit-depth rule per channel type (as ExportArgs); RGB: maxv[0] = coef[9]
+  int32_t e;                       // fractional bits kept between the passes (hmgpu_export_plan.coef[11])
+  int32_t vec;                     // every group of 4 output samples may be one 4- or 8-byte store (alignment of dst and pitches)
+  uint8_t* dst[3];
+  int64_t pitch[3];                // bytes
+  int32_t coef[16];                // hmgpu_export_plan.coef
+};
+void launch_export_scaled(const ScaleArgs& a, int layout, int bytes, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

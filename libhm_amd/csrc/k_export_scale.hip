@@ -1,0 +1,218 @@
+// k_export_scale.hip -- scaled device export (hmgpu_picture_export_scaled, include/hmgpu.h "scaled export"): a finished picture
+// converted as k_export.hip converts it and resized in the same pass, horizontally then vertically, with the host's Q14 tables.
+//
+// One workgroup of 256 lanes owns a tile of tw x th outputs of one plane class (RGB: R, G and B together; YUV: Y, or Cb and Cr
+// together).  It walks the tile's source rows in passes of `rows` rows through LDS:
+//   1. the pass's source rows, over the tile's source span, are read once with 16-byte loads (8 luma samples or 4 CbCr pairs) and
+//      converted to output code values (the bit-depth rule, or the RGB matrix) into LDS as 16-bit samples;
+//   2. the horizontal taps turn them into t values, one tile column per lane and up to four rows per lane (a weight is loaded once for
+//      its rows), into LDS as 32-bit values;
+//   3. each lane adds the rows of the pass that fall in the vertical windows of its four outputs (four adjacent columns of one row)
+//      to sums it keeps in registers.
+// After the last pass the sums are rounded, clipped and stored, 4 or 8 bytes per plane and lane where aligned.  No intermediate
+// leaves the workgroup.  One instance per layout and container size; the class, and the channels with it, is uniform per workgroup.
+// Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
+// margin on both sides, and the tables never point at them.
+#include "hmgpu_dev.h"
+
+namespace hmgpu {
+
+namespace {
+
+__device__ inline int depth_conv(int v, int sh, int maxv) {
+  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
+}
+
+__device__ inline void unpack8(const u32x4 w, int v[8]) {
+  for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(w[i] & 0xffff); v[2 * i + 1] = (int16_t)(w[i] >> 16); }
+}
+
+template <int BYTES>
+__device__ inline void store4(uint8_t* d, const uint32_t o[4], int n, bool vec) {
+  if (vec && n == 4) {
+    if (BYTES == 1) stg(reinterpret_cast<uint32_t*>(d), o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24);
+    else { u32x2 w; w.x = o[0] | o[1] << 16; w.y = o[2] | o[3] << 16; stg2(d, w); }
+    return;
+  }
+  for (int i = 0; i < n; i++) {
+    if (BYTES == 1) stg(d + i, (uint8_t)o[i]);
+    else stg(reinterpret_cast<uint16_t*>(d) + i, (uint16_t)o[i]);
+  }
+}
+
+// C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane
+template <int LAYOUT, int BYTES, int C>
+__device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds) {
+  constexpr int G = C == 2 ? 4 : 8;                       // samples per 16-byte group
+  const int chan = C == 2 ? 1 : 0;                        // channel type of the bit-depth rule
+  const int tid = threadIdx.x;
+  const int tyi = blk / k.tiles_x, txi = blk - tyi * k.tiles_x;
+  const int ox0 = txi * k.tw, oy0 = tyi * k.th;
+  const int nx = min(k.tw, k.tx.n - ox0), ny = min(k.th, k.ty.n - oy0);
+  const int sx_lo = ldg(k.tx.span + 2 * txi), sx_hi = ldg(k.tx.span + 2 * txi + 1);
+  const int sy_lo = ldg(k.ty.span + 2 * tyi), sy_hi = ldg(k.ty.span + 2 * tyi + 1);
+  const int ax = (k.x0 + sx_lo) & ~(G - 1);               // first sample (plane coordinates) of the staged span, 16-byte aligned
+  const int groups = (k.x0 + sx_hi - ax + G - 1) / G;
+  const int cap = k.span_cap, R = k.rows, TW = k.tw;
+  uint16_t* sbuf = reinterpret_cast<uint16_t*>(lds);      // [C][R][cap]
+  int32_t* tbuf = lds + (C * R * cap) / 2;                // [C][R][tw]
+  // horizontal pass: column hx of the tile, rows hr + q * hstep (q < 4)
+  const int hx = tid & (TW - 1), hr = tid / TW, hstep = 256 / TW;
+  const bool hval = hx < nx;
+  const int hf = hval ? ldg(k.tx.first + ox0 + hx) : 0, hn = hval ? ldg(k.tx.count + ox0 + hx) : 0;
+  const int hbase = k.x0 + hf - ax;
+  const int hsh = 14 - a.e, hrnd = 1 << (13 - a.e);
+  // vertical sums: columns vx .. vx + 3, row vy of the tile
+  const int vx = 4 * (tid % (TW / 4)), vy = tid / (TW / 4);
+  const bool vval = vy < ny && vx < nx;
+  const int vf = vval ? ldg(k.ty.first + oy0 + vy) : 0, vn = vval ? ldg(k.ty.count + oy0 + vy) : 0;
+  int acc[C][4];
+  for (int c = 0; c < C; c++)
+    for (int j = 0; j < 4; j++) acc[c][j] = 0;
+
+  for (int r0 = sy_lo; r0 < sy_hi; r0 += R) {
+    const int nr = min(R, sy_hi - r0);
+    // 1. stage: nr rows x `groups` 16-byte groups, converted
+    for (int i = tid; i < nr * groups; i += 256) {
+      const int r = i / groups, g = i - r * groups;
+      const int x = ax + g * G, y = k.y0 + r0 + r;
+      uint32_t o[C][8];
+      if constexpr (C == 2) {
+        int p[8];
+        unpack8(ldg4(k.src + (ptrdiff_t)y * k.pitch + kCStep * x), p);
+        for (int s = 0; s < 4; s++) {
+          o[0][s] = (uint32_t)depth_conv(p[2 * s], a.sh[1], a.maxv[1]);
+          o[C - 1][s] = (uint32_t)depth_conv(p[2 * s + 1], a.sh[1], a.maxv[1]);
+        }
+      } else {
+        int yv[8];
+        unpack8(ldg4(k.src + (ptrdiff_t)y * k.pitch + x), yv);
+        if constexpr (C == 1) {
+          for (int s = 0; s < 8; s++) o[0][s] = (uint32_t)depth_conv(yv[s], a.sh[0], a.maxv[0]);
+        } else {
+          int u[8], v[8];
+          if (a.mono) {
+            for (int s = 0; s < 8; s++) u[s] = v[s] = a.coef[3];
+          } else {
+            const int16_t* cp = a.c + (ptrdiff_t)(y >> a.csy) * a.pitch_c + kCStep * (x >> a.csx);
+            int p[16];
+            unpack8(ldg4(cp), p);
+            if (a.csx) {
+              for (int s = 0; s < 8; s++) { u[s] = p[2 * (s >> 1)]; v[s] = p[2 * (s >> 1) + 1]; }
+            } else {
+              unpack8(ldg4(cp + 8), p + 8);
+              for (int s = 0; s < 8; s++) { u[s] = p[2 * s]; v[s] = p[2 * s + 1]; }
+            }
+          }
+          if (a.coef[10]) {                   // identity (GBR)
+            for (int s = 0; s < 8; s++) {
+              o[0][s] = (uint32_t)depth_conv(v[s], a.sh[1], a.maxv[1]);
+              o[1][s] = (uint32_t)depth_conv(yv[s], a.sh[0], a.maxv[0]);
+              o[C - 1][s] = (uint32_t)depth_conv(u[s], a.sh[1], a.maxv[1]);
+            }
+          } else {
+            const int S = a.coef[0], M = a.coef[9];
+            for (int s = 0; s < 8; s++) {
+              const int t = a.coef[4] * (yv[s] - a.coef[2]) + a.coef[1];
+              const int cu = u[s] - a.coef[3], cv = v[s] - a.coef[3];
+              o[0][s] = (uint32_t)min(M, max(0, (t + a.coef[5] * cv) >> S));
+              o[1][s] = (uint32_t)min(M, max(0, (t + a.coef[6] * cu + a.coef[7] * cv) >> S));
+              o[C - 1][s] = (uint32_t)min(M, max(0, (t + a.coef[8] * cu) >> S));
+            }
+          }
+        }
+      }
+      for (int c = 0; c < C; c++) {
+        uint16_t* d = sbuf + (c * R + r) * cap + g * G;
+        if constexpr (G == 8) {
+          u32x4 w;
+          for (int s = 0; s < 4; s++) w[s] = o[c][2 * s] | o[c][2 * s + 1] << 16;
+          *reinterpret_cast<u32x4*>(d) = w;
+        } else {
+          u32x2 w;
+          w.x = o[c][0] | o[c][1] << 16; w.y = o[c][2] | o[c][3] << 16;
+          *reinterpret_cast<u32x2*>(d) = w;
+        }
+      }
+    }
+    __syncthreads();
+    // 2. horizontal taps
+    if (hval && hr < nr) {
+      int h[C][4];
+      for (int c = 0; c < C; c++)
+        for (int q = 0; q < 4; q++) h[c][q] = 0;
+      const int16_t* wp = k.tx.w + ox0 + hx;
+      for (int j = 0; j < hn; j++) {
+        const int w = ldg(wp + (ptrdiff_t)j * k.tx.n);
+        for (int q = 0; q < 4; q++) {
+          const int r = hr + q * hstep;
+          if (r < nr)
+            for (int c = 0; c < C; c++) h[c][q] += w * (int)sbuf[(c * R + r) * cap + hbase + j];
+        }
+      }
+      for (int q = 0; q < 4; q++) {
+        const int r = hr + q * hstep;
+        if (r < nr)
+          for (int c = 0; c < C; c++) tbuf[(c * R + r) * TW + hx] = (h[c][q] + hrnd) >> hsh;
+      }
+    }
+    __syncthreads();
+    // 3. vertical taps of the rows of this pass
+    if (vval) {
+      const int j0 = max(r0, vf), j1 = min(r0 + nr, vf + vn);
+      const int16_t* wp = k.ty.w + oy0 + vy;
+      for (int j = j0; j < j1; j++) {
+        const int w = ldg(wp + (ptrdiff_t)(j - vf) * k.ty.n);
+        for (int c = 0; c < C; c++) {
+          const u32x4 t = *reinterpret_cast<const u32x4*>(tbuf + (c * R + j - r0) * TW + vx);
+          for (int q = 0; q < 4; q++) acc[c][q] += w * (int)t[q];
+        }
+      }
+    }
+  }
+  if (!vval) return;
+  const int vsh = 14 + a.e, vrnd = 1 << (13 + a.e);
+  const int M = a.maxv[chan], msb = a.msb[chan];
+  uint32_t o[C][4];
+  for (int c = 0; c < C; c++)
+    for (int q = 0; q < 4; q++) o[c][q] = (uint32_t)min(M, max(0, (acc[c][q] + vrnd) >> vsh)) << msb;
+  const int x = ox0 + vx, y = oy0 + vy, n = min(4, k.tx.n - x);
+  const bool vec = a.vec != 0;
+  if constexpr (C != 2) {
+    for (int c = 0; c < C; c++) store4<BYTES>(a.dst[c] + y * a.pitch[c] + (ptrdiff_t)x * BYTES, o[c], n, vec);
+  } else if (LAYOUT == HMGPU_EXPORT_PLANAR) {
+    store4<BYTES>(a.dst[1] + y * a.pitch[1] + (ptrdiff_t)x * BYTES, o[0], n, vec);
+    store4<BYTES>(a.dst[2] + y * a.pitch[2] + (ptrdiff_t)x * BYTES, o[C - 1], n, vec);
+  } else {                                    // semi-planar: the pairs interleaved
+    const uint32_t p0[4] = {o[0][0], o[C - 1][0], o[0][1], o[C - 1][1]}, p1[4] = {o[0][2], o[C - 1][2], o[0][3], o[C - 1][3]};
+    uint8_t* d = a.dst[1] + y * a.pitch[1] + (ptrdiff_t)x * 2 * BYTES;
+    store4<BYTES>(d, p0, min(4, 2 * n), vec);
+    if (n > 2) store4<BYTES>(d + 4 * BYTES, p1, 2 * n - 4, vec);
+  }
+}
+
+}  // namespace
+
+template <int LAYOUT, int BYTES>
+__global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
+  __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
+  const int b = blockIdx.x;
+  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, BYTES, 3>(a, a.cls[0], b, lds);
+  else if (b < a.cls[0].blocks) scale_tile<LAYOUT, BYTES, 1>(a, a.cls[0], b, lds);
+  else scale_tile<LAYOUT, BYTES, 2>(a, a.cls[1], b - a.cls[0].blocks, lds);
+}
+
+void launch_export_scaled(const ScaleArgs& a, int layout, int bytes, hipStream_t s) {
+  const dim3 grid((unsigned)(a.cls[0].blocks + (layout == HMGPU_EXPORT_RGB ? 0 : a.cls[1].blocks))), block(256);
+#define HMGPU_SCALE_CASE(L)                                                                  \
+  if (layout == L) {                                                                         \
+    if (bytes == 1) hipLaunchKernelGGL((k_export_scale<L, 1>), grid, block, 0, s, a);        \
+    else hipLaunchKernelGGL((k_export_scale<L, 2>), grid, block, 0, s, a);                   \
+  }
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB)
+#undef HMGPU_SCALE_CASE
+}
+
+}  // namespace hmgpu

@@ -987,10 +987,12 @@ bool Decoder::deliver(PicData* pic) {
   return true;
 }
 
-hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream) {
+hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, void* const dst[3],
+                                      const int64_t pitch_bytes[3], int on_stream, void* stream) {
   if (!gpu_ || !pic || pic->owner != this) return HMGPU_EINVAL;
   flush_batch();
   if (!pic->on_device || !pic->decoded) return HMGPU_EINVAL;
+  if (scale) return hmgpu_picture_export_scaled(ctx_of(pic), pic->handle, desc, scale, dst, pitch_bytes, on_stream, stream);
   return hmgpu_picture_export(ctx_of(pic), pic->handle, desc, dst, pitch_bytes, on_stream, stream);
 }
 

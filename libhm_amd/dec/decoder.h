@@ -66,7 +66,9 @@ class Decoder {
   void set_error(const std::string& s) { last_error_ = s; }
   bool fetch_planes(PicData* pic);                        // device -> host planes of a finished picture (no-op when parse-only)
   bool deliver(PicData* pic);                             // a picture handed to the application: planes downloaded, or (device output) its work submitted
-  hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream);
+  // scale: nullptr = hmgpu_picture_export, else hmgpu_picture_export_scaled
+  hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, void* const dst[3], const int64_t pitch_bytes[3],
+                              int on_stream, void* stream);
   int device_of(const PicData* pic) const { return pic && pic->on_device && pic->owner == this ? devices_[pic->home] : -1; }
   uint64_t download_bytes() const { return download_bytes_; }
   int last_display_poc = -(1 << 30);

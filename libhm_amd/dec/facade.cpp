@@ -305,7 +305,12 @@ unsigned long long hmdec_download_bytes(libHMDec_context* ctx) { return ctx ? (u
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3], const int64_t pitch_bytes[3],
                          int on_stream, void* stream) {
   if (!ctx || !pic) return HMGPU_EINVAL;
-  return static_cast<Wrapper*>(ctx)->dec.export_picture(as_pic(pic), desc, dst, pitch_bytes, on_stream, stream);
+  return static_cast<Wrapper*>(ctx)->dec.export_picture(as_pic(pic), desc, nullptr, dst, pitch_bytes, on_stream, stream);
+}
+int hmdec_picture_export_scaled(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream) {
+  if (!ctx || !pic || !scale) return HMGPU_EINVAL;
+  return static_cast<Wrapper*>(ctx)->dec.export_picture(as_pic(pic), desc, scale, dst, pitch_bytes, on_stream, stream);
 }
 int hmdec_picture_device(libHMDec_picture* pic) {
   if (!pic || !as_pic(pic)->owner) return -1;

@@ -11,6 +11,8 @@ from . import abi
 LAYOUTS = {"planar": abi.EXPORT_PLANAR, "yuv": abi.EXPORT_PLANAR, "semiplanar": abi.EXPORT_SEMIPLANAR, "nv12": abi.EXPORT_SEMIPLANAR,
            "rgb": abi.EXPORT_RGB}
 UNSPECIFIED = 2
+FILTERS = {"nearest": abi.SCALE_NEAREST, "nearest-exact": abi.SCALE_NEAREST, "bilinear": abi.SCALE_BILINEAR, "bicubic": abi.SCALE_BICUBIC,
+           "area": abi.SCALE_AREA}
 
 
 def resolve_colour(matrix, full_range, vui_matrix=UNSPECIFIED, vui_full_range=0):
@@ -46,6 +48,67 @@ def make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned=False):
     return abi.make_export_desc(layout_code(layout), bd, nbytes, msb_aligned, tuple(crop), matrix, full_range)
 
 
+def make_scale(size, filter="bilinear"):
+    """size: (height, width) or None (no scaling)"""
+    if size is None:
+        return None
+    if isinstance(filter, str):
+        if filter.lower() not in FILTERS:
+            raise ValueError("unknown filter %r (one of %s)" % (filter, ", ".join(sorted(FILTERS))))
+        filter = FILTERS[filter.lower()]
+    h, w = (int(v) for v in size)
+    return abi.make_export_scale(w, h, filter)
+
+
+def plane_shapes(plan, desc):
+    """the shape of every plane tensor: [H, W], or [H, W, 2] for the CbCr plane of the semi-planar layout"""
+    return [(plan.height[k], plan.width[k], 2) if desc.layout == abi.EXPORT_SEMIPLANAR and k == 1 else (plan.height[k], plan.width[k])
+            for k in range(plan.planes)]
+
+
+def _check_tensor(t, desc, device):
+    import torch
+    if t.dtype != torch_dtype(desc.bytes_per_sample) and not (desc.bytes_per_sample == 2 and t.dtype == torch.int16):
+        raise ValueError("out: dtype %s, the plan gives %s" % (t.dtype, torch_dtype(desc.bytes_per_sample)))
+    if t.get_device() != device:
+        raise ValueError("out: on device %d, the picture is on %d" % (t.get_device(), device))
+
+
+def out_spans(out, plan, desc, device):
+    """a caller's destination (RGB: one [3, H, W] tensor or three planes; YUV: a tuple of planes) as (pointers, pitches in bytes)
+    per plane.  Each plane has the planned shape and dtype on the device and its samples dense within a row; rows may be any stride
+    apart (e.g. a view batch[i]).  Reads only shapes, strides and pointers: no views are made."""
+    import torch
+    shapes = plane_shapes(plan, desc)
+    if isinstance(out, torch.Tensor):
+        if desc.layout != abi.EXPORT_RGB:
+            raise ValueError("out: the planar / semi-planar layouts take a tuple of planes")
+        h, w = shapes[0]
+        if out.shape != (3, h, w):
+            raise ValueError("out: shape %s, the plan gives %s" % (tuple(out.shape), (3, h, w)))
+        _check_tensor(out, desc, device)
+        s0, s1, s2 = out.stride()
+        if s2 != 1 or s1 < w or s0 < s1 * (h - 1) + w:
+            raise ValueError("out: the planes' samples must be dense within a row, rows and planes apart (stride %s)" % ((s0, s1, s2),))
+        es, base = out.element_size(), out.data_ptr()
+        return [base + k * s0 * es for k in range(3)], [s1 * es] * 3
+    planes = tuple(out)
+    if len(planes) != len(shapes):
+        raise ValueError("out: %d planes, the plan gives %d" % (len(planes), len(shapes)))
+    ptrs, pitches = [], []
+    for p, shape in zip(planes, shapes):
+        if not isinstance(p, torch.Tensor) or p.shape != shape:
+            raise ValueError("out: a plane is not a tensor of shape %s" % (shape,))
+        _check_tensor(p, desc, device)
+        st = p.stride()
+        inner = (1,) if len(shape) == 2 else (2, 1)
+        if st[1:] != inner or st[0] < shape[1] * inner[0]:
+            raise ValueError("out: a plane's samples must be dense within a row (stride %s)" % (st,))
+        ptrs.append(p.data_ptr())
+        pitches.append(st[0] * p.element_size())
+    return ptrs, pitches
+
+
 def alloc_outputs(plan, desc, device):
     """torch tensors for what `plan` describes: RGB [3, H, W]; planar (Y, Cb, Cr) 2-D; semi-planar (Y [H, W], CbCr [Hc, Wc, 2]).
     Returns (result, per-plane tensors)."""
@@ -64,16 +127,22 @@ def alloc_outputs(plan, desc, device):
     return tuple(planes), planes
 
 
-def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True):
-    """allocate with torch on `device` and run `call(desc, ptrs, pitches, stream)` on torch's current stream"""
+def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
+                   filter="bilinear", out=None):
+    """allocate with torch on `device` (or take `out`) and run `call(desc, scale, ptrs, pitches, stream)` on torch's current stream;
+    scale: None (size None), else the abi.ExportScale of size (height, width) and filter"""
     import torch
-    from . import export_plan
+    from . import export_plan, export_scaled_plan
     desc = make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned)
-    plan = export_plan(seq, desc)
+    scale = make_scale(size, filter)
+    plan = export_plan(seq, desc) if scale is None else export_scaled_plan(seq, desc, scale)
     with torch.cuda.device(device):
-        out, planes = alloc_outputs(plan, desc, device)
+        if out is None:
+            out, planes = alloc_outputs(plan, desc, device)
+            ptrs = [p.data_ptr() for p in planes]
+            pitches = [p.stride(0) * p.element_size() for p in planes]
+        else:
+            ptrs, pitches = out_spans(out, plan, desc, device)
         stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
-        ptrs = [p.data_ptr() for p in planes]
-        pitches = [p.stride(0) * p.element_size() for p in planes]
-        call(desc, ptrs, pitches, stream)
+        call(desc, scale, ptrs, pitches, stream)
     return out

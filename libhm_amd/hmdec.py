@@ -70,6 +70,8 @@ def lib():
         L.hmdec_download_bytes.restype = C.c_ulonglong
         L.hmdec_picture_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.ExportDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                            C.c_int, C.c_void_p]
+        L.hmdec_picture_export_scaled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -196,20 +198,27 @@ class Picture:
         lib().hmdec_picture_colour(self.h, v)
         return dict(zip(("full_range", "primaries", "transfer", "matrix", "video_format"), (int(x) for x in v)))
 
-    def export_into(self, desc, ptrs, pitches, on_stream=1, stream=0):
-        """hmdec_picture_export into device memory the caller owns"""
+    def export_into(self, desc, ptrs, pitches, on_stream=1, stream=0, scale=None):
+        """hmdec_picture_export (scale: an abi.ExportScale, hmdec_picture_export_scaled) into device memory the caller owns"""
         p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
         q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        st = lib().hmdec_picture_export(self.ctx, self.h, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None))
+        if scale is None:
+            st, name = lib().hmdec_picture_export(self.ctx, self.h, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmdec_picture_export"
+        else:
+            st = lib().hmdec_picture_export_scaled(self.ctx, self.h, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None))
+            name = "hmdec_picture_export_scaled"
         if st != 0:
             from . import HmgpuError
-            raise HmgpuError(st, "hmdec_picture_export")
+            raise HmgpuError(st, name)
 
-    def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False):
+    def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
+               filter="bilinear", out=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
-        VUI (the colour policy of libhm_amd.export).  Valid until the next push into the decoder."""
+        VUI (the colour policy of libhm_amd.export); size: (height, width) of the output, resized with `filter` ("nearest",
+        "bilinear", "bicubic", "area"), None = the crop's size; out: a tensor (or tuple of planes) of the planned shape to write
+        instead of new ones.  Valid until the next push into the decoder."""
         from . import export
         if self.ctx is None:
             raise RuntimeError("Picture.export: the picture does not know its decoder")
@@ -225,8 +234,8 @@ class Picture:
         dev = self.device
         if dev < 0:
             raise RuntimeError("Picture.export: the picture is not on a device (parse-only, or its sequence has ended)")
-        return export.export_tensors(lambda desc, ptrs, pitches, st: self.export_into(desc, ptrs, pitches, 1, st),
-                                     seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned)
+        return export.export_tensors(lambda desc, scale, ptrs, pitches, st: self.export_into(desc, ptrs, pitches, 1, st, scale),
+                                     seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out)
 
 
 class Decoder:
