@@ -342,11 +342,11 @@ hmgpu_status alloc_picture(hmgpu_ctx* c, Picture& p) {
     d.edges = m.take<EdgeRec>((size_t)(c->grid_w / 2) * (c->grid_h / 2));
     d.tmv = m.take<TileMv>((size_t)(c->grid_w / 2) * (c->grid_h / 2));
     for (int k = 0; k < 3; k++) d.resid[k] = m.take<int16_t>(c->coef_elems[k]);
-    for (int k = 0; k < 3; k++) d.quad_off[k] = m.take<uint32_t>((size_t)c->num_ctus * (c->parts / 4));
     p.coef_start = m.take<uint32_t>((size_t)3 * (c->num_ctus + 1));
     d.fault = m.take<uint32_t>(1);
     for (int k = 0; k < 4; k++) d.tu[k] = m.take<TuRec>((size_t)c->tu_cap[k] * kTuShards);
     d.tu_count = m.take<uint32_t>(4 * kTuShards);
+    d.tu_work = m.take<uint32_t>(4 * kTuShards + 1);
     d.stats = m.take<unsigned long long>(2 * kTuShards);
     d.saoprm = m.take<SaoDev>((size_t)c->num_ctus * 3);
     d.slices = m.take<SliceDev>(HMGPU_MAX_SLICES);
@@ -441,7 +441,7 @@ hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp
   int max_ctus = 0;
   for (int i = 0; i < b.n; i++) max_ctus = std::max(max_ctus, b.num_ctus[i]);
   // 4:2:2 / 4:4:4: the chroma of every inter cell comes from the format-generic kernel, which reads the BlkInfo grid
-  { ProfScope ps(c, K_PREP); launch_prep(c->d_pics, b, max_ctus, c->parts, any_intra, any_cells || c->fmt != 1, c->fmt, c->stream); }
+  { ProfScope ps(c, K_PREP); launch_prep(c->d_pics, b, max_ctus, c->parts, any_intra, any_bi, any_cells || c->fmt != 1, c->fmt, c->stream); }
   if (c->fmt != 1) {
     // ... and adds the residual wherever it predicts: tiles no coded block covers must read as zero (Cb and Cr tiles are neighbours in memory)
     for (int i = 0; i < b.n; i++) {

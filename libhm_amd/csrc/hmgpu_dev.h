@@ -151,14 +151,14 @@ struct PicDev {
   // (resid_slot): a motion-compensation lane owns rows 2q, 2q+1, so each of its two loads reads 64 consecutive bytes per tile
   int16_t* resid[3];
   const uint32_t* coef_start[3];   // compact levels: element offset of every CTU's first coded TU (+ total), else null (HM's dense layout)
-  uint32_t* quad_off[3];           // compact levels: offset of the first TU that starts in every 8x8 luma area (z-order), written by k_prep
   const SliceDev* slices;
   // derived
   BlkInfo* blk;                    // written only for calls that run kernels which read it (mixed-motion tiles, exempt CUs): launch_prep
   EdgeRec* edges;                  // [grid_h / 2][grid_w / 2]
   TileMv* tmv;                     // [grid_h / 2][grid_w / 2]
   TuRec* tu[4];                    // by log2 size - 2: kTuShards shards of tu_cap[] records each
-  uint32_t* tu_count;              // [4][kTuShards]
+  uint32_t* tu_count;              // [4][kTuShards]: the lists' lengths, published by the last workgroup of k_prep
+  uint32_t* tu_work;               // [4][kTuShards] + 1: the lengths while k_prep appends, and its arrival ticket; zero between launches
   uint32_t tu_cap[4];              // capacity of ONE shard
   SaoDev* saoprm;                  // [num_ctus][3]
   unsigned long long* stats;       // [2][kTuShards]: intra / inter partitions seen by the prep kernel
@@ -277,7 +277,8 @@ struct UnpackArgs {
   const char* blob[kMaxBatch];
 };
 void launch_unpack_input(const PicDev* pics, const UnpackArgs& ua, int num_ctus, hipStream_t s);
-void launch_prep(const PicDev* pics, const Batch& b, int max_ctus, int parts, bool intra, bool write_blk, int fmt, hipStream_t s);
+// bi: the batch holds B slices (else list 1 is not read)
+void launch_prep(const PicDev* pics, const Batch& b, int max_ctus, int parts, bool intra, bool bi, bool write_blk, int fmt, hipStream_t s);
 // npics = entries of the finals table (device pictures of the context, <= kMaxPics)
 // bi: the batch holds B slices (the variants that run the H and V passes once per list)
 void launch_mc_luma(McArgs& a, int max_ctus, bool wp, bool bi, hipStream_t s);
