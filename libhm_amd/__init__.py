@@ -449,7 +449,8 @@ class Context:
         h = C.c_void_p()
         m, co = abi.CtuMeta(), abi.Coeffs()
         self._chk(lib().hmgpu_staging_alloc(self._h, C.byref(h), C.byref(m), C.byref(co)), "hmgpu_staging_alloc")
-        return abi.StagingHolder(h, m, co, self.num_ctus, abi.parts_per_ctu(self.seq), 1 << self.seq.log2_ctu_size)
+        return abi.StagingHolder(h, m, co, self.num_ctus, abi.parts_per_ctu(self.seq), 1 << self.seq.log2_ctu_size,
+                                 chroma_shift=sum(self.chroma_scale))
 
     def pack_levels(self, meta, coeffs):
         return pack_levels(self.seq, meta, coeffs)

@@ -188,7 +188,8 @@ class StagingHolder:
     .struct / .coeffs are the structs to hand to the whole-picture calls.  fill() copies ordinary arrays in, levels in HM's dense
     layout; fill_compact() packs the levels (hmgpu_pack_levels: coded TUs only)."""
 
-    def __init__(self, handle, meta_struct, coeff_struct, num_ctus, parts, ctu):
+    def __init__(self, handle, meta_struct, coeff_struct, num_ctus, parts, ctu, chroma_shift=2):
+        """chroma_shift: log2 of the luma samples per chroma sample (csx + csy): 2 for 4:2:0 / 4:0:0, 1 for 4:2:2, 0 for 4:4:4"""
         self.handle, self.struct = handle, meta_struct
         self.num_ctus = num_ctus
         np_ = num_ctus * parts
@@ -207,7 +208,7 @@ class StagingHolder:
                 continue                                    # (arrays a staging block does not hold: cross-component prediction weights)
             n = num_ctus if name in ("slice_idx", "tile_idx") else (2 * np_ if name in ("mv0", "mv1") else np_)
             self.arrays[name] = view(addr[name], dt, n)
-        self.levels = [view(coeff_struct.level[k], np.int16, num_ctus * ctu * ctu >> (2 if k else 0)) for k in range(3)]
+        self.levels = [view(coeff_struct.level[k], np.int16, num_ctus * ctu * ctu >> (chroma_shift if k else 0)) for k in range(3)]
         self.starts = [view(coeff_struct.ctu_level_start[k], np.uint32, num_ctus + 1) for k in range(3)]
         self._all = {"intra": (m.intra_dir[0], m.intra_dir[1]), "ts": tuple(m.transform_skip[k] for k in range(3)),
                      "bypass": m.transquant_bypass, "ipcm": m.ipcm}

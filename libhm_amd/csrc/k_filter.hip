@@ -204,7 +204,7 @@ __device__ inline void edge_apply(const PicDev& P, FilterLds& L, int x0, int y0,
     for (int k = 1; k < 7; k++) *reinterpret_cast<u32x2*>(base + (k - 4) * kYW) = (u32x2){a[k], b[k]};
   }
   // chroma: Bs 2 only, edges on the 8-sample chroma grid (TComLoopFilter.cpp:225-229, 684-692, 727)
-  if (bs == 2 && ((DIR == 0 ? x : y) & 15) == 0) {
+  if (bs == 2 && ((DIR == 0 ? x : y) & 15) == 0 && !P.mono) {      // (4:0:0: the chroma planes are left alone)
     const int maxc = (1 << P.bd[1]) - 1;
 #pragma unroll
     for (int comp = 1; comp < 3; comp++) {

@@ -426,6 +426,7 @@ typedef struct
   const hmgpu_pic_params* pp;
   int ctu, pw, parts, ctus_w, ctus_h, num_ctus, max_cu_depth;
   int w[3], h[3], bd[3];
+  int ncomp;                        /* components that are reconstructed and filtered: 1 for 4:0:0 (the chroma planes are left alone), else 3 */
   int fmt, csx[3], csy[3];          /* chroma_format_idc (0 handled as 4:2:0 geometry); getComponentScaleX / Y (TComChromaFormat.h:59-62) */
 } geom;
 
@@ -442,6 +443,7 @@ static void geom_init(geom* g, const hmgpu_seq_params* seq, const hmgpu_slice_pa
   g->num_ctus = g->ctus_w * g->ctus_h;
   g->max_cu_depth = seq->log2_ctu_size - 3;           /* g_uiMaxCUDepth - g_uiAddCUDepth: CUs down to 8x8 */
   g->fmt = seq->chroma_format == 0 ? 1 : seq->chroma_format;
+  g->ncomp = seq->chroma_format == 0 ? 1 : 3;
   g->csx[0] = g->csy[0] = 0;
   g->csx[1] = g->csx[2] = g->fmt == 3 ? 0 : 1;
   g->csy[1] = g->csy[2] = g->fmt == 1 ? 1 : 0;
@@ -1018,7 +1020,7 @@ static void decompress_cu(cu_ctx* c, int z, int depth, int64_t* n_intra)
     /* xReconPCM / xDecodePCMTexture (TDecCu.cpp:770-830): the transmitted samples, shifted up to the coding bit depth */
     int comp, x, y;
     *n_intra += num_part;
-    for (comp = 0; comp < 3; comp++)
+    for (comp = 0; comp < g->ncomp; comp++)
     {
       const int cw = size >> g->csx[comp], chh = size >> g->csy[comp];
       const int shift = g->bd[comp] - (comp ? g->seq->pcm_bit_depth_chroma : g->seq->pcm_bit_depth_luma);
@@ -1033,7 +1035,7 @@ static void decompress_cu(cu_ctx* c, int z, int depth, int64_t* n_intra)
     *n_intra += num_part;
     if (!g->m->intra_dir[0] || !g->m->intra_dir[1]) return;      /* no intra modes supplied: the CU's samples are left alone */
     intra_recurse(c, 0, z, 0, g->seq->log2_ctu_size - depth);       /* xReconIntraQT: luma of the whole CU, then chroma (:665-690) */
-    intra_recurse(c, 1, z, 0, g->seq->log2_ctu_size - depth);
+    if (g->ncomp > 1) intra_recurse(c, 1, z, 0, g->seq->log2_ctu_size - depth);
     return;
   }
   {
@@ -1043,7 +1045,7 @@ static void decompress_cu(cu_ctx* c, int z, int depth, int64_t* n_intra)
     for (i = 0; i < n; i++) pred_pu(c, z + z_off[i], xr[i], yr[i], w[i], h[i]);
     for (comp = 0; comp < 3; comp++)                                             /* m_ppcYuvResi->clear(): :413 */
       memset(c->resi[comp], 0, sizeof(int16_t) * (size >> g->csx[comp]) * (size >> g->csy[comp]));
-    for (comp = 0; comp < 3; comp++)
+    for (comp = 0; comp < g->ncomp; comp++)
     {
       const int cw = size >> g->csx[comp], chh = size >> g->csy[comp];
       tu_recurse(c, comp, z, 0, g->seq->log2_ctu_size - depth, 0, 0);          /* xDecodeInterTexture: :743-757 (luma first: chroma may predict from its residual) */
@@ -1604,10 +1606,10 @@ int hmo_sao_process(const hmgpu_seq_params* seq, const hmgpu_slice_params* slice
     const int yp = (a / g.ctus_w) * g.ctu, xp = (a % g.ctus_w) * g.ctu;
     const int hh = imin(g.ctu, seq->height - yp), ww = imin(g.ctu, seq->width - xp);
     int all_off = 1;
-    for (comp = 0; comp < 3; comp++) if (rec[(size_t)a * 3 + comp].mode_idc != HMGPU_SAO_OFF) all_off = 0;
+    for (comp = 0; comp < g.ncomp; comp++) if (rec[(size_t)a * 3 + comp].mode_idc != HMGPU_SAO_OFF) all_off = 0;
     if (all_off) continue;
     sao_avail(&g, a, av);
-    for (comp = 0; comp < 3; comp++)
+    for (comp = 0; comp < g.ncomp; comp++)
     {
       const hmgpu_sao_param* p = &rec[(size_t)a * 3 + comp];
       const int sx = g.csx[comp], sy = g.csy[comp];
@@ -1627,7 +1629,7 @@ int hmo_sao_process(const hmgpu_seq_params* seq, const hmgpu_slice_params* slice
     {
       const int px = (a % g.ctus_w) * g.ctu + zx(z) * 4, py = (a / g.ctus_w) * g.ctu + zy(z) * 4;
       if (px >= seq->width || py >= seq->height || !no_filter(&g, a, z)) continue;
-      for (comp = 0; comp < 3; comp++)
+      for (comp = 0; comp < g.ncomp; comp++)
       {
         const int sx = g.csx[comp], sy = g.csy[comp];
         int x, y;

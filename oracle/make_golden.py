@@ -372,6 +372,9 @@ LITE.update({
                                             CF422 + ["--WaveFrontSynchro=1", "--SliceMode=1", "--SliceArgument=10", "--SliceSegmentMode=1", "--SliceSegmentArgument=3"]),
     "intra_422_qp12_main10_208x120": ("encoder_intra_main_rext.cfg", 208, 120, 1, 10, 10, 12, CF422),
     "ldb_422_ctu32_main8_208x120": ("encoder_lowdelay_main_rext.cfg", 208, 120, 3, 8, 8, 30, CF422 + ["--MaxCUWidth=32", "--MaxCUHeight=32", "--MaxPartitionDepth=3"]),
+    # scaling lists from a file in 4:4:4: the only format with 32x32 chroma blocks, whose lists HM copies from the 16x16 chroma lists (the file
+    # format has no 32x32 chroma entries); write_scaling_list_file gives every 16x16 chroma list its own matrix and DC value
+    "ldb_444_sl_main8_208x120": ("encoder_lowdelay_main_rext.cfg", 208, 120, 3, 8, 8, 24, CF444 + ["--ScalingList=2", "--ScalingListFile=@SLFILE@"]),
 })
 
 

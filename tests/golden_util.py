@@ -26,10 +26,13 @@ LITE = ["ldp_slices_main8_208x120", "ldp_depslices_main10_208x120", "ldp_wpp_mai
         # monochrome (4:0:0)
         "ldb_mono_rext_main8_208x120", "ldb_mono_wp_crop_main10_204x116", "intra_mono_main8_208x120"]
 # 4:2:2 / 4:4:4 variants: without cross-component prediction, lossless (rotation + RDPCM on full-size chroma), transform skip up to 32x32
-# chroma blocks, cross-component prediction between different bit depths, 16- and 32-sample CTUs, weighted prediction, wavefronts + slices
+# chroma blocks, cross-component prediction between different bit depths, 16- and 32-sample CTUs, weighted prediction, wavefronts + slices,
+# scaling lists
 LITE_CF = ["ldb_444_main10_208x120", "ldb_444_lossless_main8_208x120", "intra_444_ts32_nosmooth_main8_208x120", "ldb_444_ccp_bd10_8_208x120",
            "ldb_444_ctu16_main8_208x120", "ldb_422_lossless_main8_208x120", "ldb_422_wp_main10_208x120", "ldb_422_wpp_depslices_main8_416x240",
-           "intra_422_qp12_main10_208x120", "ldb_422_ctu32_main8_208x120"]
+           "intra_422_qp12_main10_208x120", "ldb_422_ctu32_main8_208x120",
+           # scaling lists from a file in 4:4:4: coded 32x32 chroma blocks, de-quantised with the lists HM copies from the 16x16 chroma lists
+           "ldb_444_sl_main8_208x120"]
 # bit depth 12, 4:2:0 (oracle/make_golden.py: CF420 streams)
 STREAMS_BD12 = ["ldb_main12_208x120", "intra_main12_208x120"]
 LITE_BD12 = ["ldb_ts32_main12_208x120", "ldb_wp_main12_208x120", "ldb_sl_main12_208x120", "intra_qp4_main12_208x120", "ldb_bd12_10_208x120",

@@ -31,50 +31,70 @@ class SynthPicture:
 
 def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, num_refs=1, slice_qp_range=(22, 37),
                  cbf_prob=0.5, sao=True, mode_probs=(0.1, 0.3, 0.3, 0.2, 0.1), ref_handles=None, mv_range=64,
-                 coef_dist="typical", tr_split_prob=0.35, intra_modes=True, num_slices=1, lf_across_slices=1):
+                 coef_dist="typical", tr_split_prob=0.35, intra_modes=True, num_slices=1, lf_across_slices=1,
+                 chroma_format=1, log2_ctu=6, bit_depth_chroma=None, ccp_prob=0.0):
     """Returns a SynthPicture with .seq, .slice (abi.SliceParams), .meta (MetaHolder), .coeffs (CoeffHolder),
     .sao_raw [num_ctus,3,35], .pp, .meta_np.  ref_handles: device picture handles of list-0 / list-1 references.
     coef_dist: "typical" (see above), "stress" (every level of a coded TU uniform over the full int16 range) or
-    "dense" (every level uniform in -3..3)."""
+    "dense" (every level uniform in -3..3).
+    chroma_format 0 / 1 / 2 / 3, log2_ctu 4 / 5 / 6 and bit_depth_chroma (None: the luma depth) select the other shapes of
+    include/hmgpu.h (hmgpu_seq_params, hmgpu_ctu_meta, hmgpu_coeffs); with the defaults every array is what it always was, the PRNG
+    being consumed in the same order (tests/test_synth_digests_cpu.py).
+      * CTUs of 32 / 16 samples: the CU-size modes name the same CU sizes, capped at the CTU (a "64x64" CTU of a 16-sample CTU picture is
+        one 16x16 CU); AMP at min(32, CTU size), which gives 4- and 12-sample wide PUs in 16-sample CTUs; QP and SAO stay per CTU
+      * 4:4:4: every luma TU has chroma twins of its size (4x4 chroma per 4x4 luma, 32x32 chroma); 4:2:2: the chroma block of a transform
+        unit is two squares, the upper one first, each with a flag of its own one transform depth below the unit's bit over the upper /
+        lower half of the unit's partitions (TDecSbac::parseQtCbf), the 4x8 block of an 8x8 CU split into 4x4 luma TUs riding with the
+        first child; 4:0:0: no coded chroma block
+      * ccp_prob (4:4:4 only): probability that a transform unit whose luma block is coded carries a cross-component prediction weight
+        from {+-1, +-2, +-4, +-8} per chroma component (meta ccp_u / ccp_v, on all partitions of the unit; intra units only with the
+        chroma mode DM, as in HM); 0 = the arrays are absent"""
+    assert chroma_format in (0, 1, 2, 3) and log2_ctu in (4, 5, 6)
+    fmt = 1 if chroma_format == 0 else chroma_format                  # 4:0:0 keeps the geometry of 4:2:0
+    csx, csy = (0 if fmt == 3 else 1), (1 if fmt == 1 else 0)
+    bdc = bit_depth if bit_depth_chroma is None else bit_depth_chroma
     rng = np.random.RandomState(seed)
-    ctu, pw, parts = 64, 16, 256
-    cw, ch = (width + 63) // 64, (height + 63) // 64
+    ctu, pw, parts = 1 << log2_ctu, 1 << (log2_ctu - 2), 1 << (2 * log2_ctu - 4)
+    cw, ch = (width + ctu - 1) // ctu, (height + ctu - 1) // ctu
     n = cw * ch
     zx, zy = _zxy(parts)
-    ctu_x = (np.arange(n) % cw) * 64
-    ctu_y = (np.arange(n) // cw) * 64
+    ctu_x = (np.arange(n) % cw) * ctu
+    ctu_y = (np.arange(n) // cw) * ctu
     px = ctu_x[:, None] + 4 * zx[None, :]
     py = ctu_y[:, None] + 4 * zy[None, :]
     inside = (px < width) & (py < height)
 
     # ---- CTU partitioning mode.  CTUs cut by the picture border take the modes whose CUs fit (16x16 / 8x8)
     mode = rng.choice(5, size=n, p=mode_probs)
-    partial = (ctu_x + 64 > width) | (ctu_y + 64 > height)
+    partial = (ctu_x + ctu > width) | (ctu_y + ctu > height)
     if width % 16 or height % 16:
         mode[partial] = 3                                          # only 8x8 CUs tile a picture that is not a multiple of 16
     else:
         mode[partial] = np.where(rng.rand(int(partial.sum())) < 0.6, 2, 3)
-    cu_log2 = np.array([6, 5, 4, 3, 5])[mode]                     # per CTU
-    depth = (6 - cu_log2)[:, None] * np.ones((1, parts), dtype=np.int64)
+    cu_log2 = np.minimum(np.array([6, 5, 4, 3, 5])[mode], log2_ctu)  # per CTU
+    depth = (log2_ctu - cu_log2)[:, None] * np.ones((1, parts), dtype=np.int64)
     cu_parts = (1 << (2 * (cu_log2 - 2)))[:, None]                # partitions per CU
     z = np.arange(parts)[None, :]
     cu_idx = z // cu_parts                                         # CU index inside the CTU (z order)
     child = (z % cu_parts) // np.maximum(cu_parts // 4, 1)         # quadrant inside the CU
-    n_cu_max = 64
+    n_cu_max = parts // 4
+    n_pu_max = 2 * n_cu_max
 
     # ---- part size: 2Nx2N except mode 4 (AMP, one of 2NxnU, 2NxnD, nLx2N, nRx2N per CU)
     amp_type = rng.randint(4, 8, size=(n, n_cu_max))
     part_size = np.zeros((n, parts), dtype=np.int64)
     is_amp = (mode == 4)[:, None] & np.ones((1, parts), dtype=bool)
     part_size[is_amp] = np.take_along_axis(amp_type, cu_idx, axis=1)[is_amp]
-    # PU index inside the CU (0/1) for AMP CUs: depends on the partition's row/column inside the 32x32 CU (8 partitions wide)
-    rel_x = zx[None, :] % 8
-    rel_y = zy[None, :] % 8
+    # PU index inside the CU (0/1) for AMP CUs: depends on the partition's row/column inside the 32x32 CU (8 partitions wide;
+    # 16x16 CUs in 16-sample CTUs: 4 wide)
+    amp_w = min(8, pw)
+    rel_x = zx[None, :] % amp_w
+    rel_y = zy[None, :] % amp_w
     pu_in_cu = np.zeros((n, parts), dtype=np.int64)
-    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_2NxnU), (rel_y >= 2).astype(np.int64), pu_in_cu)
-    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_2NxnD), (rel_y >= 6).astype(np.int64), pu_in_cu)
-    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_nLx2N), (rel_x >= 2).astype(np.int64), pu_in_cu)
-    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_nRx2N), (rel_x >= 6).astype(np.int64), pu_in_cu)
+    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_2NxnU), (rel_y >= amp_w // 4).astype(np.int64), pu_in_cu)
+    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_2NxnD), (rel_y >= amp_w - amp_w // 4).astype(np.int64), pu_in_cu)
+    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_nLx2N), (rel_x >= amp_w // 4).astype(np.int64), pu_in_cu)
+    pu_in_cu = np.where(is_amp & (part_size == abi.SIZE_nRx2N), (rel_x >= amp_w - amp_w // 4).astype(np.int64), pu_in_cu)
     pu_idx = cu_idx * 2 + pu_in_cu                                 # < 128
 
     # ---- prediction mode per CU
@@ -85,8 +105,8 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
 
     # ---- motion per PU
     def draw_mv():
-        mvi = rng.randint(-mv_range, mv_range + 1, size=(n, 128, 2))
-        mvf = rng.randint(0, 4, size=(n, 128, 2))
+        mvi = rng.randint(-mv_range, mv_range + 1, size=(n, n_pu_max, 2))
+        mvf = rng.randint(0, 4, size=(n, n_pu_max, 2))
         return mvi * 4 + mvf
     mv0_pu = draw_mv()
     mv1_pu = draw_mv()
@@ -95,12 +115,12 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     mv1 = np.take_along_axis(mv1_pu, idx3, axis=1)
     ref_idx0 = np.zeros((n, parts), dtype=np.int64)
     if num_refs > 1:
-        ref_pu = rng.randint(0, num_refs, size=(n, 128))
+        ref_pu = rng.randint(0, num_refs, size=(n, n_pu_max))
         ref_idx0 = np.take_along_axis(ref_pu, pu_idx, axis=1)
     ref_idx1 = np.full((n, parts), -1, dtype=np.int64)
     if bi:
         # per PU: 0 = L0 only, 1 = L1 only, 2 = both   (8x4 / 4x8 PUs do not exist here, so bi is legal everywhere)
-        kind_pu = rng.choice(3, size=(n, 128), p=(0.2, 0.1, 0.7))
+        kind_pu = rng.choice(3, size=(n, n_pu_max), p=(0.2, 0.1, 0.7))
         kind = np.take_along_axis(kind_pu, pu_idx, axis=1)
         ref_idx1 = np.where(kind >= 1, 0, -1)
         ref_idx0 = np.where(kind == 1, -1, ref_idx0)
@@ -112,22 +132,39 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     # ---- transform tree: tr_idx in {0,1} per CU (64x64 CUs and AMP CUs always split once)
     tr_cu = (rng.rand(n, n_cu_max) < tr_split_prob).astype(np.int64)
     tr_idx = np.take_along_axis(tr_cu, cu_idx, axis=1)
-    tr_idx = np.where(((mode == 0) | (mode == 4))[:, None], 1, tr_idx)
+    tr_idx = np.where(((cu_log2 == 6) | (mode == 4))[:, None], 1, tr_idx)
     # cbf: per CU one flag for the unsplit TU and four for the children, per component
     cbf = []
     for comp in range(3):
         c0 = rng.rand(n, n_cu_max) < cbf_prob
         c1 = rng.rand(n, n_cu_max, 4) < cbf_prob
-        if comp > 0:
+        if comp > 0 and csx:
             # 8x8 CUs split once: a single 4x4 chroma TU for the four 4x4 luma TUs; its flag is stored at both depths
+            # (4:4:4: every 4x4 luma TU has its own chroma twins)
             one = np.repeat(c1[:, :, :1], 4, axis=2)
             c1 = np.where((mode == 3)[:, None, None], one, c1)
+        if comp > 0 and chroma_format == 0:
+            c0, c1 = np.zeros_like(c0), np.zeros_like(c1)
         any1 = c1.any(axis=2)
         b0_unsplit = np.take_along_axis(c0, cu_idx, axis=1)
         b0_split = np.take_along_axis(any1, cu_idx, axis=1)
         flat = c1.reshape(n, n_cu_max * 4)
         b1 = np.take_along_axis(flat, cu_idx * 4 + child, axis=1)
         bits = np.where(tr_idx == 0, b0_unsplit.astype(np.int64), b0_split.astype(np.int64) | (b1.astype(np.int64) << 1))
+        if comp > 0 and fmt == 2:
+            # 4:2:2: which of the block's two squares are coded -- 0 both, 1 the upper one only, 2 the lower one only --, drawn per
+            # block like its flag; the squares' flags sit one depth below the block's bit, over the upper / lower half of the block's
+            # partitions.  The block of an 8x8 CU split once (4x8) belongs to the CU: halves of the CU, the draw of its first child
+            k0 = rng.randint(0, 3, size=(n, n_cu_max))
+            k1 = rng.randint(0, 3, size=(n, n_cu_max, 4))
+            k1 = np.where((mode == 3)[:, None, None], np.repeat(k1[:, :, :1], 4, axis=2), k1)
+            kind = np.where(tr_idx == 0, np.take_along_axis(k0, cu_idx, axis=1),
+                            np.take_along_axis(k1.reshape(n, n_cu_max * 4), cu_idx * 4 + child, axis=1))
+            blk_parts = np.where((tr_idx == 0) | (cu_parts == 4), cu_parts, np.maximum(cu_parts // 4, 1)) * np.ones((1, parts), dtype=np.int64)
+            lower = (z % blk_parts) >= blk_parts // 2
+            coded = ((bits >> tr_idx) & 1) != 0
+            sub = coded & np.where(lower, kind != 1, kind != 2)
+            bits = bits | (sub.astype(np.int64) << (tr_idx + 1))
         cbf.append(bits)
     # ---- intra prediction modes: one luma mode per CU (2Nx2N), chroma mode from HM's candidate set incl. DM (36)
     luma_mode_cu = rng.randint(0, 35, size=(n, n_cu_max))
@@ -151,8 +188,9 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     mv1 = np.where(inside[:, :, None], mv1, 0)
 
     # ---- coefficient levels in HM's layout
-    coef = [np.zeros((n, 4096), dtype=np.int16), np.zeros((n, 1024), dtype=np.int16), np.zeros((n, 1024), dtype=np.int16)]
-    log2cu_p = (6 - depth)
+    coef = [np.zeros((n, ctu * ctu), dtype=np.int16), np.zeros((n, ctu * ctu >> (csx + csy)), dtype=np.int16),
+            np.zeros((n, ctu * ctu >> (csx + csy)), dtype=np.int16)]
+    log2cu_p = (log2_ctu - depth)
     log2tu_p = log2cu_p - tr_idx
     decoded = inside & (part_size != abi.SIZE_NONE)
     for comp in range(3):
@@ -161,29 +199,51 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
         for log2tu_l in range(2, 6):           # luma TU size of the node
             tu_parts = 1 << (2 * max(log2tu_l - 2, 0))
             sel = has & (log2tu_p == log2tu_l)
-            if comp == 0 or log2tu_l > 2:
+            if comp == 0 or log2tu_l > 2 or not csx:
                 origin = sel & ((np.arange(parts)[None, :] % tu_parts) == 0)
-                size = (1 << log2tu_l) >> (1 if comp else 0)
+                size = (1 << log2tu_l) >> (csx if comp else 0)
+                blk_parts = tu_parts
             else:
                 origin = sel & ((np.arange(parts)[None, :] % 4) == 0)      # shared 4x4 chroma TU rides with the first child
                 size = 4
-            a_idx, z_idx = np.nonzero(origin)
-            if a_idx.size == 0:
-                continue
-            if coef_dist == "stress":
-                k = size
-                lev = rng.randint(-32768, 32768, size=(a_idx.size, k, k)).astype(np.int16)
-            elif coef_dist == "dense":       # every position of the TU small and non-zero-ish: all basis functions, few samples reach the final clip
-                k = size
-                lev = rng.randint(-3, 4, size=(a_idx.size, k, k)).astype(np.int16)
-            else:
-                k = min(size, 8)
-                lev = np.round(rng.laplace(0, 12, size=(a_idx.size, k, k))) * (rng.rand(a_idx.size, k, k) < 0.35)
-                lev = np.clip(lev, -32768, 32767).astype(np.int16)
-            off = (16 if comp == 0 else 4) * z_idx
-            rr, cc = np.meshgrid(np.arange(k), np.arange(k), indexing="ij")
-            flat_idx = off[:, None, None] + rr[None] * size + cc[None]
-            coef[comp][a_idx[:, None, None], flat_idx] = lev
+                blk_parts = 4
+            # the squares of the block: one, or in 4:2:2 chroma two of half the width one above the other, the upper one first; the
+            # lower one's flag is that of the first partition of the block's lower half
+            squares = [(origin, 0)]
+            if comp and fmt == 2:
+                sub_bit = (cbf[comp] >> (tr_idx + 1)) & 1
+                squares = [(origin & (sub_bit != 0), 0), (origin & (np.roll(sub_bit, -(blk_parts // 2), axis=1) != 0), size * size)]
+            for org, sq_off in squares:
+                a_idx, z_idx = np.nonzero(org)
+                if a_idx.size == 0:
+                    continue
+                if coef_dist == "stress":
+                    k = size
+                    lev = rng.randint(-32768, 32768, size=(a_idx.size, k, k)).astype(np.int16)
+                elif coef_dist == "dense":       # every position of the TU small and non-zero-ish: all basis functions, few samples reach the final clip
+                    k = size
+                    lev = rng.randint(-3, 4, size=(a_idx.size, k, k)).astype(np.int16)
+                else:
+                    k = min(size, 8)
+                    lev = np.round(rng.laplace(0, 12, size=(a_idx.size, k, k))) * (rng.rand(a_idx.size, k, k) < 0.35)
+                    lev = np.clip(lev, -32768, 32767).astype(np.int16)
+                off = ((16 * z_idx) >> ((csx + csy) if comp else 0)) + sq_off
+                rr, cc = np.meshgrid(np.arange(k), np.arange(k), indexing="ij")
+                flat_idx = off[:, None, None] + rr[None] * size + cc[None]
+                coef[comp][a_idx[:, None, None], flat_idx] = lev
+
+    # ---- cross-component prediction weights (4:4:4): per transform unit = luma TU, non-zero only where its luma block is coded
+    ccp = None
+    if fmt == 3 and ccp_prob > 0:
+        tu_first = np.arange(parts)[None, :] & ~(np.maximum(1 << (2 * (log2tu_p - 2)), 1) - 1)
+        chain = (1 << (tr_idx + 1)) - 1
+        luma_coded = decoded & ((cbf[0] & chain) == chain)
+        allowed = luma_coded & (~intra | (intra_dir_c == 36))
+        ccp = []
+        for comp in (1, 2):
+            w = np.array([1, 2, 4, 8])[rng.randint(0, 4, size=(n, parts))] * np.where(rng.rand(n, parts) < 0.5, -1, 1)
+            w = w * (rng.rand(n, parts) < ccp_prob)
+            ccp.append(np.where(allowed, np.take_along_axis(w, tu_first, axis=1), 0))
 
     # ---- SAO
     sao_raw = np.zeros((n, 3, 35), dtype=np.int32)
@@ -205,9 +265,13 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
             eo[:, 0] = np.abs(offs[:, 0]); eo[:, 1] = np.abs(offs[:, 1]); eo[:, 3] = -np.abs(offs[:, 2]); eo[:, 4] = -np.abs(offs[:, 3])
             sao_raw[:, comp, 3:] += np.where((kind >= 2)[:, None], eo, 0)
 
+    if chroma_format == 0:
+        sao_raw[:, 1:, :] = 0               # no chroma syntax in a monochrome stream: the parser leaves SAO_OFF (0)
     p = SynthPicture()
     p.width, p.height, p.bit_depth, p.num_ctus, p.ctus_w = width, height, bit_depth, n, cw
-    p.seq = abi.make_seq(width, height, bit_depth, bit_depth, log2_ctu=6, max_pictures=4)
+    p.seq = abi.make_seq(width, height, bit_depth, bdc, log2_ctu=log2_ctu, max_pictures=4)
+    p.seq.chroma_format = chroma_format
+    p.chroma_format, p.log2_ctu, p.bit_depth_chroma, p.csx, p.csy = chroma_format, log2_ctu, bdc, csx, csy
     handles = ref_handles if ref_handles is not None else ([0] * num_refs, [0])
     l0 = list(handles[0])[:max(num_refs, 1)]
     l1 = list(handles[1])[:1] if bi else []
@@ -234,6 +298,8 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
          "cbf_v": cbf[2], "mv0": mv0, "mv1": mv1, "ref_idx0": ref_idx0, "ref_idx1": ref_idx1,
          "intra_dir_l": np.where(intra, intra_dir_l, 1), "intra_dir_c": np.where(intra, intra_dir_c, 36)}
     m["slice_idx"] = slice_idx
+    if ccp is not None:
+        m["ccp_u"], m["ccp_v"] = ccp
     if not intra_modes:                 # the caller leaves intra CUs to somebody else: no modes, nothing reconstructed there
         del m["intra_dir_l"], m["intra_dir_c"]
     p.meta_np = m
@@ -261,17 +327,24 @@ def intra_sample_mask(p, comp):
     return mask
 
 
-def noise_planes(width, height, bit_depth, seed):
+def _plane_geometry(chroma_format, bit_depth, bit_depth_chroma):
+    """per component (log2 horizontal, log2 vertical subsampling, bit depth); 4:0:0 keeps 4:2:0-shaped chroma planes (hmgpu_seq_params)"""
+    csx, csy = (0 if chroma_format == 3 else 1), (1 if chroma_format in (0, 1) else 0)
+    bdc = bit_depth if bit_depth_chroma is None else bit_depth_chroma
+    return [(0, 0, bit_depth), (csx, csy, bdc), (csx, csy, bdc)]
+
+
+def noise_planes(width, height, bit_depth, seed, chroma_format=1, bit_depth_chroma=None):
     rng = np.random.RandomState(seed)
-    return [rng.randint(0, 1 << bit_depth, size=(height >> (1 if c else 0), width >> (1 if c else 0))).astype(np.int16) for c in range(3)]
+    return [rng.randint(0, 1 << bd, size=(height >> sy, width >> sx)).astype(np.int16) for sx, sy, bd in _plane_geometry(chroma_format, bit_depth, bit_depth_chroma)]
 
 
-def blocky_planes(width, height, bit_depth, seed):
+def blocky_planes(width, height, bit_depth, seed, chroma_format=1, bit_depth_chroma=None):
     """low-pass noise + 8x8 blocking steps: splits the deblocking decisions between off / weak / strong"""
     rng = np.random.RandomState(seed)
     out = []
-    for c in range(3):
-        w, h = width >> (1 if c else 0), height >> (1 if c else 0)
+    for sx, sy, bit_depth in _plane_geometry(chroma_format, bit_depth, bit_depth_chroma):
+        w, h = width >> sx, height >> sy
         base = rng.randint(0, 1 << bit_depth, size=((h + 15) // 16 + 1, (w + 15) // 16 + 1)).astype(np.float64)
         up = np.kron(base, np.ones((16, 16)))[:h, :w]
         for _ in range(2):
@@ -280,3 +353,58 @@ def blocky_planes(width, height, bit_depth, seed):
         up = up * 0.6 + (1 << (bit_depth - 1)) * 0.4 + np.kron(steps, np.ones((8, 8)))[:h, :w] + rng.randint(-2, 3, size=(h, w))
         out.append(np.clip(np.round(up), 0, (1 << bit_depth) - 1).astype(np.int16))
     return out
+
+
+def coded_blocks(meta, chroma_format, log2_ctu):
+    """The coded transform blocks of a picture, from HM's per-partition arrays alone (meta: dict with depth, part_size, tr_idx, cbf_y /
+    cbf_u / cbf_v as [num_ctus, parts]): an int64 array [N, 4] of (component, CTU, offset of the block in the CTU's piece of the
+    component's level array, size of the square block).  The rules are those of include/hmgpu.h (hmgpu_coeffs): a block is coded iff the
+    cbf bits of its transform unit are set down to the unit's transform depth; luma at 16 * z; chroma at (16 * z) >> (csx + csy), half the
+    size in 4:2:0 (the four 4x4 luma TUs of an 8x8 node share the 4x4 block at the first of them), the luma size in 4:4:4, and in 4:2:2
+    two squares of half the width, the lower one behind the upper one, each coded iff its own flag -- one transform depth below the unit's
+    bit, at the first partition of the upper / lower half of the block's partitions -- is set.  make_picture lays its levels out by the same
+    rules but in code of its own; tests/test_synth_formats_cpu.py holds this function against HM's own fixtures."""
+    fmt = 1 if chroma_format == 0 else chroma_format
+    csx, csy = (0 if fmt == 3 else 1), (1 if fmt == 1 else 0)
+    depth, tr = np.asarray(meta["depth"]).astype(np.int64), np.asarray(meta["tr_idx"]).astype(np.int64)
+    n, parts = depth.shape
+    decoded = np.asarray(meta["part_size"]) != abi.SIZE_NONE
+    log2tu = log2_ctu - depth - tr
+    z = np.arange(parts)[None, :]
+    tu_parts = 1 << (2 * np.maximum(log2tu - 2, 0))
+    chain = (1 << (tr + 1)) - 1
+    out = []
+    for comp, key in enumerate(("cbf_y", "cbf_u", "cbf_v")):
+        if comp and chroma_format == 0:
+            break
+        cbf = np.asarray(meta[key]).astype(np.int64)
+        coded = decoded & ((cbf & chain) == chain) & (log2tu >= 2) & (log2tu <= 5)
+        shared = (log2tu == 2) & (comp > 0) & (csx == 1)           # the chroma block of an 8x8 node with four 4x4 luma TUs
+        blk_parts = np.where(shared, 4, tu_parts)
+        origin = coded & ((z % blk_parts) == 0)
+        size = np.where(shared, 4, (1 << log2tu) >> (csx if comp else 0))
+        off = (16 * z[0]) >> ((csx + csy) if comp else 0)
+        squares = [(origin, 0)]
+        if comp and fmt == 2:
+            sub = (cbf >> (tr + 1)) & 1
+            a, zz = np.nonzero(origin)
+            low = np.zeros_like(origin)
+            low[a, zz] = sub[a, zz + blk_parts[a, zz] // 2] != 0
+            squares = [(origin & (sub != 0), 0), (low, 1)]
+        for org, second in squares:
+            a, zz = np.nonzero(org)
+            sz = size[a, zz] * np.ones_like(a)
+            out.append(np.stack([np.full(a.shape, comp, dtype=np.int64), a, off[zz] + second * sz * sz, sz], axis=1))
+    return np.concatenate(out, axis=0) if out else np.zeros((0, 4), dtype=np.int64)
+
+
+def block_mask(blocks, num_ctus, elems):
+    """boolean [3][num_ctus, elems[comp]]: True at the level positions the blocks of coded_blocks() cover"""
+    masks = [np.zeros((num_ctus, e), dtype=bool) for e in elems]
+    for comp in range(3):
+        b = blocks[blocks[:, 0] == comp]
+        for sz in np.unique(b[:, 3]):
+            s = b[b[:, 3] == sz]
+            idx = s[:, 2][:, None] + np.arange(sz * sz)[None, :]
+            masks[comp][s[:, 1][:, None], idx] = True
+    return masks
