@@ -88,6 +88,7 @@ void hmdec_set_packed_input(libHMDec_context* ctx, int on);
 #ifndef HMGPU_H
 typedef struct hmgpu_export_desc hmgpu_export_desc;
 typedef struct hmgpu_export_scale hmgpu_export_scale;
+typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -95,6 +96,14 @@ int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmg
 /* the same with scaling (hmgpu_picture_export_scaled), under the same rules */
 int hmdec_picture_export_scaled(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                 void* const dst[3], const int64_t pitch_bytes[3], int on_stream, void* stream);
+/* Up to 16 pictures in one call (hmgpu_pictures_export: scale NULL = unscaled, tensor NULL = unsigned integers; plane k of picture i at
+ * dst[k] + i * batch_stride_bytes[k]).  Every picture must have been put out by this decoder and still be valid (fetched since the last
+ * push), be of one sequence and sit on one GPU ordinal, else HMGPU_EINVAL and nothing is written.  With hmdec_set_devices the pictures
+ * may sit in several device contexts of that GPU: the destination is validated once for the whole batch
+ * (hmgpu_export_destination_check), then each context gets one call for its slots (more where its slots are not equally far apart). */
+int hmdec_pictures_export(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                          const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, void* const dst[3],
+                          const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

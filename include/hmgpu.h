@@ -348,6 +348,43 @@ hmgpu_status hmgpu_export_scale_taps(const hmgpu_seq_params* seq, const hmgpu_ex
  * last export that read it has finished). */
 hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* ctx, hmgpu_pic pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                          void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream);
+/* Batched tensor export: up to HMGPU_EXPORT_MAX_BATCH pictures of the context in one call, as unsigned integers
+ * (what the two calls above write) or as float16 / bfloat16 / float32 with a per-plane affine map, ready to feed a model.
+ *   v = the integer the export of `desc` (scaled when `scale` is given) writes for a sample, before the msb_aligned shift
+ *   HMGPU_SAMPLE_UINT   v, then the msb_aligned shift: slot i of a batch is bit for bit what the single-picture call writes
+ *   a float type        convert(fadd(fmul((float)v, scale[k]), bias[k])) for output plane k: the product and the sum are two
+ *                       separately rounded binary32 operations (never one fma), and the conversion to float16 / bfloat16 rounds to
+ *                       nearest even, overflow to infinity, denormals kept.  numpy's float32 `*`, `+` and astype restate it exactly.
+ * Float types: msb_aligned must be 0 and every scale / bias finite (else HMGPU_EINVAL); desc->bit_depth chooses the integer depth D
+ * of v, and bytes_per_sample must be what an unsigned export of that depth needs (1 when no plane's depth exceeds 8, else 2; else
+ * HMGPU_EINVAL); the RGB and planar layouts only (semi-planar: HMGPU_EUNSUPPORTED).  reserved must be 0 (else HMGPU_EINVAL). */
+enum { HMGPU_SAMPLE_UINT = 0, HMGPU_SAMPLE_F16 = 1, HMGPU_SAMPLE_BF16 = 2, HMGPU_SAMPLE_F32 = 3 };
+enum { HMGPU_EXPORT_MAX_BATCH = 16 };
+typedef struct hmgpu_export_tensor {
+  int32_t sample_type;         /* HMGPU_SAMPLE_* */
+  float scale[3], bias[3];     /* float types: per output plane (R, G, B or Y, Cb, Cr); ignored for HMGPU_SAMPLE_UINT */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_export_tensor;
+/* the plan of the unscaled (scale NULL) or scaled export of `desc`, with row_bytes at the element size of tensor->sample_type
+ * (tensor NULL: HMGPU_SAMPLE_UINT); host code, no device needed */
+hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          const hmgpu_export_tensor* tensor, hmgpu_export_plan* out);
+/* Enqueues the export of pics[0 .. n) (n = 1 .. HMGPU_EXPORT_MAX_BATCH; a handle may appear more than once) and returns without
+ * waiting: plane k of picture i goes to dst[k] + i * batch_stride_bytes[k], rows pitch_bytes[k] apart -- one [N, 3, H, W] tensor
+ * (dst[k] = base + k * plane stride) as well as a tuple of [N, H, W] planes.  scale NULL: unscaled; tensor NULL: HMGPU_SAMPLE_UINT.
+ * One kernel launch per call, and the stream ordering of hmgpu_picture_export once per call (one event pair in, one out, when
+ * on_stream is 1).  Everything is validated before anything is enqueued and a refused call leaves the destination untouched:
+ * an invalid handle anywhere in the list, n outside its range, a batch stride smaller than pitch * (height - 1) + row_bytes of its
+ * plane, and a plane whose bytes [dst[k], dst[k] + (n - 1) * batch stride + pitch * (height - 1) + row_bytes) do not lie inside one
+ * allocation of the context's device all give HMGPU_EINVAL. */
+hmgpu_status hmgpu_pictures_export(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                   const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, void* const dst[3],
+                                   const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* the validation hmgpu_pictures_export makes of a descriptor and a destination for n pictures, and nothing else: nothing is enqueued
+ * and no picture is named.  For callers that spread one batch over several calls (libhmdec, pictures in several contexts of a GPU). */
+hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                            const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
+                                            const int64_t batch_stride_bytes[3]);
 
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->

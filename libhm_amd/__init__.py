@@ -88,6 +88,14 @@ def lib():
                                               C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]
         L.hmgpu_picture_export_scaled.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_tensor_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                            C.POINTER(abi.ExportTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.c_int32, C.c_void_p]
+        L.hmgpu_export_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                     C.POINTER(abi.ExportTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                     C.POINTER(C.c_int64)]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -158,6 +166,16 @@ def export_scaled_plan(seq, desc, scale):
     st = lib().hmgpu_export_scaled_plan_for(C.byref(seq), C.byref(desc), C.byref(scale), C.byref(plan))
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_scaled_plan_for")
+    return plan
+
+
+def export_tensor_plan(seq, desc, scale=None, tensor=None):
+    """what an export writes (hmgpu_export_tensor_plan_for: host code, no GPU): scale None = unscaled, tensor None = unsigned integers"""
+    plan = abi.ExportPlan()
+    st = lib().hmgpu_export_tensor_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
+                                            C.byref(tensor) if tensor is not None else None, C.byref(plan))
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_tensor_plan_for")
     return plan
 
 
@@ -322,13 +340,54 @@ class Context:
             self._chk(lib().hmgpu_picture_export_scaled(self._h, pic, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None)),
                       "hmgpu_picture_export_scaled")
 
+    def export_batch_into(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None):
+        """hmgpu_pictures_export into device memory the caller owns: plane k of picture i at ptrs[k] + i * bstrides[k] (bytes)"""
+        pics = list(pics)
+        h = (C.c_int32 * max(len(pics), 1))(*pics)
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        self._chk(lib().hmgpu_pictures_export(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
+                                              C.byref(tensor) if tensor is not None else None, p, q, b, on_stream, C.c_void_p(stream or None)),
+                  "hmgpu_pictures_export")
+
+    def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
+        """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None,
+                                                    C.byref(tensor) if tensor is not None else None, p, q, b)
+
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
-               size=None, filter="bilinear", out=None):
+               size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
-        (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it"""
+        (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
+        gives normalised float elements (export_batch with one picture, without the batch dimension)"""
         from . import export
-        return export.export_tensors(lambda desc, scale, ptrs, pitches, st: self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st, scale),
-                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter, out)
+
+        def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
+            if tensor is None:
+                return self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st, sc)
+            plan = export_tensor_plan(self.seq, desc, sc, tensor)
+            extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+            self.export_batch_into([pic], desc, ptrs, pitches, extent, 1 if on_stream else 0, st, sc, tensor)
+        return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
+                                     filter, out, None, dtype, mean, std, scale, bias)
+
+    def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
+                     size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+        """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
+        with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
+        dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
+        (scale, bias) = export.affine(output depth, mean, std) -- (v / (2^D - 1) - mean_k) / std_k -- or explicit scale= / bias=
+        triples.  out: a tensor (or tuple of planes) of that shape; rows, planes and batch entries may be any stride apart."""
+        from . import export
+        pics = list(pics)
+        return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
+                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor),
+                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
+                                     out, len(pics), dtype, mean, std, scale, bias)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

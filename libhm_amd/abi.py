@@ -111,6 +111,22 @@ def make_export_scale(width, height, filter=SCALE_BILINEAR):
     return s
 
 
+SAMPLE_UINT, SAMPLE_F16, SAMPLE_BF16, SAMPLE_F32 = 0, 1, 2, 3
+EXPORT_MAX_BATCH = 16
+
+
+class ExportTensor(C.Structure):
+    _fields_ = [("sample_type", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3), ("reserved", C.c_int32 * 5)]
+
+
+def make_export_tensor(sample_type, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
+    t = ExportTensor()
+    t.sample_type = sample_type
+    for k in range(3):
+        t.scale[k], t.bias[k] = float(scale[k]), float(bias[k])
+    return t
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

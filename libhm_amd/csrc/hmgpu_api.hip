@@ -128,7 +128,7 @@ struct hmgpu_ctx {
   hipEvent_t exp_ev[2] = {};             // hmgpu_picture_export on a caller's stream: picture ready / export done (created when first used)
   // hmgpu_picture_export_scaled: resampling tables in device memory, one slot per export shape, least recently used slot reused
   struct ScaleSlot {
-    int32_t key[8] = {};                 // crop[4], output width / height, filter, RGB
+    int32_t key[8] = {};                 // crop[4], output width / height, filter, RGB | the classes' starting tiles (log2 tw, log2 th) << 1
     bool valid = false, pending = false; // pending: `done` stands for an export that read the slot
     uint64_t used = 0;
     char* dev = nullptr;                 // the tables (ScaleTable)
@@ -1236,17 +1236,6 @@ static bool device_span_ok(const void* p, size_t bytes, int device) {
   return q >= b && q - b + bytes <= size;
 }
 
-// every plane's destination inside one allocation of the context's device; vec is cleared unless every plane may take 4-sample stores
-static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& plan, int B, void* const dst[3], const int64_t pitch_bytes[3],
-                                  bool* vec) {
-  for (int k = 0; k < plan.planes; k++) {
-    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    if (!device_span_ok(dst[k], (size_t)pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k], c->device)) return HMGPU_EINVAL;
-    *vec = *vec && ((uintptr_t)dst[k] % (4 * B)) == 0 && pitch_bytes[k] % (4 * B) == 0;
-  }
-  return HMGPU_OK;
-}
-
 // the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device
 static hmgpu_status export_stream(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
   *hs = c->stream;
@@ -1270,52 +1259,15 @@ static hmgpu_status export_begin(hmgpu_ctx* c, int32_t on_stream, hipStream_t hs
 }
 
 // after the export's launch
-static hmgpu_status export_end(hmgpu_ctx* c, hmgpu_pic pic, int32_t on_stream, hipStream_t hs) {
+static hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs) {
   HIP_TRY(c, hipGetLastError());
   if (on_stream) {
     HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
   }
-  touch(c, pic);
+  for (int i = 0; i < n; i++) touch(c, pics[i]);
   commit_use(c);
   return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
-                                  int32_t on_stream, void* stream) {
-  if (!c || !valid_pic(c, pic) || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  hmgpu_export_plan plan;
-  { const hmgpu_status st = hmgpu_export_plan_for(&c->seq, d, &plan); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  const int B = d->bytes_per_sample;
-  bool vec = (d->crop[0] & 3) == 0;
-  { const hmgpu_status st = export_dst_ok(c, plan, B, dst, pitch_bytes, &vec); if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  const Picture& p = c->pics[pic];
-  int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-  ExportArgs a;
-  memset(&a, 0, sizeof(a));
-  const int x0 = d->crop[0], y0 = d->crop[2];
-  a.y = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
-  a.c = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
-  a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
-  a.layout = d->layout; a.bytes = B; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-  a.w = plan.width[0]; a.h = plan.height[0];
-  a.cw = (plan.width[0]) >> c->csx; a.ch = plan.height[0] >> c->csy;
-  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
-  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
-  const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
-  const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
-  a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
-  a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
-  a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
-  a.vec = vec ? 1 : 0;
-  for (int k = 0; k < 3; k++) { a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr; a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0; }
-  memcpy(a.coef, plan.coef, sizeof(a.coef));
-  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
-  launch_export(a, hs);
-  return export_end(c, pic, on_stream, hs);
 }
 
 // ------------------------------------------------------------------------------------------------ scaled export (k_export_scale.hip)
@@ -1520,19 +1472,26 @@ std::vector<int32_t> scale_spans(const ScaleTab& t, int n, int tile) {
   return sp;
 }
 
-ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int outh, int x0, int C) {
-  const int G = C == 2 ? 4 : 8;
-  ScaleTiles z;
-  z.tw = 128;
-  while (z.tw > 4 && z.tw / 2 >= outw) z.tw /= 2;
-  z.th = 1024 / z.tw;
-  while (z.th > 1 && z.th / 2 >= outh) z.th /= 2;
-  auto blocks = [&]() { return (long long)((outw + z.tw - 1) / z.tw) * ((outh + z.th - 1) / z.th); };
-  while (blocks() < 1024 && z.tw * z.th > 64) {      // (large reductions: small tiles, or a few workgroups would do all the work)
-    if (z.th >= z.tw / 4 && z.th > 2) z.th /= 2;
-    else if (z.tw > 16) z.tw /= 2;
+// the tile a class starts from: wide for sharing source samples, shrunk towards 64 outputs while the n pictures of a call bring fewer
+// than ~1000 workgroups (large reductions: or a few workgroups would do all the work)
+void scale_tile_start(int outw, int outh, int n, int* tw_out, int* th_out) {
+  int tw = 128;
+  while (tw > 4 && tw / 2 >= outw) tw /= 2;
+  int th = 1024 / tw;
+  while (th > 1 && th / 2 >= outh) th /= 2;
+  auto blocks = [&]() { return (long long)((outw + tw - 1) / tw) * ((outh + th - 1) / th); };
+  while (blocks() * n < 1024 && tw * th > 64) {
+    if (th >= tw / 4 && th > 2) th /= 2;
+    else if (tw > 16) tw /= 2;
     else break;
   }
+  *tw_out = tw; *th_out = th;
+}
+
+ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int outh, int x0, int C, int tw, int th) {
+  const int G = C == 2 ? 4 : 8;
+  ScaleTiles z;
+  z.tw = tw; z.th = th;
   for (;;) {
     z.span[0] = scale_spans(tx, outw, z.tw);
     z.cap = 0;
@@ -1552,7 +1511,7 @@ ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int out
 }
 
 // the slot that holds the tables of `key`: found, or filled (least recently used slot) with a copy enqueued on hs
-hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s, bool rgb, int x0c[2], hipStream_t hs, hmgpu_ctx::ScaleSlot** out) {
+hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s, bool rgb, int x0c[2], const int tile[2][2], hipStream_t hs, hmgpu_ctx::ScaleSlot** out) {
   hmgpu_ctx::ScaleSlot* slot = nullptr;
   for (auto& sl : c->scale_slot)
     if (sl.valid && !memcmp(sl.key, key, sizeof(sl.key))) { slot = &sl; break; }
@@ -1569,7 +1528,7 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
     size_t off[2][2][4], bytes = 0;
     for (int k = 0; k < s.classes; k++) {
       const int C = rgb ? 3 : k ? 2 : 1;
-      z[k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], x0c[k], C);
+      z[k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], x0c[k], C, tile[k][0], tile[k][1]);
       for (int ax = 0; ax < 2; ax++) {
         const size_t n = (size_t)s.out[k][ax], sizes[4] = {4 * n, 4 * n, 4 * z[k].span[ax].size(), 2 * n * (size_t)s.tab[k][ax]->taps};
         for (int f = 0; f < 4; f++) { off[k][ax][f] = bytes; bytes += align_up(sizes[f], 256); }
@@ -1618,50 +1577,185 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
 
 }  // namespace
 
-hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
-  if (!c || !valid_pic(c, pic) || !d || !sc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+// ------------------------------------------------------------------------------------------------ the export entry points
+// the output element (kElem*) of a descriptor already validated by its plan function, and of `t` (null: unsigned)
+static hmgpu_status export_elem(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int* elem) {
+  *elem = d->bytes_per_sample == 1 ? kElemU8 : kElemU16;
+  if (!t) return HMGPU_OK;
+  for (int k = 0; k < 5; k++) if (t->reserved[k]) return HMGPU_EINVAL;
+  if (t->sample_type < HMGPU_SAMPLE_UINT || t->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
+  if (t->sample_type == HMGPU_SAMPLE_UINT) return HMGPU_OK;
+  if (d->msb_aligned) return HMGPU_EINVAL;
+  for (int k = 0; k < 3; k++) if (!std::isfinite(t->scale[k]) || !std::isfinite(t->bias[k])) return HMGPU_EINVAL;
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
+  int D = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+  if (!rgb && seq->chroma_format != 0) D = std::max(D, d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma);
+  if (d->bytes_per_sample != (D <= 8 ? 1 : 2)) return HMGPU_EINVAL;      // the container an unsigned export of that depth needs
+  if (d->layout == HMGPU_EXPORT_SEMIPLANAR) return HMGPU_EUNSUPPORTED;
+  *elem = t->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : t->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+  return HMGPU_OK;
+}
+
+static int elem_size(int elem) { return elem == kElemU8 ? 1 : elem == kElemF32 ? 4 : 2; }
+
+static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
+  const hmgpu_status st = export_elem(seq, d, t, elem);
+  if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
+  if (*elem >= kElemF16)
+    for (int k = 0; k < out->planes; k++) out->row_bytes[k] = out->width[k] * elem_size(*elem);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, hmgpu_export_plan* out) {
+  int elem = 0;
+  return tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+}
+
+// every plane's destination, all n pictures of it, inside one allocation of the context's device (bstride null: one picture); vec is
+// cleared unless every group of 4 samples of every picture may be one store; bs: the batch strides in use
+static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& plan, int ES, int n, void* const dst[3],
+                                  const int64_t pitch_bytes[3], const int64_t* bstride, bool* vec, int64_t bs[3]) {
+  for (int k = 0; k < plan.planes; k++) {
+    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t extent = pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    if (bstride) {
+      if (bstride[k] < extent || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+      bs[k] = bstride[k];
+    }
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bs[k] + extent), c->device)) return HMGPU_EINVAL;
+    *vec = *vec && ((uintptr_t)dst[k] % (4 * ES)) == 0 && pitch_bytes[k] % (4 * ES) == 0 && (n == 1 || bs[k] % (4 * ES) == 0);
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                            const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  int elem = 0;
+  { const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, nullptr, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  bool vec = true;
+  int64_t bs[3];
+  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
+}
+
+// every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; bstride null: one picture, no batch
+// stride to check.  One launch, the stream ordering once.
+static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
+                                int32_t on_stream, void* stream) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   hmgpu_export_plan plan;
   ScaleShape s;
-  { const hmgpu_status st = scaled_plan(&c->seq, d, sc, &plan, &s); if (st != HMGPU_OK) return st; }
+  int elem = 0;
+  { const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem); if (st != HMGPU_OK) return st; }
   hipSetDevice(c->device);
-  const int B = d->bytes_per_sample;
-  bool vec = true;
-  { const hmgpu_status st = export_dst_ok(c, plan, B, dst, pitch_bytes, &vec); if (st != HMGPU_OK) return st; }
+  const int ES = elem_size(elem);
+  bool vec = sc ? true : (d->crop[0] & 3) == 0;
+  int64_t bs[3] = {0, 0, 0};
+  { const hmgpu_status st = export_dst_ok(c, plan, ES, n, dst, pitch_bytes, bstride, &vec, bs); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
   { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
-  const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, rgb ? 1 : 0};
+  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
+  const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
+  const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
+  const int x0 = d->crop[0], y0 = d->crop[2];
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  if (!sc) {
+    ExportArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < n; i++) {
+      const Picture& p = c->pics[pics[i]];
+      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+      a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
+      a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+    }
+    a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
+    a.n = n; a.layout = d->layout; a.elem = elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+    a.w = plan.width[0]; a.h = plan.height[0];
+    a.cw = (plan.width[0]) >> c->csx; a.ch = plan.height[0] >> c->csy;
+    a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
+    a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
+    a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
+    a.vec = vec ? 1 : 0;
+    for (int k = 0; k < 3; k++) {
+      a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
+      a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
+      a.bstride[k] = bs[k];
+      if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+    }
+    memcpy(a.coef, plan.coef, sizeof(a.coef));
+    launch_export(a, hs);
+    return export_end(c, n, pics, on_stream, hs);
+  }
+  // the tables' slot is keyed by the tiles the batch size leads to, not by the batch size: calls of varying n share a slot
+  int tile[2][2] = {{0, 0}, {0, 0}};
+  int32_t tkey = rgb ? 1 : 0;
+  for (int k = 0; k < s.classes; k++) {
+    scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
+    tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
+  }
+  const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
   int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
   hmgpu_ctx::ScaleSlot* slot = nullptr;
-  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, hs, &slot); if (st != HMGPU_OK) return st; }
-  const Picture& p = c->pics[pic];
-  int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+  { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
   ScaleArgs a;
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < s.classes; k++) {
     a.cls[k] = slot->cls[k];
-    a.cls[k].src = src[k];
     a.cls[k].pitch = c->pitch[k];
     a.cls[k].x0 = x0c[k];
     a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
   }
-  a.c = src[1]; a.pitch_c = c->pitch[1];
+  for (int i = 0; i < n; i++) {
+    const Picture& p = c->pics[pics[i]];
+    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+    a.src[i][0] = src[0]; a.src[i][1] = src[1];
+  }
+  a.pitch_c = c->pitch[1];
   a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
-  const int obY = s.depth[0], obC = rgb ? obY : s.depth[1];
-  a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
-  a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
-  a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
+  a.sh[0] = s.depth[0] - bdY; a.sh[1] = (rgb ? s.depth[0] : s.depth[1]) - bdC;
+  a.maxv[0] = (1 << s.depth[0]) - 1; a.maxv[1] = (1 << (rgb ? s.depth[0] : s.depth[1])) - 1;
+  a.msb[0] = d->msb_aligned ? 16 - s.depth[0] : 0; a.msb[1] = d->msb_aligned ? 16 - (rgb ? s.depth[0] : s.depth[1]) : 0;
   a.e = plan.coef[11];
   a.vec = vec ? 1 : 0;
-  for (int k = 0; k < 3; k++) { a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr; a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0; }
+  for (int k = 0; k < 3; k++) {
+    a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
+    a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
+    a.bstride[k] = bs[k];
+    if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+  }
   memcpy(a.coef, plan.coef, sizeof(a.coef));
-  launch_export_scaled(a, d->layout, B, hs);
+  launch_export_scaled(a, d->layout, elem, n, hs);
   HIP_TRY(c, hipEventRecord(slot->done, hs));
   slot->pending = true;
-  return export_end(c, pic, on_stream, hs);
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
+                                  int32_t on_stream, void* stream) {
+  return export_impl(c, 1, &pic, d, nullptr, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
+  if (!sc) return HMGPU_EINVAL;
+  return export_impl(c, 1, &pic, d, sc, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                   const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                   const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 
 // slice table entry of one slice (validation, SliceDev, scaling lists): the part of a slice call that does not depend on CTUs

@@ -297,18 +297,58 @@ struct Md5Batch { int32_t n, pad_; const uint8_t* msg[128]; unsigned long long b
 void launch_md5(const Md5Batch& job, hipStream_t s);
 void launch_crc(const int16_t* src, int pitch, int step, int w, int h, int bd, uint32_t* rows, uint32_t* out, hipStream_t s);
 void launch_intra(const PicDev* pics, const Batch& b, const int32_t* order, int num_ctus, bool lean, hipStream_t s);   // lean: no I slices in the call
-// device export of a finished picture (k_export.hip, hmgpu_picture_export): everything by value, validated on the host
+// device export of finished pictures (k_export.hip, hmgpu_picture_export / hmgpu_pictures_export): everything by value, validated on
+// the host.  A call converts n pictures (grid z); picture i writes plane k at dst[k] + i * bstride[k].
+constexpr int kMaxExportBatch = 16;
+// output element of an export kernel instance: 1- or 2-byte unsigned (container shift msb), or a float type that takes
+// convert(v * scale[k] + bias[k]) of the integer v (two binary32 roundings, then round to nearest even)
+enum { kElemU8 = 0, kElemU16 = 1, kElemF16 = 2, kElemBF16 = 3, kElemF32 = 4 };
+template <int ELEM> constexpr int elem_bytes() { return ELEM == kElemU8 ? 1 : ELEM == kElemF32 ? 4 : 2; }
+// n (<= 4) consecutive elements of one plane from the integers v; full groups of an aligned export as one 4-, 8- or 16-byte store.
+// Float elements: the product and the sum are rounded separately (no contraction into an fma), overflow gives infinity, denormals stay.
+template <int ELEM>
+__device__ inline void export_store4(uint8_t* d, const uint32_t v[4], int n, bool vec, int msb, float sc, float bi) {
+  uint32_t o[4];
+  for (int i = 0; i < 4; i++) {
+    if constexpr (ELEM <= kElemU16) {
+      o[i] = v[i] << msb;
+    } else {
+#pragma clang fp contract(off)
+      const float m = (float)(int)v[i] * sc;
+      const float f = m + bi;
+      const uint32_t u = __builtin_bit_cast(uint32_t, f);
+      if constexpr (ELEM == kElemF32) o[i] = u;
+      else if constexpr (ELEM == kElemF16) o[i] = __builtin_bit_cast(uint16_t, (_Float16)f);
+      else o[i] = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;      // bfloat16, nearest even (f is never a NaN: v, sc and bi are finite)
+    }
+  }
+  constexpr int B = elem_bytes<ELEM>();
+  if (vec && n == 4) {
+    if constexpr (B == 1) stg(reinterpret_cast<uint32_t*>(d), o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24);
+    else if constexpr (B == 2) { u32x2 w; w.x = o[0] | o[1] << 16; w.y = o[2] | o[3] << 16; stg2(d, w); }
+    else { u32x4 w; w.x = o[0]; w.y = o[1]; w.z = o[2]; w.w = o[3]; stg4(d, w); }
+    return;
+  }
+  for (int i = 0; i < n; i++) {
+    if constexpr (B == 1) stg(d + i, (uint8_t)o[i]);
+    else if constexpr (B == 2) stg(reinterpret_cast<uint16_t*>(d) + i, (uint16_t)o[i]);
+    else stg(reinterpret_cast<uint32_t*>(d) + i, o[i]);
+  }
+}
 struct ExportArgs {
-  const int16_t* y;                // luma sample (crop left, crop top)
-  const int16_t* c;                // Cb of chroma sample (crop left >> csx, crop top >> csy) in the pair plane (Cr one element on)
+  const int16_t* y[kMaxExportBatch];   // per picture: luma sample (crop left, crop top)
+  const int16_t* c[kMaxExportBatch];   // Cb of chroma sample (crop left >> csx, crop top >> csy) in the pair plane (Cr one element on)
   int32_t pitch_y, pitch_c;        // int16 elements
-  int32_t layout, bytes, mono, csx, csy;
+  int32_t n;                       // pictures
+  int32_t layout, elem, mono, csx, csy;   // elem: kElem*
   int32_t w, h, cw, ch;            // output luma / chroma size (chroma rows follow the luma rows in the grid, YUV layouts)
   int32_t sh[2], maxv[2];          // bit-depth rule per channel type: out - coding depth, 2^out - 1
   int32_t msb[2];                  // container shift per channel type (msb_aligned: 16 - out)
   int32_t vec;                     // every group of 4 samples may use vector loads and stores (alignment of crop, dst and pitches)
   uint8_t* dst[3];
   int64_t pitch[3];                // bytes
+  int64_t bstride[3];              // bytes between the planes of consecutive pictures
+  float scale[3], bias[3];         // float elements: per output plane
   int32_t coef[16];                // hmgpu_export_plan.coef
 };
 void launch_export(const ExportArgs& a, hipStream_t s);
@@ -330,22 +370,24 @@ struct ScaleClass {                // one plane class: 0 = luma (YUV) or RGB, 1 
   int32_t span_cap;                // LDS samples per row and channel: the widest source span of a tile in 16-byte groups
   int32_t tiles_x, blocks;         // tiles per row, workgroups of the class
   int32_t x0, y0;                  // crop origin in the class's plane (samples)
-  const int16_t* src;              // sample (0, 0) of the class's plane (chroma: Cb in the pair plane)
   int32_t pitch;                   // int16 elements
 };
 struct ScaleArgs {
   ScaleClass cls[2];
-  const int16_t* c;                // RGB: chroma sample (0, 0) (Cb) in the pair plane, rows pitch_c apart
-  int32_t pitch_c;
+  const int16_t* src[kMaxExportBatch][2];   // per picture (grid y): sample (0, 0) of the luma plane and of the pair plane (Cb)
+  int32_t pitch_c;                 // RGB: rows of the pair plane
   int32_t mono, csx, csy;
   int32_t sh[2], maxv[2], msb[2];  // bit-depth rule per channel type (as ExportArgs); RGB: maxv[0] = coef[9]
   int32_t e;                       // fractional bits kept between the passes (hmgpu_export_plan.coef[11])
   int32_t vec;                     // every group of 4 output samples may be one 4- or 8-byte store (alignment of dst and pitches)
   uint8_t* dst[3];
   int64_t pitch[3];                // bytes
+  int64_t bstride[3];              // bytes between the planes of consecutive pictures
+  float scale[3], bias[3];         // float elements: per output plane
   int32_t coef[16];                // hmgpu_export_plan.coef
 };
-void launch_export_scaled(const ScaleArgs& a, int layout, int bytes, hipStream_t s);
+// n pictures; elem: kElem*
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

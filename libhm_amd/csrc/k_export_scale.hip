@@ -1,5 +1,6 @@
-// k_export_scale.hip -- scaled device export (hmgpu_picture_export_scaled, include/hmgpu.h "scaled export"): a finished picture
-// converted as k_export.hip converts it and resized in the same pass, horizontally then vertically, with the host's Q14 tables.
+// k_export_scale.hip -- scaled device export (hmgpu_picture_export_scaled / hmgpu_pictures_export, include/hmgpu.h "scaled export"):
+// finished pictures converted as k_export.hip converts them and resized in the same pass, horizontally then vertically, with the
+// host's Q14 tables.  The pictures of a batch lie along the grid's y and share the tables and the tiling.
 //
 // One workgroup of 256 lanes owns a tile of tw x th outputs of one plane class (RGB: R, G and B together; YUV: Y, or Cb and Cr
 // together).  It walks the tile's source rows in passes of `rows` rows through LDS:
@@ -10,7 +11,8 @@
 //   3. each lane adds the rows of the pass that fall in the vertical windows of its four outputs (four adjacent columns of one row)
 //      to sums it keeps in registers.
 // After the last pass the sums are rounded, clipped and stored, 4 or 8 bytes per plane and lane where aligned.  No intermediate
-// leaves the workgroup.  One instance per layout and container size; the class, and the channels with it, is uniform per workgroup.
+// leaves the workgroup.  One instance per layout and output element (hmgpu_dev.h export_store4); the class, and the channels with
+// it, is uniform per workgroup.
 // Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
 // margin on both sides, and the tables never point at them.
 #include "hmgpu_dev.h"
@@ -27,23 +29,14 @@ __device__ inline void unpack8(const u32x4 w, int v[8]) {
   for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(w[i] & 0xffff); v[2 * i + 1] = (int16_t)(w[i] >> 16); }
 }
 
-template <int BYTES>
-__device__ inline void store4(uint8_t* d, const uint32_t o[4], int n, bool vec) {
-  if (vec && n == 4) {
-    if (BYTES == 1) stg(reinterpret_cast<uint32_t*>(d), o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24);
-    else { u32x2 w; w.x = o[0] | o[1] << 16; w.y = o[2] | o[3] << 16; stg2(d, w); }
-    return;
-  }
-  for (int i = 0; i < n; i++) {
-    if (BYTES == 1) stg(d + i, (uint8_t)o[i]);
-    else stg(reinterpret_cast<uint16_t*>(d) + i, (uint16_t)o[i]);
-  }
-}
-
 // C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane
-template <int LAYOUT, int BYTES, int C>
+template <int LAYOUT, int ELEM, int C>
 __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds) {
+  constexpr int BYTES = elem_bytes<ELEM>();
   constexpr int G = C == 2 ? 4 : 8;                       // samples per 16-byte group
+  const int pic = blockIdx.y;
+  const int16_t* const src = a.src[pic][C == 2 ? 1 : 0];  // the class's plane of this picture
+  const int16_t* const csrc = a.src[pic][1];              // RGB: its chroma
   const int chan = C == 2 ? 1 : 0;                        // channel type of the bit-depth rule
   const int tid = threadIdx.x;
   const int tyi = blk / k.tiles_x, txi = blk - tyi * k.tiles_x;
@@ -79,14 +72,14 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
       uint32_t o[C][8];
       if constexpr (C == 2) {
         int p[8];
-        unpack8(ldg4(k.src + (ptrdiff_t)y * k.pitch + kCStep * x), p);
+        unpack8(ldg4(src + (ptrdiff_t)y * k.pitch + kCStep * x), p);
         for (int s = 0; s < 4; s++) {
           o[0][s] = (uint32_t)depth_conv(p[2 * s], a.sh[1], a.maxv[1]);
           o[C - 1][s] = (uint32_t)depth_conv(p[2 * s + 1], a.sh[1], a.maxv[1]);
         }
       } else {
         int yv[8];
-        unpack8(ldg4(k.src + (ptrdiff_t)y * k.pitch + x), yv);
+        unpack8(ldg4(src + (ptrdiff_t)y * k.pitch + x), yv);
         if constexpr (C == 1) {
           for (int s = 0; s < 8; s++) o[0][s] = (uint32_t)depth_conv(yv[s], a.sh[0], a.maxv[0]);
         } else {
@@ -94,7 +87,7 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
           if (a.mono) {
             for (int s = 0; s < 8; s++) u[s] = v[s] = a.coef[3];
           } else {
-            const int16_t* cp = a.c + (ptrdiff_t)(y >> a.csy) * a.pitch_c + kCStep * (x >> a.csx);
+            const int16_t* cp = csrc + (ptrdiff_t)(y >> a.csy) * a.pitch_c + kCStep * (x >> a.csx);
             int p[16];
             unpack8(ldg4(cp), p);
             if (a.csx) {
@@ -175,43 +168,51 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
   const int M = a.maxv[chan], msb = a.msb[chan];
   uint32_t o[C][4];
   for (int c = 0; c < C; c++)
-    for (int q = 0; q < 4; q++) o[c][q] = (uint32_t)min(M, max(0, (acc[c][q] + vrnd) >> vsh)) << msb;
+    for (int q = 0; q < 4; q++) o[c][q] = (uint32_t)min(M, max(0, (acc[c][q] + vrnd) >> vsh));
   const int x = ox0 + vx, y = oy0 + vy, n = min(4, k.tx.n - x);
   const bool vec = a.vec != 0;
   if constexpr (C != 2) {
-    for (int c = 0; c < C; c++) store4<BYTES>(a.dst[c] + y * a.pitch[c] + (ptrdiff_t)x * BYTES, o[c], n, vec);
+    for (int c = 0; c < C; c++)
+      export_store4<ELEM>(a.dst[c] + pic * a.bstride[c] + y * a.pitch[c] + (ptrdiff_t)x * BYTES, o[c], n, vec, msb, a.scale[c], a.bias[c]);
   } else if (LAYOUT == HMGPU_EXPORT_PLANAR) {
-    store4<BYTES>(a.dst[1] + y * a.pitch[1] + (ptrdiff_t)x * BYTES, o[0], n, vec);
-    store4<BYTES>(a.dst[2] + y * a.pitch[2] + (ptrdiff_t)x * BYTES, o[C - 1], n, vec);
-  } else {                                    // semi-planar: the pairs interleaved
+    export_store4<ELEM>(a.dst[1] + pic * a.bstride[1] + y * a.pitch[1] + (ptrdiff_t)x * BYTES, o[0], n, vec, msb, a.scale[1], a.bias[1]);
+    export_store4<ELEM>(a.dst[2] + pic * a.bstride[2] + y * a.pitch[2] + (ptrdiff_t)x * BYTES, o[C - 1], n, vec, msb, a.scale[2], a.bias[2]);
+  } else if constexpr (ELEM <= kElemU16) {    // semi-planar (integer elements only): the pairs interleaved
     const uint32_t p0[4] = {o[0][0], o[C - 1][0], o[0][1], o[C - 1][1]}, p1[4] = {o[0][2], o[C - 1][2], o[0][3], o[C - 1][3]};
-    uint8_t* d = a.dst[1] + y * a.pitch[1] + (ptrdiff_t)x * 2 * BYTES;
-    store4<BYTES>(d, p0, min(4, 2 * n), vec);
-    if (n > 2) store4<BYTES>(d + 4 * BYTES, p1, 2 * n - 4, vec);
+    uint8_t* d = a.dst[1] + pic * a.bstride[1] + y * a.pitch[1] + (ptrdiff_t)x * 2 * BYTES;
+    export_store4<ELEM>(d, p0, min(4, 2 * n), vec, msb, 0.f, 0.f);
+    if (n > 2) export_store4<ELEM>(d + 4 * BYTES, p1, 2 * n - 4, vec, msb, 0.f, 0.f);
   }
 }
 
 }  // namespace
 
-template <int LAYOUT, int BYTES>
+template <int LAYOUT, int ELEM>
 __global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
   __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
   const int b = blockIdx.x;
-  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, BYTES, 3>(a, a.cls[0], b, lds);
-  else if (b < a.cls[0].blocks) scale_tile<LAYOUT, BYTES, 1>(a, a.cls[0], b, lds);
-  else scale_tile<LAYOUT, BYTES, 2>(a, a.cls[1], b - a.cls[0].blocks, lds);
+  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3>(a, a.cls[0], b, lds);
+  else if (b < a.cls[0].blocks) scale_tile<LAYOUT, ELEM, 1>(a, a.cls[0], b, lds);
+  else scale_tile<LAYOUT, ELEM, 2>(a, a.cls[1], b - a.cls[0].blocks, lds);
 }
 
-void launch_export_scaled(const ScaleArgs& a, int layout, int bytes, hipStream_t s) {
-  const dim3 grid((unsigned)(a.cls[0].blocks + (layout == HMGPU_EXPORT_RGB ? 0 : a.cls[1].blocks))), block(256);
-#define HMGPU_SCALE_CASE(L)                                                                  \
-  if (layout == L) {                                                                         \
-    if (bytes == 1) hipLaunchKernelGGL((k_export_scale<L, 1>), grid, block, 0, s, a);        \
-    else hipLaunchKernelGGL((k_export_scale<L, 2>), grid, block, 0, s, a);                   \
-  }
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB)
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s) {
+  const dim3 grid((unsigned)(a.cls[0].blocks + (layout == HMGPU_EXPORT_RGB ? 0 : a.cls[1].blocks)), (unsigned)n), block(256);
+#define HMGPU_SCALE_CASE(L, E) \
+  if (layout == L && elem == E) hipLaunchKernelGGL((k_export_scale<L, E>), grid, block, 0, s, a);
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemU8)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemU16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR, kElemU8)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR, kElemU16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemU8)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemU16)
+  // float elements: the planar and RGB layouts (the host refuses semi-planar)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemF16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemBF16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemF32)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemF16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemBF16)
+  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemF32)
 #undef HMGPU_SCALE_CASE
 }
 

@@ -996,6 +996,51 @@ hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc
   return hmgpu_picture_export(ctx_of(pic), pic->handle, desc, dst, pitch_bytes, on_stream, stream);
 }
 
+hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                       const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
+                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
+  flush_batch();
+  for (int i = 0; i < n; i++) {
+    const PicData* p = pics[i];
+    if (!p->on_device || !p->decoded) return HMGPU_EINVAL;               // (on the device: of the sequence whose contexts exist)
+    if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
+  }
+  // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
+  // the slots of one context as runs of equal distance (slot j of a run lies run-distance * batch stride after the one before), one
+  // hmgpu_pictures_export each: a single call when one context holds every picture.
+  { const hmgpu_status st = hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
+    if (st != HMGPU_OK) return st; }
+  struct Run { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; };
+  std::vector<Run> runs;
+  std::vector<bool> taken((size_t)n, false);
+  for (int i = 0; i < n; i++) {
+    if (taken[(size_t)i]) continue;
+    std::vector<int> idx;                                                // the slots of this context not yet in a run, ascending
+    for (int j = i; j < n; j++) if (!taken[(size_t)j] && pics[j]->home == pics[i]->home) idx.push_back(j);
+    size_t m = 1;
+    const int step = idx.size() > 1 ? idx[1] - idx[0] : 1;
+    while (m < idx.size() && idx[m] - idx[m - 1] == step) m++;
+    Run r;
+    r.home = pics[i]->home; r.first = i; r.step = step; r.n = (int)m;
+    for (size_t q = 0; q < m; q++) { r.h[q] = pics[idx[q]]->handle; taken[(size_t)idx[q]] = true; }
+    runs.push_back(r);
+  }
+  for (const Run& r : runs) {
+    void* d[3];
+    int64_t bs[3];
+    for (int k = 0; k < 3; k++) {
+      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+      bs[k] = batch_stride_bytes[k] * r.step;
+    }
+    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
+    const hmgpu_status st = hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row
 bool Decoder::md5_plane_matches(const PicData* pic, int comp, int bd, const uint8_t want[16]) {
   Md5 md5;

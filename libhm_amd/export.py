@@ -5,7 +5,12 @@ Colour policy (the one place it is decided): an RGB export takes `matrix` / `ful
 them None they come from the picture's VUI (matrix_coefficients, video_full_range_flag).  A stream without a colour description
 (matrix 2, "unspecified") is treated as BT.709 (matrix 1); without video_signal_type it is limited range (E.3.1's default).  Codes
 the kernel does not implement (anything but 0, 1, 5, 6, 9) are refused with HMGPU_EUNSUPPORTED rather than guessed.
+
+Tensor output (export_batch, dtype=): float16 / bfloat16 / float32 elements take fl(fl(v * scale_k) + bias_k) of the integer v the
+export writes, with (scale, bias) from `affine`: v / (2^D - 1) normalised by a per-plane mean and std.
 """
+import numpy as np
+
 from . import abi
 
 LAYOUTS = {"planar": abi.EXPORT_PLANAR, "yuv": abi.EXPORT_PLANAR, "semiplanar": abi.EXPORT_SEMIPLANAR, "nv12": abi.EXPORT_SEMIPLANAR,
@@ -41,11 +46,61 @@ def layout_code(layout):
         raise ValueError("unknown export layout %r (one of %s)" % (layout, ", ".join(sorted(LAYOUTS))))
 
 
-def make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned=False):
-    """bit_depth: an int for every channel type, a (luma, chroma) pair, or None / 0 for the coding bit depths"""
+def make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned=False, seq=None):
+    """bit_depth: an int for every channel type, a (luma, chroma) pair, or None / 0 for the coding bit depths.  seq (float output):
+    the container is the one the output depths need (1 byte when none exceeds 8), the coding depths taken from the sequence"""
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
-    nbytes = 2 if msb_aligned or max(bd) > 8 or min(bd) == 0 else 1
+    if seq is not None:
+        nbytes = 2 if max(plane_depths(seq, layout_code(layout), bd)) > 8 else 1
+    else:
+        nbytes = 2 if msb_aligned or max(bd) > 8 or min(bd) == 0 else 1
     return abi.make_export_desc(layout_code(layout), bd, nbytes, msb_aligned, tuple(crop), matrix, full_range)
+
+
+def plane_depths(seq, layout, bd):
+    """the integer depth D of every output plane: RGB the luma output depth three times; YUV luma, chroma, chroma (4:0:0: luma)"""
+    y = bd[0] or seq.bit_depth_luma
+    if layout == abi.EXPORT_RGB:
+        return (y, y, y)
+    if seq.chroma_format == 0:
+        return (y,)
+    c = bd[1] or seq.bit_depth_chroma
+    return (y, c, c)
+
+
+def affine(depth, mean=None, std=None):
+    """(scale, bias), float32 triples, that map an integer sample v of `depth` bits (an int, or one per plane) to
+    (v / (2^depth - 1) - mean_k) / std_k:  scale_k = 1 / ((2^D - 1) * std_k), bias_k = -mean_k / std_k, each computed in double and
+    rounded once.  mean None: 0, std None: 1 (values in [0, 1])."""
+    d = (depth,) * 3 if isinstance(depth, int) else tuple(depth) + (depth[-1],) * (3 - len(depth))
+    mean = (0.0,) * 3 if mean is None else tuple(float(m) for m in mean)
+    std = (1.0,) * 3 if std is None else tuple(float(v) for v in std)
+    scale = tuple(np.float32(1.0 / (float((1 << d[k]) - 1) * std[k])) for k in range(3))
+    bias = tuple(np.float32(-mean[k] / std[k]) for k in range(3))
+    return scale, bias
+
+
+def sample_type(dtype):
+    """abi.SAMPLE_* of a torch float dtype"""
+    import torch
+    try:
+        return {torch.float16: abi.SAMPLE_F16, torch.bfloat16: abi.SAMPLE_BF16, torch.float32: abi.SAMPLE_F32}[dtype]
+    except KeyError:
+        raise ValueError("dtype %r: None (unsigned integers), torch.float16, torch.bfloat16 or torch.float32" % (dtype,))
+
+
+def make_tensor(dtype, depths, mean=None, std=None, scale=None, bias=None):
+    """the abi.ExportTensor of a float dtype (None for dtype None): `affine` of the planes' depths, or an explicit scale / bias"""
+    if dtype is None:
+        if any(v is not None for v in (mean, std, scale, bias)):
+            raise ValueError("mean / std / scale / bias need a float dtype")
+        return None
+    sc, bi = affine(depths, mean, std)
+    if scale is not None:
+        sc = tuple(scale)
+    if bias is not None:
+        bi = tuple(bias)
+    return abi.make_export_tensor(sample_type(dtype), sc, bi)
 
 
 def make_scale(size, filter="bilinear"):
@@ -66,83 +121,87 @@ def plane_shapes(plan, desc):
             for k in range(plan.planes)]
 
 
-def _check_tensor(t, desc, device):
+def _check_tensor(t, desc, device, dtype=None):
     import torch
-    if t.dtype != torch_dtype(desc.bytes_per_sample) and not (desc.bytes_per_sample == 2 and t.dtype == torch.int16):
+    if dtype is not None:
+        if t.dtype != dtype:
+            raise ValueError("out: dtype %s, asked for %s" % (t.dtype, dtype))
+    elif t.dtype != torch_dtype(desc.bytes_per_sample) and not (desc.bytes_per_sample == 2 and t.dtype == torch.int16):
         raise ValueError("out: dtype %s, the plan gives %s" % (t.dtype, torch_dtype(desc.bytes_per_sample)))
     if t.get_device() != device:
         raise ValueError("out: on device %d, the picture is on %d" % (t.get_device(), device))
 
 
-def out_spans(out, plan, desc, device):
-    """a caller's destination (RGB: one [3, H, W] tensor or three planes; YUV: a tuple of planes) as (pointers, pitches in bytes)
-    per plane.  Each plane has the planned shape and dtype on the device and its samples dense within a row; rows may be any stride
-    apart (e.g. a view batch[i]).  Reads only shapes, strides and pointers: no views are made."""
+def out_spans(out, plan, desc, device, n=None, dtype=None):
+    """a caller's destination as (pointers, pitches in bytes, batch strides in bytes or None) per plane.  n None, one picture: RGB
+    one [3, H, W] tensor or three planes, YUV a tuple of planes.  n pictures: the same with a leading dimension of n ([n, 3, H, W];
+    planes [n, H, W], [n, Hc, Wc, 2]).  Each plane has the planned shape and dtype on the device and its samples dense within a
+    row; rows, planes and batch entries may be any stride apart (e.g. a view batch[i]).  Reads only shapes, strides and pointers:
+    no views are made."""
     import torch
     shapes = plane_shapes(plan, desc)
+    lead = () if n is None else (n,)
+    b = len(lead)
     if isinstance(out, torch.Tensor):
         if desc.layout != abi.EXPORT_RGB:
             raise ValueError("out: the planar / semi-planar layouts take a tuple of planes")
         h, w = shapes[0]
-        if out.shape != (3, h, w):
-            raise ValueError("out: shape %s, the plan gives %s" % (tuple(out.shape), (3, h, w)))
-        _check_tensor(out, desc, device)
-        s0, s1, s2 = out.stride()
+        if out.shape != lead + (3, h, w):
+            raise ValueError("out: shape %s, the plan gives %s" % (tuple(out.shape), lead + (3, h, w)))
+        _check_tensor(out, desc, device, dtype)
+        st = out.stride()
+        s0, s1, s2 = st[b:]
         if s2 != 1 or s1 < w or s0 < s1 * (h - 1) + w:
-            raise ValueError("out: the planes' samples must be dense within a row, rows and planes apart (stride %s)" % ((s0, s1, s2),))
+            raise ValueError("out: the planes' samples must be dense within a row, rows and planes apart (stride %s)" % (st,))
         es, base = out.element_size(), out.data_ptr()
-        return [base + k * s0 * es for k in range(3)], [s1 * es] * 3
+        return [base + k * s0 * es for k in range(3)], [s1 * es] * 3, [st[0] * es] * 3 if b else None
     planes = tuple(out)
     if len(planes) != len(shapes):
         raise ValueError("out: %d planes, the plan gives %d" % (len(planes), len(shapes)))
-    ptrs, pitches = [], []
+    ptrs, pitches, bstrides = [], [], []
     for p, shape in zip(planes, shapes):
-        if not isinstance(p, torch.Tensor) or p.shape != shape:
-            raise ValueError("out: a plane is not a tensor of shape %s" % (shape,))
-        _check_tensor(p, desc, device)
+        if not isinstance(p, torch.Tensor) or p.shape != lead + shape:
+            raise ValueError("out: a plane is not a tensor of shape %s" % (lead + shape,))
+        _check_tensor(p, desc, device, dtype)
         st = p.stride()
         inner = (1,) if len(shape) == 2 else (2, 1)
-        if st[1:] != inner or st[0] < shape[1] * inner[0]:
+        if st[b + 1:] != inner or st[b] < shape[1] * inner[0]:
             raise ValueError("out: a plane's samples must be dense within a row (stride %s)" % (st,))
         ptrs.append(p.data_ptr())
-        pitches.append(st[0] * p.element_size())
-    return ptrs, pitches
+        pitches.append(st[b] * p.element_size())
+        bstrides.append(st[0] * p.element_size())
+    return ptrs, pitches, bstrides if b else None
 
 
-def alloc_outputs(plan, desc, device):
-    """torch tensors for what `plan` describes: RGB [3, H, W]; planar (Y, Cb, Cr) 2-D; semi-planar (Y [H, W], CbCr [Hc, Wc, 2]).
-    Returns (result, per-plane tensors)."""
+def alloc_outputs(plan, desc, device, n=None, dtype=None):
+    """torch tensors for what `plan` describes: RGB [3, H, W]; planar (Y, Cb, Cr) 2-D; semi-planar (Y [H, W], CbCr [Hc, Wc, 2]);
+    with n, each with a leading dimension of n.  dtype None: the unsigned type of the container."""
     import torch
-    dt = torch_dtype(desc.bytes_per_sample)
+    dt = torch_dtype(desc.bytes_per_sample) if dtype is None else dtype
     dev = torch.device("cuda", device)
+    lead = () if n is None else (n,)
     if desc.layout == abi.EXPORT_RGB:
-        t = torch.empty((3, plan.height[0], plan.width[0]), dtype=dt, device=dev)
-        return t, [t[0], t[1], t[2]]
-    planes = []
-    for k in range(plan.planes):
-        if desc.layout == abi.EXPORT_SEMIPLANAR and k == 1:
-            planes.append(torch.empty((plan.height[1], plan.width[1], 2), dtype=dt, device=dev))
-        else:
-            planes.append(torch.empty((plan.height[k], plan.width[k]), dtype=dt, device=dev))
-    return tuple(planes), planes
+        return torch.empty(lead + (3, plan.height[0], plan.width[0]), dtype=dt, device=dev)
+    return tuple(torch.empty(lead + shape, dtype=dt, device=dev) for shape in plane_shapes(plan, desc))
 
 
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
-                   filter="bilinear", out=None):
-    """allocate with torch on `device` (or take `out`) and run `call(desc, scale, ptrs, pitches, stream)` on torch's current stream;
-    scale: None (size None), else the abi.ExportScale of size (height, width) and filter"""
+                   filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+    """allocate with torch on `device` (or take `out`) and run `call(desc, scale, tensor, ptrs, pitches, bstrides, stream)` on torch's
+    current stream.  scale: None (size None), else the abi.ExportScale of size (height, width) and filter; tensor: None (dtype None),
+    else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); bstrides: None for one picture
+    (n None), else the bytes between the batch entries of every plane of the n pictures."""
     import torch
-    from . import export_plan, export_scaled_plan
-    desc = make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned)
-    scale = make_scale(size, filter)
-    plan = export_plan(seq, desc) if scale is None else export_scaled_plan(seq, desc, scale)
+    from . import export_tensor_plan
+    bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
+    desc = make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned, seq if dtype is not None else None)
+    sc = make_scale(size, filter)
+    tensor = make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias)
+    plan = export_tensor_plan(seq, desc, sc, tensor)
     with torch.cuda.device(device):
         if out is None:
-            out, planes = alloc_outputs(plan, desc, device)
-            ptrs = [p.data_ptr() for p in planes]
-            pitches = [p.stride(0) * p.element_size() for p in planes]
-        else:
-            ptrs, pitches = out_spans(out, plan, desc, device)
+            out = alloc_outputs(plan, desc, device, n, dtype)
+        ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype)
         stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
-        call(desc, scale, ptrs, pitches, stream)
+        call(desc, sc, tensor, ptrs, pitches, bstrides, stream)
     return out

@@ -72,6 +72,9 @@ def lib():
                                            C.c_int, C.c_void_p]
         L.hmdec_picture_export_scaled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                            C.POINTER(abi.ExportTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -212,30 +215,69 @@ class Picture:
             raise HmgpuError(st, name)
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-               filter="bilinear", out=None):
+               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
         VUI (the colour policy of libhm_amd.export); size: (height, width) of the output, resized with `filter` ("nearest",
         "bilinear", "bicubic", "area"), None = the crop's size; out: a tensor (or tuple of planes) of the planned shape to write
-        instead of new ones.  Valid until the next push into the decoder."""
-        from . import export
-        if self.ctx is None:
-            raise RuntimeError("Picture.export: the picture does not know its decoder")
-        g = self.geometry()
-        seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
-        seq.chroma_format = g["chroma_format"]
-        if crop == "conformance":
-            crop = self.conformance_window()
-        elif crop is None:
-            crop = (0, 0, 0, 0)
-        col = self.colour()
-        matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
-        dev = self.device
-        if dev < 0:
-            raise RuntimeError("Picture.export: the picture is not on a device (parse-only, or its sequence has ended)")
-        return export.export_tensors(lambda desc, scale, ptrs, pitches, st: self.export_into(desc, ptrs, pitches, 1, st, scale),
-                                     seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out)
+        instead of new ones; dtype: torch.float16 / bfloat16 / float32 gives normalised float elements (export_batch with one
+        picture, without the batch dimension; mean / std / scale / bias as there).  Valid until the next push into the decoder."""
+        return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias)
+
+
+def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
+            scale=None, bias=None, enqueue=True):
+    """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
+    the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated"""
+    from . import HmgpuError, export, export_tensor_plan
+    first = pictures[0]
+    if first.ctx is None:
+        raise RuntimeError("export: the picture does not know its decoder")
+    g = first.geometry()
+    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
+    seq.chroma_format = g["chroma_format"]
+    if crop == "conformance":
+        crop = first.conformance_window()
+    elif crop is None:
+        crop = (0, 0, 0, 0)
+    col = first.colour()
+    matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
+    dev = first.device
+    if dev < 0:
+        raise RuntimeError("export: the picture is not on a device (parse-only, or its sequence has ended)")
+
+    def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
+        if not enqueue:
+            return None
+        if tensor is None and bstrides is None:
+            return first.export_into(desc, ptrs, pitches, 1, st, sc)
+        if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
+            plan = export_tensor_plan(seq, desc, sc, tensor)
+            bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        r = lib().hmdec_pictures_export(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
+                                        C.byref(tensor) if tensor is not None else None, p, q, b, 1, C.c_void_p(st or None))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export")
+    return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,
+                                 dtype, mean, std, scale, bias)
+
+
+def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
+                 filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+    """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
+    GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
+    torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
+    of Picture.export (crop and colour are taken from the first picture) and of libhm_amd.Context.export_batch (dtype, mean, std)."""
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("export_batch: no pictures")
+    return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
+                   scale, bias)
 
 
 class Decoder:
@@ -346,9 +388,15 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def frames(self, stream, **export_kw):
+    def frames(self, stream, batch=None, **export_kw):
         """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
-        of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's."""
+        of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
+        batch=N: (pocs, tensors) with up to N (<= 16) pictures per item instead, the tensors those of export_batch: slots are filled
+        in output order, the pictures fetched after one push in one batched call each; an item is yielded when it is full, the
+        remainder at the end of the stream as a view of the first n slots."""
+        if batch is not None:
+            yield from self._frames_batched(stream, int(batch), export_kw)
+            return
         nals = split_nal_units(stream)
         for i, nal in enumerate(nals):
             eof = i == len(nals) - 1
@@ -362,3 +410,43 @@ class Decoder:
                         yield p.poc, p.export(**export_kw)
                 if not new_pic:
                     break
+
+    def _frames_batched(self, stream, batch, export_kw):
+        if not 1 <= batch <= abi.EXPORT_MAX_BATCH:
+            raise ValueError("batch: 1 .. %d" % abi.EXPORT_MAX_BATCH)
+        if "out" in export_kw:
+            raise ValueError("frames(batch=): the items are allocated here")
+        kw = dict(layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
+                  filter="bilinear", out=None)
+        kw.update(export_kw)
+        nals = split_nal_units(stream)
+        item, pocs = None, []
+        for i, nal in enumerate(nals):
+            eof = i == len(nals) - 1
+            while True:
+                new_pic, check = self.push(nal, eof)
+                if check:
+                    got = []
+                    while True:
+                        p = self.get_picture()
+                        if p is None:
+                            break
+                        got.append(p)
+                    while got:                       # into the free slots of the item being filled, one call per item touched
+                        take, got = got[:batch - len(pocs)], got[batch - len(pocs):]
+                        if item is None:             # the first picture of an item allocates all N slots
+                            item = _export(take[:1], batch, enqueue=False, **kw)
+                        export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **export_kw)
+                        pocs += [p.poc for p in take]
+                        if len(pocs) == batch:
+                            yield pocs, _slots(item, 0, batch)
+                            item, pocs = None, []
+                if not new_pic:
+                    break
+        if pocs:
+            yield pocs, _slots(item, 0, len(pocs))
+
+
+def _slots(item, a, b):
+    """slots a .. b - 1 of an item: a tensor (RGB) or a tuple of planes"""
+    return tuple(t[a:b] for t in item) if isinstance(item, tuple) else item[a:b]
