@@ -89,6 +89,7 @@ void hmdec_set_packed_input(libHMDec_context* ctx, int on);
 typedef struct hmgpu_export_desc hmgpu_export_desc;
 typedef struct hmgpu_export_scale hmgpu_export_scale;
 typedef struct hmgpu_export_tensor hmgpu_export_tensor;
+typedef struct hmgpu_export_window hmgpu_export_window;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -104,6 +105,13 @@ int hmdec_picture_export_scaled(libHMDec_context* ctx, libHMDec_picture* pic, co
 int hmdec_pictures_export(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                           const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, void* const dst[3],
                           const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+/* hmdec_pictures_export with a source window and a mirror flag per picture (hmgpu_pictures_export_windows: desc->crop 0, windows[i] for
+ * pics[i]), under the same rules.  Where the pictures sit in several device contexts of the GPU the destination and every window are
+ * validated once for the whole batch (hmgpu_export_windows_destination_check), then each run of slots carries its own windows. */
+int hmdec_pictures_export_windows(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                  void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
+                                  void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

@@ -385,6 +385,41 @@ hmgpu_status hmgpu_pictures_export(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pi
 hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                             const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                             const int64_t batch_stride_bytes[3]);
+/* Batched export with a source window and a horizontal mirror per picture: random-resized-crop and random flip per
+ * sample, still one launch per call.  Slot i of the batch is, bit for bit,
+ *   hmgpu_pictures_export of pics[i] alone with desc->crop replaced by windows[i].crop, the same `scale` and the same `tensor`,
+ *   then, when windows[i].flip & 1, every output row of every plane reversed: the mirror acts on the output, after resampling and
+ *   after the float map; a semi-planar CbCr plane is reversed pair by pair (Cb stays first).
+ * desc->crop must be 0, 0, 0, 0: the window is the crop (else HMGPU_EINVAL).  Each window obeys the rules of hmgpu_export_plan_for
+ * (non-negative, non-empty, whole chroma samples) and, with `scale`, on its own the limits of the scaled export (32x reduction, 8x
+ * enlargement per axis and plane class, no 32-bit sum of its own tables overflows); one failing window refuses the whole call with
+ * the status the single call would give (the first failing window's), nothing is enqueued and the destination stays untouched.
+ * Without `scale` all windows must have one size (else HMGPU_EINVAL), which is the output's; their origins may differ, left edges
+ * that are no multiple of 4 included.  A flip with a bit other than bit 0, a non-zero reserved word, windows NULL and n outside
+ * 1 .. HMGPU_EXPORT_MAX_BATCH give HMGPU_EINVAL.  The plan is that of the single calls -- one output size for every slot -- with
+ * coef[12] / coef[13] the widest tables over all windows.  Destination validation, stream ordering (one event pair in, one out, when
+ * on_stream is 1) and the one launch per call are those of hmgpu_pictures_export.  A call whose windows are all equal uses the
+ * table slot of that shape (a repeated shape enqueues no copy), and unflipped it writes what hmgpu_pictures_export with that crop
+ * writes; a scaled call whose windows differ derives its tables per call (windows that share source size and output size on an axis
+ * share a table) and sends them, with the per-picture descriptors, in one copy into one of a small ring of per-call buffers, each
+ * rewritten only after the export that read it has finished. */
+typedef struct hmgpu_export_window {
+  int32_t crop[4];             /* left, right, top, bottom: luma samples removed from the coded picture, as hmgpu_export_desc::crop */
+  int32_t flip;                /* bit 0: mirror each output row; every other bit 0 */
+  int32_t reserved[3];         /* 0 */
+} hmgpu_export_window;
+/* validates and reports what hmgpu_pictures_export_windows writes per slot; host code, no device needed */
+hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                           const hmgpu_export_tensor* tensor, int32_t n, const hmgpu_export_window windows[],
+                                           hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                           const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                           const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
+                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_windows */
+hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                                    const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                                    void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
 
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->

@@ -96,6 +96,15 @@ def lib():
         L.hmgpu_export_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                      C.POINTER(abi.ExportTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                      C.POINTER(C.c_int64)]
+        L.hmgpu_export_windows_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                    C.POINTER(abi.ExportTensor), C.c_int32, C.POINTER(abi.ExportWindow),
+                                                    C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_windows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_windows_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
+                                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -176,6 +185,19 @@ def export_tensor_plan(seq, desc, scale=None, tensor=None):
                                             C.byref(tensor) if tensor is not None else None, C.byref(plan))
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_tensor_plan_for")
+    return plan
+
+
+def export_windows_plan(seq, desc, scale, tensor, windows):
+    """what an export with a window per picture writes per slot (hmgpu_export_windows_plan_for: host code, no GPU); windows: a
+    sequence of abi.ExportWindow (desc.crop 0)"""
+    plan = abi.ExportPlan()
+    windows = list(windows)
+    w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+    st = lib().hmgpu_export_windows_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
+                                             C.byref(tensor) if tensor is not None else None, len(windows), w, C.byref(plan))
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_windows_plan_for")
     return plan
 
 
@@ -340,13 +362,21 @@ class Context:
             self._chk(lib().hmgpu_picture_export_scaled(self._h, pic, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None)),
                       "hmgpu_picture_export_scaled")
 
-    def export_batch_into(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None):
-        """hmgpu_pictures_export into device memory the caller owns: plane k of picture i at ptrs[k] + i * bstrides[k] (bytes)"""
+    def export_batch_into(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
+        """hmgpu_pictures_export into device memory the caller owns: plane k of picture i at ptrs[k] + i * bstrides[k] (bytes);
+        windows: one abi.ExportWindow per picture (hmgpu_pictures_export_windows, desc.crop 0)"""
         pics = list(pics)
         h = (C.c_int32 * max(len(pics), 1))(*pics)
         p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
         q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
         b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+            self._chk(lib().hmgpu_pictures_export_windows(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
+                                                          C.byref(tensor) if tensor is not None else None, w, p, q, b, on_stream,
+                                                          C.c_void_p(stream or None)), "hmgpu_pictures_export_windows")
+            return
         self._chk(lib().hmgpu_pictures_export(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
                                               C.byref(tensor) if tensor is not None else None, p, q, b, on_stream, C.c_void_p(stream or None)),
                   "hmgpu_pictures_export")
@@ -358,6 +388,18 @@ class Context:
         b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
         return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None,
                                                     C.byref(tensor) if tensor is not None else None, p, q, b)
+
+    def export_windows_destination_status(self, desc, ptrs, pitches, bstrides, windows, scale=None, tensor=None, n=None):
+        """hmgpu_export_windows_destination_check: the status hmgpu_pictures_export_windows would give these windows (abi.ExportWindow,
+        one per picture; n: another count than len(windows)) and this destination; enqueues nothing"""
+        windows = list(windows)
+        w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
+        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        return lib().hmgpu_export_windows_destination_check(self._h, len(windows) if n is None else n, C.byref(desc),
+                                                            C.byref(scale) if scale is not None else None,
+                                                            C.byref(tensor) if tensor is not None else None, w, p, q, b)
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
@@ -376,18 +418,23 @@ class Context:
                                      filter, out, None, dtype, mean, std, scale, bias)
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
-                     size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+                     size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
         (scale, bias) = export.affine(output depth, mean, std) -- (v / (2^D - 1) - mean_k) / std_k -- or explicit scale= / bias=
-        triples.  out: a tensor (or tuple of planes) of that shape; rows, planes and batch entries may be any stride apart."""
+        triples.  out: a tensor (or tuple of planes) of that shape; rows, planes and batch entries may be any stride apart.
+        windows: one (x, y, w, h) per picture, luma samples relative to `crop`: the part of the picture slot i shows, resized to
+        `size` (size None: all of one (w, h), the output's); flip: one boolean per picture (None: none), the slot mirrored left to
+        right.  Still one launch (hmgpu_pictures_export_windows): random-resized-crop and random flip per sample
+        (export.random_resized_crop)."""
         from . import export
         pics = list(pics)
+        win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
-                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor),
+                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
-                                     out, len(pics), dtype, mean, std, scale, bias)
+                                     out, len(pics), dtype, mean, std, scale, bias, win)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

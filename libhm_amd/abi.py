@@ -127,6 +127,19 @@ def make_export_tensor(sample_type, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0))
     return t
 
 
+class ExportWindow(C.Structure):
+    _fields_ = [("crop", C.c_int32 * 4), ("flip", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def make_export_window(crop, flip=False):
+    """crop: (left, right, top, bottom) luma samples removed from the coded picture; flip: mirror each output row"""
+    w = ExportWindow()
+    for i in range(4):
+        w.crop[i] = int(crop[i])
+    w.flip = 1 if flip else 0
+    return w
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

@@ -140,6 +140,18 @@ struct hmgpu_ctx {
   static constexpr int kScaleSlots = 8;
   ScaleSlot scale_slot[kScaleSlots];
   uint64_t scale_tick = 0;
+  // hmgpu_pictures_export_windows, windows that differ: the tables, spans and per-picture classes of one call (no key ever repeats, so
+  // nothing is cached): a ring of per-call buffers, the next one rewritten only after the export that read it has finished
+  struct WindowBuf {
+    char* dev = nullptr;
+    char* host = nullptr;                // page-locked
+    size_t cap = 0;
+    bool pending = false;
+    hipEvent_t done = nullptr;           // recorded behind the export that read the buffer
+  };
+  static constexpr int kWindowBufs = 4;
+  WindowBuf window_buf[kWindowBufs];
+  int window_next = 0;
   uint64_t xfer_bytes = 0;
   uint32_t* dl_fault = nullptr;        // [32] page-locked: the picture's fault word (k_intra's bounded spin) as it stood behind the copies of ticket t
   std::vector<int> touched;            // pictures the entry point under way has enqueued work on, in any role (commit_use)
@@ -763,6 +775,11 @@ void hmgpu_destroy(hmgpu_ctx* c) {
     if (sl.dev) (void)hipFree(sl.dev);
     if (sl.host) (void)hipHostFree(sl.host);
   }
+  for (auto& wb : c->window_buf) {
+    if (wb.done) hipEventDestroy(wb.done);
+    if (wb.dev) (void)hipFree(wb.dev);
+    if (wb.host) (void)hipHostFree(wb.host);
+  }
   if (c->hash_host) (void)hipHostFree(c->hash_host);
   for (int k = 0; k < 2; k++) if (c->lane_ev[k]) hipEventDestroy(c->lane_ev[k]);
   delete c;
@@ -1346,6 +1363,35 @@ std::shared_ptr<const ScaleTab> build_scale_tab(int in, int out, int filter) {
   return t;
 }
 
+// the tables of one call whose windows differ (hmgpu_pictures_export_windows), keyed by (in, out, filter): windows that share them on
+// an axis share a table.  Random windows never repeat, so these stay out of the process-wide map below, which would only be emptied by
+// them.  The tables of the most recent such call are kept (call_tabs_recent), because one export validates the same windows more than
+// once -- the plan for the caller's allocation, the destination check of libhmdec, then the export itself, per run of slots -- and
+// each of these would derive every table again.
+typedef std::map<std::tuple<int, int, int>, std::shared_ptr<const ScaleTab>> CallTabs;
+std::mutex call_tabs_mu;
+CallTabs call_tabs_recent;
+
+std::shared_ptr<const ScaleTab> call_tab(CallTabs& tabs, int in, int out, int filter) {
+  const auto key = std::make_tuple(in, out, filter);
+  auto& t = tabs[key];
+  if (t) return t;
+  {
+    std::lock_guard<std::mutex> g(call_tabs_mu);
+    auto it = call_tabs_recent.find(key);
+    if (it != call_tabs_recent.end()) t = it->second;
+  }
+  if (!t) t = build_scale_tab(in, out, filter);
+  return t;
+}
+
+// after a windows call has been validated: its tables replace the kept ones
+void call_tabs_keep(const CallTabs& tabs) {
+  if (tabs.empty()) return;
+  std::lock_guard<std::mutex> g(call_tabs_mu);
+  call_tabs_recent = tabs;
+}
+
 // process-wide: the tables of recent shapes (a plan or an export of a repeated shape derives nothing)
 std::shared_ptr<const ScaleTab> scale_tab(int in, int out, int filter) {
   static std::mutex mu;
@@ -1383,7 +1429,7 @@ bool scale_sums_fit(const ScaleTab& x, const ScaleTab& y, int D, int E) {
 }
 
 hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, hmgpu_export_plan* out,
-                         ScaleShape* shape) {
+                         ScaleShape* shape, CallTabs* call_tabs = nullptr) {
   if (!seq || !d || !sc || !out) return HMGPU_EINVAL;
   memset(out, 0, sizeof(*out));
   for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
@@ -1413,7 +1459,11 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
   int taps[2] = {0, 0};
   for (int k = 0; k < s.classes; k++) {
     for (int ax = 0; ax < 2; ax++) {
-      s.tab[k][ax] = scale_tab(s.in[k][ax], s.out[k][ax], sc->filter);
+      if (call_tabs) {
+        s.tab[k][ax] = call_tab(*call_tabs, s.in[k][ax], s.out[k][ax], sc->filter);
+      } else {
+        s.tab[k][ax] = scale_tab(s.in[k][ax], s.out[k][ax], sc->filter);
+      }
       taps[ax] = std::max(taps[ax], s.tab[k][ax]->taps);
     }
     if (!scale_sums_fit(*s.tab[k][0], *s.tab[k][1], rgb ? s.depth[0] : s.depth[k], E)) return HMGPU_EUNSUPPORTED;
@@ -1575,6 +1625,110 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
   return HMGPU_OK;
 }
 
+// hmgpu_pictures_export_windows, windows that differ: the blob of one call -- the per-picture classes ([n][2] ScaleClass), then every
+// distinct table (first, count, weights tap-major) and every distinct span list, each 256-byte aligned -- built in the next buffer of
+// the ring and sent in one copy on hs.  tile: where the classes' tiles start (scale_tile_start); tw shrinks until the LDS of a pass
+// fits the most demanding window.  cls: tw, th, tiles_x and blocks of the call; *pic_cls: the classes in device memory.
+hmgpu_status window_tables(hmgpu_ctx* c, int n, const std::vector<ScaleShape>& shapes, const hmgpu_export_window* win, bool rgb,
+                           const int tile[2][2], hipStream_t hs, ScaleClass cls[2], const ScaleClass** pic_cls, hmgpu_ctx::WindowBuf** out) {
+  const int classes = shapes[0].classes;
+  std::vector<ScaleTiles> z((size_t)n * 2);
+  for (int k = 0; k < classes; k++) {
+    const int C = rgb ? 3 : k ? 2 : 1;
+    for (int tw = tile[k][0];;) {
+      int least = tw;
+      for (int i = 0; i < n; i++) {
+        const ScaleShape& s = shapes[(size_t)i];
+        z[(size_t)i * 2 + k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], k ? win[i].crop[0] >> c->csx : win[i].crop[0], C, tw, tile[k][1]);
+        least = std::min(least, z[(size_t)i * 2 + k].tw);
+      }
+      if (least == tw) break;
+      tw = least;
+    }
+  }
+  std::vector<char> blob(align_up((size_t)n * 2 * sizeof(ScaleClass), 256), 0);
+  auto place = [&](const void* src, size_t bytes) {
+    const size_t off = blob.size();
+    blob.resize(off + align_up(bytes, 256), 0);
+    memcpy(blob.data() + off, src, bytes);
+    return off;
+  };
+  std::map<const ScaleTab*, size_t> tab_at;                                // first; count and the weights follow
+  std::map<std::pair<const ScaleTab*, int>, size_t> span_at;               // (table, tile size)
+  struct TabOff { size_t first, count, w, span; };
+  std::vector<TabOff> offs((size_t)n * 4);
+  std::vector<int16_t> w;
+  for (int i = 0; i < n; i++) {
+    for (int k = 0; k < classes; k++) {
+      const ScaleTiles& zt = z[(size_t)i * 2 + k];
+      for (int ax = 0; ax < 2; ax++) {
+        const ScaleTab* t = shapes[(size_t)i].tab[k][ax].get();
+        const int no = shapes[(size_t)i].out[k][ax];
+        TabOff& o = offs[(size_t)i * 4 + k * 2 + ax];
+        auto it = tab_at.find(t);
+        if (it == tab_at.end()) {
+          const size_t at = place(t->first.data(), 4 * (size_t)no);
+          place(t->count.data(), 4 * (size_t)no);
+          w.assign((size_t)no * t->taps, 0);
+          for (int j = 0; j < t->taps; j++)
+            for (int q = 0; q < no; q++) w[(size_t)j * no + q] = t->w[(size_t)q * t->taps + j];
+          place(w.data(), 2 * w.size());
+          it = tab_at.emplace(t, at).first;
+        }
+        o.first = it->second;
+        o.count = o.first + align_up(4 * (size_t)no, 256);
+        o.w = o.count + align_up(4 * (size_t)no, 256);
+        const auto skey = std::make_pair(t, ax ? zt.th : zt.tw);
+        auto sp = span_at.find(skey);
+        if (sp == span_at.end()) sp = span_at.emplace(skey, place(zt.span[ax].data(), 4 * zt.span[ax].size())).first;
+        o.span = sp->second;
+      }
+    }
+  }
+  hmgpu_ctx::WindowBuf* wb = &c->window_buf[c->window_next];
+  c->window_next = (c->window_next + 1) % hmgpu_ctx::kWindowBufs;
+  if (wb->pending) HIP_TRY(c, hipEventSynchronize(wb->done));              // the export that read it last may still be in flight
+  wb->pending = false;
+  if (blob.size() > wb->cap) {
+    if (wb->dev) HIP_TRY(c, hipFree(wb->dev));
+    if (wb->host) HIP_TRY(c, hipHostFree(wb->host));
+    wb->dev = wb->host = nullptr;
+    wb->cap = 0;
+    const size_t cap = align_up(blob.size() + blob.size() / 2, 4096);      // (head room: the next call's windows differ)
+    HIP_TRY(c, hipMalloc(&wb->dev, cap));
+    HIP_TRY(c, hipHostMalloc(&wb->host, cap, hipHostMallocDefault));
+    wb->cap = cap;
+  }
+  if (!wb->done) HIP_TRY(c, hipEventCreateWithFlags(&wb->done, hipEventDisableTiming));
+  ScaleClass* pc = reinterpret_cast<ScaleClass*>(blob.data());
+  for (int i = 0; i < n; i++) {
+    for (int k = 0; k < classes; k++) {
+      const ScaleTiles& zt = z[(size_t)i * 2 + k];
+      ScaleClass& cl = pc[i * 2 + k];
+      for (int ax = 0; ax < 2; ax++) {
+        const TabOff& o = offs[(size_t)i * 4 + k * 2 + ax];
+        ScaleTable& d = ax ? cl.ty : cl.tx;
+        d.first = reinterpret_cast<const int32_t*>(wb->dev + o.first);
+        d.count = reinterpret_cast<const int32_t*>(wb->dev + o.count);
+        d.span = reinterpret_cast<const int32_t*>(wb->dev + o.span);
+        d.w = reinterpret_cast<const int16_t*>(wb->dev + o.w);
+        d.n = shapes[(size_t)i].out[k][ax];
+      }
+      cl.tw = zt.tw; cl.th = zt.th; cl.rows = zt.rows; cl.span_cap = zt.cap;
+      cl.tiles_x = zt.tiles_x; cl.blocks = zt.tiles_x * zt.tiles_y;
+      cl.x0 = k ? win[i].crop[0] >> c->csx : win[i].crop[0];
+      cl.y0 = k ? win[i].crop[2] >> c->csy : win[i].crop[2];
+      cl.pitch = c->pitch[k];
+      if (!i) cls[k] = cl;
+    }
+  }
+  memcpy(wb->host, blob.data(), blob.size());
+  HIP_TRY(c, hipMemcpyAsync(wb->dev, wb->host, blob.size(), hipMemcpyHostToDevice, hs));
+  *pic_cls = reinterpret_cast<const ScaleClass*>(wb->dev);
+  *out = wb;
+  return HMGPU_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the export entry points
@@ -1599,9 +1753,9 @@ static hmgpu_status export_elem(const hmgpu_seq_params* seq, const hmgpu_export_
 static int elem_size(int elem) { return elem == kElemU8 ? 1 : elem == kElemF32 ? 4 : 2; }
 
 static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem) {
+                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem, CallTabs* call_tabs = nullptr) {
   if (!seq || !d || !out) return HMGPU_EINVAL;
-  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape, call_tabs) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
   const hmgpu_status st = export_elem(seq, d, t, elem);
   if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
   if (*elem >= kElemF16)
@@ -1613,6 +1767,45 @@ hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmg
                                           const hmgpu_export_tensor* t, hmgpu_export_plan* out) {
   int elem = 0;
   return tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+}
+
+// hmgpu_pictures_export_windows: every window validated as the single call validates its crop, in order (the first failure is the
+// call's status).  differ: the windows are not all equal; shapes (scaled): one per window then, else one for all.
+static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
+                                 int n, const hmgpu_export_window* win, hmgpu_export_plan* out, std::vector<ScaleShape>* shapes, int* elem,
+                                 bool* differ) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  if (!win || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;          // the window is the crop
+  *differ = false;
+  for (int i = 1; i < n; i++) if (memcmp(win[i].crop, win[0].crop, sizeof(win[0].crop))) *differ = true;
+  CallTabs tabs;
+  hmgpu_export_plan plan;
+  if (shapes) shapes->clear();
+  for (int i = 0; i < n; i++) {
+    if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }
+    if (i && !*differ) continue;
+    hmgpu_export_desc dd = *d;
+    memcpy(dd.crop, win[i].crop, sizeof(dd.crop));
+    ScaleShape s;
+    const hmgpu_status st = tensor_plan(seq, &dd, sc, t, &plan, &s, elem, *differ && sc ? &tabs : nullptr);
+    if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
+    if (shapes && sc) shapes->push_back(s);
+    if (!i) { *out = plan; continue; }
+    if (plan.width[0] != out->width[0] || plan.height[0] != out->height[0]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }   // (unscaled)
+    out->coef[12] = std::max(out->coef[12], plan.coef[12]);
+    out->coef[13] = std::max(out->coef[13], plan.coef[13]);
+  }
+  call_tabs_keep(tabs);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[], hmgpu_export_plan* out) {
+  int elem = 0;
+  bool differ = false;
+  return windows_plan(seq, d, sc, t, n, windows, out, nullptr, &elem, &differ);
 }
 
 // every plane's destination, all n pictures of it, inside one allocation of the context's device (bstride null: one picture); vec is
@@ -1645,20 +1838,50 @@ hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu
   return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
 }
 
+hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  int elem = 0;
+  bool differ = false;
+  { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, windows, &plan, nullptr, &elem, &differ); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  bool vec = true;
+  int64_t bs[3];
+  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
+}
+
 // every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; bstride null: one picture, no batch
-// stride to check.  One launch, the stream ordering once.
+// stride to check; win null: desc->crop for every picture, no mirror.  One launch, the stream ordering once.
 static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
                                 const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
-                                int32_t on_stream, void* stream) {
+                                int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr) {
   if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   hmgpu_export_plan plan;
   ScaleShape s;
   int elem = 0;
-  { const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem); if (st != HMGPU_OK) return st; }
+  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
+  hmgpu_export_desc dd;
+  bool differ = false;
+  uint32_t flip = 0;
+  if (win) {
+    { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, win, &plan, &shapes, &elem, &differ); if (st != HMGPU_OK) return st; }
+    for (int i = 0; i < n; i++) flip |= (uint32_t)(win[i].flip & 1) << i;
+    if (!differ) {                                   // one window for all: the descriptor with that crop, its table slot
+      dd = *d;
+      memcpy(dd.crop, win[0].crop, sizeof(dd.crop));
+      d = &dd;
+      if (sc) s = shapes[0];
+    }
+  } else {
+    const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem);
+    if (st != HMGPU_OK) return st;
+  }
   hipSetDevice(c->device);
   const int ES = elem_size(elem);
-  bool vec = sc ? true : (d->crop[0] & 3) == 0;
+  bool vec = true;
   int64_t bs[3] = {0, 0, 0};
   { const hmgpu_status st = export_dst_ok(c, plan, ES, n, dst, pitch_bytes, bstride, &vec, bs); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
@@ -1667,7 +1890,6 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
   const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
   const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
-  const int x0 = d->crop[0], y0 = d->crop[2];
   { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
   if (!sc) {
     ExportArgs a;
@@ -1675,9 +1897,12 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     for (int i = 0; i < n; i++) {
       const Picture& p = c->pics[pics[i]];
       int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+      const int x0 = differ ? win[i].crop[0] : d->crop[0], y0 = differ ? win[i].crop[2] : d->crop[2];
       a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
       a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+      if (vec && (x0 & 3) == 0) a.vec |= 1u << i;                         // (a batch may mix aligned and unaligned left edges)
     }
+    a.flip = flip;
     a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
     a.n = n; a.layout = d->layout; a.elem = elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
     a.w = plan.width[0]; a.h = plan.height[0];
@@ -1685,7 +1910,6 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
     a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
     a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
-    a.vec = vec ? 1 : 0;
     for (int k = 0; k < 3; k++) {
       a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
       a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
@@ -1696,6 +1920,7 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     launch_export(a, hs);
     return export_end(c, n, pics, on_stream, hs);
   }
+  if (differ) s = shapes[0];                         // (the output size and the depths are those of every window)
   // the tables' slot is keyed by the tiles the batch size leads to, not by the batch size: calls of varying n share a slot
   int tile[2][2] = {{0, 0}, {0, 0}};
   int32_t tkey = rgb ? 1 : 0;
@@ -1703,18 +1928,25 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
     tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
   }
-  const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
-  int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
   hmgpu_ctx::ScaleSlot* slot = nullptr;
-  { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::WindowBuf* wbuf = nullptr;
   ScaleArgs a;
   memset(&a, 0, sizeof(a));
-  for (int k = 0; k < s.classes; k++) {
-    a.cls[k] = slot->cls[k];
-    a.cls[k].pitch = c->pitch[k];
-    a.cls[k].x0 = x0c[k];
-    a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
+  if (differ) {
+    const hmgpu_status st = window_tables(c, n, shapes, win, rgb, tile, hs, a.cls, &a.pic_cls, &wbuf);
+    if (st != HMGPU_OK) return st;
+  } else {
+    const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
+    int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
+    { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
+    for (int k = 0; k < s.classes; k++) {
+      a.cls[k] = slot->cls[k];
+      a.cls[k].pitch = c->pitch[k];
+      a.cls[k].x0 = x0c[k];
+      a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
+    }
   }
+  a.flip = flip;
   for (int i = 0; i < n; i++) {
     const Picture& p = c->pics[pics[i]];
     int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
@@ -1735,8 +1967,13 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   }
   memcpy(a.coef, plan.coef, sizeof(a.coef));
   launch_export_scaled(a, d->layout, elem, n, hs);
-  HIP_TRY(c, hipEventRecord(slot->done, hs));
-  slot->pending = true;
+  if (wbuf) {
+    HIP_TRY(c, hipEventRecord(wbuf->done, hs));
+    wbuf->pending = true;
+  } else {
+    HIP_TRY(c, hipEventRecord(slot->done, hs));
+    slot->pending = true;
+  }
   return export_end(c, n, pics, on_stream, hs);
 }
 
@@ -1756,6 +1993,13 @@ hmgpu_status hmgpu_pictures_export(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics
                                    const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
   if (!batch_stride_bytes) return HMGPU_EINVAL;
   return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                           const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes || !windows) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
 }
 
 // slice table entry of one slice (validation, SliceDev, scaling lists): the part of a slice call that does not depend on CTUs

@@ -335,6 +335,38 @@ __device__ inline void export_store4(uint8_t* d, const uint32_t v[4], int n, boo
     else stg(reinterpret_cast<uint32_t*>(d) + i, o[i]);
   }
 }
+// export_store4 of the group of n (<= 4) samples at column x of a row of w samples.  flip: the row is mirrored, so the group goes
+// out reversed at columns w - x - n .. (the last, partial group of a row lands at the row's start); either way one vector store
+// where the group's position is aligned, else sample by sample.
+template <int ELEM>
+__device__ inline void export_store_row(uint8_t* row, int x, int w, const uint32_t v[4], int n, bool vec, bool flip, int msb, float sc, float bi) {
+  uint32_t r[4];
+  for (int i = 0; i < 4; i++) r[i] = flip ? v[3 - i] : v[i];
+  if (flip && n < 4) {                                         // a partial group: its samples are the last n of r
+    if (n == 3) { r[0] = r[1]; r[1] = r[2]; r[2] = r[3]; }
+    else if (n == 2) { r[0] = r[2]; r[1] = r[3]; }
+    else r[0] = r[3];
+  }
+  const int xs = flip ? w - x - n : x;
+  export_store4<ELEM>(row + (ptrdiff_t)xs * elem_bytes<ELEM>(), r, n, vec && !(xs & 3), msb, sc, bi);
+}
+// the same for n (<= 4) CbCr pairs o[2j], o[2j + 1] at pair x of a semi-planar row of cw pairs (integer elements): mirrored pair
+// by pair, Cb stays first
+template <int ELEM>
+__device__ inline void export_store_pairs(uint8_t* row, int x, int cw, const uint32_t o[8], int n, bool vec, bool flip, int msb) {
+  uint32_t r[8];
+  for (int j = 0; j < 4; j++) { r[2 * j] = flip ? o[6 - 2 * j] : o[2 * j]; r[2 * j + 1] = flip ? o[7 - 2 * j] : o[2 * j + 1]; }
+  if (flip && n < 4) {
+    if (n == 3) { r[0] = r[2]; r[1] = r[3]; r[2] = r[4]; r[3] = r[5]; r[4] = r[6]; r[5] = r[7]; }
+    else if (n == 2) { r[0] = r[4]; r[1] = r[5]; r[2] = r[6]; r[3] = r[7]; }
+    else { r[0] = r[6]; r[1] = r[7]; }
+  }
+  const int xs = flip ? cw - x - n : x;
+  const bool vv = vec && !(xs & 1);
+  uint8_t* d = row + (ptrdiff_t)xs * 2 * elem_bytes<ELEM>();
+  export_store4<ELEM>(d, r, min(4, 2 * n), vv, msb, 0.f, 0.f);
+  if (n > 2) export_store4<ELEM>(d + 4 * elem_bytes<ELEM>(), r + 4, 2 * n - 4, vv, msb, 0.f, 0.f);
+}
 struct ExportArgs {
   const int16_t* y[kMaxExportBatch];   // per picture: luma sample (crop left, crop top)
   const int16_t* c[kMaxExportBatch];   // Cb of chroma sample (crop left >> csx, crop top >> csy) in the pair plane (Cr one element on)
@@ -344,7 +376,9 @@ struct ExportArgs {
   int32_t w, h, cw, ch;            // output luma / chroma size (chroma rows follow the luma rows in the grid, YUV layouts)
   int32_t sh[2], maxv[2];          // bit-depth rule per channel type: out - coding depth, 2^out - 1
   int32_t msb[2];                  // container shift per channel type (msb_aligned: 16 - out)
-  int32_t vec;                     // every group of 4 samples may use vector loads and stores (alignment of crop, dst and pitches)
+  uint32_t vec;                    // bit i: every group of 4 samples of picture i may use vector loads and stores (alignment of its
+                                   // crop, of dst and of the pitches)
+  uint32_t flip;                   // bit i: picture i is mirrored (every output row reversed)
   uint8_t* dst[3];
   int64_t pitch[3];                // bytes
   int64_t bstride[3];              // bytes between the planes of consecutive pictures
@@ -373,13 +407,15 @@ struct ScaleClass {                // one plane class: 0 = luma (YUV) or RGB, 1 
   int32_t pitch;                   // int16 elements
 };
 struct ScaleArgs {
-  ScaleClass cls[2];
+  ScaleClass cls[2];               // the classes of every picture; with pic_cls: tw, th, tiles_x and blocks, common to the call (one grid)
+  const ScaleClass* pic_cls;       // null, or per picture and class ([grid y][2], device memory beside the tables): windows that differ
   const int16_t* src[kMaxExportBatch][2];   // per picture (grid y): sample (0, 0) of the luma plane and of the pair plane (Cb)
   int32_t pitch_c;                 // RGB: rows of the pair plane
   int32_t mono, csx, csy;
   int32_t sh[2], maxv[2], msb[2];  // bit-depth rule per channel type (as ExportArgs); RGB: maxv[0] = coef[9]
   int32_t e;                       // fractional bits kept between the passes (hmgpu_export_plan.coef[11])
   int32_t vec;                     // every group of 4 output samples may be one 4- or 8-byte store (alignment of dst and pitches)
+  uint32_t flip;                   // bit i: picture i is mirrored (every output row reversed)
   uint8_t* dst[3];
   int64_t pitch[3];                // bytes
   int64_t bstride[3];              // bytes between the planes of consecutive pictures

@@ -4,7 +4,7 @@
 //   RGB: chroma replicated to the luma grid (writePlane's 4:2:2 -> 4:4:4, TVideoIOYuv.cpp:425-443), an integer Y'CbCr -> R'G'B' matrix
 //        whose coefficients the host derives (hmgpu_export_plan.coef), or the identity (RGBtoGBR, TVideoIOYuv.cpp:962-978)
 // Memory-bound, no reuse beyond chroma: one lane per 4 samples of a row (8-byte loads per plane, 4- or 8-byte stores), rows along
-// the grid's y, the pictures of a batch along z, no LDS.  One instance per layout and output element (1- or 2-byte unsigned, float16,
+// the grid's y, the pictures of a batch along z (each with its own origin, alignment and mirror flag: hmgpu_pictures_export_windows), no LDS.  One instance per layout and output element (1- or 2-byte unsigned, float16,
 // bfloat16, float32: hmgpu_dev.h export_store4), so nothing per sample branches on either.  The source planes
 // keep at least 128 samples of margin right of the picture, so the loads of the last group of a row never leave the allocation;
 // only its stores are cut to the row.
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
   constexpr int BYTES = elem_bytes<ELEM>();
   const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
   const int r = blockIdx.y, pic = blockIdx.z;
-  const bool vec = a.vec != 0;
+  const bool vec = (a.vec >> pic) & 1, flip = (a.flip >> pic) & 1;
   const int16_t* const ay = a.y[pic];
   const int16_t* const ac = a.c[pic];
   uint8_t* const d0 = a.dst[0] + pic * a.bstride[0];
@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
     if (LAYOUT != HMGPU_EXPORT_RGB) {
       uint32_t o[4];
       for (int i = 0; i < 4; i++) o[i] = (uint32_t)depth_conv(yv[i], a.sh[0], a.maxv[0]);
-      export_store4<ELEM>(d0 + r * a.pitch[0] + (ptrdiff_t)x * BYTES, o, n, vec, a.msb[0], a.scale[0], a.bias[0]);
+      export_store_row<ELEM>(d0 + r * a.pitch[0], x, a.w, o, n, vec, flip, a.msb[0], a.scale[0], a.bias[0]);
       return;
     }
     // RGB: the chroma of the group's four luma samples (one pair for two of them when csx = 1)
@@ -84,12 +84,11 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
         B[i] = (uint32_t)min(M, max(0, (t + a.coef[8] * cu) >> S));
       }
     }
-    const ptrdiff_t off = (ptrdiff_t)x * BYTES;
     // (identity: G carries the luma container shift, B and R the chroma one; the matrix: all three the luma one)
     const int mc = a.coef[10] ? a.msb[1] : a.msb[0];
-    export_store4<ELEM>(d0 + r * a.pitch[0] + off, R, n, vec, mc, a.scale[0], a.bias[0]);
-    export_store4<ELEM>(d1 + r * a.pitch[1] + off, G, n, vec, a.msb[0], a.scale[1], a.bias[1]);
-    export_store4<ELEM>(d2 + r * a.pitch[2] + off, B, n, vec, mc, a.scale[2], a.bias[2]);
+    export_store_row<ELEM>(d0 + r * a.pitch[0], x, a.w, R, n, vec, flip, mc, a.scale[0], a.bias[0]);
+    export_store_row<ELEM>(d1 + r * a.pitch[1], x, a.w, G, n, vec, flip, a.msb[0], a.scale[1], a.bias[1]);
+    export_store_row<ELEM>(d2 + r * a.pitch[2], x, a.w, B, n, vec, flip, mc, a.scale[2], a.bias[2]);
     return;
   }
   // chroma rows of the YUV layouts: four CbCr pairs per lane
@@ -104,13 +103,10 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
   for (int i = 0; i < 8; i++) o[i] = (uint32_t)depth_conv(p[i], a.sh[1], a.maxv[1]);
   if (LAYOUT == HMGPU_EXPORT_PLANAR) {
     const uint32_t cb[4] = {o[0], o[2], o[4], o[6]}, cr[4] = {o[1], o[3], o[5], o[7]};
-    const ptrdiff_t off = (ptrdiff_t)x * BYTES;
-    export_store4<ELEM>(d1 + rc * a.pitch[1] + off, cb, n, vec, a.msb[1], a.scale[1], a.bias[1]);
-    export_store4<ELEM>(d2 + rc * a.pitch[2] + off, cr, n, vec, a.msb[1], a.scale[2], a.bias[2]);
+    export_store_row<ELEM>(d1 + rc * a.pitch[1], x, a.cw, cb, n, vec, flip, a.msb[1], a.scale[1], a.bias[1]);
+    export_store_row<ELEM>(d2 + rc * a.pitch[2], x, a.cw, cr, n, vec, flip, a.msb[1], a.scale[2], a.bias[2]);
   } else {                                // the pairs as they lie: two groups of four samples
-    uint8_t* d = d1 + rc * a.pitch[1] + (ptrdiff_t)x * 2 * BYTES;
-    export_store4<ELEM>(d, o, min(4, 2 * n), vec, a.msb[1], 0.f, 0.f);
-    if (n > 2) export_store4<ELEM>(d + 4 * BYTES, o + 4, 2 * n - 4, vec, a.msb[1], 0.f, 0.f);
+    export_store_pairs<ELEM>(d1 + rc * a.pitch[1], x, a.cw, o, n, vec, flip, a.msb[1]);
   }
 }
 

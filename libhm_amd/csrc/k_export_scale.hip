@@ -1,6 +1,7 @@
 // k_export_scale.hip -- scaled device export (hmgpu_picture_export_scaled / hmgpu_pictures_export, include/hmgpu.h "scaled export"):
 // finished pictures converted as k_export.hip converts them and resized in the same pass, horizontally then vertically, with the
-// host's Q14 tables.  The pictures of a batch lie along the grid's y and share the tables and the tiling.
+// host's Q14 tables.  The pictures of a batch lie along the grid's y and share the tiling; they share the tables too, unless the call
+// gives each picture a source window of its own (hmgpu_pictures_export_windows: ScaleArgs::pic_cls), and each may be mirrored.
 //
 // One workgroup of 256 lanes owns a tile of tw x th outputs of one plane class (RGB: R, G and B together; YUV: Y, or Cb and Cr
 // together).  It walks the tile's source rows in passes of `rows` rows through LDS:
@@ -170,18 +171,17 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
   for (int c = 0; c < C; c++)
     for (int q = 0; q < 4; q++) o[c][q] = (uint32_t)min(M, max(0, (acc[c][q] + vrnd) >> vsh));
   const int x = ox0 + vx, y = oy0 + vy, n = min(4, k.tx.n - x);
-  const bool vec = a.vec != 0;
+  const bool vec = a.vec != 0, flip = (a.flip >> pic) & 1;    // the mirror: columns x .. x + 3 reversed to W - 1 - x ..
+  const int W = k.tx.n;
   if constexpr (C != 2) {
     for (int c = 0; c < C; c++)
-      export_store4<ELEM>(a.dst[c] + pic * a.bstride[c] + y * a.pitch[c] + (ptrdiff_t)x * BYTES, o[c], n, vec, msb, a.scale[c], a.bias[c]);
+      export_store_row<ELEM>(a.dst[c] + pic * a.bstride[c] + y * a.pitch[c], x, W, o[c], n, vec, flip, msb, a.scale[c], a.bias[c]);
   } else if (LAYOUT == HMGPU_EXPORT_PLANAR) {
-    export_store4<ELEM>(a.dst[1] + pic * a.bstride[1] + y * a.pitch[1] + (ptrdiff_t)x * BYTES, o[0], n, vec, msb, a.scale[1], a.bias[1]);
-    export_store4<ELEM>(a.dst[2] + pic * a.bstride[2] + y * a.pitch[2] + (ptrdiff_t)x * BYTES, o[C - 1], n, vec, msb, a.scale[2], a.bias[2]);
+    export_store_row<ELEM>(a.dst[1] + pic * a.bstride[1] + y * a.pitch[1], x, W, o[0], n, vec, flip, msb, a.scale[1], a.bias[1]);
+    export_store_row<ELEM>(a.dst[2] + pic * a.bstride[2] + y * a.pitch[2], x, W, o[C - 1], n, vec, flip, msb, a.scale[2], a.bias[2]);
   } else if constexpr (ELEM <= kElemU16) {    // semi-planar (integer elements only): the pairs interleaved
-    const uint32_t p0[4] = {o[0][0], o[C - 1][0], o[0][1], o[C - 1][1]}, p1[4] = {o[0][2], o[C - 1][2], o[0][3], o[C - 1][3]};
-    uint8_t* d = a.dst[1] + pic * a.bstride[1] + y * a.pitch[1] + (ptrdiff_t)x * 2 * BYTES;
-    export_store4<ELEM>(d, p0, min(4, 2 * n), vec, msb, 0.f, 0.f);
-    if (n > 2) export_store4<ELEM>(d + 4 * BYTES, p1, 2 * n - 4, vec, msb, 0.f, 0.f);
+    const uint32_t p[8] = {o[0][0], o[C - 1][0], o[0][1], o[C - 1][1], o[0][2], o[C - 1][2], o[0][3], o[C - 1][3]};
+    export_store_pairs<ELEM>(a.dst[1] + pic * a.bstride[1] + y * a.pitch[1], x, W, p, n, vec, flip, msb);
   }
 }
 
@@ -191,9 +191,13 @@ template <int LAYOUT, int ELEM>
 __global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
   __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
   const int b = blockIdx.x;
-  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3>(a, a.cls[0], b, lds);
-  else if (b < a.cls[0].blocks) scale_tile<LAYOUT, ELEM, 1>(a, a.cls[0], b, lds);
-  else scale_tile<LAYOUT, ELEM, 2>(a, a.cls[1], b - a.cls[0].blocks, lds);
+  const int c = LAYOUT == HMGPU_EXPORT_RGB || b < a.cls[0].blocks ? 0 : 1;
+  // the class as this picture sees it: the call's own, or (windows that differ) the picture's from device memory, a wave-uniform load
+  ScaleClass k = a.cls[c];
+  if (a.pic_cls) k = a.pic_cls[2 * blockIdx.y + c];
+  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3>(a, k, b, lds);
+  else if (c == 0) scale_tile<LAYOUT, ELEM, 1>(a, k, b, lds);
+  else scale_tile<LAYOUT, ELEM, 2>(a, k, b - a.cls[0].blocks, lds);
 }
 
 void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s) {

@@ -998,7 +998,7 @@ hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc
 
 hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows) {
   if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
   flush_batch();
@@ -1010,9 +1010,10 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
   // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
   // the slots of one context as runs of equal distance (slot j of a run lies run-distance * batch stride after the one before), one
   // hmgpu_pictures_export each: a single call when one context holds every picture.
-  { const hmgpu_status st = hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
+  { const hmgpu_status st = windows ? hmgpu_export_windows_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, dst, pitch_bytes, batch_stride_bytes)
+                                    : hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
     if (st != HMGPU_OK) return st; }
-  struct Run { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; };
+  struct Run { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; hmgpu_export_window w[HMGPU_EXPORT_MAX_BATCH]; };
   std::vector<Run> runs;
   std::vector<bool> taken((size_t)n, false);
   for (int i = 0; i < n; i++) {
@@ -1024,7 +1025,11 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
     while (m < idx.size() && idx[m] - idx[m - 1] == step) m++;
     Run r;
     r.home = pics[i]->home; r.first = i; r.step = step; r.n = (int)m;
-    for (size_t q = 0; q < m; q++) { r.h[q] = pics[idx[q]]->handle; taken[(size_t)idx[q]] = true; }
+    for (size_t q = 0; q < m; q++) {
+      r.h[q] = pics[idx[q]]->handle;
+      if (windows) r.w[q] = windows[idx[q]];               // (the windows of a run's own slots)
+      taken[(size_t)idx[q]] = true;
+    }
     runs.push_back(r);
   }
   for (const Run& r : runs) {
@@ -1035,7 +1040,8 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
       bs[k] = batch_stride_bytes[k] * r.step;
     }
     hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
-    const hmgpu_status st = hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
+    const hmgpu_status st = windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
+                                    : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
     if (st != HMGPU_OK) return st;
   }
   return HMGPU_OK;

@@ -69,10 +69,11 @@ class Decoder {
   // scale: nullptr = hmgpu_picture_export, else hmgpu_picture_export_scaled
   hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, void* const dst[3], const int64_t pitch_bytes[3],
                               int on_stream, void* stream);
-  // hmgpu_pictures_export of pictures put out and still valid: one sequence, one GPU ordinal; one call per device context that holds some
+  // hmgpu_pictures_export of pictures put out and still valid: one sequence, one GPU ordinal; one call per device context that holds some.
+  // windows: nullptr, or one per picture (hmgpu_pictures_export_windows; each run of slots carries its own)
   hmgpu_status export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                               const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+                               const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr);
   int device_of(const PicData* pic) const { return pic && pic->on_device && pic->owner == this ? devices_[pic->home] : -1; }
   uint64_t download_bytes() const { return download_bytes_; }
   int last_display_poc = -(1 << 30);

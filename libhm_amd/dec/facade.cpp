@@ -320,6 +320,14 @@ int hmdec_pictures_export(libHMDec_context* ctx, int n, libHMDec_picture* const 
   for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
   return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
+int hmdec_pictures_export_windows(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                  void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!ctx || !pics || !windows || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
+}
 int hmdec_picture_device(libHMDec_picture* pic) {
   if (!pic || !as_pic(pic)->owner) return -1;
   return static_cast<const Decoder*>(as_pic(pic)->owner)->device_of(as_pic(pic));

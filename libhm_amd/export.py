@@ -115,6 +115,72 @@ def make_scale(size, filter="bilinear"):
     return abi.make_export_scale(w, h, filter)
 
 
+def make_windows(seq, crop, windows, flip, n):
+    """the abi.ExportWindow list of n pictures (None when neither windows nor flip is given).  windows: one (x, y, w, h) per picture
+    in luma samples relative to `crop` (left, right, top, bottom), inside it; None: all of `crop`.  flip: one boolean per picture, or
+    None.  The two are composed into absolute crops: the call then takes a descriptor whose own crop is 0."""
+    if windows is None and flip is None:
+        return None
+    l, r, t, b = (int(v) for v in crop)
+    cw, ch = seq.width - l - r, seq.height - t - b
+    windows = [(0, 0, cw, ch)] * n if windows is None else [tuple(int(v) for v in w) for w in windows]
+    flip = [False] * n if flip is None else [bool(f) for f in flip]
+    if len(windows) != n or len(flip) != n:
+        raise ValueError("windows / flip: one per picture (%d pictures, %d windows, %d flips)" % (n, len(windows), len(flip)))
+    out = []
+    for (x, y, w, h), f in zip(windows, flip):
+        if x < 0 or y < 0 or w <= 0 or h <= 0 or x + w > cw or y + h > ch:
+            raise ValueError("window %r leaves the %dx%d crop" % ((x, y, w, h), cw, ch))
+        out.append(abi.make_export_window((l + x, seq.width - (l + x) - w, t + y, seq.height - (t + y) - h), f))
+    return out
+
+
+def random_resized_crop(n, width, height, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip=0.5, generator=None, chroma_format=1):
+    """(windows, flips) for n pictures of width x height: torchvision's RandomResizedCrop sampling rule per picture -- up to ten
+    tries of an area fraction uniform in `scale` and an aspect ratio log-uniform in `ratio`, the first that fits placed uniformly,
+    else the central crop of the nearest allowed ratio -- and a flip with probability p_flip.  Each window (x, y, w, h) is then
+    snapped outwards to whole chroma samples of chroma_format (0 .. 3) and clamped to the picture.  Deterministic for a seeded
+    torch.Generator (CPU); feed the result to export_batch(windows=, flip=)."""
+    import math
+    import torch
+    mx = 0 if chroma_format in (0, 3) else 1
+    my = 1 if chroma_format == 1 else 0
+    area = float(width * height)
+    log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+
+    def uniform(a, b):
+        return float(torch.empty(1).uniform_(float(a), float(b), generator=generator).item())
+
+    def randint(hi):
+        return int(torch.randint(0, hi, (1,), generator=generator).item())
+
+    windows, flips = [], []
+    for _ in range(n):
+        for _try in range(10):
+            target = area * uniform(scale[0], scale[1])
+            aspect = math.exp(uniform(log_ratio[0], log_ratio[1]))
+            w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < w <= width and 0 < h <= height:
+                y, x = randint(height - h + 1), randint(width - w + 1)
+                break
+        else:
+            in_ratio = float(width) / float(height)
+            if in_ratio < min(ratio):
+                w = width
+                h = int(round(w / min(ratio)))
+            elif in_ratio > max(ratio):
+                h = height
+                w = int(round(h * max(ratio)))
+            else:
+                w, h = width, height
+            y, x = (height - h) // 2, (width - w) // 2
+        x0, y0 = x & ~mx, y & ~my
+        x1, y1 = min((x + w + mx) & ~mx, width), min((y + h + my) & ~my, height)
+        windows.append((x0, y0, x1 - x0, y1 - y0))
+        flips.append(bool(torch.rand(1, generator=generator).item() < p_flip))
+    return windows, flips
+
+
 def plane_shapes(plan, desc):
     """the shape of every plane tensor: [H, W], or [H, W, 2] for the CbCr plane of the semi-planar layout"""
     return [(plan.height[k], plan.width[k], 2) if desc.layout == abi.EXPORT_SEMIPLANAR and k == 1 else (plan.height[k], plan.width[k])
@@ -186,18 +252,20 @@ def alloc_outputs(plan, desc, device, n=None, dtype=None):
 
 
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
-                   filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+                   filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None):
     """allocate with torch on `device` (or take `out`) and run `call(desc, scale, tensor, ptrs, pitches, bstrides, stream)` on torch's
     current stream.  scale: None (size None), else the abi.ExportScale of size (height, width) and filter; tensor: None (dtype None),
     else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); bstrides: None for one picture
-    (n None), else the bytes between the batch entries of every plane of the n pictures."""
+    (n None), else the bytes between the batch entries of every plane of the n pictures.  windows: None, or the abi.ExportWindow of
+    every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0)."""
     import torch
-    from . import export_tensor_plan
+    from . import export_tensor_plan, export_windows_plan
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
-    desc = make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned, seq if dtype is not None else None)
+    desc = make_desc(layout, bit_depth, crop if windows is None else (0, 0, 0, 0), matrix, full_range, msb_aligned,
+                     seq if dtype is not None else None)
     sc = make_scale(size, filter)
     tensor = make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias)
-    plan = export_tensor_plan(seq, desc, sc, tensor)
+    plan = export_tensor_plan(seq, desc, sc, tensor) if windows is None else export_windows_plan(seq, desc, sc, tensor, windows)
     with torch.cuda.device(device):
         if out is None:
             out = alloc_outputs(plan, desc, device, n, dtype)

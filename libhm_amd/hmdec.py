@@ -75,6 +75,9 @@ def lib():
         L.hmdec_pictures_export.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                             C.POINTER(abi.ExportTensor), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_windows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -227,9 +230,10 @@ class Picture:
 
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
-            scale=None, bias=None, enqueue=True):
+            scale=None, bias=None, enqueue=True, windows=None, flip=None):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
-    the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated"""
+    the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
+    windows / flip: per picture, relative to crop (export.make_windows)"""
     from . import HmgpuError, export, export_tensor_plan
     first = pictures[0]
     if first.ctx is None:
@@ -246,6 +250,7 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     dev = first.device
     if dev < 0:
         raise RuntimeError("export: the picture is not on a device (parse-only, or its sequence has ended)")
+    win = export.make_windows(seq, crop, windows, flip, n if not enqueue else len(pictures))
 
     def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
         if not enqueue:
@@ -259,25 +264,33 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
         p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
         q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
         b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        if win is not None:
+            w = (abi.ExportWindow * len(win))(*win)
+            r = lib().hmdec_pictures_export_windows(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
+                                                    C.byref(tensor) if tensor is not None else None, w, p, q, b, 1, C.c_void_p(st or None))
+            if r != 0:
+                raise HmgpuError(r, "hmdec_pictures_export_windows")
+            return None
         r = lib().hmdec_pictures_export(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
                                         C.byref(tensor) if tensor is not None else None, p, q, b, 1, C.c_void_p(st or None))
         if r != 0:
             raise HmgpuError(r, "hmdec_pictures_export")
     return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,
-                                 dtype, mean, std, scale, bias)
+                                 dtype, mean, std, scale, bias, win)
 
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-                 filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+                 filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
-    of Picture.export (crop and colour are taken from the first picture) and of libhm_amd.Context.export_batch (dtype, mean, std)."""
+    of Picture.export (crop and colour are taken from the first picture) and of libhm_amd.Context.export_batch (dtype, mean, std;
+    windows: one (x, y, w, h) per picture relative to crop, flip: one boolean per picture -- hmdec_pictures_export_windows)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
-                   scale, bias)
+                   scale, bias, windows=windows, flip=flip)
 
 
 class Decoder:
@@ -388,14 +401,17 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def frames(self, stream, batch=None, **export_kw):
+    def frames(self, stream, batch=None, windows=None, **export_kw):
         """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
         of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
         batch=N: (pocs, tensors) with up to N (<= 16) pictures per item instead, the tensors those of export_batch: slots are filled
         in output order, the pictures fetched after one push in one batched call each; an item is yielded when it is full, the
-        remainder at the end of the stream as a view of the first n slots."""
+        remainder at the end of the stream as a view of the first n slots.  windows (batch=N only): a function; fn(n) returns
+        (windows, flips) for the n pictures of one batched call (export.random_resized_crop with the picture's size bound)."""
+        if windows is not None and batch is None:
+            raise ValueError("frames(windows=) needs batch=")
         if batch is not None:
-            yield from self._frames_batched(stream, int(batch), export_kw)
+            yield from self._frames_batched(stream, int(batch), export_kw, windows)
             return
         nals = split_nal_units(stream)
         for i, nal in enumerate(nals):
@@ -411,7 +427,7 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def _frames_batched(self, stream, batch, export_kw):
+    def _frames_batched(self, stream, batch, export_kw, windows=None):
         if not 1 <= batch <= abi.EXPORT_MAX_BATCH:
             raise ValueError("batch: 1 .. %d" % abi.EXPORT_MAX_BATCH)
         if "out" in export_kw:
@@ -434,9 +450,13 @@ class Decoder:
                         got.append(p)
                     while got:                       # into the free slots of the item being filled, one call per item touched
                         take, got = got[:batch - len(pocs)], got[batch - len(pocs):]
+                        wkw = {}
+                        if windows is not None:      # the windows and flips of this call's pictures
+                            w, f = windows(len(take))
+                            wkw = dict(windows=list(w), flip=None if f is None else list(f))
                         if item is None:             # the first picture of an item allocates all N slots
-                            item = _export(take[:1], batch, enqueue=False, **kw)
-                        export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **export_kw)
+                            item = _export(take[:1], batch, enqueue=False, windows=[wkw["windows"][0]] * batch if wkw else None, **kw)
+                        export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **wkw, **export_kw)
                         pocs += [p.poc for p in take]
                         if len(pocs) == batch:
                             yield pocs, _slots(item, 0, batch)
