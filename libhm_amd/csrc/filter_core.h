@@ -52,8 +52,11 @@ __device__ inline u16x2 usplat(int v) { return (u16x2){(unsigned short)v, (unsig
 __device__ inline s16x2 pk_clip(s16x2 lo, s16x2 hi, s16x2 v) { return __builtin_elementwise_min(__builtin_elementwise_max(v, lo), hi); }
 
 // Two lines across a luma edge at once (xPelFilterLuma, :800-859): s[k] holds sample k (p3 p2 p1 p0 q0 q1 q2 q3) of the two
-// lines in its 16-bit halves.  Samples are at most 10 bits wide (hmgpu_set_sequence refuses more), so every intermediate of
-// the HM formulas -- the largest is 9*(q0-p0) - 3*(q1-p1) + 8, |.| <= 12284 -- is exact in 16 bits.
+// lines in its 16-bit halves.  Samples are at most 12 bits wide (hmgpu_set_sequence refuses more).  Every intermediate of the HM
+// formulas is exact in 16 bits at that width -- the strong filter's sums are unsigned and at most 8 * 4095 + 4, d1 / d2 of the weak
+// filter stay within +-(4095 + 4095 + 3071) -- except one: 9*(q0-p0) - 3*(q1-p1) + 8 of the weak filter, |.| <= 12284 up to 10 bits
+// but up to 49148 at 12.  `wide` (bit depth above 10, uniform over the launch) computes that one per half in 32 bits; its shifted
+// value, at most 3071 in magnitude, is a 16-bit quantity again.  DESIGN.md, "Packed 16-bit arithmetic in the loop filters".
 __device__ inline void filter_luma_pair_strong(uint32_t (&s)[8], int tc) {
   const u16x2 m0 = as_u16x2(s[0]), m1 = as_u16x2(s[1]), m2 = as_u16x2(s[2]), m3 = as_u16x2(s[3]);
   const u16x2 m4 = as_u16x2(s[4]), m5 = as_u16x2(s[5]), m6 = as_u16x2(s[6]), m7 = as_u16x2(s[7]);
@@ -70,10 +73,17 @@ __device__ inline void filter_luma_pair_strong(uint32_t (&s)[8], int tc) {
   s[1] = lim(m1, n1); s[2] = lim(m2, n2); s[3] = lim(m3, n3);
   s[4] = lim(m4, n4); s[5] = lim(m5, n5); s[6] = lim(m6, n6);
 }
-__device__ inline void filter_luma_pair_weak(uint32_t (&s)[8], int tc, int thr_cut, bool filt_p, bool filt_q, int maxv) {
+__device__ inline void filter_luma_pair_weak(uint32_t (&s)[8], int tc, int thr_cut, bool filt_p, bool filt_q, int maxv, bool wide) {
   const s16x2 m1 = as_s16x2(s[1]), m2 = as_s16x2(s[2]), m3 = as_s16x2(s[3]), m4 = as_s16x2(s[4]), m5 = as_s16x2(s[5]), m6 = as_s16x2(s[6]);
   const s16x2 zero = splat(0), mx = splat(maxv), tcv = splat(tc), tc2 = splat(tc >> 1);
-  s16x2 delta = ((m4 - m3) * splat(9) - (m5 - m2) * splat(3) + splat(8)) >> 4;
+  s16x2 delta;
+  if (wide) {
+    const int lo = (9 * ((int)m4.x - (int)m3.x) - 3 * ((int)m5.x - (int)m2.x) + 8) >> 4;
+    const int hi = (9 * ((int)m4.y - (int)m3.y) - 3 * ((int)m5.y - (int)m2.y) + 8) >> 4;
+    delta = (s16x2){(short)lo, (short)hi};
+  } else {
+    delta = ((m4 - m3) * splat(9) - (m5 - m2) * splat(3) + splat(8)) >> 4;
+  }
   // 0xffff in the halves whose line is filtered (|delta| < thr_cut): the sign of |delta| - thr_cut
   const uint32_t on = as_u32((__builtin_elementwise_max(delta, -delta) - splat(thr_cut)) >> 15);
   delta = pk_clip(-tcv, tcv, delta);
@@ -119,8 +129,8 @@ __device__ inline void filter_luma_unit(uint32_t (&a)[8], uint32_t (&b)[8], int 
     filter_luma_pair_strong(a, tc);
     filter_luma_pair_strong(b, tc);
   } else {
-    filter_luma_pair_weak(a, tc, tc * 10, fp, fq, maxv);
-    filter_luma_pair_weak(b, tc, tc * 10, fp, fq, maxv);
+    filter_luma_pair_weak(a, tc, tc * 10, fp, fq, maxv, bd > 10);
+    filter_luma_pair_weak(b, tc, tc * 10, fp, fq, maxv, bd > 10);
   }
 #pragma unroll
   for (int k = 0; k < 4; k++) {

@@ -1201,8 +1201,8 @@ static void boundary_strength(lf_ctx* l, int ctu, int dir, int zq)
   l->bs[dir][zq] = (uint8_t)bs;
 }
 
-/* xPelFilterLuma: TComLoopFilter.cpp:800-859 (no PCM / lossless sides) */
-static void pel_filter_luma(int16_t* s, int off, int tc, int sw, int thr_cut, int filt_p, int filt_q, int maxv)
+/* xPelFilterLuma: TComLoopFilter.cpp:800-859 */
+static void pel_filter_luma(int16_t* s, int off, int tc, int sw, int p_nofilt, int q_nofilt, int thr_cut, int filt_p, int filt_q, int maxv)
 {
   const int m4 = s[0], m3 = s[-off], m5 = s[off], m2 = s[-off * 2], m6 = s[off * 2], m1 = s[-off * 3], m7 = s[off * 3], m0 = s[-off * 4];
   if (sw)
@@ -1235,6 +1235,30 @@ static void pel_filter_luma(int16_t* s, int off, int tc, int sw, int thr_cut, in
       }
     }
   }
+  /* bPartPNoFilter / bPartQNoFilter (:847-858): a lossless / PCM side gets its samples back */
+  if (p_nofilt) { s[-off] = (int16_t)m3; s[-off * 2] = (int16_t)m2; s[-off * 3] = (int16_t)m1; }
+  if (q_nofilt) { s[0] = (int16_t)m4; s[off] = (int16_t)m5; s[off * 2] = (int16_t)m6; }
+}
+/* xPelFilterChroma: TComLoopFilter.cpp:870-891 */
+static void pel_filter_chroma(int16_t* s, int off, int tc, int p_nofilt, int q_nofilt, int maxv)
+{
+  const int m4 = s[0], m3 = s[-off], m5 = s[off], m2 = s[-off * 2];
+  const int delta = CLIP3(-tc, tc, ((((m4 - m3) << 2) + m2 - m5 + 4) >> 3));
+  if (!p_nofilt) s[-off] = (int16_t)CLIP3(0, maxv, m3 + delta);
+  if (!q_nofilt) s[0] = (int16_t)CLIP3(0, maxv, m4 - delta);
+}
+/* the two pel filters on n lines (tests/test_oracle_kats.py: against HM's own): line i has q0 at s[first + i * line_step], sample k of a
+ * line at k * off from there */
+void hmo_pel_filter_luma(int bit_depth, int16_t* s, int first, int line_step, int n, int off, int tc, int sw, int p_nofilt, int q_nofilt,
+                         int thr_cut, int filt_p, int filt_q)
+{
+  int i;
+  for (i = 0; i < n; i++) pel_filter_luma(s + first + (ptrdiff_t)i * line_step, off, tc, sw, p_nofilt, q_nofilt, thr_cut, filt_p, filt_q, (1 << bit_depth) - 1);
+}
+void hmo_pel_filter_chroma(int bit_depth, int16_t* s, int first, int line_step, int n, int off, int tc, int p_nofilt, int q_nofilt)
+{
+  int i;
+  for (i = 0; i < n; i++) pel_filter_chroma(s + first + (ptrdiff_t)i * line_step, off, tc, p_nofilt, q_nofilt, (1 << bit_depth) - 1);
 }
 static int calc_dp(const int16_t* s, int off) { return iabs(s[-off * 3] - 2 * s[-off * 2] + s[-off]); }
 static int calc_dq(const int16_t* s, int off) { return iabs(s[0] - 2 * s[off] + s[off * 2]); }
@@ -1284,16 +1308,7 @@ static void edge_filter_luma(lf_ctx* l, int ctu, int z_cu, int depth, int dir, i
           const int fp = dp < side, fq = dq < side;
           const int sw = use_strong(off, 2 * d0, beta, tc, s) && use_strong(off, 2 * d3, beta, tc, s + step * 3);
           const int np = no_filter(g, pctu, zp), nq = no_filter(g, ctu, zq);             /* bPartPNoFilter / bPartQNoFilter: :629-634 */
-          for (i = 0; i < 4; i++)
-          {
-            int16_t* t = s + step * i;
-            int16_t keep[8];
-            int k;
-            for (k = 0; k < 8; k++) keep[k] = t[(k - 4) * off];
-            pel_filter_luma(t, off, tc, sw, thr_cut, fp, fq, maxv);
-            if (np) for (k = 0; k < 4; k++) t[(k - 4) * off] = keep[k];                   /* xPelFilterLuma :847-858 */
-            if (nq) for (k = 4; k < 8; k++) t[(k - 4) * off] = keep[k];
-          }
+          for (i = 0; i < 4; i++) pel_filter_luma(s + step * i, off, tc, sw, np, nq, thr_cut, fp, fq, maxv);
         }
       }
     }
@@ -1336,12 +1351,7 @@ static void edge_filter_chroma(lf_ctx* l, int ctu, int z_cu, int depth, int dir,
         base += dir == 0 ? edge * pels_h : edge * pels_v * stride;
         for (stp = 0; stp < loop; stp++)
         {
-          /* xPelFilterChroma: :870-891 */
-          int16_t* s = base + step * (stp + idx * loop);
-          const int m4 = s[0], m3 = s[-off], m5 = s[off], m2 = s[-off * 2];
-          const int delta = CLIP3(-tc, tc, ((((m4 - m3) << 2) + m2 - m5 + 4) >> 3));
-          if (!no_filter(g, pctu, zp)) s[-off] = (int16_t)CLIP3(0, maxv, m3 + delta);      /* xPelFilterChroma :883-890 */
-          if (!no_filter(g, ctu, zq)) s[0] = (int16_t)CLIP3(0, maxv, m4 - delta);
+          pel_filter_chroma(base + step * (stp + idx * loop), off, tc, no_filter(g, pctu, zp), no_filter(g, ctu, zq), maxv);
         }
       }
     }

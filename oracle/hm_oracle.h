@@ -47,6 +47,11 @@ void hmo_add_avg(const int16_t* s0, const int16_t* s1, int16_t* dst, int w, int 
 /* offsetBlock (TComSampleAdaptiveOffset.cpp:375-661); avail[8] = L,R,A,B,AL,AR,BL,BR */
 void hmo_sao_offset_block(int bit_depth, int type_idx, const int32_t* offset, const int16_t* src, int16_t* res,
                           int src_stride, int res_stride, int w, int h, const int32_t* avail);
+/* xPelFilterLuma / xPelFilterChroma (TComLoopFilter.cpp:800-891) on n lines across an edge, every argument HM takes: line i has its q0
+ * sample at s[first + i * line_step], sample k of a line (p3 = -4 .. q3 = 3) at k * off from there */
+void hmo_pel_filter_luma(int bit_depth, int16_t* s, int first, int line_step, int n, int off, int tc, int sw, int p_nofilt, int q_nofilt,
+                         int thr_cut, int filt_p, int filt_q);
+void hmo_pel_filter_chroma(int bit_depth, int16_t* s, int first, int line_step, int n, int off, int tc, int p_nofilt, int q_nofilt);
 
 /* ---- picture level ---- */
 /* TDecSlice/TDecCu::decompressCU over all CTUs [first_ctu, first_ctu+num_ctus).  refs[handle] are the reference

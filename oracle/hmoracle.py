@@ -102,6 +102,31 @@ def sao_offset_block(bit_depth, type_idx, offset32, plane, x0, y0, w, h, avail8)
     return res
 
 
+def _pel_lines(lines, transposed):
+    """lines int16 [n, 8] (p3 .. q3) -> (buffer, first, line_step, n, off, view of the buffer as [n, 8]): rows of the buffer, or, transposed, its
+    columns (the layout of a horizontal edge: sample k of a line lies a whole row from sample k - 1)"""
+    lines = np.asarray(lines, dtype=np.int16)
+    n = lines.shape[0]
+    if transposed:
+        buf = np.ascontiguousarray(lines.T)
+        return buf, 4 * n, 1, n, n, buf.T
+    buf = np.ascontiguousarray(lines).copy()
+    return buf, 4, 8, n, 1, buf
+
+
+def pel_filter_luma(bit_depth, lines, tc, sw, p_nofilt, q_nofilt, thr_cut, filt_p, filt_q, transposed=False):
+    """xPelFilterLuma on every line of int16 [n, 8] -> the filtered lines"""
+    buf, first, step, n, off, view = _pel_lines(lines, transposed)
+    lib().hmo_pel_filter_luma(bit_depth, _p(buf), first, step, n, off, int(tc), int(sw), int(p_nofilt), int(q_nofilt), int(thr_cut), int(filt_p), int(filt_q))
+    return np.array(view)
+
+
+def pel_filter_chroma(bit_depth, lines, tc, p_nofilt, q_nofilt, transposed=False):
+    buf, first, step, n, off, view = _pel_lines(lines, transposed)
+    lib().hmo_pel_filter_chroma(bit_depth, _p(buf), first, step, n, off, int(tc), int(p_nofilt), int(q_nofilt))
+    return np.array(view)
+
+
 # ------------------------------------------------------------------------------------------------ picture level
 def decompress_ctus(seq, slices, meta, coeffs, cur_planes, ref_planes_list, first_ctu=0, num_ctus=None):
     """cur_planes: list of 3 int16 arrays (modified in place).  ref_planes_list: list indexed by picture handle."""

@@ -86,6 +86,22 @@ def kat_addavg(s0, s1):
     return dst
 
 
+def kat_pel_filter_luma(bit_depth, lines, tc, sw, p_nofilt, q_nofilt, thr_cut, filt_p, filt_q, transposed=False):
+    """HM's xPelFilterLuma on every line of int16 [n, 8] (p3 .. q3) -> the filtered lines; transposed: the lines are the columns of the
+    buffer handed to HM (iOffset = n), as across a horizontal edge"""
+    from oracle.hmoracle import _pel_lines
+    buf, first, step, n, off, view = _pel_lines(lines, transposed)
+    lib().ref_kat_pel_filter_luma(bit_depth, _p(buf), first, step, n, off, int(tc), int(sw), int(p_nofilt), int(q_nofilt), int(thr_cut), int(filt_p), int(filt_q))
+    return np.array(view)
+
+
+def kat_pel_filter_chroma(bit_depth, lines, tc, p_nofilt, q_nofilt, transposed=False):
+    from oracle.hmoracle import _pel_lines
+    buf, first, step, n, off, view = _pel_lines(lines, transposed)
+    lib().ref_kat_pel_filter_chroma(bit_depth, _p(buf), first, step, n, off, int(tc), int(p_nofilt), int(q_nofilt))
+    return np.array(view)
+
+
 def kat_sao_block(comp, bdY, bdC, type_idx, offset32, plane, x0, y0, w, h, avail8):
     """plane int16 2-D with >= 1 sample margin around block; returns copy of plane with block filtered"""
     plane = np.ascontiguousarray(plane, dtype=np.int16)

@@ -9,6 +9,7 @@ Fixtures are DATA only (inputs + HM's outputs); no reference source text is stor
 
   python oracle/make_golden.py streams     # P1/P2: picture-level dumps of small real streams
   python oracle/make_golden.py kats        # K1/K3/K4: kernel-level known-answer tests
+  python oracle/make_golden.py dbk_kats    # the pel filters of the deblocking filter (a file of its own: dbk_kats.npz)
   python oracle/make_golden.py all
 """
 import os
@@ -520,10 +521,85 @@ def make_kats():
     print("wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024.0))
 
 
+def dbk_kat_lines(bd):
+    """the lines (int16 [n, 8]: p3 p2 p1 p0 q0 q1 q2 q3) of the deblocking known answers: constants, alternating extremes, ramps of both signs
+    with the step across the edge swept over the whole range, lines whose weak-filter delta 9(q0-p0) - 3(q1-p1) + 8 leaves 16 bits (12 bits
+    only: it cannot at less), noise"""
+    mx = (1 << bd) - 1
+    rng = xorshift_rng(0xDB4 + bd)
+    lines = [[0] * 8, [mx] * 8, [0, mx] * 4, [mx, 0] * 4]
+    k = np.arange(8)
+    for sign in (1, -1):
+        for i in range(48):
+            step = (mx * i) // 47                                     # 0 .. max across the edge
+            slope = (i % 5) * (1 << (bd - 8))                          # 0 .. 4 (scaled) per sample on both sides
+            base = (mx - step) // 2 if sign > 0 else (mx + step) // 2
+            ln = base + sign * (slope * (k - 3) + np.where(k >= 4, step - slope, 0))
+            lines.append(list(np.clip(ln, 0, mx)))
+    wide = []
+    while len(wide) < 72:                                              # big step, p1 / q1 far inside: the largest |delta| the depth allows
+        p0, q0 = int(rng.randint(0, mx // 16)), mx - int(rng.randint(0, mx // 16))
+        p1, q1 = p0 + int(rng.randint(mx // 4, mx // 2)), q0 - int(rng.randint(mx // 4, mx // 2))
+        ln = [int(rng.randint(0, mx + 1)), int(rng.randint(0, mx + 1)), p1, p0, q0, q1, int(rng.randint(0, mx + 1)), int(rng.randint(0, mx + 1))]
+        if bd < 12 or abs(9 * (q0 - p0) - 3 * (q1 - p1) + 8) > 32767:
+            wide.append(ln if len(wide) % 2 == 0 else ln[::-1])
+    lines += wide
+    lines += [list(r) for r in rng.randint(0, mx + 1, size=(20, 8))]
+    near = rng.randint(-3 << (bd - 8), (3 << (bd - 8)) + 1, size=(24, 8)) + rng.randint(0, mx + 1, size=(24, 1))   # flat + small noise: d1 / d2 unclipped
+    lines += [list(r) for r in np.clip(near, 0, mx)]
+    return np.array(lines, dtype=np.int16)
+
+
+def dbk_kat_cases(bd, n_lines):
+    """(luma cases [c, 10]: tc, sw, PartPNoFilter, PartQNoFilter, ThrCut, FilterSecondP, FilterSecondQ, first line, lines, transposed;
+    chroma cases [c, 7]: tc, PartPNoFilter, PartQNoFilter, first line, lines, transposed, 0).  Every tc from 0 to 24 << (bd - 8), each with
+    per_tc of the 32 combinations of the five booleans (all 32 at every tc at 8 bits; cycling, so that every combination meets small and
+    large tc, above); a case runs a window of lines that moves through the set; ThrCut is HM's 10 * tc, every seventh case 3 * tc"""
+    per_tc = {8: 32, 10: 8, 12: 4}[bd]
+    luma, chroma, c = [], [], 0
+    for tc in range(0, (24 << (bd - 8)) + 1):
+        for j in range(per_tc):
+            combo = (tc * per_tc + j) % 32 if per_tc < 32 else j
+            sw, pn, qn, fp, fq = [(combo >> b) & 1 for b in range(5)]
+            luma.append([tc, sw, pn, qn, (3 if c % 7 == 6 else 10) * tc, fp, fq, (c * 29) % n_lines, 40, c % 2])
+            c += 1
+        for j in range(4):
+            chroma.append([tc, j & 1, j >> 1, (c * 29 + j * 11) % n_lines, 24, (tc + j) % 2, 0])
+    return np.array(luma, dtype=np.int32), np.array(chroma, dtype=np.int32)
+
+
+def make_dbk_kats():
+    """tests/golden/dbk_kats.npz: HM's own xPelFilterLuma / xPelFilterChroma (TComLoopFilter.cpp:800-891).  The results are stored as the
+    change they make to the lines (most samples of most cases do not change: it is what keeps the file small)"""
+    out = {}
+    for bd in (8, 10, 12):
+        lines = dbk_kat_lines(bd)
+        luma, chroma = dbk_kat_cases(bd, len(lines))
+        if bd == 12:
+            wide = np.abs(9 * (lines[:, 4].astype(np.int64) - lines[:, 3]) - 3 * (lines[:, 5].astype(np.int64) - lines[:, 2]) + 8) > 32767
+            assert int(wide.sum()) >= 64
+        res_l, res_c = [], []
+        for tc, sw, pn, qn, thr, fp, fq, first, num, tr in luma:
+            sel = lines[(first + np.arange(num)) % len(lines)]
+            res_l.append((hmref.kat_pel_filter_luma(bd, sel, tc, sw, pn, qn, thr, fp, fq, bool(tr)).astype(np.int32) - sel).ravel())
+        for tc, pn, qn, first, num, tr, _ in chroma:
+            sel = lines[(first + np.arange(num)) % len(lines)]
+            res_c.append((hmref.kat_pel_filter_chroma(bd, sel, tc, pn, qn, bool(tr)).astype(np.int32) - sel).ravel())
+        out["lines_bd%d" % bd] = lines
+        out["luma_cases_bd%d" % bd], out["chroma_cases_bd%d" % bd] = luma, chroma
+        out["luma_change_bd%d" % bd] = np.concatenate(res_l).astype(np.int16)
+        out["chroma_change_bd%d" % bd] = np.concatenate(res_c).astype(np.int16)
+    path = os.path.join(GOLD, "dbk_kats.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024.0))
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what in ("kats", "all"):
         make_kats()
+    if what in ("dbk_kats", "all"):
+        make_dbk_kats()
     if what in ("streams", "all"):
         make_streams(sys.argv[2:] or None)
     if what in ("lite", "all"):

@@ -10,7 +10,7 @@
  * Two groups of entry points:
  *   ref_kat_*   direct calls of HM's own free/public functions on caller-supplied arrays
  *               (xITrMxN, TComInterpolationFilter::filterHor/Ver, TComYuv::addAvg,
- *                TComSampleAdaptiveOffset::offsetBlock)
+ *                TComSampleAdaptiveOffset::offsetBlock, TComLoopFilter::xPelFilterLuma / xPelFilterChroma)
  *   ref_dec_*   drive HM's TDecTop over an Annex-B stream exactly like TAppDecTop::decode
  *               (TAppDecTop.cpp:93-215), but stop between decompressSlice() and filterPicture()
  *               so that the per-CTU TComDataCU metadata, the coefficients and the planes
@@ -134,6 +134,28 @@ void ref_kat_sao_block(int comp, int bdY, int bdC, int typeIdx, const int32_t* o
   sao.offsetBlock(ComponentID(comp), typeIdx, off, const_cast<Pel*>(src), res, srcStride, resStride, w, h,
                   avail[0] != 0, avail[1] != 0, avail[2] != 0, avail[3] != 0, avail[4] != 0, avail[5] != 0, avail[6] != 0, avail[7] != 0);
   sao.destroy();
+}
+
+/* HM TComLoopFilter::xPelFilterLuma / xPelFilterChroma (TComLoopFilter.cpp:800-891) on n lines across an edge, with every argument
+ * HM takes.  Line i has its q0 sample at s[first + i * lineStep]; sample k of a line (p3 = -4 .. q3 = 3) lies at k * offset from there
+ * (offset 1: lines are rows, a vertical edge; offset = row length: lines are columns, a horizontal edge).  The two functions are
+ * __inline members defined in TComLoopFilter.cpp, so no object file carries them: the harness compiles that file as part of this
+ * translation unit (end of this file; oracle/Makefile leaves TComLoopFilter.o out of libhmref.so).                                */
+void ref_kat_pel_filter_luma(int bd, int16_t* s, int first, int lineStep, int n, int offset, int tc, int sw, int partPNoFilter,
+                             int partQNoFilter, int thrCut, int filterSecondP, int filterSecondQ)
+{
+  set_globals(bd, bd);
+  TComLoopFilter lf;
+  for (int i = 0; i < n; i++)
+    lf.xPelFilterLuma(s + first + (ptrdiff_t)i * lineStep, offset, tc, sw != 0, partPNoFilter != 0, partQNoFilter != 0, thrCut,
+                      filterSecondP != 0, filterSecondQ != 0);
+}
+void ref_kat_pel_filter_chroma(int bd, int16_t* s, int first, int lineStep, int n, int offset, int tc, int partPNoFilter, int partQNoFilter)
+{
+  set_globals(bd, bd);
+  TComLoopFilter lf;
+  for (int i = 0; i < n; i++)
+    lf.xPelFilterChroma(s + first + (ptrdiff_t)i * lineStep, offset, tc, partPNoFilter != 0, partQNoFilter != 0);
 }
 
 /* ------------------------------------------------------------------ stream decode ------------------ */
@@ -570,3 +592,6 @@ int ref_dec_finish(void* h, uint8_t* md5out)
  * the harness simply clocks ref_dec_next/ref_dec_finish from the caller side (see bench.py).            */
 
 } /* extern "C" */
+
+/* HM's loop filter itself, compiled here so that its __inline pel filters exist for ref_kat_pel_filter_* above */
+#include "TLibCommon/TComLoopFilter.cpp"

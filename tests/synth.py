@@ -32,7 +32,7 @@ class SynthPicture:
 def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, num_refs=1, slice_qp_range=(22, 37),
                  cbf_prob=0.5, sao=True, mode_probs=(0.1, 0.3, 0.3, 0.2, 0.1), ref_handles=None, mv_range=64,
                  coef_dist="typical", tr_split_prob=0.35, intra_modes=True, num_slices=1, lf_across_slices=1,
-                 chroma_format=1, log2_ctu=6, bit_depth_chroma=None, ccp_prob=0.0):
+                 chroma_format=1, log2_ctu=6, bit_depth_chroma=None, ccp_prob=0.0, mv_coherence=0.0, l1_refs=1):
     """Returns a SynthPicture with .seq, .slice (abi.SliceParams), .meta (MetaHolder), .coeffs (CoeffHolder),
     .sao_raw [num_ctus,3,35], .pp, .meta_np.  ref_handles: device picture handles of list-0 / list-1 references.
     coef_dist: "typical" (see above), "stress" (every level of a coded TU uniform over the full int16 range) or
@@ -48,8 +48,15 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
         first child; 4:0:0: no coded chroma block
       * ccp_prob (4:4:4 only): probability that a transform unit whose luma block is coded carries a cross-component prediction weight
         from {+-1, +-2, +-4, +-8} per chroma component (meta ccp_u / ccp_v, on all partitions of the unit; intra units only with the
-        chroma mode DM, as in HM); 0 = the arrays are absent"""
-    assert chroma_format in (0, 1, 2, 3) and log2_ctu in (4, 5, 6)
+        chroma mode DM, as in HM); 0 = the arrays are absent
+    Motion that lets the deblocking filter decide both ways (boundary strength 0 or 1 between inter PUs); both options draw from a second
+    generator, so the arrays of a picture made without them stay what they were:
+      * mv_coherence: probability that a PU, instead of its own draw, takes the vectors and reference indices of the PU left of it or above
+        it (as that PU ends up, so motion spreads over areas), each vector component moved by -5 .. 5 quarter samples: the |difference| >= 4
+        test of xGetBoundaryStrengthSingle then falls both ways
+      * l1_refs (with bi): number of list-1 references, 1 or 2.  ref_handles=([0, 1], [1, 0]) with num_refs=2, l1_refs=2 gives PUs the same
+        two pictures in swapped lists and PUs whose two vectors point into one picture -- the "crossed" and p0 == p1 branches"""
+    assert chroma_format in (0, 1, 2, 3) and log2_ctu in (4, 5, 6) and l1_refs in (1, 2)
     fmt = 1 if chroma_format == 0 else chroma_format                  # 4:0:0 keeps the geometry of 4:2:0
     csx, csy = (0 if fmt == 3 else 1), (1 if fmt == 1 else 0)
     bdc = bit_depth if bit_depth_chroma is None else bit_depth_chroma
@@ -128,6 +135,35 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     ref_idx1 = np.where(intra, -1, ref_idx1)
     mv0 = np.where((ref_idx0 < 0)[:, :, None], 0, mv0)
     mv1 = np.where((ref_idx1 < 0)[:, :, None], 0, mv1)
+
+    rng2 = np.random.RandomState(seed ^ 0x5EED2)                 # the later options: never the first generator, whose order is pinned
+    if bi and l1_refs > 1:
+        ref1_pu = rng2.randint(0, l1_refs, size=(n, n_pu_max))
+        ref_idx1 = np.where(ref_idx1 >= 0, np.take_along_axis(ref1_pu, pu_idx, axis=1), -1)
+    if mv_coherence > 0:
+        # PUs in decoding order (CTU by CTU, z order inside): the PU left of / above a PU's first partition has had its turn
+        key = (np.arange(n)[:, None] * n_pu_max + pu_idx)[inside & ~intra]
+        _, first = np.unique(key, return_index=True)
+        a_all, z_all = np.nonzero(inside & ~intra)
+        order = np.argsort(first, kind="stable")
+        take = rng2.rand(first.size) < mv_coherence
+        above = rng2.rand(first.size) < 0.5
+        delta = rng2.randint(-5, 6, size=(first.size, 2, 2))
+        for i in order:
+            if not take[i]:
+                continue
+            a, zf = a_all[first[i]], z_all[first[i]]
+            nx, ny = px[a, zf] - (0 if above[i] else 4), py[a, zf] - (4 if above[i] else 0)
+            if nx < 0 or ny < 0:
+                continue
+            na = (ny // ctu) * cw + nx // ctu
+            nz = np.nonzero((zx == (nx % ctu) // 4) & (zy == (ny % ctu) // 4))[0][0]
+            if intra[na, nz]:
+                continue
+            mine = (pu_idx[a] == pu_idx[a, zf]) & inside[a] & ~intra[a]
+            ref_idx0[a, mine], ref_idx1[a, mine] = ref_idx0[na, nz], ref_idx1[na, nz]
+            mv0[a, mine] = mv0[na, nz] + delta[i, 0] if ref_idx0[na, nz] >= 0 else 0
+            mv1[a, mine] = mv1[na, nz] + delta[i, 1] if ref_idx1[na, nz] >= 0 else 0
 
     # ---- transform tree: tr_idx in {0,1} per CU (64x64 CUs and AMP CUs always split once)
     tr_cu = (rng.rand(n, n_cu_max) < tr_split_prob).astype(np.int64)
@@ -274,7 +310,7 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     p.chroma_format, p.log2_ctu, p.bit_depth_chroma, p.csx, p.csy = chroma_format, log2_ctu, bdc, csx, csy
     handles = ref_handles if ref_handles is not None else ([0] * num_refs, [0])
     l0 = list(handles[0])[:max(num_refs, 1)]
-    l1 = list(handles[1])[:1] if bi else []
+    l1 = list(handles[1])[:l1_refs] if bi else []
     p.slice = abi.make_slice(abi.B_SLICE if bi else abi.P_SLICE, (l0, l1), ([100 + i for i in range(len(l0))], [200 + i for i in range(len(l1))]))
     # slices: contiguous CTU ranges starting at seeded CTU addresses (mid-row starts included); slice k may differ in its
     # deblocking offsets and chroma QP offsets, all share the reference lists
@@ -310,6 +346,7 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     p.inside = inside
     p.intra = intra & decoded
     p.px, p.py = px, py
+    p.pu_idx = pu_idx                     # [num_ctus, parts]: the PU a partition belongs to, numbered inside its CTU
     return p
 
 
@@ -337,6 +374,24 @@ def _plane_geometry(chroma_format, bit_depth, bit_depth_chroma):
 def noise_planes(width, height, bit_depth, seed, chroma_format=1, bit_depth_chroma=None):
     rng = np.random.RandomState(seed)
     return [rng.randint(0, 1 << bd, size=(height >> sy, width >> sx)).astype(np.int16) for sx, sy, bd in _plane_geometry(chroma_format, bit_depth, bit_depth_chroma)]
+
+
+def smooth_planes(width, height, bit_depth, seed, chroma_format=1, bit_depth_chroma=None):
+    """piecewise ramps: every 32x32 region of a plane (the same area in chroma samples) has a level and two slopes of its own, plus noise of
+    +-1 -- references on which motion-compensated prediction stays smooth inside a block and steps at block edges, so that the deblocking
+    filter finds d < beta on a large part of the edges (on noise_planes it almost never does)"""
+    rng = np.random.RandomState(seed)
+    out = []
+    for sx, sy, bd in _plane_geometry(chroma_format, bit_depth, bit_depth_chroma):
+        w, h = width >> sx, height >> sy
+        gh, gw = (h + 31) // 32, (w + 31) // 32
+        sc = 1 << (bd - 8)
+        level = rng.randint(40 * sc, 216 * sc, size=(gh, gw))
+        slope = rng.randint(-4 * sc, 4 * sc + 1, size=(2, gh, gw)) / 8.0
+        y, x = np.mgrid[0:h, 0:w]
+        v = level[y // 32, x // 32] + slope[0][y // 32, x // 32] * (x % 32 - 16) + slope[1][y // 32, x // 32] * (y % 32 - 16) + rng.randint(-1, 2, size=(h, w))
+        out.append(np.clip(np.round(v), 0, (1 << bd) - 1).astype(np.int16))
+    return out
 
 
 def blocky_planes(width, height, bit_depth, seed, chroma_format=1, bit_depth_chroma=None):
