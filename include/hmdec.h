@@ -90,6 +90,7 @@ typedef struct hmgpu_export_desc hmgpu_export_desc;
 typedef struct hmgpu_export_scale hmgpu_export_scale;
 typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 typedef struct hmgpu_export_window hmgpu_export_window;
+typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -112,6 +113,17 @@ int hmdec_pictures_export_windows(libHMDec_context* ctx, int n, libHMDec_picture
                                   const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
                                   void* stream);
+/* Motion vectors, reference POCs and block information of up to 16 pictures in one call (hmgpu_pictures_export_motion: the BLOCKS
+ * grid or the DENSE per-sample form; destinations, strides and statuses as there), under the validity rule of hmdec_pictures_export:
+ * every picture put out by this decoder and fetched since the last push, of one sequence and on one GPU ordinal, else HMGPU_EINVAL
+ * and nothing is written.  A picture's side information lies in the device context that decoded it: with hmdec_set_devices the
+ * destination and every window are validated once for the whole batch (hmgpu_motion_destination_check) and every context is asked
+ * whether its pictures all have side information (hmgpu_pictures_motion_check) before any context is given work; then each context
+ * gets one call per run of equally spaced slots.  The POC of a picture itself: libHMDEC_get_POC. */
+int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_motion_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,
+                                 void* dst_block, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                 const int64_t batch_stride_bytes[4], int on_stream, void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

@@ -421,6 +421,96 @@ hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* ctx, int32_t n, c
                                                     const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                                     void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ motion and block export
+ * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
+ * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one
+ * kernel launch per call.  The source is what the decompress calls staged for the picture: HM's per-partition arrays
+ * (hmgpu_ctu_meta) and the slice table.
+ *
+ * Source grid: the picture as W4 x H4 blocks of 4x4 luma samples, W4 = width / 4, H4 = height / 4 (exact: the SPS sizes are
+ * multiples of the minimum CU size).  Block (bx, by) is partition z of CTU a: s = log2_ctu_size - 2, a = (by >> s) * ctus_w +
+ * (bx >> s), z = the low s bits of bx on the even and of by on the odd bit positions (HM's z-scan, g_auiRasterToZscan).
+ * Per block and list L (0, 1):
+ *   used     part_size != HMGPU_SIZE_NONE, pred_mode == HMGPU_MODE_INTER, the slice of CTU a (slice_idx[a] -> slice table) is a P or
+ *            B slice for list 0 / a B slice for list 1, and ref_idx[L] >= 0.  The slice-type term is part of the rule: the list-1
+ *            arrays of a picture are not staged by calls without B slices and may hold an earlier picture's values;
+ *            nothing the current picture did not supply is read.
+ *   mv       the coded vector {hor, ver} in quarter luma samples as TComMv holds it, unclipped (reference sample = current +
+ *            mv / 4); 0, 0 where the list is unused, whatever the array holds
+ *   ref_poc  slice ref_poc[L][ref_idx[L]]; HMGPU_MOTION_NO_REF where the list is unused
+ *   block    four int8 channels: 0 mode (-1 not decoded: part_size == HMGPU_SIZE_NONE; 0 inter; 1 intra; any other pred_mode: -1),
+ *            1 log2 CU size (log2_ctu_size - depth), 2 part_size (-1 where not decoded), 3 QP
+ * A picture has side information only when decompress calls have covered every one of its CTUs since it was acquired:
+ * hmgpu_decompress_slice covers its CTU range, the picture, batch and packed entry points all CTUs; hmgpu_picture_acquire,
+ * hmgpu_picture_upload and hmgpu_picture_commit_received (a transferred picture) clear the record.  A picture without full coverage
+ * gives HMGPU_EINVAL.
+ *
+ * HMGPU_MOTION_BLOCKS: the grid itself, in integers.  desc->crop (left, right, top, bottom in luma samples, each a multiple of 4,
+ * else HMGPU_EINVAL; 0,0,0,0 = the coded picture) selects w4 x h4 blocks; scale and windows must be NULL and sample_type
+ * HMGPU_SAMPLE_UINT.  With L = the number of lists selected by desc->lists (bit 0: list 0, bit 1: list 1; selected lists in list order):
+ *   dst_mv[0]   int16 [n][L][2][h4][w4]  (hor plane, then ver plane, per list);  dst_mv[1] must be NULL
+ *   dst_ref     int32 [n][L][h4][w4]
+ *   dst_block   int8  [n][4][h4][w4]
+ * HMGPU_MOTION_DENSE: one value per output sample of hmgpu_pictures_export_windows with the same windows, output size and flips.
+ * windows[i] (the rules of hmgpu_export_window: non-negative, non-empty, whole chroma samples of the sequence's format, flip bit 0
+ * only, reserved 0; origins that are no multiple of 4 included) and either `scale` (width x height outputs; filter must be
+ * HMGPU_SCALE_NEAREST, else HMGPU_EUNSUPPORTED) or no scale and windows of one size (the output's; else HMGPU_EINVAL); desc->crop
+ * must be 0.  Limits per window and axis as for the scaled export: window <= 32 * output, output <= 8 * window, at most 16384
+ * outputs per side (else HMGPU_EUNSUPPORTED).
+ *   output sample (ox, oy) of slot i, window of win_w x win_h luma samples at (left, top), output W x H:
+ *   sx = min(floor((2 * ox + 1) * win_w / (2 * W)), win_w - 1), sy alike (HMGPU_SCALE_NEAREST, in integers); block
+ *   ((left + sx) >> 2, (top + sy) >> 2)
+ *   dst_mv[l]   list l (selected by desc->lists, else must be NULL): sample_type F16 / BF16 / F32 (UINT: HMGPU_EINVAL) [n][2][H][W],
+ *               channel 0 dx = convert(fmul((float)mv hor, kx)), channel 1 dy = convert(fmul((float)mv ver, ky)) in OUTPUT samples:
+ *               kx = (float)((double)W / (4.0 * win_w)), ky = (float)((double)H / (4.0 * win_h)), derived per window on the host; one
+ *               binary32 product, then the conversion of the batched tensor export (nearest even)
+ *   dst_ref     int32 [n][L][H][W], dst_block int8 [n][4][H][W]: the block's values
+ *   flip & 1    every output row reversed and dx negated -- the integer mv hor is negated before the product, which is exact and
+ *               leaves a zero vector +0; ref_poc and block are reversed only
+ * Destinations: slots 0 dst_mv[0], 1 dst_mv[1], 2 dst_ref, 3 dst_block index pitch_bytes (row to row), plane_stride_bytes (channel
+ * to channel) and batch_stride_bytes (picture to picture), so a destination may be a strided view of a larger tensor.  Any
+ * destination may be NULL (not written; its strides are ignored); at least one must be given.  Each must be aligned to its element,
+ * as must its strides; pitch >= row_bytes, plane stride >= pitch * (height - 1) + row_bytes, batch stride >= plane stride *
+ * (channels - 1) + that; and all n pictures of it must lie inside one allocation of the context's device.  Everything is validated
+ * before anything is enqueued and a refused call leaves every destination untouched: an invalid handle anywhere in the list (a
+ * handle may repeat), a picture without side information, n outside 1 .. HMGPU_EXPORT_MAX_BATCH, non-zero reserved words, a lists
+ * mask outside 1 .. 3 and every destination rule give HMGPU_EINVAL.  Stream ordering is that of hmgpu_picture_export, once per call. */
+enum { HMGPU_MOTION_BLOCKS = 0, HMGPU_MOTION_DENSE = 1 };
+#define HMGPU_MOTION_NO_REF INT32_MIN
+enum { HMGPU_MOTION_DST_MV0 = 0, HMGPU_MOTION_DST_MV1 = 1, HMGPU_MOTION_DST_REF = 2, HMGPU_MOTION_DST_BLOCK = 3, HMGPU_MOTION_DSTS = 4 };
+typedef struct hmgpu_motion_desc {
+  int32_t form;                /* HMGPU_MOTION_* */
+  int32_t lists;               /* bit 0: list 0, bit 1: list 1 */
+  int32_t sample_type;         /* DENSE: HMGPU_SAMPLE_F16 / BF16 / F32 of the vectors; BLOCKS: HMGPU_SAMPLE_UINT */
+  int32_t crop[4];             /* BLOCKS: left, right, top, bottom in luma samples, multiples of 4; DENSE: 0 */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_motion_desc;
+typedef struct hmgpu_motion_plan {
+  int32_t lists;               /* L: lists selected */
+  int32_t channels[4];         /* per destination slot (HMGPU_MOTION_DST_*): planes per picture, 0 = the slot does not exist */
+  int32_t width[4], height[4]; /* of every plane, in elements */
+  int32_t elem_bytes[4];
+  int32_t row_bytes[4];        /* width * elem_bytes: the least pitch */
+  int32_t reserved[3];
+} hmgpu_motion_plan;
+/* validates a call's description and reports what it writes; host code, no device needed.  scale / windows: NULL for BLOCKS */
+hmgpu_status hmgpu_motion_plan_for(const hmgpu_seq_params* seq, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
+                                   int32_t n, const hmgpu_export_window windows[], hmgpu_motion_plan* out);
+hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_motion_desc* desc,
+                                          const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2],
+                                          void* dst_ref, void* dst_block, const int64_t pitch_bytes[4],
+                                          const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
+                                          void* stream);
+/* the validation hmgpu_pictures_export_motion makes of a description and a destination for n pictures, and nothing else: nothing is
+ * enqueued and no picture is named (libhmdec: pictures in several contexts of a GPU) */
+/* the other half of that validation: HMGPU_OK when pics[0 .. n) are all valid handles of pictures with side information, else
+ * HMGPU_EINVAL; nothing is enqueued */
+hmgpu_status hmgpu_pictures_motion_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[]);
+hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
+                                            const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref, void* dst_block,
+                                            const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                            const int64_t batch_stride_bytes[4]);
+
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->
  * TDecCu::decompressCU (TDecSlice.cpp:334, TDecCu.cpp:142,373) for the CTUs [first_ctu, first_ctu+num_ctus) of

@@ -105,6 +105,16 @@ def lib():
         L.hmgpu_export_windows_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                              C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
                                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_motion_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale), C.c_int32,
+                                            C.POINTER(abi.ExportWindow), C.POINTER(abi.MotionPlan)]
+        L.hmgpu_pictures_export_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MotionDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
+                                                   C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                                                   C.c_void_p]
+        L.hmgpu_pictures_motion_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.hmgpu_motion_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale),
+                                                     C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -199,6 +209,21 @@ def export_windows_plan(seq, desc, scale, tensor, windows):
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_windows_plan_for")
     return plan
+
+
+def motion_plan(seq, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, crop=(0, 0, 0, 0), n=None):
+    """what Context.export_motion with these arguments writes per picture (hmgpu_motion_plan_for: host code, no GPU): an
+    abi.MotionPlan -- per destination slot (abi.MOTION_DST_*) the channels, width, height, element size and row bytes.  dtype: a
+    torch float dtype, or an abi.SAMPLE_* code (dense; None: float32).  n: the number of pictures (default: one per window, else 1)"""
+    from . import export, motion
+    code = motion.form_code(form)
+    if code == abi.MOTION_BLOCKS:
+        return motion.plan_for(seq, abi.make_motion_desc(code, motion.lists_mask(lists), abi.SAMPLE_UINT, crop), n=1 if n is None else n)
+    st = abi.SAMPLE_F32 if dtype is None else dtype if isinstance(dtype, int) else export.sample_type(dtype)
+    count = n if n is not None else (len(list(windows)) if windows is not None else 1)
+    l, r, t, b = (int(v) for v in crop)
+    win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * count, flip, count)
+    return motion.plan_for(seq, abi.make_motion_desc(code, motion.lists_mask(lists), st), export.make_scale(size, "nearest"), win, count)
 
 
 def export_scale_taps(seq, desc, scale, chroma, axis):
@@ -435,6 +460,47 @@ class Context:
                                      self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win)
+
+    def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
+        """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per
+        destination slot (abi.MOTION_DST_*: vectors 0 and 1, ref_poc, block; a pointer None / 0 = not written)"""
+        from . import motion
+        pics = list(pics)
+        h = (C.c_int32 * max(len(pics), 1))(*pics)
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
+        self._chk(lib().hmgpu_pictures_export_motion(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None, w,
+                                                     mv, ref, blk, q, ps, bs, on_stream, C.c_void_p(stream or None)),
+                  "hmgpu_pictures_export_motion")
+
+    def motion_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides, scale=None, windows=None):
+        """hmgpu_motion_destination_check: the status hmgpu_pictures_export_motion would give this destination; enqueues nothing"""
+        from . import motion
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
+        return lib().hmgpu_motion_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None, w, mv, ref, blk,
+                                                    q, ps, bs)
+
+    def export_motion(self, pics, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=(0, 0, 0, 0),
+                      on_stream=True):
+        """motion vectors, reference POCs and block information of up to 16 decoded pictures as a dict of torch tensors on this
+        context's GPU (libhm_amd.motion: "mv" or "flow0" / "flow1", "ref_poc", "block"), one launch, written on
+        torch.cuda.current_stream() (on_stream) or on the context's own stream.  form "blocks": the grid of 4x4 luma blocks, crop in
+        multiples of 4 luma samples.  form "dense": one value per output sample of export_batch(windows=, flip=, size=,
+        filter="nearest") with the same arguments; dtype torch.float16 / bfloat16 / float32.  out: a dict with some of those keys
+        (only they are written); rows, planes and batch entries may be any stride apart.  Pictures that were uploaded, received or
+        only partly decoded have no side information (HMGPU_EINVAL)."""
+        from . import motion
+        pics = list(pics)
+        return motion.export_motion(lambda desc, sc, win, ptrs, pitches, pstrides, bstrides, st:
+                                    self.export_motion_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st, sc, win),
+                                    self.seq, self.device, len(pics), form, lists, size, windows, flip, dtype, out, crop)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

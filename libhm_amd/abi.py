@@ -140,6 +140,29 @@ def make_export_window(crop, flip=False):
     return w
 
 
+MOTION_BLOCKS, MOTION_DENSE = 0, 1
+MOTION_NO_REF = -(1 << 31)
+MOTION_DST_MV0, MOTION_DST_MV1, MOTION_DST_REF, MOTION_DST_BLOCK, MOTION_DSTS = 0, 1, 2, 3, 4
+
+
+class MotionDesc(C.Structure):
+    _fields_ = [("form", C.c_int32), ("lists", C.c_int32), ("sample_type", C.c_int32), ("crop", C.c_int32 * 4), ("reserved", C.c_int32 * 5)]
+
+
+class MotionPlan(C.Structure):
+    _fields_ = [("lists", C.c_int32), ("channels", C.c_int32 * 4), ("width", C.c_int32 * 4), ("height", C.c_int32 * 4),
+                ("elem_bytes", C.c_int32 * 4), ("row_bytes", C.c_int32 * 4), ("reserved", C.c_int32 * 3)]
+
+
+def make_motion_desc(form, lists=3, sample_type=SAMPLE_UINT, crop=(0, 0, 0, 0)):
+    """form: MOTION_BLOCKS / MOTION_DENSE; lists: the mask (bit 0 list 0, bit 1 list 1); crop: (left, right, top, bottom), BLOCKS only"""
+    d = MotionDesc()
+    d.form, d.lists, d.sample_type = int(form), int(lists), int(sample_type)
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    return d
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

@@ -59,6 +59,10 @@ struct Picture {
   int max_slice = -1;
   bool flags_staged = true;             // the device copies of transform_skip / bypass / ipcm may hold non-zero values
   uint64_t last_use = 0;                // use_seq of the last batch of kernels that read this picture's input arrays (0: none)
+  // CTUs whose input arrays decompress calls have staged since the picture was acquired (hmgpu_pictures_export_motion: a picture has
+  // side information when all are); cleared by acquire, upload and hmgpu_picture_commit_received
+  std::vector<bool> covered;
+  int covered_ctus = 0;
 };
 
 struct EventPair { hipEvent_t a, b; int kind; };
@@ -423,6 +427,14 @@ hmgpu_status push_final(hmgpu_ctx* c, int pic) {
 }
 
 bool valid_pic(const hmgpu_ctx* c, hmgpu_pic pic) { return pic >= 0 && pic < (int)c->pics.size() && c->pics[pic].in_use; }
+
+// the record of which CTUs of a picture carry staged side information (Picture::covered)
+void coverage_clear(Picture& p) { p.covered.clear(); p.covered_ctus = 0; }
+void coverage_add(const hmgpu_ctx* c, Picture& p, int first_ctu, int num_ctus) {
+  if (p.covered.empty()) p.covered.assign((size_t)c->num_ctus, false);
+  for (int a = first_ctu; a < first_ctu + num_ctus; a++)
+    if (!p.covered[(size_t)a]) { p.covered[(size_t)a] = true; p.covered_ctus++; }
+}
 
 // lazy border extension, as HM does when a picture first enters a reference list (TComSlice.cpp:350: extendPicBorder)
 hmgpu_status ensure_extended(hmgpu_ctx* c, int pic) {
@@ -815,6 +827,7 @@ hmgpu_status hmgpu_picture_acquire(hmgpu_ctx* c, hmgpu_pic* out) {
     if (!p.in_use) {
       p.in_use = true; p.sao_applied = false; p.filter_ready = false; p.sao_any = false; p.calls.clear(); p.max_slice = -1;
       p.extended = false;
+      coverage_clear(p);
       p.dev.sao_applied = 0; p.dev.any_nofilt = 0;
       *out = (hmgpu_pic)i;
       hmgpu_status st = push_final(c, (int)i);
@@ -833,6 +846,7 @@ hmgpu_status hmgpu_picture_release(hmgpu_ctx* c, hmgpu_pic pic) {
 hmgpu_status hmgpu_picture_upload(hmgpu_ctx* c, hmgpu_pic pic, const int16_t* const planes[3], const int32_t strides[3]) {
   if (!c || !valid_pic(c, pic) || !planes || !strides) return HMGPU_EINVAL;
   Picture& p = c->pics[pic];
+  coverage_clear(p);                   // (uploaded samples come without side information)
   if (p.sao_applied) {                 // uploaded samples ARE the picture: back to the reconstruction planes
     p.sao_applied = false; p.dev.sao_applied = 0;
     hmgpu_status st = push_final(c, pic);
@@ -1121,6 +1135,7 @@ hmgpu_status hmgpu_picture_commit_received(hmgpu_ctx* c, hmgpu_pic pic) {
   if (!c || !valid_pic(c, pic)) return HMGPU_EINVAL;
   Picture& p = c->pics[pic];
   if (p.sao_applied) return HMGPU_EINVAL;          // hmgpu_picture_device_region(RECEIVE) was not called
+  coverage_clear(p);                               // (only the planes travelled)
   p.extended = true;                               // the margins travelled with the planes
   return HMGPU_OK;
 }
@@ -2002,6 +2017,175 @@ hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_
   return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
 }
 
+// ------------------------------------------------------------------------------------------------ motion and block export (k_motion.hip)
+// hmgpu_motion_plan_for and what the entry point needs beyond the plan: the output element of the dense form (kElem*)
+static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int n,
+                                const hmgpu_export_window* win, hmgpu_motion_plan* out, int* elem) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  *elem = kElemU16;
+  const int fmt = seq->chroma_format;
+  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 3) || (seq->height & 3)) return HMGPU_EINVAL;
+  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int k = 0; k < 5; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->form != HMGPU_MOTION_BLOCKS && d->form != HMGPU_MOTION_DENSE) return HMGPU_EINVAL;
+  if (d->lists < 1 || d->lists > 3) return HMGPU_EINVAL;
+  const int L = (d->lists & 1) + (d->lists >> 1);
+  int w = 0, h = 0;
+  if (d->form == HMGPU_MOTION_BLOCKS) {
+    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
+    const int* cr = d->crop;
+    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0 || ((cr[0] | cr[1] | cr[2] | cr[3]) & 3)) return HMGPU_EINVAL;      // whole blocks
+    w = (seq->width - cr[0] - cr[1]) / 4; h = (seq->height - cr[2] - cr[3]) / 4;
+    if (w <= 0 || h <= 0) return HMGPU_EINVAL;
+    out->channels[HMGPU_MOTION_DST_MV0] = 2 * L;
+    out->elem_bytes[HMGPU_MOTION_DST_MV0] = 2;
+  } else {
+    if (!win) return HMGPU_EINVAL;
+    if (d->sample_type != HMGPU_SAMPLE_F16 && d->sample_type != HMGPU_SAMPLE_BF16 && d->sample_type != HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
+    if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;            // the window is the crop
+    *elem = d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+    if (sc) {
+      for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+      if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+      if (sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                       // vectors are not interpolated
+    }
+    const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0, mono = fmt == 0;
+    for (int i = 0; i < n; i++) {
+      const int* cr = win[i].crop;
+      if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) return HMGPU_EINVAL;
+      if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+      const int ww = seq->width - cr[0] - cr[1], wh = seq->height - cr[2] - cr[3];
+      if (ww <= 0 || wh <= 0) return HMGPU_EINVAL;
+      if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+      if (sc) {
+        const long long in[2] = {ww, wh}, o[2] = {sc->width, sc->height};
+        for (int ax = 0; ax < 2; ax++) if (o[ax] > 16384 || in[ax] > 32 * o[ax] || o[ax] > 8 * in[ax]) return HMGPU_EUNSUPPORTED;
+      } else {
+        if (!i) { w = ww; h = wh; }
+        if (ww != w || wh != h) return HMGPU_EINVAL;                                          // unscaled: one size, the output's
+        if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
+      }
+    }
+    if (sc) { w = sc->width; h = sc->height; }
+    const int es = *elem == kElemF32 ? 4 : 2;
+    for (int l = 0; l < 2; l++) if ((d->lists >> l) & 1) { out->channels[l] = 2; out->elem_bytes[l] = es; }
+  }
+  out->lists = L;
+  out->channels[HMGPU_MOTION_DST_REF] = L; out->elem_bytes[HMGPU_MOTION_DST_REF] = 4;
+  out->channels[HMGPU_MOTION_DST_BLOCK] = 4; out->elem_bytes[HMGPU_MOTION_DST_BLOCK] = 1;
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!out->channels[k]) { out->elem_bytes[k] = 0; continue; }
+    out->width[k] = w; out->height[k] = h; out->row_bytes[k] = w * out->elem_bytes[k];
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_motion_plan_for(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int32_t n,
+                                   const hmgpu_export_window windows[], hmgpu_motion_plan* out) {
+  int elem = 0;
+  const hmgpu_status st = motion_plan(seq, d, sc, n, windows, out, &elem);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// every destination given: element alignment, strides against the extents they step over, and the whole span of n pictures inside one
+// allocation of the context's device.  vec: bit k set when every group of four elements of slot k may be one store
+static hmgpu_status motion_dst_ok(const hmgpu_ctx* c, const hmgpu_motion_plan& plan, int n, void* const dst[4], const int64_t* pitch,
+                                  const int64_t* pstride, const int64_t* bstride, int* vec) {
+  bool any = false;
+  *vec = 0;
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!dst[k]) continue;
+    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
+    any = true;
+    const int64_t es = plan.elem_bytes[k];
+    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48)) return HMGPU_EINVAL;
+    const int64_t pic = pstride[k] * (plan.channels[k] - 1) + plane;
+    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % es || pitch[k] % es || pstride[k] % es || bstride[k] % es) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
+    const int64_t g = 4 * es;
+    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && pstride[k] % g == 0 && bstride[k] % g == 0) *vec |= 1 << k;
+  }
+  return any ? HMGPU_OK : HMGPU_EINVAL;
+}
+
+hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref, void* dst_block,
+                                            const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                            const int64_t batch_stride_bytes[4]) {
+  if (!c || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_motion_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+  return motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+}
+
+hmgpu_status hmgpu_pictures_motion_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) {
+    if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+    if (c->pics[pics[i]].covered_ctus != c->num_ctus) return HMGPU_EINVAL;       // no side information (uploaded, received, partly decoded)
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_motion_desc* d,
+                                          const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst_mv[2],
+                                          void* dst_ref, void* dst_block, const int64_t pitch_bytes[4],
+                                          const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
+                                          void* stream) {
+  if (!c || !pics || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  { const hmgpu_status st = hmgpu_pictures_motion_check(c, n, pics); if (st != HMGPU_OK) return st; }
+  hmgpu_motion_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+  { const hmgpu_status st = motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  MotionArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.lists = d->lists; a.nlists = plan.lists;
+  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
+  for (int i = 0; i < n; i++) {
+    const PicDev& p = c->pics[pics[i]].dev;
+    MotionSrc& s = a.src[i];
+    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.qp = p.qp;
+    for (int l = 0; l < 2; l++) { s.mv[l] = p.mv[l]; s.ref_idx[l] = p.ref_idx[l]; }
+    s.slice_idx = p.slice_idx; s.slices = p.slices;
+  }
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!dst[k]) continue;
+    a.dst[k] = static_cast<uint8_t*>(dst[k]);
+    a.pitch[k] = pitch_bytes[k]; a.pstride[k] = plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
+  }
+  a.vec = vec;
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  if (d->form == HMGPU_MOTION_BLOCKS) {
+    a.x4 = d->crop[0] / 4; a.y4 = d->crop[2] / 4; a.w4 = plan.width[HMGPU_MOTION_DST_REF]; a.h4 = plan.height[HMGPU_MOTION_DST_REF];
+    if (a.x4 & 3) a.vec = 0;                         // a lane's four blocks are aligned in the picture, not in the crop
+    launch_motion_blocks(a, hs);
+  } else {
+    a.W = plan.width[HMGPU_MOTION_DST_REF]; a.H = plan.height[HMGPU_MOTION_DST_REF];
+    for (int i = 0; i < n; i++) {
+      const int* cr = windows[i].crop;
+      MotionWin& w = a.win[i];
+      w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
+      w.kx = (float)((double)a.W / (4.0 * w.w)); w.ky = (float)((double)a.H / (4.0 * w.h));     // quarter luma samples -> output samples
+      a.flip |= (uint32_t)(windows[i].flip & 1) << i;
+    }
+    launch_motion_dense(a, elem, hs);
+  }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
 // slice table entry of one slice (validation, SliceDev, scaling lists): the part of a slice call that does not depend on CTUs
 static hmgpu_status register_slice(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx, const hmgpu_slice_params* sl, hipStream_t hs) {
   if (slice_idx < 0 || slice_idx >= HMGPU_MAX_SLICES || !sl) return HMGPU_EINVAL;
@@ -2114,6 +2298,7 @@ static hmgpu_status finish_stage(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx,
   SliceCall call = {first_ctu, num_ctus, slice_idx, has_intra, any_wp, cells, any_b, any_i};
   p.calls.push_back(call);
   p.extended = false;
+  coverage_add(c, p, first_ctu, num_ctus);
   *call_out = call;
   return HMGPU_OK;
 }

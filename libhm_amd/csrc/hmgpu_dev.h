@@ -424,6 +424,30 @@ struct ScaleArgs {
 };
 // n pictures; elem: kElem*
 void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s);
+// motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
+// arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
+// dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.
+struct MotionSrc {
+  const uint8_t* depth; const int8_t* part_size; const int8_t* pred_mode; const int8_t* qp;
+  const int16_t* mv[2]; const int8_t* ref_idx[2];
+  const uint16_t* slice_idx;
+  const SliceDev* slices;
+};
+struct MotionWin { int32_t left, top, w, h; float kx, ky; };   // dense form: window in luma samples, quarter samples -> output samples
+struct MotionArgs {
+  MotionSrc src[kMaxExportBatch];
+  MotionWin win[kMaxExportBatch];
+  int32_t n, lists, nlists;        // pictures; the lists mask; selected lists
+  int32_t log2ctu, ctus_w, parts;  // geometry of the context
+  int32_t x4, y4, w4, h4;          // blocks form: first block and size of the cropped grid
+  int32_t W, H;                    // dense form: output size
+  uint32_t flip;                   // dense form: bit i: slot i is mirrored
+  int32_t vec;                     // blocks form: a group of four blocks may be one store per plane (alignment of crop, dst and strides)
+  uint8_t* dst[4];
+  int64_t pitch[4], pstride[4], bstride[4];   // bytes: row to row, plane to plane, picture to picture
+};
+void launch_motion_blocks(const MotionArgs& a, hipStream_t s);
+void launch_motion_dense(const MotionArgs& a, int elem, hipStream_t s);   // elem: kElemF16 / kElemBF16 / kElemF32
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

@@ -996,6 +996,34 @@ hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc
   return hmgpu_picture_export(ctx_of(pic), pic->handle, desc, dst, pitch_bytes, on_stream, stream);
 }
 
+// The slots of a batched export by device context, as runs of equally spaced slots (slot j of a run lies run-distance * batch stride
+// after the one before): one device call each, a single run when one context holds every picture.  windows: null, or one per picture
+// (each run carries those of its own slots).
+namespace {
+struct ExportRun { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; hmgpu_export_window w[HMGPU_EXPORT_MAX_BATCH]; };
+std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_export_window* windows) {
+  std::vector<ExportRun> runs;
+  std::vector<bool> taken((size_t)n, false);
+  for (int i = 0; i < n; i++) {
+    if (taken[(size_t)i]) continue;
+    std::vector<int> idx;                                                // the slots of this context not yet in a run, ascending
+    for (int j = i; j < n; j++) if (!taken[(size_t)j] && pics[j]->home == pics[i]->home) idx.push_back(j);
+    size_t m = 1;
+    const int step = idx.size() > 1 ? idx[1] - idx[0] : 1;
+    while (m < idx.size() && idx[m] - idx[m - 1] == step) m++;
+    ExportRun r;
+    r.home = pics[i]->home; r.first = i; r.step = step; r.n = (int)m;
+    for (size_t q = 0; q < m; q++) {
+      r.h[q] = pics[idx[q]]->handle;
+      if (windows) r.w[q] = windows[idx[q]];
+      taken[(size_t)idx[q]] = true;
+    }
+    runs.push_back(r);
+  }
+  return runs;
+}
+}  // namespace
+
 hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                        const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows) {
@@ -1008,31 +1036,11 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
     if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
   }
   // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
-  // the slots of one context as runs of equal distance (slot j of a run lies run-distance * batch stride after the one before), one
-  // hmgpu_pictures_export each: a single call when one context holds every picture.
+  // one hmgpu_pictures_export per run of slots (export_runs).
   { const hmgpu_status st = windows ? hmgpu_export_windows_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, dst, pitch_bytes, batch_stride_bytes)
                                     : hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
     if (st != HMGPU_OK) return st; }
-  struct Run { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; hmgpu_export_window w[HMGPU_EXPORT_MAX_BATCH]; };
-  std::vector<Run> runs;
-  std::vector<bool> taken((size_t)n, false);
-  for (int i = 0; i < n; i++) {
-    if (taken[(size_t)i]) continue;
-    std::vector<int> idx;                                                // the slots of this context not yet in a run, ascending
-    for (int j = i; j < n; j++) if (!taken[(size_t)j] && pics[j]->home == pics[i]->home) idx.push_back(j);
-    size_t m = 1;
-    const int step = idx.size() > 1 ? idx[1] - idx[0] : 1;
-    while (m < idx.size() && idx[m] - idx[m - 1] == step) m++;
-    Run r;
-    r.home = pics[i]->home; r.first = i; r.step = step; r.n = (int)m;
-    for (size_t q = 0; q < m; q++) {
-      r.h[q] = pics[idx[q]]->handle;
-      if (windows) r.w[q] = windows[idx[q]];               // (the windows of a run's own slots)
-      taken[(size_t)idx[q]] = true;
-    }
-    runs.push_back(r);
-  }
-  for (const Run& r : runs) {
+  for (const ExportRun& r : export_runs(n, pics, windows)) {
     void* d[3];
     int64_t bs[3];
     for (int k = 0; k < 3; k++) {
@@ -1042,6 +1050,45 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
     hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
     const hmgpu_status st = windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
                                     : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status Decoder::export_motion(int n, PicData* const* pics, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
+                                     const hmgpu_export_window* windows, void* const dst_mv[2], void* dst_ref, void* dst_block,
+                                     const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4],
+                                     int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
+  flush_batch();
+  for (int i = 0; i < n; i++) {
+    const PicData* p = pics[i];
+    if (!p->on_device || !p->decoded) return HMGPU_EINVAL;
+    if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
+  }
+  // as export_pictures: the destination (and every window) validated once for all n slots, then one call per run of slots of one
+  // context -- the context that decoded the pictures (PicData::home), the only one that holds their side information.  Whether every
+  // picture has side information is asked of every context first (hmgpu_pictures_motion_check), so that no context is given work
+  // when another one's call would be refused.
+  { const hmgpu_status st = hmgpu_motion_destination_check(ctx_of(pics[0]), n, desc, scale, windows, dst_mv, dst_ref, dst_block, pitch_bytes,
+                                                           plane_stride_bytes, batch_stride_bytes);
+    if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, windows);
+  for (const ExportRun& r : runs) {
+    const hmgpu_status st = hmgpu_pictures_motion_check(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
+    if (st != HMGPU_OK) return st;
+  }
+  for (const ExportRun& r : runs) {
+    void* d[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+    int64_t bs[4];
+    for (int k = 0; k < 4; k++) {
+      if (d[k]) d[k] = static_cast<char*>(d[k]) + (int64_t)r.first * batch_stride_bytes[k];
+      bs[k] = batch_stride_bytes[k] * r.step;
+    }
+    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
+    const hmgpu_status st = hmgpu_pictures_export_motion(c, r.n, r.h, desc, scale, windows ? r.w : nullptr, d, d[2], d[3], pitch_bytes,
+                                                         plane_stride_bytes, bs, on_stream, stream);
     if (st != HMGPU_OK) return st;
   }
   return HMGPU_OK;

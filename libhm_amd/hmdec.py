@@ -78,6 +78,10 @@ def lib():
         L.hmdec_pictures_export_windows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
                                                     C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MotionDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
+                                                   C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                                   C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -227,6 +231,54 @@ class Picture:
         instead of new ones; dtype: torch.float16 / bfloat16 / float32 gives normalised float elements (export_batch with one
         picture, without the batch dimension; mean / std / scale / bias as there).  Valid until the next push into the decoder."""
         return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias)
+
+    def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
+        """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
+        out = export_motion_batch([self], form, lists, size, None if window is None else [window],
+                                  [flip] if (flip or window is not None) and _form_is_dense(form) else None, dtype, None, crop)
+        return {k: t[0] for k, t in out.items()}
+
+
+def _form_is_dense(form):
+    from . import motion
+    return motion.form_code(form) == abi.MOTION_DENSE
+
+
+def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=None,
+                        enqueue=True, n=None):
+    """Motion vectors, reference POCs and block information of up to 16 pictures a decoder has put out (fetched since the last push,
+    one sequence, one GPU: hmdec_pictures_export_motion) as a dict of torch tensors with a leading batch dimension, written on
+    torch.cuda.current_stream(): libhm_amd.motion describes the forms and keys.  crop: None = the whole coded picture for
+    form="blocks" and the conformance window for form="dense" (what export_batch shows: the same windows, flips and size give
+    aligned pixels and vectors), "conformance", or (left, right, top, bottom).  enqueue False / n: only the tensors of n pictures are
+    allocated (Decoder.frames)."""
+    from . import HmgpuError, motion
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("export_motion_batch: no pictures")
+    first = pictures[0]
+    if first.ctx is None:
+        raise RuntimeError("export_motion_batch: the picture does not know its decoder")
+    g = first.geometry()
+    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
+    seq.chroma_format = g["chroma_format"]
+    if crop is None:
+        crop = (0, 0, 0, 0) if motion.form_code(form) == abi.MOTION_BLOCKS else "conformance"
+    if crop == "conformance":
+        crop = first.conformance_window()
+    dev = first.device
+    if dev < 0:
+        raise RuntimeError("export_motion_batch: the picture is not on a device (parse-only, or its sequence has ended)")
+
+    def call(desc, sc, win, ptrs, pitches, pstrides, bstrides, st):
+        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
+        w = None if win is None else (abi.ExportWindow * len(win))(*win)
+        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
+        r = lib().hmdec_pictures_export_motion(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None, w, mv, ref,
+                                               blk, q, ps, bs, 1, C.c_void_p(st or None))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_motion")
+    return motion.export_motion(call, seq, dev, len(pictures) if n is None else n, form, lists, size, windows, flip, dtype, out, crop, enqueue)
 
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
@@ -401,17 +453,22 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def frames(self, stream, batch=None, windows=None, **export_kw):
+    def frames(self, stream, batch=None, windows=None, motion=None, **export_kw):
         """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
         of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
         batch=N: (pocs, tensors) with up to N (<= 16) pictures per item instead, the tensors those of export_batch: slots are filled
         in output order, the pictures fetched after one push in one batched call each; an item is yielded when it is full, the
         remainder at the end of the stream as a view of the first n slots.  windows (batch=N only): a function; fn(n) returns
-        (windows, flips) for the n pictures of one batched call (export.random_resized_crop with the picture's size bound)."""
+        (windows, flips) for the n pictures of one batched call (export.random_resized_crop with the picture's size bound).
+        motion (batch=N only): True, or a dict of export_motion_batch arguments (form, lists, dtype, ...): the items become
+        (pocs, tensors, motion dict), the motion tensors allocated and filled slot by slot like the picture tensors; with the
+        dense form the windows and flips fn(n) returned, and size=, apply to both.  motion=None leaves the items as they were."""
         if windows is not None and batch is None:
             raise ValueError("frames(windows=) needs batch=")
+        if motion is not None and motion is not False and batch is None:
+            raise ValueError("frames(motion=) needs batch=")
         if batch is not None:
-            yield from self._frames_batched(stream, int(batch), export_kw, windows)
+            yield from self._frames_batched(stream, int(batch), export_kw, windows, None if motion is False else motion)
             return
         nals = split_nal_units(stream)
         for i, nal in enumerate(nals):
@@ -427,7 +484,7 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def _frames_batched(self, stream, batch, export_kw, windows=None):
+    def _frames_batched(self, stream, batch, export_kw, windows=None, motion=None):
         if not 1 <= batch <= abi.EXPORT_MAX_BATCH:
             raise ValueError("batch: 1 .. %d" % abi.EXPORT_MAX_BATCH)
         if "out" in export_kw:
@@ -435,8 +492,20 @@ class Decoder:
         kw = dict(layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                   filter="bilinear", out=None)
         kw.update(export_kw)
+        mkw = None
+        from . import motion as _motion
+        if motion is not None:
+            mkw = dict(form="blocks") if motion is True else dict(motion)
+            for key in ("out", "windows", "flip"):
+                if key in mkw:
+                    raise ValueError("frames(motion=): no %s= in the motion dict (the items are allocated here; windows and flips come "
+                                     "from frames(windows=fn))" % key)
+            mkw["form"] = _motion.form_code(mkw.get("form", "blocks"))
+            if mkw["form"] == abi.MOTION_DENSE:
+                mkw.setdefault("size", kw["size"])
+                mkw.setdefault("crop", kw["crop"])
         nals = split_nal_units(stream)
-        item, pocs = None, []
+        item, pocs, mitem = None, [], None
         for i, nal in enumerate(nals):
             eof = i == len(nals) - 1
             while True:
@@ -457,14 +526,26 @@ class Decoder:
                         if item is None:             # the first picture of an item allocates all N slots
                             item = _export(take[:1], batch, enqueue=False, windows=[wkw["windows"][0]] * batch if wkw else None, **kw)
                         export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **wkw, **export_kw)
+                        if mkw is not None:
+                            mw = wkw if mkw["form"] == abi.MOTION_DENSE else {}
+                            if mitem is None:
+                                mitem = export_motion_batch(take[:1], enqueue=False, n=batch,
+                                                            **dict(mkw, **({"windows": [mw["windows"][0]] * batch} if mw else {})))
+                            export_motion_batch(take, out={k: t[len(pocs):len(pocs) + len(take)] for k, t in mitem.items()}, **mw, **mkw)
                         pocs += [p.poc for p in take]
                         if len(pocs) == batch:
-                            yield pocs, _slots(item, 0, batch)
-                            item, pocs = None, []
+                            if mkw is None:
+                                yield pocs, _slots(item, 0, batch)
+                            else:
+                                yield pocs, _slots(item, 0, batch), mitem
+                            item, pocs, mitem = None, [], None
                 if not new_pic:
                     break
         if pocs:
-            yield pocs, _slots(item, 0, len(pocs))
+            if mkw is None:
+                yield pocs, _slots(item, 0, len(pocs))
+            else:
+                yield pocs, _slots(item, 0, len(pocs)), {k: t[:len(pocs)] for k, t in mitem.items()}
 
 
 def _slots(item, a, b):
