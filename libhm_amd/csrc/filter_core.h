@@ -190,7 +190,8 @@ __device__ inline s16x2 lut_offsets(uint32_t idx_pk, uint32_t tab_lo, uint32_t t
 // PCMLFDisableProcess (TComSampleAdaptiveOffset.cpp:742-835) folded into SAO: which of the 8 samples at (x, row) of component
 // comp belong to lossless / PCM-unfiltered CUs and keep the SAO input.  Returns a mask with 0xffff per exempt sample pair half
 // packed like the samples (4 dwords); only called for pictures that hold such CUs (PicDev::any_nofilt).
-__device__ inline void sao_exempt_mask(const PicDev& P, int comp, int x, int row, uint32_t (&m)[4]) {
+template <typename PIC>
+__device__ inline void sao_exempt_mask(const PIC& P, int comp, int x, int row, uint32_t (&m)[4]) {
   const int sx = comp ? P.csx : 0, sy = comp ? P.csy : 0;
   const BlkInfo* g = P.blk + (size_t)((row << sy) >> 2) * P.grid_w + ((x << sx) >> 2);
   // full horizontal resolution: samples 0-3 / 4-7 lie in two 4x4 blocks; subsampled chroma: every pair of samples in its own block (four blocks)

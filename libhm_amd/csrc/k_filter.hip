@@ -35,23 +35,69 @@ struct FilterLds {
   int32_t units[2][4];
 };
 
-// SAO of one group of 8 samples at (x, row) of component comp, reading the deblocked copy; (ox, oy) = picture coordinates
-// of copy element [0][0]
-struct SaoPrm { uint32_t w0, off_lo, off_hi; };               // SaoDev as three dwords
-__device__ inline SaoPrm sao_fetch(const PicDev& P, int comp, int x, int row) {
-  const int log2ctb = P.log2ctu - (comp ? 1 : 0);
-  const int w = P.width >> (comp ? 1 : 0), h = P.height >> (comp ? 1 : 0);
-  SaoPrm r = {0xffu, 0u, 0u};
-  if (x < w && row < h) {
-    const uint32_t* pw = reinterpret_cast<const uint32_t*>(P.saoprm + ((size_t)(row >> log2ctb) * P.ctus_w + (x >> log2ctb)) * 3 + comp);
-    r.w0 = ldg(pw); r.off_lo = ldg(pw + 1); r.off_hi = ldg(pw + 2);
-  }
-  return r;
+// What the kernel reads of a picture's PicDev and of its slice 0, fetched ONCE at kernel entry through the constant address space: the
+// descriptor is the same for the whole workgroup, so these are scalar loads (merged by the struct's layout) issued together and waited
+// for once, before the first vector address is formed; from then on the values sit in SGPRs and no branch fetches a field again.
+// (Nothing on the device writes a PicDev or the slice table while the filter runs.)
+struct SliceLf { int tc_off, beta_off, cb_off, cr_off; };     // the deblocking constants of one slice
+struct FPic {
+  static constexpr int csx = 1, csy = 1;                      // the fused kernel runs on 4:2:0-shaped pictures only (run_filter)
+  int width, height, bd0, bd1, bd2, log2ctu, ctus_w, pitch[2], grid_w, any_nofilt, mono;
+  __device__ inline int bd(int comp) const { return comp == 0 ? bd0 : comp == 1 ? bd1 : bd2; }   // (no array: a lane's component is a run-time value)
+  const int16_t* rec[2];
+  int16_t* sao[2];
+  const uint16_t* slice_idx;
+  const SliceDev* slices;
+  const BlkInfo* blk;
+  const EdgeRec* edges;
+  const SaoDev* saoprm;
+  SliceLf s0;
+};
+template <typename T> __device__ inline T ldc(const T* p) { return *(const T __attribute__((address_space(4)))*)p; }
+__device__ inline FPic pic_state(const PicDev* p) {
+  FPic f;
+  f.width = ldc(&p->width); f.height = ldc(&p->height);
+  f.bd0 = ldc(&p->bd[0]); f.bd1 = ldc(&p->bd[1]); f.bd2 = ldc(&p->bd[2]);
+  f.log2ctu = ldc(&p->log2ctu); f.ctus_w = ldc(&p->ctus_w);
+  f.pitch[0] = ldc(&p->pitch[0]); f.pitch[1] = ldc(&p->pitch[1]);
+  f.grid_w = ldc(&p->grid_w);
+  f.rec[0] = ldc(&p->rec[0]); f.rec[1] = ldc(&p->rec[1]);
+  f.sao[0] = ldc(&p->sao[0]); f.sao[1] = ldc(&p->sao[1]);
+  f.any_nofilt = ldc(&p->any_nofilt); f.mono = ldc(&p->mono);
+  f.slice_idx = ldc(&p->slice_idx); f.slices = ldc(&p->slices);
+  f.blk = ldc(&p->blk); f.edges = ldc(&p->edges); f.saoprm = ldc(&p->saoprm);
+  const SliceDev* s = f.slices;
+  f.s0 = {ldc(&s->tc_offset_div2), ldc(&s->beta_offset_div2), ldc(&s->pps_cb_qp_offset), ldc(&s->pps_cr_qp_offset)};
+  return f;
 }
 
+// Per-lane memory accesses go through buffer descriptors: a 64-bit base that is the same for the whole workgroup (the tile's first
+// row of a plane, the tile's first cell of a grid; SGPRs) plus a 32-bit byte offset per lane, bounded by the tile's own extent, so no
+// picture size limit arises.  The descriptor's size is exactly what the tile may touch: a lane with nothing to fetch asks at that
+// offset -- the range check answers with zeros and nothing goes to memory (as k_mc.hip does for idle lanes), so no load is predicated
+// and all of a thread's loads can be in flight together.
+struct Span {
+  __amdgpu_buffer_rsrc_t rs;
+  uint32_t bytes;                                              // the offset of "nowhere"
+  __device__ inline Span(const void* base, uint32_t n) : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000)), bytes(n) {}
+  __device__ inline uint32_t at(bool valid, uint32_t off) const { return valid ? off : bytes; }
+  __device__ inline u32x4 load4(uint32_t off) const { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0)); }
+  __device__ inline uint32_t load_u16(uint32_t off) const { return (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, 0); }
+  __device__ inline void store4(uint32_t off, u32x4 v) const { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b128(rs, 0, 0, 0)), v), rs, off, 0, 0); }
+};
+
+// SaoDev as three dwords
+struct SaoPrm { uint32_t w0, off_lo, off_hi; };
+__device__ inline SaoPrm sao_fetch(const Span& sp, uint32_t off) {
+  const auto v = __builtin_amdgcn_raw_buffer_load_b96(sp.rs, off, 0, 0);
+  return {(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]};
+}
+
+// SAO of one group of 8 samples at (x, row) of component comp, reading the deblocked copy; (ox, oy) = picture coordinates
+// of copy element [0][0]
 // returns the group's eight output samples (the caller stores them: luma as they are, chroma paired with the other component's)
 template <int W, bool NF>
-__device__ inline u32x4 sao_group(const PicDev& P, int comp, const int16_t (*t)[W], int ox, int oy, int x, int row, const SaoPrm& prm) {
+__device__ inline u32x4 sao_group(const FPic& P, int comp, const int16_t (*t)[W], int ox, int oy, int x, int row, const SaoPrm& prm) {
   const int cs = comp ? 1 : 0;
   const int w = P.width >> cs, h = P.height >> cs;
   const int log2ctb = P.log2ctu - cs;
@@ -62,7 +108,7 @@ __device__ inline u32x4 sao_group(const PicDev& P, int comp, const int16_t (*t)[
   const u32x4 cur = *reinterpret_cast<const u32x4*>(line);
   if (type < 0) return cur;
   const uint32_t off_lo = prm.off_lo, off_hi = prm.off_hi;
-  const int bd = P.bd[comp], maxv = (1 << bd) - 1;
+  const int bd = P.bd(comp), maxv = (1 << bd) - 1;
   uint32_t out[4];
   if (type == HMGPU_SAO_BO) {
     const int shift = bd - 5, band0 = (w0 >> 8) & 0xff;
@@ -111,35 +157,25 @@ __device__ inline u32x4 sao_group(const PicDev& P, int comp, const int16_t (*t)[
   return u32x4{out[0], out[1], out[2], out[3]};
 }
 
-// the EdgeRec unit (k_prep: Bs, mean QP, exemptions) of the edge unit of direction DIR whose Q block is at luma (x, y); requested at
-// kernel entry, long before the unit is filtered (its latency hides behind the tile load)
-template <int DIR>
-__device__ inline uint32_t edge_fetch(const PicDev& P, int x, int y, bool mine) {
-  if (!(mine && x >= 0 && y >= 0 && x < P.width && y < P.height)) return 0u;
-  const uint16_t* rec = reinterpret_cast<const uint16_t*>(P.edges + (size_t)(y >> 3) * (P.grid_w >> 1) + (x >> 3));
-  return ldg(rec + (DIR == 0 ? ((y >> 2) & 1) : 2 + ((x >> 2) & 1)));
-}
-
 // Deblocking runs in two steps so that lanes are spent on real work only: every edge unit of the tile is CLASSIFIED by its
 // own thread (edge flags, Bs; most units of large blocks stop here), the units that filter are compacted into a list in LDS
 // and APPLIED by the first threads of the block -- a tile of 32x32 CUs keeps one wave busy with the filter arithmetic instead
 // of three.  A list entry: unit index | Bs << 8 | P side unfiltered << 10 | Q side unfiltered << 11 | (QP + 64) << 12 |
 // Q side's slice << 20.
-struct SliceLf { int tc_off, beta_off, cb_off, cr_off; };     // the deblocking constants of one slice
 __device__ inline SliceLf slice_lf(const SliceDev* s) {
   return {ldg(&s->tc_offset_div2), ldg(&s->beta_offset_div2), ldg(&s->pps_cb_qp_offset), ldg(&s->pps_cr_qp_offset)};
 }
 static_assert(HMGPU_MAX_SLICES <= 4096, "slice index must fit the 12 bits of a list entry");
 
-// unit u of the tile with EdgeRec unit `rec` (0: not filtered) at luma (x, y) -> list entry
+// unit u of the tile with EdgeRec unit `rec` (0: not filtered; k_prep: Bs, mean QP, exemptions) -> list entry.  slice: the one whose
+// deblocking constants apply, that of the Q side's CTU (TComLoopFilter.cpp:565-566).  Both were requested at kernel entry: nothing is
+// fetched here
 template <bool NF>
-__device__ inline uint32_t edge_classify(const PicDev& P, uint32_t rec, int u, int x, int y) {
-  if ((rec & 3u) == 0u) return 0u;
+__device__ inline uint32_t edge_classify(uint32_t rec, uint32_t slice, int u) {
   const uint32_t bs = rec & 3u, qp = (rec >> 2) & 127u;                 // QP + 32
   const uint32_t p_nf = NF ? (rec >> 9) & 1u : 0u, q_nf = NF ? (rec >> 10) & 1u : 0u;
-  // the slice whose deblocking constants apply: the one of the Q side's CTU (TComLoopFilter.cpp:565-566)
-  const uint32_t slice = P.slice_idx ? (uint32_t)ldg(P.slice_idx + (size_t)(y >> P.log2ctu) * P.ctus_w + (x >> P.log2ctu)) : 0u;
-  return (uint32_t)u | (bs << 8) | (p_nf << 10) | (q_nf << 11) | ((qp + 32u) << 12) | (slice << 20);
+  const uint32_t e = (uint32_t)u | (bs << 8) | (p_nf << 10) | (q_nf << 11) | ((qp + 32u) << 12) | (slice << 20);
+  return bs ? e : 0u;
 }
 
 // append the wave's active units to its list; called by the three waves that classify
@@ -159,14 +195,14 @@ __device__ inline uint32_t pop_unit(const uint32_t (&list)[3][64], const int32_t
 
 // one classified edge unit of direction DIR, filtered on the copies
 template <int DIR, bool NF>
-__device__ inline void edge_apply(const PicDev& P, FilterLds& L, int x0, int y0, uint32_t rec, const SliceLf& s0) {
+__device__ inline void edge_apply(const FPic& P, FilterLds& L, int x0, int y0, uint32_t rec) {
   if (rec == 0u) return;
   const int u = rec & 0xff, bs = (rec >> 8) & 3, qp = (int)((rec >> 12) & 0xff) - 64, slice = rec >> 20;
   const bool p_nf = NF && ((rec >> 10) & 1), q_nf = NF && ((rec >> 11) & 1);
   const int x = DIR == 0 ? x0 + 8 * (u % 9) : x0 - 4 + 4 * (u % 18);
   const int y = DIR == 0 ? y0 - 4 + 4 * (u / 9) : y0 + 8 * (u / 18);
   // offsets come from the Q side's slice (TComLoopFilter.cpp:565-566); slice 0's were fetched at kernel entry
-  const SliceLf sl = slice == 0 ? s0 : slice_lf(P.slices + slice);
+  const SliceLf sl = slice == 0 ? P.s0 : slice_lf(P.slices + slice);
   const int tc_off = sl.tc_off, beta_off = sl.beta_off;
   int16_t* base = &L.y[y - (y0 - 4)][x - (x0 - 8)];
   // the unit as line pairs (filter_core.h): a = lines 0|1, b = lines 2|3, index = position across the edge
@@ -189,7 +225,7 @@ __device__ inline void edge_apply(const PicDev& P, FilterLds& L, int x0, int y0,
       a[k] = v.x; b[k] = v.y;
     }
   }
-  filter_luma_unit(a, b, bs, qp, tc_off, beta_off, P.bd[0], p_nf, q_nf);
+  filter_luma_unit(a, b, bs, qp, tc_off, beta_off, P.bd(0), p_nf, q_nf);
   if (DIR == 0) {
     uint32_t r[4][4];
     pairs_to_rows(a, r[0], r[1]);
@@ -205,10 +241,10 @@ __device__ inline void edge_apply(const PicDev& P, FilterLds& L, int x0, int y0,
   }
   // chroma: Bs 2 only, edges on the 8-sample chroma grid (TComLoopFilter.cpp:225-229, 684-692, 727)
   if (bs == 2 && ((DIR == 0 ? x : y) & 15) == 0 && !P.mono) {      // (4:0:0: the chroma planes are left alone)
-    const int maxc = (1 << P.bd[1]) - 1;
+    const int maxc = (1 << P.bd(1)) - 1;
 #pragma unroll
     for (int comp = 1; comp < 3; comp++) {
-      const int tc = chroma_tc(qp, comp == 1 ? sl.cb_off : sl.cr_off, tc_off, P.bd[comp]);
+      const int tc = chroma_tc(qp, comp == 1 ? sl.cb_off : sl.cr_off, tc_off, P.bd(comp));
       int16_t* cb = &L.c[comp - 1][(y >> 1) - ((y0 >> 1) - 2)][(x >> 1) - ((x0 >> 1) - 8)];
 #pragma unroll
       for (int i = 0; i < 2; i++) {
@@ -234,84 +270,92 @@ __global__ void __launch_bounds__(256) k_filter_fused(const PicDev* __restrict__
   // L2 instead of being fetched from memory once per neighbour (measured: 0.9 GB of reads per batch without)
   int slot, lb;
   if (!xcd_remap(blockIdx.x, b.n, tiles, slot, lb)) return;
-  const PicDev& P = pics[b.pic[slot]];
+  const FPic P = pic_state(pics + b.pic[slot]);
+  __builtin_amdgcn_sched_barrier(0);
   const int x0 = (lb % tiles_x) * kTW, y0 = (lb / tiles_x) * kTH;
   const int t = threadIdx.x;
+  const int l2 = P.log2ctu, p0 = P.pitch[0], p1 = P.pitch[1];
+  // ---- 1. everything the thread reads from memory is requested here, back to back: its edge records with the slice of their Q side's
+  // CTU, the tile and its halo before any filtering (pictures carry margins: every address is inside the allocation), the parameters
+  // of its SAO groups.  The edge units are classified while the tile flies, then the copy is written.
   // edge units of this thread: vertical edges x0, x0+8 .. x0+64 over the rows [y0-4, y0+68) (9 edges x 18 units), horizontal
-  // edges y0 .. y0+64 over the columns [x0-4, x0+68)
+  // edges y0 .. y0+64 over the columns [x0-4, x0+68); cells and CTUs are counted from those of (x0-8, y0-8)
   const int vx = x0 + 8 * (t % 9), vy = y0 - 4 + 4 * (t / 9), hx = x0 - 4 + 4 * (t % 18), hy = y0 + 8 * (t / 18);
-  const uint32_t ev = edge_fetch<0>(P, vx, vy, t < kUnits), eh = edge_fetch<1>(P, hx, hy, t < kUnits);
-  const SliceLf s0 = slice_lf(P.slices);
-  // SAO groups of this thread (8 samples each): two of luma (64 rows x 8 groups), one of Cb or Cr (32 rows x 4 groups each);
-  // their parameters are requested now as well
-  int lx[2], ly[2];
-  SaoPrm sl[2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int g = t + 256 * k;
-    lx[k] = x0 + (g & 7) * 8; ly[k] = y0 + (g >> 3);
-    sl[k] = sao_fetch(P, 0, lx[k], ly[k]);
-  }
-  // (neighbouring lanes hold Cb and Cr of the same group: the plane wants them pair by pair, hmgpu_dev.h "chroma planes")
-  const int ccomp = 1 + (t & 1), ccx = (x0 >> 1) + ((t >> 1) & 3) * 8, ccy = (y0 >> 1) + (t >> 3);
-  const SaoPrm sc = sao_fetch(P, ccomp, ccx, ccy);
-  // ---- 1. the tile and its halo, before any filtering (pictures carry margins: every address is inside the allocation):
-  // all loads of the thread are issued, the edge units are classified while they fly, then the copy is written
-  constexpr int VPR = kYC / 8, VPC = kCC / 8, NY = (kYH * VPR + 255) / 256, NC = (2 * kCH * VPC + 255) / 256;
-  u32x4 ty[NY], tc[NC];
-  {
-    const int16_t* src = P.rec[0] + (ptrdiff_t)(y0 - 4) * P.pitch[0] + (x0 - 8);
-#pragma unroll
-    for (int k = 0; k < NY; k++) {
-      const int i = t + 256 * k, r = i / VPR, v = i % VPR;
-      if (i < kYH * VPR) ty[k] = ldg4(src + (ptrdiff_t)r * P.pitch[0] + 8 * v);
-    }
-#pragma unroll
-    for (int k = 0; k < NC; k++) {
-      // a vector = the (Cb, Cr) pairs of four positions of a row of the copy
-      const int i = t + 256 * k, r = i / (2 * VPC), v = i % (2 * VPC);
-      if (i < 2 * kCH * VPC) tc[k] = ldg4(P.rec[1] + (ptrdiff_t)((y0 >> 1) - 2 + r) * P.pitch[1] + kCStep * (((x0 >> 1) - 8) + 4 * v));
-    }
-  }
+  const bool vin = t < kUnits && vy >= 0 && vx < P.width && vy < P.height, hin = t < kUnits && hx >= 0 && hx < P.width && hy < P.height;
+  const int ecw = P.grid_w >> 1, ex0 = (x0 >> 3) - 1, ey0 = (y0 >> 3) - 1;
+  const Span se(reinterpret_cast<const char*>(P.edges) + ((ptrdiff_t)ey0 * ecw + ex0) * (ptrdiff_t)sizeof(EdgeRec), (uint32_t)((9 * ecw + 10) * (int)sizeof(EdgeRec)));
+  const uint32_t ev = se.load_u16(se.at(vin, (uint32_t)((((vy >> 3) - ey0) * ecw + (vx >> 3) - ex0) * 8 + ((vy >> 2) & 1) * 2)));
+  const uint32_t eh = se.load_u16(se.at(hin, (uint32_t)((((hy >> 3) - ey0) * ecw + (hx >> 3) - ex0) * 8 + 4 + ((hx >> 2) & 1) * 2)));
+  // (P.slice_idx == nullptr: an empty span, every answer is slice 0)
+  const int sx0 = (x0 - 8) >> l2, sy0 = (y0 - 8) >> l2;
+  const Span ss(reinterpret_cast<const char*>(P.slice_idx) + ((ptrdiff_t)sy0 * P.ctus_w + sx0) * 2,
+                P.slice_idx ? (uint32_t)(((((y0 + 64) >> l2) - sy0) * P.ctus_w + ((x0 + 64) >> l2) - sx0 + 1) * 2) : 0u);
+  uint32_t sv = ss.load_u16(ss.at(vin, (uint32_t)((((vy >> l2) - sy0) * P.ctus_w + (vx >> l2) - sx0) * 2)));
+  uint32_t sh = ss.load_u16(ss.at(hin, (uint32_t)((((hy >> l2) - sy0) * P.ctus_w + (hx >> l2) - sx0) * 2)));
+  // the copies: luma 72 rows of 10 vectors (8 samples), chroma 36 rows of 12 vectors (the (Cb, Cr) pairs of four positions), dealt to the
+  // threads in turn; the last round of each is short
+  constexpr int VPR = kYC / 8, VPC = 2 * kCC / 8;
+  static_assert(kYH * VPR > 512 && kYH * VPR <= 768 && kCH * VPC > 256 && kCH * VPC <= 512, "three rounds of luma vectors, two of chroma");
+  const int yr0 = t / VPR, yv0 = t % VPR, yr1 = (t + 256) / VPR, yv1 = (t + 256) % VPR, yr2 = (t + 512) / VPR, yv2 = (t + 512) % VPR;
+  const int ur0 = t / VPC, uv0 = t % VPC, ur1 = (t + 256) / VPC, uv1 = (t + 256) % VPC;
+  const bool yin2 = t + 512 < kYH * VPR, uin1 = t + 256 < kCH * VPC;
+  const Span sy(P.rec[0] + ((ptrdiff_t)(y0 - 4) * p0 + (x0 - 8)), (uint32_t)(((kYH - 1) * p0 + kYC) * 2));
+  const Span sc(P.rec[1] + ((ptrdiff_t)((y0 >> 1) - 2) * p1 + kCStep * ((x0 >> 1) - 8)), (uint32_t)(((kCH - 1) * p1 + kCStep * kCC) * 2));
+  const u32x4 ty0 = sy.load4((uint32_t)((yr0 * p0 + 8 * yv0) * 2));
+  const u32x4 ty1 = sy.load4((uint32_t)((yr1 * p0 + 8 * yv1) * 2));
+  const u32x4 ty2 = sy.load4(sy.at(yin2, (uint32_t)((yr2 * p0 + 8 * yv2) * 2)));
+  const u32x4 tc0 = sc.load4((uint32_t)((ur0 * p1 + 8 * uv0) * 2));
+  const u32x4 tc1 = sc.load4(sc.at(uin1, (uint32_t)((ur1 * p1 + 8 * uv1) * 2)));
+  // SAO groups of this thread (8 samples each): two of luma (64 rows x 8 groups), one of Cb or Cr (32 rows x 4 groups each; neighbouring
+  // lanes hold Cb and Cr of the same group: the plane wants them pair by pair, hmgpu_dev.h "chroma planes")
+  const int gx = (t & 7) * 8, gy = t >> 3;                          // luma group k at (gx, gy + 32 k) of the tile
+  const int lx = x0 + gx, ly[2] = {y0 + gy, y0 + gy + 32};
+  const int ccomp = 1 + (t & 1), ccx = (x0 >> 1) + ((t >> 1) & 3) * 8, ccy = (y0 >> 1) + gy;
+  const bool lin[2] = {lx < P.width && ly[0] < P.height, lx < P.width && ly[1] < P.height}, cin = ccx < (P.width >> 1) && ccy < (P.height >> 1);
+  const int n64 = 63 >> l2;                                         // the tile's CTUs: (n64 + 1) x (n64 + 1), counted from that of (x0, y0)
+  const Span sp(P.saoprm + ((ptrdiff_t)(y0 >> l2) * P.ctus_w + (x0 >> l2)) * 3, (uint32_t)(((n64 * P.ctus_w + n64) * 3 + 3) * (int)sizeof(SaoDev)));
+  const uint32_t prow = (uint32_t)(3 * (int)sizeof(SaoDev)) * (uint32_t)P.ctus_w;
+  const SaoPrm sl0 = sao_fetch(sp, sp.at(lin[0], (uint32_t)(gy >> l2) * prow + (uint32_t)((gx >> l2) * 3 * (int)sizeof(SaoDev))));
+  const SaoPrm sl1 = sao_fetch(sp, sp.at(lin[1], (uint32_t)((gy + 32) >> l2) * prow + (uint32_t)((gx >> l2) * 3 * (int)sizeof(SaoDev))));
+  const SaoPrm sc0 = sao_fetch(sp, sp.at(cin, (uint32_t)((2 * gy) >> l2) * prow + (uint32_t)(((((t >> 1) & 3) * 16) >> l2) * 3 + ccomp) * (uint32_t)sizeof(SaoDev)));
+  // (a slice index is only looked at for units that filter: left alone, the compiler moves its request into that branch, behind the
+  // tile's loads, and the classification waits for all of them.  The empty statement takes the two values here, where they are due.)
+  asm volatile("" : "+v"(sv), "+v"(sh));
   if (t < 192) {
-    push_units(L.unit[0], L.units[0], edge_classify<NF>(P, ev, t, vx, vy), t);
-    push_units(L.unit[1], L.units[1], edge_classify<NF>(P, eh, t, hx, hy), t);
+    push_units(L.unit[0], L.units[0], edge_classify<NF>(ev, sv, t), t);
+    push_units(L.unit[1], L.units[1], edge_classify<NF>(eh, sh, t), t);
   }
-#pragma unroll
-  for (int k = 0; k < NY; k++) {
-    const int i = t + 256 * k, r = i / VPR, v = i % VPR;
-    if (i < kYH * VPR) *reinterpret_cast<u32x4*>(&L.y[r][8 * v]) = ty[k];
-  }
-#pragma unroll
-  for (int k = 0; k < NC; k++) {
-    const int i = t + 256 * k, r = i / (2 * VPC), v = i % (2 * VPC);
-    if (i < 2 * kCH * VPC) {
-      // the copies in LDS are one per component: the filters run on them as they did on separate planes
-      *reinterpret_cast<u32x2*>(&L.c[0][r][4 * v]) = u32x2{__builtin_amdgcn_perm(tc[k].y, tc[k].x, 0x05040100u), __builtin_amdgcn_perm(tc[k].w, tc[k].z, 0x05040100u)};
-      *reinterpret_cast<u32x2*>(&L.c[1][r][4 * v]) = u32x2{__builtin_amdgcn_perm(tc[k].y, tc[k].x, 0x07060302u), __builtin_amdgcn_perm(tc[k].w, tc[k].z, 0x07060302u)};
-    }
-  }
+  *reinterpret_cast<u32x4*>(&L.y[yr0][8 * yv0]) = ty0;
+  *reinterpret_cast<u32x4*>(&L.y[yr1][8 * yv1]) = ty1;
+  if (yin2) *reinterpret_cast<u32x4*>(&L.y[yr2][8 * yv2]) = ty2;
+  // the copies in LDS are one per component: the filters run on them as they did on separate planes
+  auto put_chroma = [&](int r, int v, const u32x4 c) {
+    *reinterpret_cast<u32x2*>(&L.c[0][r][4 * v]) = u32x2{__builtin_amdgcn_perm(c.y, c.x, 0x05040100u), __builtin_amdgcn_perm(c.w, c.z, 0x05040100u)};
+    *reinterpret_cast<u32x2*>(&L.c[1][r][4 * v]) = u32x2{__builtin_amdgcn_perm(c.y, c.x, 0x07060302u), __builtin_amdgcn_perm(c.w, c.z, 0x07060302u)};
+  };
+  put_chroma(ur0, uv0, tc0);
+  if (uin1) put_chroma(ur1, uv1, tc1);
   __syncthreads();
   // ---- 2. vertical edges
-  edge_apply<0, NF>(P, L, x0, y0, pop_unit(L.unit[0], L.units[0], t), s0);
+  edge_apply<0, NF>(P, L, x0, y0, pop_unit(L.unit[0], L.units[0], t));
   __syncthreads();
   // ---- 3. horizontal edges
-  edge_apply<1, NF>(P, L, x0, y0, pop_unit(L.unit[1], L.units[1], t), s0);
+  edge_apply<1, NF>(P, L, x0, y0, pop_unit(L.unit[1], L.units[1], t));
   __syncthreads();
-  // ---- 4. SAO of the tile from the deblocked copy
-#pragma unroll
-  for (int k = 0; k < 2; k++)
-    if (lx[k] < P.width && ly[k] < P.height)
-      stg4(P.sao[0] + (size_t)ly[k] * P.pitch[0] + lx[k], sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx[k], ly[k], sl[k]));
-  if (ccx < (P.width >> 1) && ccy < (P.height >> 1)) {
-    const u32x4 own = sao_group<kCW, NF>(P, ccomp, L.c[ccomp - 1], (x0 >> 1) - 8, (y0 >> 1) - 2, ccx, ccy, sc);
+  // ---- 4. SAO of the tile from the deblocked copy, stored relative to the tile's first sample in the SAO planes
+  const Span oy(P.sao[0] + ((ptrdiff_t)y0 * p0 + x0), (uint32_t)(((kTH - 1) * p0 + kTW) * 2));
+  if (lin[0]) oy.store4((uint32_t)((gy * p0 + gx) * 2), sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[0], sl0));
+  if (lin[1]) oy.store4((uint32_t)(((gy + 32) * p0 + gx) * 2), sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[1], sl1));
+  if (cin) {
+    const u32x4 own = sao_group<kCW, NF>(P, ccomp, L.c[ccomp - 1], (x0 >> 1) - 8, (y0 >> 1) - 2, ccx, ccy, sc0);
     // the even lane (Cb) writes positions 0..3 of the group, the odd lane (Cr) positions 4..7: each hands the other the half it does not write
     const bool odd = t & 1;
     const uint32_t r0 = (uint32_t)__shfl_xor((int)(odd ? own.x : own.z), 1, 64), r1 = (uint32_t)__shfl_xor((int)(odd ? own.y : own.w), 1, 64);
     const uint32_t cb0 = odd ? r0 : own.x, cb1 = odd ? r1 : own.y, cr0 = odd ? own.z : r0, cr1 = odd ? own.w : r1;
     const u32x4 o = {__builtin_amdgcn_perm(cr0, cb0, 0x05040100u), __builtin_amdgcn_perm(cr0, cb0, 0x07060302u),
                      __builtin_amdgcn_perm(cr1, cb1, 0x05040100u), __builtin_amdgcn_perm(cr1, cb1, 0x07060302u)};
-    stg4(P.sao[1] + (size_t)ccy * P.pitch[1] + kCStep * (ccx + (odd ? 4 : 0)), o);
+    const Span oc(P.sao[1] + ((ptrdiff_t)(y0 >> 1) * p1 + kCStep * (x0 >> 1)), (uint32_t)(((kTH / 2 - 1) * p1 + kCStep * kTW / 2) * 2));
+    oc.store4((uint32_t)((gy * p1 + kCStep * (((t >> 1) & 3) * 8 + (odd ? 4 : 0))) * 2), o);
   }
 }
 
