@@ -689,9 +689,10 @@ hmgpu_status hmgpu_replay_batch(hmgpu_ctx* ctx, const hmgpu_pic* pics, int32_t n
  * forces one lane). */
 hmgpu_status hmgpu_set_streams(hmgpu_ctx* ctx, int32_t n);
 
-#define HMGPU_NUM_KERNELS 12
+#define HMGPU_NUM_KERNELS 13
 typedef struct hmgpu_stats {
-  double   kernel_ms[HMGPU_NUM_KERNELS];      /* accumulated device time per kernel class since the last reset */
+  double   kernel_ms[HMGPU_NUM_KERNELS];      /* accumulated device time per kernel class since the last reset ("mc_cells": the launches of
+                                               * the cells kernels, whose time "mc_luma" / "mc_chroma" include as well) */
   uint64_t kernel_launches[HMGPU_NUM_KERNELS];
   uint64_t intra_partitions;                  /* 4x4 partitions of intra CUs seen */
   uint64_t inter_partitions;

@@ -15,7 +15,7 @@ MODE_INTER, MODE_INTRA = 0, 1
 SIZE_2Nx2N, SIZE_2NxN, SIZE_Nx2N, SIZE_NxN, SIZE_2NxnU, SIZE_2NxnD, SIZE_nLx2N, SIZE_nRx2N, SIZE_NONE = range(9)
 SAO_OFF, SAO_NEW, SAO_MERGE = 0, 1, 2
 SAO_EO_0, SAO_EO_90, SAO_EO_135, SAO_EO_45, SAO_BO = range(5)
-NUM_KERNELS = 12
+NUM_KERNELS = 13
 
 STAGE_DEBLOCK_VER, STAGE_DEBLOCK_HOR, STAGE_SAO, STAGE_RECON = 1, 2, 4, 8
 

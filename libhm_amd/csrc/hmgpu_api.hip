@@ -27,9 +27,9 @@ using namespace hmgpu;
 
 namespace {
 
-enum { K_PREP = 0, K_MC_LUMA, K_MC_CHROMA, K_ITX, K_DBK_VER, K_DBK_HOR, K_SAO, K_EXTEND, K_H2D, K_INTRA, K_FILTER, K_UNPACK };
+enum { K_PREP = 0, K_MC_LUMA, K_MC_CHROMA, K_ITX, K_DBK_VER, K_DBK_HOR, K_SAO, K_EXTEND, K_H2D, K_INTRA, K_FILTER, K_UNPACK, K_MC_CELLS };
 const char* const kKernelNames[HMGPU_NUM_KERNELS] = {"prep", "mc_luma", "mc_chroma", "itx", "deblock_ver", "deblock_hor", "sao",
-                                                     "extend_border", "h2d_stage", "intra", "filter_fused", "unpack"};
+                                                     "extend_border", "h2d_stage", "intra", "filter_fused", "unpack", "mc_cells"};    // mc_cells: the launches of k_mc_cells.hip, inside the mc_luma / mc_chroma spans
 
 struct SliceCall { int first_ctu, num_ctus, slice_idx; bool intra, wp, cells, bi, islice; };   // intra: the range holds intra CUs the device reconstructs; islice: mostly intra CUs;
                                                                                     // cells: it holds PUs that cut an 8x8 luma tile (k_mc_cells.hip); bi: B slices
@@ -518,7 +518,7 @@ hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp
     ma.rtw = c->grid_w / 2;
     for (int i = 0; i < b.n; i++) { ma.dst[i] = c->pics[b.pic[i]].dev.rec[0]; ma.resid[i] = c->pics[b.pic[i]].dev.resid[0]; }
     launch_mc_luma(ma, max_ctus, any_wp, any_bi, c->stream);
-    if (any_cells) launch_mc_luma_cells(c->d_pics, c->d_finals, b, max_ctus, c->seq.log2_ctu_size, any_wp, c->stream);
+    if (any_cells) { ProfScope pc(c, K_MC_CELLS); launch_mc_luma_cells(c->d_pics, c->d_finals, b, max_ctus, c->seq.log2_ctu_size, any_wp, c->stream); }
   }
   if (c->fmt != 1) {
     ProfScope ps(c, K_MC_CHROMA);
@@ -534,7 +534,7 @@ hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp
       ma.dst[i] = d.rec[1]; ma.dst2[i] = d.rec[2]; ma.resid[i] = d.resid[1]; ma.resid2[i] = d.resid[2];
     }
     launch_mc_chroma(ma, max_ctus, any_wp, any_bi, c->stream);
-    if (any_cells) launch_mc_chroma_cells(c->d_pics, c->d_finals, b, max_ctus, c->seq.log2_ctu_size, any_wp, c->stream);
+    if (any_cells) { ProfScope pc(c, K_MC_CELLS); launch_mc_chroma_cells(c->d_pics, c->d_finals, b, max_ctus, c->seq.log2_ctu_size, any_wp, c->stream); }
   }
   // intra CUs predict from finished neighbours (inter ones included): after motion compensation and the inter residuals
   if (any_intra) {

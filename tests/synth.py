@@ -32,7 +32,8 @@ class SynthPicture:
 def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, num_refs=1, slice_qp_range=(22, 37),
                  cbf_prob=0.5, sao=True, mode_probs=(0.1, 0.3, 0.3, 0.2, 0.1), ref_handles=None, mv_range=64,
                  coef_dist="typical", tr_split_prob=0.35, intra_modes=True, num_slices=1, lf_across_slices=1,
-                 chroma_format=1, log2_ctu=6, bit_depth_chroma=None, ccp_prob=0.0, mv_coherence=0.0, l1_refs=1):
+                 chroma_format=1, log2_ctu=6, bit_depth_chroma=None, ccp_prob=0.0, mv_coherence=0.0, l1_refs=1,
+                 part_probs=None, min_cu_log2=3, intra_nxn_prob=0.0, tr_depth_max=1):
     """Returns a SynthPicture with .seq, .slice (abi.SliceParams), .meta (MetaHolder), .coeffs (CoeffHolder),
     .sao_raw [num_ctus,3,35], .pp, .meta_np.  ref_handles: device picture handles of list-0 / list-1 references.
     coef_dist: "typical" (see above), "stress" (every level of a coded TU uniform over the full int16 range) or
@@ -55,8 +56,20 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
         it (as that PU ends up, so motion spreads over areas), each vector component moved by -5 .. 5 quarter samples: the |difference| >= 4
         test of xGetBoundaryStrengthSingle then falls both ways
       * l1_refs (with bi): number of list-1 references, 1 or 2.  ref_handles=([0, 1], [1, 0]) with num_refs=2, l1_refs=2 gives PUs the same
-        two pictures in swapped lists and PUs whose two vectors point into one picture -- the "crossed" and p0 == p1 branches"""
+        two pictures in swapped lists and PUs whose two vectors point into one picture -- the "crossed" and p0 == p1 branches
+    The rest of HM's CU syntax; these draw from a third generator, and with all four at their defaults nothing changes:
+      * part_probs = (p 2Nx2N, p 2NxN, p Nx2N, p NxN) for the inter CUs of CTU modes 0-3 (mode 4 stays AMP): motion, reference indices
+        and the bi-prediction kind per PU, on all partitions of the PU; 8x4 / 4x8 PUs take one list only; inter NxN only in CUs of the
+        minimum size when that is above 8 (elsewhere 2Nx2N)
+      * min_cu_log2 3 / 4: with 4 the "64x8x8" CTU mode gives 16x16 CUs (width and height multiples of 16)
+      * intra_nxn_prob: share of the intra CUs of the minimum size that are SIZE_NxN: tr_idx >= 1, a luma mode per PU, the chroma mode per
+        CU (4:4:4: per PU)
+      * tr_depth_max 1 .. 3: transform trees drawn node by node with tr_split_prob (_transform_trees); any of the four options switches
+        to these trees.  Only they follow rqt_root_cbf: the default pictures, pinned byte for byte, keep tr_idx 1 in inter CUs without any
+        coded block, where HM's parser leaves 0 -- the one rule of check_parser_invariants() that default pictures break"""
     assert chroma_format in (0, 1, 2, 3) and log2_ctu in (4, 5, 6) and l1_refs in (1, 2)
+    assert min_cu_log2 in (3, 4) and tr_depth_max in (1, 2, 3) and (min_cu_log2 == 3 or (width % 16 == 0 and height % 16 == 0))
+    shapes = part_probs is not None or min_cu_log2 != 3 or intra_nxn_prob > 0 or tr_depth_max > 1
     fmt = 1 if chroma_format == 0 else chroma_format                  # 4:0:0 keeps the geometry of 4:2:0
     csx, csy = (0 if fmt == 3 else 1), (1 if fmt == 1 else 0)
     bdc = bit_depth if bit_depth_chroma is None else bit_depth_chroma
@@ -78,7 +91,7 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
         mode[partial] = 3                                          # only 8x8 CUs tile a picture that is not a multiple of 16
     else:
         mode[partial] = np.where(rng.rand(int(partial.sum())) < 0.6, 2, 3)
-    cu_log2 = np.minimum(np.array([6, 5, 4, 3, 5])[mode], log2_ctu)  # per CTU
+    cu_log2 = np.minimum(np.array([6, 5, 4, min_cu_log2, 5])[mode], log2_ctu)  # per CTU
     depth = (log2_ctu - cu_log2)[:, None] * np.ones((1, parts), dtype=np.int64)
     cu_parts = (1 << (2 * (cu_log2 - 2)))[:, None]                # partitions per CU
     z = np.arange(parts)[None, :]
@@ -110,25 +123,55 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     intra &= ~is_amp                                               # AMP is inter only
     pred_mode = intra.astype(np.int64)
 
+    # ---- the CU shapes beyond 2Nx2N / AMP (part_probs, min_cu_log2, intra_nxn_prob, tr_depth_max): everything they draw comes from a
+    # third generator; a CU then has four PU slots, the first two filled by the pinned generators as before
+    rng3 = np.random.RandomState(seed ^ 0x5A9E5)
+    slots = 4 if shapes else 2
+    small_pu = np.zeros((n, parts), dtype=bool)                    # partitions of 8x4 / 4x8 PUs: one list only (8.5.3.2.2)
+    if shapes:
+        at_min = (cu_log2 == min(min_cu_log2, log2_ctu))[:, None]
+        ps = np.take_along_axis(rng3.choice(4, size=(n, n_cu_max), p=part_probs if part_probs is not None else (1, 0, 0, 0)), cu_idx, axis=1)
+        ps = np.where((ps == abi.SIZE_NxN) & ~(at_min & (min_cu_log2 > 3)), abi.SIZE_2Nx2N, ps)      # inter NxN: minimum CUs above 8x8 only
+        nxn_intra = np.take_along_axis(rng3.rand(n, n_cu_max) < intra_nxn_prob, cu_idx, axis=1) & at_min
+        ps = np.where(intra, np.where(nxn_intra, abi.SIZE_NxN, abi.SIZE_2Nx2N), ps)
+        part_size = np.where(is_amp, part_size, ps)
+        cu_w = (1 << (cu_log2 - 2))[:, None]                       # CU width in partitions
+        hx = ((zx[None, :] % cu_w) >= cu_w // 2).astype(np.int64)
+        hy = ((zy[None, :] % cu_w) >= cu_w // 2).astype(np.int64)
+        pu_in_cu = np.where(part_size == abi.SIZE_2NxN, hy, np.where(part_size == abi.SIZE_Nx2N, hx, np.where(part_size == abi.SIZE_NxN, 2 * hy + hx, pu_in_cu)))
+        pu_idx = cu_idx * 4 + pu_in_cu
+        small_pu = (cu_log2 == 3)[:, None] & ((part_size == abi.SIZE_2NxN) | (part_size == abi.SIZE_Nx2N))
+
+    def widen(a, extra):
+        """per-PU draws [n, 2 per CU, ...] -> [n, 4 per CU, ...]: slots 2 and 3 from extra()"""
+        if slots == 2:
+            return a
+        a = a.reshape((n, n_cu_max, 2) + a.shape[2:])
+        return np.concatenate([a, extra().reshape(a.shape)], axis=2).reshape((n, 4 * n_cu_max) + a.shape[3:])
+
     # ---- motion per PU
     def draw_mv():
         mvi = rng.randint(-mv_range, mv_range + 1, size=(n, n_pu_max, 2))
         mvf = rng.randint(0, 4, size=(n, n_pu_max, 2))
         return mvi * 4 + mvf
-    mv0_pu = draw_mv()
-    mv1_pu = draw_mv()
+    def draw_mv3():
+        return rng3.randint(-mv_range, mv_range + 1, size=(n, n_pu_max, 2)) * 4 + rng3.randint(0, 4, size=(n, n_pu_max, 2))
+    mv0_pu = widen(draw_mv(), draw_mv3)
+    mv1_pu = widen(draw_mv(), draw_mv3)
     idx3 = np.repeat(pu_idx[:, :, None], 2, axis=2)
     mv0 = np.take_along_axis(mv0_pu, idx3, axis=1)
     mv1 = np.take_along_axis(mv1_pu, idx3, axis=1)
     ref_idx0 = np.zeros((n, parts), dtype=np.int64)
     if num_refs > 1:
-        ref_pu = rng.randint(0, num_refs, size=(n, n_pu_max))
+        ref_pu = widen(rng.randint(0, num_refs, size=(n, n_pu_max)), lambda: rng3.randint(0, num_refs, size=(n, n_pu_max)))
         ref_idx0 = np.take_along_axis(ref_pu, pu_idx, axis=1)
     ref_idx1 = np.full((n, parts), -1, dtype=np.int64)
     if bi:
         # per PU: 0 = L0 only, 1 = L1 only, 2 = both   (8x4 / 4x8 PUs do not exist here, so bi is legal everywhere)
-        kind_pu = rng.choice(3, size=(n, n_pu_max), p=(0.2, 0.1, 0.7))
+        kind_pu = widen(rng.choice(3, size=(n, n_pu_max), p=(0.2, 0.1, 0.7)), lambda: rng3.choice(3, size=(n, n_pu_max), p=(0.2, 0.1, 0.7)))
         kind = np.take_along_axis(kind_pu, pu_idx, axis=1)
+        if shapes:
+            kind = np.where(small_pu & (kind == 2), np.take_along_axis(rng3.randint(0, 2, size=(n, 4 * n_cu_max)), pu_idx, axis=1), kind)
         ref_idx1 = np.where(kind >= 1, 0, -1)
         ref_idx0 = np.where(kind == 1, -1, ref_idx0)
     ref_idx0 = np.where(intra, -1, ref_idx0)
@@ -138,11 +181,11 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
 
     rng2 = np.random.RandomState(seed ^ 0x5EED2)                 # the later options: never the first generator, whose order is pinned
     if bi and l1_refs > 1:
-        ref1_pu = rng2.randint(0, l1_refs, size=(n, n_pu_max))
+        ref1_pu = widen(rng2.randint(0, l1_refs, size=(n, n_pu_max)), lambda: rng3.randint(0, l1_refs, size=(n, n_pu_max)))
         ref_idx1 = np.where(ref_idx1 >= 0, np.take_along_axis(ref1_pu, pu_idx, axis=1), -1)
     if mv_coherence > 0:
         # PUs in decoding order (CTU by CTU, z order inside): the PU left of / above a PU's first partition has had its turn
-        key = (np.arange(n)[:, None] * n_pu_max + pu_idx)[inside & ~intra]
+        key = (np.arange(n)[:, None] * (slots * n_cu_max) + pu_idx)[inside & ~intra]
         _, first = np.unique(key, return_index=True)
         a_all, z_all = np.nonzero(inside & ~intra)
         order = np.argsort(first, kind="stable")
@@ -158,7 +201,7 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
                 continue
             na = (ny // ctu) * cw + nx // ctu
             nz = np.nonzero((zx == (nx % ctu) // 4) & (zy == (ny % ctu) // 4))[0][0]
-            if intra[na, nz]:
+            if intra[na, nz] or (small_pu[a, zf] and ref_idx0[na, nz] >= 0 and ref_idx1[na, nz] >= 0):
                 continue
             mine = (pu_idx[a] == pu_idx[a, zf]) & inside[a] & ~intra[a]
             ref_idx0[a, mine], ref_idx1[a, mine] = ref_idx0[na, nz], ref_idx1[na, nz]
@@ -202,11 +245,21 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
             sub = coded & np.where(lower, kind != 1, kind != 2)
             bits = bits | (sub.astype(np.int64) << (tr_idx + 1))
         cbf.append(bits)
+    if shapes:
+        tr_idx, cbf = _transform_trees(rng3, n, parts, cu_log2, cu_parts, z, tr_split_prob, tr_depth_max, cbf_prob, chroma_format,
+                                       ((cu_log2 == 6) | (mode == 4))[:, None] | (intra & (part_size == abi.SIZE_NxN)), intra)
     # ---- intra prediction modes: one luma mode per CU (2Nx2N), chroma mode from HM's candidate set incl. DM (36)
     luma_mode_cu = rng.randint(0, 35, size=(n, n_cu_max))
     intra_dir_l = np.take_along_axis(luma_mode_cu, cu_idx, axis=1)
     chroma_mode_cu = np.array([0, 1, 10, 26, 34, 36])[rng.randint(0, 6, size=(n, n_cu_max))]
     intra_dir_c = np.take_along_axis(chroma_mode_cu, cu_idx, axis=1)
+    if shapes:                                                      # NxN: a luma mode per PU; the chroma mode per CU, in 4:4:4 per PU
+        nxn = intra & (part_size == abi.SIZE_NxN)
+        slot = cu_idx * 4 + pu_in_cu
+        intra_dir_l = np.where(nxn, np.take_along_axis(rng3.randint(0, 35, size=(n, 4 * n_cu_max)), slot, axis=1), intra_dir_l)
+        if not csx:
+            cm4 = np.array([0, 1, 10, 26, 34, 36])[rng3.randint(0, 6, size=(n, 4 * n_cu_max))]
+            intra_dir_c = np.where(nxn, np.take_along_axis(cm4, slot, axis=1), intra_dir_c)
     qp_ctu = rng.randint(slice_qp_range[0], slice_qp_range[1] + 1, size=n)
     qp = np.repeat(qp_ctu[:, None], parts, axis=1)
 
@@ -347,7 +400,66 @@ def make_picture(width, height, bit_depth=10, seed=1, bi=False, intra_frac=0.0, 
     p.intra = intra & decoded
     p.px, p.py = px, py
     p.pu_idx = pu_idx                     # [num_ctus, parts]: the PU a partition belongs to, numbered inside its CTU
+    p.small_pu = small_pu & decoded & ~intra      # partitions of 8x4 / 4x8 PUs
     return p
+
+
+def _transform_trees(rng3, n, parts, cu_log2, cu_parts, z, split_prob, depth_max, cbf_prob, chroma_format, force, intra):
+    """A transform tree per CU and its flags as HM's parser leaves them (TDecEntropy::xDecodeTransform, TDecSbac::parseQtCbf): a node splits
+    with split_prob while its luma size is above 4 and its depth below depth_max (force: at depth 0 regardless); tr_idx = depth of a
+    partition's leaf; cbf bit d = flag of the depth-d node the partition lies in -- luma: the OR of the node's leaves; chroma: a flag of the
+    node's own, set wherever a child's is and now and then without one (the children are then not coded at all); 4x4 luma leaves share the
+    chroma block of their 8x8 parent, whose bit they repeat at their own depth (4:4:4: chroma follows luma); 4:2:2: the two squares' flags
+    one depth below the block's bit over the halves of its partitions.  An inter CU with no flag set at all has tr_idx 0 (rqt_root_cbf).
+    Returns (tr_idx, [cbf_y, cbf_u, cbf_v])."""
+    fmt = 1 if chroma_format == 0 else chroma_format
+    csx = 0 if fmt == 3 else 1
+
+    def at(a, first):
+        return np.take_along_axis(a, first, axis=1)
+    tr_idx = np.zeros((n, parts), dtype=np.int64)
+    alive = np.ones((n, parts), dtype=bool)
+    for d in range(3):
+        first = z & ~(np.maximum(cu_parts >> (2 * d), 1) - 1)
+        draw = at(rng3.rand(n, parts) < split_prob, first)
+        if d == 0:
+            draw = draw | force
+        alive = alive & draw & ((cu_log2[:, None] - d) > 2) & (d < depth_max)
+        tr_idx = tr_idx + alive
+    leaf_parts = np.maximum(cu_parts >> (2 * tr_idx), 1)
+    cbf = []
+    for comp in range(3):
+        if comp and chroma_format == 0:
+            cbf.append(np.zeros((n, parts), dtype=np.int64))
+            continue
+        share = bool(comp and csx)
+        shared = (leaf_parts == 1) & share
+        tc = tr_idx - shared                                       # depth of the node that owns the block
+        blk = np.where(shared, 4, leaf_parts)
+        leaf = at(rng3.rand(n, parts) < cbf_prob, z & ~(blk - 1))
+        # a chroma node now and then set with nothing coded below it: the shallowest such node on a partition's path
+        alone = np.full((n, parts), 9, dtype=np.int64)
+        for d in range(3):
+            pick = at(rng3.rand(n, parts) < 0.25, z & ~(np.maximum(cu_parts >> (2 * d), 1) - 1)) & (tc > d) & (alone == 9) & bool(comp)
+            alone = np.where(pick, d, alone)
+        leaf = leaf & (alone == 9)
+        cur = np.zeros((n, parts), dtype=bool)
+        bits = np.zeros((n, parts), dtype=np.int64)
+        for d in (3, 2, 1, 0):
+            node_parts = np.maximum(cu_parts >> (2 * d), 1)
+            inner = _group_any(cur, node_parts) | (alone == d)
+            cur = np.where(tc == d, leaf, (tc > d) & inner)
+            bits = bits | (cur.astype(np.int64) << d)
+        bits = bits | np.where(shared, ((bits >> tc) & 1) << tr_idx, 0)
+        if comp and fmt == 2:
+            kind = at(rng3.randint(0, 3, size=(n, parts)), z & ~(blk - 1))     # 0 both squares, 1 the upper one only, 2 the lower one only
+            lower = (z % blk) >= blk // 2
+            sub = (((bits >> tr_idx) & 1) != 0) & np.where(lower, kind != 1, kind != 2)
+            bits = bits | (sub.astype(np.int64) << (tr_idx + 1))
+        cbf.append(bits)
+    empty = ~_group_any((cbf[0] | cbf[1] | cbf[2]) != 0, cu_parts) & ~intra      # no flag anywhere in the CU: nothing to undo but tr_idx
+    tr_idx = np.where(empty, 0, tr_idx)
+    return tr_idx, cbf
 
 
 def intra_sample_mask(p, comp):
@@ -463,3 +575,142 @@ def block_mask(blocks, num_ctus, elems):
             idx = s[:, 2][:, None] + np.arange(sz * sz)[None, :]
             masks[comp][s[:, 1][:, None], idx] = True
     return masks
+
+
+def _group_any(flag, group_parts):
+    """flag [n, parts] ORed over the aligned z-order group of group_parts[a, z] (a power of four) partitions that holds partition z"""
+    n, parts = flag.shape
+    out = np.zeros_like(flag)
+    v = 1
+    while v <= parts:
+        sel = group_parts == v
+        if sel.any():
+            out = np.where(sel, np.repeat(flag.reshape(n, parts // v, v).any(axis=2), v, axis=1), out)
+        v *= 4
+    return out
+
+
+def check_parser_invariants(meta, chroma_format, log2_ctu, slice_types):
+    """What the standard's syntax (7.3.8, 7.4.9, 8.5.3.2.2) and HM's parser (TDecEntropy::xDecodeTransform, TDecSbac::parseQtCbf) guarantee
+    of the per-partition arrays of a picture, whatever the stream; raises AssertionError naming the first rule broken.  meta: dict of
+    [num_ctus, parts] arrays as in SynthPicture.meta_np; slice_types: HMGPU slice type per entry of the slice table (meta["slice_idx"]).
+      1. depth, part_size, pred_mode, qp are uniform over a CU, which is aligned to its size
+      2. motion vectors, reference indices and so the lists in use are uniform over each PU of the part_size geometry (eight shapes);
+         intra CUs use no list; P slices use list 0 only, I slices none; an inter PU uses a list
+      3. no 8x4 / 4x8 PU uses both lists
+      4. AMP in CUs of 16 and more; NxN only in CUs of one size, the smallest in the picture (the minimum CU size), inter NxN only
+         when that is above 8; intra CUs are 2Nx2N or NxN, intra NxN has tr_idx >= 1
+      5. tr_idx is uniform over its leaf, the leaf lies inside the CU and is 4 .. 32 samples; an inter CU with no flag set has no tree: tr_idx 0, whatever its size
+      6. cbf: no bit above tr_idx (4:2:2 chroma: tr_idx + 1); every bit d <= tr_idx is uniform over the depth-d node; bit d + 1 set implies
+         bit d; luma bit d = OR over the node of the leaves' bits; chroma bit d is set wherever a deeper one of the node is; 4x4 luma leaves
+         under subsampled chroma repeat their parent's chroma bit; 4:2:2: the bit below the block's own is uniform over each half of the
+         block and the block's bit is the OR of the halves; 4:0:0 has no chroma flag
+      7. chroma modes of intra partitions are planar, DC, horizontal, vertical, 34 or DM (36), and uniform over a CU unless 4:4:4 NxN"""
+    fmt = 1 if chroma_format == 0 else chroma_format
+    csx = 0 if fmt == 3 else 1
+    g = {k: np.asarray(v).astype(np.int64) for k, v in meta.items() if k in (
+        "depth", "part_size", "pred_mode", "qp", "tr_idx", "cbf_y", "cbf_u", "cbf_v", "mv0", "mv1", "ref_idx0", "ref_idx1", "intra_dir_l", "intra_dir_c")}
+    depth, ps, tr = g["depth"], g["part_size"], g["tr_idx"]
+    n, parts = depth.shape
+    dec = ps != abi.SIZE_NONE
+    z = np.arange(parts)[None, :]
+    zx, zy = _zxy(parts)
+    z_of = np.zeros((1 << (log2_ctu - 2), 1 << (log2_ctu - 2)), dtype=np.int64)
+    z_of[zy, zx] = np.arange(parts)
+
+    def at(a, first):
+        return np.take_along_axis(a, first, axis=1)
+
+    def same(a, first, where, what):
+        bad = where & (at(a, first) != a) if a.ndim == 2 else where & (np.take_along_axis(a, first[:, :, None], axis=1) != a).any(axis=2)
+        assert not bad.any(), "%s: %d partitions, first at CTU %d z %d" % ((what, int(bad.sum())) + tuple(int(v[0]) for v in np.nonzero(bad)))
+    # 1
+    assert (depth[dec] <= log2_ctu - 3).all(), "CU below 8x8"
+    cu_parts = parts >> (2 * depth)
+    cu_first = z & ~(cu_parts - 1)
+    for k in ("depth", "part_size", "pred_mode", "qp"):
+        same(g[k], cu_first, dec, "%s not uniform over the CU" % k)
+    assert not (dec & ~at(dec, cu_first)).any()
+    cu_log2 = log2_ctu - depth
+    intra = dec & (g["pred_mode"] == abi.MODE_INTRA)
+    inter = dec & ~intra
+    # 2: the PU of every partition: its index and the z index of its first partition
+    cu_w = 1 << (cu_log2 - 2)
+    rx, ry = zx[None, :] % cu_w, zy[None, :] % cu_w
+    q, h = cu_w // 4, cu_w // 2
+    zero = np.zeros_like(rx)
+    ox = np.select([ps == abi.SIZE_Nx2N, ps == abi.SIZE_NxN, ps == abi.SIZE_nLx2N, ps == abi.SIZE_nRx2N], [h, h, q, cu_w - q], cu_w)
+    oy = np.select([ps == abi.SIZE_2NxN, ps == abi.SIZE_NxN, ps == abi.SIZE_2NxnU, ps == abi.SIZE_2NxnD], [h, h, q, cu_w - q], cu_w)
+    pux, puy = np.where(rx >= ox, ox, zero), np.where(ry >= oy, oy, zero)      # the PU's origin inside the CU
+    pu_first = z_of[(zy[None, :] - ry + puy), (zx[None, :] - rx + pux)]
+    for k in ("mv0", "mv1", "ref_idx0", "ref_idx1"):
+        same(g[k], pu_first, dec, "%s not uniform over the PU" % k)
+    st = np.asarray(slice_types).reshape(-1)[np.asarray(meta["slice_idx"]).astype(np.int64) if "slice_idx" in meta else np.zeros(n, dtype=np.int64)][:, None]
+    l0, l1 = g["ref_idx0"] >= 0, g["ref_idx1"] >= 0
+    assert not (intra & (l0 | l1)).any(), "an intra CU uses a reference list"
+    assert not (inter & ~(l0 | l1)).any(), "an inter PU uses no list"
+    assert not (dec & l1 & (st != abi.B_SLICE)).any() and not (dec & (l0 | l1) & (st == abi.I_SLICE)).any(), "list not allowed by the slice type"
+    assert not (inter & (st == abi.I_SLICE)).any(), "inter CU in an I slice"
+    # 3
+    assert not (inter & (cu_log2 == 3) & ((ps == abi.SIZE_2NxN) | (ps == abi.SIZE_Nx2N)) & l0 & l1).any(), "bi-predicted 8x4 / 4x8 PU"
+    # 4
+    amp = dec & (ps >= abi.SIZE_2NxnU) & (ps <= abi.SIZE_nRx2N)
+    assert (cu_log2[amp] >= 4).all(), "AMP in an 8x8 CU"
+    nxn = dec & (ps == abi.SIZE_NxN)
+    if nxn.any():
+        sizes = np.unique(cu_log2[nxn])
+        assert sizes.size == 1 and sizes[0] == cu_log2[dec].min(), "NxN outside the minimum CU size"
+        assert not (nxn & inter).any() or sizes[0] > 3, "inter NxN in 8x8 CUs"
+    assert not (intra & (ps != abi.SIZE_2Nx2N) & ~nxn).any(), "intra CU neither 2Nx2N nor NxN"
+    assert (tr[nxn & intra] >= 1).all(), "intra NxN without its transform split"
+    # 5
+    cbfs = [g["cbf_y"], g["cbf_u"], g["cbf_v"]]
+    log2tu = cu_log2 - tr
+    assert (log2tu[dec] >= 2).all(), "transform leaf below 4x4"
+    leaf_parts = np.maximum(cu_parts >> (2 * tr), 1)
+    same(tr, z & ~(leaf_parts - 1), dec, "tr_idx not uniform over its leaf")
+    coded_cu = _group_any(dec & ((cbfs[0] | cbfs[1] | cbfs[2]) != 0), cu_parts)
+    assert not (dec & coded_cu & (log2tu > 5)).any(), "transform leaf above 32x32"
+    assert not (dec & ~coded_cu & ~intra & (tr != 0)).any(), "inter CU without a coded block (rqt_root_cbf 0) with a transform tree"
+    # 6
+    for comp, cbf in enumerate(cbfs):
+        what = "cbf of component %d: " % comp
+        if comp and chroma_format == 0:
+            assert not cbf[dec].any(), what + "set in 4:0:0"
+            continue
+        top = tr + (1 if comp and fmt == 2 else 0)
+        assert not (dec & ((cbf >> (top + 1)) != 0)).any(), what + "bit above the leaf's depth"
+        shared = (leaf_parts == 1) & bool(comp and csx)
+        own = tr - shared                                               # depth of the node that carries the block
+        bit = [(cbf >> d) & 1 for d in range(6)]
+        for d in range(4):
+            node_parts = np.maximum(cu_parts >> (2 * d), 1)
+            here = dec & (d <= own)
+            same(bit[d], z & ~(node_parts - 1), here, what + "bit %d not uniform over its node" % d)
+            below = dec & (d < tr)
+            assert not (below & (bit[d + 1] > bit[d])).any(), what + "bit %d set under a clear bit %d" % (d + 1, d)
+            deeper = _group_any(dec & (d < own) & (bit[d + 1] != 0), node_parts)
+            assert not (dec & (d < own) & deeper & (bit[d] == 0)).any(), what + "node at depth %d clear above a set child" % d
+            if comp == 0:
+                leaves = _group_any(dec & (np.take_along_axis(np.stack(bit, axis=2), tr[:, :, None], axis=2)[:, :, 0] != 0), node_parts)
+                assert not (here & (leaves != (bit[d] != 0))).any(), what + "bit %d is not the OR of its node's leaves" % d
+        if comp and csx:
+            rep = np.take_along_axis(np.stack(bit, axis=2), tr[:, :, None], axis=2)[:, :, 0]
+            par = np.take_along_axis(np.stack(bit, axis=2), np.maximum(tr - 1, 0)[:, :, None], axis=2)[:, :, 0]
+            assert not (dec & shared & (rep != par)).any(), what + "a 4x4 luma leaf does not repeat its parent's bit"
+        if comp and fmt == 2:
+            blk = np.where(shared, 4, leaf_parts)
+            first = z & ~(blk - 1)
+            sub = np.take_along_axis(np.stack(bit, axis=2), (tr + 1)[:, :, None], axis=2)[:, :, 0]
+            up, lo = at(sub, first), at(sub, np.minimum(first + blk // 2, parts - 1))
+            same(sub, np.where((z - first) >= blk // 2, first + blk // 2, first), dec, what + "square flag not uniform over its half")
+            ownbit = np.take_along_axis(np.stack(bit, axis=2), tr[:, :, None], axis=2)[:, :, 0]
+            assert not (dec & (ownbit != (up | lo))).any(), what + "block bit is not the OR of its squares' flags"
+    # 7
+    if "intra_dir_c" in g and chroma_format:
+        ok = np.isin(g["intra_dir_c"], (0, 1, 10, 26, 34, 36))
+        assert ok[intra].all(), "chroma mode outside HM's candidate set"
+        same(g["intra_dir_c"], cu_first, intra & ~(nxn & (fmt == 3)), "chroma mode not uniform over the CU")
+        same(g["intra_dir_c"], pu_first, intra, "chroma mode not uniform over the PU")
+        same(g["intra_dir_l"], pu_first, intra, "luma mode not uniform over the PU")
+        assert (g["intra_dir_l"][intra] <= 34).all()
