@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libhmgpu.so")
-SOURCES = ["k_prep.hip", "k_mc.hip", "k_mc_cells.hip", "k_itx.hip", "k_intra.hip", "k_dbk.hip", "k_sao.hip", "k_filter.hip", "k_out.hip", "k_cfmt.hip", "k_unpack.hip", "k_export.hip", "k_export_scale.hip", "k_motion.hip", "hmgpu_packed.hip", "hmgpu_api.hip"]
+SOURCES = ["k_prep.hip", "k_mc.hip", "k_mc_cells.hip", "k_itx.hip", "k_intra.hip", "k_dbk.hip", "k_sao.hip", "k_filter.hip", "k_out.hip", "k_cfmt.hip", "k_unpack.hip", "k_export.hip", "k_export_scale.hip", "k_motion.hip", "hmgpu_packed.hip", "hmgpu_api.hip", "hmgpu_input.hip", "hmgpu_output.hip", "hmgpu_export.hip"]
 # Code objects for gfx950 with XNACK (retry on page fault) off, the mode these GPUs run in: with the mode known the compiler schedules loads
 # more freely than for "any" (k_mc_luma 0.213 -> 0.208 ms per launch of 16 pictures, measured A/B/A/B on one box).  A device that runs with
 # HSA_XNACK=1 does not load them: HMGPU_XNACK_ANY=1 in the environment of the build gives the mode-agnostic objects back.
@@ -23,7 +23,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "hmgpu_dev.h"), os.path.join(CSRC, "itx_core.h"), os.path.join(CSRC, "mc_core.h"), os.path.join(CSRC, "filter_core.h"), os.path.join(CSRC, "packed_format.h"), os.path.join(os.path.dirname(HERE), "include", "hmgpu.h")]
+    headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [os.path.join(os.path.dirname(HERE), "include", "hmgpu.h")]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     objs, procs = [], []

@@ -1,0 +1,1022 @@
+// hmgpu_export.hip -- device export of the host runtime: the export plans, scale tables and their slots, window tables, destination
+// checks, export_impl behind the four picture export entry points, and the motion / block export (k_export.hip, k_export_scale.hip,
+// k_motion.hip).
+#include "hmgpu_host.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <cstdlib>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <tuple>
+#include <vector>
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ device export (k_export.hip)
+static long long round_half_away(double v) { return v < 0 ? -(long long)std::floor(-v + 0.5) : (long long)std::floor(v + 0.5); }
+
+// H.273 Kr / Kb of the matrix_coefficients codes the export takes (Table 4): false for any other code
+static bool matrix_kr_kb(int matrix, double* kr, double* kb) {
+  switch (matrix) {
+    case 1: *kr = 0.2126; *kb = 0.0722; return true;            // BT.709
+    case 5: case 6: *kr = 0.299; *kb = 0.114; return true;      // BT.601 (625 / 525)
+    case 9: *kr = 0.2627; *kb = 0.0593; return true;            // BT.2020 non-constant luminance
+    default: return false;
+  }
+}
+
+hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, hmgpu_export_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const int fmt = seq->chroma_format, bdY = seq->bit_depth_luma, bdC = seq->bit_depth_chroma;
+  if (fmt < 0 || fmt > 3 || bdY < 8 || bdY > 12 || bdC < 8 || bdC > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
+  if (d->layout < HMGPU_EXPORT_PLANAR || d->layout > HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (d->bytes_per_sample != 1 && d->bytes_per_sample != 2) return HMGPU_EINVAL;
+  if ((d->msb_aligned != 0 && d->msb_aligned != 1) || (d->msb_aligned && d->bytes_per_sample != 2)) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB, mono = fmt == 0;
+  const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
+  const int ob[2] = {d->bit_depth[0] ? d->bit_depth[0] : bdY, rgb ? (d->bit_depth[0] ? d->bit_depth[0] : bdY) : (d->bit_depth[1] ? d->bit_depth[1] : bdC)};
+  const int lo = rgb ? 8 : 1;
+  for (int t = 0; t < (mono && !rgb ? 1 : 2); t++)
+    if (ob[t] < lo || ob[t] > 16 || (d->bytes_per_sample == 1 && ob[t] > 8)) return HMGPU_EINVAL;
+  const int* cr = d->crop;
+  if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+  const int W = seq->width - cr[0] - cr[1], H = seq->height - cr[2] - cr[3];
+  if (W <= 0 || H <= 0) return HMGPU_EINVAL;
+  if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  const int B = d->bytes_per_sample;
+  if (rgb) {
+    if (d->full_range != 0 && d->full_range != 1) return HMGPU_EINVAL;
+    double kr = 0, kb = 0;
+    if (d->matrix == 0) {
+      if (fmt != 3) return HMGPU_EINVAL;                         // identity: 4:4:4 only
+    } else if (!matrix_kr_kb(d->matrix, &kr, &kb)) {
+      return HMGPU_EUNSUPPORTED;
+    }
+    out->planes = 3;
+    for (int k = 0; k < 3; k++) { out->width[k] = W; out->height[k] = H; out->row_bytes[k] = W * B; }
+    const int M = (1 << ob[0]) - 1;
+    out->coef[9] = M;
+    if (d->matrix == 0) { out->coef[10] = 1; return HMGPU_OK; }
+    const double kg = 1.0 - kr - kb;
+    const int yo = d->full_range ? 0 : 16 << (bdY - 8), co = 1 << (bdC - 1);
+    const double ys = d->full_range ? (double)((1 << bdY) - 1) : (double)(219 << (bdY - 8));
+    const double cs = d->full_range ? (double)((1 << bdC) - 1) : (double)(224 << (bdC - 8));
+    const double r[5] = {M / ys, M * 2.0 * (1.0 - kr) / cs, -M * 2.0 * kb * (1.0 - kb) / kg / cs, -M * 2.0 * kr * (1.0 - kr) / kg / cs, M * 2.0 * (1.0 - kb) / cs};
+    const long long maxdy = std::max(yo, (1 << bdY) - 1 - yo), maxdc = co;
+    for (int S = 30; S >= 1; S--) {
+      long long c[5];
+      for (int i = 0; i < 5; i++) c[i] = round_half_away(r[i] * (double)(1LL << S));
+      const long long t = std::llabs(c[0]) * maxdy + (1LL << (S - 1));
+      const long long bound = std::max({t + std::llabs(c[1]) * maxdc, t + (std::llabs(c[2]) + std::llabs(c[3])) * maxdc, t + std::llabs(c[4]) * maxdc});
+      if (bound > INT32_MAX) continue;
+      out->coef[0] = S; out->coef[1] = 1 << (S - 1); out->coef[2] = yo; out->coef[3] = co;
+      for (int i = 0; i < 5; i++) out->coef[4 + i] = (int32_t)c[i];
+      return HMGPU_OK;
+    }
+    return HMGPU_EUNSUPPORTED;
+  }
+  out->planes = mono ? 1 : d->layout == HMGPU_EXPORT_PLANAR ? 3 : 2;
+  out->width[0] = W; out->height[0] = H; out->row_bytes[0] = W * B;
+  for (int k = 1; k < out->planes; k++) {
+    out->width[k] = W >> csx; out->height[k] = H >> csy;
+    out->row_bytes[k] = (d->layout == HMGPU_EXPORT_PLANAR ? 1 : 2) * out->width[k] * B;
+  }
+  return HMGPU_OK;
+}
+
+// true if [p, p + bytes) lies inside one device allocation of `device`
+static bool device_span_ok(const void* p, size_t bytes, int device) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (at.type != hipMemoryTypeDevice || at.device != device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+  return q >= b && q - b + bytes <= size;
+}
+
+// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device
+static hmgpu_status export_stream(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
+  *hs = c->stream;
+  if (!on_stream) return HMGPU_OK;
+  *hs = (hipStream_t)stream;
+  if (*hs) {
+    hipDevice_t dev = -1;
+    if (hipStreamGetDevice(*hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
+    if ((int)dev != c->device) return HMGPU_EINVAL;
+  }
+  for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
+  return HMGPU_OK;
+}
+
+static hmgpu_status export_begin(hmgpu_ctx* c, int32_t on_stream, hipStream_t hs) {
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                 // behind everything enqueued for the picture ...
+    HIP_TRY(c, hipStreamWaitEvent(hs, c->exp_ev[0], 0));                 // ... and behind what is already on the caller's stream
+  }
+  return HMGPU_OK;
+}
+
+// after the export's launch
+static hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs) {
+  HIP_TRY(c, hipGetLastError());
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
+  }
+  for (int i = 0; i < n; i++) touch(c, pics[i]);
+  commit_use(c);
+  return HMGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ scaled export (k_export_scale.hip)
+namespace {
+
+// one resampling table: `in` source samples to `out` outputs (include/hmgpu.h "scaled export")
+struct ScaleTab {
+  int taps = 0;                        // widest row
+  std::vector<int32_t> first, count;
+  std::vector<int16_t> w;              // [out][taps]
+  long long pos = 0, neg = 0;          // the largest sum of the positive / of the magnitudes of the negative weights of a row
+};
+
+double scale_filter(int filter, double x) {
+  x = std::fabs(x);
+  if (filter == HMGPU_SCALE_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  const double a = -0.5;                                         // Keys, as PIL and torch's antialiased bicubic
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+  if (x < 2.0) return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a;
+  return 0.0;
+}
+
+std::shared_ptr<const ScaleTab> build_scale_tab(int in, int out, int filter) {
+  auto t = std::make_shared<ScaleTab>();
+  std::vector<std::vector<int>> rows((size_t)out);
+  t->first.resize((size_t)out);
+  t->count.resize((size_t)out);
+  std::vector<double> w;
+  for (int i = 0; i < out; i++) {
+    int lo = 0;
+    w.clear();
+    if (filter == HMGPU_SCALE_NEAREST) {                         // nearest-exact, the source index exact (no rounding at ties)
+      lo = (int)std::min((2LL * i + 1) * in / (2LL * out), (long long)in - 1);
+      w.push_back(1.0);
+    } else if (filter == HMGPU_SCALE_AREA) {                     // adaptive average pooling
+      lo = (int)((long long)i * in / out);
+      const int hi = (int)(((long long)(i + 1) * in + out - 1) / out);
+      w.assign((size_t)(hi - lo), 1.0 / (hi - lo));
+    } else {                                                     // torch's antialiased interpolation (PIL's weights)
+      const double scale = (double)in / out, support = (filter == HMGPU_SCALE_BILINEAR ? 1.0 : 2.0) * (scale >= 1.0 ? scale : 1.0);
+      const double centre = scale * (i + 0.5), inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+      lo = (int)std::max((long long)(centre - support + 0.5), 0LL);
+      const int hi = (int)std::min((long long)(centre + support + 0.5), (long long)in);
+      double total = 0;
+      for (int j = lo; j < hi; j++) { w.push_back(scale_filter(filter, (j - centre + 0.5) * inv)); total += w.back(); }
+      if (total != 0.0) for (double& v : w) v /= total;
+    }
+    // Q14 by largest remainders: every weight rounded down, then one unit each to the largest remainders (lower index first on a tie)
+    // until the row sums to 16384, so that every weight is within one unit of its exact value
+    std::vector<int>& q = rows[(size_t)i];
+    std::vector<std::pair<double, int>> rem;
+    int sum = 0;
+    for (size_t j = 0; j < w.size(); j++) {
+      const double v = w[j] * 16384.0, f = std::floor(v);
+      q.push_back((int)f);
+      sum += q.back();
+      rem.emplace_back(-(v - f), (int)j);
+    }
+    std::sort(rem.begin(), rem.end());
+    for (int u = 0; u < 16384 - sum; u++) q[(size_t)rem[(size_t)u % rem.size()].second] += 1;
+    size_t b = 0, e = q.size();
+    while (q[b] == 0) b++;
+    while (q[e - 1] == 0) e--;
+    q = std::vector<int>(q.begin() + (ptrdiff_t)b, q.begin() + (ptrdiff_t)e);
+    t->first[(size_t)i] = lo + (int)b;
+    t->count[(size_t)i] = (int)q.size();
+    t->taps = std::max(t->taps, (int)q.size());
+    long long p = 0, n = 0;
+    for (int v : q) (v > 0 ? p : n) += std::llabs(v);
+    t->pos = std::max(t->pos, p);
+    t->neg = std::max(t->neg, n);
+  }
+  t->w.assign((size_t)out * t->taps, 0);
+  for (int i = 0; i < out; i++)
+    for (size_t j = 0; j < rows[(size_t)i].size(); j++) t->w[(size_t)i * t->taps + j] = (int16_t)rows[(size_t)i][j];
+  return t;
+}
+
+// the tables of one call whose windows differ (hmgpu_pictures_export_windows), keyed by (in, out, filter): windows that share them on
+// an axis share a table.  Random windows never repeat, so these stay out of the process-wide map below, which would only be emptied by
+// them.  The tables of the most recent such call are kept (call_tabs_recent), because one export validates the same windows more than
+// once -- the plan for the caller's allocation, the destination check of libhmdec, then the export itself, per run of slots -- and
+// each of these would derive every table again.
+typedef std::map<std::tuple<int, int, int>, std::shared_ptr<const ScaleTab>> CallTabs;
+std::mutex call_tabs_mu;
+CallTabs call_tabs_recent;
+
+std::shared_ptr<const ScaleTab> call_tab(CallTabs& tabs, int in, int out, int filter) {
+  const auto key = std::make_tuple(in, out, filter);
+  auto& t = tabs[key];
+  if (t) return t;
+  {
+    std::lock_guard<std::mutex> g(call_tabs_mu);
+    auto it = call_tabs_recent.find(key);
+    if (it != call_tabs_recent.end()) t = it->second;
+  }
+  if (!t) t = build_scale_tab(in, out, filter);
+  return t;
+}
+
+// after a windows call has been validated: its tables replace the kept ones
+void call_tabs_keep(const CallTabs& tabs) {
+  if (tabs.empty()) return;
+  std::lock_guard<std::mutex> g(call_tabs_mu);
+  call_tabs_recent = tabs;
+}
+
+// process-wide: the tables of recent shapes (a plan or an export of a repeated shape derives nothing)
+std::shared_ptr<const ScaleTab> scale_tab(int in, int out, int filter) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, std::shared_ptr<const ScaleTab>> tabs;
+  const auto key = std::make_tuple(in, out, filter);
+  {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = tabs.find(key);
+    if (it != tabs.end()) return it->second;
+  }
+  auto t = build_scale_tab(in, out, filter);
+  std::lock_guard<std::mutex> g(mu);
+  if (tabs.size() >= 64) tabs.clear();
+  tabs[key] = t;
+  return t;
+}
+
+// everything a scaled export of one shape needs on the host: the plan, per plane class its tables
+struct ScaleShape {
+  int classes = 1;                                              // 2: YUV with chroma
+  int in[2][2] = {}, out[2][2] = {};                             // [class][axis]
+  std::shared_ptr<const ScaleTab> tab[2][2];
+  int depth[2] = {8, 8};                                         // output depth per class
+};
+
+// t = (h + 2^(13-E)) >> (14-E), o = (sum wy t + 2^(13+E)) >> (14+E): no 32-bit sum overflows for samples 0 .. 2^D - 1
+bool scale_sums_fit(const ScaleTab& x, const ScaleTab& y, int D, int E) {
+  const long long V = (1LL << D) - 1, r1 = 1LL << (13 - E), r2 = 1LL << (13 + E);
+  const long long hmax = x.pos * V + r1, hmin = -x.neg * V + r1;
+  if (hmax > INT32_MAX || hmin < INT32_MIN) return false;
+  const long long tmax = hmax >> (14 - E), tmin = hmin >> (14 - E);       // (arithmetic shifts: floor)
+  const long long vmax = y.pos * tmax + y.neg * std::max(-tmin, 0LL) + r2;
+  const long long vmin = -(y.pos * std::max(-tmin, 0LL) + y.neg * tmax) + r2;
+  return vmax <= INT32_MAX && vmin >= INT32_MIN;
+}
+
+hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, hmgpu_export_plan* out,
+                         ScaleShape* shape, CallTabs* call_tabs = nullptr) {
+  if (!seq || !d || !sc || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+  if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+  hmgpu_export_plan base;
+  { const hmgpu_status st = hmgpu_export_plan_for(seq, d, &base); if (st != HMGPU_OK) return st; }
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB, chroma = !rgb && base.planes > 1;
+  const int fmt = seq->chroma_format, csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
+  if (chroma && ((sc->width & ((1 << csx) - 1)) || (sc->height & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  ScaleShape s;
+  s.classes = chroma ? 2 : 1;
+  const int W = base.width[0], H = base.height[0];
+  const int bdY = seq->bit_depth_luma, bdC = seq->bit_depth_chroma;
+  s.depth[0] = d->bit_depth[0] ? d->bit_depth[0] : bdY;
+  s.depth[1] = d->bit_depth[1] ? d->bit_depth[1] : bdC;
+  for (int k = 0; k < s.classes; k++) {
+    const int sx = k ? csx : 0, sy = k ? csy : 0;
+    s.in[k][0] = W >> sx; s.in[k][1] = H >> sy;
+    s.out[k][0] = sc->width >> sx; s.out[k][1] = sc->height >> sy;
+    for (int ax = 0; ax < 2; ax++) {
+      const long long i = s.in[k][ax], o = s.out[k][ax];
+      if (o > 16384 || i > 32 * o || o > 8 * i) return HMGPU_EUNSUPPORTED;
+    }
+  }
+  const int D = rgb ? s.depth[0] : chroma ? std::max(s.depth[0], s.depth[1]) : s.depth[0];
+  const int E = 16 - D;
+  int taps[2] = {0, 0};
+  for (int k = 0; k < s.classes; k++) {
+    for (int ax = 0; ax < 2; ax++) {
+      if (call_tabs) {
+        s.tab[k][ax] = call_tab(*call_tabs, s.in[k][ax], s.out[k][ax], sc->filter);
+      } else {
+        s.tab[k][ax] = scale_tab(s.in[k][ax], s.out[k][ax], sc->filter);
+      }
+      taps[ax] = std::max(taps[ax], s.tab[k][ax]->taps);
+    }
+    if (!scale_sums_fit(*s.tab[k][0], *s.tab[k][1], rgb ? s.depth[0] : s.depth[k], E)) return HMGPU_EUNSUPPORTED;
+  }
+  *out = base;
+  for (int p = 0; p < out->planes; p++) {
+    const int k = rgb || p == 0 ? 0 : 1;
+    const int w = k ? sc->width >> csx : sc->width, h = k ? sc->height >> csy : sc->height;
+    out->row_bytes[p] = out->row_bytes[p] / out->width[p] * w;
+    out->width[p] = w; out->height[p] = h;
+  }
+  out->coef[11] = E; out->coef[12] = taps[0]; out->coef[13] = taps[1];
+  if (shape) *shape = s;
+  return HMGPU_OK;
+}
+
+}  // namespace
+
+hmgpu_status hmgpu_export_scaled_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          hmgpu_export_plan* out) {
+  return scaled_plan(seq, d, sc, out, nullptr);
+}
+
+hmgpu_status hmgpu_export_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, int32_t chroma,
+                                     int32_t axis, int32_t max_taps, int32_t* first, int32_t* count, int16_t* weights) {
+  if (!first || !count || !weights || (chroma != 0 && chroma != 1) || (axis != 0 && axis != 1)) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  ScaleShape s;
+  { const hmgpu_status st = scaled_plan(seq, d, sc, &plan, &s); if (st != HMGPU_OK) return st; }
+  if (chroma >= s.classes) return HMGPU_EINVAL;
+  const ScaleTab& t = *s.tab[chroma][axis];
+  if (max_taps < t.taps) return HMGPU_EINVAL;
+  const int n = s.out[chroma][axis];
+  memcpy(first, t.first.data(), sizeof(int32_t) * (size_t)n);
+  memcpy(count, t.count.data(), sizeof(int32_t) * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    memset(weights + (size_t)i * max_taps, 0, sizeof(int16_t) * (size_t)max_taps);
+    memcpy(weights + (size_t)i * max_taps, t.w.data() + (size_t)i * t.taps, sizeof(int16_t) * (size_t)t.taps);
+  }
+  return HMGPU_OK;
+}
+
+namespace {
+
+// tile of one plane class (ScaleClass): wide enough to share source samples, small enough to give the GPU work for every CU, and the
+// LDS of a pass (C channels: 16-bit staged samples + 32-bit horizontal sums) within kScaleLdsBytes
+struct ScaleTiles { int tw, th, rows, cap, tiles_x, tiles_y; std::vector<int32_t> span[2]; };
+
+std::vector<int32_t> scale_spans(const ScaleTab& t, int n, int tile) {
+  std::vector<int32_t> sp;
+  for (int i0 = 0; i0 < n; i0 += tile) {
+    int lo = INT32_MAX, hi = 0;
+    for (int i = i0; i < std::min(n, i0 + tile); i++) { lo = std::min(lo, t.first[(size_t)i]); hi = std::max(hi, t.first[(size_t)i] + t.count[(size_t)i]); }
+    sp.push_back(lo); sp.push_back(hi);
+  }
+  return sp;
+}
+
+// the tile a class starts from: wide for sharing source samples, shrunk towards 64 outputs while the n pictures of a call bring fewer
+// than ~1000 workgroups (large reductions: or a few workgroups would do all the work)
+void scale_tile_start(int outw, int outh, int n, int* tw_out, int* th_out) {
+  int tw = 128;
+  while (tw > 4 && tw / 2 >= outw) tw /= 2;
+  int th = 1024 / tw;
+  while (th > 1 && th / 2 >= outh) th /= 2;
+  auto blocks = [&]() { return (long long)((outw + tw - 1) / tw) * ((outh + th - 1) / th); };
+  while (blocks() * n < 1024 && tw * th > 64) {
+    if (th >= tw / 4 && th > 2) th /= 2;
+    else if (tw > 16) tw /= 2;
+    else break;
+  }
+  *tw_out = tw; *th_out = th;
+}
+
+ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int outh, int x0, int C, int tw, int th) {
+  const int G = C == 2 ? 4 : 8;
+  ScaleTiles z;
+  z.tw = tw; z.th = th;
+  for (;;) {
+    z.span[0] = scale_spans(tx, outw, z.tw);
+    z.cap = 0;
+    for (size_t i = 0; i < z.span[0].size(); i += 2) {
+      const int a = (x0 + z.span[0][i]) & ~(G - 1), b = (x0 + z.span[0][i + 1] + G - 1) & ~(G - 1);
+      z.cap = std::max(z.cap, b - a);
+    }
+    z.cap = (z.cap + 7) & ~7;
+    z.rows = std::min(1024 / z.tw, kScaleLdsBytes / (C * (2 * z.cap + 4 * z.tw)));
+    if ((z.rows >= 4 || z.tw <= 16) && z.rows >= 1) break;
+    z.tw /= 2;
+  }
+  z.span[1] = scale_spans(ty, outh, z.th);
+  z.tiles_x = (outw + z.tw - 1) / z.tw;
+  z.tiles_y = (outh + z.th - 1) / z.th;
+  return z;
+}
+
+// the slot that holds the tables of `key`: found, or filled (least recently used slot) with a copy enqueued on hs
+hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s, bool rgb, int x0c[2], const int tile[2][2], hipStream_t hs, hmgpu_ctx::ScaleSlot** out) {
+  hmgpu_ctx::ScaleSlot* slot = nullptr;
+  for (auto& sl : c->scale_slot)
+    if (sl.valid && !memcmp(sl.key, key, sizeof(sl.key))) { slot = &sl; break; }
+  if (!slot) {
+    slot = &c->scale_slot[0];
+    for (auto& sl : c->scale_slot) {
+      if (!sl.valid) { slot = &sl; break; }
+      if (sl.used < slot->used) slot = &sl;
+    }
+    if (slot->pending) HIP_TRY(c, hipEventSynchronize(slot->done));   // an export in flight still reads it
+    slot->valid = slot->pending = false;
+    // layout: per class and axis first, count, span, weights (tap-major), each 256-byte aligned
+    ScaleTiles z[2];
+    size_t off[2][2][4], bytes = 0;
+    for (int k = 0; k < s.classes; k++) {
+      const int C = rgb ? 3 : k ? 2 : 1;
+      z[k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], x0c[k], C, tile[k][0], tile[k][1]);
+      for (int ax = 0; ax < 2; ax++) {
+        const size_t n = (size_t)s.out[k][ax], sizes[4] = {4 * n, 4 * n, 4 * z[k].span[ax].size(), 2 * n * (size_t)s.tab[k][ax]->taps};
+        for (int f = 0; f < 4; f++) { off[k][ax][f] = bytes; bytes += align_up(sizes[f], 256); }
+      }
+    }
+    if (bytes > slot->cap) {
+      if (slot->dev) HIP_TRY(c, hipFree(slot->dev));
+      if (slot->host) HIP_TRY(c, hipHostFree(slot->host));
+      slot->dev = slot->host = nullptr;
+      slot->cap = 0;
+      HIP_TRY(c, hipMalloc(&slot->dev, bytes));
+      HIP_TRY(c, hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
+      slot->cap = bytes;
+    }
+    if (!slot->done) HIP_TRY(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    for (int k = 0; k < s.classes; k++) {
+      ScaleClass& cl = slot->cls[k];
+      memset(&cl, 0, sizeof(cl));
+      for (int ax = 0; ax < 2; ax++) {
+        const ScaleTab& t = *s.tab[k][ax];
+        const int n = s.out[k][ax];
+        memcpy(slot->host + off[k][ax][0], t.first.data(), 4 * (size_t)n);
+        memcpy(slot->host + off[k][ax][1], t.count.data(), 4 * (size_t)n);
+        memcpy(slot->host + off[k][ax][2], z[k].span[ax].data(), 4 * z[k].span[ax].size());
+        int16_t* w = reinterpret_cast<int16_t*>(slot->host + off[k][ax][3]);
+        for (int j = 0; j < t.taps; j++)
+          for (int i = 0; i < n; i++) w[(size_t)j * n + i] = t.w[(size_t)i * t.taps + j];
+        ScaleTable& d = ax ? cl.ty : cl.tx;
+        d.first = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][0]);
+        d.count = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][1]);
+        d.span = reinterpret_cast<const int32_t*>(slot->dev + off[k][ax][2]);
+        d.w = reinterpret_cast<const int16_t*>(slot->dev + off[k][ax][3]);
+        d.n = n;
+      }
+      cl.tw = z[k].tw; cl.th = z[k].th; cl.rows = z[k].rows; cl.span_cap = z[k].cap;
+      cl.tiles_x = z[k].tiles_x; cl.blocks = z[k].tiles_x * z[k].tiles_y;
+    }
+    HIP_TRY(c, hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, hs));
+    memcpy(slot->key, key, sizeof(slot->key));
+    slot->valid = true;
+  }
+  slot->used = ++c->scale_tick;
+  *out = slot;
+  return HMGPU_OK;
+}
+
+// hmgpu_pictures_export_windows, windows that differ: the blob of one call -- the per-picture classes ([n][2] ScaleClass), then every
+// distinct table (first, count, weights tap-major) and every distinct span list, each 256-byte aligned -- built in the next buffer of
+// the ring and sent in one copy on hs.  tile: where the classes' tiles start (scale_tile_start); tw shrinks until the LDS of a pass
+// fits the most demanding window.  cls: tw, th, tiles_x and blocks of the call; *pic_cls: the classes in device memory.
+hmgpu_status window_tables(hmgpu_ctx* c, int n, const std::vector<ScaleShape>& shapes, const hmgpu_export_window* win, bool rgb,
+                           const int tile[2][2], hipStream_t hs, ScaleClass cls[2], const ScaleClass** pic_cls, hmgpu_ctx::WindowBuf** out) {
+  const int classes = shapes[0].classes;
+  std::vector<ScaleTiles> z((size_t)n * 2);
+  for (int k = 0; k < classes; k++) {
+    const int C = rgb ? 3 : k ? 2 : 1;
+    for (int tw = tile[k][0];;) {
+      int least = tw;
+      for (int i = 0; i < n; i++) {
+        const ScaleShape& s = shapes[(size_t)i];
+        z[(size_t)i * 2 + k] = scale_tiles(*s.tab[k][0], *s.tab[k][1], s.out[k][0], s.out[k][1], k ? win[i].crop[0] >> c->csx : win[i].crop[0], C, tw, tile[k][1]);
+        least = std::min(least, z[(size_t)i * 2 + k].tw);
+      }
+      if (least == tw) break;
+      tw = least;
+    }
+  }
+  std::vector<char> blob(align_up((size_t)n * 2 * sizeof(ScaleClass), 256), 0);
+  auto place = [&](const void* src, size_t bytes) {
+    const size_t off = blob.size();
+    blob.resize(off + align_up(bytes, 256), 0);
+    memcpy(blob.data() + off, src, bytes);
+    return off;
+  };
+  std::map<const ScaleTab*, size_t> tab_at;                                // first; count and the weights follow
+  std::map<std::pair<const ScaleTab*, int>, size_t> span_at;               // (table, tile size)
+  struct TabOff { size_t first, count, w, span; };
+  std::vector<TabOff> offs((size_t)n * 4);
+  std::vector<int16_t> w;
+  for (int i = 0; i < n; i++) {
+    for (int k = 0; k < classes; k++) {
+      const ScaleTiles& zt = z[(size_t)i * 2 + k];
+      for (int ax = 0; ax < 2; ax++) {
+        const ScaleTab* t = shapes[(size_t)i].tab[k][ax].get();
+        const int no = shapes[(size_t)i].out[k][ax];
+        TabOff& o = offs[(size_t)i * 4 + k * 2 + ax];
+        auto it = tab_at.find(t);
+        if (it == tab_at.end()) {
+          const size_t at = place(t->first.data(), 4 * (size_t)no);
+          place(t->count.data(), 4 * (size_t)no);
+          w.assign((size_t)no * t->taps, 0);
+          for (int j = 0; j < t->taps; j++)
+            for (int q = 0; q < no; q++) w[(size_t)j * no + q] = t->w[(size_t)q * t->taps + j];
+          place(w.data(), 2 * w.size());
+          it = tab_at.emplace(t, at).first;
+        }
+        o.first = it->second;
+        o.count = o.first + align_up(4 * (size_t)no, 256);
+        o.w = o.count + align_up(4 * (size_t)no, 256);
+        const auto skey = std::make_pair(t, ax ? zt.th : zt.tw);
+        auto sp = span_at.find(skey);
+        if (sp == span_at.end()) sp = span_at.emplace(skey, place(zt.span[ax].data(), 4 * zt.span[ax].size())).first;
+        o.span = sp->second;
+      }
+    }
+  }
+  hmgpu_ctx::WindowBuf* wb = &c->window_buf[c->window_next];
+  c->window_next = (c->window_next + 1) % hmgpu_ctx::kWindowBufs;
+  if (wb->pending) HIP_TRY(c, hipEventSynchronize(wb->done));              // the export that read it last may still be in flight
+  wb->pending = false;
+  if (blob.size() > wb->cap) {
+    if (wb->dev) HIP_TRY(c, hipFree(wb->dev));
+    if (wb->host) HIP_TRY(c, hipHostFree(wb->host));
+    wb->dev = wb->host = nullptr;
+    wb->cap = 0;
+    const size_t cap = align_up(blob.size() + blob.size() / 2, 4096);      // (head room: the next call's windows differ)
+    HIP_TRY(c, hipMalloc(&wb->dev, cap));
+    HIP_TRY(c, hipHostMalloc(&wb->host, cap, hipHostMallocDefault));
+    wb->cap = cap;
+  }
+  if (!wb->done) HIP_TRY(c, hipEventCreateWithFlags(&wb->done, hipEventDisableTiming));
+  ScaleClass* pc = reinterpret_cast<ScaleClass*>(blob.data());
+  for (int i = 0; i < n; i++) {
+    for (int k = 0; k < classes; k++) {
+      const ScaleTiles& zt = z[(size_t)i * 2 + k];
+      ScaleClass& cl = pc[i * 2 + k];
+      for (int ax = 0; ax < 2; ax++) {
+        const TabOff& o = offs[(size_t)i * 4 + k * 2 + ax];
+        ScaleTable& d = ax ? cl.ty : cl.tx;
+        d.first = reinterpret_cast<const int32_t*>(wb->dev + o.first);
+        d.count = reinterpret_cast<const int32_t*>(wb->dev + o.count);
+        d.span = reinterpret_cast<const int32_t*>(wb->dev + o.span);
+        d.w = reinterpret_cast<const int16_t*>(wb->dev + o.w);
+        d.n = shapes[(size_t)i].out[k][ax];
+      }
+      cl.tw = zt.tw; cl.th = zt.th; cl.rows = zt.rows; cl.span_cap = zt.cap;
+      cl.tiles_x = zt.tiles_x; cl.blocks = zt.tiles_x * zt.tiles_y;
+      cl.x0 = k ? win[i].crop[0] >> c->csx : win[i].crop[0];
+      cl.y0 = k ? win[i].crop[2] >> c->csy : win[i].crop[2];
+      cl.pitch = c->pitch[k];
+      if (!i) cls[k] = cl;
+    }
+  }
+  memcpy(wb->host, blob.data(), blob.size());
+  HIP_TRY(c, hipMemcpyAsync(wb->dev, wb->host, blob.size(), hipMemcpyHostToDevice, hs));
+  *pic_cls = reinterpret_cast<const ScaleClass*>(wb->dev);
+  *out = wb;
+  return HMGPU_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ the export entry points
+// the output element (kElem*) of a descriptor already validated by its plan function, and of `t` (null: unsigned)
+static hmgpu_status export_elem(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int* elem) {
+  *elem = d->bytes_per_sample == 1 ? kElemU8 : kElemU16;
+  if (!t) return HMGPU_OK;
+  for (int k = 0; k < 5; k++) if (t->reserved[k]) return HMGPU_EINVAL;
+  if (t->sample_type < HMGPU_SAMPLE_UINT || t->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
+  if (t->sample_type == HMGPU_SAMPLE_UINT) return HMGPU_OK;
+  if (d->msb_aligned) return HMGPU_EINVAL;
+  for (int k = 0; k < 3; k++) if (!std::isfinite(t->scale[k]) || !std::isfinite(t->bias[k])) return HMGPU_EINVAL;
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
+  int D = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+  if (!rgb && seq->chroma_format != 0) D = std::max(D, d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma);
+  if (d->bytes_per_sample != (D <= 8 ? 1 : 2)) return HMGPU_EINVAL;      // the container an unsigned export of that depth needs
+  if (d->layout == HMGPU_EXPORT_SEMIPLANAR) return HMGPU_EUNSUPPORTED;
+  *elem = t->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : t->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+  return HMGPU_OK;
+}
+
+static int elem_size(int elem) { return elem == kElemU8 ? 1 : elem == kElemF32 ? 4 : 2; }
+
+static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem, CallTabs* call_tabs = nullptr) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape, call_tabs) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
+  const hmgpu_status st = export_elem(seq, d, t, elem);
+  if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
+  if (*elem >= kElemF16)
+    for (int k = 0; k < out->planes; k++) out->row_bytes[k] = out->width[k] * elem_size(*elem);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, hmgpu_export_plan* out) {
+  int elem = 0;
+  return tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+}
+
+// hmgpu_pictures_export_windows: every window validated as the single call validates its crop, in order (the first failure is the
+// call's status).  differ: the windows are not all equal; shapes (scaled): one per window then, else one for all.
+static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
+                                 int n, const hmgpu_export_window* win, hmgpu_export_plan* out, std::vector<ScaleShape>* shapes, int* elem,
+                                 bool* differ) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  if (!win || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;          // the window is the crop
+  *differ = false;
+  for (int i = 1; i < n; i++) if (memcmp(win[i].crop, win[0].crop, sizeof(win[0].crop))) *differ = true;
+  CallTabs tabs;
+  hmgpu_export_plan plan;
+  if (shapes) shapes->clear();
+  for (int i = 0; i < n; i++) {
+    if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }
+    if (i && !*differ) continue;
+    hmgpu_export_desc dd = *d;
+    memcpy(dd.crop, win[i].crop, sizeof(dd.crop));
+    ScaleShape s;
+    const hmgpu_status st = tensor_plan(seq, &dd, sc, t, &plan, &s, elem, *differ && sc ? &tabs : nullptr);
+    if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
+    if (shapes && sc) shapes->push_back(s);
+    if (!i) { *out = plan; continue; }
+    if (plan.width[0] != out->width[0] || plan.height[0] != out->height[0]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }   // (unscaled)
+    out->coef[12] = std::max(out->coef[12], plan.coef[12]);
+    out->coef[13] = std::max(out->coef[13], plan.coef[13]);
+  }
+  call_tabs_keep(tabs);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[], hmgpu_export_plan* out) {
+  int elem = 0;
+  bool differ = false;
+  return windows_plan(seq, d, sc, t, n, windows, out, nullptr, &elem, &differ);
+}
+
+// every plane's destination, all n pictures of it, inside one allocation of the context's device (bstride null: one picture); vec is
+// cleared unless every group of 4 samples of every picture may be one store; bs: the batch strides in use
+static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& plan, int ES, int n, void* const dst[3],
+                                  const int64_t pitch_bytes[3], const int64_t* bstride, bool* vec, int64_t bs[3]) {
+  for (int k = 0; k < plan.planes; k++) {
+    if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t extent = pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    if (bstride) {
+      if (bstride[k] < extent || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+      bs[k] = bstride[k];
+    }
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bs[k] + extent), c->device)) return HMGPU_EINVAL;
+    *vec = *vec && ((uintptr_t)dst[k] % (4 * ES)) == 0 && pitch_bytes[k] % (4 * ES) == 0 && (n == 1 || bs[k] % (4 * ES) == 0);
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                            const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  int elem = 0;
+  { const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, nullptr, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  bool vec = true;
+  int64_t bs[3];
+  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
+}
+
+hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  int elem = 0;
+  bool differ = false;
+  { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, windows, &plan, nullptr, &elem, &differ); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  bool vec = true;
+  int64_t bs[3];
+  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
+}
+
+// every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; bstride null: one picture, no batch
+// stride to check; win null: desc->crop for every picture, no mirror.  One launch, the stream ordering once.
+static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
+                                int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  ScaleShape s;
+  int elem = 0;
+  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
+  hmgpu_export_desc dd;
+  bool differ = false;
+  uint32_t flip = 0;
+  if (win) {
+    { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, win, &plan, &shapes, &elem, &differ); if (st != HMGPU_OK) return st; }
+    for (int i = 0; i < n; i++) flip |= (uint32_t)(win[i].flip & 1) << i;
+    if (!differ) {                                   // one window for all: the descriptor with that crop, its table slot
+      dd = *d;
+      memcpy(dd.crop, win[0].crop, sizeof(dd.crop));
+      d = &dd;
+      if (sc) s = shapes[0];
+    }
+  } else {
+    const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem);
+    if (st != HMGPU_OK) return st;
+  }
+  hipSetDevice(c->device);
+  const int ES = elem_size(elem);
+  bool vec = true;
+  int64_t bs[3] = {0, 0, 0};
+  { const hmgpu_status st = export_dst_ok(c, plan, ES, n, dst, pitch_bytes, bstride, &vec, bs); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
+  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
+  const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
+  const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  if (!sc) {
+    ExportArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < n; i++) {
+      const Picture& p = c->pics[pics[i]];
+      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+      const int x0 = differ ? win[i].crop[0] : d->crop[0], y0 = differ ? win[i].crop[2] : d->crop[2];
+      a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
+      a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+      if (vec && (x0 & 3) == 0) a.vec |= 1u << i;                         // (a batch may mix aligned and unaligned left edges)
+    }
+    a.flip = flip;
+    a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
+    a.n = n; a.layout = d->layout; a.elem = elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+    a.w = plan.width[0]; a.h = plan.height[0];
+    a.cw = (plan.width[0]) >> c->csx; a.ch = plan.height[0] >> c->csy;
+    a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
+    a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
+    a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
+    for (int k = 0; k < 3; k++) {
+      a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
+      a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
+      a.bstride[k] = bs[k];
+      if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+    }
+    memcpy(a.coef, plan.coef, sizeof(a.coef));
+    launch_export(a, hs);
+    return export_end(c, n, pics, on_stream, hs);
+  }
+  if (differ) s = shapes[0];                         // (the output size and the depths are those of every window)
+  // the tables' slot is keyed by the tiles the batch size leads to, not by the batch size: calls of varying n share a slot
+  int tile[2][2] = {{0, 0}, {0, 0}};
+  int32_t tkey = rgb ? 1 : 0;
+  for (int k = 0; k < s.classes; k++) {
+    scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
+    tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
+  }
+  hmgpu_ctx::ScaleSlot* slot = nullptr;
+  hmgpu_ctx::WindowBuf* wbuf = nullptr;
+  ScaleArgs a;
+  memset(&a, 0, sizeof(a));
+  if (differ) {
+    const hmgpu_status st = window_tables(c, n, shapes, win, rgb, tile, hs, a.cls, &a.pic_cls, &wbuf);
+    if (st != HMGPU_OK) return st;
+  } else {
+    const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
+    int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
+    { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
+    for (int k = 0; k < s.classes; k++) {
+      a.cls[k] = slot->cls[k];
+      a.cls[k].pitch = c->pitch[k];
+      a.cls[k].x0 = x0c[k];
+      a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
+    }
+  }
+  a.flip = flip;
+  for (int i = 0; i < n; i++) {
+    const Picture& p = c->pics[pics[i]];
+    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+    a.src[i][0] = src[0]; a.src[i][1] = src[1];
+  }
+  a.pitch_c = c->pitch[1];
+  a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+  a.sh[0] = s.depth[0] - bdY; a.sh[1] = (rgb ? s.depth[0] : s.depth[1]) - bdC;
+  a.maxv[0] = (1 << s.depth[0]) - 1; a.maxv[1] = (1 << (rgb ? s.depth[0] : s.depth[1])) - 1;
+  a.msb[0] = d->msb_aligned ? 16 - s.depth[0] : 0; a.msb[1] = d->msb_aligned ? 16 - (rgb ? s.depth[0] : s.depth[1]) : 0;
+  a.e = plan.coef[11];
+  a.vec = vec ? 1 : 0;
+  for (int k = 0; k < 3; k++) {
+    a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
+    a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
+    a.bstride[k] = bs[k];
+    if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+  }
+  memcpy(a.coef, plan.coef, sizeof(a.coef));
+  launch_export_scaled(a, d->layout, elem, n, hs);
+  if (wbuf) {
+    HIP_TRY(c, hipEventRecord(wbuf->done, hs));
+    wbuf->pending = true;
+  } else {
+    HIP_TRY(c, hipEventRecord(slot->done, hs));
+    slot->pending = true;
+  }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
+                                  int32_t on_stream, void* stream) {
+  return export_impl(c, 1, &pic, d, nullptr, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
+  if (!sc) return HMGPU_EINVAL;
+  return export_impl(c, 1, &pic, d, sc, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                   const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                   const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                           const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes || !windows) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
+}
+
+// ------------------------------------------------------------------------------------------------ motion and block export (k_motion.hip)
+// hmgpu_motion_plan_for and what the entry point needs beyond the plan: the output element of the dense form (kElem*)
+static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int n,
+                                const hmgpu_export_window* win, hmgpu_motion_plan* out, int* elem) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  *elem = kElemU16;
+  const int fmt = seq->chroma_format;
+  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 3) || (seq->height & 3)) return HMGPU_EINVAL;
+  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int k = 0; k < 5; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->form != HMGPU_MOTION_BLOCKS && d->form != HMGPU_MOTION_DENSE) return HMGPU_EINVAL;
+  if (d->lists < 1 || d->lists > 3) return HMGPU_EINVAL;
+  const int L = (d->lists & 1) + (d->lists >> 1);
+  int w = 0, h = 0;
+  if (d->form == HMGPU_MOTION_BLOCKS) {
+    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
+    const int* cr = d->crop;
+    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0 || ((cr[0] | cr[1] | cr[2] | cr[3]) & 3)) return HMGPU_EINVAL;      // whole blocks
+    w = (seq->width - cr[0] - cr[1]) / 4; h = (seq->height - cr[2] - cr[3]) / 4;
+    if (w <= 0 || h <= 0) return HMGPU_EINVAL;
+    out->channels[HMGPU_MOTION_DST_MV0] = 2 * L;
+    out->elem_bytes[HMGPU_MOTION_DST_MV0] = 2;
+  } else {
+    if (!win) return HMGPU_EINVAL;
+    if (d->sample_type != HMGPU_SAMPLE_F16 && d->sample_type != HMGPU_SAMPLE_BF16 && d->sample_type != HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
+    if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;            // the window is the crop
+    *elem = d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+    if (sc) {
+      for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+      if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+      if (sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                       // vectors are not interpolated
+    }
+    const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0, mono = fmt == 0;
+    for (int i = 0; i < n; i++) {
+      const int* cr = win[i].crop;
+      if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) return HMGPU_EINVAL;
+      if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+      const int ww = seq->width - cr[0] - cr[1], wh = seq->height - cr[2] - cr[3];
+      if (ww <= 0 || wh <= 0) return HMGPU_EINVAL;
+      if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+      if (sc) {
+        const long long in[2] = {ww, wh}, o[2] = {sc->width, sc->height};
+        for (int ax = 0; ax < 2; ax++) if (o[ax] > 16384 || in[ax] > 32 * o[ax] || o[ax] > 8 * in[ax]) return HMGPU_EUNSUPPORTED;
+      } else {
+        if (!i) { w = ww; h = wh; }
+        if (ww != w || wh != h) return HMGPU_EINVAL;                                          // unscaled: one size, the output's
+        if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
+      }
+    }
+    if (sc) { w = sc->width; h = sc->height; }
+    const int es = *elem == kElemF32 ? 4 : 2;
+    for (int l = 0; l < 2; l++) if ((d->lists >> l) & 1) { out->channels[l] = 2; out->elem_bytes[l] = es; }
+  }
+  out->lists = L;
+  out->channels[HMGPU_MOTION_DST_REF] = L; out->elem_bytes[HMGPU_MOTION_DST_REF] = 4;
+  out->channels[HMGPU_MOTION_DST_BLOCK] = 4; out->elem_bytes[HMGPU_MOTION_DST_BLOCK] = 1;
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!out->channels[k]) { out->elem_bytes[k] = 0; continue; }
+    out->width[k] = w; out->height[k] = h; out->row_bytes[k] = w * out->elem_bytes[k];
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_motion_plan_for(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int32_t n,
+                                   const hmgpu_export_window windows[], hmgpu_motion_plan* out) {
+  int elem = 0;
+  const hmgpu_status st = motion_plan(seq, d, sc, n, windows, out, &elem);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// every destination given: element alignment, strides against the extents they step over, and the whole span of n pictures inside one
+// allocation of the context's device.  vec: bit k set when every group of four elements of slot k may be one store
+static hmgpu_status motion_dst_ok(const hmgpu_ctx* c, const hmgpu_motion_plan& plan, int n, void* const dst[4], const int64_t* pitch,
+                                  const int64_t* pstride, const int64_t* bstride, int* vec) {
+  bool any = false;
+  *vec = 0;
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!dst[k]) continue;
+    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
+    any = true;
+    const int64_t es = plan.elem_bytes[k];
+    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48)) return HMGPU_EINVAL;
+    const int64_t pic = pstride[k] * (plan.channels[k] - 1) + plane;
+    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % es || pitch[k] % es || pstride[k] % es || bstride[k] % es) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
+    const int64_t g = 4 * es;
+    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && pstride[k] % g == 0 && bstride[k] % g == 0) *vec |= 1 << k;
+  }
+  return any ? HMGPU_OK : HMGPU_EINVAL;
+}
+
+hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref, void* dst_block,
+                                            const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                            const int64_t batch_stride_bytes[4]) {
+  if (!c || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_motion_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+  return motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+}
+
+hmgpu_status hmgpu_pictures_motion_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) {
+    if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+    if (c->pics[pics[i]].covered_ctus != c->num_ctus) return HMGPU_EINVAL;       // no side information (uploaded, received, partly decoded)
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_motion_desc* d,
+                                          const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst_mv[2],
+                                          void* dst_ref, void* dst_block, const int64_t pitch_bytes[4],
+                                          const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
+                                          void* stream) {
+  if (!c || !pics || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  { const hmgpu_status st = hmgpu_pictures_motion_check(c, n, pics); if (st != HMGPU_OK) return st; }
+  hmgpu_motion_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+  { const hmgpu_status st = motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  MotionArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.lists = d->lists; a.nlists = plan.lists;
+  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
+  for (int i = 0; i < n; i++) {
+    const PicDev& p = c->pics[pics[i]].dev;
+    MotionSrc& s = a.src[i];
+    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.qp = p.qp;
+    for (int l = 0; l < 2; l++) { s.mv[l] = p.mv[l]; s.ref_idx[l] = p.ref_idx[l]; }
+    s.slice_idx = p.slice_idx; s.slices = p.slices;
+  }
+  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
+    if (!dst[k]) continue;
+    a.dst[k] = static_cast<uint8_t*>(dst[k]);
+    a.pitch[k] = pitch_bytes[k]; a.pstride[k] = plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
+  }
+  a.vec = vec;
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  if (d->form == HMGPU_MOTION_BLOCKS) {
+    a.x4 = d->crop[0] / 4; a.y4 = d->crop[2] / 4; a.w4 = plan.width[HMGPU_MOTION_DST_REF]; a.h4 = plan.height[HMGPU_MOTION_DST_REF];
+    if (a.x4 & 3) a.vec = 0;                         // a lane's four blocks are aligned in the picture, not in the crop
+    launch_motion_blocks(a, hs);
+  } else {
+    a.W = plan.width[HMGPU_MOTION_DST_REF]; a.H = plan.height[HMGPU_MOTION_DST_REF];
+    for (int i = 0; i < n; i++) {
+      const int* cr = windows[i].crop;
+      MotionWin& w = a.win[i];
+      w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
+      w.kx = (float)((double)a.W / (4.0 * w.w)); w.ky = (float)((double)a.H / (4.0 * w.h));     // quarter luma samples -> output samples
+      a.flip |= (uint32_t)(windows[i].flip & 1) << i;
+    }
+    launch_motion_dense(a, elem, hs);
+  }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+}  // extern "C"
