@@ -91,6 +91,7 @@ typedef struct hmgpu_export_scale hmgpu_export_scale;
 typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 typedef struct hmgpu_export_window hmgpu_export_window;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
+typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -124,6 +125,14 @@ int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,
                                  void* dst_block, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
                                  const int64_t batch_stride_bytes[4], int on_stream, void* stream);
+/* The decoded residual of up to 16 pictures in one call (hmgpu_pictures_export_residual: int16 PLANES or the DENSE per-sample form;
+ * destinations, strides and statuses as there), under the rules of hmdec_pictures_export_motion: the residual lies in the device
+ * context that decoded a picture, everything is validated before any context is given work (hmgpu_residual_destination_check,
+ * hmgpu_pictures_residual_check), then each context gets one call per run of equally spaced slots. */
+int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_residual_desc* desc,
+                                   const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                   const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
+                                   int on_stream, void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

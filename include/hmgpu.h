@@ -511,6 +511,82 @@ hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* ctx, int32_t n, const hmg
                                             const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
                                             const int64_t batch_stride_bytes[4]);
 
+/* ------------------------------------------------------------------------------------------------ residual export
+ * The decoded residual of finished pictures -- what is added to the prediction -- written on the device straight into caller-owned
+ * device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one kernel launch per call.  The source is what the
+ * decompress calls left on the device for the picture: the residual of every coded transform unit, and HM's per-partition arrays.
+ *
+ * Value of a sample of component c: what HM adds to the prediction there, the int16 output of TComTrQuant::invRecurTransformNxN / xIT
+ * for the transform block that covers it -- de-quantisation with scaling lists, inverse DCT / DST, transform skip, rotation, RDPCM,
+ * and for cu_transquant_bypass CUs the level itself -- and exactly 0 wherever no coded transform block covers the sample.
+ * Covered: the sample lies in a block whose cbf bits are set down to its transform unit's depth, (cbf & chain) == chain with
+ * chain = (1 << (tr_idx + 1)) - 1, of a decoded partition (part_size != HMGPU_SIZE_NONE) with a transform size of 4 .. 32: the rule of
+ * hmgpu_coeffs, the 4x4 chroma block under four 4x4 luma units (flagged at the first of them) included.  Codedness is taken from the
+ * arrays cbf, tr_idx, depth, part_size, pred_mode and ipcm alone, never from what the device buffers hold.  Zero although flagged:
+ *   PCM CUs (ipcm; their samples are not a residual);
+ *   intra CUs of a picture decoded without intra_dir[] (the device leaves such CUs alone and computes nothing for them).
+ * The flag group (transform_skip / transquant_bypass / ipcm) is read only for a picture it was staged for.  Intra CUs carry a
+ * residual only when every decompress call that covers the picture came with intra_dir[]: a picture built with
+ * hmgpu_decompress_slice whose calls disagree about intra_dir[] has the intra CUs of ALL its slices exported as 0 (a limitation:
+ * the record is per picture, not per CTU).  Nothing an earlier picture of the handle left behind is returned.
+ * Formats: 4:0:0 and 4:2:0 (8 .. 12 bits, CTUs of 16 / 32 / 64 samples).  4:2:2 and 4:4:4 give HMGPU_EUNSUPPORTED before anything is
+ * enqueued: cross-component prediction rewrites their chroma residual in place, and a 4:2:2 chroma block is two squares.  For a 4:0:0
+ * picture the chroma components do not exist: their bits in `components` are ignored and nothing is written for them (PLANES: dst[1] /
+ * dst[2] are ignored; DENSE: their channels keep their place and are left untouched).
+ * A picture has a residual under the rule of the motion export: decompress calls have covered every CTU since it was acquired (else
+ * HMGPU_EINVAL); pictures decoded through the packed entry point qualify.
+ *
+ * HMGPU_RESIDUAL_PLANES: int16, each component at its own resolution.  desc->components (bit c: component c; at least one) selects;
+ * desc->crop (left, right, top, bottom in luma samples, each a multiple of 8, else HMGPU_EINVAL; 0,0,0,0 = the coded picture) selects
+ * w x h luma samples; scale and windows must be NULL, sample_type HMGPU_SAMPLE_UINT (the elements are SIGNED 16-bit integers).
+ *   dst[0]  int16 [n][h][w];  dst[1], dst[2]  int16 [n][h / 2][w / 2]  (Cb, Cr); a dst of a component that is not selected must be NULL
+ * HMGPU_RESIDUAL_DENSE: one value per output sample of hmgpu_pictures_export_windows with the same windows, output size and flips, by
+ * the integer nearest rule of the dense motion export: output (ox, oy) of slot i takes luma position (left + sx, top + sy),
+ * sx = min(floor((2 * ox + 1) * win_w / (2 * W)), win_w - 1), sy alike, and of a chroma component the sample ((left + sx) >> 1,
+ * (top + sy) >> 1).  windows[i] as for the motion export; either `scale` (filter must be HMGPU_SCALE_NEAREST, else
+ * HMGPU_EUNSUPPORTED) or windows of one size; desc->crop must be 0; the limits are those of the scaled export (HMGPU_EUNSUPPORTED).
+ *   dst[0]  [n][C][H][W], C = the selected components in component order;  dst[1], dst[2] must be NULL
+ *   sample_type HMGPU_SAMPLE_UINT: int16, the residual r itself.  F16 / BF16 / F32: convert(fmul((float)r, desc->scale[c])), one
+ *   binary32 product, then the conversion of the batched tensor export (nearest even); every scale of a selected component finite
+ *   flip & 1: every output row reversed; the values are unchanged
+ * Destinations: pitch_bytes (row to row), plane_stride_bytes (DENSE: channel to channel; PLANES: ignored) and batch_stride_bytes
+ * (picture to picture) per dst slot.  Any destination may be NULL (not written); at least one must be given.  Each must be aligned to
+ * its element, as must its strides; pitch >= row_bytes, plane stride >= pitch * (height - 1) + row_bytes, batch stride >= plane stride *
+ * (channels - 1) + that; and all n pictures of it must lie inside one allocation of the context's device.  Everything is validated
+ * before anything is enqueued and a refused call leaves every destination untouched.  Stream ordering is that of
+ * hmgpu_picture_export, once per call.  The launch is not accounted in hmgpu_stats. */
+enum { HMGPU_RESIDUAL_PLANES = 0, HMGPU_RESIDUAL_DENSE = 1 };
+typedef struct hmgpu_residual_desc {
+  int32_t form;                /* HMGPU_RESIDUAL_* */
+  int32_t components;          /* bit 0: Y, bit 1: Cb, bit 2: Cr */
+  int32_t sample_type;         /* HMGPU_SAMPLE_UINT: int16; DENSE also HMGPU_SAMPLE_F16 / BF16 / F32 */
+  int32_t crop[4];             /* PLANES: left, right, top, bottom in luma samples, multiples of 8; DENSE: 0 */
+  float scale[3];              /* DENSE, float types: per component */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_residual_desc;
+typedef struct hmgpu_residual_plan {
+  int32_t channels[3];         /* per destination slot: planes per picture, 0 = the slot does not exist (PLANES: 1 per selected component
+                                  that the format has; DENSE: slot 0 holds C planes) */
+  int32_t width[3], height[3]; /* of every plane, in elements */
+  int32_t elem_bytes[3];
+  int32_t row_bytes[3];        /* width * elem_bytes: the least pitch */
+  int32_t reserved[1];
+} hmgpu_residual_plan;
+/* validates a call's description and reports what it writes; host code, no device needed.  scale / windows: NULL for PLANES */
+hmgpu_status hmgpu_residual_plan_for(const hmgpu_seq_params* seq, const hmgpu_residual_desc* desc, const hmgpu_export_scale* scale,
+                                     int32_t n, const hmgpu_export_window windows[], hmgpu_residual_plan* out);
+hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_residual_desc* desc,
+                                            const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                            const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3],
+                                            const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* the two halves of that validation, nothing enqueued (libhmdec: pictures in several contexts of a GPU): HMGPU_OK when pics[0 .. n)
+ * are all valid handles of pictures with a residual; the status hmgpu_pictures_export_residual would give a description and a
+ * destination for n pictures */
+hmgpu_status hmgpu_pictures_residual_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[]);
+hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_residual_desc* desc, const hmgpu_export_scale* scale,
+                                              const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
+                                              const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->
  * TDecCu::decompressCU (TDecSlice.cpp:334, TDecCu.cpp:142,373) for the CTUs [first_ctu, first_ctu+num_ctus) of

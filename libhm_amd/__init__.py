@@ -115,6 +115,15 @@ def lib():
         L.hmgpu_motion_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale),
                                                      C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_residual_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ResidualDesc), C.POINTER(abi.ExportScale), C.c_int32,
+                                              C.POINTER(abi.ExportWindow), C.POINTER(abi.ResidualPlan)]
+        L.hmgpu_pictures_export_residual.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ResidualDesc),
+                                                     C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_pictures_residual_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.hmgpu_residual_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ResidualDesc), C.POINTER(abi.ExportScale),
+                                                       C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -224,6 +233,13 @@ def motion_plan(seq, form="blocks", lists=(0, 1), size=None, windows=None, flip=
     l, r, t, b = (int(v) for v in crop)
     win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * count, flip, count)
     return motion.plan_for(seq, abi.make_motion_desc(code, motion.lists_mask(lists), st), export.make_scale(size, "nearest"), win, count)
+
+
+def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0),
+                  n=None):
+    """what Context.export_residual with these arguments writes per picture (libhm_amd.residual.residual_plan: host code, no GPU)"""
+    from . import residual
+    return residual.residual_plan(seq, form, components, size, windows, flip, dtype, scale, crop, n)
 
 
 def export_scale_taps(seq, desc, scale, chroma, axis):
@@ -501,6 +517,51 @@ class Context:
         return motion.export_motion(lambda desc, sc, win, ptrs, pitches, pstrides, bstrides, st:
                                     self.export_motion_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st, sc, win),
                                     self.seq, self.device, len(pics), form, lists, size, windows, flip, dtype, out, crop)
+
+    def export_residual_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
+        """hmgpu_pictures_export_residual into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per
+        destination slot (planes: one per component; dense: slot 0; a pointer None / 0 = not written)"""
+        from . import residual
+        pics = list(pics)
+        h = (C.c_int32 * max(len(pics), 1))(*pics)
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
+        self._chk(lib().hmgpu_pictures_export_residual(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None, w,
+                                                       d, q, ps, bs, on_stream, C.c_void_p(stream or None)),
+                  "hmgpu_pictures_export_residual")
+
+    def residual_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides, scale=None, windows=None):
+        """hmgpu_residual_destination_check: the status hmgpu_pictures_export_residual would give this destination; enqueues nothing"""
+        from . import residual
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
+        return lib().hmgpu_residual_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None, w, d, q, ps, bs)
+
+    def residual_status(self, pics):
+        """hmgpu_pictures_residual_check: HMGPU_OK when every picture of the list has a residual to export; enqueues nothing"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_residual_check(self._h, len(pics), (C.c_int32 * max(len(pics), 1))(*pics))
+
+    def export_residual(self, pics, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None,
+                        out=None, crop=(0, 0, 0, 0), on_stream=True):
+        """the decoded residual of up to 16 decoded pictures as a dict of torch tensors on this context's GPU (libhm_amd.residual), one
+        launch, written on torch.cuda.current_stream() (on_stream) or on the context's own stream.  form "planes": int16 "y" [N, H, W],
+        "cb" / "cr" [N, H / 2, W / 2], crop in multiples of 8 luma samples.  form "dense": "residual" [N, C, H, W], one value per output
+        sample of export_batch(windows=, flip=, size=, filter="nearest") with the same arguments; dtype None (int16) or torch.float16 /
+        bfloat16 / float32 with scale (one factor per component).  out: a dict with some of those keys (only they are written); rows,
+        planes and batch entries may be any stride apart.  4:0:0 and 4:2:0 pictures; pictures that were uploaded, received or only
+        partly decoded have no residual (HMGPU_EINVAL)."""
+        from . import residual
+        pics = list(pics)
+        return residual.export_residual(lambda desc, sc, win, ptrs, pitches, pstrides, bstrides, st:
+                                        self.export_residual_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st, sc, win),
+                                        self.seq, self.device, len(pics), form, components, size, windows, flip, dtype, scale, out, crop)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

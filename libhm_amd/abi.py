@@ -163,6 +163,31 @@ def make_motion_desc(form, lists=3, sample_type=SAMPLE_UINT, crop=(0, 0, 0, 0)):
     return d
 
 
+RESIDUAL_PLANES, RESIDUAL_DENSE = 0, 1
+
+
+class ResidualDesc(C.Structure):
+    _fields_ = [("form", C.c_int32), ("components", C.c_int32), ("sample_type", C.c_int32), ("crop", C.c_int32 * 4),
+                ("scale", C.c_float * 3), ("reserved", C.c_int32 * 6)]
+
+
+class ResidualPlan(C.Structure):
+    _fields_ = [("channels", C.c_int32 * 3), ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("elem_bytes", C.c_int32 * 3),
+                ("row_bytes", C.c_int32 * 3), ("reserved", C.c_int32 * 1)]
+
+
+def make_residual_desc(form, components=7, sample_type=SAMPLE_UINT, crop=(0, 0, 0, 0), scale=(1.0, 1.0, 1.0)):
+    """form: RESIDUAL_PLANES / RESIDUAL_DENSE; components: the mask (bit c: component c); crop: (left, right, top, bottom), PLANES only;
+    scale: per component, the float types of DENSE"""
+    d = ResidualDesc()
+    d.form, d.components, d.sample_type = int(form), int(components), int(sample_type)
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    for k in range(3):
+        d.scale[k] = float(scale[k])
+    return d
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

@@ -448,6 +448,34 @@ struct MotionArgs {
 };
 void launch_motion_blocks(const MotionArgs& a, hipStream_t s);
 void launch_motion_dense(const MotionArgs& a, int elem, hipStream_t s);   // elem: kElemF16 / kElemBF16 / kElemF32
+// residual export (k_residual.hip, hmgpu_pictures_export_residual): everything by value, validated on the host.  The residual tiles
+// of every picture of the call (PicDev::resid) and the HM arrays that say which samples a coded transform block covers; `gate` is what
+// the host knows was staged for the picture: the arrays of a group that did not travel are never read.
+enum { kResidIntra = 1, kResidFlags = 2 };      // ResidSrc::gate: intra CUs carry a residual (intra_dir[] was given); the flag group (ipcm) was staged
+struct ResidSrc {
+  const uint8_t* depth; const int8_t* part_size; const int8_t* pred_mode; const uint8_t* tr_idx;
+  const uint8_t* cbf[3]; const uint8_t* ipcm;
+  const int16_t* resid[3];
+  int32_t gate, pad_;
+};
+struct ResidWin { int32_t left, top, w, h; };   // dense form: window in luma samples
+struct ResidArgs {
+  ResidSrc src[kMaxExportBatch];
+  ResidWin win[kMaxExportBatch];
+  int32_t n, comps, mono;          // pictures; the component mask (bit c; chroma bits cleared for 4:0:0 pictures); 4:0:0
+  int32_t log2ctu, ctus_w, parts;  // geometry of the context
+  int32_t rtw[3];                  // residual tiles per tile row of the component
+  int32_t x0, y0, w, h;            // planes form: first luma sample and size of the cropped picture (multiples of 8)
+  int32_t W, H;                    // dense form: output size
+  uint32_t flip;                   // dense form: bit i: slot i is mirrored
+  int32_t vec;                     // bit k: destination k may take 16-byte stores (alignment of crop, dst and strides)
+  int32_t chan[3];                 // dense form: the plane of component c in dst[0]
+  float scale[3];                  // dense form, float elements: per component
+  uint8_t* dst[3];                 // planes form: per component; dense form: dst[0]
+  int64_t pitch[3], pstride[3], bstride[3];   // bytes: row to row, plane to plane (dense), picture to picture
+};
+void launch_residual_planes(const ResidArgs& a, hipStream_t s);
+void launch_residual_dense(const ResidArgs& a, int elem, hipStream_t s);   // elem: kElemU16 (int16) / kElemF16 / kElemBF16 / kElemF32
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

@@ -1019,4 +1019,174 @@ hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_p
   return export_end(c, n, pics, on_stream, hs);
 }
 
+// ------------------------------------------------------------------------------------------------ residual export (k_residual.hip)
+// hmgpu_residual_plan_for and what the entry point needs beyond the plan: the output element (kElem*; kElemU16 stands for int16)
+static hmgpu_status residual_plan(const hmgpu_seq_params* seq, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc, int n,
+                                  const hmgpu_export_window* win, hmgpu_residual_plan* out, int* elem) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  *elem = kElemU16;
+  const int fmt = seq->chroma_format;
+  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 7) || (seq->height & 7)) return HMGPU_EINVAL;
+  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->form != HMGPU_RESIDUAL_PLANES && d->form != HMGPU_RESIDUAL_DENSE) return HMGPU_EINVAL;
+  if (d->components < 1 || d->components > 7) return HMGPU_EINVAL;
+  if (sc) {
+    for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+    if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+  }
+  if (fmt >= 2) return HMGPU_EUNSUPPORTED;          // k_ccp rewrites their chroma tiles in place; 4:2:2 blocks are two squares
+  const bool mono = fmt == 0;
+  if (d->form == HMGPU_RESIDUAL_PLANES) {
+    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
+    const int* cr = d->crop;
+    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0 || ((cr[0] | cr[1] | cr[2] | cr[3]) & 7)) return HMGPU_EINVAL;
+    const int w = seq->width - cr[0] - cr[1], h = seq->height - cr[2] - cr[3];
+    if (w <= 0 || h <= 0) return HMGPU_EINVAL;
+    for (int k = 0; k < 3; k++) {
+      if (!((d->components >> k) & 1) || (k && mono)) continue;
+      out->channels[k] = 1; out->elem_bytes[k] = 2;
+      out->width[k] = k ? w / 2 : w; out->height[k] = k ? h / 2 : h; out->row_bytes[k] = out->width[k] * 2;
+    }
+    return HMGPU_OK;
+  }
+  if (!win) return HMGPU_EINVAL;
+  if (d->sample_type < HMGPU_SAMPLE_UINT || d->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
+  if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;              // the window is the crop
+  *elem = d->sample_type == HMGPU_SAMPLE_UINT ? kElemU16 : d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+  if (*elem != kElemU16)
+    for (int k = 0; k < 3; k++) if (((d->components >> k) & 1) && !std::isfinite(d->scale[k])) return HMGPU_EINVAL;
+  if (sc && sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                    // a residual is not interpolated
+  int w = 0, h = 0;
+  for (int i = 0; i < n; i++) {
+    const int* cr = win[i].crop;
+    if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) return HMGPU_EINVAL;
+    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+    const int ww = seq->width - cr[0] - cr[1], wh = seq->height - cr[2] - cr[3];
+    if (ww <= 0 || wh <= 0) return HMGPU_EINVAL;
+    if (!mono && ((cr[0] | cr[1] | cr[2] | cr[3]) & 1)) return HMGPU_EINVAL;                  // whole chroma samples
+    if (sc) {
+      const long long in[2] = {ww, wh}, o[2] = {sc->width, sc->height};
+      for (int ax = 0; ax < 2; ax++) if (o[ax] > 16384 || in[ax] > 32 * o[ax] || o[ax] > 8 * in[ax]) return HMGPU_EUNSUPPORTED;
+    } else {
+      if (!i) { w = ww; h = wh; }
+      if (ww != w || wh != h) return HMGPU_EINVAL;                                            // unscaled: one size, the output's
+      if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
+    }
+  }
+  if (sc) { w = sc->width; h = sc->height; }
+  out->channels[0] = (d->components & 1) + ((d->components >> 1) & 1) + ((d->components >> 2) & 1);
+  out->elem_bytes[0] = *elem == kElemF32 ? 4 : 2;
+  out->width[0] = w; out->height[0] = h; out->row_bytes[0] = w * out->elem_bytes[0];
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_residual_plan_for(const hmgpu_seq_params* seq, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc, int32_t n,
+                                     const hmgpu_export_window windows[], hmgpu_residual_plan* out) {
+  int elem = 0;
+  const hmgpu_status st = residual_plan(seq, d, sc, n, windows, out, &elem);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// the rules of motion_dst_ok for the three slots of a residual export.  vec: bit k set when slot k may take 16-byte stores
+static hmgpu_status residual_dst_ok(const hmgpu_ctx* c, const hmgpu_residual_desc* d, const hmgpu_residual_plan& plan, int n, void* const dst[3],
+                                    const int64_t* pitch, const int64_t* pstride, const int64_t* bstride, int* vec) {
+  const bool mono = c->seq.chroma_format == 0, planes = d->form == HMGPU_RESIDUAL_PLANES;
+  bool any = false;
+  *vec = 0;
+  for (int k = 0; k < 3; k++) {
+    if (!dst[k] || (planes && mono && k)) continue;                   // (the chroma destinations of a 4:0:0 picture are ignored)
+    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
+    any = true;
+    const int64_t es = plan.elem_bytes[k];
+    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    int64_t pic = plane;
+    if (!planes) {
+      if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48) || pstride[k] % es) return HMGPU_EINVAL;
+      pic = pstride[k] * (plan.channels[k] - 1) + plane;
+    }
+    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % es || pitch[k] % es || bstride[k] % es) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % 16 == 0 && pitch[k] % 16 == 0 && bstride[k] % 16 == 0 && (planes || pstride[k] % 16 == 0)) *vec |= 1 << k;
+  }
+  return any ? HMGPU_OK : HMGPU_EINVAL;
+}
+
+hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc,
+                                              const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
+                                              const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_residual_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  return residual_dst_ok(c, d, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+}
+
+hmgpu_status hmgpu_pictures_residual_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
+  return hmgpu_pictures_motion_check(c, n, pics);                      // the same record: every CTU covered by decompress calls
+}
+
+hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_residual_desc* d,
+                                            const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst[3],
+                                            const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3],
+                                            const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!c || !pics || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  hmgpu_residual_plan plan;
+  int elem = 0, vec = 0;
+  // (the format's refusal comes first: it does not depend on the pictures)
+  { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = hmgpu_pictures_residual_check(c, n, pics); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  { const hmgpu_status st = residual_dst_ok(c, d, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  const bool mono = c->seq.chroma_format == 0, planes = d->form == HMGPU_RESIDUAL_PLANES;
+  ResidArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.mono = mono; a.comps = mono ? d->components & 1 : d->components;
+  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
+  for (int k = 0; k < 3; k++) a.rtw[k] = (c->grid_w / 2) >> (k ? c->csx : 0);
+  for (int i = 0; i < n; i++) {
+    const Picture& pic = c->pics[pics[i]];
+    const PicDev& p = pic.dev;
+    ResidSrc& s = a.src[i];
+    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.tr_idx = p.tr_idx; s.ipcm = p.ipcm;
+    for (int k = 0; k < 3; k++) { s.cbf[k] = p.cbf[k]; s.resid[k] = p.resid[k]; }
+    // intra CUs carry a residual only when EVERY call that covers the picture came with intra_dir[]: a picture whose slice calls
+    // disagree exports its intra CUs as 0 (k_prep listed no TU for those of the calls without the modes: their tiles are stale)
+    bool dir = !pic.calls.empty();
+    for (const SliceCall& sc : pic.calls) dir = dir && sc.dir;
+    s.gate = (dir ? kResidIntra : 0) | (pic.flags_staged ? kResidFlags : 0);
+  }
+  for (int k = 0; k < 3; k++) {
+    if (!dst[k] || (planes && mono && k)) continue;
+    a.dst[k] = static_cast<uint8_t*>(dst[k]);
+    a.pitch[k] = pitch_bytes[k]; a.pstride[k] = planes ? 0 : plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
+  }
+  a.vec = vec;
+  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
+  if (planes) {
+    a.x0 = d->crop[0]; a.y0 = d->crop[2]; a.w = c->seq.width - d->crop[0] - d->crop[1]; a.h = c->seq.height - d->crop[2] - d->crop[3];
+    if (a.x0 & 15) a.vec &= 1;                       // a chroma lane's eight samples are aligned in the picture, not in the crop
+    launch_residual_planes(a, hs);
+  } else {
+    a.W = plan.width[0]; a.H = plan.height[0];
+    int ch = 0;
+    for (int k = 0; k < 3; k++) { a.chan[k] = ch; if ((d->components >> k) & 1) ch++; a.scale[k] = d->scale[k]; }
+    for (int i = 0; i < n; i++) {
+      const int* cr = windows[i].crop;
+      ResidWin& w = a.win[i];
+      w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
+      a.flip |= (uint32_t)(windows[i].flip & 1) << i;
+    }
+    launch_residual_dense(a, elem, hs);
+  }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
 }  // extern "C"

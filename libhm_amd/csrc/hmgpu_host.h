@@ -17,7 +17,7 @@ using namespace hmgpu;
 
 enum { K_PREP = 0, K_MC_LUMA, K_MC_CHROMA, K_ITX, K_DBK_VER, K_DBK_HOR, K_SAO, K_EXTEND, K_H2D, K_INTRA, K_FILTER, K_UNPACK, K_MC_CELLS };
 
-struct SliceCall { int first_ctu, num_ctus, slice_idx; bool intra, wp, cells, bi, islice; };   // intra: the range holds intra CUs the device reconstructs; islice: mostly intra CUs;
+struct SliceCall { int first_ctu, num_ctus, slice_idx; bool intra, wp, cells, bi, islice, dir; };   // dir: the call came with intra_dir[]; intra: the range holds intra CUs the device reconstructs; islice: mostly intra CUs;
                                                                                     // cells: it holds PUs that cut an 8x8 luma tile (k_mc_cells.hip); bi: B slices
 
 struct Picture {

@@ -126,7 +126,7 @@ static hmgpu_status finish_stage(hmgpu_ctx* c, hmgpu_pic cur, int32_t slice_idx,
   for (int si : slices) { any_b |= p.slices[si].slice_type == HMGPU_B_SLICE; any_i |= p.slices[si].slice_type == HMGPU_I_SLICE; }
   // I slices, or a range at least half intra, take the intra kernel that stages whole CTUs
   if (has_intra && !any_i) any_i = 2 * n_intra >= pn;
-  SliceCall call = {first_ctu, num_ctus, slice_idx, has_intra, any_wp, cells, any_b, any_i};
+  SliceCall call = {first_ctu, num_ctus, slice_idx, has_intra, any_wp, cells, any_b, any_i, p.dev.has_intra_dir != 0};
   p.calls.push_back(call);
   p.extended = false;
   coverage_add(c, p, first_ctu, num_ctus);

@@ -1094,6 +1094,42 @@ hmgpu_status Decoder::export_motion(int n, PicData* const* pics, const hmgpu_mot
   return HMGPU_OK;
 }
 
+hmgpu_status Decoder::export_residual(int n, PicData* const* pics, const hmgpu_residual_desc* desc, const hmgpu_export_scale* scale,
+                                       const hmgpu_export_window* windows, void* const dst[3], const int64_t pitch_bytes[3],
+                                       const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
+  flush_batch();
+  for (int i = 0; i < n; i++) {
+    const PicData* p = pics[i];
+    if (!p->on_device || !p->decoded) return HMGPU_EINVAL;
+    if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
+  }
+  // as export_motion: the residual tiles and the arrays lie in the context that decoded a picture (PicData::home).  Everything is
+  // validated first -- the destination and every window once for all n slots, then every context's pictures -- then one call per run.
+  { const hmgpu_status st = hmgpu_residual_destination_check(ctx_of(pics[0]), n, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes,
+                                                             batch_stride_bytes);
+    if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, windows);
+  for (const ExportRun& r : runs) {
+    const hmgpu_status st = hmgpu_pictures_residual_check(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
+    if (st != HMGPU_OK) return st;
+  }
+  for (const ExportRun& r : runs) {
+    void* d[3];
+    int64_t bs[3];
+    for (int k = 0; k < 3; k++) {
+      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+      bs[k] = batch_stride_bytes[k] * r.step;
+    }
+    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
+    const hmgpu_status st = hmgpu_pictures_export_residual(c, r.n, r.h, desc, scale, windows ? r.w : nullptr, d, pitch_bytes, plane_stride_bytes, bs,
+                                                           on_stream, stream);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row
 bool Decoder::md5_plane_matches(const PicData* pic, int comp, int bd, const uint8_t want[16]) {
   Md5 md5;

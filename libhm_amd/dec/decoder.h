@@ -79,6 +79,10 @@ class Decoder {
                              const hmgpu_export_window* windows, void* const dst_mv[2], void* dst_ref, void* dst_block,
                              const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4],
                              int on_stream, void* stream);
+  // hmgpu_pictures_export_residual under the same rules
+  hmgpu_status export_residual(int n, PicData* const* pics, const hmgpu_residual_desc* desc, const hmgpu_export_scale* scale,
+                               const hmgpu_export_window* windows, void* const dst[3], const int64_t pitch_bytes[3],
+                               const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
   int device_of(const PicData* pic) const { return pic && pic->on_device && pic->owner == this ? devices_[pic->home] : -1; }
   uint64_t download_bytes() const { return download_bytes_; }
   int last_display_poc = -(1 << 30);

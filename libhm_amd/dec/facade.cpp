@@ -338,6 +338,16 @@ int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture*
   return static_cast<Wrapper*>(ctx)->dec.export_motion(n, p, desc, scale, windows, dst_mv, dst_ref, dst_block, pitch_bytes, plane_stride_bytes,
                                                        batch_stride_bytes, on_stream, stream);
 }
+int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_residual_desc* desc,
+                                   const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                   const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
+                                   int on_stream, void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_residual(n, p, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes,
+                                                         on_stream, stream);
+}
 int hmdec_picture_device(libHMDec_picture* pic) {
   if (!pic || !as_pic(pic)->owner) return -1;
   return static_cast<const Decoder*>(as_pic(pic)->owner)->device_of(as_pic(pic));

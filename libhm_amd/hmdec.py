@@ -82,6 +82,9 @@ def lib():
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
                                                    C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
                                                    C.c_void_p]
+        L.hmdec_pictures_export_residual.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ResidualDesc),
+                                                     C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -238,10 +241,55 @@ class Picture:
                                   [flip] if (flip or window is not None) and _form_is_dense(form) else None, dtype, None, crop)
         return {k: t[0] for k, t in out.items()}
 
+    def residual(self, form="planes", components=(0, 1, 2), size=None, window=None, flip=False, dtype=None, scale=None, crop=None):
+        """export_residual_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None.
+        window and flip belong to form="dense": with form="planes" they are refused (ValueError), as by Context.export_residual"""
+        out = export_residual_batch([self], form, components, size, None if window is None else [window],
+                                    [flip] if flip or window is not None else None, dtype, scale, None, crop)
+        return {k: t[0] for k, t in out.items()}
+
 
 def _form_is_dense(form):
     from . import motion
     return motion.form_code(form) == abi.MOTION_DENSE
+
+
+def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, out=None,
+                          crop=None, enqueue=True, n=None):
+    """The decoded residual of up to 16 pictures a decoder has put out (fetched since the last push, one sequence, one GPU:
+    hmdec_pictures_export_residual) as a dict of torch tensors with a leading batch dimension, written on
+    torch.cuda.current_stream(): libhm_amd.residual describes the forms and keys.  crop: None = the whole coded picture for
+    form="planes" and the conformance window for form="dense" (what export_batch shows: the same windows, flips and size give
+    aligned pixels, vectors and residuals), "conformance", or (left, right, top, bottom).  enqueue False / n: only the tensors of n
+    pictures are allocated (Decoder.frames)."""
+    from . import HmgpuError, residual
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("export_residual_batch: no pictures")
+    first = pictures[0]
+    if first.ctx is None:
+        raise RuntimeError("export_residual_batch: the picture does not know its decoder")
+    g = first.geometry()
+    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
+    seq.chroma_format = g["chroma_format"]
+    if crop is None:
+        crop = (0, 0, 0, 0) if residual.form_code(form) == abi.RESIDUAL_PLANES else "conformance"
+    if crop == "conformance":
+        crop = first.conformance_window()
+    dev = first.device
+    if dev < 0:
+        raise RuntimeError("export_residual_batch: the picture is not on a device (parse-only, or its sequence has ended)")
+
+    def call(desc, sc, win, ptrs, pitches, pstrides, bstrides, st):
+        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
+        w = None if win is None else (abi.ExportWindow * len(win))(*win)
+        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
+        r = lib().hmdec_pictures_export_residual(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None, w, d, q, ps,
+                                                 bs, 1, C.c_void_p(st or None))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_residual")
+    return residual.export_residual(call, seq, dev, len(pictures) if n is None else n, form, components, size, windows, flip, dtype, scale, out,
+                                    crop, enqueue)
 
 
 def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=None,
@@ -453,7 +501,7 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def frames(self, stream, batch=None, windows=None, motion=None, **export_kw):
+    def frames(self, stream, batch=None, windows=None, motion=None, residual=None, **export_kw):
         """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
         of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
         batch=N: (pocs, tensors) with up to N (<= 16) pictures per item instead, the tensors those of export_batch: slots are filled
@@ -462,13 +510,19 @@ class Decoder:
         (windows, flips) for the n pictures of one batched call (export.random_resized_crop with the picture's size bound).
         motion (batch=N only): True, or a dict of export_motion_batch arguments (form, lists, dtype, ...): the items become
         (pocs, tensors, motion dict), the motion tensors allocated and filled slot by slot like the picture tensors; with the
-        dense form the windows and flips fn(n) returned, and size=, apply to both.  motion=None leaves the items as they were."""
+        dense form the windows and flips fn(n) returned, and size=, apply to both.  motion=None leaves the items as they were.
+        residual (batch=N only): True, or a dict of export_residual_batch arguments (form, components, dtype, scale, ...): the
+        residual dict is appended to the items in the same way -- (pocs, tensors, residual dict), or (pocs, tensors, motion dict,
+        residual dict) with motion= -- and its dense form takes each call's windows, flips and size= like the pixels and the motion."""
         if windows is not None and batch is None:
             raise ValueError("frames(windows=) needs batch=")
         if motion is not None and motion is not False and batch is None:
             raise ValueError("frames(motion=) needs batch=")
+        if residual is not None and residual is not False and batch is None:
+            raise ValueError("frames(residual=) needs batch=")
         if batch is not None:
-            yield from self._frames_batched(stream, int(batch), export_kw, windows, None if motion is False else motion)
+            yield from self._frames_batched(stream, int(batch), export_kw, windows, None if motion is False else motion,
+                                            None if residual is False else residual)
             return
         nals = split_nal_units(stream)
         for i, nal in enumerate(nals):
@@ -484,7 +538,7 @@ class Decoder:
                 if not new_pic:
                     break
 
-    def _frames_batched(self, stream, batch, export_kw, windows=None, motion=None):
+    def _frames_batched(self, stream, batch, export_kw, windows=None, motion=None, residual=None):
         if not 1 <= batch <= abi.EXPORT_MAX_BATCH:
             raise ValueError("batch: 1 .. %d" % abi.EXPORT_MAX_BATCH)
         if "out" in export_kw:
@@ -504,8 +558,21 @@ class Decoder:
             if mkw["form"] == abi.MOTION_DENSE:
                 mkw.setdefault("size", kw["size"])
                 mkw.setdefault("crop", kw["crop"])
+        rkw = None
+        from . import residual as _residual
+        if residual is not None:
+            rkw = dict(form="planes") if residual is True else dict(residual)
+            for key in ("out", "windows", "flip"):
+                if key in rkw:
+                    raise ValueError("frames(residual=): no %s= in the residual dict (the items are allocated here; windows and flips come "
+                                     "from frames(windows=fn))" % key)
+            rkw["form"] = _residual.form_code(rkw.get("form", "planes"))
+            if rkw["form"] == abi.RESIDUAL_DENSE:
+                rkw.setdefault("size", kw["size"])
+                rkw.setdefault("crop", kw["crop"])
+        sides = lambda: tuple(t for t in (mitem if mkw is not None else None, ritem if rkw is not None else None) if t is not None)
         nals = split_nal_units(stream)
-        item, pocs, mitem = None, [], None
+        item, pocs, mitem, ritem = None, [], None, None
         for i, nal in enumerate(nals):
             eof = i == len(nals) - 1
             while True:
@@ -532,20 +599,20 @@ class Decoder:
                                 mitem = export_motion_batch(take[:1], enqueue=False, n=batch,
                                                             **dict(mkw, **({"windows": [mw["windows"][0]] * batch} if mw else {})))
                             export_motion_batch(take, out={k: t[len(pocs):len(pocs) + len(take)] for k, t in mitem.items()}, **mw, **mkw)
+                        if rkw is not None:
+                            rw = wkw if rkw["form"] == abi.RESIDUAL_DENSE else {}
+                            if ritem is None:
+                                ritem = export_residual_batch(take[:1], enqueue=False, n=batch,
+                                                              **dict(rkw, **({"windows": [rw["windows"][0]] * batch} if rw else {})))
+                            export_residual_batch(take, out={k: t[len(pocs):len(pocs) + len(take)] for k, t in ritem.items()}, **rw, **rkw)
                         pocs += [p.poc for p in take]
                         if len(pocs) == batch:
-                            if mkw is None:
-                                yield pocs, _slots(item, 0, batch)
-                            else:
-                                yield pocs, _slots(item, 0, batch), mitem
-                            item, pocs, mitem = None, [], None
+                            yield (pocs, _slots(item, 0, batch)) + sides()
+                            item, pocs, mitem, ritem = None, [], None, None
                 if not new_pic:
                     break
         if pocs:
-            if mkw is None:
-                yield pocs, _slots(item, 0, len(pocs))
-            else:
-                yield pocs, _slots(item, 0, len(pocs)), {k: t[:len(pocs)] for k, t in mitem.items()}
+            yield (pocs, _slots(item, 0, len(pocs))) + tuple({k: t[:len(pocs)] for k, t in d.items()} for d in sides())
 
 
 def _slots(item, a, b):

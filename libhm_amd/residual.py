@@ -1,0 +1,118 @@
+"""Residual export to torch tensors (hmgpu_pictures_export_residual, k_residual.hip): the argument handling shared by
+Context.export_residual, hmdec.export_residual_batch and hmdec.Picture.residual.  No compute here.
+
+form "planes": int16 planes, each component at its own resolution -- {"y": [N, H, W], "cb" / "cr": [N, H / 2, W / 2]} (4:0:0: "y"
+only).  form "dense": {"residual": [N, C, H, W]}, one value per output sample of export_batch(windows=, flip=, size=,
+filter="nearest"), C the selected components in component order, int16 or a float dtype (value = float32(r) * scale[c], converted).
+The residual is what the decoder adds to the prediction; it is 0 wherever no coded transform block covers the sample.
+"""
+import ctypes as C
+
+from . import abi
+from . import export
+
+FORMS = {"planes": abi.RESIDUAL_PLANES, "dense": abi.RESIDUAL_DENSE}
+NAMES = ("y", "cb", "cr")
+
+
+def components_mask(components):
+    """(0, 1, 2) -> 7; an int is taken as the mask"""
+    if isinstance(components, int):
+        return components
+    mask = 0
+    for c in components:
+        if c not in (0, 1, 2):
+            raise ValueError("components: 0, 1 and / or 2")
+        mask |= 1 << c
+    return mask
+
+
+def form_code(form):
+    try:
+        return form if isinstance(form, int) else FORMS[form.lower()]
+    except KeyError:
+        raise ValueError("unknown residual form %r (planes or dense)" % (form,))
+
+
+def plan_for(seq, desc, scale=None, windows=None, n=None):
+    """what an export with `desc` writes (hmgpu_residual_plan_for: host code, no GPU); windows: abi.ExportWindow per picture (dense)"""
+    from . import HmgpuError, lib
+    plan = abi.ResidualPlan()
+    windows = None if windows is None else list(windows)
+    w = None if windows is None else (abi.ExportWindow * max(len(windows), 1))(*windows)
+    count = n if n is not None else (len(windows) if windows is not None else 1)
+    st = lib().hmgpu_residual_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None, count, w, C.byref(plan))
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_residual_plan_for")
+    return plan
+
+
+def describe(seq, n, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0)):
+    """(desc, abi.ExportScale or None, windows or None) of a call; dtype: None (int16), a torch float dtype or an abi.SAMPLE_* code"""
+    form = form_code(form)
+    mask = components_mask(components)
+    if form == abi.RESIDUAL_PLANES:
+        if size is not None or windows is not None or flip is not None or dtype is not None or scale is not None:
+            raise ValueError("export_residual(form='planes') takes crop only: size / windows / flip / dtype / scale belong to form='dense'")
+        return abi.make_residual_desc(form, mask, abi.SAMPLE_UINT, crop), None, None
+    st = abi.SAMPLE_UINT if dtype is None else dtype if isinstance(dtype, int) else export.sample_type(dtype)
+    if scale is not None and st == abi.SAMPLE_UINT:
+        raise ValueError("scale needs a float dtype")
+    desc = abi.make_residual_desc(form, mask, st, scale=(1.0, 1.0, 1.0) if scale is None else tuple(scale))
+    l, r, t, b = (int(v) for v in crop)
+    win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * n, flip, n)
+    return desc, export.make_scale(size, "nearest"), win
+
+
+def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0),
+                  n=None):
+    """what Context.export_residual with these arguments writes per picture (hmgpu_residual_plan_for: host code, no GPU): an
+    abi.ResidualPlan -- per destination slot the channels, width, height, element size and row bytes.  n: the number of pictures
+    (default: one per window, else 1)"""
+    count = n if n is not None else (len(list(windows)) if windows is not None else 1)
+    desc, sc, win = describe(seq, count, form, components, size, windows, flip, dtype, scale, crop)
+    return plan_for(seq, desc, sc, win, count)
+
+
+def export_residual(call, seq, device, n, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None,
+                    out=None, crop=(0, 0, 0, 0), enqueue=True):
+    """allocate with torch on `device` (or take the tensors of the dict `out`: only its keys are written) and run
+    call(desc, scale, windows, ptrs[3], pitches[3], plane_strides[3], batch_strides[3], stream) on torch's current stream."""
+    import torch
+    desc, sc, win = describe(seq, n, form, components, size, windows, flip, dtype, scale, crop)
+    plan = plan_for(seq, desc, sc, win, n)
+    planes = desc.form == abi.RESIDUAL_PLANES
+    elem = torch.int16 if desc.sample_type == abi.SAMPLE_UINT else dtype
+    if isinstance(elem, int):
+        elem = {abi.SAMPLE_F16: torch.float16, abi.SAMPLE_BF16: torch.bfloat16, abi.SAMPLE_F32: torch.float32}[elem]
+    names = {k: NAMES[k] for k in range(3) if plan.channels[k]} if planes else {0: "residual"}
+
+    def shape(k):
+        return (n, plan.height[k], plan.width[k]) if planes else (n, plan.channels[k], plan.height[k], plan.width[k])
+    with torch.cuda.device(device):
+        if out is None:
+            dev = torch.device("cuda", device)
+            out = {name: torch.empty(shape(k), dtype=elem, device=dev) for k, name in names.items()}
+        for key in out:
+            if key not in names.values():
+                raise ValueError("out: no tensor %r in this export (one of %s)" % (key, ", ".join(sorted(names.values()))))
+        ptrs, pitches, pstrides, bstrides = [None] * 3, [0] * 3, [0] * 3, [0] * 3
+        for k, name in names.items():
+            t = out.get(name)
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape(k) or t.dtype != elem or t.get_device() != device:
+                raise ValueError("out[%r]: a %s tensor of shape %s on device %d" % (name, elem, shape(k), device))
+            st, es = t.stride(), t.element_size()
+            if st[-1] != 1:
+                raise ValueError("out[%r]: elements dense within a row (stride %s)" % (name, st))
+            ptrs[k], pitches[k], bstrides[k] = t.data_ptr(), st[-2] * es, st[0] * es
+            pstrides[k] = 0 if planes else st[1] * es
+        if enqueue:
+            call(desc, sc, win, ptrs, pitches, pstrides, bstrides, torch.cuda.current_stream(device).cuda_stream)
+    return out
+
+
+def c_args(ptrs, pitches, pstrides, bstrides):
+    """the ctypes arguments (dst[3], pitch[3], plane stride[3], batch stride[3]) of the C entry points"""
+    return ((C.c_void_p * 3)(*ptrs), (C.c_int64 * 3)(*pitches), (C.c_int64 * 3)(*pstrides), (C.c_int64 * 3)(*bstrides))
