@@ -90,6 +90,7 @@ typedef struct hmgpu_export_desc hmgpu_export_desc;
 typedef struct hmgpu_export_scale hmgpu_export_scale;
 typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 typedef struct hmgpu_export_window hmgpu_export_window;
+typedef struct hmgpu_export_pixel hmgpu_export_pixel;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 #endif
@@ -114,6 +115,14 @@ int hmdec_pictures_export_windows(libHMDec_context* ctx, int n, libHMDec_picture
                                   const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
                                   void* stream);
+/* hmdec_pictures_export as packed pixels (hmgpu_pictures_export_pixels: RGB / BGR / RGBA / BGRA / ARGB / ABGR into the one destination
+ * dst, pixel x of row y of picture i at dst + i * batch_stride_bytes + y * pitch_bytes; windows NULL or one per picture), under the
+ * same rules.  Where the pictures sit in several device contexts of the GPU the destination, the pixel description and every window
+ * are validated once for the whole batch (hmgpu_export_pixels_destination_check), then each run of slots carries its own windows. */
+int hmdec_pictures_export_pixels(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                 const hmgpu_export_pixel* pixel, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int on_stream,
+                                 void* stream);
 /* Motion vectors, reference POCs and block information of up to 16 pictures in one call (hmgpu_pictures_export_motion: the BLOCKS
  * grid or the DENSE per-sample form; destinations, strides and statuses as there), under the validity rule of hmdec_pictures_export:
  * every picture put out by this decoder and fetched since the last push, of one sequence and on one GPU ordinal, else HMGPU_EINVAL

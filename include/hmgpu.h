@@ -421,6 +421,54 @@ hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* ctx, int32_t n, c
                                                     const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                                     void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ packed pixel export
+ * The RGB layout as packed pixels: one destination whose pixels hold C = 3 (RGB, BGR) or 4 (RGBA, BGRA, ARGB, ABGR)
+ * elements side by side -- [H, W, C] images, [N, H, W, C] batches, which are also the bytes of a channels-last [N, C, H, W] tensor.
+ * No arithmetic of its own: let P be the three planes slot i receives from the existing call with the same `desc`, `scale` and
+ * `tensor` -- hmgpu_pictures_export_windows with `windows`, else hmgpu_pictures_export with the crop of desc->crop -- with the
+ * msb_aligned shift, the float map fl(fl(v * scale[k]) + bias[k]) and the mirror.  Element c of pixel (y, x) of slot i is
+ * P[chan(order, c)][y][x], stored at
+ *   dst + i * batch_stride_bytes + y * pitch_bytes + (x * C + c) * ES,   ES the element size of the tensor plan.
+ * tensor->scale[k] / bias[k] belong to the colour (k = 0 R, 1 G, 2 B), not to the position inside the pixel; a mirrored row is
+ * reversed pixel by pixel, the channels of a pixel in place.  The A element of the 4-channel orders is one value for the call:
+ *   unsigned elements: alpha << (msb_aligned ? 16 - D : 0), D the output depth; alpha = -1 stands for 2^D - 1 (opaque), and a value
+ *                      outside -1 .. 2^D - 1 gives HMGPU_EINVAL;
+ *   float elements:    alpha_value converted like a sample (round to nearest even, overflow to infinity); a value that is not
+ *                      finite gives HMGPU_EINVAL.
+ * The three-channel orders ignore both fields.
+ * desc->layout must be HMGPU_EXPORT_RGB (else HMGPU_EINVAL).  The plan has one plane: width[0] / height[0] in pixels, row_bytes[0] =
+ * width * C * ES (pixels of 3, 4, 6, 8, 12 or 16 bytes), and the coef of the planar RGB plan.  Validation is that of the planar call,
+ * made by the same code, with the same statuses and in the same order -- the descriptor, scale, tensor and every window, the limits
+ * of the scaled export, n, the handles, the destination (one plane of row_bytes[0]: pitch, batch stride, the span inside one
+ * allocation of the context's device), the stream -- and after the plan of the planar call: the layout, then an unknown `order` or
+ * a non-zero reserved word, then the alpha rules, each HMGPU_EINVAL; `pixel` NULL is HMGPU_EINVAL.  Everything is validated before
+ * anything is enqueued and a refused call leaves the destination untouched.  The table slots, the per-call ring of window buffers,
+ * the stream ordering (one event pair in, one out, when on_stream is 1) and the one launch per call are those of the planar calls.
+ * A full group of 4 pixels whose first byte is 4-byte aligned (dst, pitch_bytes and batch_stride_bytes multiples of 4) is written
+ * with dword stores, any other element by element; no byte beyond row_bytes[0] of a row is written.  The launch is not accounted
+ * in hmgpu_stats. */
+enum { HMGPU_PIXEL_RGB = 0, HMGPU_PIXEL_BGR = 1, HMGPU_PIXEL_RGBA = 2, HMGPU_PIXEL_BGRA = 3, HMGPU_PIXEL_ARGB = 4, HMGPU_PIXEL_ABGR = 5 };
+typedef struct hmgpu_export_pixel {
+  int32_t order;               /* HMGPU_PIXEL_* */
+  int32_t alpha;               /* unsigned elements, 4-channel orders: code value 0 .. 2^D - 1 of A; -1 = 2^D - 1 (opaque) */
+  float   alpha_value;         /* float elements, 4-channel orders: A = convert(alpha_value); must be finite */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_export_pixel;
+/* validates and reports what hmgpu_pictures_export_pixels writes per slot; host code, no device needed.  windows NULL: the crop of
+ * desc->crop (n is not looked at); else n windows under the rules of hmgpu_export_windows_plan_for */
+hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          const hmgpu_export_tensor* tensor, int32_t n, const hmgpu_export_window windows[],
+                                          const hmgpu_export_pixel* pixel, hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                          const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                          const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel, void* dst,
+                                          int64_t pitch_bytes, int64_t batch_stride_bytes, int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_pixels */
+hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                                   const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* pixel, void* dst, int64_t pitch_bytes,
+                                                   int64_t batch_stride_bytes);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

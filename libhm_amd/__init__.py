@@ -105,6 +105,15 @@ def lib():
         L.hmgpu_export_windows_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                              C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
                                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_export_pixels_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportTensor), C.c_int32, C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_pixels.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+        L.hmgpu_export_pixels_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                            C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                            C.POINTER(abi.ExportPixel), C.c_void_p, C.c_int64, C.c_int64]
         L.hmgpu_motion_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale), C.c_int32,
                                             C.POINTER(abi.ExportWindow), C.POINTER(abi.MotionPlan)]
         L.hmgpu_pictures_export_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MotionDesc),
@@ -217,6 +226,22 @@ def export_windows_plan(seq, desc, scale, tensor, windows):
                                              C.byref(tensor) if tensor is not None else None, len(windows), w, C.byref(plan))
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_windows_plan_for")
+    return plan
+
+
+def export_pixels_plan(seq, desc, scale, tensor, windows, pixel):
+    """what a packed-pixel export writes per slot (hmgpu_export_pixels_plan_for: host code, no GPU): one plane of [H, W, C] pixels;
+    windows: None (desc.crop) or a sequence of abi.ExportWindow; pixel: an abi.ExportPixel"""
+    plan = abi.ExportPlan()
+    w = None
+    if windows is not None:
+        windows = list(windows)
+        w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+    st = lib().hmgpu_export_pixels_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
+                                            C.byref(tensor) if tensor is not None else None, len(windows) if windows is not None else 1, w,
+                                            C.byref(pixel) if pixel is not None else None, C.byref(plan))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_export_pixels_plan_for")
     return plan
 
 
@@ -422,6 +447,30 @@ class Context:
                                               C.byref(tensor) if tensor is not None else None, p, q, b, on_stream, C.c_void_p(stream or None)),
                   "hmgpu_pictures_export")
 
+    def export_pixels_into(self, pics, desc, pixel, ptr, pitch, bstride, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
+        """hmgpu_pictures_export_pixels into device memory the caller owns: pixel x of row y of picture i at
+        ptr + i * bstride + y * pitch (bytes); pixel: an abi.ExportPixel; windows: None or one abi.ExportWindow per picture"""
+        pics = list(pics)
+        h = (C.c_int32 * max(len(pics), 1))(*pics)
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        self._chk(lib().hmgpu_pictures_export_pixels(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
+                                                     C.byref(tensor) if tensor is not None else None, w,
+                                                     C.byref(pixel) if pixel is not None else None, C.c_void_p(ptr or None), pitch, bstride,
+                                                     on_stream, C.c_void_p(stream or None)), "hmgpu_pictures_export_pixels")
+
+    def export_pixels_destination_status(self, n, desc, pixel, ptr, pitch, bstride, scale=None, tensor=None, windows=None):
+        """hmgpu_export_pixels_destination_check: the status hmgpu_pictures_export_pixels would give this destination; enqueues nothing"""
+        w = None
+        if windows is not None:
+            windows = list(windows)
+            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
+        return lib().hmgpu_export_pixels_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None,
+                                                           C.byref(tensor) if tensor is not None else None, w,
+                                                           C.byref(pixel) if pixel is not None else None, C.c_void_p(ptr or None), pitch, bstride)
+
     def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
         """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
         p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
@@ -443,10 +492,11 @@ class Context:
                                                             C.byref(tensor) if tensor is not None else None, w, p, q, b)
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
-               size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+               size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
-        gives normalised float elements (export_batch with one picture, without the batch dimension)"""
+        gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
+        "bgra", "argb", "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels instead, alpha the A element (None: opaque)"""
         from . import export
 
         def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
@@ -456,10 +506,13 @@ class Context:
             extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
             self.export_batch_into([pic], desc, ptrs, pitches, extent, 1 if on_stream else 0, st, sc, tensor)
         return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
-                                     filter, out, None, dtype, mean, std, scale, bias)
+                                     filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha,
+                                     pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, 1 if on_stream else 0, st, sc, tensor))
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
-                     size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None):
+                     size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
+                     pixel=None, alpha=None, memory_format=None):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -468,14 +521,20 @@ class Context:
         windows: one (x, y, w, h) per picture, luma samples relative to `crop`: the part of the picture slot i shows, resized to
         `size` (size None: all of one (w, h), the output's); flip: one boolean per picture (None: none), the slot mirrored left to
         right.  Still one launch (hmgpu_pictures_export_windows): random-resized-crop and random flip per sample
-        (export.random_resized_crop)."""
+        (export.random_resized_crop).
+        pixel ("rgb", "bgr", "rgba", "bgra", "argb", "abgr"; layout "rgb"): ONE tensor [N, H, W, C] of packed pixels instead
+        (hmgpu_pictures_export_pixels), alpha the A element (None: opaque; an integer code value, or a float for float dtypes).
+        memory_format=torch.channels_last (layout "rgb", no pixel): a [N, 3, H, W] tensor whose strides are channels-last, the bytes
+        of pixel="rgb".  out: either form, its pixels dense."""
         from . import export
         pics = list(pics)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
                                      self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
-                                     out, len(pics), dtype, mean, std, scale, bias, win)
+                                     out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
+                                     pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, 1 if on_stream else 0, st, sc, tensor, win))
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

@@ -140,6 +140,20 @@ def make_export_window(crop, flip=False):
     return w
 
 
+PIXEL_RGB, PIXEL_BGR, PIXEL_RGBA, PIXEL_BGRA, PIXEL_ARGB, PIXEL_ABGR = range(6)
+
+
+class ExportPixel(C.Structure):
+    _fields_ = [("order", C.c_int32), ("alpha", C.c_int32), ("alpha_value", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+def make_export_pixel(order, alpha=-1, alpha_value=1.0):
+    """order: PIXEL_*; alpha: the A code value of unsigned elements (-1: opaque); alpha_value: the A of float elements"""
+    p = ExportPixel()
+    p.order, p.alpha, p.alpha_value = int(order), int(alpha), float(alpha_value)
+    return p
+
+
 MOTION_BLOCKS, MOTION_DENSE = 0, 1
 MOTION_NO_REF = -(1 << 31)
 MOTION_DST_MV0, MOTION_DST_MV1, MOTION_DST_REF, MOTION_DST_BLOCK, MOTION_DSTS = 0, 1, 2, 3, 4

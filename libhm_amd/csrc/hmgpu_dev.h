@@ -304,24 +304,28 @@ constexpr int kMaxExportBatch = 16;
 // convert(v * scale[k] + bias[k]) of the integer v (two binary32 roundings, then round to nearest even)
 enum { kElemU8 = 0, kElemU16 = 1, kElemF16 = 2, kElemBF16 = 3, kElemF32 = 4 };
 template <int ELEM> constexpr int elem_bytes() { return ELEM == kElemU8 ? 1 : ELEM == kElemF32 ? 4 : 2; }
-// n (<= 4) consecutive elements of one plane from the integers v; full groups of an aligned export as one 4-, 8- or 16-byte store.
-// Float elements: the product and the sum are rounded separately (no contraction into an fma), overflow gives infinity, denormals stay.
+// one element from the integer v.  Float elements: the product and the sum are rounded separately (no contraction into an fma),
+// overflow gives infinity, denormals stay.
+template <int ELEM>
+__device__ inline uint32_t export_conv(uint32_t v, int msb, float sc, float bi) {
+  if constexpr (ELEM <= kElemU16) {
+    return v << msb;
+  } else {
+#pragma clang fp contract(off)
+    const float m = (float)(int)v * sc;
+    const float f = m + bi;
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if constexpr (ELEM == kElemF32) return u;
+    else if constexpr (ELEM == kElemF16) return __builtin_bit_cast(uint16_t, (_Float16)f);
+    else return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;      // bfloat16, nearest even (f is never a NaN: v, sc and bi are finite)
+  }
+}
+// n (<= 4) consecutive elements of one plane from the integers v (export_conv); full groups of an aligned export as one 4-, 8- or
+// 16-byte store.
 template <int ELEM>
 __device__ inline void export_store4(uint8_t* d, const uint32_t v[4], int n, bool vec, int msb, float sc, float bi) {
   uint32_t o[4];
-  for (int i = 0; i < 4; i++) {
-    if constexpr (ELEM <= kElemU16) {
-      o[i] = v[i] << msb;
-    } else {
-#pragma clang fp contract(off)
-      const float m = (float)(int)v[i] * sc;
-      const float f = m + bi;
-      const uint32_t u = __builtin_bit_cast(uint32_t, f);
-      if constexpr (ELEM == kElemF32) o[i] = u;
-      else if constexpr (ELEM == kElemF16) o[i] = __builtin_bit_cast(uint16_t, (_Float16)f);
-      else o[i] = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;      // bfloat16, nearest even (f is never a NaN: v, sc and bi are finite)
-    }
-  }
+  for (int i = 0; i < 4; i++) o[i] = export_conv<ELEM>(v[i], msb, sc, bi);
   constexpr int B = elem_bytes<ELEM>();
   if (vec && n == 4) {
     if constexpr (B == 1) stg(reinterpret_cast<uint32_t*>(d), o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24);
@@ -367,6 +371,75 @@ __device__ inline void export_store_pairs(uint8_t* row, int x, int cw, const uin
   export_store4<ELEM>(d, r, min(4, 2 * n), vv, msb, 0.f, 0.f);
   if (n > 2) export_store4<ELEM>(d + 4 * elem_bytes<ELEM>(), r + 4, 2 * n - 4, vv, msb, 0.f, 0.f);
 }
+// packed pixels (k_export_px.hip, k_export_scale.hip; include/hmgpu.h "packed pixel export"): the channel order as two launch-uniform
+// flags, the A element's bits, and whether dst, the pitch and the batch stride are multiples of 4 bytes (dword stores possible)
+struct PxOrder {
+  int32_t swap;                    // B first, R third (BGR, BGRA, ABGR)
+  int32_t afirst;                  // 4 channels: A before the colours (ARGB, ABGR)
+  uint32_t abits;                  // 4 channels: the A element as stored (host: the container shift, or the float conversion)
+  uint32_t vst;
+};
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+// the group of n (<= 4) pixels at column x of a packed row of w pixels, NCH (3, 4) elements each, from the integers R, G, B of the
+// group (export_conv per colour: scale / bias belong to the colour, not to the position).  flip: the row is mirrored pixel by pixel
+// (export_store_row's rule, the channels of a pixel in place).  A full group whose first byte is dword aligned (vst: dst, pitch and
+// batch stride are) goes out as 4 * NCH * element bytes of dword stores, 12 .. 64 contiguous bytes; any other element by element.
+// Never writes beyond pixel w - 1.
+template <int ELEM, int NCH>
+__device__ inline void export_store_px(uint8_t* row, int x, int w, const uint32_t R[4], const uint32_t G[4], const uint32_t B[4], int n,
+                                       bool vst, bool flip, int mrb, int mg, const float sc[3], const float bi[3], const PxOrder& po) {
+  constexpr int EB = elem_bytes<ELEM>();
+  uint32_t e[4][NCH];
+  for (int i = 0; i < 4; i++) {
+    const uint32_t r = export_conv<ELEM>(flip ? R[3 - i] : R[i], mrb, sc[0], bi[0]);
+    const uint32_t g = export_conv<ELEM>(flip ? G[3 - i] : G[i], mg, sc[1], bi[1]);
+    const uint32_t b = export_conv<ELEM>(flip ? B[3 - i] : B[i], mrb, sc[2], bi[2]);
+    const uint32_t c0 = po.swap ? b : r, c2 = po.swap ? r : b;
+    if constexpr (NCH == 3) {
+      e[i][0] = c0; e[i][1] = g; e[i][2] = c2;
+    } else {
+      e[i][0] = po.afirst ? po.abits : c0; e[i][1] = po.afirst ? c0 : g;
+      e[i][2] = po.afirst ? g : c2; e[i][NCH - 1] = po.afirst ? c2 : po.abits;
+    }
+  }
+  if (flip && n < 4) {                                         // a partial group: its pixels are the last n of e
+    for (int c = 0; c < NCH; c++) {
+      if (n == 3) { e[0][c] = e[1][c]; e[1][c] = e[2][c]; e[2][c] = e[3][c]; }
+      else if (n == 2) { e[0][c] = e[2][c]; e[1][c] = e[3][c]; }
+      else e[0][c] = e[3][c];
+    }
+  }
+  const int xs = flip ? w - x - n : x;
+  const ptrdiff_t off = (ptrdiff_t)xs * (NCH * EB);
+  uint8_t* d = row + off;
+  if (vst && n == 4 && !(off & 3)) {
+    constexpr int DW = NCH * EB, PER = 4 / EB;                  // dwords of the group, elements per dword
+    uint32_t q[DW];
+    for (int k = 0; k < DW; k++) {
+      q[k] = 0;
+      for (int j = 0; j < PER; j++) {
+        const int f = k * PER + j;
+        q[k] |= e[f / NCH][f % NCH] << (8 * EB * j);
+      }
+    }
+    for (int k = 0; k + 4 <= DW; k += 4) {
+      u32x4_a4 v; v.x = q[k]; v.y = q[k + 1]; v.z = q[k + 2]; v.w = q[k + 3];
+      *(u32x4_a4 HMGPU_AS1*)(d + 4 * k) = v;
+    }
+    constexpr int T = DW & ~3;
+    if constexpr (DW - T == 3) { u32x3_a4 v; v.x = q[T]; v.y = q[T + 1]; v.z = q[T + 2]; *(u32x3_a4 HMGPU_AS1*)(d + 4 * T) = v; }
+    if constexpr (DW - T == 2) { u32x2_a4 v; v.x = q[T]; v.y = q[T + 1]; *(u32x2_a4 HMGPU_AS1*)(d + 4 * T) = v; }
+    return;
+  }
+  for (int i = 0; i < n; i++)
+    for (int c = 0; c < NCH; c++) {
+      if constexpr (EB == 1) stg(d + i * NCH + c, (uint8_t)e[i][c]);
+      else if constexpr (EB == 2) stg(reinterpret_cast<uint16_t*>(d) + i * NCH + c, (uint16_t)e[i][c]);
+      else stg(reinterpret_cast<uint32_t*>(d) + i * NCH + c, e[i][c]);
+    }
+}
 struct ExportArgs {
   const int16_t* y[kMaxExportBatch];   // per picture: luma sample (crop left, crop top)
   const int16_t* c[kMaxExportBatch];   // Cb of chroma sample (crop left >> csx, crop top >> csy) in the pair plane (Cr one element on)
@@ -386,6 +459,9 @@ struct ExportArgs {
   int32_t coef[16];                // hmgpu_export_plan.coef
 };
 void launch_export(const ExportArgs& a, hipStream_t s);
+// the RGB export of `a` as packed pixels (k_export_px.hip): one destination, dst[0] / pitch[0] / bstride[0]; a.vec: the loads only;
+// nch: 3 or 4 elements per pixel
+void launch_export_px(const ExportArgs& a, const PxOrder& po, int nch, hipStream_t s);
 // scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
 // memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
 // tap-major (w[tap * n + i], zero beyond count[i])
@@ -421,9 +497,10 @@ struct ScaleArgs {
   int64_t bstride[3];              // bytes between the planes of consecutive pictures
   float scale[3], bias[3];         // float elements: per output plane
   int32_t coef[16];                // hmgpu_export_plan.coef
+  PxOrder px;                      // packed pixels (nch below): dst[0] / pitch[0] / bstride[0] the one destination, vec = px.vst
 };
-// n pictures; elem: kElem*
-void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s);
+// n pictures; elem: kElem*; nch: 0, or (RGB) 3 / 4 elements per packed pixel
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch = 0);
 // motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
 // arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
 // dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.

@@ -1,6 +1,6 @@
 // hmgpu_export.hip -- device export of the host runtime: the export plans, scale tables and their slots, window tables, destination
-// checks, export_impl behind the four picture export entry points, and the motion / block export (k_export.hip, k_export_scale.hip,
-// k_motion.hip).
+// checks, export_impl behind the five picture export entry points, and the motion / block export (k_export.hip, k_export_px.hip,
+// k_export_scale.hip, k_motion.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -700,11 +700,77 @@ hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, con
   return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
 }
 
+// packed pixels (include/hmgpu.h "packed pixel export"): `plan`, the planar RGB plan of the call already validated, becomes the
+// one-plane plan of the packed destination; po: the channel order and the A element as the kernels take them
+static hmgpu_status pixel_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int elem, const hmgpu_export_pixel* px,
+                               hmgpu_export_plan* plan, PxOrder* po) {
+  hmgpu_export_plan p = *plan;
+  memset(plan, 0, sizeof(*plan));
+  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (px->order < HMGPU_PIXEL_RGB || px->order > HMGPU_PIXEL_ABGR) return HMGPU_EINVAL;
+  for (int k = 0; k < 5; k++) if (px->reserved[k]) return HMGPU_EINVAL;
+  const int C = px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
+  memset(po, 0, sizeof(*po));
+  po->swap = px->order == HMGPU_PIXEL_BGR || px->order == HMGPU_PIXEL_BGRA || px->order == HMGPU_PIXEL_ABGR;
+  po->afirst = px->order == HMGPU_PIXEL_ARGB || px->order == HMGPU_PIXEL_ABGR;
+  if (C == 4 && elem <= kElemU16) {
+    const int D = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+    if (px->alpha < -1 || px->alpha > (1 << D) - 1) return HMGPU_EINVAL;
+    po->abits = (uint32_t)(px->alpha < 0 ? (1 << D) - 1 : px->alpha) << (d->msb_aligned ? 16 - D : 0);
+  } else if (C == 4) {
+    const float f = px->alpha_value;
+    if (!std::isfinite(f)) return HMGPU_EINVAL;
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if (elem == kElemF16) { const _Float16 h = (_Float16)f; uint16_t b; memcpy(&b, &h, 2); u = b; }
+    else if (elem == kElemBF16) u = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    po->abits = u;
+  }
+  p.planes = 1;
+  p.row_bytes[0] = p.width[0] * C * elem_size(elem);
+  for (int k = 1; k < 3; k++) p.width[k] = p.height[k] = p.row_bytes[k] = 0;
+  *plan = p;
+  return HMGPU_OK;
+}
+
+// the plan of a packed call: the planar call's own (windows_plan / tensor_plan), then pixel_plan
+static hmgpu_status pixels_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
+                                int n, const hmgpu_export_window* win, const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
+  if (!seq || !d || !px || !out) return HMGPU_EINVAL;
+  int elem = 0;
+  bool differ = false;
+  PxOrder po;
+  const hmgpu_status st = win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+  return st != HMGPU_OK ? st : pixel_plan(seq, d, elem, px, out, &po);
+}
+
+hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[],
+                                          const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
+  return pixels_plan(seq, d, sc, t, n, windows, px, out);
+}
+
+hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !px) return HMGPU_EINVAL;
+  hmgpu_export_plan plan;
+  { const hmgpu_status st = pixels_plan(&c->seq, d, sc, t, n, windows, px, &plan); if (st != HMGPU_OK) return st; }
+  hipSetDevice(c->device);
+  bool vec = true;
+  int64_t bs[3];
+  void* const dst3[3] = {dst, nullptr, nullptr};
+  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
+  return export_dst_ok(c, plan, 1, n, dst3, pitch3, bstride3, &vec, bs);
+}
+
 // every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; bstride null: one picture, no batch
-// stride to check; win null: desc->crop for every picture, no mirror.  One launch, the stream ordering once.
+// stride to check; win null: desc->crop for every picture, no mirror; px: packed pixels, dst[0] the one destination.  One launch, the
+// stream ordering once.
 static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
                                 const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
-                                int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr) {
+                                int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr,
+                                const hmgpu_export_pixel* px = nullptr) {
   if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   hmgpu_export_plan plan;
@@ -727,11 +793,16 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem);
     if (st != HMGPU_OK) return st;
   }
+  PxOrder po;
+  if (px) { const hmgpu_status st = pixel_plan(&c->seq, d, elem, px, &plan, &po); if (st != HMGPU_OK) return st; }
+  const int nch = !px ? 0 : px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
   hipSetDevice(c->device);
   const int ES = elem_size(elem);
   bool vec = true;
   int64_t bs[3] = {0, 0, 0};
   { const hmgpu_status st = export_dst_ok(c, plan, ES, n, dst, pitch_bytes, bstride, &vec, bs); if (st != HMGPU_OK) return st; }
+  // packed pixels: a full group is a run of dwords where the destination is dword aligned; the loads have their own condition
+  if (px) po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || bs[0] % 4 == 0);
   hipStream_t hs = c->stream;
   { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
@@ -748,7 +819,7 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
       const int x0 = differ ? win[i].crop[0] : d->crop[0], y0 = differ ? win[i].crop[2] : d->crop[2];
       a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
       a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
-      if (vec && (x0 & 3) == 0) a.vec |= 1u << i;                         // (a batch may mix aligned and unaligned left edges)
+      if ((vec || px) && (x0 & 3) == 0) a.vec |= 1u << i;                 // (a batch may mix aligned and unaligned left edges)
     }
     a.flip = flip;
     a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
@@ -765,7 +836,8 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
       if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
     }
     memcpy(a.coef, plan.coef, sizeof(a.coef));
-    launch_export(a, hs);
+    if (px) launch_export_px(a, po, nch, hs);
+    else launch_export(a, hs);
     return export_end(c, n, pics, on_stream, hs);
   }
   if (differ) s = shapes[0];                         // (the output size and the depths are those of every window)
@@ -806,7 +878,8 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   a.maxv[0] = (1 << s.depth[0]) - 1; a.maxv[1] = (1 << (rgb ? s.depth[0] : s.depth[1])) - 1;
   a.msb[0] = d->msb_aligned ? 16 - s.depth[0] : 0; a.msb[1] = d->msb_aligned ? 16 - (rgb ? s.depth[0] : s.depth[1]) : 0;
   a.e = plan.coef[11];
-  a.vec = vec ? 1 : 0;
+  a.vec = px ? (int)po.vst : vec ? 1 : 0;
+  if (px) a.px = po;
   for (int k = 0; k < 3; k++) {
     a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
     a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
@@ -814,7 +887,7 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
   }
   memcpy(a.coef, plan.coef, sizeof(a.coef));
-  launch_export_scaled(a, d->layout, elem, n, hs);
+  launch_export_scaled(a, d->layout, elem, n, hs, nch);
   if (wbuf) {
     HIP_TRY(c, hipEventRecord(wbuf->done, hs));
     wbuf->pending = true;
@@ -848,6 +921,15 @@ hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_
                                            const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
   if (!batch_stride_bytes || !windows) return HMGPU_EINVAL;
   return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
+}
+
+hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int32_t on_stream, void* stream) {
+  if (!px) return HMGPU_EINVAL;
+  void* const dst3[3] = {dst, nullptr, nullptr};
+  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
+  return export_impl(c, n, pics, d, sc, t, dst3, pitch3, bstride3, on_stream, stream, windows, px);
 }
 
 // ------------------------------------------------------------------------------------------------ motion and block export (k_motion.hip)

@@ -13,7 +13,8 @@
 //      to sums it keeps in registers.
 // After the last pass the sums are rounded, clipped and stored, 4 or 8 bytes per plane and lane where aligned.  No intermediate
 // leaves the workgroup.  One instance per layout and output element (hmgpu_dev.h export_store4); the class, and the channels with
-// it, is uniform per workgroup.
+// it, is uniform per workgroup.  Packed pixels (hmgpu_pictures_export_pixels): an instance family of the RGB layout whose epilogue
+// writes the lane's four columns x 3 or 4 elements as one run of bytes (hmgpu_dev.h export_store_px).
 // Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
 // margin on both sides, and the tables never point at them.
 #include "hmgpu_dev.h"
@@ -30,8 +31,8 @@ __device__ inline void unpack8(const u32x4 w, int v[8]) {
   for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(w[i] & 0xffff); v[2 * i + 1] = (int16_t)(w[i] >> 16); }
 }
 
-// C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane
-template <int LAYOUT, int ELEM, int C>
+// C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane; NCH: 0, or (C = 3) the elements of a packed pixel
+template <int LAYOUT, int ELEM, int C, int NCH = 0>
 __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds) {
   constexpr int BYTES = elem_bytes<ELEM>();
   constexpr int G = C == 2 ? 4 : 8;                       // samples per 16-byte group
@@ -173,7 +174,10 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
   const int x = ox0 + vx, y = oy0 + vy, n = min(4, k.tx.n - x);
   const bool vec = a.vec != 0, flip = (a.flip >> pic) & 1;    // the mirror: columns x .. x + 3 reversed to W - 1 - x ..
   const int W = k.tx.n;
-  if constexpr (C != 2) {
+  if constexpr (NCH != 0) {                   // packed pixels: the lane's four columns as one run of bytes
+    export_store_px<ELEM, NCH>(a.dst[0] + pic * a.bstride[0] + y * a.pitch[0], x, W, o[0], o[1], o[C - 1], n, vec, flip, msb, msb,
+                               a.scale, a.bias, a.px);
+  } else if constexpr (C != 2) {
     for (int c = 0; c < C; c++)
       export_store_row<ELEM>(a.dst[c] + pic * a.bstride[c] + y * a.pitch[c], x, W, o[c], n, vec, flip, msb, a.scale[c], a.bias[c]);
   } else if (LAYOUT == HMGPU_EXPORT_PLANAR) {
@@ -187,7 +191,7 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
 
 }  // namespace
 
-template <int LAYOUT, int ELEM>
+template <int LAYOUT, int ELEM, int NCH = 0>
 __global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
   __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
   const int b = blockIdx.x;
@@ -195,13 +199,25 @@ __global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
   // the class as this picture sees it: the call's own, or (windows that differ) the picture's from device memory, a wave-uniform load
   ScaleClass k = a.cls[c];
   if (a.pic_cls) k = a.pic_cls[2 * blockIdx.y + c];
-  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3>(a, k, b, lds);
+  if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3, NCH>(a, k, b, lds);
   else if (c == 0) scale_tile<LAYOUT, ELEM, 1>(a, k, b, lds);
   else scale_tile<LAYOUT, ELEM, 2>(a, k, b - a.cls[0].blocks, lds);
 }
 
-void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s) {
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch) {
   const dim3 grid((unsigned)(a.cls[0].blocks + (layout == HMGPU_EXPORT_RGB ? 0 : a.cls[1].blocks)), (unsigned)n), block(256);
+  if (nch) {                                  // packed pixels (RGB only)
+#define HMGPU_SCALE_PX_CASE(E) \
+    if (elem == E && nch == 3) hipLaunchKernelGGL((k_export_scale<HMGPU_EXPORT_RGB, E, 3>), grid, block, 0, s, a); \
+    if (elem == E && nch == 4) hipLaunchKernelGGL((k_export_scale<HMGPU_EXPORT_RGB, E, 4>), grid, block, 0, s, a);
+    HMGPU_SCALE_PX_CASE(kElemU8)
+    HMGPU_SCALE_PX_CASE(kElemU16)
+    HMGPU_SCALE_PX_CASE(kElemF16)
+    HMGPU_SCALE_PX_CASE(kElemBF16)
+    HMGPU_SCALE_PX_CASE(kElemF32)
+#undef HMGPU_SCALE_PX_CASE
+    return;
+  }
 #define HMGPU_SCALE_CASE(L, E) \
   if (layout == L && elem == E) hipLaunchKernelGGL((k_export_scale<L, E>), grid, block, 0, s, a);
   HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemU8)

@@ -1026,7 +1026,8 @@ std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_expo
 
 hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows) {
+                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
+                                       const hmgpu_export_pixel* pixel) {
   if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
   flush_batch();
@@ -1037,7 +1038,8 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
   }
   // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
   // one hmgpu_pictures_export per run of slots (export_runs).
-  { const hmgpu_status st = windows ? hmgpu_export_windows_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, dst, pitch_bytes, batch_stride_bytes)
+  { const hmgpu_status st = pixel ? hmgpu_export_pixels_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, dst[0], pitch_bytes[0], batch_stride_bytes[0])
+                          : windows ? hmgpu_export_windows_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, dst, pitch_bytes, batch_stride_bytes)
                                     : hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
     if (st != HMGPU_OK) return st; }
   for (const ExportRun& r : export_runs(n, pics, windows)) {
@@ -1048,7 +1050,8 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
       bs[k] = batch_stride_bytes[k] * r.step;
     }
     hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
-    const hmgpu_status st = windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
+    const hmgpu_status st = pixel ? hmgpu_pictures_export_pixels(c, r.n, r.h, desc, scale, tensor, windows ? r.w : nullptr, pixel, d[0], pitch_bytes[0], bs[0], on_stream, stream)
+                          : windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
                                     : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
     if (st != HMGPU_OK) return st;
   }

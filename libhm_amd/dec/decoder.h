@@ -70,10 +70,12 @@ class Decoder {
   hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, void* const dst[3], const int64_t pitch_bytes[3],
                               int on_stream, void* stream);
   // hmgpu_pictures_export of pictures put out and still valid: one sequence, one GPU ordinal; one call per device context that holds some.
-  // windows: nullptr, or one per picture (hmgpu_pictures_export_windows; each run of slots carries its own)
+  // windows: nullptr, or one per picture (hmgpu_pictures_export_windows; each run of slots carries its own); pixel: nullptr, or packed
+  // pixels (hmgpu_pictures_export_pixels: dst[0], pitch_bytes[0] and batch_stride_bytes[0] the one destination)
   hmgpu_status export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                               const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr);
+                               const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr,
+                               const hmgpu_export_pixel* pixel = nullptr);
   // hmgpu_pictures_export_motion under the rules of export_pictures; the side information lies in the context that decoded a picture
   hmgpu_status export_motion(int n, PicData* const* pics, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
                              const hmgpu_export_window* windows, void* const dst_mv[2], void* dst_ref, void* dst_block,

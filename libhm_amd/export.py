@@ -16,6 +16,8 @@ from . import abi
 LAYOUTS = {"planar": abi.EXPORT_PLANAR, "yuv": abi.EXPORT_PLANAR, "semiplanar": abi.EXPORT_SEMIPLANAR, "nv12": abi.EXPORT_SEMIPLANAR,
            "rgb": abi.EXPORT_RGB}
 UNSPECIFIED = 2
+PIXELS = {"rgb": abi.PIXEL_RGB, "bgr": abi.PIXEL_BGR, "rgba": abi.PIXEL_RGBA, "bgra": abi.PIXEL_BGRA, "argb": abi.PIXEL_ARGB,
+          "abgr": abi.PIXEL_ABGR}
 FILTERS = {"nearest": abi.SCALE_NEAREST, "nearest-exact": abi.SCALE_NEAREST, "bilinear": abi.SCALE_BILINEAR, "bicubic": abi.SCALE_BICUBIC,
            "area": abi.SCALE_AREA}
 
@@ -251,20 +253,106 @@ def alloc_outputs(plan, desc, device, n=None, dtype=None):
     return tuple(torch.empty(lead + shape, dtype=dt, device=dev) for shape in plane_shapes(plan, desc))
 
 
+def make_pixel(pixel, alpha, memory_format, layout, dtype, n):
+    """the abi.ExportPixel of pixel= / alpha= / memory_format= (None when none is given: the planar call).  pixel: a name of PIXELS
+    or an abi.PIXEL_* code; alpha: None (opaque: the largest code value, 1.0 for float elements), else the A element -- an integer
+    code value for unsigned elements, a number for float ones; memory_format: None or torch.channels_last (the batch calls, no
+    pixel: the bytes of pixel "rgb")"""
+    import torch
+    if pixel is None and memory_format is None:
+        if alpha is not None:
+            raise ValueError("alpha needs pixel=")
+        return None
+    if layout_code(layout) != abi.EXPORT_RGB:
+        raise ValueError("pixel / memory_format need layout=\"rgb\"")
+    if memory_format is not None:
+        if memory_format != torch.channels_last:
+            raise ValueError("memory_format: None or torch.channels_last")
+        if pixel is not None or alpha is not None:
+            raise ValueError("memory_format=torch.channels_last is a [N, 3, H, W] tensor: no pixel= / alpha= with it")
+        if n is None:
+            raise ValueError("memory_format belongs to the batch calls")
+        return abi.make_export_pixel(abi.PIXEL_RGB)
+    if isinstance(pixel, str):
+        if pixel.lower() not in PIXELS:
+            raise ValueError("unknown pixel order %r (one of %s)" % (pixel, ", ".join(sorted(PIXELS))))
+        pixel = PIXELS[pixel.lower()]
+    if alpha is None:
+        return abi.make_export_pixel(pixel)
+    if dtype is None:
+        if int(alpha) != alpha:
+            raise ValueError("alpha: an integer code value for unsigned elements")
+        return abi.make_export_pixel(pixel, alpha=int(alpha))
+    return abi.make_export_pixel(pixel, alpha_value=float(alpha))
+
+
+def pixel_channels(px):
+    return 3 if px.order in (abi.PIXEL_RGB, abi.PIXEL_BGR) else 4
+
+
+def alloc_pixels(plan, desc, px, device, n=None, dtype=None, channels_last=False):
+    """a torch tensor for the packed plan: [H, W, C], with n [N, H, W, C]; channels_last: that memory seen as [N, C, H, W]"""
+    import torch
+    dt = torch_dtype(desc.bytes_per_sample) if dtype is None else dtype
+    lead = () if n is None else (n,)
+    t = torch.empty(lead + (plan.height[0], plan.width[0], pixel_channels(px)), dtype=dt, device=torch.device("cuda", device))
+    return t.permute(0, 3, 1, 2) if channels_last else t
+
+
+def out_pixels(out, plan, desc, px, device, n=None, dtype=None):
+    """a caller's packed destination as (pointer, pitch in bytes, batch stride in bytes or None).  n None: [H, W, C]; n pictures:
+    [n, H, W, C], or [n, C, H, W] with channels-last strides.  The planned shape and dtype on the device, the pixels dense (the
+    elements of a pixel and the pixels of a row side by side); rows and batch entries may be any stride apart (e.g. clip[:, t] of a
+    [N, T, H, W, C] tensor).  Reads only shapes, strides and pointers: no views are made."""
+    import torch
+    h, w, c = plan.height[0], plan.width[0], pixel_channels(px)
+    lead = () if n is None else (n,)
+    b = len(lead)
+    if not isinstance(out, torch.Tensor):
+        raise ValueError("out: packed pixels take one tensor")
+    st = out.stride()
+    if out.shape == lead + (h, w, c):
+        sy, sx, sc = st[b:]
+    elif b and out.shape == lead + (c, h, w):
+        sc, sy, sx = st[b:]
+    else:
+        raise ValueError("out: shape %s, the plan gives %s%s" % (tuple(out.shape), lead + (h, w, c), " or %s channels-last" % (lead + (c, h, w),) if b else ""))
+    _check_tensor(out, desc, device, dtype)
+    if sc != 1 or sx != c or sy < w * c or (b and st[0] < sy * (h - 1) + w * c):
+        raise ValueError("out: the pixels must be dense within a row, rows and batch entries apart (stride %s)" % (st,))
+    es = out.element_size()
+    return out.data_ptr(), sy * es, st[0] * es if b else None
+
+
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
-                   filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None):
+                   filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None,
+                   pixel=None, alpha=None, memory_format=None, pixel_call=None):
     """allocate with torch on `device` (or take `out`) and run `call(desc, scale, tensor, ptrs, pitches, bstrides, stream)` on torch's
     current stream.  scale: None (size None), else the abi.ExportScale of size (height, width) and filter; tensor: None (dtype None),
     else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); bstrides: None for one picture
     (n None), else the bytes between the batch entries of every plane of the n pictures.  windows: None, or the abi.ExportWindow of
-    every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0)."""
+    every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0).
+    pixel / alpha / memory_format (make_pixel): packed pixels, ONE tensor [H, W, C] ([N, H, W, C]; channels-last [N, 3, H, W]) through
+    `pixel_call(desc, scale, tensor, pixel, ptr, pitch, bstride, stream)`; bstride of one picture: the extent of its rows."""
     import torch
-    from . import export_tensor_plan, export_windows_plan
+    from . import export_pixels_plan, export_tensor_plan, export_windows_plan
+    px = make_pixel(pixel, alpha, memory_format, layout, dtype, n)
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
     desc = make_desc(layout, bit_depth, crop if windows is None else (0, 0, 0, 0), matrix, full_range, msb_aligned,
                      seq if dtype is not None else None)
     sc = make_scale(size, filter)
     tensor = make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias)
+    if px is not None:
+        plan = export_pixels_plan(seq, desc, sc, tensor, windows, px)
+        with torch.cuda.device(device):
+            if out is None:
+                out = alloc_pixels(plan, desc, px, device, n, dtype, memory_format is not None)
+            ptr, pitch, bstride = out_pixels(out, plan, desc, px, device, n, dtype)
+            if bstride is None:
+                bstride = pitch * (plan.height[0] - 1) + plan.row_bytes[0]
+            stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
+            pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, stream)
+        return out
     plan = export_tensor_plan(seq, desc, sc, tensor) if windows is None else export_windows_plan(seq, desc, sc, tensor, windows)
     with torch.cuda.device(device):
         if out is None:

@@ -78,6 +78,9 @@ def lib():
         L.hmdec_pictures_export_windows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
                                                     C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_pixels.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_pictures_export_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MotionDesc),
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
                                                    C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
@@ -225,15 +228,18 @@ class Picture:
             raise HmgpuError(st, name)
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None):
+               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
         VUI (the colour policy of libhm_amd.export); size: (height, width) of the output, resized with `filter` ("nearest",
         "bilinear", "bicubic", "area"), None = the crop's size; out: a tensor (or tuple of planes) of the planned shape to write
         instead of new ones; dtype: torch.float16 / bfloat16 / float32 gives normalised float elements (export_batch with one
-        picture, without the batch dimension; mean / std / scale / bias as there).  Valid until the next push into the decoder."""
-        return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias)
+        picture, without the batch dimension; mean / std / scale / bias as there); pixel ("rgb", "bgr", "rgba", "bgra", "argb",
+        "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels, alpha its A element (None: opaque).  Valid until the next push
+        into the decoder."""
+        return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias,
+                       pixel=pixel, alpha=alpha)
 
     def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
         """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
@@ -330,10 +336,11 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
 
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
-            scale=None, bias=None, enqueue=True, windows=None, flip=None):
+            scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
     the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
-    windows / flip: per picture, relative to crop (export.make_windows)"""
+    windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
+    (export.make_pixel, hmdec_pictures_export_pixels)"""
     from . import HmgpuError, export, export_tensor_plan
     first = pictures[0]
     if first.ctx is None:
@@ -375,22 +382,36 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
                                         C.byref(tensor) if tensor is not None else None, p, q, b, 1, C.c_void_p(st or None))
         if r != 0:
             raise HmgpuError(r, "hmdec_pictures_export")
+    def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
+        if not enqueue:
+            return None
+        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
+        w = (abi.ExportWindow * len(win))(*win) if win is not None else None
+        r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
+                                               C.byref(tensor) if tensor is not None else None, w, C.byref(px), C.c_void_p(ptr or None), pitch,
+                                               bstride, 1, C.c_void_p(st or None))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_pixels")
     return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,
-                                 dtype, mean, std, scale, bias, win)
+                                 dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
+                                 pixel_call=pixel_call)
 
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-                 filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None):
+                 filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
+                 pixel=None, alpha=None, memory_format=None):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
     of Picture.export (crop and colour are taken from the first picture) and of libhm_amd.Context.export_batch (dtype, mean, std;
-    windows: one (x, y, w, h) per picture relative to crop, flip: one boolean per picture -- hmdec_pictures_export_windows)."""
+    windows: one (x, y, w, h) per picture relative to crop, flip: one boolean per picture -- hmdec_pictures_export_windows;
+    pixel / alpha: one [N, H, W, C] tensor of packed pixels, memory_format=torch.channels_last: [N, 3, H, W] with channels-last
+    strides -- hmdec_pictures_export_pixels)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
-                   scale, bias, windows=windows, flip=flip)
+                   scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format)
 
 
 class Decoder:
