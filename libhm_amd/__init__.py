@@ -209,8 +209,7 @@ def export_scaled_plan(seq, desc, scale):
 def export_tensor_plan(seq, desc, scale=None, tensor=None):
     """what an export writes (hmgpu_export_tensor_plan_for: host code, no GPU): scale None = unscaled, tensor None = unsigned integers"""
     plan = abi.ExportPlan()
-    st = lib().hmgpu_export_tensor_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
-                                            C.byref(tensor) if tensor is not None else None, C.byref(plan))
+    st = lib().hmgpu_export_tensor_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor), C.byref(plan))
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_tensor_plan_for")
     return plan
@@ -221,9 +220,8 @@ def export_windows_plan(seq, desc, scale, tensor, windows):
     sequence of abi.ExportWindow (desc.crop 0)"""
     plan = abi.ExportPlan()
     windows = list(windows)
-    w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-    st = lib().hmgpu_export_windows_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
-                                             C.byref(tensor) if tensor is not None else None, len(windows), w, C.byref(plan))
+    st = lib().hmgpu_export_windows_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor), len(windows),
+                                             abi.window_array(windows), C.byref(plan))
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_windows_plan_for")
     return plan
@@ -233,13 +231,9 @@ def export_pixels_plan(seq, desc, scale, tensor, windows, pixel):
     """what a packed-pixel export writes per slot (hmgpu_export_pixels_plan_for: host code, no GPU): one plane of [H, W, C] pixels;
     windows: None (desc.crop) or a sequence of abi.ExportWindow; pixel: an abi.ExportPixel"""
     plan = abi.ExportPlan()
-    w = None
-    if windows is not None:
-        windows = list(windows)
-        w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-    st = lib().hmgpu_export_pixels_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None,
-                                            C.byref(tensor) if tensor is not None else None, len(windows) if windows is not None else 1, w,
-                                            C.byref(pixel) if pixel is not None else None, C.byref(plan))
+    windows = None if windows is None else list(windows)
+    st = lib().hmgpu_export_pixels_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                            len(windows) if windows is not None else 1, abi.window_array(windows), abi.ref(pixel), C.byref(plan))
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_pixels_plan_for")
     return plan
@@ -249,15 +243,10 @@ def motion_plan(seq, form="blocks", lists=(0, 1), size=None, windows=None, flip=
     """what Context.export_motion with these arguments writes per picture (hmgpu_motion_plan_for: host code, no GPU): an
     abi.MotionPlan -- per destination slot (abi.MOTION_DST_*) the channels, width, height, element size and row bytes.  dtype: a
     torch float dtype, or an abi.SAMPLE_* code (dense; None: float32).  n: the number of pictures (default: one per window, else 1)"""
-    from . import export, motion
-    code = motion.form_code(form)
-    if code == abi.MOTION_BLOCKS:
-        return motion.plan_for(seq, abi.make_motion_desc(code, motion.lists_mask(lists), abi.SAMPLE_UINT, crop), n=1 if n is None else n)
-    st = abi.SAMPLE_F32 if dtype is None else dtype if isinstance(dtype, int) else export.sample_type(dtype)
-    count = n if n is not None else (len(list(windows)) if windows is not None else 1)
-    l, r, t, b = (int(v) for v in crop)
-    win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * count, flip, count)
-    return motion.plan_for(seq, abi.make_motion_desc(code, motion.lists_mask(lists), st), export.make_scale(size, "nearest"), win, count)
+    from . import motion
+    count = n if n is not None else (len(list(windows)) if windows is not None and motion.form_code(form) == abi.MOTION_DENSE else 1)
+    desc, sc, win = motion.describe(seq, count, form, lists, size, windows, flip, dtype, crop, strict=False)
+    return motion.plan_for(seq, desc, sc, win, count)
 
 
 def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0),
@@ -420,76 +409,49 @@ class Context:
     def export_into(self, pic, desc, ptrs, pitches, on_stream=0, stream=0, scale=None):
         """hmgpu_picture_export (scale: an abi.ExportScale, hmgpu_picture_export_scaled) into device memory the caller owns:
         ptrs / pitches (bytes) per plane"""
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        p, q = abi.ptr_array(ptrs), abi.i64_array(pitches)
         if scale is None:
-            self._chk(lib().hmgpu_picture_export(self._h, pic, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmgpu_picture_export")
+            self._chk(lib().hmgpu_picture_export(self._h, pic, C.byref(desc), p, q, on_stream, abi.addr(stream)), "hmgpu_picture_export")
         else:
-            self._chk(lib().hmgpu_picture_export_scaled(self._h, pic, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None)),
+            self._chk(lib().hmgpu_picture_export_scaled(self._h, pic, C.byref(desc), C.byref(scale), p, q, on_stream, abi.addr(stream)),
                       "hmgpu_picture_export_scaled")
 
     def export_batch_into(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
         """hmgpu_pictures_export into device memory the caller owns: plane k of picture i at ptrs[k] + i * bstrides[k] (bytes);
         windows: one abi.ExportWindow per picture (hmgpu_pictures_export_windows, desc.crop 0)"""
         pics = list(pics)
-        h = (C.c_int32 * max(len(pics), 1))(*pics)
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        head = (self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale), abi.ref(tensor))
+        tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), on_stream, abi.addr(stream))
         if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-            self._chk(lib().hmgpu_pictures_export_windows(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
-                                                          C.byref(tensor) if tensor is not None else None, w, p, q, b, on_stream,
-                                                          C.c_void_p(stream or None)), "hmgpu_pictures_export_windows")
-            return
-        self._chk(lib().hmgpu_pictures_export(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
-                                              C.byref(tensor) if tensor is not None else None, p, q, b, on_stream, C.c_void_p(stream or None)),
-                  "hmgpu_pictures_export")
+            self._chk(lib().hmgpu_pictures_export_windows(*head, abi.window_array(windows), *tail), "hmgpu_pictures_export_windows")
+        else:
+            self._chk(lib().hmgpu_pictures_export(*head, *tail), "hmgpu_pictures_export")
 
     def export_pixels_into(self, pics, desc, pixel, ptr, pitch, bstride, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
         """hmgpu_pictures_export_pixels into device memory the caller owns: pixel x of row y of picture i at
         ptr + i * bstride + y * pitch (bytes); pixel: an abi.ExportPixel; windows: None or one abi.ExportWindow per picture"""
         pics = list(pics)
-        h = (C.c_int32 * max(len(pics), 1))(*pics)
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        self._chk(lib().hmgpu_pictures_export_pixels(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None,
-                                                     C.byref(tensor) if tensor is not None else None, w,
-                                                     C.byref(pixel) if pixel is not None else None, C.c_void_p(ptr or None), pitch, bstride,
-                                                     on_stream, C.c_void_p(stream or None)), "hmgpu_pictures_export_pixels")
+        self._chk(lib().hmgpu_pictures_export_pixels(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                                     abi.window_array(windows), abi.ref(pixel), abi.addr(ptr), pitch, bstride, on_stream,
+                                                     abi.addr(stream)), "hmgpu_pictures_export_pixels")
 
     def export_pixels_destination_status(self, n, desc, pixel, ptr, pitch, bstride, scale=None, tensor=None, windows=None):
         """hmgpu_export_pixels_destination_check: the status hmgpu_pictures_export_pixels would give this destination; enqueues nothing"""
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        return lib().hmgpu_export_pixels_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None,
-                                                           C.byref(tensor) if tensor is not None else None, w,
-                                                           C.byref(pixel) if pixel is not None else None, C.c_void_p(ptr or None), pitch, bstride)
+        return lib().hmgpu_export_pixels_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
+                                                           abi.ref(pixel), abi.addr(ptr), pitch, bstride)
 
     def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
         """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
-        return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None,
-                                                    C.byref(tensor) if tensor is not None else None, p, q, b)
+        return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.ptr_array(ptrs),
+                                                    abi.i64_array(pitches), abi.i64_array(bstrides))
 
     def export_windows_destination_status(self, desc, ptrs, pitches, bstrides, windows, scale=None, tensor=None, n=None):
         """hmgpu_export_windows_destination_check: the status hmgpu_pictures_export_windows would give these windows (abi.ExportWindow,
         one per picture; n: another count than len(windows)) and this destination; enqueues nothing"""
         windows = list(windows)
-        w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
-        return lib().hmgpu_export_windows_destination_check(self._h, len(windows) if n is None else n, C.byref(desc),
-                                                            C.byref(scale) if scale is not None else None,
-                                                            C.byref(tensor) if tensor is not None else None, w, p, q, b)
+        return lib().hmgpu_export_windows_destination_check(self._h, len(windows) if n is None else n, C.byref(desc), abi.ref(scale),
+                                                            abi.ref(tensor), abi.window_array(windows), abi.ptr_array(ptrs),
+                                                            abi.i64_array(pitches), abi.i64_array(bstrides))
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None):
@@ -541,26 +503,15 @@ class Context:
         destination slot (abi.MOTION_DST_*: vectors 0 and 1, ref_poc, block; a pointer None / 0 = not written)"""
         from . import motion
         pics = list(pics)
-        h = (C.c_int32 * max(len(pics), 1))(*pics)
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
-        self._chk(lib().hmgpu_pictures_export_motion(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None, w,
-                                                     mv, ref, blk, q, ps, bs, on_stream, C.c_void_p(stream or None)),
-                  "hmgpu_pictures_export_motion")
+        self._chk(lib().hmgpu_pictures_export_motion(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale),
+                                                     abi.window_array(windows), *motion.c_args(ptrs, pitches, pstrides, bstrides), on_stream,
+                                                     abi.addr(stream)), "hmgpu_pictures_export_motion")
 
     def motion_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides, scale=None, windows=None):
         """hmgpu_motion_destination_check: the status hmgpu_pictures_export_motion would give this destination; enqueues nothing"""
         from . import motion
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
-        return lib().hmgpu_motion_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None, w, mv, ref, blk,
-                                                    q, ps, bs)
+        return lib().hmgpu_motion_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.window_array(windows),
+                                                    *motion.c_args(ptrs, pitches, pstrides, bstrides))
 
     def export_motion(self, pics, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=(0, 0, 0, 0),
                       on_stream=True):
@@ -582,30 +533,20 @@ class Context:
         destination slot (planes: one per component; dense: slot 0; a pointer None / 0 = not written)"""
         from . import residual
         pics = list(pics)
-        h = (C.c_int32 * max(len(pics), 1))(*pics)
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
-        self._chk(lib().hmgpu_pictures_export_residual(self._h, len(pics), h, C.byref(desc), C.byref(scale) if scale is not None else None, w,
-                                                       d, q, ps, bs, on_stream, C.c_void_p(stream or None)),
-                  "hmgpu_pictures_export_residual")
+        self._chk(lib().hmgpu_pictures_export_residual(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale),
+                                                       abi.window_array(windows), *residual.c_args(ptrs, pitches, pstrides, bstrides), on_stream,
+                                                       abi.addr(stream)), "hmgpu_pictures_export_residual")
 
     def residual_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides, scale=None, windows=None):
         """hmgpu_residual_destination_check: the status hmgpu_pictures_export_residual would give this destination; enqueues nothing"""
         from . import residual
-        w = None
-        if windows is not None:
-            windows = list(windows)
-            w = (abi.ExportWindow * max(len(windows), 1))(*windows)
-        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
-        return lib().hmgpu_residual_destination_check(self._h, n, C.byref(desc), C.byref(scale) if scale is not None else None, w, d, q, ps, bs)
+        return lib().hmgpu_residual_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.window_array(windows),
+                                                      *residual.c_args(ptrs, pitches, pstrides, bstrides))
 
     def residual_status(self, pics):
         """hmgpu_pictures_residual_check: HMGPU_OK when every picture of the list has a residual to export; enqueues nothing"""
         pics = list(pics)
-        return lib().hmgpu_pictures_residual_check(self._h, len(pics), (C.c_int32 * max(len(pics), 1))(*pics))
+        return lib().hmgpu_pictures_residual_check(self._h, len(pics), abi.handle_array(pics))
 
     def export_residual(self, pics, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None,
                         out=None, crop=(0, 0, 0, 0), on_stream=True):

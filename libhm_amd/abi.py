@@ -214,6 +214,40 @@ def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0
     return d
 
 
+# ------------------------------------------------------------------------------------------------ marshalling of the export calls
+def ref(x):
+    """an optional struct argument: byref(x), or NULL for None"""
+    return C.byref(x) if x is not None else None
+
+
+def addr(v):
+    """a pointer argument (a destination, a stream) from an integer: 0 / None is NULL"""
+    return C.c_void_p(v or None)
+
+
+def window_array(windows):
+    """the ExportWindow array of a sequence of windows (never of length 0), or NULL for None"""
+    if windows is None:
+        return None
+    windows = list(windows)
+    return (ExportWindow * max(len(windows), 1))(*windows)
+
+
+def handle_array(pics):
+    """the int32 array of a list of picture handles (never of length 0)"""
+    return (C.c_int32 * max(len(pics), 1))(*pics)
+
+
+def ptr_array(ptrs, n=3):
+    """n pointers, the missing ones NULL"""
+    return (C.c_void_p * n)(*(list(ptrs) + [None] * (n - len(ptrs))))
+
+
+def i64_array(values, n=3):
+    """n int64 (pitches, strides), the missing ones 0"""
+    return (C.c_int64 * n)(*(list(values) + [0] * (n - len(values))))
+
+
 # ------------------------------------------------------------------------------------------------ helpers
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p).value

@@ -589,16 +589,8 @@ void hmgpu_destroy(hmgpu_ctx* c) {
   if (c->hash_dev) (void)hipFree(c->hash_dev);
   for (int k = 0; k < 2; k++) if (c->xfer_ev[k]) hipEventDestroy(c->xfer_ev[k]);
   for (int k = 0; k < 2; k++) if (c->exp_ev[k]) hipEventDestroy(c->exp_ev[k]);
-  for (auto& sl : c->scale_slot) {
-    if (sl.done) hipEventDestroy(sl.done);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.host) (void)hipHostFree(sl.host);
-  }
-  for (auto& wb : c->window_buf) {
-    if (wb.done) hipEventDestroy(wb.done);
-    if (wb.dev) (void)hipFree(wb.dev);
-    if (wb.host) (void)hipHostFree(wb.host);
-  }
+  for (auto& sl : c->scale_slot) sl.release();
+  for (auto& wb : c->window_buf) wb.release();
   if (c->hash_host) (void)hipHostFree(c->hash_host);
   for (int k = 0; k < 2; k++) if (c->lane_ev[k]) hipEventDestroy(c->lane_ev[k]);
   delete c;

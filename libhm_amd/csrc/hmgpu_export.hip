@@ -1,6 +1,6 @@
-// hmgpu_export.hip -- device export of the host runtime: the export plans, scale tables and their slots, window tables, destination
-// checks, export_impl behind the five picture export entry points, and the motion / block export (k_export.hip, k_export_px.hip,
-// k_export_scale.hip, k_motion.hip).
+// hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
+// slots, window tables, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
+// and residual exports (k_export.hip, k_export_px.hip, k_export_scale.hip, k_motion.hip, k_residual.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -17,6 +17,42 @@ extern "C" {
 
 // ------------------------------------------------------------------------------------------------ device export (k_export.hip)
 static long long round_half_away(double v) { return v < 0 ? -(long long)std::floor(-v + 0.5) : (long long)std::floor(v + 0.5); }
+
+// the chroma subsampling of a chroma_format_idc
+static void chroma_shifts(int fmt, int* csx, int* csy) { *csx = fmt == 3 ? 0 : 1; *csy = fmt == 1 || fmt == 0 ? 1 : 0; }
+
+// the output depth per channel type (a 0 of the descriptor: the coding depth); RGB: the first one for both
+static void out_depths(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int ob[2]) {
+  ob[0] = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+  ob[1] = d->layout == HMGPU_EXPORT_RGB ? ob[0] : d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma;
+}
+
+static hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc) {
+  for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
+  if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+  return HMGPU_OK;
+}
+
+// the scaling limits of one axis: 16384 outputs, 32x down, 8x up
+static bool scale_ratio_ok(long long in, long long out) { return out <= 16384 && in <= 32 * out && out <= 8 * in; }
+
+// a crop of the coded picture, w x h: nothing negative, not empty, whole chroma samples, and (sc) within the limits of scaling to sc
+static hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], const hmgpu_export_scale* sc, int* w, int* h) {
+  if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
+  *w = seq->width - cr[0] - cr[1]; *h = seq->height - cr[2] - cr[3];
+  if (*w <= 0 || *h <= 0) return HMGPU_EINVAL;
+  int csx, csy;
+  chroma_shifts(seq->chroma_format, &csx, &csy);
+  if (seq->chroma_format != 0 && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;
+  if (sc && !(scale_ratio_ok(*w, sc->width) && scale_ratio_ok(*h, sc->height))) return HMGPU_EUNSUPPORTED;
+  return HMGPU_OK;
+}
+
+// a window: its own fields, then its crop
+static bool window_fields_ok(const hmgpu_export_window& win) { return !((win.flip & ~1) || win.reserved[0] || win.reserved[1] || win.reserved[2]); }
+static hmgpu_status window_ok(const hmgpu_seq_params* seq, const hmgpu_export_window& win, const hmgpu_export_scale* sc, int* w, int* h) {
+  return window_fields_ok(win) ? crop_ok(seq, win.crop, sc, w, h) : HMGPU_EINVAL;
+}
 
 // H.273 Kr / Kb of the matrix_coefficients codes the export takes (Table 4): false for any other code
 static bool matrix_kr_kb(int matrix, double* kr, double* kb) {
@@ -38,16 +74,13 @@ hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_expo
   if ((d->msb_aligned != 0 && d->msb_aligned != 1) || (d->msb_aligned && d->bytes_per_sample != 2)) return HMGPU_EINVAL;
   for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
   const bool rgb = d->layout == HMGPU_EXPORT_RGB, mono = fmt == 0;
-  const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
-  const int ob[2] = {d->bit_depth[0] ? d->bit_depth[0] : bdY, rgb ? (d->bit_depth[0] ? d->bit_depth[0] : bdY) : (d->bit_depth[1] ? d->bit_depth[1] : bdC)};
+  int csx, csy, ob[2], W, H;
+  chroma_shifts(fmt, &csx, &csy);
+  out_depths(seq, d, ob);
   const int lo = rgb ? 8 : 1;
   for (int t = 0; t < (mono && !rgb ? 1 : 2); t++)
     if (ob[t] < lo || ob[t] > 16 || (d->bytes_per_sample == 1 && ob[t] > 8)) return HMGPU_EINVAL;
-  const int* cr = d->crop;
-  if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
-  const int W = seq->width - cr[0] - cr[1], H = seq->height - cr[2] - cr[3];
-  if (W <= 0 || H <= 0) return HMGPU_EINVAL;
-  if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
   const int B = d->bytes_per_sample;
   if (rgb) {
     if (d->full_range != 0 && d->full_range != 1) return HMGPU_EINVAL;
@@ -101,8 +134,9 @@ static bool device_span_ok(const void* p, size_t bytes, int device) {
   return q >= b && q - b + bytes <= size;
 }
 
-// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device
-static hmgpu_status export_stream(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
+// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device and then waits
+// for everything enqueued for the pictures
+static hmgpu_status export_open(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
   *hs = c->stream;
   if (!on_stream) return HMGPU_OK;
   *hs = (hipStream_t)stream;
@@ -112,14 +146,8 @@ static hmgpu_status export_stream(hmgpu_ctx* c, int32_t on_stream, void* stream,
     if ((int)dev != c->device) return HMGPU_EINVAL;
   }
   for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
-  return HMGPU_OK;
-}
-
-static hmgpu_status export_begin(hmgpu_ctx* c, int32_t on_stream, hipStream_t hs) {
-  if (on_stream) {
-    HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                 // behind everything enqueued for the picture ...
-    HIP_TRY(c, hipStreamWaitEvent(hs, c->exp_ev[0], 0));                 // ... and behind what is already on the caller's stream
-  }
+  HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                   // behind everything enqueued for the picture ...
+  HIP_TRY(c, hipStreamWaitEvent(*hs, c->exp_ev[0], 0));                  // ... and behind what is already on the caller's stream
   return HMGPU_OK;
 }
 
@@ -280,29 +308,24 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
                          ScaleShape* shape, CallTabs* call_tabs = nullptr) {
   if (!seq || !d || !sc || !out) return HMGPU_EINVAL;
   memset(out, 0, sizeof(*out));
-  for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
-  if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+  { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
   hmgpu_export_plan base;
   { const hmgpu_status st = hmgpu_export_plan_for(seq, d, &base); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB, chroma = !rgb && base.planes > 1;
-  const int fmt = seq->chroma_format, csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0;
+  int csx, csy;
+  chroma_shifts(seq->chroma_format, &csx, &csy);
   if (chroma && ((sc->width & ((1 << csx) - 1)) || (sc->height & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
   ScaleShape s;
   s.classes = chroma ? 2 : 1;
   const int W = base.width[0], H = base.height[0];
-  const int bdY = seq->bit_depth_luma, bdC = seq->bit_depth_chroma;
-  s.depth[0] = d->bit_depth[0] ? d->bit_depth[0] : bdY;
-  s.depth[1] = d->bit_depth[1] ? d->bit_depth[1] : bdC;
+  out_depths(seq, d, s.depth);
   for (int k = 0; k < s.classes; k++) {
     const int sx = k ? csx : 0, sy = k ? csy : 0;
     s.in[k][0] = W >> sx; s.in[k][1] = H >> sy;
     s.out[k][0] = sc->width >> sx; s.out[k][1] = sc->height >> sy;
-    for (int ax = 0; ax < 2; ax++) {
-      const long long i = s.in[k][ax], o = s.out[k][ax];
-      if (o > 16384 || i > 32 * o || o > 8 * i) return HMGPU_EUNSUPPORTED;
-    }
+    for (int ax = 0; ax < 2; ax++) if (!scale_ratio_ok(s.in[k][ax], s.out[k][ax])) return HMGPU_EUNSUPPORTED;
   }
-  const int D = rgb ? s.depth[0] : chroma ? std::max(s.depth[0], s.depth[1]) : s.depth[0];
+  const int D = std::max(s.depth[0], s.depth[chroma ? 1 : 0]);
   const int E = 16 - D;
   int taps[2] = {0, 0};
   for (int k = 0; k < s.classes; k++) {
@@ -314,7 +337,7 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
       }
       taps[ax] = std::max(taps[ax], s.tab[k][ax]->taps);
     }
-    if (!scale_sums_fit(*s.tab[k][0], *s.tab[k][1], rgb ? s.depth[0] : s.depth[k], E)) return HMGPU_EUNSUPPORTED;
+    if (!scale_sums_fit(*s.tab[k][0], *s.tab[k][1], s.depth[k], E)) return HMGPU_EUNSUPPORTED;
   }
   *out = base;
   for (int p = 0; p < out->planes; p++) {
@@ -408,6 +431,24 @@ ScaleTiles scale_tiles(const ScaleTab& tx, const ScaleTab& ty, int outw, int out
   return z;
 }
 
+// a table buffer nobody reads any more, with room for `bytes`: waits for the export that read it last; too small, the device and host
+// pair is allocated again with `grow` bytes
+static hmgpu_status table_room(hmgpu_ctx* c, hmgpu_ctx::TableBuf* b, size_t bytes, size_t grow) {
+  if (b->pending) HIP_TRY(c, hipEventSynchronize(b->done));
+  b->pending = false;
+  if (bytes > b->cap) {
+    if (b->dev) HIP_TRY(c, hipFree(b->dev));
+    if (b->host) HIP_TRY(c, hipHostFree(b->host));
+    b->dev = b->host = nullptr;
+    b->cap = 0;
+    HIP_TRY(c, hipMalloc(&b->dev, grow));
+    HIP_TRY(c, hipHostMalloc(&b->host, grow, hipHostMallocDefault));
+    b->cap = grow;
+  }
+  if (!b->done) HIP_TRY(c, hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+  return HMGPU_OK;
+}
+
 // the slot that holds the tables of `key`: found, or filled (least recently used slot) with a copy enqueued on hs
 hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s, bool rgb, int x0c[2], const int tile[2][2], hipStream_t hs, hmgpu_ctx::ScaleSlot** out) {
   hmgpu_ctx::ScaleSlot* slot = nullptr;
@@ -419,8 +460,7 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
       if (!sl.valid) { slot = &sl; break; }
       if (sl.used < slot->used) slot = &sl;
     }
-    if (slot->pending) HIP_TRY(c, hipEventSynchronize(slot->done));   // an export in flight still reads it
-    slot->valid = slot->pending = false;
+    slot->valid = false;
     // layout: per class and axis first, count, span, weights (tap-major), each 256-byte aligned
     ScaleTiles z[2];
     size_t off[2][2][4], bytes = 0;
@@ -432,16 +472,7 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
         for (int f = 0; f < 4; f++) { off[k][ax][f] = bytes; bytes += align_up(sizes[f], 256); }
       }
     }
-    if (bytes > slot->cap) {
-      if (slot->dev) HIP_TRY(c, hipFree(slot->dev));
-      if (slot->host) HIP_TRY(c, hipHostFree(slot->host));
-      slot->dev = slot->host = nullptr;
-      slot->cap = 0;
-      HIP_TRY(c, hipMalloc(&slot->dev, bytes));
-      HIP_TRY(c, hipHostMalloc(&slot->host, bytes, hipHostMallocDefault));
-      slot->cap = bytes;
-    }
-    if (!slot->done) HIP_TRY(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+    { const hmgpu_status st = table_room(c, slot, bytes, bytes); if (st != HMGPU_OK) return st; }   // (an export in flight may still read it)
     for (int k = 0; k < s.classes; k++) {
       ScaleClass& cl = slot->cls[k];
       memset(&cl, 0, sizeof(cl));
@@ -478,7 +509,7 @@ hmgpu_status scale_slot(hmgpu_ctx* c, const int32_t key[8], const ScaleShape& s,
 // the ring and sent in one copy on hs.  tile: where the classes' tiles start (scale_tile_start); tw shrinks until the LDS of a pass
 // fits the most demanding window.  cls: tw, th, tiles_x and blocks of the call; *pic_cls: the classes in device memory.
 hmgpu_status window_tables(hmgpu_ctx* c, int n, const std::vector<ScaleShape>& shapes, const hmgpu_export_window* win, bool rgb,
-                           const int tile[2][2], hipStream_t hs, ScaleClass cls[2], const ScaleClass** pic_cls, hmgpu_ctx::WindowBuf** out) {
+                           const int tile[2][2], hipStream_t hs, ScaleClass cls[2], const ScaleClass** pic_cls, hmgpu_ctx::TableBuf** out) {
   const int classes = shapes[0].classes;
   std::vector<ScaleTiles> z((size_t)n * 2);
   for (int k = 0; k < classes; k++) {
@@ -533,21 +564,10 @@ hmgpu_status window_tables(hmgpu_ctx* c, int n, const std::vector<ScaleShape>& s
       }
     }
   }
-  hmgpu_ctx::WindowBuf* wb = &c->window_buf[c->window_next];
+  hmgpu_ctx::TableBuf* wb = &c->window_buf[c->window_next];
   c->window_next = (c->window_next + 1) % hmgpu_ctx::kWindowBufs;
-  if (wb->pending) HIP_TRY(c, hipEventSynchronize(wb->done));              // the export that read it last may still be in flight
-  wb->pending = false;
-  if (blob.size() > wb->cap) {
-    if (wb->dev) HIP_TRY(c, hipFree(wb->dev));
-    if (wb->host) HIP_TRY(c, hipHostFree(wb->host));
-    wb->dev = wb->host = nullptr;
-    wb->cap = 0;
-    const size_t cap = align_up(blob.size() + blob.size() / 2, 4096);      // (head room: the next call's windows differ)
-    HIP_TRY(c, hipMalloc(&wb->dev, cap));
-    HIP_TRY(c, hipHostMalloc(&wb->host, cap, hipHostMallocDefault));
-    wb->cap = cap;
-  }
-  if (!wb->done) HIP_TRY(c, hipEventCreateWithFlags(&wb->done, hipEventDisableTiming));
+  // (the export that read the buffer last may still be in flight; head room: the next call's windows differ)
+  { const hmgpu_status st = table_room(c, wb, blob.size(), align_up(blob.size() + blob.size() / 2, 4096)); if (st != HMGPU_OK) return st; }
   ScaleClass* pc = reinterpret_cast<ScaleClass*>(blob.data());
   for (int i = 0; i < n; i++) {
     for (int k = 0; k < classes; k++) {
@@ -589,9 +609,9 @@ static hmgpu_status export_elem(const hmgpu_seq_params* seq, const hmgpu_export_
   if (t->sample_type == HMGPU_SAMPLE_UINT) return HMGPU_OK;
   if (d->msb_aligned) return HMGPU_EINVAL;
   for (int k = 0; k < 3; k++) if (!std::isfinite(t->scale[k]) || !std::isfinite(t->bias[k])) return HMGPU_EINVAL;
-  const bool rgb = d->layout == HMGPU_EXPORT_RGB;
-  int D = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
-  if (!rgb && seq->chroma_format != 0) D = std::max(D, d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma);
+  int ob[2];
+  out_depths(seq, d, ob);
+  const int D = seq->chroma_format != 0 ? std::max(ob[0], ob[1]) : ob[0];
   if (d->bytes_per_sample != (D <= 8 ? 1 : 2)) return HMGPU_EINVAL;      // the container an unsigned export of that depth needs
   if (d->layout == HMGPU_EXPORT_SEMIPLANAR) return HMGPU_EUNSUPPORTED;
   *elem = t->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : t->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
@@ -632,7 +652,7 @@ static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export
   hmgpu_export_plan plan;
   if (shapes) shapes->clear();
   for (int i = 0; i < n; i++) {
-    if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }
+    if (!window_fields_ok(win[i])) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }
     if (i && !*differ) continue;
     hmgpu_export_desc dd = *d;
     memcpy(dd.crop, win[i].crop, sizeof(dd.crop));
@@ -660,6 +680,7 @@ hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hm
 // cleared unless every group of 4 samples of every picture may be one store; bs: the batch strides in use
 static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& plan, int ES, int n, void* const dst[3],
                                   const int64_t pitch_bytes[3], const int64_t* bstride, bool* vec, int64_t bs[3]) {
+  hipSetDevice(c->device);
   for (int k = 0; k < plan.planes; k++) {
     if (!dst[k] || pitch_bytes[k] < plan.row_bytes[k] || pitch_bytes[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
     const int64_t extent = pitch_bytes[k] * (plan.height[k] - 1) + plan.row_bytes[k];
@@ -671,33 +692,6 @@ static hmgpu_status export_dst_ok(const hmgpu_ctx* c, const hmgpu_export_plan& p
     *vec = *vec && ((uintptr_t)dst[k] % (4 * ES)) == 0 && pitch_bytes[k] % (4 * ES) == 0 && (n == 1 || bs[k] % (4 * ES) == 0);
   }
   return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
-                                            const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  hmgpu_export_plan plan;
-  int elem = 0;
-  { const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, nullptr, &elem); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  bool vec = true;
-  int64_t bs[3];
-  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
-}
-
-hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
-                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  hmgpu_export_plan plan;
-  int elem = 0;
-  bool differ = false;
-  { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, windows, &plan, nullptr, &elem, &differ); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  bool vec = true;
-  int64_t bs[3];
-  return export_dst_ok(c, plan, elem_size(elem), n, dst, pitch_bytes, batch_stride_bytes, &vec, bs);
 }
 
 // packed pixels (include/hmgpu.h "packed pixel export"): `plan`, the planar RGB plan of the call already validated, becomes the
@@ -714,7 +708,9 @@ static hmgpu_status pixel_plan(const hmgpu_seq_params* seq, const hmgpu_export_d
   po->swap = px->order == HMGPU_PIXEL_BGR || px->order == HMGPU_PIXEL_BGRA || px->order == HMGPU_PIXEL_ABGR;
   po->afirst = px->order == HMGPU_PIXEL_ARGB || px->order == HMGPU_PIXEL_ABGR;
   if (C == 4 && elem <= kElemU16) {
-    const int D = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+    int ob[2];
+    out_depths(seq, d, ob);
+    const int D = ob[0];
     if (px->alpha < -1 || px->alpha > (1 << D) - 1) return HMGPU_EINVAL;
     po->abits = (uint32_t)(px->alpha < 0 ? (1 << D) - 1 : px->alpha) << (d->msb_aligned ? 16 - D : 0);
   } else if (C == 4) {
@@ -734,8 +730,9 @@ static hmgpu_status pixel_plan(const hmgpu_seq_params* seq, const hmgpu_export_d
 }
 
 // the plan of a packed call: the planar call's own (windows_plan / tensor_plan), then pixel_plan
-static hmgpu_status pixels_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
-                                int n, const hmgpu_export_window* win, const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
+hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
   if (!seq || !d || !px || !out) return HMGPU_EINVAL;
   int elem = 0;
   bool differ = false;
@@ -744,103 +741,164 @@ static hmgpu_status pixels_plan(const hmgpu_seq_params* seq, const hmgpu_export_
   return st != HMGPU_OK ? st : pixel_plan(seq, d, elem, px, out, &po);
 }
 
-hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[],
-                                          const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
-  return pixels_plan(seq, d, sc, t, n, windows, px, out);
+// what every picture export resolves its arguments to before anything is enqueued, and what the destination checks stop at: the
+// plan, the element, the shapes of a scaled call, the pixel order, and the destination checked against the plan
+namespace {
+struct ExportCall {
+  hmgpu_export_plan plan;
+  hmgpu_export_desc d;                               // the descriptor; windows that are all equal: with that window as its crop
+  int elem = 0, nch = 0;                             // nch: elements per packed pixel (0: planes)
+  bool differ = false;                               // the windows are not all equal
+  uint32_t flip = 0;
+  ScaleShape s;                                      // scaled: the output size and the depths (those of every window)
+  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
+  PxOrder po;
+  bool vec = true;
+  int64_t bs[3] = {0, 0, 0};
+};
+}  // namespace
+
+// bstride null: one picture, no batch stride to check; win null: desc->crop for every picture, no mirror; px: packed pixels, dst[0]
+// the one destination; shapes: the export itself asks (a check needs none)
+static hmgpu_status export_resolve(hmgpu_ctx* c, int n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
+                                   const hmgpu_export_window* win, const hmgpu_export_pixel* px, void* const dst[3],
+                                   const int64_t pitch_bytes[3], const int64_t* bstride, bool shapes, ExportCall* r) {
+  if (win) {
+    const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, win, &r->plan, shapes ? &r->shapes : nullptr, &r->elem, &r->differ);
+    if (st != HMGPU_OK) return st;
+    for (int i = 0; i < n; i++) r->flip |= (uint32_t)(win[i].flip & 1) << i;
+    if (sc && shapes) r->s = r->shapes[0];
+  } else {
+    const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &r->plan, shapes ? &r->s : nullptr, &r->elem);
+    if (st != HMGPU_OK) return st;
+  }
+  r->d = *d;
+  if (win && !r->differ) memcpy(r->d.crop, win[0].crop, sizeof(r->d.crop));
+  if (px) {
+    const hmgpu_status st = pixel_plan(&c->seq, d, r->elem, px, &r->plan, &r->po);
+    if (st != HMGPU_OK) return st;
+    r->nch = px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
+  }
+  { const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs); if (st != HMGPU_OK) return st; }
+  // packed pixels: a full group is a run of dwords where the destination is dword aligned; the loads have their own condition
+  if (px) r->po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || r->bs[0] % 4 == 0);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                            const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  return export_resolve(c, n, d, sc, t, nullptr, nullptr, dst, pitch_bytes, batch_stride_bytes, false, &r);
+}
+
+hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  // (!windows: export_resolve would take null windows for a call without windows and check the wrong plan)
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !windows || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  return export_resolve(c, n, d, sc, t, windows, nullptr, dst, pitch_bytes, batch_stride_bytes, false, &r);
 }
 
 hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
                                                    const hmgpu_export_pixel* px, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes) {
   if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !px) return HMGPU_EINVAL;
-  hmgpu_export_plan plan;
-  { const hmgpu_status st = pixels_plan(&c->seq, d, sc, t, n, windows, px, &plan); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  bool vec = true;
-  int64_t bs[3];
   void* const dst3[3] = {dst, nullptr, nullptr};
   const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
-  return export_dst_ok(c, plan, 1, n, dst3, pitch3, bstride3, &vec, bs);
+  ExportCall r;
+  return export_resolve(c, n, d, sc, t, windows, px, dst3, pitch3, bstride3, false, &r);
 }
 
-// every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; bstride null: one picture, no batch
-// stride to check; win null: desc->crop for every picture, no mirror; px: packed pixels, dst[0] the one destination.  One launch, the
-// stream ordering once.
-static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+}  // extern "C"
+
+// what ExportArgs and ScaleArgs share behind their sources: the depth rule, the destination, the float conversion, the plan's constants
+template <class Args>
+static void export_args_tail(Args& a, const hmgpu_seq_params& seq, const ExportCall& r, const hmgpu_export_tensor* t, void* const dst[3],
+                             const int64_t pitch_bytes[3]) {
+  int ob[2];
+  out_depths(&seq, &r.d, ob);
+  a.flip = r.flip;
+  a.sh[0] = ob[0] - seq.bit_depth_luma; a.sh[1] = ob[1] - seq.bit_depth_chroma;
+  for (int k = 0; k < 2; k++) { a.maxv[k] = (1 << ob[k]) - 1; a.msb[k] = r.d.msb_aligned ? 16 - ob[k] : 0; }
+  for (int k = 0; k < 3; k++) {
+    a.dst[k] = k < r.plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
+    a.pitch[k] = k < r.plan.planes ? pitch_bytes[k] : 0;
+    a.bstride[k] = r.bs[k];
+    if (r.elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
+  }
+  memcpy(a.coef, r.plan.coef, sizeof(a.coef));
+}
+
+// the destinations of a side-information export, `slots` of them, a null one not written: element alignment, strides against the extents
+// they step over (pstride null: one plane per slot), and the whole span of n pictures inside one allocation of the context's device,
+// which it makes the current one.
+// vec: bit k set when slot k may take stores of `granule` bytes (0: four elements)
+template <class Plan>
+static hmgpu_status strided_dst_ok(const hmgpu_ctx* c, const Plan& plan, int slots, int n, void* const* dst, const int64_t* pitch,
+                                   const int64_t* pstride, const int64_t* bstride, int granule, int* vec) {
+  hipSetDevice(c->device);
+  bool any = false;
+  *vec = 0;
+  for (int k = 0; k < slots; k++) {
+    if (!dst[k]) continue;
+    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
+    any = true;
+    const int64_t es = plan.elem_bytes[k], g = granule ? granule : 4 * es;
+    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    int64_t pic = plane;
+    if (pstride) {
+      if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48) || pstride[k] % es) return HMGPU_EINVAL;
+      pic = pstride[k] * (plan.channels[k] - 1) + plane;
+    }
+    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % es || pitch[k] % es || bstride[k] % es) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && bstride[k] % g == 0 && (!pstride || pstride[k] % g == 0)) *vec |= 1 << k;
+  }
+  return any ? HMGPU_OK : HMGPU_EINVAL;
+}
+
+extern "C" {
+
+// every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; the arguments as export_resolve takes
+// them.  One launch, the stream ordering once.
+static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* sc,
                                 const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
                                 int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr,
                                 const hmgpu_export_pixel* px = nullptr) {
-  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-  hmgpu_export_plan plan;
-  ScaleShape s;
-  int elem = 0;
-  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
-  hmgpu_export_desc dd;
-  bool differ = false;
-  uint32_t flip = 0;
-  if (win) {
-    { const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, win, &plan, &shapes, &elem, &differ); if (st != HMGPU_OK) return st; }
-    for (int i = 0; i < n; i++) flip |= (uint32_t)(win[i].flip & 1) << i;
-    if (!differ) {                                   // one window for all: the descriptor with that crop, its table slot
-      dd = *d;
-      memcpy(dd.crop, win[0].crop, sizeof(dd.crop));
-      d = &dd;
-      if (sc) s = shapes[0];
-    }
-  } else {
-    const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &plan, &s, &elem);
-    if (st != HMGPU_OK) return st;
-  }
-  PxOrder po;
-  if (px) { const hmgpu_status st = pixel_plan(&c->seq, d, elem, px, &plan, &po); if (st != HMGPU_OK) return st; }
-  const int nch = !px ? 0 : px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
-  hipSetDevice(c->device);
-  const int ES = elem_size(elem);
-  bool vec = true;
-  int64_t bs[3] = {0, 0, 0};
-  { const hmgpu_status st = export_dst_ok(c, plan, ES, n, dst, pitch_bytes, bstride, &vec, bs); if (st != HMGPU_OK) return st; }
-  // packed pixels: a full group is a run of dwords where the destination is dword aligned; the loads have their own condition
-  if (px) po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || bs[0] % 4 == 0);
+  ExportCall r;
+  { const hmgpu_status st = export_resolve(c, n, desc, sc, t, win, px, dst, pitch_bytes, bstride, true, &r); if (st != HMGPU_OK) return st; }
+  const hmgpu_export_desc* d = &r.d;
   hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
-  const int bdY = c->seq.bit_depth_luma, bdC = c->seq.bit_depth_chroma;
-  const int obY = d->bit_depth[0] ? d->bit_depth[0] : bdY;
-  const int obC = rgb ? obY : (d->bit_depth[1] ? d->bit_depth[1] : bdC);
-  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
   if (!sc) {
     ExportArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < n; i++) {
       const Picture& p = c->pics[pics[i]];
       int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-      const int x0 = differ ? win[i].crop[0] : d->crop[0], y0 = differ ? win[i].crop[2] : d->crop[2];
+      const int x0 = r.differ ? win[i].crop[0] : d->crop[0], y0 = r.differ ? win[i].crop[2] : d->crop[2];
       a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
       a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
-      if ((vec || px) && (x0 & 3) == 0) a.vec |= 1u << i;                 // (a batch may mix aligned and unaligned left edges)
+      if ((r.vec || px) && (x0 & 3) == 0) a.vec |= 1u << i;               // (a batch may mix aligned and unaligned left edges)
     }
-    a.flip = flip;
     a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
-    a.n = n; a.layout = d->layout; a.elem = elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-    a.w = plan.width[0]; a.h = plan.height[0];
-    a.cw = (plan.width[0]) >> c->csx; a.ch = plan.height[0] >> c->csy;
-    a.sh[0] = obY - bdY; a.sh[1] = obC - bdC;
-    a.maxv[0] = (1 << obY) - 1; a.maxv[1] = (1 << obC) - 1;
-    a.msb[0] = d->msb_aligned ? 16 - obY : 0; a.msb[1] = d->msb_aligned ? 16 - obC : 0;
-    for (int k = 0; k < 3; k++) {
-      a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
-      a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
-      a.bstride[k] = bs[k];
-      if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
-    }
-    memcpy(a.coef, plan.coef, sizeof(a.coef));
-    if (px) launch_export_px(a, po, nch, hs);
+    a.n = n; a.layout = d->layout; a.elem = r.elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+    a.w = r.plan.width[0]; a.h = r.plan.height[0];
+    a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
+    export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
+    if (px) launch_export_px(a, r.po, r.nch, hs);
     else launch_export(a, hs);
     return export_end(c, n, pics, on_stream, hs);
   }
-  if (differ) s = shapes[0];                         // (the output size and the depths are those of every window)
+  const ScaleShape& s = r.s;
   // the tables' slot is keyed by the tiles the batch size leads to, not by the batch size: calls of varying n share a slot
   int tile[2][2] = {{0, 0}, {0, 0}};
   int32_t tkey = rgb ? 1 : 0;
@@ -848,16 +906,16 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
     tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
   }
-  hmgpu_ctx::ScaleSlot* slot = nullptr;
-  hmgpu_ctx::WindowBuf* wbuf = nullptr;
+  hmgpu_ctx::TableBuf* tables = nullptr;
   ScaleArgs a;
   memset(&a, 0, sizeof(a));
-  if (differ) {
-    const hmgpu_status st = window_tables(c, n, shapes, win, rgb, tile, hs, a.cls, &a.pic_cls, &wbuf);
+  if (r.differ) {
+    const hmgpu_status st = window_tables(c, n, r.shapes, win, rgb, tile, hs, a.cls, &a.pic_cls, &tables);
     if (st != HMGPU_OK) return st;
   } else {
     const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
     int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
+    hmgpu_ctx::ScaleSlot* slot = nullptr;
     { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
     for (int k = 0; k < s.classes; k++) {
       a.cls[k] = slot->cls[k];
@@ -865,8 +923,8 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
       a.cls[k].x0 = x0c[k];
       a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
     }
+    tables = slot;
   }
-  a.flip = flip;
   for (int i = 0; i < n; i++) {
     const Picture& p = c->pics[pics[i]];
     int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
@@ -874,27 +932,13 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   }
   a.pitch_c = c->pitch[1];
   a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-  a.sh[0] = s.depth[0] - bdY; a.sh[1] = (rgb ? s.depth[0] : s.depth[1]) - bdC;
-  a.maxv[0] = (1 << s.depth[0]) - 1; a.maxv[1] = (1 << (rgb ? s.depth[0] : s.depth[1])) - 1;
-  a.msb[0] = d->msb_aligned ? 16 - s.depth[0] : 0; a.msb[1] = d->msb_aligned ? 16 - (rgb ? s.depth[0] : s.depth[1]) : 0;
-  a.e = plan.coef[11];
-  a.vec = px ? (int)po.vst : vec ? 1 : 0;
-  if (px) a.px = po;
-  for (int k = 0; k < 3; k++) {
-    a.dst[k] = k < plan.planes ? static_cast<uint8_t*>(dst[k]) : nullptr;
-    a.pitch[k] = k < plan.planes ? pitch_bytes[k] : 0;
-    a.bstride[k] = bs[k];
-    if (elem >= kElemF16) { a.scale[k] = t->scale[k]; a.bias[k] = t->bias[k]; }
-  }
-  memcpy(a.coef, plan.coef, sizeof(a.coef));
-  launch_export_scaled(a, d->layout, elem, n, hs, nch);
-  if (wbuf) {
-    HIP_TRY(c, hipEventRecord(wbuf->done, hs));
-    wbuf->pending = true;
-  } else {
-    HIP_TRY(c, hipEventRecord(slot->done, hs));
-    slot->pending = true;
-  }
+  a.e = r.plan.coef[11];
+  a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
+  if (px) a.px = r.po;
+  export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
+  launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  HIP_TRY(c, hipEventRecord(tables->done, hs));
+  tables->pending = true;
   return export_end(c, n, pics, on_stream, hs);
 }
 
@@ -932,6 +976,22 @@ hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* c, int32_t n, const hmgpu_p
   return export_impl(c, n, pics, d, sc, t, dst3, pitch3, bstride3, on_stream, stream, windows, px);
 }
 
+// ------------------------------------------------------------------------------------------------ side information: what motion and residual share
+// the windows of a dense form, in order (the first failure is the call's status); w x h: the output -- sc's size, or (unscaled) the one
+// size every window has
+static hmgpu_status dense_windows_ok(const hmgpu_seq_params* seq, const hmgpu_export_scale* sc, int n, const hmgpu_export_window* win, int* w, int* h) {
+  for (int i = 0; i < n; i++) {
+    int ww, wh;
+    { const hmgpu_status st = window_ok(seq, win[i], sc, &ww, &wh); if (st != HMGPU_OK) return st; }
+    if (sc) continue;
+    if (!i) { *w = ww; *h = wh; }
+    if (ww != *w || wh != *h) return HMGPU_EINVAL;
+    if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
+  }
+  if (sc) { *w = sc->width; *h = sc->height; }
+  return HMGPU_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ motion and block export (k_motion.hip)
 // hmgpu_motion_plan_for and what the entry point needs beyond the plan: the output element of the dense form (kElem*)
 static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int n,
@@ -949,10 +1009,9 @@ static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_
   int w = 0, h = 0;
   if (d->form == HMGPU_MOTION_BLOCKS) {
     if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
-    const int* cr = d->crop;
-    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0 || ((cr[0] | cr[1] | cr[2] | cr[3]) & 3)) return HMGPU_EINVAL;      // whole blocks
-    w = (seq->width - cr[0] - cr[1]) / 4; h = (seq->height - cr[2] - cr[3]) / 4;
-    if (w <= 0 || h <= 0) return HMGPU_EINVAL;
+    if ((d->crop[0] | d->crop[1] | d->crop[2] | d->crop[3]) & 3) return HMGPU_EINVAL;         // whole blocks (a negative crop: crop_ok)
+    if (crop_ok(seq, d->crop, nullptr, &w, &h) != HMGPU_OK) return HMGPU_EINVAL;
+    w /= 4; h /= 4;
     out->channels[HMGPU_MOTION_DST_MV0] = 2 * L;
     out->elem_bytes[HMGPU_MOTION_DST_MV0] = 2;
   } else {
@@ -961,28 +1020,10 @@ static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_
     if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;            // the window is the crop
     *elem = d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
     if (sc) {
-      for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
-      if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
+      { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
       if (sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                       // vectors are not interpolated
     }
-    const int csx = fmt == 3 ? 0 : 1, csy = fmt == 1 || fmt == 0 ? 1 : 0, mono = fmt == 0;
-    for (int i = 0; i < n; i++) {
-      const int* cr = win[i].crop;
-      if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) return HMGPU_EINVAL;
-      if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
-      const int ww = seq->width - cr[0] - cr[1], wh = seq->height - cr[2] - cr[3];
-      if (ww <= 0 || wh <= 0) return HMGPU_EINVAL;
-      if (!mono && (((cr[0] | cr[1]) & ((1 << csx) - 1)) || ((cr[2] | cr[3]) & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
-      if (sc) {
-        const long long in[2] = {ww, wh}, o[2] = {sc->width, sc->height};
-        for (int ax = 0; ax < 2; ax++) if (o[ax] > 16384 || in[ax] > 32 * o[ax] || o[ax] > 8 * in[ax]) return HMGPU_EUNSUPPORTED;
-      } else {
-        if (!i) { w = ww; h = wh; }
-        if (ww != w || wh != h) return HMGPU_EINVAL;                                          // unscaled: one size, the output's
-        if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
-      }
-    }
-    if (sc) { w = sc->width; h = sc->height; }
+    { const hmgpu_status st = dense_windows_ok(seq, sc, n, win, &w, &h); if (st != HMGPU_OK) return st; }
     const int es = *elem == kElemF32 ? 4 : 2;
     for (int l = 0; l < 2; l++) if ((d->lists >> l) & 1) { out->channels[l] = 2; out->elem_bytes[l] = es; }
   }
@@ -1004,30 +1045,6 @@ hmgpu_status hmgpu_motion_plan_for(const hmgpu_seq_params* seq, const hmgpu_moti
   return st;
 }
 
-// every destination given: element alignment, strides against the extents they step over, and the whole span of n pictures inside one
-// allocation of the context's device.  vec: bit k set when every group of four elements of slot k may be one store
-static hmgpu_status motion_dst_ok(const hmgpu_ctx* c, const hmgpu_motion_plan& plan, int n, void* const dst[4], const int64_t* pitch,
-                                  const int64_t* pstride, const int64_t* bstride, int* vec) {
-  bool any = false;
-  *vec = 0;
-  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
-    if (!dst[k]) continue;
-    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
-    any = true;
-    const int64_t es = plan.elem_bytes[k];
-    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
-    if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48)) return HMGPU_EINVAL;
-    const int64_t pic = pstride[k] * (plan.channels[k] - 1) + plane;
-    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
-    if ((uintptr_t)dst[k] % es || pitch[k] % es || pstride[k] % es || bstride[k] % es) return HMGPU_EINVAL;
-    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
-    const int64_t g = 4 * es;
-    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && pstride[k] % g == 0 && bstride[k] % g == 0) *vec |= 1 << k;
-  }
-  return any ? HMGPU_OK : HMGPU_EINVAL;
-}
-
 hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc,
                                             const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref, void* dst_block,
                                             const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
@@ -1036,9 +1053,8 @@ hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu
   hmgpu_motion_plan plan;
   int elem = 0, vec = 0;
   { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
   void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
-  return motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+  return strided_dst_ok(c, plan, HMGPU_MOTION_DSTS, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, 0, &vec);
 }
 
 hmgpu_status hmgpu_pictures_motion_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
@@ -1060,11 +1076,10 @@ hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_p
   hmgpu_motion_plan plan;
   int elem = 0, vec = 0;
   { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
   void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
-  { const hmgpu_status st = motion_dst_ok(c, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = strided_dst_ok(c, plan, HMGPU_MOTION_DSTS, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, 0, &vec); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   MotionArgs a;
   memset(&a, 0, sizeof(a));
   a.n = n; a.lists = d->lists; a.nlists = plan.lists;
@@ -1082,7 +1097,6 @@ hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_p
     a.pitch[k] = pitch_bytes[k]; a.pstride[k] = plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
   }
   a.vec = vec;
-  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
   if (d->form == HMGPU_MOTION_BLOCKS) {
     a.x4 = d->crop[0] / 4; a.y4 = d->crop[2] / 4; a.w4 = plan.width[HMGPU_MOTION_DST_REF]; a.h4 = plan.height[HMGPU_MOTION_DST_REF];
     if (a.x4 & 3) a.vec = 0;                         // a lane's four blocks are aligned in the picture, not in the crop
@@ -1093,8 +1107,8 @@ hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_p
       const int* cr = windows[i].crop;
       MotionWin& w = a.win[i];
       w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
-      w.kx = (float)((double)a.W / (4.0 * w.w)); w.ky = (float)((double)a.H / (4.0 * w.h));     // quarter luma samples -> output samples
       a.flip |= (uint32_t)(windows[i].flip & 1) << i;
+      w.kx = (float)((double)a.W / (4.0 * w.w)); w.ky = (float)((double)a.H / (4.0 * w.h));     // quarter luma samples -> output samples
     }
     launch_motion_dense(a, elem, hs);
   }
@@ -1114,18 +1128,14 @@ static hmgpu_status residual_plan(const hmgpu_seq_params* seq, const hmgpu_resid
   for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
   if (d->form != HMGPU_RESIDUAL_PLANES && d->form != HMGPU_RESIDUAL_DENSE) return HMGPU_EINVAL;
   if (d->components < 1 || d->components > 7) return HMGPU_EINVAL;
-  if (sc) {
-    for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
-    if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
-  }
+  if (sc) { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
   if (fmt >= 2) return HMGPU_EUNSUPPORTED;          // k_ccp rewrites their chroma tiles in place; 4:2:2 blocks are two squares
   const bool mono = fmt == 0;
   if (d->form == HMGPU_RESIDUAL_PLANES) {
     if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
-    const int* cr = d->crop;
-    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0 || ((cr[0] | cr[1] | cr[2] | cr[3]) & 7)) return HMGPU_EINVAL;
-    const int w = seq->width - cr[0] - cr[1], h = seq->height - cr[2] - cr[3];
-    if (w <= 0 || h <= 0) return HMGPU_EINVAL;
+    if ((d->crop[0] | d->crop[1] | d->crop[2] | d->crop[3]) & 7) return HMGPU_EINVAL;         // whole 8x8 tiles (a negative crop: crop_ok)
+    int w, h;
+    if (crop_ok(seq, d->crop, nullptr, &w, &h) != HMGPU_OK) return HMGPU_EINVAL;
     for (int k = 0; k < 3; k++) {
       if (!((d->components >> k) & 1) || (k && mono)) continue;
       out->channels[k] = 1; out->elem_bytes[k] = 2;
@@ -1141,23 +1151,7 @@ static hmgpu_status residual_plan(const hmgpu_seq_params* seq, const hmgpu_resid
     for (int k = 0; k < 3; k++) if (((d->components >> k) & 1) && !std::isfinite(d->scale[k])) return HMGPU_EINVAL;
   if (sc && sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                    // a residual is not interpolated
   int w = 0, h = 0;
-  for (int i = 0; i < n; i++) {
-    const int* cr = win[i].crop;
-    if ((win[i].flip & ~1) || win[i].reserved[0] || win[i].reserved[1] || win[i].reserved[2]) return HMGPU_EINVAL;
-    if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
-    const int ww = seq->width - cr[0] - cr[1], wh = seq->height - cr[2] - cr[3];
-    if (ww <= 0 || wh <= 0) return HMGPU_EINVAL;
-    if (!mono && ((cr[0] | cr[1] | cr[2] | cr[3]) & 1)) return HMGPU_EINVAL;                  // whole chroma samples
-    if (sc) {
-      const long long in[2] = {ww, wh}, o[2] = {sc->width, sc->height};
-      for (int ax = 0; ax < 2; ax++) if (o[ax] > 16384 || in[ax] > 32 * o[ax] || o[ax] > 8 * in[ax]) return HMGPU_EUNSUPPORTED;
-    } else {
-      if (!i) { w = ww; h = wh; }
-      if (ww != w || wh != h) return HMGPU_EINVAL;                                            // unscaled: one size, the output's
-      if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
-    }
-  }
-  if (sc) { w = sc->width; h = sc->height; }
+  { const hmgpu_status st = dense_windows_ok(seq, sc, n, win, &w, &h); if (st != HMGPU_OK) return st; }
   out->channels[0] = (d->components & 1) + ((d->components >> 1) & 1) + ((d->components >> 2) & 1);
   out->elem_bytes[0] = *elem == kElemF32 ? 4 : 2;
   out->width[0] = w; out->height[0] = h; out->row_bytes[0] = w * out->elem_bytes[0];
@@ -1172,32 +1166,6 @@ hmgpu_status hmgpu_residual_plan_for(const hmgpu_seq_params* seq, const hmgpu_re
   return st;
 }
 
-// the rules of motion_dst_ok for the three slots of a residual export.  vec: bit k set when slot k may take 16-byte stores
-static hmgpu_status residual_dst_ok(const hmgpu_ctx* c, const hmgpu_residual_desc* d, const hmgpu_residual_plan& plan, int n, void* const dst[3],
-                                    const int64_t* pitch, const int64_t* pstride, const int64_t* bstride, int* vec) {
-  const bool mono = c->seq.chroma_format == 0, planes = d->form == HMGPU_RESIDUAL_PLANES;
-  bool any = false;
-  *vec = 0;
-  for (int k = 0; k < 3; k++) {
-    if (!dst[k] || (planes && mono && k)) continue;                   // (the chroma destinations of a 4:0:0 picture are ignored)
-    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
-    any = true;
-    const int64_t es = plan.elem_bytes[k];
-    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
-    int64_t pic = plane;
-    if (!planes) {
-      if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48) || pstride[k] % es) return HMGPU_EINVAL;
-      pic = pstride[k] * (plan.channels[k] - 1) + plane;
-    }
-    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
-    if ((uintptr_t)dst[k] % es || pitch[k] % es || bstride[k] % es) return HMGPU_EINVAL;
-    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
-    if ((uintptr_t)dst[k] % 16 == 0 && pitch[k] % 16 == 0 && bstride[k] % 16 == 0 && (planes || pstride[k] % 16 == 0)) *vec |= 1 << k;
-  }
-  return any ? HMGPU_OK : HMGPU_EINVAL;
-}
-
 hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc,
                                               const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
                                               const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]) {
@@ -1205,8 +1173,9 @@ hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* c, int32_t n, const hmg
   hmgpu_residual_plan plan;
   int elem = 0, vec = 0;
   { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  return residual_dst_ok(c, d, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+  const bool planes = d->form == HMGPU_RESIDUAL_PLANES;
+  const int slots = planes && c->seq.chroma_format == 0 ? 1 : 3;       // (the chroma destinations of a 4:0:0 picture's planes are ignored)
+  return strided_dst_ok(c, plan, slots, n, dst, pitch_bytes, planes ? nullptr : plane_stride_bytes, batch_stride_bytes, 16, &vec);
 }
 
 hmgpu_status hmgpu_pictures_residual_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
@@ -1223,13 +1192,14 @@ hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu
   // (the format's refusal comes first: it does not depend on the pictures)
   { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
   { const hmgpu_status st = hmgpu_pictures_residual_check(c, n, pics); if (st != HMGPU_OK) return st; }
-  hipSetDevice(c->device);
-  { const hmgpu_status st = residual_dst_ok(c, d, plan, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  const bool planes = d->form == HMGPU_RESIDUAL_PLANES;
+  const int slots = planes && c->seq.chroma_format == 0 ? 1 : 3;       // (the chroma destinations of a 4:0:0 picture's planes are ignored)
+  { const hmgpu_status st = strided_dst_ok(c, plan, slots, n, dst, pitch_bytes, planes ? nullptr : plane_stride_bytes, batch_stride_bytes, 16, &vec); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_stream(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  const bool mono = c->seq.chroma_format == 0, planes = d->form == HMGPU_RESIDUAL_PLANES;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   ResidArgs a;
   memset(&a, 0, sizeof(a));
+  const bool mono = c->seq.chroma_format == 0;
   a.n = n; a.mono = mono; a.comps = mono ? d->components & 1 : d->components;
   a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
   for (int k = 0; k < 3; k++) a.rtw[k] = (c->grid_w / 2) >> (k ? c->csx : 0);
@@ -1245,13 +1215,12 @@ hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu
     for (const SliceCall& sc : pic.calls) dir = dir && sc.dir;
     s.gate = (dir ? kResidIntra : 0) | (pic.flags_staged ? kResidFlags : 0);
   }
-  for (int k = 0; k < 3; k++) {
-    if (!dst[k] || (planes && mono && k)) continue;
+  for (int k = 0; k < slots; k++) {
+    if (!dst[k]) continue;
     a.dst[k] = static_cast<uint8_t*>(dst[k]);
     a.pitch[k] = pitch_bytes[k]; a.pstride[k] = planes ? 0 : plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
   }
   a.vec = vec;
-  { const hmgpu_status st = export_begin(c, on_stream, hs); if (st != HMGPU_OK) return st; }
   if (planes) {
     a.x0 = d->crop[0]; a.y0 = d->crop[2]; a.w = c->seq.width - d->crop[0] - d->crop[1]; a.h = c->seq.height - d->crop[2] - d->crop[3];
     if (a.x0 & 15) a.vec &= 1;                       // a chroma lane's eight samples are aligned in the picture, not in the crop

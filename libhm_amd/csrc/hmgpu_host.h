@@ -119,15 +119,25 @@ struct hmgpu_ctx {
   uint64_t hash_seq = 0, hash_launched = 0, hash_launches = 0;
   hipEvent_t xfer_ev[2] = {};            // hmgpu_picture_transfer: source ready / copy done
   hipEvent_t exp_ev[2] = {};             // hmgpu_picture_export on a caller's stream: picture ready / export done (created when first used)
-  // hmgpu_picture_export_scaled: resampling tables in device memory, one slot per export shape, least recently used slot reused
-  struct ScaleSlot {
-    int32_t key[8] = {};                 // crop[4], output width / height, filter, RGB | the classes' starting tiles (log2 tw, log2 th) << 1
-    bool valid = false, pending = false; // pending: `done` stands for an export that read the slot
-    uint64_t used = 0;
-    char* dev = nullptr;                 // the tables (ScaleTable)
-    char* host = nullptr;                // page-locked: the same bytes on their way over
+  // the export's tables in device memory and, page-locked, the same bytes on their way over; `done` is recorded behind the last export
+  // that read them (pending), and the buffer is rewritten only after it (hmgpu_export.hip: table_room)
+  struct TableBuf {
+    char* dev = nullptr;
+    char* host = nullptr;
     size_t cap = 0;
-    hipEvent_t done = nullptr;           // recorded behind the last export that read the slot
+    bool pending = false;
+    hipEvent_t done = nullptr;
+    void release() {
+      if (done) hipEventDestroy(done);
+      if (dev) (void)hipFree(dev);
+      if (host) (void)hipHostFree(host);
+    }
+  };
+  // hmgpu_picture_export_scaled: one slot per export shape, least recently used slot reused
+  struct ScaleSlot : TableBuf {
+    int32_t key[8] = {};                 // crop[4], output width / height, filter, RGB | the classes' starting tiles (log2 tw, log2 th) << 1
+    bool valid = false;
+    uint64_t used = 0;
     ScaleClass cls[2];
   };
   static constexpr int kScaleSlots = 8;
@@ -135,15 +145,8 @@ struct hmgpu_ctx {
   uint64_t scale_tick = 0;
   // hmgpu_pictures_export_windows, windows that differ: the tables, spans and per-picture classes of one call (no key ever repeats, so
   // nothing is cached): a ring of per-call buffers, the next one rewritten only after the export that read it has finished
-  struct WindowBuf {
-    char* dev = nullptr;
-    char* host = nullptr;                // page-locked
-    size_t cap = 0;
-    bool pending = false;
-    hipEvent_t done = nullptr;           // recorded behind the export that read the buffer
-  };
   static constexpr int kWindowBufs = 4;
-  WindowBuf window_buf[kWindowBufs];
+  TableBuf window_buf[kWindowBufs];
   int window_next = 0;
   uint64_t xfer_bytes = 0;
   uint32_t* dl_fault = nullptr;        // [32] page-locked: the picture's fault word (k_intra's bounded spin) as it stood behind the copies of ticket t

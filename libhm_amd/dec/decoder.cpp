@@ -1024,11 +1024,8 @@ std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_expo
 }
 }  // namespace
 
-hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
-                                       const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
-                                       const hmgpu_export_pixel* pixel) {
-  if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+// what every batched export asks of its pictures: this decoder's, on the device and decoded (their device work enqueued first), one size, one GPU
+hmgpu_status Decoder::export_pics_ok(int n, PicData* const* pics) {
   for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
   flush_batch();
   for (int i = 0; i < n; i++) {
@@ -1036,6 +1033,15 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
     if (!p->on_device || !p->decoded) return HMGPU_EINVAL;               // (on the device: of the sequence whose contexts exist)
     if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
   }
+  return HMGPU_OK;
+}
+
+hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                       const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
+                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
+                                       const hmgpu_export_pixel* pixel) {
+  if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
   // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
   // one hmgpu_pictures_export per run of slots (export_runs).
   { const hmgpu_status st = pixel ? hmgpu_export_pixels_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, dst[0], pitch_bytes[0], batch_stride_bytes[0])
@@ -1058,79 +1064,55 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
   return HMGPU_OK;
 }
 
+// As export_pictures: the destination (and every window) validated once for all n slots, then one call per run of slots of one
+// context -- the context that decoded the pictures (PicData::home), the only one that holds their side information and residual
+// tiles.  Whether every picture has side information is asked of every context first, so that no context is given work when another
+// one's call would be refused.
+template <int SLOTS, class Check, class Side, class Run>
+hmgpu_status Decoder::export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,
+                                  Check check, Side side, Run run) {
+  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = check(ctx_of(pics[0])); if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, windows);
+  for (const ExportRun& r : runs) {
+    const hmgpu_status st = side(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
+    if (st != HMGPU_OK) return st;
+  }
+  for (const ExportRun& r : runs) {
+    void* d[SLOTS];
+    int64_t bs[SLOTS];
+    for (int k = 0; k < SLOTS; k++) {
+      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+      bs[k] = batch_stride_bytes[k] * r.step;
+    }
+    const hmgpu_status st = run(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, windows ? r.w : nullptr, d, bs);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
 hmgpu_status Decoder::export_motion(int n, PicData* const* pics, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
                                      const hmgpu_export_window* windows, void* const dst_mv[2], void* dst_ref, void* dst_block,
                                      const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4],
                                      int on_stream, void* stream) {
   if (!gpu_ || !pics || !desc || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
-  flush_batch();
-  for (int i = 0; i < n; i++) {
-    const PicData* p = pics[i];
-    if (!p->on_device || !p->decoded) return HMGPU_EINVAL;
-    if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
-  }
-  // as export_pictures: the destination (and every window) validated once for all n slots, then one call per run of slots of one
-  // context -- the context that decoded the pictures (PicData::home), the only one that holds their side information.  Whether every
-  // picture has side information is asked of every context first (hmgpu_pictures_motion_check), so that no context is given work
-  // when another one's call would be refused.
-  { const hmgpu_status st = hmgpu_motion_destination_check(ctx_of(pics[0]), n, desc, scale, windows, dst_mv, dst_ref, dst_block, pitch_bytes,
-                                                           plane_stride_bytes, batch_stride_bytes);
-    if (st != HMGPU_OK) return st; }
-  const std::vector<ExportRun> runs = export_runs(n, pics, windows);
-  for (const ExportRun& r : runs) {
-    const hmgpu_status st = hmgpu_pictures_motion_check(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
-    if (st != HMGPU_OK) return st;
-  }
-  for (const ExportRun& r : runs) {
-    void* d[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
-    int64_t bs[4];
-    for (int k = 0; k < 4; k++) {
-      if (d[k]) d[k] = static_cast<char*>(d[k]) + (int64_t)r.first * batch_stride_bytes[k];
-      bs[k] = batch_stride_bytes[k] * r.step;
-    }
-    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
-    const hmgpu_status st = hmgpu_pictures_export_motion(c, r.n, r.h, desc, scale, windows ? r.w : nullptr, d, d[2], d[3], pitch_bytes,
-                                                         plane_stride_bytes, bs, on_stream, stream);
-    if (st != HMGPU_OK) return st;
-  }
-  return HMGPU_OK;
+  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
+  return export_side<4>(n, pics, windows, dst, batch_stride_bytes,
+      [&](hmgpu_ctx* c) { return hmgpu_motion_destination_check(c, n, desc, scale, windows, dst_mv, dst_ref, dst_block, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
+      hmgpu_pictures_motion_check,
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window* w, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_export_motion(c, rn, h, desc, scale, w, d, d[2], d[3], pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
 hmgpu_status Decoder::export_residual(int n, PicData* const* pics, const hmgpu_residual_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_window* windows, void* const dst[3], const int64_t pitch_bytes[3],
                                        const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
   if (!gpu_ || !pics || !desc || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int i = 0; i < n; i++) if (!pics[i] || pics[i]->owner != this) return HMGPU_EINVAL;
-  flush_batch();
-  for (int i = 0; i < n; i++) {
-    const PicData* p = pics[i];
-    if (!p->on_device || !p->decoded) return HMGPU_EINVAL;
-    if (p->width != pics[0]->width || p->height != pics[0]->height || device_of(p) != device_of(pics[0])) return HMGPU_EINVAL;
-  }
-  // as export_motion: the residual tiles and the arrays lie in the context that decoded a picture (PicData::home).  Everything is
-  // validated first -- the destination and every window once for all n slots, then every context's pictures -- then one call per run.
-  { const hmgpu_status st = hmgpu_residual_destination_check(ctx_of(pics[0]), n, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes,
-                                                             batch_stride_bytes);
-    if (st != HMGPU_OK) return st; }
-  const std::vector<ExportRun> runs = export_runs(n, pics, windows);
-  for (const ExportRun& r : runs) {
-    const hmgpu_status st = hmgpu_pictures_residual_check(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
-    if (st != HMGPU_OK) return st;
-  }
-  for (const ExportRun& r : runs) {
-    void* d[3];
-    int64_t bs[3];
-    for (int k = 0; k < 3; k++) {
-      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-      bs[k] = batch_stride_bytes[k] * r.step;
-    }
-    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
-    const hmgpu_status st = hmgpu_pictures_export_residual(c, r.n, r.h, desc, scale, windows ? r.w : nullptr, d, pitch_bytes, plane_stride_bytes, bs,
-                                                           on_stream, stream);
-    if (st != HMGPU_OK) return st;
-  }
-  return HMGPU_OK;
+  return export_side<3>(n, pics, windows, dst, batch_stride_bytes,
+      [&](hmgpu_ctx* c) { return hmgpu_residual_destination_check(c, n, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
+      hmgpu_pictures_residual_check,
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window* w, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_export_residual(c, rn, h, desc, scale, w, d, pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row

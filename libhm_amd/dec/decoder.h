@@ -103,6 +103,12 @@ class Decoder {
   void poll_device_hashes(bool block);
   void submit_picture(PicData* pic, int parsed_ctbs);     // marks of a completely parsed picture; its device work joins the batch
   void flush_batch();                                     // the device work of the pictures retired together (hmgpu_decompress_pictures / hmgpu_filter_pictures)
+  __attribute__((visibility("hidden"))) hmgpu_status export_pics_ok(int n, PicData* const* pics);   // what every batched export asks of its pictures (their device work enqueued first)
+  // export_motion / export_residual: SLOTS destinations; check: the destination check on a context; side: the side-information check
+  // of a run's pictures; run: the export of one run (context, n, handles, windows, destinations, batch strides)
+  template <int SLOTS, class Check, class Side, class Run>
+  hmgpu_status export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,
+                           Check check, Side side, Run run);
   void close_current();
   void worker_main();
   static void hook_wait_rows(void* self, const PicData* pic, int rows);

@@ -9,6 +9,8 @@ the kernel does not implement (anything but 0, 1, 5, 6, 9) are refused with HMGP
 Tensor output (export_batch, dtype=): float16 / bfloat16 / float32 elements take fl(fl(v * scale_k) + bias_k) of the integer v the
 export writes, with (scale, bias) from `affine`: v / (2^D - 1) normalised by a per-plane mean and std.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import abi
@@ -135,6 +137,51 @@ def make_windows(seq, crop, windows, flip, n):
             raise ValueError("window %r leaves the %dx%d crop" % ((x, y, w, h), cw, ch))
         out.append(abi.make_export_window((l + x, seq.width - (l + x) - w, t + y, seq.height - (t + y) - h), f))
     return out
+
+
+def dense_windows(seq, crop, windows, flip, n):
+    """make_windows for the dense forms of the motion and residual exports, which always take windows: None is all of `crop`"""
+    l, r, t, b = (int(v) for v in crop)
+    return make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * n, flip, n)
+
+
+def side_plan(entry, plan, seq, desc, scale=None, windows=None, n=None):
+    """hmgpu_motion_plan_for / hmgpu_residual_plan_for (`entry`, host code, no GPU) into `plan`, an empty abi.MotionPlan /
+    abi.ResidualPlan; windows: abi.ExportWindow per picture (dense); n: the number of pictures (default: one per window, else 1)"""
+    from . import HmgpuError, lib
+    windows = None if windows is None else list(windows)
+    count = n if n is not None else (len(windows) if windows is not None else 1)
+    st = getattr(lib(), entry)(C.byref(seq), C.byref(desc), abi.ref(scale), count, abi.window_array(windows), C.byref(plan))
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, entry)
+    return plan
+
+
+def side_tensors(out, device, names, shape, dtype, slots, rule="elements dense within a row"):
+    """the result dict of a motion or residual export and its destinations.  names: slot -> key; shape(k) / dtype(k): of slot k's
+    tensor.  out None: every tensor allocated on `device`; else a dict with some of the keys, each a tensor of that shape, dtype and
+    device whose rows are dense (a 5-d tensor: its pairs of channels equally far apart).  Returns (out, pointers, pitches, plane
+    strides, batch strides), bytes, `slots` long; a slot without a tensor: None / 0; a plane stride: 0 for [N, H, W]."""
+    import torch
+    if out is None:
+        out = {name: torch.empty(shape(k), dtype=dtype(k), device=torch.device("cuda", device)) for k, name in names.items()}
+    for key in out:
+        if key not in names.values():
+            raise ValueError("out: no tensor %r in this export (one of %s)" % (key, ", ".join(sorted(names.values()))))
+    ptrs, pitches, pstrides, bstrides = [None] * slots, [0] * slots, [0] * slots, [0] * slots
+    for k, name in names.items():
+        t = out.get(name)
+        if t is None:
+            continue
+        want = shape(k)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != dtype(k) or t.get_device() != device:
+            raise ValueError("out[%r]: a %s tensor of shape %s on device %d" % (name, dtype(k), want, device))
+        st, es = t.stride(), t.element_size()
+        if st[-1] != 1 or (len(want) == 5 and st[1] != 2 * st[2]):
+            raise ValueError("out[%r]: %s (stride %s)" % (name, rule, st))
+        ptrs[k], pitches[k], bstrides[k] = t.data_ptr(), st[-2] * es, st[0] * es
+        pstrides[k] = st[-3] * es if len(want) > 3 else 0
+    return out, ptrs, pitches, pstrides, bstrides
 
 
 def random_resized_crop(n, width, height, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip=0.5, generator=None, chroma_format=1):

@@ -216,12 +216,11 @@ class Picture:
 
     def export_into(self, desc, ptrs, pitches, on_stream=1, stream=0, scale=None):
         """hmdec_picture_export (scale: an abi.ExportScale, hmdec_picture_export_scaled) into device memory the caller owns"""
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
+        p, q = abi.ptr_array(ptrs), abi.i64_array(pitches)
         if scale is None:
-            st, name = lib().hmdec_picture_export(self.ctx, self.h, C.byref(desc), p, q, on_stream, C.c_void_p(stream or None)), "hmdec_picture_export"
+            st, name = lib().hmdec_picture_export(self.ctx, self.h, C.byref(desc), p, q, on_stream, abi.addr(stream)), "hmdec_picture_export"
         else:
-            st = lib().hmdec_picture_export_scaled(self.ctx, self.h, C.byref(desc), C.byref(scale), p, q, on_stream, C.c_void_p(stream or None))
+            st = lib().hmdec_picture_export_scaled(self.ctx, self.h, C.byref(desc), C.byref(scale), p, q, on_stream, abi.addr(stream))
             name = "hmdec_picture_export_scaled"
         if st != 0:
             from . import HmgpuError
@@ -260,6 +259,33 @@ def _form_is_dense(form):
     return motion.form_code(form) == abi.MOTION_DENSE
 
 
+def _prologue(pictures, name, crop, none_crop):
+    """what the batch exports start with: (the first picture, its sequence, the crop resolved -- "conformance": the picture's window,
+    None: none_crop()); _device(first, name) follows, after whatever else a caller takes from the picture"""
+    first = pictures[0]
+    if first.ctx is None:
+        raise RuntimeError("%s: the picture does not know its decoder" % name)
+    g = first.geometry()
+    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
+    seq.chroma_format = g["chroma_format"]
+    if crop is None:
+        crop = none_crop()
+    if crop == "conformance":
+        crop = first.conformance_window()
+    return first, seq, crop
+
+
+def _device(first, name):
+    dev = first.device
+    if dev < 0:
+        raise RuntimeError("%s: the picture is not on a device (parse-only, or its sequence has ended)" % name)
+    return dev
+
+
+def _handles(pictures):
+    return abi.ptr_array([p.h for p in pictures], len(pictures))
+
+
 def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, out=None,
                           crop=None, enqueue=True, n=None):
     """The decoded residual of up to 16 pictures a decoder has put out (fetched since the last push, one sequence, one GPU:
@@ -272,26 +298,13 @@ def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=No
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_residual_batch: no pictures")
-    first = pictures[0]
-    if first.ctx is None:
-        raise RuntimeError("export_residual_batch: the picture does not know its decoder")
-    g = first.geometry()
-    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
-    seq.chroma_format = g["chroma_format"]
-    if crop is None:
-        crop = (0, 0, 0, 0) if residual.form_code(form) == abi.RESIDUAL_PLANES else "conformance"
-    if crop == "conformance":
-        crop = first.conformance_window()
-    dev = first.device
-    if dev < 0:
-        raise RuntimeError("export_residual_batch: the picture is not on a device (parse-only, or its sequence has ended)")
+    first, seq, crop = _prologue(pictures, "export_residual_batch", crop,
+                                 lambda: (0, 0, 0, 0) if residual.form_code(form) == abi.RESIDUAL_PLANES else "conformance")
+    dev = _device(first, "export_residual_batch")
 
     def call(desc, sc, win, ptrs, pitches, pstrides, bstrides, st):
-        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
-        w = None if win is None else (abi.ExportWindow * len(win))(*win)
-        d, q, ps, bs = residual.c_args(ptrs, pitches, pstrides, bstrides)
-        r = lib().hmdec_pictures_export_residual(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None, w, d, q, ps,
-                                                 bs, 1, C.c_void_p(st or None))
+        r = lib().hmdec_pictures_export_residual(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.window_array(win),
+                                                 *residual.c_args(ptrs, pitches, pstrides, bstrides), 1, abi.addr(st))
         if r != 0:
             raise HmgpuError(r, "hmdec_pictures_export_residual")
     return residual.export_residual(call, seq, dev, len(pictures) if n is None else n, form, components, size, windows, flip, dtype, scale, out,
@@ -310,26 +323,13 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_motion_batch: no pictures")
-    first = pictures[0]
-    if first.ctx is None:
-        raise RuntimeError("export_motion_batch: the picture does not know its decoder")
-    g = first.geometry()
-    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
-    seq.chroma_format = g["chroma_format"]
-    if crop is None:
-        crop = (0, 0, 0, 0) if motion.form_code(form) == abi.MOTION_BLOCKS else "conformance"
-    if crop == "conformance":
-        crop = first.conformance_window()
-    dev = first.device
-    if dev < 0:
-        raise RuntimeError("export_motion_batch: the picture is not on a device (parse-only, or its sequence has ended)")
+    first, seq, crop = _prologue(pictures, "export_motion_batch", crop,
+                                 lambda: (0, 0, 0, 0) if motion.form_code(form) == abi.MOTION_BLOCKS else "conformance")
+    dev = _device(first, "export_motion_batch")
 
     def call(desc, sc, win, ptrs, pitches, pstrides, bstrides, st):
-        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
-        w = None if win is None else (abi.ExportWindow * len(win))(*win)
-        mv, ref, blk, q, ps, bs = motion.c_args(ptrs, pitches, pstrides, bstrides)
-        r = lib().hmdec_pictures_export_motion(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None, w, mv, ref,
-                                               blk, q, ps, bs, 1, C.c_void_p(st or None))
+        r = lib().hmdec_pictures_export_motion(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.window_array(win),
+                                               *motion.c_args(ptrs, pitches, pstrides, bstrides), 1, abi.addr(st))
         if r != 0:
             raise HmgpuError(r, "hmdec_pictures_export_motion")
     return motion.export_motion(call, seq, dev, len(pictures) if n is None else n, form, lists, size, windows, flip, dtype, out, crop, enqueue)
@@ -342,21 +342,10 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
     (export.make_pixel, hmdec_pictures_export_pixels)"""
     from . import HmgpuError, export, export_tensor_plan
-    first = pictures[0]
-    if first.ctx is None:
-        raise RuntimeError("export: the picture does not know its decoder")
-    g = first.geometry()
-    seq = abi.make_seq(g["width"], g["height"], g["bd_y"], g["bd_c"], log2_ctu=g["log2_ctb"])
-    seq.chroma_format = g["chroma_format"]
-    if crop == "conformance":
-        crop = first.conformance_window()
-    elif crop is None:
-        crop = (0, 0, 0, 0)
+    first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
     matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
-    dev = first.device
-    if dev < 0:
-        raise RuntimeError("export: the picture is not on a device (parse-only, or its sequence has ended)")
+    dev = _device(first, "export")
     win = export.make_windows(seq, crop, windows, flip, n if not enqueue else len(pictures))
 
     def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
@@ -367,29 +356,20 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
         if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
             plan = export_tensor_plan(seq, desc, sc, tensor)
             bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
-        p = (C.c_void_p * 3)(*(list(ptrs) + [None] * (3 - len(ptrs))))
-        q = (C.c_int64 * 3)(*(list(pitches) + [0] * (3 - len(pitches))))
-        b = (C.c_int64 * 3)(*(list(bstrides) + [0] * (3 - len(bstrides))))
+        head = (first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor))
+        tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
         if win is not None:
-            w = (abi.ExportWindow * len(win))(*win)
-            r = lib().hmdec_pictures_export_windows(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
-                                                    C.byref(tensor) if tensor is not None else None, w, p, q, b, 1, C.c_void_p(st or None))
-            if r != 0:
-                raise HmgpuError(r, "hmdec_pictures_export_windows")
-            return None
-        r = lib().hmdec_pictures_export(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
-                                        C.byref(tensor) if tensor is not None else None, p, q, b, 1, C.c_void_p(st or None))
+            r, name = lib().hmdec_pictures_export_windows(*head, abi.window_array(win), *tail), "hmdec_pictures_export_windows"
+        else:
+            r, name = lib().hmdec_pictures_export(*head, *tail), "hmdec_pictures_export"
         if r != 0:
-            raise HmgpuError(r, "hmdec_pictures_export")
+            raise HmgpuError(r, name)
+
     def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
         if not enqueue:
             return None
-        h = (C.c_void_p * len(pictures))(*[p.h for p in pictures])
-        w = (abi.ExportWindow * len(win))(*win) if win is not None else None
-        r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), h, C.byref(desc), C.byref(sc) if sc is not None else None,
-                                               C.byref(tensor) if tensor is not None else None, w, C.byref(px), C.c_void_p(ptr or None), pitch,
-                                               bstride, 1, C.c_void_p(st or None))
+        r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
+                                               abi.window_array(win), C.byref(px), abi.addr(ptr), pitch, bstride, 1, abi.addr(st))
         if r != 0:
             raise HmgpuError(r, "hmdec_pictures_export_pixels")
     return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,

@@ -7,8 +7,6 @@ part_size, QP)}.  form "dense": one value per output sample of export_batch(wind
 "flow1": float [N, 2, H, W] (dx, dy in output samples), "ref_poc": int32 [N, L, H, W], "block": int8 [N, 4, H, W]}.  L counts the
 lists selected by `lists`, in list order.
 """
-import ctypes as C
-
 from . import abi
 from . import export
 
@@ -36,15 +34,20 @@ def form_code(form):
 
 def plan_for(seq, desc, scale=None, windows=None, n=None):
     """what an export with `desc` writes (hmgpu_motion_plan_for: host code, no GPU); windows: abi.ExportWindow per picture (dense)"""
-    from . import HmgpuError, lib
-    plan = abi.MotionPlan()
-    windows = None if windows is None else list(windows)
-    w = None if windows is None else (abi.ExportWindow * max(len(windows), 1))(*windows)
-    count = n if n is not None else (len(windows) if windows is not None else 1)
-    st = lib().hmgpu_motion_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None, count, w, C.byref(plan))
-    if st != abi.HMGPU_OK:
-        raise HmgpuError(st, "hmgpu_motion_plan_for")
-    return plan
+    return export.side_plan("hmgpu_motion_plan_for", abi.MotionPlan(), seq, desc, scale, windows, n)
+
+
+def describe(seq, n, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, crop=(0, 0, 0, 0), strict=True):
+    """(desc, abi.ExportScale or None, windows or None) of a call; dtype: None (float32), a torch float dtype or an abi.SAMPLE_* code;
+    strict: blocks refuses the arguments of dense (else it leaves them aside)"""
+    form = form_code(form)
+    mask = lists_mask(lists)
+    if form == abi.MOTION_BLOCKS:
+        if strict and (size is not None or windows is not None or flip is not None or dtype is not None):
+            raise ValueError("export_motion(form='blocks') takes crop only: size / windows / flip / dtype belong to form='dense'")
+        return abi.make_motion_desc(form, mask, abi.SAMPLE_UINT, crop), None, None
+    st = abi.SAMPLE_F32 if dtype is None else dtype if isinstance(dtype, int) else export.sample_type(dtype)
+    return abi.make_motion_desc(form, mask, st), export.make_scale(size, "nearest"), export.dense_windows(seq, crop, windows, flip, n)
 
 
 def tensor_names(form, mask):
@@ -72,43 +75,15 @@ def export_motion(call, seq, device, n, form="blocks", lists=(0, 1), size=None, 
     blocks: crop (left, right, top, bottom) in multiples of 4 luma samples.  dense: windows (x, y, w, h) per picture relative to crop,
     flip per picture, size (height, width) or None (windows of one size); dtype torch.float16 / bfloat16 / float32 (None: float32)."""
     import torch
-    form = form_code(form)
-    mask = lists_mask(lists)
-    if form == abi.MOTION_BLOCKS:
-        if size is not None or windows is not None or flip is not None or dtype is not None:
-            raise ValueError("export_motion(form='blocks') takes crop only: size / windows / flip / dtype belong to form='dense'")
-        desc = abi.make_motion_desc(form, mask, abi.SAMPLE_UINT, crop)
-        sc, win = None, None
-        dtypes = {abi.MOTION_DST_MV0: torch.int16}
-    else:
-        dtype = torch.float32 if dtype is None else dtype
-        desc = abi.make_motion_desc(form, mask, export.sample_type(dtype))
-        sc = export.make_scale(size, "nearest")
-        l, r, t, b = (int(v) for v in crop)
-        win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * n, flip, n)
-        dtypes = {0: dtype, 1: dtype}
-    dtypes[abi.MOTION_DST_REF], dtypes[abi.MOTION_DST_BLOCK] = torch.int32, torch.int8
+    desc, sc, win = describe(seq, n, form, lists, size, windows, flip, dtype, crop)
+    form = desc.form
+    vec = torch.int16 if form == abi.MOTION_BLOCKS else torch.float32 if dtype is None else dtype
+    dtypes = {0: vec, 1: vec, abi.MOTION_DST_REF: torch.int32, abi.MOTION_DST_BLOCK: torch.int8}
     plan = plan_for(seq, desc, sc, win, n)
-    names = tensor_names(form, mask)
     with torch.cuda.device(device):
-        if out is None:
-            dev = torch.device("cuda", device)
-            out = {name: torch.empty(_shape(form, plan, k, n), dtype=dtypes[k], device=dev) for k, name in names.items()}
-        ptrs, pitches, pstrides, bstrides = [None] * 4, [0] * 4, [0] * 4, [0] * 4
-        for key in out:
-            if key not in names.values():
-                raise ValueError("out: no tensor %r in this export (one of %s)" % (key, ", ".join(sorted(names.values()))))
-        for k, name in names.items():
-            t = out.get(name)
-            if t is None:
-                continue
-            shape = _shape(form, plan, k, n)
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtypes[k] or t.get_device() != device:
-                raise ValueError("out[%r]: a %s tensor of shape %s on device %d" % (name, dtypes[k], shape, device))
-            st, es = t.stride(), t.element_size()
-            if st[-1] != 1 or (len(shape) == 5 and st[1] != 2 * st[2]):
-                raise ValueError("out[%r]: elements dense within a row, channels equally far apart (stride %s)" % (name, st))
-            ptrs[k], pitches[k], pstrides[k], bstrides[k] = t.data_ptr(), st[-2] * es, st[-3] * es, st[0] * es
+        out, ptrs, pitches, pstrides, bstrides = export.side_tensors(
+            out, device, tensor_names(form, desc.lists), lambda k: _shape(form, plan, k, n), dtypes.get, 4,
+            "elements dense within a row, channels equally far apart")
         if enqueue:
             call(desc, sc, win, ptrs, pitches, pstrides, bstrides, torch.cuda.current_stream(device).cuda_stream)
     return out
@@ -116,5 +91,5 @@ def export_motion(call, seq, device, n, form="blocks", lists=(0, 1), size=None, 
 
 def c_args(ptrs, pitches, pstrides, bstrides):
     """the ctypes arguments (dst_mv[2], dst_ref, dst_block, pitch[4], plane stride[4], batch stride[4]) of the C entry points"""
-    mv = (C.c_void_p * 2)(ptrs[0], ptrs[1])
-    return (mv, C.c_void_p(ptrs[2]), C.c_void_p(ptrs[3]), (C.c_int64 * 4)(*pitches), (C.c_int64 * 4)(*pstrides), (C.c_int64 * 4)(*bstrides))
+    return (abi.ptr_array(ptrs[:2], 2), abi.addr(ptrs[2]), abi.addr(ptrs[3]), abi.i64_array(pitches, 4), abi.i64_array(pstrides, 4),
+            abi.i64_array(bstrides, 4))

@@ -6,8 +6,6 @@ only).  form "dense": {"residual": [N, C, H, W]}, one value per output sample of
 filter="nearest"), C the selected components in component order, int16 or a float dtype (value = float32(r) * scale[c], converted).
 The residual is what the decoder adds to the prediction; it is 0 wherever no coded transform block covers the sample.
 """
-import ctypes as C
-
 from . import abi
 from . import export
 
@@ -36,15 +34,7 @@ def form_code(form):
 
 def plan_for(seq, desc, scale=None, windows=None, n=None):
     """what an export with `desc` writes (hmgpu_residual_plan_for: host code, no GPU); windows: abi.ExportWindow per picture (dense)"""
-    from . import HmgpuError, lib
-    plan = abi.ResidualPlan()
-    windows = None if windows is None else list(windows)
-    w = None if windows is None else (abi.ExportWindow * max(len(windows), 1))(*windows)
-    count = n if n is not None else (len(windows) if windows is not None else 1)
-    st = lib().hmgpu_residual_plan_for(C.byref(seq), C.byref(desc), C.byref(scale) if scale is not None else None, count, w, C.byref(plan))
-    if st != abi.HMGPU_OK:
-        raise HmgpuError(st, "hmgpu_residual_plan_for")
-    return plan
+    return export.side_plan("hmgpu_residual_plan_for", abi.ResidualPlan(), seq, desc, scale, windows, n)
 
 
 def describe(seq, n, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0)):
@@ -59,9 +49,7 @@ def describe(seq, n, form="planes", components=(0, 1, 2), size=None, windows=Non
     if scale is not None and st == abi.SAMPLE_UINT:
         raise ValueError("scale needs a float dtype")
     desc = abi.make_residual_desc(form, mask, st, scale=(1.0, 1.0, 1.0) if scale is None else tuple(scale))
-    l, r, t, b = (int(v) for v in crop)
-    win = export.make_windows(seq, crop, windows if windows is not None else [(0, 0, seq.width - l - r, seq.height - t - b)] * n, flip, n)
-    return desc, export.make_scale(size, "nearest"), win
+    return desc, export.make_scale(size, "nearest"), export.dense_windows(seq, crop, windows, flip, n)
 
 
 def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0),
@@ -90,24 +78,7 @@ def export_residual(call, seq, device, n, form="planes", components=(0, 1, 2), s
     def shape(k):
         return (n, plan.height[k], plan.width[k]) if planes else (n, plan.channels[k], plan.height[k], plan.width[k])
     with torch.cuda.device(device):
-        if out is None:
-            dev = torch.device("cuda", device)
-            out = {name: torch.empty(shape(k), dtype=elem, device=dev) for k, name in names.items()}
-        for key in out:
-            if key not in names.values():
-                raise ValueError("out: no tensor %r in this export (one of %s)" % (key, ", ".join(sorted(names.values()))))
-        ptrs, pitches, pstrides, bstrides = [None] * 3, [0] * 3, [0] * 3, [0] * 3
-        for k, name in names.items():
-            t = out.get(name)
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape(k) or t.dtype != elem or t.get_device() != device:
-                raise ValueError("out[%r]: a %s tensor of shape %s on device %d" % (name, elem, shape(k), device))
-            st, es = t.stride(), t.element_size()
-            if st[-1] != 1:
-                raise ValueError("out[%r]: elements dense within a row (stride %s)" % (name, st))
-            ptrs[k], pitches[k], bstrides[k] = t.data_ptr(), st[-2] * es, st[0] * es
-            pstrides[k] = 0 if planes else st[1] * es
+        out, ptrs, pitches, pstrides, bstrides = export.side_tensors(out, device, names, shape, lambda k: elem, 3)
         if enqueue:
             call(desc, sc, win, ptrs, pitches, pstrides, bstrides, torch.cuda.current_stream(device).cuda_stream)
     return out
@@ -115,4 +86,4 @@ def export_residual(call, seq, device, n, form="planes", components=(0, 1, 2), s
 
 def c_args(ptrs, pitches, pstrides, bstrides):
     """the ctypes arguments (dst[3], pitch[3], plane stride[3], batch stride[3]) of the C entry points"""
-    return ((C.c_void_p * 3)(*ptrs), (C.c_int64 * 3)(*pitches), (C.c_int64 * 3)(*pstrides), (C.c_int64 * 3)(*bstrides))
+    return (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(pstrides), abi.i64_array(bstrides))
