@@ -93,6 +93,7 @@ typedef struct hmgpu_export_window hmgpu_export_window;
 typedef struct hmgpu_export_pixel hmgpu_export_pixel;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
+typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -142,6 +143,14 @@ int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_pictur
                                    const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
                                    const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
                                    int on_stream, void* stream);
+/* Up to 16 output pictures kept on the device compared with planes the caller holds in device memory -- decoded against original
+ * (hmgpu_pictures_metrics with HMGPU_METRICS_REF_PLANES: records, reference planes, strides and statuses as there), under the rules of
+ * hmdec_pictures_export_residual: everything is validated before any context is given work (hmgpu_metrics_check), then each context
+ * gets one call per run of equally spaced slots.  HMGPU_METRICS_REF_PICTURES is refused (HMGPU_EUNSUPPORTED, hmdec_last_error says
+ * why): the pictures a decoder puts out are compared with the caller's planes only. */
+int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc, const void* const ref[3],
+                           const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* results,
+                           int64_t results_batch_stride_bytes, int on_stream, void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

@@ -635,6 +635,80 @@ hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* ctx, int32_t n, const h
                                               const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
                                               const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ picture metrics
+ * Finished pictures compared on the device, sample by sample, with other pictures of the context or with planes the caller holds in
+ * device memory: up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_metrics.hip) behind one
+ * hipMemsetAsync of the results, and one 64-byte record per picture and component.  Every field is an integer and exact: two calls on
+ * the same inputs give the same bytes.
+ *
+ * a: the final sample of pics[i] -- the plane set the exports read -- inside desc->crop (left, right, top, bottom in luma samples,
+ * whole chroma samples as in hmgpu_export_desc), each component at its own resolution, w_c x h_c.  All four chroma formats, 8 .. 12
+ * bits.  b, by desc->reference:
+ *   HMGPU_METRICS_REF_PICTURES  the same sample of ref_pics[i], a valid handle of the same context (it may be pics[i] itself); ref,
+ *                               ref_pitch_bytes and ref_batch_stride_bytes must be NULL, desc->ref_bytes_per_sample 0
+ *   HMGPU_METRICS_REF_PLANES    plane c of picture i at ref[c] + i * ref_batch_stride_bytes[c], rows ref_pitch_bytes[c] apart, elements
+ *                               uint8 (ref_bytes_per_sample 1: only where the coding depth of every selected component is <= 8) or
+ *                               uint16 (2), at the component's own resolution; row 0 / column 0 is the crop window's top-left sample.
+ *                               ref[c] of every selected component the format has must be given, every other one NULL; ref_pics must
+ *                               be NULL.  Alignment (to the element), strides and "all n planes inside one allocation of the context's
+ *                               device" as for the destinations of the residual export.  The planes are only read.
+ * desc->components (bit c: component c; at least one that the format has; the chroma bits of a 4:0:0 sequence are ignored).
+ * results: device memory of the context's GPU, 8-byte aligned, record (i, c) at results + i * results_batch_stride_bytes + c * 64
+ * (stride >= 192, a multiple of 8; all n * 3 records inside one allocation).  The record of a component that is not selected, or that
+ * the format lacks, is written as all zero.  d = a - b:
+ *   samples = w_c * h_c, sse = sum d^2, sad = sum |d|, differing = #(d != 0), max_abs = max |d|,
+ *   first_diff = the least y * w_c + x with d != 0 in the cropped plane, UINT64_MAX if there is none.
+ * SSIM (desc->ssim 1), the 8x8 / stride-4 integer form of x264 and FFmpeg's ssim filter: windows with their top-left at (4i, 4j) of the
+ * cropped plane, 4i + 8 <= w_c, 4j + 8 <= h_c: ((w_c >> 2) - 1) * ((h_c >> 2) - 1) of them, none when a side is below 8.  Per window, in
+ * 64-bit integers: s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b, vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2; with
+ * maxv = 2^bd - 1 of the channel type, c1 = (int64)(.01 * .01 * maxv * maxv * 64 + .5), c2 = (int64)(.03 * .03 * maxv * maxv * 64 * 63 + .5);
+ *   ssim = ((double)(2 s1 s2 + c1) * (double)(2 covar + c2)) / ((double)(s1^2 + s2^2 + c1) * (double)(vars + c2))      (binary64)
+ * and the window adds llrint(ssim * 2^32) to ssim_q32 (identical planes: exactly ssim_windows << 32).
+ * Everything is validated before anything is enqueued and a refused call leaves `results` untouched.  Stream ordering is that of
+ * hmgpu_picture_export, once per call.  The launch is not accounted in hmgpu_stats. */
+enum { HMGPU_METRICS_REF_PICTURES = 0, HMGPU_METRICS_REF_PLANES = 1 };
+typedef struct hmgpu_metrics_desc {
+  int32_t reference;           /* HMGPU_METRICS_REF_* */
+  int32_t components;          /* bit c: component c; at least one */
+  int32_t ssim;                /* 0: distortion only; 1: also SSIM */
+  int32_t ref_bytes_per_sample; /* REF_PLANES: 1 (coding depth of that channel type <= 8) or 2 (uint16); REF_PICTURES: 0 */
+  int32_t crop[4];             /* left, right, top, bottom in luma samples; must cover whole chroma samples, as in hmgpu_export_desc */
+  int32_t reserved[7];         /* 0 */
+} hmgpu_metrics_desc;
+typedef struct hmgpu_metrics_result {   /* 64 bytes, one per picture and component */
+  uint64_t samples;            /* w_c * h_c of the cropped component plane */
+  uint64_t sse;                /* sum (a - b)^2 */
+  uint64_t sad;                /* sum |a - b| */
+  uint64_t differing;          /* samples with a != b */
+  uint64_t first_diff;         /* least y * w_c + x with a != b inside the cropped plane; UINT64_MAX if none */
+  int64_t  ssim_q32;           /* sum over windows of llrint(ssim * 2^32); 0 when desc->ssim == 0 */
+  uint64_t ssim_windows;       /* windows summed; 0 when desc->ssim == 0 or the plane is smaller than 8x8 */
+  uint32_t max_abs;            /* max |a - b| */
+  uint32_t reserved;           /* 0 */
+} hmgpu_metrics_result;
+typedef struct hmgpu_metrics_plan {
+  int32_t channels[3];         /* per component: 1 = compared (selected, and the format has it), 0 = its record is all zero */
+  int32_t width[3], height[3]; /* w_c, h_c of the cropped component plane */
+  int32_t elem_bytes[3];       /* REF_PLANES: desc->ref_bytes_per_sample; REF_PICTURES: 0 */
+  int32_t row_bytes[3];        /* REF_PLANES: width * elem_bytes, the least reference pitch; REF_PICTURES: 0 */
+  int32_t result_bytes;        /* per picture: 3 * sizeof(hmgpu_metrics_result), the least results_batch_stride_bytes */
+  int64_t ssim_windows[3];     /* what the records will hold (0 when desc->ssim == 0) */
+} hmgpu_metrics_plan;
+/* validates a call's description and reports what it compares; host code, no device needed.  HMGPU_EUNSUPPORTED for a cropped component
+ * plane of 2^32 - 1 samples or more */
+hmgpu_status hmgpu_metrics_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* desc, hmgpu_metrics_plan* out);
+/* HM's PSNR of a record (TEncGOP::xCalculateAddPSNR): maxval = 255 << (bit_depth - 8), 10 * log10(maxval^2 * samples / sse), 999.99
+ * when sse == 0; host code.  NaN for a null record or a bit depth outside 8 .. 16 */
+double hmgpu_metrics_psnr(const hmgpu_metrics_result* result, int32_t bit_depth);
+hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* desc,
+                                    const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                                    const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes,
+                                    int32_t on_stream, void* stream);
+/* the validation of hmgpu_pictures_metrics alone, nothing enqueued: the status that call would give */
+hmgpu_status hmgpu_metrics_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* desc,
+                                 const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                                 const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes);
+
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->
  * TDecCu::decompressCU (TDecSlice.cpp:334, TDecCu.cpp:142,373) for the CTUs [first_ctu, first_ctu+num_ctus) of

@@ -133,6 +133,13 @@ def lib():
         L.hmgpu_residual_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ResidualDesc), C.POINTER(abi.ExportScale),
                                                        C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_metrics_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MetricsDesc), C.POINTER(abi.MetricsPlan)]
+        L.hmgpu_metrics_psnr.argtypes = [C.POINTER(abi.MetricsResult), C.c_int32]
+        L.hmgpu_metrics_psnr.restype = C.c_double
+        L.hmgpu_pictures_metrics.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                             C.c_int32, C.c_void_p]
+        L.hmgpu_metrics_check.argtypes = L.hmgpu_pictures_metrics.argtypes[:10]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -254,6 +261,16 @@ def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=N
     """what Context.export_residual with these arguments writes per picture (libhm_amd.residual.residual_plan: host code, no GPU)"""
     from . import residual
     return residual.residual_plan(seq, form, components, size, windows, flip, dtype, scale, crop, n)
+
+
+def metrics_plan(seq, reference="pictures", components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), ref_bytes_per_sample=2):
+    """what Context.metrics with these arguments compares (hmgpu_metrics_plan_for: host code, no GPU): an abi.MetricsPlan -- per
+    component width, height, SSIM windows and the least reference pitch.  reference: "pictures" or "planes" (then ref_bytes_per_sample 1 or 2)"""
+    from . import metrics
+    planes = {"pictures": False, "planes": True}[reference]
+    desc = abi.make_metrics_desc(abi.METRICS_REF_PLANES if planes else abi.METRICS_REF_PICTURES, metrics.components_mask(components),
+                                 1 if ssim else 0, ref_bytes_per_sample if planes else 0, crop)
+    return metrics.plan_for(seq, desc)
 
 
 def export_scale_taps(seq, desc, scale, chroma, axis):
@@ -566,6 +583,34 @@ class Context:
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""
         self._chk(lib().hmgpu_set_streams(self._h, n), "hmgpu_set_streams")
+
+    def metrics_into(self, pics, desc, results, results_stride, ref_pics=None, ptrs=None, pitches=None, bstrides=None, on_stream=0, stream=0):
+        """hmgpu_pictures_metrics into device memory the caller owns: `results` the address of [n][3] records, results_stride bytes
+        from picture to picture; ref_pics (handles) or ptrs / pitches / batch strides (bytes) of the reference planes"""
+        from . import metrics
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_metrics(self._h, len(pics), abi.handle_array(pics), C.byref(desc),
+                                               *metrics.c_args(ref_pics, ptrs, pitches, bstrides), abi.addr(results), results_stride, on_stream,
+                                               abi.addr(stream)), "hmgpu_pictures_metrics")
+
+    def metrics_status(self, pics, desc, results, results_stride, ref_pics=None, ptrs=None, pitches=None, bstrides=None):
+        """hmgpu_metrics_check: the status hmgpu_pictures_metrics would give these arguments; enqueues nothing"""
+        from . import metrics
+        pics = list(pics)
+        return lib().hmgpu_metrics_check(self._h, len(pics), abi.handle_array(pics), C.byref(desc),
+                                         *metrics.c_args(ref_pics, ptrs, pitches, bstrides), abi.addr(results), results_stride)
+
+    def metrics(self, pics, ref_pics=None, ref=None, components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), on_stream=True):
+        """up to 16 pictures compared on this context's GPU with other pictures of the context (ref_pics: handles) or with planar torch
+        tensors (ref: [n, h_c, w_c] per component, uint8 or uint16 / int16 storage): {"y": {...}, "cb": {...}, "cr": {...}}, per
+        component int64 tensors [n] of samples, sse, sad, differing, first_diff, ssim_q32, ssim_windows and max_abs (libhm_amd.metrics;
+        metrics.psnr / metrics.ssim turn them into HM's PSNR and the mean SSIM).  One launch on torch's current stream (on_stream) or
+        the context's own; nothing synchronises."""
+        from . import metrics
+        pics = list(pics)
+        return metrics.metrics(lambda desc, rp, ptrs, pitches, bstrides, res, rs, st:
+                               self.metrics_into(pics, desc, res, rs, rp, ptrs, pitches, bstrides, 1 if on_stream else 0, st),
+                               self.seq, self.device, len(pics), None if ref_pics is None else list(ref_pics), ref, components, ssim, crop)
 
     def download_packed(self, pic, bytes_per_sample, crop=(0, 0, 0, 0)):
         """the picture as 8- or 16-bit planes cropped by (left, right, top, bottom) luma samples"""

@@ -202,6 +202,35 @@ def make_residual_desc(form, components=7, sample_type=SAMPLE_UINT, crop=(0, 0, 
     return d
 
 
+METRICS_REF_PICTURES, METRICS_REF_PLANES = 0, 1
+METRICS_NO_DIFF = (1 << 64) - 1
+
+
+class MetricsDesc(C.Structure):
+    _fields_ = [("reference", C.c_int32), ("components", C.c_int32), ("ssim", C.c_int32), ("ref_bytes_per_sample", C.c_int32),
+                ("crop", C.c_int32 * 4), ("reserved", C.c_int32 * 7)]
+
+
+class MetricsResult(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("sse", C.c_uint64), ("sad", C.c_uint64), ("differing", C.c_uint64), ("first_diff", C.c_uint64),
+                ("ssim_q32", C.c_int64), ("ssim_windows", C.c_uint64), ("max_abs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MetricsPlan(C.Structure):
+    _fields_ = [("channels", C.c_int32 * 3), ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("elem_bytes", C.c_int32 * 3),
+                ("row_bytes", C.c_int32 * 3), ("result_bytes", C.c_int32), ("ssim_windows", C.c_int64 * 3)]
+
+
+def make_metrics_desc(reference, components=7, ssim=1, ref_bytes_per_sample=0, crop=(0, 0, 0, 0)):
+    """reference: METRICS_REF_*; components: the mask (bit c: component c); ref_bytes_per_sample: 1 / 2 with METRICS_REF_PLANES;
+    crop: (left, right, top, bottom) in luma samples"""
+    d = MetricsDesc()
+    d.reference, d.components, d.ssim, d.ref_bytes_per_sample = int(reference), int(components), int(ssim), int(ref_bytes_per_sample)
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    return d
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

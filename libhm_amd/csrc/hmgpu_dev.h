@@ -553,6 +553,29 @@ struct ResidArgs {
 };
 void launch_residual_planes(const ResidArgs& a, hipStream_t s);
 void launch_residual_dense(const ResidArgs& a, int elem, hipStream_t s);   // elem: kElemU16 (int16) / kElemF16 / kElemBF16 / kElemF32
+// picture metrics (k_metrics.hip, hmgpu_pictures_metrics): everything by value, validated on the host.  Plane class 0 is luma, class 1
+// the chroma pair (Cb and Cr from one load of the pair plane); a class with no selected component has no tiles.  Work items are
+// (picture, class, tile) in that order; workgroup g walks items [g * per, (g + 1) * per).  A tile is 2048 samples: 64 x 32 with SSIM (the
+// 4-sample apron right and below costs least on a squarish tile), 256 x 8 without (rows of 512 contiguous bytes).
+constexpr int kMetricsTileW = 64, kMetricsTileH = 32, kMetricsRowTileW = 256, kMetricsRowTileH = 8;
+// workgroups of a call: four per CU without SSIM (all resident at once), eight with (its barriers want more waves to hide behind)
+constexpr int kMetricsGrid = 1024, kMetricsGridSsim = 2048;
+struct MetricsArgs {
+  const int16_t* a[kMaxExportBatch][2];   // per picture: luma sample (crop left, crop top); Cb of the same chroma sample in the pair plane
+  const int16_t* bp[kMaxExportBatch][2];  // REF_PICTURES: the same of the reference picture
+  const uint8_t* bq[3];                   // REF_PLANES: per component (null: not compared), uint8 or uint16 elements
+  int64_t bpitch[3], bstride[3];          // bytes: row to row, picture to picture
+  uint8_t* results;                       // record (i, c) at results + i * rstride + c * 64, zeroed before the launch
+  int64_t rstride;
+  int64_t c1[2], c2[2];                   // SSIM constants per channel type
+  int32_t n, comps;                       // pictures; the component mask (only components the format has)
+  int32_t w[2], h[2], pitch[2];           // per class: the cropped plane in samples; the source pitch in int16 elements
+  int32_t tiles_x[2], tiles[2];           // per class: tiles per tile row, tiles per picture (0: class not selected)
+  int32_t per, total;                     // items per workgroup, items of the call
+  uint32_t avec[2];                       // per class, bit i: the groups of 4 samples of picture i (and of its reference picture) are aligned for one load
+  uint32_t bvec;                          // REF_PLANES, bit c: the same for the planes of component c
+};
+void launch_metrics(const MetricsArgs& a, int ref_kind, bool ssim, hipStream_t s);   // ref_kind: 0 pictures, 1 uint8 planes, 2 uint16 planes
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

@@ -1,6 +1,7 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
 // slots, window tables, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
-// and residual exports (k_export.hip, k_export_px.hip, k_export_scale.hip, k_motion.hip, k_residual.hip).
+// and residual exports and the reference planes of the picture metrics (k_export.hip, k_export_px.hip, k_export_scale.hip,
+// k_motion.hip, k_residual.hip, k_metrics.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -1237,6 +1238,141 @@ hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu
     }
     launch_residual_dense(a, elem, hs);
   }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+// ------------------------------------------------------------------------------------------------ picture metrics (k_metrics.hip)
+// hmgpu_metrics_plan_for; the plan's channels / elem_bytes / row_bytes / height describe the reference planes to strided_dst_ok
+static hmgpu_status metrics_plan(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, hmgpu_metrics_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const int fmt = seq->chroma_format, bd[2] = {seq->bit_depth_luma, seq->bit_depth_chroma};
+  if (fmt < 0 || fmt > 3 || bd[0] < 8 || bd[0] > 12 || bd[1] < 8 || bd[1] > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
+  for (int k = 0; k < 7; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->reference != HMGPU_METRICS_REF_PICTURES && d->reference != HMGPU_METRICS_REF_PLANES) return HMGPU_EINVAL;
+  if (d->components < 1 || d->components > 7 || (d->ssim != 0 && d->ssim != 1)) return HMGPU_EINVAL;
+  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
+  const int B = d->ref_bytes_per_sample;
+  if (planes ? (B != 1 && B != 2) : B != 0) return HMGPU_EINVAL;
+  const int comps = fmt == 0 ? d->components & 1 : d->components;
+  if (!comps) return HMGPU_EINVAL;                                    // (4:0:0: the chroma bits alone select nothing)
+  int W, H, csx, csy;
+  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
+  chroma_shifts(fmt, &csx, &csy);
+  for (int k = 0; k < 3; k++) {
+    if (!((comps >> k) & 1)) continue;
+    if (B == 1 && bd[k ? 1 : 0] > 8) return HMGPU_EINVAL;
+    const int w = k ? W >> csx : W, h = k ? H >> csy : H;
+    if ((int64_t)w * h >= 0xffffffffll) return HMGPU_EUNSUPPORTED;     // a lane of k_metrics keeps y * w + x in 32 bits, all ones: none
+    out->channels[k] = 1; out->width[k] = w; out->height[k] = h;
+    out->elem_bytes[k] = B; out->row_bytes[k] = w * B;
+    out->ssim_windows[k] = d->ssim && w >= 8 && h >= 8 ? (int64_t)((w >> 2) - 1) * ((h >> 2) - 1) : 0;
+  }
+  out->result_bytes = 3 * (int)sizeof(hmgpu_metrics_result);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_metrics_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, hmgpu_metrics_plan* out) {
+  const hmgpu_status st = metrics_plan(seq, d, out);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+double hmgpu_metrics_psnr(const hmgpu_metrics_result* r, int32_t bit_depth) {
+  if (!r || bit_depth < 8 || bit_depth > 16) return NAN;
+  if (!r->sse) return 999.99;
+  const int maxval = 255 << (bit_depth - 8);
+  const double ref = (double)maxval * maxval * (double)r->samples;     // (fRefValue of TEncGOP::xCalculateAddPSNR)
+  return 10.0 * std::log10(ref / (double)r->sse);
+}
+
+// everything hmgpu_pictures_metrics checks; vec: bit c: the planes of component c take whole loads of 4 elements
+static hmgpu_status metrics_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
+                                    const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, void* results, int64_t rstride,
+                                    hmgpu_metrics_plan* plan, int* vec) {
+  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = metrics_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+  *vec = 0;
+  if (d->reference == HMGPU_METRICS_REF_PICTURES) {
+    if (!ref_pics || ref || ref_pitch || ref_bstride) return HMGPU_EINVAL;
+    for (int i = 0; i < n; i++) if (!valid_pic(c, ref_pics[i])) return HMGPU_EINVAL;
+    hipSetDevice(c->device);
+  } else {
+    if (ref_pics || !ref || !ref_pitch || !ref_bstride) return HMGPU_EINVAL;
+    for (int k = 0; k < 3; k++) if (plan->channels[k] && !ref[k]) return HMGPU_EINVAL;   // (one that is not compared: strided_dst_ok refuses it)
+    const hmgpu_status st = strided_dst_ok(c, *plan, 3, n, const_cast<void* const*>(ref), ref_pitch, nullptr, ref_bstride, 0, vec);
+    if (st != HMGPU_OK) return st;
+  }
+  const int64_t rec = plan->result_bytes;
+  if (!results || (uintptr_t)results % 8 || rstride < rec || rstride % 8 || rstride > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+  if (!device_span_ok(results, (size_t)((n - 1) * rstride + rec), c->device)) return HMGPU_EINVAL;
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_metrics_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_pic ref_pics[],
+                                 const void* const ref[3], const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3],
+                                 void* results, int64_t results_batch_stride_bytes) {
+  hmgpu_metrics_plan plan;
+  int vec = 0;
+  return metrics_resolve(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes, &plan, &vec);
+}
+
+hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_pic ref_pics[],
+                                    const void* const ref[3], const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3],
+                                    void* results, int64_t results_batch_stride_bytes, int32_t on_stream, void* stream) {
+  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
+  hmgpu_metrics_plan plan;
+  int vec = 0;
+  { const hmgpu_status st = metrics_resolve(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes, &plan, &vec);
+    if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
+  MetricsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.results = static_cast<uint8_t*>(results); a.rstride = results_batch_stride_bytes;
+  const int bd[2] = {c->seq.bit_depth_luma, c->seq.bit_depth_chroma};
+  for (int k = 0; k < 2; k++) {
+    const double maxv = (double)((1 << bd[k]) - 1);
+    a.c1[k] = (int64_t)(.01 * .01 * maxv * maxv * 64 + .5);
+    a.c2[k] = (int64_t)(.03 * .03 * maxv * maxv * 64 * 63 + .5);
+    const int comp = k ? (plan.channels[1] ? 1 : 2) : 0;             // a component of the class that is compared, if any
+    if (!plan.channels[comp]) continue;
+    a.w[k] = plan.width[comp]; a.h[k] = plan.height[comp]; a.pitch[k] = c->pitch[k];
+    const int tw = d->ssim ? kMetricsTileW : kMetricsRowTileW, th = d->ssim ? kMetricsTileH : kMetricsRowTileH;
+    a.tiles_x[k] = (a.w[k] + tw - 1) / tw;
+    a.tiles[k] = a.tiles_x[k] * ((a.h[k] + th - 1) / th);
+  }
+  for (int k = 0; k < 3; k++) {
+    if (!plan.channels[k]) continue;
+    a.comps |= 1 << k;
+    if (planes) { a.bq[k] = static_cast<const uint8_t*>(ref[k]); a.bpitch[k] = ref_pitch_bytes[k]; a.bstride[k] = ref_batch_stride_bytes[k]; }
+  }
+  a.bvec = (uint32_t)vec;
+  const int x0 = d->crop[0], y0 = d->crop[2];
+  for (int i = 0; i < n; i++) {
+    for (int side = 0; side < (planes ? 1 : 2); side++) {
+      const Picture& p = c->pics[side ? ref_pics[i] : pics[i]];
+      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+      const int16_t* org[2] = {src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0, src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx)};
+      for (int k = 0; k < 2; k++) {
+        (side ? a.bp : a.a)[i][k] = org[k];
+        const size_t g = k ? 16 : 8;                                   // a group of 4 samples, of 4 pairs
+        if (side == 0) a.avec[k] |= 1u << i;
+        if ((uintptr_t)org[k] % g || ((size_t)c->pitch[k] * 2) % g) a.avec[k] &= ~(1u << i);
+      }
+    }
+  }
+  a.total = n * (a.tiles[0] + a.tiles[1]);
+  const int grid = d->ssim ? kMetricsGridSsim : kMetricsGrid;
+  a.per = (a.total + grid - 1) / grid;
+  const int64_t rec = plan.result_bytes;
+  if (n == 1 || a.rstride == rec) HIP_TRY(c, hipMemsetAsync(results, 0, (size_t)(n * rec), hs));
+  else HIP_TRY(c, hipMemset2DAsync(results, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
+  launch_metrics(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
+  if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
   return export_end(c, n, pics, on_stream, hs);
 }
 

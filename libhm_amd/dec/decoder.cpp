@@ -1115,6 +1115,43 @@ hmgpu_status Decoder::export_residual(int n, PicData* const* pics, const hmgpu_r
         return hmgpu_pictures_export_residual(c, rn, h, desc, scale, w, d, pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
+// The whole call -- description, reference planes and results of all n slots at the caller's strides -- is validated once on the first
+// run's context (its first handle standing for every slot), then every run's handles, then one hmgpu_pictures_metrics per run.
+hmgpu_status Decoder::metrics(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                              const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes, int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  if (desc->reference != HMGPU_METRICS_REF_PLANES) {
+    set_error("hmdec_pictures_metrics: decoded pictures are compared with planes of the caller (HMGPU_METRICS_REF_PLANES) only");
+    return HMGPU_EUNSUPPORTED;
+  }
+  if (!ref || !ref_pitch_bytes || !ref_batch_stride_bytes) return HMGPU_EINVAL;
+  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, nullptr);
+  auto ctx_of_run = [&](const ExportRun& r) { return gpus_.empty() ? gpu_ : gpus_[(size_t)r.home]; };
+  {
+    hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
+    for (int i = 0; i < n; i++) all[i] = runs[0].h[0];
+    const hmgpu_status st = hmgpu_metrics_check(ctx_of_run(runs[0]), n, all, desc, nullptr, ref, ref_pitch_bytes, ref_batch_stride_bytes, results,
+                                                results_batch_stride_bytes);
+    if (st != HMGPU_OK) return st;
+  }
+  for (int pass = 0; pass < 2; pass++)
+    for (const ExportRun& r : runs) {
+      const void* d[3];
+      int64_t bs[3];
+      for (int k = 0; k < 3; k++) {
+        d[k] = ref[k] ? static_cast<const char*>(ref[k]) + (int64_t)r.first * ref_batch_stride_bytes[k] : nullptr;
+        bs[k] = ref_batch_stride_bytes[k] * r.step;
+      }
+      void* res = static_cast<char*>(results) + (int64_t)r.first * results_batch_stride_bytes;
+      const int64_t rs = results_batch_stride_bytes * r.step;
+      const hmgpu_status st = pass == 0 ? hmgpu_metrics_check(ctx_of_run(r), r.n, r.h, desc, nullptr, d, ref_pitch_bytes, bs, res, rs)
+                                        : hmgpu_pictures_metrics(ctx_of_run(r), r.n, r.h, desc, nullptr, d, ref_pitch_bytes, bs, res, rs, on_stream, stream);
+      if (st != HMGPU_OK) return st;
+    }
+  return HMGPU_OK;
+}
+
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row
 bool Decoder::md5_plane_matches(const PicData* pic, int comp, int bd, const uint8_t want[16]) {
   Md5 md5;

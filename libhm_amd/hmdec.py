@@ -88,6 +88,8 @@ def lib():
         L.hmdec_pictures_export_residual.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ResidualDesc),
                                                      C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_metrics.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -253,6 +255,11 @@ class Picture:
                                     [flip] if flip or window is not None else None, dtype, scale, None, crop)
         return {k: t[0] for k, t in out.items()}
 
+    def metrics(self, ref, components=(0, 1, 2), ssim=True, crop=None):
+        """metrics_batch of this picture alone: ref the planes [h_c, w_c] per component; the fields without the batch dimension"""
+        out = metrics_batch([self], [None if t is None else t[None] for t in ref], components, ssim, crop)
+        return {k: {f: t[0] for f, t in v.items()} for k, v in out.items()}
+
 
 def _form_is_dense(form):
     from . import motion
@@ -309,6 +316,27 @@ def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=No
             raise HmgpuError(r, "hmdec_pictures_export_residual")
     return residual.export_residual(call, seq, dev, len(pictures) if n is None else n, form, components, size, windows, flip, dtype, scale, out,
                                     crop, enqueue)
+
+
+def metrics_batch(pictures, ref, components=(0, 1, 2), ssim=True, crop=None):
+    """Up to 16 pictures a decoder has put out with device output on (fetched since the last push, one sequence, one GPU) compared
+    on the device with planar torch tensors -- decoded against original (hmdec_pictures_metrics): ref a sequence of [n, h_c, w_c]
+    tensors per component, uint8 or uint16 / int16 storage; the result dict of libhm_amd.metrics, written on
+    torch.cuda.current_stream().  crop: None = the whole coded picture, "conformance", or (left, right, top, bottom)."""
+    from . import HmgpuError, metrics
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("metrics_batch: no pictures")
+    first, seq, crop = _prologue(pictures, "metrics_batch", crop, lambda: (0, 0, 0, 0))
+    dev = _device(first, "metrics_batch")
+
+    def call(desc, ref_pics, ptrs, pitches, bstrides, res, rs, st):
+        r = lib().hmdec_pictures_metrics(first.ctx, len(pictures), _handles(pictures), C.byref(desc), *metrics.c_args(None, ptrs, pitches, bstrides)[1:],
+                                         abi.addr(res), rs, 1, abi.addr(st))
+        if r != 0:
+            why = lib().hmdec_last_error(first.ctx).decode() if r == abi.HMGPU_EUNSUPPORTED else ""
+            raise HmgpuError(r, "hmdec_pictures_metrics" + (": " + why if why else ""))
+    return metrics.metrics(call, seq, dev, len(pictures), None, ref, components, ssim, crop)
 
 
 def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=None,
