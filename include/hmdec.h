@@ -91,6 +91,7 @@ typedef struct hmgpu_export_scale hmgpu_export_scale;
 typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 typedef struct hmgpu_export_window hmgpu_export_window;
 typedef struct hmgpu_export_pixel hmgpu_export_pixel;
+typedef struct hmgpu_colour_lut_desc hmgpu_colour_lut_desc;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
@@ -124,6 +125,20 @@ int hmdec_pictures_export_pixels(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int on_stream,
                                  void* stream);
+/* A colour LUT of the decoder (include/hmgpu.h "colour export"): the decoder validates the tables (hmgpu_colour_lut_check) and keeps
+ * a host copy; the LUT is created in a device context when an export first needs it there and goes with the contexts of a sequence
+ * that ends (the next sequence's contexts get it the same way).  *out: a handle of this decoder, never 0.  hmdec_colour_lut_destroy
+ * releases it everywhere; an unknown handle is HMGPU_EINVAL. */
+int hmdec_colour_lut_create(libHMDec_context* ctx, const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice,
+                            int64_t* out);
+int hmdec_colour_lut_destroy(libHMDec_context* ctx, int64_t lut);
+/* hmdec_pictures_export / _windows / _pixels (windows NULL: desc->crop; pixel NULL: three planes, else packed pixels in dst[0]) through
+ * the colour stage of `lut` (hmgpu_pictures_export_colour), under the same rules: the whole batch is validated once
+ * (hmgpu_export_colour_destination_check), then each run of slots of a device context is one call. */
+int hmdec_pictures_export_colour(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                 const hmgpu_export_pixel* pixel, int64_t lut, void* const dst[3], const int64_t pitch_bytes[3],
+                                 const int64_t batch_stride_bytes[3], int on_stream, void* stream);
 /* Motion vectors, reference POCs and block information of up to 16 pictures in one call (hmgpu_pictures_export_motion: the BLOCKS
  * grid or the DENSE per-sample form; destinations, strides and statuses as there), under the validity rule of hmdec_pictures_export:
  * every picture put out by this decoder and fetched since the last push, of one sequence and on one GPU ordinal, else HMGPU_EINVAL

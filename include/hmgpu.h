@@ -469,6 +469,73 @@ hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* ctx, int32_t n, co
                                                    const hmgpu_export_pixel* pixel, void* dst, int64_t pitch_bytes,
                                                    int64_t batch_stride_bytes);
 
+/* ------------------------------------------------------------------------------------------------ colour export
+ * A colour stage inside the RGB exports: a per-channel 1D shaper and a 3D lattice with tetrahedral interpolation,
+ * the mechanism of .cube files -- transfer change (PQ / HLG to SDR), gamut change, tone mapping and grades as one table.  The colour
+ * science stays on the host as data; the device part is integer arithmetic that tests/export_colour_ref.py restates exactly.
+ *
+ * Let D be the RGB output depth of the call (desc->bit_depth[0], or the coding luma depth when that is 0; 8 .. 16), M = 2^D - 1, and
+ * (v_r, v_g, v_b) the integers the RGB export produces for an output pixel: after the matrix, after resampling and the final clip,
+ * before the msb_aligned shift, the float map, the mirror and the packing.  A LUT has a depth (that D), an optional shaper
+ * sh[3][2^D] of uint16 and a lattice of L^3 nodes, L = 0 (shaper only) or 2 .. 65; a node is three uint16 output code values <= M.
+ * Host layout lattice[b][g][r][3], R fastest (the order of a .cube file).
+ *   1. position per channel c: with a shaper u_c = sh[c][v_c] (0 .. 65535); without, u_c = (v_c << (16 - D)) | (v_c >> (2D - 16))
+ *      (bit replication);
+ *   2. L = 0: the result is u_c (the shaper's entries are then code values <= M, checked at creation);
+ *   3. cell and fraction: t_c = u_c * (L - 1), i_c = t_c >> 16, f_c = t_c & 0xffff; so i_c <= L - 2: the last node is approached,
+ *      never indexed past;
+ *   4. tetrahedral interpolation: the three fractions in descending order f_a >= f_b >= f_c (on a tie either order gives the same
+ *      result: the differing vertex has weight 0); vertices V0 at (i_r, i_g, i_b), V1 one step along a, V2 along b as well, V3 along
+ *      c as well (the far corner); weights 65536 - f_a, f_a - f_b, f_b - f_c, f_c; per output channel
+ *         out = (sum_k w_k * V_k + 32768) >> 16
+ *      in unsigned 32-bit arithmetic (the sum stays below 2^32); no clip: a convex combination of values <= M;
+ *   5. out takes the place of v in everything the existing calls do afterwards: the msb_aligned shift, the float map
+ *      fl(fl(v * scale[k]) + bias[k]) with k the colour, the mirror, the alpha element and the channel order of packed pixels.
+ *
+ * hmgpu_colour_lut_create copies the tables from host memory into device memory of the context and returns when the copy is done;
+ * at most HMGPU_COLOUR_MAX_LUTS are live per context (HMGPU_ENOMEM beyond).  HMGPU_EINVAL (hmgpu_colour_lut_check, host code: the
+ * same rules without a context): depth outside 8 .. 16; size not 0 and not 2 .. 65; has_shaper not 0 / 1; neither shaper nor
+ * lattice; a non-zero reserved word; a null pointer that is needed; a node above M; an entry of a shaper-only LUT above M.
+ * hmgpu_colour_lut_destroy is safe while exports that read the LUT are in flight: it waits for the last of them before the memory is
+ * released (the rule of the scale-table slots).  A destroyed handle, or one of another context, gives HMGPU_EINVAL wherever used.
+ *
+ * hmgpu_pictures_export_colour is one call for every RGB form: pixel NULL three planes (dst / pitch_bytes / batch_stride_bytes per
+ * plane), else packed pixels in dst[0]; windows NULL the crop of desc; scale and tensor may be NULL.  Slot i receives what
+ * hmgpu_pictures_export / _windows / _pixels write for the same arguments, with step 5 applied.  Validation is that of the matching
+ * existing call, made by the same code with the same statuses in the same order; then, each HMGPU_EINVAL: a layout that is not RGB,
+ * a `lut` not live in this context, a LUT depth different from D.  Everything is validated before anything is enqueued and a refused
+ * call leaves the destination untouched.  One launch per call, the stream ordering of the existing calls; not accounted in
+ * hmgpu_stats. */
+enum { HMGPU_COLOUR_MAX_LUTS = 8 };
+typedef int64_t hmgpu_lut;     /* handle of a LUT of one context; 0 is never a handle */
+typedef struct hmgpu_colour_lut_desc {
+  int32_t depth;               /* D: 8 .. 16 */
+  int32_t size;                /* L: 0 (shaper only), 2 .. 65 */
+  int32_t has_shaper;          /* 0 / 1 */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_colour_lut_desc;
+/* the rules of hmgpu_colour_lut_create that need no context; host code */
+hmgpu_status hmgpu_colour_lut_check(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice);
+hmgpu_status hmgpu_colour_lut_create(hmgpu_ctx* ctx, const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice,
+                                     hmgpu_lut* out);
+hmgpu_status hmgpu_colour_lut_destroy(hmgpu_ctx* ctx, hmgpu_lut lut);
+/* the plan of the matching existing call (pixel NULL: hmgpu_export_windows_plan_for / hmgpu_export_tensor_plan_for, else
+ * hmgpu_export_pixels_plan_for) with its refusals, then: the layout not RGB, an invalid `lut` description (the rules above that
+ * need no tables), its depth different from D, each HMGPU_EINVAL; host code, no device needed */
+hmgpu_status hmgpu_export_colour_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          const hmgpu_export_tensor* tensor, int32_t n, const hmgpu_export_window windows[],
+                                          const hmgpu_export_pixel* pixel, const hmgpu_colour_lut_desc* lut, hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_colour(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                          const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                          const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel, hmgpu_lut lut,
+                                          void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                          int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_colour: the status it would give these arguments; enqueues nothing */
+hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                                   const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* pixel, hmgpu_lut lut, void* const dst[3],
+                                                   const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

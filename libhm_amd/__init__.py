@@ -114,6 +114,20 @@ def lib():
         L.hmgpu_export_pixels_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                             C.POINTER(abi.ExportPixel), C.c_void_p, C.c_int64, C.c_int64]
+        L.hmgpu_colour_lut_check.argtypes = [C.POINTER(abi.ColourLutDesc), C.c_void_p, C.c_void_p]
+        L.hmgpu_colour_lut_create.argtypes = [C.c_void_p, C.POINTER(abi.ColourLutDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.hmgpu_colour_lut_destroy.argtypes = [C.c_void_p, C.c_int64]
+        L.hmgpu_export_colour_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportTensor), C.c_int32, C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.POINTER(abi.ColourLutDesc), C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_colour.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_colour_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                            C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                            C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(C.c_void_p),
+                                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_motion_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale), C.c_int32,
                                             C.POINTER(abi.ExportWindow), C.POINTER(abi.MotionPlan)]
         L.hmgpu_pictures_export_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MotionDesc),
@@ -244,6 +258,71 @@ def export_pixels_plan(seq, desc, scale, tensor, windows, pixel):
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_pixels_plan_for")
     return plan
+
+
+def export_colour_plan(seq, desc, scale, tensor, windows, pixel, lut_desc):
+    """what a colour export writes per slot (hmgpu_export_colour_plan_for: host code, no GPU): the plan of the matching call without
+    the colour stage; lut_desc: an abi.ColourLutDesc; pixel None: planes"""
+    plan = abi.ExportPlan()
+    windows = None if windows is None else list(windows)
+    st = lib().hmgpu_export_colour_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                            len(windows) if windows is not None else 1, abi.window_array(windows), abi.ref(pixel),
+                                            abi.ref(lut_desc), C.byref(plan))
+    if st != 0:
+        raise HmgpuError(st, "hmgpu_export_colour_plan_for")
+    return plan
+
+
+def colour_lut_arrays(lattice, shaper, depth):
+    """(abi.ColourLutDesc, shaper, lattice) of a LUT as the C calls take it: lattice None or [L, L, L, 3] (b, g, r, channel), shaper
+    None or [3, 2^depth], both converted to contiguous uint16 (values outside 0 .. 65535 raise)"""
+    import numpy as np
+
+    def u16(a, what):
+        a = np.asarray(a)
+        if a.dtype != np.uint16:
+            if a.size and (a.min() < 0 or a.max() > 65535):
+                raise ValueError("%s: values outside 0 .. 65535" % what)
+            a = a.astype(np.uint16)
+        return np.ascontiguousarray(a)
+    size = 0
+    if lattice is not None:
+        lattice = u16(lattice, "lattice")
+        if lattice.ndim != 4 or lattice.shape[3] != 3 or len(set(lattice.shape[:3])) != 1:
+            raise ValueError("lattice: shape [L, L, L, 3], got %s" % (lattice.shape,))
+        size = lattice.shape[0]
+    if shaper is not None:
+        shaper = u16(shaper, "shaper")
+        if shaper.shape != (3, 1 << int(depth)):
+            raise ValueError("shaper: shape [3, %d], got %s" % (1 << int(depth), shaper.shape))
+    return abi.make_colour_lut_desc(depth, size, shaper is not None), shaper, lattice
+
+
+def colour_lut_status(lattice, shaper=None, depth=8, desc=None):
+    """hmgpu_colour_lut_check (host code, no GPU): the status hmgpu_colour_lut_create gives these tables before it looks at a
+    context; desc: an abi.ColourLutDesc in place of the one the arrays imply"""
+    d, sh, la = colour_lut_arrays(lattice, shaper, depth)
+    return lib().hmgpu_colour_lut_check(C.byref(desc if desc is not None else d), _p(sh) if sh is not None else None,
+                                        _p(la) if la is not None else None)
+
+
+class ColourLut:
+    """a colour LUT in device memory of one Context (hmgpu_colour_lut_create); close() releases it, also while exports that read it
+    are in flight"""
+
+    def __init__(self, ctx, handle, desc):
+        self.ctx, self.handle, self.depth, self.size, self.has_shaper = ctx, handle, desc.depth, desc.size, bool(desc.has_shaper)
+
+    def close(self):
+        if self.handle and self.ctx._h:
+            self.ctx._chk(lib().hmgpu_colour_lut_destroy(self.ctx._h, self.handle), "hmgpu_colour_lut_destroy")
+        self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def motion_plan(seq, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, crop=(0, 0, 0, 0), n=None):
@@ -457,6 +536,33 @@ class Context:
         return lib().hmgpu_export_pixels_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
                                                            abi.ref(pixel), abi.addr(ptr), pitch, bstride)
 
+    def colour_lut(self, lattice, shaper=None, depth=8):
+        """a ColourLut of this context (hmgpu_colour_lut_create; include/hmgpu.h "colour export"): lattice None (shaper only) or
+        [L, L, L, 3] uint16 output code values of `depth` bits indexed (b, g, r) -- the order of a .cube file -- and shaper None or
+        [3, 2^depth] uint16 positions 0 .. 65535 (shaper only: code values).  Pass it as lut= to export / export_batch; a context
+        manager."""
+        desc, sh, la = colour_lut_arrays(lattice, shaper, depth)
+        h = C.c_int64(0)
+        self._chk(lib().hmgpu_colour_lut_create(self._h, C.byref(desc), _p(sh) if sh is not None else None,
+                                                _p(la) if la is not None else None, C.byref(h)), "hmgpu_colour_lut_create")
+        return ColourLut(self, h.value, desc)
+
+    def export_colour_into(self, pics, desc, lut, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None, windows=None,
+                           pixel=None):
+        """hmgpu_pictures_export_colour into device memory the caller owns: the RGB export of export_batch_into (pixel None) or of
+        export_pixels_into (ptrs[0] / pitches[0] / bstrides[0] the one destination) through `lut`, a ColourLut or a raw handle"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_colour(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                                     abi.window_array(windows), abi.ref(pixel), getattr(lut, "handle", lut),
+                                                     abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), on_stream,
+                                                     abi.addr(stream)), "hmgpu_pictures_export_colour")
+
+    def export_colour_destination_status(self, n, desc, lut, ptrs, pitches, bstrides, scale=None, tensor=None, windows=None, pixel=None):
+        """hmgpu_export_colour_destination_check: the status hmgpu_pictures_export_colour would give; enqueues nothing"""
+        return lib().hmgpu_export_colour_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
+                                                           abi.ref(pixel), getattr(lut, "handle", lut), abi.ptr_array(ptrs),
+                                                           abi.i64_array(pitches), abi.i64_array(bstrides))
+
     def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
         """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
         return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.ptr_array(ptrs),
@@ -471,14 +577,21 @@ class Context:
                                                             abi.i64_array(pitches), abi.i64_array(bstrides))
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
-               size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None):
+               size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
+               lut=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
         gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
-        "bgra", "argb", "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels instead, alpha the A element (None: opaque)"""
+        "bgra", "argb", "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels instead, alpha the A element (None: opaque).
+        lut (layout "rgb"): a ColourLut of this context (colour_lut) of the output depth: every pixel through it before the store"""
         from . import export
+        os_ = 1 if on_stream else 0
 
         def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
+            if lut is not None:
+                plan = export_tensor_plan(self.seq, desc, sc, tensor)
+                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+                return self.export_colour_into([pic], desc, lut, ptrs, pitches, extent, os_, st, sc, tensor)
             if tensor is None:
                 return self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st, sc)
             plan = export_tensor_plan(self.seq, desc, sc, tensor)
@@ -487,11 +600,12 @@ class Context:
         return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
                                      filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
-                                     self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, 1 if on_stream else 0, st, sc, tensor))
+                                     self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, os_, st, sc, tensor) if lut is None else
+                                     self.export_colour_into([pic], desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px))
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                     pixel=None, alpha=None, memory_format=None):
+                     pixel=None, alpha=None, memory_format=None, lut=None):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -504,16 +618,22 @@ class Context:
         pixel ("rgb", "bgr", "rgba", "bgra", "argb", "abgr"; layout "rgb"): ONE tensor [N, H, W, C] of packed pixels instead
         (hmgpu_pictures_export_pixels), alpha the A element (None: opaque; an integer code value, or a float for float dtypes).
         memory_format=torch.channels_last (layout "rgb", no pixel): a [N, 3, H, W] tensor whose strides are channels-last, the bytes
-        of pixel="rgb".  out: either form, its pixels dense."""
+        of pixel="rgb".  out: either form, its pixels dense.
+        lut (layout "rgb"; any of the forms above): a ColourLut of this context (colour_lut) of the output depth -- every output
+        pixel goes through its shaper and lattice between the final clip and the store, still in the one launch
+        (hmgpu_pictures_export_colour)."""
         from . import export
         pics = list(pics)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
+        os_ = 1 if on_stream else 0
         return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
-                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, 1 if on_stream else 0, st, sc, tensor, win),
+                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, os_, st, sc, tensor, win) if lut is None else
+                                     self.export_colour_into(pics, desc, lut, ptrs, pitches, bstrides, os_, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
-                                     self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, 1 if on_stream else 0, st, sc, tensor, win))
+                                     self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, os_, st, sc, tensor, win) if lut is None else
+                                     self.export_colour_into(pics, desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px))
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

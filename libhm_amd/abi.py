@@ -154,6 +154,20 @@ def make_export_pixel(order, alpha=-1, alpha_value=1.0):
     return p
 
 
+COLOUR_MAX_LUTS = 8
+
+
+class ColourLutDesc(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("size", C.c_int32), ("has_shaper", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def make_colour_lut_desc(depth, size, has_shaper):
+    """depth: the code values' bits in and out (8 .. 16); size: nodes per axis (0: shaper only, 2 .. 65)"""
+    d = ColourLutDesc()
+    d.depth, d.size, d.has_shaper = int(depth), int(size), int(bool(has_shaper))
+    return d
+
+
 MOTION_BLOCKS, MOTION_DENSE = 0, 1
 MOTION_NO_REF = -(1 << 31)
 MOTION_DST_MV0, MOTION_DST_MV1, MOTION_DST_REF, MOTION_DST_BLOCK, MOTION_DSTS = 0, 1, 2, 3, 4

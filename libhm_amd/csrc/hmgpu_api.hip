@@ -591,6 +591,7 @@ void hmgpu_destroy(hmgpu_ctx* c) {
   for (int k = 0; k < 2; k++) if (c->exp_ev[k]) hipEventDestroy(c->exp_ev[k]);
   for (auto& sl : c->scale_slot) sl.release();
   for (auto& wb : c->window_buf) wb.release();
+  for (auto& cs : c->colour_slot) cs.release();
   if (c->hash_host) (void)hipHostFree(c->hash_host);
   for (int k = 0; k < 2; k++) if (c->lane_ev[k]) hipEventDestroy(c->lane_ev[k]);
   delete c;

@@ -462,6 +462,15 @@ void launch_export(const ExportArgs& a, hipStream_t s);
 // the RGB export of `a` as packed pixels (k_export_px.hip): one destination, dst[0] / pitch[0] / bstride[0]; a.vec: the loads only;
 // nch: 3 or 4 elements per pixel
 void launch_export_px(const ExportArgs& a, const PxOrder& po, int nch, hipStream_t s);
+// the colour stage of the RGB exports (colour_core.h, hmgpu_pictures_export_colour): one table in device memory of the context
+struct ColourLut {
+  const uint16_t* shaper;          // null, or [3][2^depth] positions 0 .. 65535 (size 0: output code values)
+  const u32x2* nodes;              // null (size 0), or [size^3] nodes {R | G << 16, B}, R fastest
+  int32_t size, depth;             // nodes per axis (0, 2 .. 65); the depth of the code values in and out
+};
+// the RGB layout of `a` with the colour stage: planes (nch 0, k_export.hip) or packed pixels (nch 3 / 4, k_export_px.hip)
+void launch_export_colour(const ExportArgs& a, const ColourLut& lut, hipStream_t s);
+void launch_export_px_colour(const ExportArgs& a, const PxOrder& po, const ColourLut& lut, int nch, hipStream_t s);
 // scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
 // memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
 // tap-major (w[tap * n + i], zero beyond count[i])
@@ -501,6 +510,8 @@ struct ScaleArgs {
 };
 // n pictures; elem: kElem*; nch: 0, or (RGB) 3 / 4 elements per packed pixel
 void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch = 0);
+// the RGB layout with the colour stage (ColourLut) in the epilogue
+void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch);
 // motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
 // arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
 // dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.

@@ -1,5 +1,5 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
-// slots, window tables, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
+// slots, window tables, colour LUTs, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
 // and residual exports and the reference planes of the picture metrics (k_export.hip, k_export_px.hip, k_export_scale.hip,
 // k_motion.hip, k_residual.hip, k_metrics.hip).
 #include "hmgpu_host.h"
@@ -786,6 +786,116 @@ static hmgpu_status export_resolve(hmgpu_ctx* c, int n, const hmgpu_export_desc*
   return HMGPU_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ colour LUTs (colour_core.h)
+// a LUT description by itself: the rules that need neither tables nor a context
+static bool colour_desc_ok(const hmgpu_colour_lut_desc* ld) {
+  if (!ld || ld->depth < 8 || ld->depth > 16 || (ld->size != 0 && (ld->size < 2 || ld->size > 65))) return false;
+  if ((ld->has_shaper != 0 && ld->has_shaper != 1) || (!ld->has_shaper && !ld->size)) return false;
+  for (int k = 0; k < 5; k++) if (ld->reserved[k]) return false;
+  return true;
+}
+
+hmgpu_status hmgpu_colour_lut_check(const hmgpu_colour_lut_desc* ld, const uint16_t* shaper, const uint16_t* lattice) {
+  if (!colour_desc_ok(ld) || (ld->has_shaper && !shaper) || (ld->size && !lattice)) return HMGPU_EINVAL;
+  const uint32_t M = (1u << ld->depth) - 1u;
+  const size_t nodes = (size_t)ld->size * ld->size * ld->size;
+  for (size_t i = 0; i < 3 * nodes; i++) if (lattice[i] > M) return HMGPU_EINVAL;
+  if (!ld->size)
+    for (size_t i = 0; i < ((size_t)3 << ld->depth); i++) if (shaper[i] > M) return HMGPU_EINVAL;
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_colour_lut_create(hmgpu_ctx* c, const hmgpu_colour_lut_desc* ld, const uint16_t* shaper, const uint16_t* lattice,
+                                     hmgpu_lut* out) {
+  if (!c || !out) return HMGPU_EINVAL;
+  *out = 0;
+  { const hmgpu_status st = hmgpu_colour_lut_check(ld, shaper, lattice); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::ColourSlot* cs = nullptr;
+  for (auto& sl : c->colour_slot) if (!sl.handle) { cs = &sl; break; }
+  if (!cs) return HMGPU_ENOMEM;
+  // device layout: the nodes, 8 bytes each {R | G << 16, B} (a vertex is one load), then the shaper as it is
+  const size_t nodes = (size_t)ld->size * ld->size * ld->size, node_bytes = align_up(8 * nodes, 256);
+  const size_t shaper_bytes = ld->has_shaper ? ((size_t)6 << ld->depth) : 0;
+  std::vector<uint32_t> blob((node_bytes + shaper_bytes + 3) / 4, 0);
+  for (size_t i = 0; i < nodes; i++) {
+    blob[2 * i] = (uint32_t)lattice[3 * i] | (uint32_t)lattice[3 * i + 1] << 16;
+    blob[2 * i + 1] = lattice[3 * i + 2];
+  }
+  if (shaper_bytes) memcpy(reinterpret_cast<char*>(blob.data()) + node_bytes, shaper, shaper_bytes);
+  hipSetDevice(c->device);
+  HIP_TRY(c, hipMalloc(&cs->dev, node_bytes + shaper_bytes));
+  if (hipMemcpy(cs->dev, blob.data(), node_bytes + shaper_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipEventCreateWithFlags(&cs->done, hipEventDisableTiming) != hipSuccess) {
+    c->last_err = (int32_t)hipGetLastError();
+    cs->release();
+    return HMGPU_EDEVICE;
+  }
+  cs->lut.nodes = nodes ? reinterpret_cast<const u32x2*>(cs->dev) : nullptr;
+  cs->lut.shaper = shaper_bytes ? reinterpret_cast<const uint16_t*>(cs->dev + node_bytes) : nullptr;
+  cs->lut.size = ld->size; cs->lut.depth = ld->depth;
+  // handles are unique in the process, so that one of another context never names a LUT of this one
+  static std::atomic<int64_t> next{1};
+  cs->handle = next.fetch_add(1);
+  *out = cs->handle;
+  return HMGPU_OK;
+}
+
+static hmgpu_ctx::ColourSlot* colour_find(hmgpu_ctx* c, hmgpu_lut lut) {
+  if (lut <= 0) return nullptr;
+  for (auto& sl : c->colour_slot) if (sl.handle == lut) return &sl;
+  return nullptr;
+}
+
+hmgpu_status hmgpu_colour_lut_destroy(hmgpu_ctx* c, hmgpu_lut lut) {
+  if (!c) return HMGPU_EINVAL;
+  hmgpu_ctx::ColourSlot* cs = colour_find(c, lut);
+  if (!cs) return HMGPU_EINVAL;
+  hipSetDevice(c->device);
+  if (cs->pending) HIP_TRY(c, hipEventSynchronize(cs->done));        // the last export that reads it
+  cs->release();
+  return HMGPU_OK;
+}
+
+// the rules a colour export adds behind the validation of the matching call: the layout, then the LUT's depth against the call's
+static hmgpu_status colour_rules(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int lut_depth) {
+  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  int ob[2];
+  out_depths(seq, d, ob);
+  return lut_depth == ob[0] ? HMGPU_OK : HMGPU_EINVAL;
+}
+static hmgpu_status colour_resolve(hmgpu_ctx* c, const hmgpu_export_desc* d, hmgpu_lut lut, hmgpu_ctx::ColourSlot** cs) {
+  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  *cs = colour_find(c, lut);
+  return *cs ? colour_rules(&c->seq, d, (*cs)->lut.depth) : HMGPU_EINVAL;
+}
+
+hmgpu_status hmgpu_export_colour_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, hmgpu_export_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  int elem = 0;
+  bool differ = false;
+  hmgpu_status st = px ? hmgpu_export_pixels_plan_for(seq, d, sc, t, n, win, px, out)
+                  : win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+  if (st != HMGPU_OK) return st;
+  if (d->layout != HMGPU_EXPORT_RGB) st = HMGPU_EINVAL;
+  else if (!colour_desc_ok(ld)) st = HMGPU_EINVAL;
+  else st = colour_rules(seq, d, ld->depth);
+  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, void* const dst[3],
+                                                   const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  { const hmgpu_status st = export_resolve(c, n, d, sc, t, windows, px, dst, pitch_bytes, batch_stride_bytes, false, &r); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::ColourSlot* cs = nullptr;
+  return colour_resolve(c, d, lut, &cs);
+}
+
 hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
                                             const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
                                             const int64_t batch_stride_bytes[3]) {
@@ -870,12 +980,14 @@ extern "C" {
 static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* sc,
                                 const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
                                 int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr,
-                                const hmgpu_export_pixel* px = nullptr) {
+                                const hmgpu_export_pixel* px = nullptr, const hmgpu_lut* lut = nullptr) {
   if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   ExportCall r;
   { const hmgpu_status st = export_resolve(c, n, desc, sc, t, win, px, dst, pitch_bytes, bstride, true, &r); if (st != HMGPU_OK) return st; }
   const hmgpu_export_desc* d = &r.d;
+  hmgpu_ctx::ColourSlot* cs = nullptr;                 // the colour stage (hmgpu_pictures_export_colour): its rules come last
+  if (lut) { const hmgpu_status st = colour_resolve(c, desc, *lut, &cs); if (st != HMGPU_OK) return st; }
   hipStream_t hs = c->stream;
   { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
@@ -895,8 +1007,16 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     a.w = r.plan.width[0]; a.h = r.plan.height[0];
     a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
     export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-    if (px) launch_export_px(a, r.po, r.nch, hs);
-    else launch_export(a, hs);
+    if (cs) {
+      if (px) launch_export_px_colour(a, r.po, cs->lut, r.nch, hs);
+      else launch_export_colour(a, cs->lut, hs);
+      HIP_TRY(c, hipEventRecord(cs->done, hs));
+      cs->pending = true;
+    } else if (px) {
+      launch_export_px(a, r.po, r.nch, hs);
+    } else {
+      launch_export(a, hs);
+    }
     return export_end(c, n, pics, on_stream, hs);
   }
   const ScaleShape& s = r.s;
@@ -937,7 +1057,13 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
   if (px) a.px = r.po;
   export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-  launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  if (cs) {
+    launch_export_scaled_colour(a, cs->lut, r.elem, n, hs, r.nch);
+    HIP_TRY(c, hipEventRecord(cs->done, hs));
+    cs->pending = true;
+  } else {
+    launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  }
   HIP_TRY(c, hipEventRecord(tables->done, hs));
   tables->pending = true;
   return export_end(c, n, pics, on_stream, hs);
@@ -975,6 +1101,14 @@ hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* c, int32_t n, const hmgpu_p
   void* const dst3[3] = {dst, nullptr, nullptr};
   const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
   return export_impl(c, n, pics, d, sc, t, dst3, pitch3, bstride3, on_stream, stream, windows, px);
+}
+
+hmgpu_status hmgpu_pictures_export_colour(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          hmgpu_lut lut, void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                          int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, &lut);
 }
 
 // ------------------------------------------------------------------------------------------------ side information: what motion and residual share

@@ -148,6 +148,21 @@ struct hmgpu_ctx {
   static constexpr int kWindowBufs = 4;
   TableBuf window_buf[kWindowBufs];
   int window_next = 0;
+  // hmgpu_colour_lut_create: the live LUTs (nodes, then the shaper, in one device allocation); `done` as for the tables above, and
+  // hmgpu_colour_lut_destroy waits for it before the memory goes
+  struct ColourSlot {
+    int64_t handle = 0;                  // 0: free
+    char* dev = nullptr;
+    ColourLut lut = {};
+    bool pending = false;
+    hipEvent_t done = nullptr;
+    void release() {
+      if (done) hipEventDestroy(done);
+      if (dev) (void)hipFree(dev);
+      handle = 0; dev = nullptr; done = nullptr; pending = false;
+    }
+  };
+  ColourSlot colour_slot[HMGPU_COLOUR_MAX_LUTS];
   uint64_t xfer_bytes = 0;
   uint32_t* dl_fault = nullptr;        // [32] page-locked: the picture's fault word (k_intra's bounded spin) as it stood behind the copies of ticket t
   std::vector<int> touched;            // pictures the entry point under way has enqueued work on, in any role (commit_use)

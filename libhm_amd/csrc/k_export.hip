@@ -7,8 +7,10 @@
 // the grid's y, the pictures of a batch along z (each with its own origin, alignment and mirror flag: hmgpu_pictures_export_windows), no LDS.  One instance per layout and output element (1- or 2-byte unsigned, float16,
 // bfloat16, float32: hmgpu_dev.h export_store4), so nothing per sample branches on either.  The source planes
 // keep at least 128 samples of margin right of the picture, so the loads of the last group of a row never leave the allocation;
-// only its stores are cut to the row.
+// only its stores are cut to the row.  The RGB layout has a second instance family with the colour stage of colour_core.h between the clip
+// and the store (hmgpu_pictures_export_colour).
 #include "hmgpu_dev.h"
+#include "colour_core.h"
 
 namespace hmgpu {
 
@@ -30,8 +32,10 @@ __device__ inline void load4(const int16_t* p, bool vec, int v[4]) {
 
 }  // namespace
 
-template <int LAYOUT, int ELEM>
-__global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
+// LUT: nothing, or one ColourLut -- the colour stage (colour_core.h) between the clip and the store of the RGB layout, an instance
+// family of its own (launch_export_colour); the instances without it have the one argument and hold no trace of it
+template <int LAYOUT, int ELEM, class... LUT>
+__global__ void __launch_bounds__(256) k_export(const ExportArgs a, const LUT... lut) {
   constexpr int BYTES = elem_bytes<ELEM>();
   const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
   const int r = blockIdx.y, pic = blockIdx.z;
@@ -84,6 +88,7 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
         B[i] = (uint32_t)min(M, max(0, (t + a.coef[8] * cu) >> S));
       }
     }
+    if constexpr (sizeof...(LUT) != 0) colour_map4(lut..., R, G, B);
     // (identity: G carries the luma container shift, B and R the chroma one; the matrix: all three the luma one)
     const int mc = a.coef[10] ? a.msb[1] : a.msb[0];
     export_store_row<ELEM>(d0 + r * a.pitch[0], x, a.w, R, n, vec, flip, mc, a.scale[0], a.bias[0]);
@@ -108,6 +113,18 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a) {
   } else {                                // the pairs as they lie: two groups of four samples
     export_store_pairs<ELEM>(d1 + rc * a.pitch[1], x, a.cw, o, n, vec, flip, a.msb[1]);
   }
+}
+
+void launch_export_colour(const ExportArgs& a, const ColourLut& lut, hipStream_t s) {
+  const dim3 grid((unsigned)(((a.w + 3) / 4 + 255) / 256), (unsigned)a.h, (unsigned)a.n), block(256);
+#define HMGPU_EXPORT_COLOUR_CASE(E) \
+  if (a.elem == E) hipLaunchKernelGGL((k_export<HMGPU_EXPORT_RGB, E, ColourLut>), grid, block, 0, s, a, lut);
+  HMGPU_EXPORT_COLOUR_CASE(kElemU8)
+  HMGPU_EXPORT_COLOUR_CASE(kElemU16)
+  HMGPU_EXPORT_COLOUR_CASE(kElemF16)
+  HMGPU_EXPORT_COLOUR_CASE(kElemBF16)
+  HMGPU_EXPORT_COLOUR_CASE(kElemF32)
+#undef HMGPU_EXPORT_COLOUR_CASE
 }
 
 void launch_export(const ExportArgs& a, hipStream_t s) {

@@ -6,8 +6,10 @@
 // the lane's 4 pixels are 12 .. 64 contiguous bytes, written as dword stores (hmgpu_dev.h export_store_px) where the group's first byte
 // is dword aligned, so the lanes of a wave write one contiguous run (768 bytes for 1-byte RGB).  The alignment of the loads (the crop's left edge: ExportArgs::vec) and of the
 // stores (the destination: PxOrder::vst, and the group's byte offset) are separate conditions.  One instance per output element and
-// pixel size; the channel order is two launch-uniform flags applied with selects.
+// pixel size; the channel order is two launch-uniform flags applied with selects.  A second instance family runs the colour stage of
+// colour_core.h between the clip and the store (hmgpu_pictures_export_colour).
 #include "hmgpu_dev.h"
+#include "colour_core.h"
 
 namespace hmgpu {
 
@@ -29,8 +31,10 @@ __device__ inline void load4(const int16_t* p, bool vec, int v[4]) {
 
 }  // namespace
 
-template <int ELEM, int NCH>
-__global__ void __launch_bounds__(256) k_export_px(const ExportArgs a, const PxOrder po) {
+// LUT: nothing, or one ColourLut -- the colour stage (colour_core.h) between the clip and the store, an instance family of its own
+// (launch_export_px_colour)
+template <int ELEM, int NCH, class... LUT>
+__global__ void __launch_bounds__(256) k_export_px(const ExportArgs a, const PxOrder po, const LUT... lut) {
   const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
   const int r = blockIdx.y, pic = blockIdx.z;
   if (x >= a.w) return;
@@ -68,10 +72,24 @@ __global__ void __launch_bounds__(256) k_export_px(const ExportArgs a, const PxO
       B[i] = (uint32_t)min(M, max(0, (t + a.coef[8] * cu) >> S));
     }
   }
+  if constexpr (sizeof...(LUT) != 0) colour_map4(lut..., R, G, B);
   // (identity: G carries the luma container shift, B and R the chroma one; the matrix: all three the luma one)
   const int mc = a.coef[10] ? a.msb[1] : a.msb[0];
   export_store_px<ELEM, NCH>(a.dst[0] + pic * a.bstride[0] + r * a.pitch[0], x, a.w, R, G, B, n, po.vst != 0, flip, mc, a.msb[0],
                              a.scale, a.bias, po);
+}
+
+void launch_export_px_colour(const ExportArgs& a, const PxOrder& po, const ColourLut& lut, int nch, hipStream_t s) {
+  const dim3 grid((unsigned)(((a.w + 3) / 4 + 255) / 256), (unsigned)a.h, (unsigned)a.n), block(256);
+#define HMGPU_EXPORT_PX_COLOUR_CASE(E) \
+  if (a.elem == E && nch == 3) hipLaunchKernelGGL((k_export_px<E, 3, ColourLut>), grid, block, 0, s, a, po, lut); \
+  if (a.elem == E && nch == 4) hipLaunchKernelGGL((k_export_px<E, 4, ColourLut>), grid, block, 0, s, a, po, lut);
+  HMGPU_EXPORT_PX_COLOUR_CASE(kElemU8)
+  HMGPU_EXPORT_PX_COLOUR_CASE(kElemU16)
+  HMGPU_EXPORT_PX_COLOUR_CASE(kElemF16)
+  HMGPU_EXPORT_PX_COLOUR_CASE(kElemBF16)
+  HMGPU_EXPORT_PX_COLOUR_CASE(kElemF32)
+#undef HMGPU_EXPORT_PX_COLOUR_CASE
 }
 
 void launch_export_px(const ExportArgs& a, const PxOrder& po, int nch, hipStream_t s) {

@@ -14,10 +14,12 @@
 // After the last pass the sums are rounded, clipped and stored, 4 or 8 bytes per plane and lane where aligned.  No intermediate
 // leaves the workgroup.  One instance per layout and output element (hmgpu_dev.h export_store4); the class, and the channels with
 // it, is uniform per workgroup.  Packed pixels (hmgpu_pictures_export_pixels): an instance family of the RGB layout whose epilogue
-// writes the lane's four columns x 3 or 4 elements as one run of bytes (hmgpu_dev.h export_store_px).
+// writes the lane's four columns x 3 or 4 elements as one run of bytes (hmgpu_dev.h export_store_px).  The colour stage
+// (hmgpu_pictures_export_colour): k_export_scale_colour, the RGB layout with colour_core.h's colour_map4 between the clip and the store.
 // Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
 // margin on both sides, and the tables never point at them.
 #include "hmgpu_dev.h"
+#include "colour_core.h"
 
 namespace hmgpu {
 
@@ -31,9 +33,10 @@ __device__ inline void unpack8(const u32x4 w, int v[8]) {
   for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(w[i] & 0xffff); v[2 * i + 1] = (int16_t)(w[i] >> 16); }
 }
 
-// C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane; NCH: 0, or (C = 3) the elements of a packed pixel
-template <int LAYOUT, int ELEM, int C, int NCH = 0>
-__device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds) {
+// C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane; NCH: 0, or (C = 3) the elements of a packed pixel;
+// COL (C = 3): the colour stage (colour_core.h) between the final clip and the store
+template <int LAYOUT, int ELEM, int C, int NCH = 0, bool COL = false>
+__device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds, const ColourLut* lut = nullptr) {
   constexpr int BYTES = elem_bytes<ELEM>();
   constexpr int G = C == 2 ? 4 : 8;                       // samples per 16-byte group
   const int pic = blockIdx.y;
@@ -171,6 +174,7 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
   uint32_t o[C][4];
   for (int c = 0; c < C; c++)
     for (int q = 0; q < 4; q++) o[c][q] = (uint32_t)min(M, max(0, (acc[c][q] + vrnd) >> vsh));
+  if constexpr (COL) colour_map4(*lut, o[0], o[1], o[C - 1]);
   const int x = ox0 + vx, y = oy0 + vy, n = min(4, k.tx.n - x);
   const bool vec = a.vec != 0, flip = (a.flip >> pic) & 1;    // the mirror: columns x .. x + 3 reversed to W - 1 - x ..
   const int W = k.tx.n;
@@ -202,6 +206,29 @@ __global__ void __launch_bounds__(256) k_export_scale(const ScaleArgs a) {
   if (LAYOUT == HMGPU_EXPORT_RGB) scale_tile<LAYOUT, ELEM, 3, NCH>(a, k, b, lds);
   else if (c == 0) scale_tile<LAYOUT, ELEM, 1>(a, k, b, lds);
   else scale_tile<LAYOUT, ELEM, 2>(a, k, b - a.cls[0].blocks, lds);
+}
+
+// the RGB layout with the colour stage: planes (NCH 0) or packed pixels
+template <int ELEM, int NCH>
+__global__ void __launch_bounds__(256) k_export_scale_colour(const ScaleArgs a, const ColourLut lut) {
+  __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
+  ScaleClass k = a.cls[0];
+  if (a.pic_cls) k = a.pic_cls[2 * blockIdx.y];
+  scale_tile<HMGPU_EXPORT_RGB, ELEM, 3, NCH, true>(a, k, blockIdx.x, lds, &lut);
+}
+
+void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch) {
+  const dim3 grid((unsigned)a.cls[0].blocks, (unsigned)n), block(256);
+#define HMGPU_SCALE_COLOUR_CASE(E) \
+  if (elem == E && nch == 0) hipLaunchKernelGGL((k_export_scale_colour<E, 0>), grid, block, 0, s, a, lut); \
+  if (elem == E && nch == 3) hipLaunchKernelGGL((k_export_scale_colour<E, 3>), grid, block, 0, s, a, lut); \
+  if (elem == E && nch == 4) hipLaunchKernelGGL((k_export_scale_colour<E, 4>), grid, block, 0, s, a, lut);
+  HMGPU_SCALE_COLOUR_CASE(kElemU8)
+  HMGPU_SCALE_COLOUR_CASE(kElemU16)
+  HMGPU_SCALE_COLOUR_CASE(kElemF16)
+  HMGPU_SCALE_COLOUR_CASE(kElemBF16)
+  HMGPU_SCALE_COLOUR_CASE(kElemF32)
+#undef HMGPU_SCALE_COLOUR_CASE
 }
 
 void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch) {

@@ -245,6 +245,7 @@ void Decoder::activate(const SliceHeader& sh) {
   for (size_t d = gpus_.size(); d-- > 0;) hmgpu_destroy(gpus_[d]);
   gpus_.clear();
   gpu_ = nullptr;
+  for (auto& l : luts_) l.second.dev.clear();              // (the device copies went with the contexts)
   zscan_.init(sps_->log2_ctb);
   memset(&seq_, 0, sizeof(seq_));
   seq_.width = sps_->width;
@@ -1039,9 +1040,34 @@ hmgpu_status Decoder::export_pics_ok(int n, PicData* const* pics) {
 hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                        const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
-                                       const hmgpu_export_pixel* pixel) {
+                                       const hmgpu_export_pixel* pixel, const int64_t* lut) {
   if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  if (lut) {
+    // the colour stage: the whole batch validated once in the first picture's context, then one call per run of slots, each with the
+    // LUT's handle in its own context
+    auto it = luts_.find(*lut);
+    if (it == luts_.end()) return HMGPU_EINVAL;
+    hmgpu_lut h = 0;
+    { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
+    { const hmgpu_status st = hmgpu_export_colour_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, h, dst, pitch_bytes, batch_stride_bytes);
+      if (st != HMGPU_OK) return st; }
+    const std::vector<ExportRun> runs = export_runs(n, pics, windows);
+    for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
+    for (const ExportRun& r : runs) {
+      void* d[3];
+      int64_t bs[3];
+      for (int k = 0; k < 3; k++) {
+        d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+        bs[k] = batch_stride_bytes[k] * r.step;
+      }
+      (void)colour_lut_on(it->second, r.home, &h);
+      const hmgpu_status st = hmgpu_pictures_export_colour(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, scale, tensor,
+                                                           windows ? r.w : nullptr, pixel, h, d, pitch_bytes, bs, on_stream, stream);
+      if (st != HMGPU_OK) return st;
+    }
+    return HMGPU_OK;
+  }
   // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
   // one hmgpu_pictures_export per run of slots (export_runs).
   { const hmgpu_status st = pixel ? hmgpu_export_pixels_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, dst[0], pitch_bytes[0], batch_stride_bytes[0])
@@ -1061,6 +1087,41 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
                                     : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
     if (st != HMGPU_OK) return st;
   }
+  return HMGPU_OK;
+}
+
+hmgpu_status Decoder::colour_lut_create(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice, int64_t* out) {
+  if (!out) return HMGPU_EINVAL;
+  *out = 0;
+  { const hmgpu_status st = hmgpu_colour_lut_check(desc, shaper, lattice); if (st != HMGPU_OK) return st; }
+  ColourLutHost l;
+  l.desc = *desc;
+  const size_t nodes = (size_t)desc->size * desc->size * desc->size;
+  if (desc->has_shaper) l.shaper.assign(shaper, shaper + ((size_t)3 << desc->depth));
+  if (nodes) l.lattice.assign(lattice, lattice + 3 * nodes);
+  *out = next_lut_++;
+  luts_.emplace(*out, std::move(l));
+  return HMGPU_OK;
+}
+
+hmgpu_status Decoder::colour_lut_on(ColourLutHost& l, int home, hmgpu_lut* out) {
+  const size_t k = gpus_.empty() ? 0 : (size_t)home;
+  if (l.dev.size() <= k) l.dev.resize(k + 1, 0);
+  if (!l.dev[k]) {
+    const hmgpu_status st = hmgpu_colour_lut_create(gpus_.empty() ? gpu_ : gpus_[k], &l.desc, l.shaper.empty() ? nullptr : l.shaper.data(),
+                                                    l.lattice.empty() ? nullptr : l.lattice.data(), &l.dev[k]);
+    if (st != HMGPU_OK) { l.dev[k] = 0; return st; }
+  }
+  *out = l.dev[k];
+  return HMGPU_OK;
+}
+
+hmgpu_status Decoder::colour_lut_destroy(int64_t lut) {
+  auto it = luts_.find(lut);
+  if (it == luts_.end()) return HMGPU_EINVAL;
+  for (size_t k = 0; k < it->second.dev.size(); k++)
+    if (it->second.dev[k]) (void)hmgpu_colour_lut_destroy(gpus_.empty() ? gpu_ : gpus_[k], it->second.dev[k]);
+  luts_.erase(it);
   return HMGPU_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -75,7 +76,11 @@ class Decoder {
   hmgpu_status export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr,
-                               const hmgpu_export_pixel* pixel = nullptr);
+                               const hmgpu_export_pixel* pixel = nullptr, const int64_t* lut = nullptr);
+  // colour LUTs (hmgpu_colour_lut_create): the host copy lives here, the device copies are made per context when an export first
+  // needs one (lut of export_pictures: hmgpu_pictures_export_colour) and go with the contexts of a sequence that ends
+  hmgpu_status colour_lut_create(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice, int64_t* out);
+  hmgpu_status colour_lut_destroy(int64_t lut);
   // hmgpu_pictures_export_motion under the rules of export_pictures; the side information lies in the context that decoded a picture
   hmgpu_status export_motion(int n, PicData* const* pics, const hmgpu_motion_desc* desc, const hmgpu_export_scale* scale,
                              const hmgpu_export_window* windows, void* const dst_mv[2], void* dst_ref, void* dst_block,
@@ -131,6 +136,14 @@ class Decoder {
   uint64_t rr_ = 0;                                        // round-robin position of the next batch
   uint64_t transfer_bytes_closed_ = 0;                     // ... of the contexts of earlier sequences
   hmgpu_seq_params seq_{};
+  struct ColourLutHost {
+    hmgpu_colour_lut_desc desc;
+    std::vector<uint16_t> shaper, lattice;
+    std::vector<hmgpu_lut> dev;                            // per context of gpus_: its handle there, 0 before the first use
+  };
+  std::map<int64_t, ColourLutHost> luts_;
+  int64_t next_lut_ = 1;
+  hmgpu_status colour_lut_on(ColourLutHost& l, int home, hmgpu_lut* out);   // the LUT's handle in context `home`, created when first asked for
   std::vector<std::unique_ptr<PicData>> pool_;            // DPB + free buffers
   std::vector<std::unique_ptr<PicData>> retired_;         // pictures of the previous sequence the application may still hold
   PicData* cur_ = nullptr;

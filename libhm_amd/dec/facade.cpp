@@ -339,6 +339,24 @@ int hmdec_pictures_export_pixels(libHMDec_context* ctx, int n, libHMDec_picture*
   const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
   return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst3, pitch3, bstride3, on_stream, stream, windows, pixel);
 }
+int hmdec_colour_lut_create(libHMDec_context* ctx, const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice,
+                            int64_t* out) {
+  if (!ctx) return HMGPU_EINVAL;
+  return static_cast<Wrapper*>(ctx)->dec.colour_lut_create(desc, shaper, lattice, out);
+}
+int hmdec_colour_lut_destroy(libHMDec_context* ctx, int64_t lut) {
+  if (!ctx) return HMGPU_EINVAL;
+  return static_cast<Wrapper*>(ctx)->dec.colour_lut_destroy(lut);
+}
+int hmdec_pictures_export_colour(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                 const hmgpu_export_pixel* pixel, int64_t lut, void* const dst[3], const int64_t pitch_bytes[3],
+                                 const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut);
+}
 int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_motion_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,
                                  void* dst_block, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],

@@ -408,3 +408,199 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
         stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
         call(desc, sc, tensor, ptrs, pitches, bstrides, stream)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ colour LUTs (host side: data for the device)
+# The colour stage of the RGB exports (include/hmgpu.h "colour export") takes any table; what follows builds tables on the host in
+# float64 -- from a .cube file, or from H.273 colour descriptions -- and rounds them once to the code values of the output depth.
+def _round_codes(x, depth):
+    """x in [0, 1] (clipped) to code values of `depth` bits, half away from zero"""
+    m = float((1 << depth) - 1)
+    return np.floor(np.clip(np.asarray(x, np.float64), 0.0, 1.0) * m + 0.5).astype(np.uint16)
+
+
+def load_cube(path, depth=8):
+    """(lattice, shaper) of a .cube text file for Context.colour_lut(lattice, shaper, depth): LUT_3D_SIZE L gives lattice
+    [L, L, L, 3] indexed (b, g, r) -- the file's order, R fastest -- of code values of `depth` bits, rounded half away from zero; an
+    optional LUT_1D_SIZE table (its rows before the 3D ones) is resampled to 2^depth entries per channel by linear interpolation in
+    float64 and gives the shaper: positions 0 .. 65535 in front of a lattice, code values on its own (then lattice is None).
+    DOMAIN_MIN / DOMAIN_MAX other than 0 / 1, a size outside 2 .. 65 or a wrong number of rows raise ValueError."""
+    n1 = n3 = 0
+    rows = []
+    with open(path) as f:
+        for raw in f:
+            line = raw.split("#", 1)[0].strip()
+            if not line:
+                continue
+            key = line.split()[0].upper()
+            if key == "TITLE":
+                continue
+            if key == "LUT_1D_SIZE":
+                n1 = int(line.split()[1])
+            elif key == "LUT_3D_SIZE":
+                n3 = int(line.split()[1])
+            elif key in ("DOMAIN_MIN", "DOMAIN_MAX"):
+                want = 0.0 if key == "DOMAIN_MIN" else 1.0
+                if [float(v) for v in line.split()[1:]] != [want] * 3:
+                    raise ValueError("%s: %s other than %g %g %g is not supported" % (path, key, want, want, want))
+            elif key[0].isalpha():
+                raise ValueError("%s: unknown keyword %s" % (path, key))
+            else:
+                vals = [float(v) for v in line.split()]
+                if len(vals) != 3:
+                    raise ValueError("%s: a table row holds three numbers: %r" % (path, line))
+                rows.append(vals)
+    if not n1 and not n3:
+        raise ValueError("%s: neither LUT_1D_SIZE nor LUT_3D_SIZE" % path)
+    if (n3 and not 2 <= n3 <= 65) or (n1 and n1 < 2):
+        raise ValueError("%s: LUT_3D_SIZE 2 .. 65, LUT_1D_SIZE 2 or more" % path)
+    if len(rows) != n1 + n3 ** 3:
+        raise ValueError("%s: %d table rows, the sizes ask for %d" % (path, len(rows), n1 + n3 ** 3))
+    rows = np.asarray(rows, np.float64).reshape(-1, 3)
+    lattice = shaper = None
+    if n1:
+        x = np.arange(1 << depth, dtype=np.float64) / float((1 << depth) - 1)
+        curve = np.stack([np.interp(x, np.linspace(0.0, 1.0, n1), rows[:n1, c]) for c in range(3)])
+        shaper = _round_codes(curve, 16 if n3 else depth)
+    if n3:
+        lattice = _round_codes(rows[n1:], depth).reshape(n3, n3, n3, 3)
+    return lattice, shaper
+
+
+# H.273 colour_primaries: the chromaticities (x, y) of R, G, B; the white point of all three is D65
+PRIMARIES = {1: ((0.640, 0.330), (0.300, 0.600), (0.150, 0.060)),       # BT.709
+             9: ((0.708, 0.292), (0.170, 0.797), (0.131, 0.046)),       # BT.2020
+             12: ((0.680, 0.320), (0.265, 0.690), (0.150, 0.060))}      # P3-D65
+D65 = (0.3127, 0.3290)
+SDR_GAMMA = (1, 6, 14, 15)            # transfer_characteristics shown with the BT.1886 display gamma 2.4
+PQ, HLG, SRGB, LINEAR = 16, 18, 13, 8
+HLG_LW, HLG_GAMMA = 1000.0, 1.2
+_PQ_M1, _PQ_M2, _PQ_C1, _PQ_C2, _PQ_C3 = 2610.0 / 16384, 2523.0 / 4096 * 128, 3424.0 / 4096, 2413.0 / 4096 * 32, 2392.0 / 4096 * 32
+_HLG_A = 0.17883277
+_HLG_B, _HLG_C = 1.0 - 4.0 * _HLG_A, 0.5 - _HLG_A * np.log(4.0 * _HLG_A)
+
+
+def rgb_to_xyz(primaries):
+    """the 3x3 matrix from linear RGB of an H.273 colour_primaries code to XYZ, white D65 at Y = 1"""
+    if primaries not in PRIMARIES:
+        raise ValueError("colour_primaries %r: one of %s" % (primaries, sorted(PRIMARIES)))
+    xyz = np.array([[x / y, 1.0, (1.0 - x - y) / y] for x, y in PRIMARIES[primaries]], np.float64).T
+    white = np.array([D65[0] / D65[1], 1.0, (1.0 - D65[0] - D65[1]) / D65[1]], np.float64)
+    return xyz * np.linalg.solve(xyz, white)[None, :]
+
+
+def primaries_matrix(src, dst):
+    """linear RGB of primaries `src` to linear RGB of `dst` through XYZ"""
+    return np.linalg.solve(rgb_to_xyz(dst), rgb_to_xyz(src))
+
+
+def pq_eotf(e):
+    """ST 2084: the non-linear value 0 .. 1 to cd/m2 (absolute, 10000 at 1)"""
+    p = np.power(np.clip(np.asarray(e, np.float64), 0.0, 1.0), 1.0 / _PQ_M2)
+    return 10000.0 * np.power(np.maximum(p - _PQ_C1, 0.0) / (_PQ_C2 - _PQ_C3 * p), 1.0 / _PQ_M1)
+
+
+def pq_inverse_eotf(l):
+    y = np.power(np.clip(np.asarray(l, np.float64), 0.0, 10000.0) / 10000.0, _PQ_M1)
+    return np.power((_PQ_C1 + _PQ_C2 * y) / (1.0 + _PQ_C3 * y), _PQ_M2)
+
+
+def hlg_inverse_oetf(e):
+    """BT.2100 HLG: the non-linear value 0 .. 1 to scene light 0 .. 1 (0.5 -> 1/12)"""
+    e = np.clip(np.asarray(e, np.float64), 0.0, 1.0)
+    return np.where(e <= 0.5, e * e / 3.0, (np.exp((np.maximum(e, 0.5) - _HLG_C) / _HLG_A) + _HLG_B) / 12.0)
+
+
+def hlg_oetf(s):
+    s = np.clip(np.asarray(s, np.float64), 0.0, 1.0)
+    return np.where(s <= 1.0 / 12.0, np.sqrt(3.0 * s), _HLG_A * np.log(np.maximum(12.0 * s - _HLG_B, 1e-300)) + _HLG_C)
+
+
+def to_display_light(rgb, primaries, transfer, white):
+    """non-linear R'G'B' [..., 3] in 0 .. 1 of an H.273 transfer_characteristics code to display light in cd/m2"""
+    rgb = np.clip(np.asarray(rgb, np.float64), 0.0, 1.0)
+    if transfer in SDR_GAMMA:
+        return white * np.power(rgb, 2.4)
+    if transfer == SRGB:
+        return white * np.where(rgb <= 0.04045, rgb / 12.92, np.power((rgb + 0.055) / 1.055, 2.4))
+    if transfer == LINEAR:
+        return white * rgb
+    if transfer == PQ:
+        return pq_eotf(rgb)
+    if transfer == HLG:                                               # inverse OETF, then the OOTF on the scene luminance
+        scene = hlg_inverse_oetf(rgb)
+        ys = scene @ rgb_to_xyz(primaries)[1]
+        return HLG_LW * np.power(np.maximum(ys, 1e-300), HLG_GAMMA - 1.0)[..., None] * scene
+    raise ValueError("transfer_characteristics %r: one of 1, 6, 14, 15, 13, 8, 16, 18" % (transfer,))
+
+
+def from_display_light(light, primaries, transfer, white):
+    """the inverse of to_display_light, the result clipped to 0 .. 1"""
+    light = np.maximum(np.asarray(light, np.float64), 0.0)
+    if transfer in SDR_GAMMA:
+        return np.power(np.clip(light / white, 0.0, 1.0), 1.0 / 2.4)
+    if transfer == SRGB:
+        v = np.clip(light / white, 0.0, 1.0)
+        return np.where(v <= 0.0031308, v * 12.92, 1.055 * np.power(v, 1.0 / 2.4) - 0.055)
+    if transfer == LINEAR:
+        return np.clip(light / white, 0.0, 1.0)
+    if transfer == PQ:
+        return pq_inverse_eotf(light)
+    if transfer == HLG:
+        d = light / HLG_LW
+        yd = d @ rgb_to_xyz(primaries)[1]
+        return hlg_oetf(np.power(np.maximum(yd, 1e-300), (1.0 - HLG_GAMMA) / HLG_GAMMA)[..., None] * d)
+    raise ValueError("transfer_characteristics %r: one of 1, 6, 14, 15, 13, 8, 16, 18" % (transfer,))
+
+
+def transfer_peak(transfer, white):
+    """the luminance in cd/m2 of code value 1.0"""
+    return 10000.0 if transfer == PQ else HLG_LW if transfer == HLG else float(white)
+
+
+def bt2390_eetf(y, src_peak, dst_peak):
+    """BT.2390's EETF on luminances y in cd/m2 (black at 0): the knee and Hermite roll-off in the PQ domain"""
+    lw, mx = pq_inverse_eotf(src_peak), pq_inverse_eotf(dst_peak)
+    if mx >= lw:
+        return np.asarray(y, np.float64)
+    e1 = pq_inverse_eotf(y) / lw
+    max_lum = mx / lw
+    ks = 1.5 * max_lum - 0.5
+    t = np.clip((e1 - ks) / (1.0 - ks), 0.0, 1.0)
+    p = (2 * t ** 3 - 3 * t ** 2 + 1) * ks + (t ** 3 - 2 * t ** 2 + t) * (1.0 - ks) + (-2 * t ** 3 + 3 * t ** 2) * max_lum
+    return pq_eotf(np.where(e1 < ks, e1, p) * lw)
+
+
+def colour_lut(src, dst, depth, size=33, white=203.0, peak=None, tone="clip"):
+    """(lattice, shaper) for Context.colour_lut that takes non-linear R'G'B' of src = (colour_primaries, transfer_characteristics) to
+    dst = (...), H.273 codes: primaries 1 (BT.709), 9 (BT.2020), 12 (P3-D65); transfers 1 / 6 / 14 / 15 (BT.1886 display gamma
+    2.4, code 1.0 = `white` cd/m2), 13 (sRGB), 8 (linear), 16 (ST 2084, absolute), 18 (HLG: inverse OETF, then the BT.2100 OOTF with
+    Lw = 1000 and gamma 1.2).  Node n of an axis stands for the value n / (size - 1); per node, in float64: display light in cd/m2,
+    the gamut matrix through XYZ (D65), the tone rule, the destination's inverse curve, a clip to 0 .. 1, and code values of
+    `depth` bits rounded half away from zero.  tone "clip": nothing before that clip; "bt2390": BT.2390's EETF from `peak` (None:
+    the source's own, 10000 / 1000 / white) to the destination's peak on the luminance in destination primaries, R, G and B scaled
+    by the ratio.  src == dst with tone "clip" is the identity lattice.  No shaper is built (None)."""
+    if tone not in ("clip", "bt2390"):
+        raise ValueError("tone %r: \"clip\" or \"bt2390\"" % (tone,))
+    if not 2 <= size <= 65 or not 8 <= depth <= 16:
+        raise ValueError("size 2 .. 65, depth 8 .. 16")
+    (sp, st), (dp, dt) = (int(v) for v in src), (int(v) for v in dst)
+    m_to, m_gamut = rgb_to_xyz(dp), primaries_matrix(sp, dp)          # (raises on unknown primaries)
+    axis = np.arange(size, dtype=np.float64) / float(size - 1)
+    b, g, r = np.meshgrid(axis, axis, axis, indexing="ij")
+    rgb = np.stack([r, g, b], axis=-1)
+    if (sp, st) == (dp, dt) and tone == "clip":
+        return _round_codes(rgb, depth), None
+    light = to_display_light(rgb, sp, st, white) @ m_gamut.T
+    if tone == "bt2390":
+        y = np.maximum(light @ m_to[1], 0.0)
+        mapped = bt2390_eetf(y, float(peak) if peak is not None else transfer_peak(st, white), transfer_peak(dt, white))
+        light = light * np.where(y > 0.0, mapped / np.maximum(y, 1e-300), 1.0)[..., None]
+    return _round_codes(from_display_light(light, dp, dt, white), depth), None
+
+
+def vui_source(primaries, transfer):
+    """(colour_primaries, transfer_characteristics) of a picture's VUI as colour_lut's src; unspecified or unknown codes raise"""
+    if primaries not in PRIMARIES or transfer not in SDR_GAMMA + (PQ, HLG, SRGB, LINEAR):
+        raise ValueError("the stream's colour description (primaries %r, transfer %r) names no source for a colour LUT: give src=" % (primaries, transfer))
+    return int(primaries), int(transfer)

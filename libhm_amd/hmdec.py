@@ -81,6 +81,12 @@ def lib():
         L.hmdec_pictures_export_pixels.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                    C.POINTER(abi.ExportPixel), C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+        L.hmdec_colour_lut_create.argtypes = [C.c_void_p, C.POINTER(abi.ColourLutDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.hmdec_colour_lut_destroy.argtypes = [C.c_void_p, C.c_int64]
+        L.hmdec_pictures_export_colour.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_export_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MotionDesc),
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
                                                    C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
@@ -229,7 +235,7 @@ class Picture:
             raise HmgpuError(st, name)
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None):
+               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None, lut=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
@@ -237,10 +243,12 @@ class Picture:
         "bilinear", "bicubic", "area"), None = the crop's size; out: a tensor (or tuple of planes) of the planned shape to write
         instead of new ones; dtype: torch.float16 / bfloat16 / float32 gives normalised float elements (export_batch with one
         picture, without the batch dimension; mean / std / scale / bias as there); pixel ("rgb", "bgr", "rgba", "bgra", "argb",
-        "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels, alpha its A element (None: opaque).  Valid until the next push
-        into the decoder."""
+        "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels, alpha its A element (None: opaque).  lut (layout "rgb"): a
+        colour LUT of the picture's decoder (Decoder.colour_lut) of the output depth, or "sdr": the LUT export.colour_lut builds
+        from the stream's own colour description (VUI primaries and transfer; unspecified codes raise) to BT.709 with the sRGB
+        curve, tone-mapped with BT.2390, made once per decoder, source and depth.  Valid until the next push into the decoder."""
         return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias,
-                       pixel=pixel, alpha=alpha)
+                       pixel=pixel, alpha=alpha, lut=lut)
 
     def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
         """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
@@ -364,14 +372,28 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
 
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
-            scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None):
+            scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None, lut=None):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
     the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
     windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
-    (export.make_pixel, hmdec_pictures_export_pixels)"""
+    (export.make_pixel, hmdec_pictures_export_pixels); lut: a DecoderColourLut, a raw handle or "sdr"
+    (hmdec_pictures_export_colour)"""
     from . import HmgpuError, export, export_tensor_plan
     first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
+    if isinstance(lut, str):
+        if lut != "sdr":
+            raise ValueError("lut: a colour LUT of the decoder, or \"sdr\"")
+        depth = bit_depth if isinstance(bit_depth, int) else (bit_depth or (0, 0))[0]
+        lut = _sdr_lut(first.ctx, export.vui_source(col["primaries"], col["transfer"]), depth or seq.bit_depth_luma) if enqueue else 0
+    handle = getattr(lut, "handle", lut)
+
+    def colour_call(desc, sc, tensor, px, ptrs, pitches, bstrides, st):
+        r = lib().hmdec_pictures_export_colour(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
+                                               abi.window_array(win), abi.ref(px), handle, abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                               abi.i64_array(bstrides), 1, abi.addr(st))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_colour")
     matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
     dev = _device(first, "export")
     win = export.make_windows(seq, crop, windows, flip, n if not enqueue else len(pictures))
@@ -379,11 +401,13 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
         if not enqueue:
             return None
-        if tensor is None and bstrides is None:
+        if tensor is None and bstrides is None and lut is None:
             return first.export_into(desc, ptrs, pitches, 1, st, sc)
         if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
             plan = export_tensor_plan(seq, desc, sc, tensor)
             bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+        if lut is not None:
+            return colour_call(desc, sc, tensor, None, ptrs, pitches, bstrides, st)
         head = (first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor))
         tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
         if win is not None:
@@ -396,6 +420,8 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
         if not enqueue:
             return None
+        if lut is not None:
+            return colour_call(desc, sc, tensor, px, [ptr], [pitch], [bstride], st)
         r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
                                                abi.window_array(win), C.byref(px), abi.addr(ptr), pitch, bstride, 1, abi.addr(st))
         if r != 0:
@@ -407,19 +433,62 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                  filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                 pixel=None, alpha=None, memory_format=None):
+                 pixel=None, alpha=None, memory_format=None, lut=None):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
     of Picture.export (crop and colour are taken from the first picture) and of libhm_amd.Context.export_batch (dtype, mean, std;
     windows: one (x, y, w, h) per picture relative to crop, flip: one boolean per picture -- hmdec_pictures_export_windows;
     pixel / alpha: one [N, H, W, C] tensor of packed pixels, memory_format=torch.channels_last: [N, 3, H, W] with channels-last
-    strides -- hmdec_pictures_export_pixels)."""
+    strides -- hmdec_pictures_export_pixels; lut: a colour LUT of the pictures' decoder, Decoder.colour_lut, or "sdr" as in
+    Picture.export -- hmdec_pictures_export_colour)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
-                   scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format)
+                   scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format, lut=lut)
+
+
+class DecoderColourLut:
+    """a colour LUT of one Decoder (hmdec_colour_lut_create): the decoder keeps the tables and makes the device copies itself;
+    close() releases it"""
+
+    def __init__(self, ctx, handle, desc):
+        self.ctx, self.handle, self.depth, self.size, self.has_shaper = ctx, handle, desc.depth, desc.size, bool(desc.has_shaper)
+
+    def close(self):
+        if self.handle and self.ctx:
+            lib().hmdec_colour_lut_destroy(self.ctx, self.handle)
+        self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _colour_lut(ctx, lattice, shaper, depth):
+    from . import HmgpuError, colour_lut_arrays
+    desc, sh, la = colour_lut_arrays(lattice, shaper, depth)
+    h = C.c_int64(0)
+    r = lib().hmdec_colour_lut_create(ctx, C.byref(desc), sh.ctypes.data_as(C.c_void_p) if sh is not None else None,
+                                      la.ctypes.data_as(C.c_void_p) if la is not None else None, C.byref(h))
+    if r != 0:
+        raise HmgpuError(r, "hmdec_colour_lut_create")
+    return DecoderColourLut(ctx, h.value, desc)
+
+
+_sdr_luts = {}     # (decoder, source, depth) -> the LUT of lut="sdr"; a decoder's entries go when it is closed
+
+
+def _sdr_lut(ctx, src, depth):
+    from . import export
+    key = (ctx, src, int(depth))
+    if key not in _sdr_luts:
+        lattice, shaper = export.colour_lut(src, (1, 13), int(depth), tone="bt2390")
+        _sdr_luts[key] = _colour_lut(ctx, lattice, shaper, int(depth))
+    return _sdr_luts[key]
 
 
 class Decoder:
@@ -445,8 +514,15 @@ class Decoder:
 
     def close(self):
         if self.ctx:
+            for key in [k for k in _sdr_luts if k[0] == self.ctx]:
+                del _sdr_luts[key]
             lib().libHMDec_free_decoder(self.ctx)
             self.ctx = None
+
+    def colour_lut(self, lattice, shaper=None, depth=8):
+        """a colour LUT of this decoder for lut= of Picture.export, export_batch and frames (libhm_amd.Context.colour_lut describes
+        the tables); it lasts across the sequences of a stream until close()"""
+        return _colour_lut(self.ctx, lattice, shaper, depth)
 
     def __enter__(self):
         return self
