@@ -354,7 +354,11 @@ hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp
   return HMGPU_OK;
 }
 
-hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages) {
+// *fused: the fused kernel ran for the batch.  Its border tiles write the margins of the SAO planes, which are these pictures' final planes:
+// the pictures are marked extended here and the caller launches no k_extend for them.  Every other route (a picture without SAO in the
+// batch, single stages, 4:2:2 / 4:4:4) leaves the margins to the caller's k_extend as before.
+hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages, bool* fused) {
+  *fused = false;
   // all three stages on pictures that all carry SAO: one pass through LDS instead of three through HBM (k_filter.hip)
   bool all_sao = stages == 7 && c->fmt == 1;            // (the fused kernel's tiles are those of 4:2:0 pictures)
   for (int i = 0; i < b.n && all_sao; i++) all_sao = c->pics[b.pic[i]].sao_any;
@@ -363,6 +367,8 @@ hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages) {
     for (int i = 0; i < b.n; i++) nofilt |= c->pics[b.pic[i]].dev.any_nofilt != 0;
     { ProfScope ps(c, K_FILTER); launch_filter_fused(c->d_pics, b, c->seq.width, c->seq.height, nofilt, c->stream); }
     HIP_TRY(c, hipGetLastError());
+    for (int i = 0; i < b.n; i++) c->pics[b.pic[i]].extended = true;
+    *fused = true;
     return HMGPU_OK;
   }
   // (4:2:2 / 4:4:4: k_deblock filters luma only, the chroma edges of the format's own grid follow from k_cfmt.hip -- per direction, as in HM)
@@ -843,8 +849,11 @@ hmgpu_status hmgpu_replay_batch(hmgpu_ctx* c, const hmgpu_pic* pics, int32_t n, 
         Batch b; memset(&b, 0, sizeof(b));
         b.n = hi - lo;
         for (int i = lo; i < hi; i++) { b.pic[i - lo] = pics[i]; b.first_ctu[i - lo] = 0; b.num_ctus[i - lo] = c->num_ctus; }
-        result = run_filter(c, b, stages & 7);
-        if (result == HMGPU_OK) {
+        // a lane's step: prep, inverse transform, luma and chroma motion compensation (run_recon), then the loop filter; the border
+        // extension follows as a launch of its own only where the fused kernel did not run (its border tiles write the margins)
+        bool fused = false;
+        result = run_filter(c, b, stages & 7, &fused);
+        if (result == HMGPU_OK && !fused) {
           { ProfScope ps(c, K_EXTEND); launch_extend(c->d_pics, b, c->seq.width, c->seq.height, c->mx[0], c->my[0], c->csx, c->csy, c->stream); }
           if (hipGetLastError() != hipSuccess) result = HMGPU_EDEVICE;
         }

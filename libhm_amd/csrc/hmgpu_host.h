@@ -249,7 +249,7 @@ hmgpu_status ensure_extended(hmgpu_ctx* c, int pic);
 
 // kernel sequencing (hmgpu_api.hip)
 hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp, bool any_cells, bool any_bi, bool any_islice);
-hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages);
+hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages, bool* fused);   // *fused: the fused kernel ran and wrote the margins
 hmgpu_status stage_sao(hmgpu_ctx* c, Picture& p, const hmgpu_pic_params* pp, const hmgpu_sao_param* sao,
                        const std::vector<uint16_t>& slice_idx, const std::vector<uint16_t>& tile_idx);
 

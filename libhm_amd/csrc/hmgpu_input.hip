@@ -669,16 +669,19 @@ hmgpu_status hmgpu_filter_pictures(hmgpu_ctx* c, int32_t n, const hmgpu_filter_j
   }
   }
   HostTimer tf(c, 5);
-  hmgpu_status st = run_filter(c, b, 7);
+  bool fused = false;
+  hmgpu_status st = run_filter(c, b, 7, &fused);
   if (st != HMGPU_OK) return st;
   for (int i = 0; i < n && st == HMGPU_OK; i++) {
     Picture& p = c->pics[jobs[i].pic];
     if (p.sao_any) st = sao_became_picture(c, jobs[i].pic);
-    p.extended = true;                   // (the batched border extension below)
+    p.extended = true;                   // (the fused kernel's border tiles, or the batched border extension below)
   }
   if (st != HMGPU_OK) return st;
-  { ProfScope ps(c, K_EXTEND); launch_extend(c->d_pics, b, c->seq.width, c->seq.height, c->mx[0], c->my[0], c->csx, c->csy, c->stream); }
-  HIP_TRY(c, hipGetLastError());
+  if (!fused) {
+    { ProfScope ps(c, K_EXTEND); launch_extend(c->d_pics, b, c->seq.width, c->seq.height, c->mx[0], c->my[0], c->csx, c->csy, c->stream); }
+    HIP_TRY(c, hipGetLastError());
+  }
   mark_use(c, b);
   return HMGPU_OK;
 }
@@ -697,13 +700,14 @@ hmgpu_status hmgpu_filter_picture_stages(hmgpu_ctx* c, hmgpu_pic cur, const hmgp
   p.filter_ready = true;
   Batch b; memset(&b, 0, sizeof(b));
   b.n = 1; b.pic[0] = cur; b.first_ctu[0] = 0; b.num_ctus[0] = c->num_ctus;
-  hmgpu_status st = run_filter(c, b, stages);
+  bool fused = false;
+  hmgpu_status st = run_filter(c, b, stages, &fused);
   if (st != HMGPU_OK) return st;
   if ((stages & 4) && p.sao_any) {
     st = sao_became_picture(c, cur);
     if (st != HMGPU_OK) return st;
   }
-  p.extended = false;
+  if (!fused) p.extended = false;        // (the fused kernel wrote the margins: nothing to launch)
   st = ensure_extended(c, cur);          // the finished picture is ready to be referenced
   commit_use(c);
   return st;

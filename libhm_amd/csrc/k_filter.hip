@@ -6,7 +6,8 @@
 // Here a workgroup owns a 64x64 luma tile (+ the 32x32 tiles of Cb and Cr), loads it ONCE with the halo the filters reach
 // through, runs vertical-edge deblocking, horizontal-edge deblocking and SAO on the copy in LDS, and writes only the SAO
 // planes: read ~1.5 x picture + BlkInfo, write 1 x picture.  The deblocked picture itself is never stored (with SAO on, the
-// SAO planes are the picture's final planes; pictures without SAO take the stand-alone path).
+// SAO planes are the picture's final planes; pictures without SAO take the stand-alone path).  A tile on the picture's edge also
+// writes the margins beside it (TComPicYuv::extendPicBorder, step 5 of the kernel): the finished picture needs no pass of k_extend.
 //
 // Halo arithmetic (luma; chroma is the same at half scale with a 1-sample filter): SAO of the tile needs deblocked samples
 // one sample around it; a deblocked sample belongs to exactly one edge per direction (edges lie on the 8x8 grid, an edge
@@ -42,7 +43,7 @@ struct FilterLds {
 struct SliceLf { int tc_off, beta_off, cb_off, cr_off; };     // the deblocking constants of one slice
 struct FPic {
   static constexpr int csx = 1, csy = 1;                      // the fused kernel runs on 4:2:0-shaped pictures only (run_filter)
-  int width, height, bd0, bd1, bd2, log2ctu, ctus_w, pitch[2], grid_w, any_nofilt, mono;
+  int width, height, bd0, bd1, bd2, log2ctu, ctus_w, pitch[2], mx, my, grid_w, any_nofilt, mono;   // mx, my: the luma margins (border tiles)
   __device__ inline int bd(int comp) const { return comp == 0 ? bd0 : comp == 1 ? bd1 : bd2; }   // (no array: a lane's component is a run-time value)
   const int16_t* rec[2];
   int16_t* sao[2];
@@ -60,6 +61,7 @@ __device__ inline FPic pic_state(const PicDev* p) {
   f.bd0 = ldc(&p->bd[0]); f.bd1 = ldc(&p->bd[1]); f.bd2 = ldc(&p->bd[2]);
   f.log2ctu = ldc(&p->log2ctu); f.ctus_w = ldc(&p->ctus_w);
   f.pitch[0] = ldc(&p->pitch[0]); f.pitch[1] = ldc(&p->pitch[1]);
+  f.mx = ldc(&p->mx[0]); f.my = ldc(&p->my[0]);
   f.grid_w = ldc(&p->grid_w);
   f.rec[0] = ldc(&p->rec[0]); f.rec[1] = ldc(&p->rec[1]);
   f.sao[0] = ldc(&p->sao[0]); f.sao[1] = ldc(&p->sao[1]);
@@ -259,6 +261,45 @@ __device__ inline void edge_apply(const FPic& P, FilterLds& L, int x0, int y0, u
   }
 }
 
+// The margins a border tile owns (TComPicYuv::extendPicBorder for the SAO planes, byte for byte what extend_plane of k_sao.hip writes):
+// `out` is the tile's FINAL samples in LDS (vw x vh valid elements, rows `opitch` int16 apart), `org` the tile's first element in the
+// plane.  el / er / et / eb: the tile holds the picture's first / last column, first / last row.  The tile's valid rectangle grows by
+// mx columns on the sides it is an edge of and by my rows likewise; every element of the grown rectangle outside the valid one is the
+// nearest valid element, and no other tile writes it (left and right bands over the tile's rows, bands above and below over its
+// columns, the corner blocks with the corner tiles).  E = int16 elements per picture element (1 luma, kCStep chroma: the (Cb, Cr) pair).
+// All 256 threads store 16-byte pieces: 16 lanes along a row of the side bands, 8 along a row of the bands above and below.
+template <int E>
+__device__ inline void put_margins(const int16_t* out, int opitch, int16_t* org, int pitch, int vw, int vh, bool el, bool er, bool et, bool eb,
+                                   int mx, int my, int t) {
+  constexpr int VE = 8 / E;                                   // elements per 16-byte vector
+  const int xl = el ? mx : 0, yt = et ? my : 0;               // margin columns / rows in front of the tile's first
+  const int rows = yt + vh + (eb ? my : 0);
+  const Span sm(org - ((ptrdiff_t)yt * pitch + E * xl), (uint32_t)(((rows - 1) * pitch + E * (xl + vw + (er ? mx : 0))) * 2));
+  // side bands, corner blocks included: rows of the grown rectangle, every vector a replica of the row's first / last valid element
+  const int nl = xl / VE, ns = nl + (er ? mx / VE : 0);
+  for (int r = t >> 4; r < rows; r += 16) {
+    const int16_t* line = out + clip3(0, vh - 1, r - yt) * opitch;
+    for (int k = t & 15; k < ns; k += 16) {
+      const bool right = k >= nl;
+      const int16_t* e = line + E * (right ? vw - 1 : 0);
+      uint32_t v;
+      if constexpr (E == 1) v = (uint16_t)e[0] * 0x10001u;
+      else v = *reinterpret_cast<const uint32_t*>(e);
+      const int x = right ? xl + vw + (k - nl) * VE : k * VE;
+      sm.store4((uint32_t)((r * pitch + E * x) * 2), u32x4{v, v, v, v});
+    }
+  }
+  // bands above and below the tile's columns: replicas of its first / last valid row
+  const int nt = yt, nb = nt + (eb ? my : 0);
+  const int k = t & 7;
+  if (k * VE < vw)
+    for (int r = t >> 3; r < nb; r += 32) {
+      const bool below = r >= nt;
+      const u32x4 v = *reinterpret_cast<const u32x4*>(out + (below ? vh - 1 : 0) * opitch + 8 * k);
+      sm.store4((uint32_t)(((below ? vh + r : r) * pitch + E * xl + 8 * k) * 2), v);
+    }
+}
+
 }  // namespace
 
 // NF: the variant for batches in which some picture holds lossless / unfiltered PCM CUs (chosen on the host)
@@ -344,19 +385,45 @@ __global__ void __launch_bounds__(256) k_filter_fused(const PicDev* __restrict__
   __syncthreads();
   // ---- 4. SAO of the tile from the deblocked copy, stored relative to the tile's first sample in the SAO planes
   const Span oy(P.sao[0] + ((ptrdiff_t)y0 * p0 + x0), (uint32_t)(((kTH - 1) * p0 + kTW) * 2));
-  if (lin[0]) oy.store4((uint32_t)((gy * p0 + gx) * 2), sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[0], sl0));
-  if (lin[1]) oy.store4((uint32_t)(((gy + 32) * p0 + gx) * 2), sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[1], sl1));
+  // the thread's final samples: border tiles use them again below.  (Threads without a group never look at theirs: any value serves, so
+  // the empty statement stands for one, and no instruction of the interior tiles' path sets it.)
+  u32x4 fy0, fy1, fc;
+  asm("" : "=v"(fy0), "=v"(fy1), "=v"(fc));
+  if (lin[0]) { fy0 = sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[0], sl0); oy.store4((uint32_t)((gy * p0 + gx) * 2), fy0); }
+  if (lin[1]) { fy1 = sao_group<kYW, NF>(P, 0, L.y, x0 - 8, y0 - 4, lx, ly[1], sl1); oy.store4((uint32_t)(((gy + 32) * p0 + gx) * 2), fy1); }
   if (cin) {
     const u32x4 own = sao_group<kCW, NF>(P, ccomp, L.c[ccomp - 1], (x0 >> 1) - 8, (y0 >> 1) - 2, ccx, ccy, sc0);
     // the even lane (Cb) writes positions 0..3 of the group, the odd lane (Cr) positions 4..7: each hands the other the half it does not write
     const bool odd = t & 1;
     const uint32_t r0 = (uint32_t)__shfl_xor((int)(odd ? own.x : own.z), 1, 64), r1 = (uint32_t)__shfl_xor((int)(odd ? own.y : own.w), 1, 64);
     const uint32_t cb0 = odd ? r0 : own.x, cb1 = odd ? r1 : own.y, cr0 = odd ? own.z : r0, cr1 = odd ? own.w : r1;
-    const u32x4 o = {__builtin_amdgcn_perm(cr0, cb0, 0x05040100u), __builtin_amdgcn_perm(cr0, cb0, 0x07060302u),
-                     __builtin_amdgcn_perm(cr1, cb1, 0x05040100u), __builtin_amdgcn_perm(cr1, cb1, 0x07060302u)};
+    fc = u32x4{__builtin_amdgcn_perm(cr0, cb0, 0x05040100u), __builtin_amdgcn_perm(cr0, cb0, 0x07060302u),
+               __builtin_amdgcn_perm(cr1, cb1, 0x05040100u), __builtin_amdgcn_perm(cr1, cb1, 0x07060302u)};
     const Span oc(P.sao[1] + ((ptrdiff_t)(y0 >> 1) * p1 + kCStep * (x0 >> 1)), (uint32_t)(((kTH / 2 - 1) * p1 + kCStep * kTW / 2) * 2));
-    oc.store4((uint32_t)((gy * p1 + kCStep * (((t >> 1) & 3) * 8 + (odd ? 4 : 0))) * 2), o);
+    oc.store4((uint32_t)((gy * p1 + kCStep * (((t >> 1) & 3) * 8 + (odd ? 4 : 0))) * 2), fc);
   }
+  // ---- 5. a tile on the picture's edge writes the margins beside it (put_margins), so that no pass over the finished picture is needed
+  // before it serves as a reference.  One scalar branch for every other tile.  The final samples go where the copies were (the SAO phase
+  // has read them: barrier), luma as 64 rows of the luma copy's pitch, chroma as 32 rows of 32 (Cb, Cr) pairs, and all threads write from there.
+  const bool el = x0 == 0, er = x0 + kTW >= P.width, et = y0 == 0, eb = y0 + kTH >= P.height;
+  if (!(el || er || et || eb)) return;
+  constexpr int kFC = kCStep * kTW / 2;                             // row pitch of the final chroma pairs in LDS
+  static_assert(kTH <= kYH && kTW <= kYW && kTH / 2 * kFC * 2 <= (int)sizeof(L.c), "the final samples fit the copies' space");
+  int16_t* const fcs = &L.c[0][0][0];
+  // (the thread index as this path's own value: what is derived from it here is computed here, not hoisted in front of the branch)
+  int tb = t;
+  asm volatile("" : "+v"(tb));
+  const int by = tb >> 3, bx = (tb & 7) * 8;                        // the thread's groups again: luma (bx, by), (bx, by + 32); chroma pairs from bp
+  const int bp = ((tb >> 1) & 3) * 8 + (tb & 1) * 4;
+  __syncthreads();
+  if (lin[0]) *reinterpret_cast<u32x4*>(&L.y[by][bx]) = fy0;
+  if (lin[1]) *reinterpret_cast<u32x4*>(&L.y[by + 32][bx]) = fy1;
+  if (cin) *reinterpret_cast<u32x4*>(fcs + by * kFC + kCStep * bp) = fc;
+  __syncthreads();
+  const int vw = min(kTW, P.width - x0), vh = min(kTH, P.height - y0);
+  put_margins<1>(&L.y[0][0], kYW, P.sao[0] + ((ptrdiff_t)y0 * p0 + x0), p0, vw, vh, el, er, et, eb, P.mx, P.my, tb);
+  if (!P.mono)                                                      // (4:0:0: the chroma planes are left alone)
+    put_margins<kCStep>(fcs, kFC, P.sao[1] + ((ptrdiff_t)(y0 >> 1) * p1 + kCStep * (x0 >> 1)), p1, vw >> 1, vh >> 1, el, er, et, eb, P.mx >> 1, P.my >> 1, tb);
 }
 
 void launch_filter_fused(const PicDev* pics, const Batch& b, int width, int height, bool nofilt, hipStream_t s) {
