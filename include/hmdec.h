@@ -92,6 +92,7 @@ typedef struct hmgpu_export_tensor hmgpu_export_tensor;
 typedef struct hmgpu_export_window hmgpu_export_window;
 typedef struct hmgpu_export_pixel hmgpu_export_pixel;
 typedef struct hmgpu_colour_lut_desc hmgpu_colour_lut_desc;
+typedef struct hmgpu_export_chroma hmgpu_export_chroma;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
@@ -139,6 +140,13 @@ int hmdec_pictures_export_colour(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, int64_t lut, void* const dst[3], const int64_t pitch_bytes[3],
                                  const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+/* hmdec_pictures_export_colour with the chroma stage of `chroma` in front (hmgpu_pictures_export_chroma; include/hmgpu.h "chroma
+ * export"): lut 0 means no colour stage.  The whole batch is validated once (hmgpu_export_chroma_destination_check), then each run of
+ * slots of a device context is one call.  The caller names the sample location; hmdec_picture_chroma_loc reports the stream's. */
+int hmdec_pictures_export_chroma(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                 const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma, void* const dst[3],
+                                 const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
 /* Motion vectors, reference POCs and block information of up to 16 pictures in one call (hmgpu_pictures_export_motion: the BLOCKS
  * grid or the DENSE per-sample form; destinations, strides and statuses as there), under the validity rule of hmdec_pictures_export:
  * every picture put out by this decoder and fetched since the last push, of one sequence and on one GPU ordinal, else HMGPU_EINVAL
@@ -171,6 +179,9 @@ int hmdec_picture_device(libHMDec_picture* pic);                             /* 
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,
  * transfer_characteristics, matrix_coefficients, video_format */
 int hmdec_picture_colour(libHMDec_picture* pic, int32_t out[5]);
+/* VUI chroma sample location of the picture's SPS (E.2.1): chroma_loc_info_present_flag, chroma_sample_loc_type_top_field,
+ * chroma_sample_loc_type_bottom_field; the types are 0 when absent */
+int hmdec_picture_chroma_loc(libHMDec_picture* pic, int32_t out[3]);
 int hmdec_hash_mismatches(libHMDec_context* ctx);                             /* pictures whose reconstruction disagreed with the hash SEI */
 int hmdec_pictures_decoded(libHMDec_context* ctx);
 void hmdec_set_device_md5(libHMDec_context* ctx, int on);                     /* MD5 hash SEIs checked on the device (hmgpu_picture_hash_begin) (the default;

@@ -263,7 +263,8 @@ void* hmgpu_stream(hmgpu_ctx* ctx);
  * Bit depth of the YUV layouts (and of matrix 0), per channel type, HM 16.0 TVideoIOYuv::write with CLIP_TO_709_RANGE 0
  * (TVideoIOYuv.cpp:70-87): s = out - coding depth; s >= 0: v << s; s < 0: Clip3(0, 2^out - 1, (v + (1 << (-s - 1))) >> -s).
  * 2-byte samples are LSB-aligned, or shifted left by 16 - out when msb_aligned.  The crop window is in luma samples and must cover
- * whole chroma samples (else HMGPU_EINVAL).  RGB: the chroma sample of luma (x, y) is (x >> csx, y >> csy); 4:0:0 uses
+ * whole chroma samples (else HMGPU_EINVAL).  RGB: the chroma sample of luma (x, y) is (x >> csx, y >> csy), replicated, unless the
+ * call asks for interpolation at the signalled sample location (hmgpu_pictures_export_chroma, "chroma export" below); 4:0:0 uses
  * Cb = Cr = 1 << (bdC - 1); `matrix` takes the VUI matrix_coefficients codes 1 (BT.709), 5 / 6 (BT.601), 9 (BT.2020 non-constant
  * luminance) -- H.273's Kr / Kb equations, limited or full range (full_range) -- and 0 (identity / GBR: G = Y, B = Cb, R = Cr, then
  * the bit-depth rule; 4:4:4 only); any other code gives HMGPU_EUNSUPPORTED.  The integers the kernel uses are derived on the host
@@ -535,6 +536,57 @@ hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* ctx, int32_t n, co
                                                    const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                                    const hmgpu_export_pixel* pixel, hmgpu_lut lut, void* const dst[3],
                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
+
+/* ------------------------------------------------------------------------------------------------ chroma export
+ * A chroma stage inside the RGB exports, off by default: Cb and Cr of 4:2:0 and 4:2:2 pictures linearly interpolated
+ * to the luma grid at the chroma sample location the stream signals (VUI chroma_sample_loc_type, H.265 figure E.1), before the
+ * matrix, where the existing calls replicate each chroma sample.  Integer arithmetic that tests/export_chroma_ref.py restates exactly.
+ *
+ * Let C be one chroma component of the decoded picture, Wc x Hc samples: the whole decoded plane, not the crop or window.  Each axis
+ * yields two taps (i0, w0) and (i0 + 1, 4 - w0), weights in quarters, tap indices clamped to 0 .. size - 1.  For the luma
+ * coordinate x (or y) on an axis, with j = x >> 1:
+ *                                                     x even                    x odd
+ *   not subsampled                                    (x: 4)                    (x: 4)
+ *   subsampled, co-sited                              (j: 4)                    (j: 2, j + 1: 2)
+ *   subsampled, centred                               (j - 1: 1, j: 3)          (j: 3, j + 1: 1)
+ *   subsampled, co-sited with the odd row (bottom)    (j - 1: 2, j: 2)          (j: 4)
+ * 4:2:0 with loc = chroma_sample_loc_type: horizontally co-sited for loc 0, 2, 4 and centred for 1, 3, 5; vertically centred for
+ * loc 0, 1, co-sited for 2, 3 and bottom for 4, 5.  4:2:2: horizontally co-sited, vertically not subsampled; loc is ignored, as the
+ * standard says.  4:4:4 and 4:0:0: the stage is the identity.  The interpolated value, at the coding chroma depth, is
+ *   c' = (sum over the 2 x 2 taps of wx * wy * C[iy][ix] + 8) >> 4
+ * and takes the place of the replicated sample in everything the existing calls do afterwards: the matrix or the identity rule,
+ * resampling, the clip, the colour stage, the msb_aligned shift, the float map, the mirror and the packing.  Taps may lie outside a
+ * crop or window as long as they are inside the decoded plane, so the export of a window is the window of the whole picture's export.
+ *
+ * hmgpu_pictures_export_chroma is one call for every RGB form and takes the arguments of hmgpu_pictures_export_colour, with lut 0
+ * meaning no colour stage.  Validation is that of the matching existing call (with a lut: hmgpu_pictures_export_colour), made by the
+ * same code with the same statuses in the same order; then a layout that is not RGB (HMGPU_EINVAL); then `chroma` NULL, a non-zero
+ * reserved word or loc outside 0 .. 5 (HMGPU_EINVAL); then an unknown filter (HMGPU_EUNSUPPORTED).  Everything is validated before
+ * anything is enqueued and a refused call leaves the destination untouched.  With HMGPU_CHROMA_REPLICATE the call writes, bit for
+ * bit, what the matching existing call writes.  One launch per call; the stream ordering, the table slots and the window ring of the
+ * existing calls; not accounted in hmgpu_stats. */
+enum { HMGPU_CHROMA_REPLICATE = 0, HMGPU_CHROMA_LINEAR = 1 };
+typedef struct hmgpu_export_chroma {
+  int32_t filter;              /* HMGPU_CHROMA_* */
+  int32_t loc;                 /* chroma_sample_loc_type 0 .. 5 (4:2:0; validated and otherwise ignored for the other formats) */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_export_chroma;
+/* the plan of the matching existing call (lut NULL: hmgpu_export_pixels_plan_for / _windows_plan_for / _tensor_plan_for, else
+ * hmgpu_export_colour_plan_for) with its refusals, then the rules above; host code, no device needed */
+hmgpu_status hmgpu_export_chroma_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          const hmgpu_export_tensor* tensor, int32_t n, const hmgpu_export_window windows[],
+                                          const hmgpu_export_pixel* pixel, const hmgpu_colour_lut_desc* lut,
+                                          const hmgpu_export_chroma* chroma, hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                          const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                          const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel, hmgpu_lut lut,
+                                          const hmgpu_export_chroma* chroma, void* const dst[3], const int64_t pitch_bytes[3],
+                                          const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_chroma: the status it would give these arguments; enqueues nothing */
+hmgpu_status hmgpu_export_chroma_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                                   const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* pixel, hmgpu_lut lut, const hmgpu_export_chroma* chroma,
+                                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
 
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --

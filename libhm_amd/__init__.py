@@ -128,6 +128,18 @@ def lib():
                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                             C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(C.c_void_p),
                                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_export_chroma_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportTensor), C.c_int32, C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.POINTER(abi.ColourLutDesc), C.POINTER(abi.ExportChroma),
+                                                   C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_chroma.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma),
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_chroma_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                            C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                            C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma),
+                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_motion_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale), C.c_int32,
                                             C.POINTER(abi.ExportWindow), C.POINTER(abi.MotionPlan)]
         L.hmgpu_pictures_export_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MotionDesc),
@@ -270,6 +282,25 @@ def export_colour_plan(seq, desc, scale, tensor, windows, pixel, lut_desc):
                                             abi.ref(lut_desc), C.byref(plan))
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_colour_plan_for")
+    return plan
+
+
+def export_chroma_status(seq, desc, scale, tensor, windows, pixel, lut_desc, chroma):
+    """(status, plan) of hmgpu_export_chroma_plan_for (host code, no GPU): the plan of the matching call without the chroma stage;
+    lut_desc None: no colour stage; chroma: an abi.ExportChroma or None"""
+    plan = abi.ExportPlan()
+    windows = list(windows) if windows is not None else None
+    st = lib().hmgpu_export_chroma_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                            len(windows) if windows is not None else 1, abi.window_array(windows), abi.ref(pixel),
+                                            abi.ref(lut_desc), abi.ref(chroma), C.byref(plan))
+    return st, plan
+
+
+def export_chroma_plan(seq, desc, scale, tensor, windows, pixel, lut_desc, chroma):
+    """what a chroma export writes per slot: export_chroma_status, a refusal raised"""
+    st, plan = export_chroma_status(seq, desc, scale, tensor, windows, pixel, lut_desc, chroma)
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_chroma_plan_for")
     return plan
 
 
@@ -563,6 +594,23 @@ class Context:
                                                            abi.ref(pixel), getattr(lut, "handle", lut), abi.ptr_array(ptrs),
                                                            abi.i64_array(pitches), abi.i64_array(bstrides))
 
+    def export_chroma_into(self, pics, desc, chroma, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None, windows=None,
+                           pixel=None, lut=None):
+        """hmgpu_pictures_export_chroma into device memory the caller owns: export_colour_into (lut None or 0: no colour stage) with the
+        chroma stage of `chroma`, an abi.ExportChroma, in front"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_chroma(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                                     abi.window_array(windows), abi.ref(pixel), getattr(lut, "handle", lut) or 0,
+                                                     abi.ref(chroma), abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides),
+                                                     on_stream, abi.addr(stream)), "hmgpu_pictures_export_chroma")
+
+    def export_chroma_destination_status(self, n, desc, chroma, ptrs, pitches, bstrides, scale=None, tensor=None, windows=None, pixel=None,
+                                         lut=None):
+        """hmgpu_export_chroma_destination_check: the status hmgpu_pictures_export_chroma would give; enqueues nothing"""
+        return lib().hmgpu_export_chroma_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
+                                                           abi.ref(pixel), getattr(lut, "handle", lut) or 0, abi.ref(chroma),
+                                                           abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides))
+
     def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
         """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
         return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.ptr_array(ptrs),
@@ -578,16 +626,23 @@ class Context:
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
-               lut=None):
+               lut=None, chroma="replicate", chroma_loc=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
         gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
         "bgra", "argb", "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels instead, alpha the A element (None: opaque).
-        lut (layout "rgb"): a ColourLut of this context (colour_lut) of the output depth: every pixel through it before the store"""
+        lut (layout "rgb"): a ColourLut of this context (colour_lut) of the output depth: every pixel through it before the store.
+        chroma (layout "rgb"): "replicate", or "linear": Cb and Cr interpolated to the luma grid at chroma_loc, the stream's
+        chroma_sample_loc_type 0 .. 5 (None: 0), before the matrix (hmgpu_pictures_export_chroma)"""
         from . import export
         os_ = 1 if on_stream else 0
+        chr_ = abi.chroma_stage(chroma, chroma_loc)
 
         def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
+            if chr_ is not None:
+                plan = export_tensor_plan(self.seq, desc, sc, tensor)
+                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+                return self.export_chroma_into([pic], desc, chr_, ptrs, pitches, extent, os_, st, sc, tensor, None, None, lut)
             if lut is not None:
                 plan = export_tensor_plan(self.seq, desc, sc, tensor)
                 extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
@@ -600,12 +655,14 @@ class Context:
         return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
                                      filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_chroma_into([pic], desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px, lut)
+                                     if chr_ is not None else
                                      self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, os_, st, sc, tensor) if lut is None else
                                      self.export_colour_into([pic], desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px))
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                     pixel=None, alpha=None, memory_format=None, lut=None):
+                     pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -621,17 +678,25 @@ class Context:
         of pixel="rgb".  out: either form, its pixels dense.
         lut (layout "rgb"; any of the forms above): a ColourLut of this context (colour_lut) of the output depth -- every output
         pixel goes through its shaper and lattice between the final clip and the store, still in the one launch
-        (hmgpu_pictures_export_colour)."""
+        (hmgpu_pictures_export_colour).
+        chroma (layout "rgb"; any of the forms above): "replicate", or "linear" -- Cb and Cr of 4:2:0 / 4:2:2 pictures interpolated
+        to the luma grid at chroma_loc (chroma_sample_loc_type 0 .. 5; None: 0) before the matrix, still in the one launch
+        (hmgpu_pictures_export_chroma).  "replicate" goes through the entries above."""
         from . import export
         pics = list(pics)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         os_ = 1 if on_stream else 0
+        chr_ = abi.chroma_stage(chroma, chroma_loc)
         return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
+                                     self.export_chroma_into(pics, desc, chr_, ptrs, pitches, bstrides, os_, st, sc, tensor, win, None, lut)
+                                     if chr_ is not None else
                                      self.export_batch_into(pics, desc, ptrs, pitches, bstrides, os_, st, sc, tensor, win) if lut is None else
                                      self.export_colour_into(pics, desc, lut, ptrs, pitches, bstrides, os_, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_chroma_into(pics, desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px, lut)
+                                     if chr_ is not None else
                                      self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, os_, st, sc, tensor, win) if lut is None else
                                      self.export_colour_into(pics, desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px))
 

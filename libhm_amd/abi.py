@@ -168,6 +168,31 @@ def make_colour_lut_desc(depth, size, has_shaper):
     return d
 
 
+CHROMA_REPLICATE, CHROMA_LINEAR = 0, 1
+CHROMA_FILTERS = {"replicate": CHROMA_REPLICATE, "linear": CHROMA_LINEAR}
+
+
+class ExportChroma(C.Structure):
+    _fields_ = [("filter", C.c_int32), ("loc", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+def make_export_chroma(filter=CHROMA_LINEAR, loc=0):
+    """filter: CHROMA_* or its name; loc: chroma_sample_loc_type 0 .. 5 (H.265 figure E.1)"""
+    c = ExportChroma()
+    c.filter, c.loc = int(CHROMA_FILTERS.get(filter, filter)), int(loc)
+    return c
+
+
+def chroma_stage(chroma, chroma_loc, default_loc=0):
+    """chroma= / chroma_loc= of the Python exports: None for "replicate" (the existing entries), else the ExportChroma of the new one;
+    chroma_loc None: default_loc"""
+    if chroma not in CHROMA_FILTERS:
+        raise ValueError("chroma: one of %s" % sorted(CHROMA_FILTERS))
+    if chroma == "replicate":
+        return None
+    return make_export_chroma(chroma, default_loc if chroma_loc is None else chroma_loc)
+
+
 MOTION_BLOCKS, MOTION_DENSE = 0, 1
 MOTION_NO_REF = -(1 << 31)
 MOTION_DST_MV0, MOTION_DST_MV1, MOTION_DST_REF, MOTION_DST_BLOCK, MOTION_DSTS = 0, 1, 2, 3, 4

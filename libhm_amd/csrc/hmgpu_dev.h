@@ -471,6 +471,17 @@ struct ColourLut {
 // the RGB layout of `a` with the colour stage: planes (nch 0, k_export.hip) or packed pixels (nch 3 / 4, k_export_px.hip)
 void launch_export_colour(const ExportArgs& a, const ColourLut& lut, hipStream_t s);
 void launch_export_px_colour(const ExportArgs& a, const PxOrder& po, const ColourLut& lut, int nch, hipStream_t s);
+// the chroma stage of the RGB exports (chroma_core.h, hmgpu_pictures_export_chroma) for 4:2:0 and 4:2:2: the weights of the signalled
+// sample location in quarters, and what clamping a tap to the decoded plane needs
+struct ChromaSite {
+  int32_t hx[2][3];                // [luma column parity]: weights of chroma columns j - 1, j, j + 1 (j = x >> 1)
+  int32_t vy[2][2];                // [luma row parity]: first row relative to j = y >> csy (-1 / 0) and its weight; row + 1 has the rest
+  int32_t wc, hc;                  // the decoded chroma plane, samples
+  int16_t x0[kMaxExportBatch], y0[kMaxExportBatch];   // unscaled: per picture, the chroma sample ExportArgs::c points at
+};
+// the RGB layout of `a` with the chroma stage, and with the colour stage as well where lut is not null
+void launch_export_chroma(const ExportArgs& a, const ChromaSite& cs, const ColourLut* lut, hipStream_t s);
+void launch_export_px_chroma(const ExportArgs& a, const PxOrder& po, const ChromaSite& cs, const ColourLut* lut, int nch, hipStream_t s);
 // scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
 // memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
 // tap-major (w[tap * n + i], zero beyond count[i])
@@ -512,6 +523,8 @@ struct ScaleArgs {
 void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch = 0);
 // the RGB layout with the colour stage (ColourLut) in the epilogue
 void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch);
+// the RGB layout with the chroma stage (ChromaSite) in the stage step, and the colour stage as well where lut is not null
+void launch_export_scaled_chroma(const ScaleArgs& a, const ChromaSite& cs, const ColourLut* lut, int elem, int n, hipStream_t s, int nch);
 // motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
 // arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
 // dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.

@@ -1,5 +1,5 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
-// slots, window tables, colour LUTs, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
+// slots, window tables, colour LUTs, the chroma stage's rules and weights, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
 // and residual exports and the reference planes of the picture metrics (k_export.hip, k_export_px.hip, k_export_scale.hip,
 // k_motion.hip, k_residual.hip, k_metrics.hip).
 #include "hmgpu_host.h"
@@ -896,6 +896,57 @@ hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* c, int32_t n, cons
   return colour_resolve(c, d, lut, &cs);
 }
 
+// ------------------------------------------------------------------------------------------------ chroma stage (chroma_core.h)
+// the rules a chroma export adds behind the validation of the matching call, in the order include/hmgpu.h "chroma export" gives
+static hmgpu_status chroma_rules(const hmgpu_export_desc* d, const hmgpu_export_chroma* ch) {
+  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (!ch || ch->loc < 0 || ch->loc > 5) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (ch->reserved[k]) return HMGPU_EINVAL;
+  if (ch->filter != HMGPU_CHROMA_REPLICATE && ch->filter != HMGPU_CHROMA_LINEAR) return HMGPU_EUNSUPPORTED;
+  return HMGPU_OK;
+}
+
+// the weights of a validated descriptor for a 4:2:0 or 4:2:2 sequence (H.265 figure E.1), in quarters
+static void chroma_site(const hmgpu_seq_params& seq, const hmgpu_export_chroma& ch, ChromaSite* s) {
+  memset(s, 0, sizeof(*s));
+  const bool f420 = seq.chroma_format == 1;
+  const bool centred = f420 && (ch.loc & 1);
+  const int32_t hx[2][2][3] = {{{0, 4, 0}, {0, 2, 2}}, {{1, 3, 0}, {0, 3, 1}}};                  // co-sited, centred
+  const int32_t vy[4][2][2] = {{{-1, 1}, {0, 3}}, {{0, 4}, {0, 2}}, {{-1, 2}, {0, 4}}, {{0, 4}, {0, 4}}};   // centred, co-sited, bottom, none
+  memcpy(s->hx, hx[centred ? 1 : 0], sizeof(s->hx));
+  memcpy(s->vy, vy[f420 ? ch.loc >> 1 : 3], sizeof(s->vy));
+  s->wc = seq.width >> 1;
+  s->hc = seq.height >> (f420 ? 1 : 0);
+}
+
+hmgpu_status hmgpu_export_chroma_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, const hmgpu_export_chroma* ch,
+                                          hmgpu_export_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  int elem = 0;
+  bool differ = false;
+  hmgpu_status st = ld ? hmgpu_export_colour_plan_for(seq, d, sc, t, n, win, px, ld, out)
+                  : px ? hmgpu_export_pixels_plan_for(seq, d, sc, t, n, win, px, out)
+                  : win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
+  if (st != HMGPU_OK) return st;
+  st = chroma_rules(d, ch);
+  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+hmgpu_status hmgpu_export_chroma_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, const hmgpu_export_chroma* ch,
+                                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  { const hmgpu_status st = export_resolve(c, n, d, sc, t, windows, px, dst, pitch_bytes, batch_stride_bytes, false, &r); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::ColourSlot* cs = nullptr;
+  if (lut) { const hmgpu_status st = colour_resolve(c, d, lut, &cs); if (st != HMGPU_OK) return st; }
+  return chroma_rules(d, ch);
+}
+
 hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
                                             const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
                                             const int64_t batch_stride_bytes[3]) {
@@ -980,7 +1031,8 @@ extern "C" {
 static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* sc,
                                 const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
                                 int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr,
-                                const hmgpu_export_pixel* px = nullptr, const hmgpu_lut* lut = nullptr) {
+                                const hmgpu_export_pixel* px = nullptr, const hmgpu_lut* lut = nullptr, bool chroma_call = false,
+                                const hmgpu_export_chroma* chroma = nullptr) {
   if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   ExportCall r;
@@ -988,6 +1040,16 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   const hmgpu_export_desc* d = &r.d;
   hmgpu_ctx::ColourSlot* cs = nullptr;                 // the colour stage (hmgpu_pictures_export_colour): its rules come last
   if (lut) { const hmgpu_status st = colour_resolve(c, desc, *lut, &cs); if (st != HMGPU_OK) return st; }
+  // the chroma stage (hmgpu_pictures_export_chroma): its rules behind those; 4:4:4 and 4:0:0, where it is the identity, and
+  // HMGPU_CHROMA_REPLICATE run the instances without it
+  ChromaSite site;
+  bool linear = false;
+  if (chroma_call) {
+    const hmgpu_status st = chroma_rules(desc, chroma);
+    if (st != HMGPU_OK) return st;
+    linear = chroma->filter == HMGPU_CHROMA_LINEAR && (c->seq.chroma_format == 1 || c->seq.chroma_format == 2);
+    if (linear) chroma_site(c->seq, *chroma, &site);
+  }
   hipStream_t hs = c->stream;
   { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
@@ -1001,13 +1063,18 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
       a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
       a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
       if ((r.vec || px) && (x0 & 3) == 0) a.vec |= 1u << i;               // (a batch may mix aligned and unaligned left edges)
+      if (linear) { site.x0[i] = (int16_t)(x0 >> c->csx); site.y0[i] = (int16_t)(y0 >> c->csy); }
     }
     a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
     a.n = n; a.layout = d->layout; a.elem = r.elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
     a.w = r.plan.width[0]; a.h = r.plan.height[0];
     a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
     export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-    if (cs) {
+    if (linear) {
+      if (px) launch_export_px_chroma(a, r.po, site, cs ? &cs->lut : nullptr, r.nch, hs);
+      else launch_export_chroma(a, site, cs ? &cs->lut : nullptr, hs);
+      if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
+    } else if (cs) {
       if (px) launch_export_px_colour(a, r.po, cs->lut, r.nch, hs);
       else launch_export_colour(a, cs->lut, hs);
       HIP_TRY(c, hipEventRecord(cs->done, hs));
@@ -1057,7 +1124,10 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
   if (px) a.px = r.po;
   export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-  if (cs) {
+  if (linear) {
+    launch_export_scaled_chroma(a, site, cs ? &cs->lut : nullptr, r.elem, n, hs, r.nch);
+    if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
+  } else if (cs) {
     launch_export_scaled_colour(a, cs->lut, r.elem, n, hs, r.nch);
     HIP_TRY(c, hipEventRecord(cs->done, hs));
     cs->pending = true;
@@ -1109,6 +1179,14 @@ hmgpu_status hmgpu_pictures_export_colour(hmgpu_ctx* c, int32_t n, const hmgpu_p
                                           int32_t on_stream, void* stream) {
   if (!batch_stride_bytes) return HMGPU_EINVAL;
   return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, &lut);
+}
+
+hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          hmgpu_lut lut, const hmgpu_export_chroma* chroma, void* const dst[3], const int64_t pitch_bytes[3],
+                                          const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!batch_stride_bytes) return HMGPU_EINVAL;
+  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, lut ? &lut : nullptr, true, chroma);
 }
 
 // ------------------------------------------------------------------------------------------------ side information: what motion and residual share

@@ -8,9 +8,11 @@
 // bfloat16, float32: hmgpu_dev.h export_store4), so nothing per sample branches on either.  The source planes
 // keep at least 128 samples of margin right of the picture, so the loads of the last group of a row never leave the allocation;
 // only its stores are cut to the row.  The RGB layout has a second instance family with the colour stage of colour_core.h between the clip
-// and the store (hmgpu_pictures_export_colour).
+// and the store (hmgpu_pictures_export_colour), and a third with the chroma stage of chroma_core.h in place of the replicated chroma
+// (hmgpu_pictures_export_chroma), with or without the colour stage.
 #include "hmgpu_dev.h"
 #include "colour_core.h"
+#include "chroma_core.h"
 
 namespace hmgpu {
 
@@ -32,10 +34,11 @@ __device__ inline void load4(const int16_t* p, bool vec, int v[4]) {
 
 }  // namespace
 
-// LUT: nothing, or one ColourLut -- the colour stage (colour_core.h) between the clip and the store of the RGB layout, an instance
-// family of its own (launch_export_colour); the instances without it have the one argument and hold no trace of it
-template <int LAYOUT, int ELEM, class... LUT>
-__global__ void __launch_bounds__(256) k_export(const ExportArgs a, const LUT... lut) {
+// X: nothing, or the stages of the RGB layout, each an instance family of its own -- a ColourLut: the colour stage (colour_core.h)
+// between the clip and the store (launch_export_colour); a ChromaSite, before it: the chroma stage (chroma_core.h) in place of the
+// replicated chroma (launch_export_chroma).  The instances without them have the one argument and hold no trace of either
+template <int LAYOUT, int ELEM, class... X>
+__global__ void __launch_bounds__(256) k_export(const ExportArgs a, const X... st) {
   constexpr int BYTES = elem_bytes<ELEM>();
   const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
   const int r = blockIdx.y, pic = blockIdx.z;
@@ -58,7 +61,26 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a, const LUT...
     }
     // RGB: the chroma of the group's four luma samples (one pair for two of them when csx = 1)
     int u[4], v[4];
-    if (a.mono) {
+    if constexpr (pack_has<ChromaSite, X...>) {
+      // the chroma stage (csx = 1): pairs J - 1 .. J + 2 of two rows, six loads none of which waits for another
+      const ChromaSite& cs = pack_get<ChromaSite>(st...);
+      const int x0 = cs.x0[pic], y0 = cs.y0[pic];
+      int ia, ib, wv;
+      chroma_rows(cs, (y0 << a.csy) + r, a.csy, &ia, &ib, &wv);
+      const int16_t* pa = ac + (ptrdiff_t)(ia - y0) * a.pitch_c + kCStep * (x >> 1);
+      const int16_t* pb = ac + (ptrdiff_t)(ib - y0) * a.pitch_c + kCStep * (x >> 1);
+      int ma[4], mb[4], ua[4], ub[4], va[4], vb[4];
+      load4(pa, vec, ma);
+      load4(pb, vec, mb);
+      chroma_pair(pa - kCStep, &ua[0], &va[0]);
+      chroma_pair(pb - kCStep, &ub[0], &vb[0]);
+      chroma_pair(pa + 2 * kCStep, &ua[3], &va[3]);
+      chroma_pair(pb + 2 * kCStep, &ub[3], &vb[3]);
+      ua[1] = ma[0]; va[1] = ma[1]; ua[2] = ma[2]; va[2] = ma[3];
+      ub[1] = mb[0]; vb[1] = mb[1]; ub[2] = mb[2]; vb[2] = mb[3];
+      chroma_line<2>(cs, x0 + (x >> 1), wv, ua, ub, u);
+      chroma_line<2>(cs, x0 + (x >> 1), wv, va, vb, v);
+    } else if (a.mono) {
       for (int i = 0; i < 4; i++) u[i] = v[i] = a.coef[3];
     } else {
       const int16_t* cp = ac + (ptrdiff_t)(r >> a.csy) * a.pitch_c + kCStep * (x >> a.csx);
@@ -88,7 +110,7 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a, const LUT...
         B[i] = (uint32_t)min(M, max(0, (t + a.coef[8] * cu) >> S));
       }
     }
-    if constexpr (sizeof...(LUT) != 0) colour_map4(lut..., R, G, B);
+    if constexpr (pack_has<ColourLut, X...>) colour_map4(pack_get<ColourLut>(st...), R, G, B);
     // (identity: G carries the luma container shift, B and R the chroma one; the matrix: all three the luma one)
     const int mc = a.coef[10] ? a.msb[1] : a.msb[0];
     export_store_row<ELEM>(d0 + r * a.pitch[0], x, a.w, R, n, vec, flip, mc, a.scale[0], a.bias[0]);
@@ -113,6 +135,19 @@ __global__ void __launch_bounds__(256) k_export(const ExportArgs a, const LUT...
   } else {                                // the pairs as they lie: two groups of four samples
     export_store_pairs<ELEM>(d1 + rc * a.pitch[1], x, a.cw, o, n, vec, flip, a.msb[1]);
   }
+}
+
+void launch_export_chroma(const ExportArgs& a, const ChromaSite& cs, const ColourLut* lut, hipStream_t s) {
+  const dim3 grid((unsigned)(((a.w + 3) / 4 + 255) / 256), (unsigned)a.h, (unsigned)a.n), block(256);
+#define HMGPU_EXPORT_CHROMA_CASE(E) \
+  if (a.elem == E && !lut) hipLaunchKernelGGL((k_export<HMGPU_EXPORT_RGB, E, ChromaSite>), grid, block, 0, s, a, cs); \
+  if (a.elem == E && lut) hipLaunchKernelGGL((k_export<HMGPU_EXPORT_RGB, E, ChromaSite, ColourLut>), grid, block, 0, s, a, cs, *lut);
+  HMGPU_EXPORT_CHROMA_CASE(kElemU8)
+  HMGPU_EXPORT_CHROMA_CASE(kElemU16)
+  HMGPU_EXPORT_CHROMA_CASE(kElemF16)
+  HMGPU_EXPORT_CHROMA_CASE(kElemBF16)
+  HMGPU_EXPORT_CHROMA_CASE(kElemF32)
+#undef HMGPU_EXPORT_CHROMA_CASE
 }
 
 void launch_export_colour(const ExportArgs& a, const ColourLut& lut, hipStream_t s) {

@@ -16,10 +16,13 @@
 // it, is uniform per workgroup.  Packed pixels (hmgpu_pictures_export_pixels): an instance family of the RGB layout whose epilogue
 // writes the lane's four columns x 3 or 4 elements as one run of bytes (hmgpu_dev.h export_store_px).  The colour stage
 // (hmgpu_pictures_export_colour): k_export_scale_colour, the RGB layout with colour_core.h's colour_map4 between the clip and the store.
+// The chroma stage (hmgpu_pictures_export_chroma): k_export_scale_chroma, whose stage step interpolates the chroma of a 16-byte group
+// (chroma_core.h) where the others replicate it; one pair left and right of the group's four come from neighbouring groups' lines.
 // Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
 // margin on both sides, and the tables never point at them.
 #include "hmgpu_dev.h"
 #include "colour_core.h"
+#include "chroma_core.h"
 
 namespace hmgpu {
 
@@ -34,9 +37,11 @@ __device__ inline void unpack8(const u32x4 w, int v[8]) {
 }
 
 // C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane; NCH: 0, or (C = 3) the elements of a packed pixel;
-// COL (C = 3): the colour stage (colour_core.h) between the final clip and the store
-template <int LAYOUT, int ELEM, int C, int NCH = 0, bool COL = false>
-__device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds, const ColourLut* lut = nullptr) {
+// COL (C = 3): the colour stage (colour_core.h) between the final clip and the store; CHR (C = 3): the chroma stage (chroma_core.h)
+// in place of the replicated chroma of the stage step
+template <int LAYOUT, int ELEM, int C, int NCH = 0, bool COL = false, bool CHR = false>
+__device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int32_t* lds, const ColourLut* lut = nullptr,
+                           const ChromaSite* site = nullptr) {
   constexpr int BYTES = elem_bytes<ELEM>();
   constexpr int G = C == 2 ? 4 : 8;                       // samples per 16-byte group
   const int pic = blockIdx.y;
@@ -89,7 +94,23 @@ __device__ void scale_tile(const ScaleArgs& a, const ScaleClass& k, int blk, int
           for (int s = 0; s < 8; s++) o[0][s] = (uint32_t)depth_conv(yv[s], a.sh[0], a.maxv[0]);
         } else {
           int u[8], v[8];
-          if (a.mono) {
+          if constexpr (CHR) {
+            // the chroma stage (csx = 1): pairs J - 1 .. J + 4 of two rows, six loads none of which waits for another
+            int ia, ib, wv;
+            chroma_rows(*site, y, a.csy, &ia, &ib, &wv);
+            const int16_t* pa = csrc + (ptrdiff_t)ia * a.pitch_c + kCStep * (x >> 1);
+            const int16_t* pb = csrc + (ptrdiff_t)ib * a.pitch_c + kCStep * (x >> 1);
+            int ma[8], mb[8], ua[6], ub[6], va[6], vb[6];
+            unpack8(ldg4(pa), ma);
+            unpack8(ldg4(pb), mb);
+            chroma_pair(pa - kCStep, &ua[0], &va[0]);
+            chroma_pair(pb - kCStep, &ub[0], &vb[0]);
+            chroma_pair(pa + 4 * kCStep, &ua[5], &va[5]);
+            chroma_pair(pb + 4 * kCStep, &ub[5], &vb[5]);
+            for (int s = 0; s < 4; s++) { ua[1 + s] = ma[2 * s]; va[1 + s] = ma[2 * s + 1]; ub[1 + s] = mb[2 * s]; vb[1 + s] = mb[2 * s + 1]; }
+            chroma_line<4>(*site, x >> 1, wv, ua, ub, u);
+            chroma_line<4>(*site, x >> 1, wv, va, vb, v);
+          } else if (a.mono) {
             for (int s = 0; s < 8; s++) u[s] = v[s] = a.coef[3];
           } else {
             const int16_t* cp = csrc + (ptrdiff_t)(y >> a.csy) * a.pitch_c + kCStep * (x >> a.csx);
@@ -215,6 +236,31 @@ __global__ void __launch_bounds__(256) k_export_scale_colour(const ScaleArgs a, 
   ScaleClass k = a.cls[0];
   if (a.pic_cls) k = a.pic_cls[2 * blockIdx.y];
   scale_tile<HMGPU_EXPORT_RGB, ELEM, 3, NCH, true>(a, k, blockIdx.x, lds, &lut);
+}
+
+// the RGB layout with the chroma stage, and (COL) the colour stage as well: planes (NCH 0) or packed pixels
+template <int ELEM, int NCH, bool COL>
+__global__ void __launch_bounds__(256) k_export_scale_chroma(const ScaleArgs a, const ChromaSite site, const ColourLut lut) {
+  __shared__ __attribute__((aligned(16))) int32_t lds[kScaleLdsBytes / 4];
+  ScaleClass k = a.cls[0];
+  if (a.pic_cls) k = a.pic_cls[2 * blockIdx.y];
+  scale_tile<HMGPU_EXPORT_RGB, ELEM, 3, NCH, COL, true>(a, k, blockIdx.x, lds, &lut, &site);
+}
+
+void launch_export_scaled_chroma(const ScaleArgs& a, const ChromaSite& cs, const ColourLut* lut, int elem, int n, hipStream_t s, int nch) {
+  const dim3 grid((unsigned)a.cls[0].blocks, (unsigned)n), block(256);
+  const ColourLut none = {};
+#define HMGPU_SCALE_CHROMA_CASE(E, N) \
+  if (elem == E && nch == N && !lut) hipLaunchKernelGGL((k_export_scale_chroma<E, N, false>), grid, block, 0, s, a, cs, none); \
+  if (elem == E && nch == N && lut) hipLaunchKernelGGL((k_export_scale_chroma<E, N, true>), grid, block, 0, s, a, cs, *lut);
+#define HMGPU_SCALE_CHROMA_ELEM(E) HMGPU_SCALE_CHROMA_CASE(E, 0) HMGPU_SCALE_CHROMA_CASE(E, 3) HMGPU_SCALE_CHROMA_CASE(E, 4)
+  HMGPU_SCALE_CHROMA_ELEM(kElemU8)
+  HMGPU_SCALE_CHROMA_ELEM(kElemU16)
+  HMGPU_SCALE_CHROMA_ELEM(kElemF16)
+  HMGPU_SCALE_CHROMA_ELEM(kElemBF16)
+  HMGPU_SCALE_CHROMA_ELEM(kElemF32)
+#undef HMGPU_SCALE_CHROMA_ELEM
+#undef HMGPU_SCALE_CHROMA_CASE
 }
 
 void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch) {

@@ -486,6 +486,8 @@ void Decoder::start_picture(const SliceHeader& sh) {
   cur_->range_ext_flags = sps_->range_ext_flags();
   cur_->colour[0] = sps_->video_full_range; cur_->colour[1] = sps_->colour_primaries; cur_->colour[2] = sps_->transfer_characteristics;
   cur_->colour[3] = sps_->matrix_coefficients; cur_->colour[4] = sps_->video_format;
+  cur_->chroma_loc[0] = sps_->chroma_loc_info_present; cur_->chroma_loc[1] = sps_->chroma_sample_loc_type_top_field;
+  cur_->chroma_loc[2] = sps_->chroma_sample_loc_type_bottom_field;
   cur_->owner = this;
   cur_->num_comps = sps_->chroma_format_idc == 0 ? 1 : 3;
   cur_->sao_offset_shift[0] = pps_->sao_offset_shift[0]; cur_->sao_offset_shift[1] = pps_->sao_offset_shift[1];
@@ -1040,9 +1042,35 @@ hmgpu_status Decoder::export_pics_ok(int n, PicData* const* pics) {
 hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                        const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                        const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
-                                       const hmgpu_export_pixel* pixel, const int64_t* lut) {
+                                       const hmgpu_export_pixel* pixel, const int64_t* lut, const hmgpu_export_chroma* const* chroma) {
   if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  if (chroma) {
+    // the chroma stage (with a LUT: the colour stage behind it): validated once in the first picture's context, then one call per
+    // run of slots, as below
+    auto it = lut && *lut ? luts_.find(*lut) : luts_.end();
+    if (lut && *lut && it == luts_.end()) return HMGPU_EINVAL;
+    const bool col = it != luts_.end();
+    hmgpu_lut h = 0;
+    if (col) { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
+    { const hmgpu_status st = hmgpu_export_chroma_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, h, *chroma, dst, pitch_bytes, batch_stride_bytes);
+      if (st != HMGPU_OK) return st; }
+    const std::vector<ExportRun> runs = export_runs(n, pics, windows);
+    if (col) for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
+    for (const ExportRun& r : runs) {
+      void* d[3];
+      int64_t bs[3];
+      for (int k = 0; k < 3; k++) {
+        d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+        bs[k] = batch_stride_bytes[k] * r.step;
+      }
+      if (col) (void)colour_lut_on(it->second, r.home, &h);
+      const hmgpu_status st = hmgpu_pictures_export_chroma(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, scale, tensor,
+                                                           windows ? r.w : nullptr, pixel, h, *chroma, d, pitch_bytes, bs, on_stream, stream);
+      if (st != HMGPU_OK) return st;
+    }
+    return HMGPU_OK;
+  }
   if (lut) {
     // the colour stage: the whole batch validated once in the first picture's context, then one call per run of slots, each with the
     // LUT's handle in its own context

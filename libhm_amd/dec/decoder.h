@@ -76,7 +76,8 @@ class Decoder {
   hmgpu_status export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
                                const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
                                const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr,
-                               const hmgpu_export_pixel* pixel = nullptr, const int64_t* lut = nullptr);
+                               const hmgpu_export_pixel* pixel = nullptr, const int64_t* lut = nullptr,
+                               const hmgpu_export_chroma* const* chroma = nullptr);   // chroma: hmgpu_pictures_export_chroma (*lut 0: no colour stage)
   // colour LUTs (hmgpu_colour_lut_create): the host copy lives here, the device copies are made per context when an export first
   // needs one (lut of export_pictures: hmgpu_pictures_export_colour) and go with the contexts of a sequence that ends
   hmgpu_status colour_lut_create(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice, int64_t* out);

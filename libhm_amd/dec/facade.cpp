@@ -357,6 +357,15 @@ int hmdec_pictures_export_colour(libHMDec_context* ctx, int n, libHMDec_picture*
   for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
   return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut);
 }
+int hmdec_pictures_export_chroma(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                 const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                 const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma, void* const dst[3],
+                                 const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut, &chroma);
+}
 int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_motion_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,
                                  void* dst_block, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
@@ -393,6 +402,11 @@ int hmdec_picture_device(libHMDec_picture* pic) {
 int hmdec_picture_colour(libHMDec_picture* pic, int32_t out[5]) {
   if (!pic || !out) return 1;
   for (int i = 0; i < 5; i++) out[i] = as_pic(pic)->colour[i];
+  return 0;
+}
+int hmdec_picture_chroma_loc(libHMDec_picture* pic, int32_t out[3]) {
+  if (!pic || !out) return 1;
+  for (int i = 0; i < 3; i++) out[i] = as_pic(pic)->chroma_loc[i];
   return 0;
 }
 void hmdec_set_packed_input(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_packed_input(on != 0); }

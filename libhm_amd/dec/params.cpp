@@ -211,7 +211,8 @@ static void skip_hrd(BitReader& br, bool common, int max_sub_layers_minus1) {
   }
 }
 
-// E.2.1 vui_parameters(): nothing of it is needed for reconstruction; the colour description is kept for the device export
+// E.2.1 vui_parameters(): nothing of it is needed for reconstruction; the colour description and the chroma sample location are
+// kept for the device export
 static void parse_vui(BitReader& br, int max_sub_layers_minus1, Sps& s) {
   if (br.flag()) { if (br.u(8) == 255) { br.u(16); br.u(16); } }
   if (br.flag()) br.u(1);
@@ -220,7 +221,7 @@ static void parse_vui(BitReader& br, int max_sub_layers_minus1, Sps& s) {
     s.video_full_range = br.u(1) != 0;
     if (br.flag()) { s.colour_primaries = br.u(8); s.transfer_characteristics = br.u(8); s.matrix_coefficients = br.u(8); }
   }
-  if (br.flag()) { br.ue(); br.ue(); }
+  if ((s.chroma_loc_info_present = br.flag())) { s.chroma_sample_loc_type_top_field = (int)br.ue(); s.chroma_sample_loc_type_bottom_field = (int)br.ue(); }
   br.u(1); br.u(1); br.u(1);
   if (br.flag()) { br.ue(); br.ue(); br.ue(); br.ue(); }
   if (br.flag()) {

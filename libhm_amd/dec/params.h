@@ -56,6 +56,8 @@ struct Sps {
   // VUI colour description (E.2.1); absent fields take the E.3.1 defaults: video_format 5, limited range, 2 = unspecified
   bool video_signal_type_present = false, video_full_range = false;
   int video_format = 5, colour_primaries = 2, transfer_characteristics = 2, matrix_coefficients = 2;
+  bool chroma_loc_info_present = false;               // E.2.1; absent: both types 0
+  int chroma_sample_loc_type_top_field = 0, chroma_sample_loc_type_bottom_field = 0;
   // sps_range_extension() (HM 16.0: TDecCAVLC.cpp:778-786); tools the device path lacks are refused while parsing
   bool rext_rotation = false, rext_ts_context = false, rext_implicit_rdpcm = false, rext_explicit_rdpcm = false;
   bool rext_persistent_rice = false, rext_intra_smoothing_disabled = false, rext_high_precision_offsets = false;

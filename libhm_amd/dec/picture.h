@@ -136,6 +136,7 @@ struct PicData {
   int home = 0;                      // the context that decoded the picture (Decoder::gpus_) ...
   uint32_t present = 0;              // ... and the contexts that hold its finished samples (bit k: gpus_[k])
   uint64_t submit_seq = 0;           // device submission that last read these arrays
+  int chroma_loc[3] = {0, 0, 0};      // VUI of the active SPS: chroma_loc_info_present_flag, chroma_sample_loc_type_top_field, _bottom_field
   int colour[5] = {0, 2, 2, 2, 5};    // VUI of the active SPS: video_full_range_flag, colour_primaries, transfer_characteristics, matrix_coefficients, video_format
   // output side
   void* owner = nullptr;             // the hmdec::Decoder whose buffer this is (lazy plane download in device-output mode)

@@ -87,6 +87,11 @@ def lib():
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                    C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                    C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_chroma.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma), C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_picture_chroma_loc.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_pictures_export_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MotionDesc),
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
                                                    C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
@@ -222,6 +227,12 @@ class Picture:
         lib().hmdec_picture_colour(self.h, v)
         return dict(zip(("full_range", "primaries", "transfer", "matrix", "video_format"), (int(x) for x in v)))
 
+    def chroma_loc(self):
+        """VUI chroma sample location: dict of present, top_field, bottom_field (chroma_sample_loc_type 0 .. 5; 0 when absent)"""
+        v = (C.c_int32 * 3)()
+        lib().hmdec_picture_chroma_loc(self.h, v)
+        return dict(zip(("present", "top_field", "bottom_field"), (int(x) for x in v)))
+
     def export_into(self, desc, ptrs, pitches, on_stream=1, stream=0, scale=None):
         """hmdec_picture_export (scale: an abi.ExportScale, hmdec_picture_export_scaled) into device memory the caller owns"""
         p, q = abi.ptr_array(ptrs), abi.i64_array(pitches)
@@ -235,7 +246,8 @@ class Picture:
             raise HmgpuError(st, name)
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
-               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None, lut=None):
+               filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None, lut=None,
+               chroma="replicate", chroma_loc=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
@@ -246,9 +258,11 @@ class Picture:
         "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels, alpha its A element (None: opaque).  lut (layout "rgb"): a
         colour LUT of the picture's decoder (Decoder.colour_lut) of the output depth, or "sdr": the LUT export.colour_lut builds
         from the stream's own colour description (VUI primaries and transfer; unspecified codes raise) to BT.709 with the sRGB
-        curve, tone-mapped with BT.2390, made once per decoder, source and depth.  Valid until the next push into the decoder."""
+        curve, tone-mapped with BT.2390, made once per decoder, source and depth.  chroma (layout "rgb"): "replicate", or "linear":
+        Cb and Cr interpolated to the luma grid before the matrix at chroma_loc, a chroma_sample_loc_type 0 .. 5 or None: the
+        stream's own (chroma_loc()["top_field"], 0 when absent).  Valid until the next push into the decoder."""
         return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias,
-                       pixel=pixel, alpha=alpha, lut=lut)
+                       pixel=pixel, alpha=alpha, lut=lut, chroma=chroma, chroma_loc=chroma_loc)
 
     def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
         """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
@@ -372,15 +386,18 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
 
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
-            scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None, lut=None):
+            scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None, lut=None,
+            chroma="replicate", chroma_loc=None):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
     the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
     windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
     (export.make_pixel, hmdec_pictures_export_pixels); lut: a DecoderColourLut, a raw handle or "sdr"
-    (hmdec_pictures_export_colour)"""
+    (hmdec_pictures_export_colour); chroma / chroma_loc: "linear" goes through hmdec_pictures_export_chroma, with the first picture's
+    VUI sample location for chroma_loc None; "replicate" through the entries it always took"""
     from . import HmgpuError, export, export_tensor_plan
     first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
+    chr_ = abi.chroma_stage(chroma, chroma_loc, first.chroma_loc()["top_field"])
     if isinstance(lut, str):
         if lut != "sdr":
             raise ValueError("lut: a colour LUT of the decoder, or \"sdr\"")
@@ -389,6 +406,13 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     handle = getattr(lut, "handle", lut)
 
     def colour_call(desc, sc, tensor, px, ptrs, pitches, bstrides, st):
+        if chr_ is not None:
+            r = lib().hmdec_pictures_export_chroma(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
+                                                   abi.window_array(win), abi.ref(px), handle or 0, C.byref(chr_), abi.ptr_array(ptrs),
+                                                   abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
+            if r != 0:
+                raise HmgpuError(r, "hmdec_pictures_export_chroma")
+            return
         r = lib().hmdec_pictures_export_colour(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
                                                abi.window_array(win), abi.ref(px), handle, abi.ptr_array(ptrs), abi.i64_array(pitches),
                                                abi.i64_array(bstrides), 1, abi.addr(st))
@@ -401,12 +425,12 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
         if not enqueue:
             return None
-        if tensor is None and bstrides is None and lut is None:
+        if tensor is None and bstrides is None and lut is None and chr_ is None:
             return first.export_into(desc, ptrs, pitches, 1, st, sc)
         if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
             plan = export_tensor_plan(seq, desc, sc, tensor)
             bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-        if lut is not None:
+        if lut is not None or chr_ is not None:
             return colour_call(desc, sc, tensor, None, ptrs, pitches, bstrides, st)
         head = (first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor))
         tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
@@ -420,7 +444,7 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
         if not enqueue:
             return None
-        if lut is not None:
+        if lut is not None or chr_ is not None:
             return colour_call(desc, sc, tensor, px, [ptr], [pitch], [bstride], st)
         r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
                                                abi.window_array(win), C.byref(px), abi.addr(ptr), pitch, bstride, 1, abi.addr(st))
@@ -433,7 +457,7 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                  filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                 pixel=None, alpha=None, memory_format=None, lut=None):
+                 pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
@@ -441,12 +465,14 @@ def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix
     windows: one (x, y, w, h) per picture relative to crop, flip: one boolean per picture -- hmdec_pictures_export_windows;
     pixel / alpha: one [N, H, W, C] tensor of packed pixels, memory_format=torch.channels_last: [N, 3, H, W] with channels-last
     strides -- hmdec_pictures_export_pixels; lut: a colour LUT of the pictures' decoder, Decoder.colour_lut, or "sdr" as in
-    Picture.export -- hmdec_pictures_export_colour)."""
+    Picture.export -- hmdec_pictures_export_colour; chroma / chroma_loc as in Picture.export, the sample location that of the first
+    picture -- hmdec_pictures_export_chroma)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
-                   scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format, lut=lut)
+                   scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format, lut=lut, chroma=chroma,
+                   chroma_loc=chroma_loc)
 
 
 class DecoderColourLut:
@@ -608,7 +634,7 @@ class Decoder:
 
     def frames(self, stream, batch=None, windows=None, motion=None, residual=None, **export_kw):
         """(poc, exported tensors) of every picture in output order: decode_stream's loop with Picture.export(**export_kw) in place
-        of a download.  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
+        of a download (chroma="linear" among them: the stream's own chroma sample location unless chroma_loc= names one).  Each export is enqueued before the next unit is pushed (the picture's lifetime); the tensors are torch's.
         batch=N: (pocs, tensors) with up to N (<= 16) pictures per item instead, the tensors those of export_batch: slots are filled
         in output order, the pictures fetched after one push in one batched call each; an item is yielded when it is full, the
         remainder at the end of the stream as a view of the first n slots.  windows (batch=N only): a function; fn(n) returns
