@@ -93,6 +93,8 @@ typedef struct hmgpu_export_window hmgpu_export_window;
 typedef struct hmgpu_export_pixel hmgpu_export_pixel;
 typedef struct hmgpu_colour_lut_desc hmgpu_colour_lut_desc;
 typedef struct hmgpu_export_chroma hmgpu_export_chroma;
+typedef struct hmgpu_export_warp hmgpu_export_warp;
+typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
@@ -147,6 +149,15 @@ int hmdec_pictures_export_chroma(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma, void* const dst[3],
                                  const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+/* The RGB exports through one inverse affine map per picture (hmgpu_pictures_export_warp; include/hmgpu.h "affine warp export"): the
+ * arguments of hmdec_pictures_export_chroma without `scale` (chroma NULL: replicate; lut 0: no colour stage), then the warp
+ * descriptor and n maps.  The whole batch is validated once (hmgpu_export_warp_destination_check), then each run of slots of a device
+ * context is one call with the windows and maps of its own slots. */
+int hmdec_pictures_export_warp(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                               const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel,
+                               int64_t lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map maps[],
+                               void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
+                               void* stream);
 /* Motion vectors, reference POCs and block information of up to 16 pictures in one call (hmgpu_pictures_export_motion: the BLOCKS
  * grid or the DENSE per-sample form; destinations, strides and statuses as there), under the validity rule of hmdec_pictures_export:
  * every picture put out by this decoder and fetched since the last push, of one sequence and on one GPU ordinal, else HMGPU_EINVAL

@@ -588,6 +588,75 @@ hmgpu_status hmgpu_export_chroma_destination_check(hmgpu_ctx* ctx, int32_t n, co
                                                    const hmgpu_export_pixel* pixel, hmgpu_lut lut, const hmgpu_export_chroma* chroma,
                                                    void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ affine warp export
+ * An inverse affine map per picture inside the RGB exports: rotation, shear, zoom, sub-sample shifts and the display
+ * orientations, in the one launch, where the other calls offer a window, a resize and a mirror.  Integer arithmetic that
+ * tests/export_warp_ref.py restates exactly.
+ *
+ * D is the RGB output depth of the call and M = 2^D - 1.  S is the Ws x Hs window of slot i (windows[i].crop, or desc->crop when
+ * windows is NULL) as three planes of integers 0 .. M: exactly what the unscaled call writes for that window with the same desc and
+ * chroma arguments before the colour stage, the msb_aligned shift, the float map, the mirror and the packing -- after the matrix or
+ * the identity rule and after the clip.  With HMGPU_CHROMA_LINEAR the chroma is interpolated before the matrix as "chroma export"
+ * says; its taps may lie outside the window but inside the decoded plane.  v, the integer of output pixel (ox, oy), 0 <= ox < width,
+ * 0 <= oy < height, takes the place of the export's v in everything the existing calls do afterwards: the colour stage, the
+ * msb_aligned shift, fl(fl(v * scale[k]) + bias[k]), the mirror of windows[i].flip, the alpha element and the channel order.
+ *
+ * A map is six int32 values in Q16, m[0..5].  All coordinate arithmetic is in signed 64-bit integers, >> an arithmetic shift.
+ *   HMGPU_WARP_BILINEAR   X = m0*ox + m1*oy + m2 + 128, Y = m3*ox + m4*oy + m5 + 128; ix = X >> 16, fx = (X >> 8) & 255, iy and fy
+ *                         alike.  Taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) with the weights (256-fx)(256-fy), fx(256-fy),
+ *                         (256-fx)fy, fx*fy, which sum to 65536; v = (sum of w * tap + 32768) >> 16 in unsigned 32-bit arithmetic
+ *                         (at most 65535 * 65536 + 32768 < 2^32).  No clip: v is a convex combination of values <= M.
+ *   HMGPU_WARP_NEAREST    the same X and Y with 32768 in place of 128; the one tap (X >> 16, Y >> 16).
+ * Border, per tap and on the 64-bit values before anything is narrowed:
+ *   HMGPU_WARP_EDGE       tap (x, y) = S[c][clamp(y, 0, Hs-1)][clamp(x, 0, Ws-1)]
+ *   HMGPU_WARP_FILL       tap (x, y) = S[c][y][x] inside the window, else fill[c]: each tap decided on its own, the blending of
+ *                         grid_sample(padding_mode="zeros") at the rim.  Samples of the decoded picture outside the window never
+ *                         contribute (the scaled export's rule).
+ * m = {65536, 0, 0, 0, 65536, 0} with width x height the window's size writes, bit for bit, what the matching existing call writes;
+ * a map whose six values are multiples of 65536 is a permutation, shift or replication of S under either filter.  There is no
+ * prefilter: a map that shrinks by more than about 2x aliases -- resize with the scaled export (hmgpu_export_scale) instead.
+ * Perspective maps, reflect padding, bicubic taps and the YUV layouts are not offered.
+ *
+ * hmgpu_pictures_export_warp takes the arguments of hmgpu_pictures_export_chroma without `scale` (the map is the scale): pixel NULL
+ * three planes, lut 0 no colour stage, chroma NULL replicate, windows NULL desc->crop.  Validation is that of the matching existing
+ * call with scale NULL, made by the same code with the same statuses in the same order, except that the windows may differ in size
+ * (the output size comes from `warp`; each window obeys hmgpu_export_plan_for's rules on its own) and that the destination is checked
+ * against width x height.  Then the warp rules: `warp` or `maps` NULL, a non-zero reserved word in either struct, width / height
+ * outside 1 .. 16384, a fill[c] outside 0 .. M under HMGPU_WARP_FILL (ignored under EDGE), a layout that is not RGB (HMGPU_EINVAL);
+ * then an unknown filter or border (HMGPU_EUNSUPPORTED).  The six map values are unrestricted: any int32 is legal and defined above.
+ * Everything is validated before anything is enqueued and a refused call leaves the destination untouched.  The plan is that of the
+ * matching planar or packed call with every plane width x height.  One launch per call; the maps and window origins travel in one
+ * copy through the window ring; the stream ordering of the existing calls; not accounted in hmgpu_stats. */
+enum { HMGPU_WARP_NEAREST = 0, HMGPU_WARP_BILINEAR = 1 };
+enum { HMGPU_WARP_EDGE = 0, HMGPU_WARP_FILL = 1 };
+typedef struct hmgpu_export_warp {
+  int32_t width, height;       /* the output, 1 .. 16384 each */
+  int32_t filter;              /* HMGPU_WARP_NEAREST / _BILINEAR */
+  int32_t border;              /* HMGPU_WARP_EDGE / _FILL */
+  int32_t fill[3];             /* R, G, B code values 0 .. M of HMGPU_WARP_FILL */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_export_warp;
+typedef struct hmgpu_warp_map {
+  int32_t m[6];                /* Q16: source x = m0*ox + m1*oy + m2, source y = m3*ox + m4*oy + m5 (sample indices of the window) */
+  int32_t reserved[2];         /* 0 */
+} hmgpu_warp_map;
+/* host code, no device needed; n maps (and windows, unless NULL) */
+hmgpu_status hmgpu_export_warp_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
+                                        int32_t n, const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel,
+                                        const hmgpu_colour_lut_desc* lut, const hmgpu_export_chroma* chroma,
+                                        const hmgpu_export_warp* warp, const hmgpu_warp_map maps[], hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                        const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                        const hmgpu_export_pixel* pixel, hmgpu_lut lut, const hmgpu_export_chroma* chroma,
+                                        const hmgpu_export_warp* warp, const hmgpu_warp_map maps[], void* const dst[3],
+                                        const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_warp: the status it would give these arguments; enqueues nothing */
+hmgpu_status hmgpu_export_warp_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
+                                                 const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel, hmgpu_lut lut,
+                                                 const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp,
+                                                 const hmgpu_warp_map maps[], void* const dst[3], const int64_t pitch_bytes[3],
+                                                 const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

@@ -140,6 +140,18 @@ def lib():
                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                             C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma),
                                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_export_warp_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportTensor), C.c_int32,
+                                                 C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel), C.POINTER(abi.ColourLutDesc),
+                                                 C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
+                                                 C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_warp.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                 C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel),
+                                                 C.c_int64, C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_warp_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportTensor),
+                                                          C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel), C.c_int64,
+                                                          C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
+                                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_motion_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MotionDesc), C.POINTER(abi.ExportScale), C.c_int32,
                                             C.POINTER(abi.ExportWindow), C.POINTER(abi.MotionPlan)]
         L.hmgpu_pictures_export_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MotionDesc),
@@ -301,6 +313,27 @@ def export_chroma_plan(seq, desc, scale, tensor, windows, pixel, lut_desc, chrom
     st, plan = export_chroma_status(seq, desc, scale, tensor, windows, pixel, lut_desc, chroma)
     if st != abi.HMGPU_OK:
         raise HmgpuError(st, "hmgpu_export_chroma_plan_for")
+    return plan
+
+
+def export_warp_status(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, maps, n=None):
+    """(status, plan) of hmgpu_export_warp_plan_for (host code, no GPU): the plan of the matching planar or packed call with every
+    plane warp.width x warp.height.  warp: an abi.ExportWarp or None; maps: an abi.WarpMap array (abi.warp_map_array) or None;
+    n: the pictures (default: one per window, else one per map, else 1)"""
+    plan = abi.ExportPlan()
+    windows = list(windows) if windows is not None else None
+    if n is None:
+        n = len(windows) if windows is not None else len(maps) if maps is not None else 1
+    st = lib().hmgpu_export_warp_plan_for(C.byref(seq), C.byref(desc), abi.ref(tensor), n, abi.window_array(windows), abi.ref(pixel),
+                                          abi.ref(lut_desc), abi.ref(chroma), abi.ref(warp), maps, C.byref(plan))
+    return st, plan
+
+
+def export_warp_plan(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, maps, n=None):
+    """what a warp export writes per slot: export_warp_status, a refusal raised"""
+    st, plan = export_warp_status(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, maps, n)
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_warp_plan_for")
     return plan
 
 
@@ -611,6 +644,23 @@ class Context:
                                                            abi.ref(pixel), getattr(lut, "handle", lut) or 0, abi.ref(chroma),
                                                            abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides))
 
+    def export_warp_into(self, pics, desc, warp, ptrs, pitches, bstrides, on_stream=0, stream=0, tensor=None, windows=None, pixel=None,
+                         lut=None, chroma=None):
+        """hmgpu_pictures_export_warp into device memory the caller owns: export_chroma_into without a scale (chroma None: replicate),
+        every picture through its own inverse affine map; warp: (abi.ExportWarp, abi.WarpMap array), either of them None for NULL"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_warp(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(tensor),
+                                                   abi.window_array(windows), abi.ref(pixel), getattr(lut, "handle", lut) or 0,
+                                                   abi.ref(chroma), abi.ref(warp[0]), warp[1], abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                                   abi.i64_array(bstrides), on_stream, abi.addr(stream)), "hmgpu_pictures_export_warp")
+
+    def export_warp_destination_status(self, n, desc, warp, ptrs, pitches, bstrides, tensor=None, windows=None, pixel=None, lut=None,
+                                       chroma=None):
+        """hmgpu_export_warp_destination_check: the status hmgpu_pictures_export_warp would give; enqueues nothing"""
+        return lib().hmgpu_export_warp_destination_check(self._h, n, C.byref(desc), abi.ref(tensor), abi.window_array(windows), abi.ref(pixel),
+                                                         getattr(lut, "handle", lut) or 0, abi.ref(chroma), abi.ref(warp[0]), warp[1],
+                                                         abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides))
+
     def export_destination_status(self, n, desc, ptrs, pitches, bstrides, scale=None, tensor=None):
         """hmgpu_export_destination_check: the status hmgpu_pictures_export would give this destination for n pictures; enqueues nothing"""
         return lib().hmgpu_export_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.ptr_array(ptrs),
@@ -626,19 +676,27 @@ class Context:
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
-               lut=None, chroma="replicate", chroma_loc=None):
+               lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
         gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
         "bgra", "argb", "abgr"; layout "rgb"): one [H, W, C] tensor of packed pixels instead, alpha the A element (None: opaque).
         lut (layout "rgb"): a ColourLut of this context (colour_lut) of the output depth: every pixel through it before the store.
         chroma (layout "rgb"): "replicate", or "linear": Cb and Cr interpolated to the luma grid at chroma_loc, the stream's
-        chroma_sample_loc_type 0 .. 5 (None: 0), before the matrix (hmgpu_pictures_export_chroma)"""
+        chroma_sample_loc_type 0 .. 5 (None: 0), before the matrix (hmgpu_pictures_export_chroma).
+        warp (layout "rgb"): one inverse affine map of six Q16 ints (export.affine_map, export.orientation_map), as export_batch
+        takes one per picture; size is then required and is the output size, filter "bilinear" or "nearest", border "edge" or "fill"
+        with fill=(r, g, b) (hmgpu_pictures_export_warp)"""
         from . import export
         os_ = 1 if on_stream else 0
         chr_ = abi.chroma_stage(chroma, chroma_loc)
+        wrp = abi.warp_stage(export.one_map(warp), size, filter, border, fill, 1)
 
         def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
+            if wrp is not None:
+                plan = export_warp_plan(self.seq, desc, tensor, None, None, None, None, wrp[0], wrp[1])
+                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+                return self.export_warp_into([pic], desc, wrp, ptrs, pitches, extent, os_, st, tensor, None, None, lut, chr_)
             if chr_ is not None:
                 plan = export_tensor_plan(self.seq, desc, sc, tensor)
                 extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
@@ -653,8 +711,10 @@ class Context:
             extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
             self.export_batch_into([pic], desc, ptrs, pitches, extent, 1 if on_stream else 0, st, sc, tensor)
         return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
-                                     filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha,
+                                     filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha, warp=wrp,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_warp_into([pic], desc, wrp, [ptr], [pitch], [bstride], os_, st, tensor, None, px, lut, chr_)
+                                     if wrp is not None else
                                      self.export_chroma_into([pic], desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px, lut)
                                      if chr_ is not None else
                                      self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, os_, st, sc, tensor) if lut is None else
@@ -662,7 +722,8 @@ class Context:
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                     pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None):
+                     pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge",
+                     fill=None):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -681,20 +742,31 @@ class Context:
         (hmgpu_pictures_export_colour).
         chroma (layout "rgb"; any of the forms above): "replicate", or "linear" -- Cb and Cr of 4:2:0 / 4:2:2 pictures interpolated
         to the luma grid at chroma_loc (chroma_sample_loc_type 0 .. 5; None: 0) before the matrix, still in the one launch
-        (hmgpu_pictures_export_chroma).  "replicate" goes through the entries above."""
+        (hmgpu_pictures_export_chroma).  "replicate" goes through the entries above.
+        warp (layout "rgb"; any of the forms above): one inverse affine map per picture, six Q16 ints each or an [n, 6] integer array
+        (export.affine_map, export.random_affine, export.orientation_map) -- rotation, shear, zoom, sub-sample shifts and the display
+        orientations, still in the one launch (hmgpu_pictures_export_warp).  size is then required and is the output size; the
+        windows, the source of each map, may differ in size; filter "bilinear" or "nearest"; border "edge", or "fill" with
+        fill=(r, g, b) code values of the output depth.  There is no prefilter: resize by more than about 2x with size= alone."""
         from . import export
         pics = list(pics)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         os_ = 1 if on_stream else 0
         chr_ = abi.chroma_stage(chroma, chroma_loc)
+        wrp = abi.warp_stage(warp, size, filter, border, fill, len(pics))
         return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
+                                     self.export_warp_into(pics, desc, wrp, ptrs, pitches, bstrides, os_, st, tensor, win, None, lut, chr_)
+                                     if wrp is not None else
                                      self.export_chroma_into(pics, desc, chr_, ptrs, pitches, bstrides, os_, st, sc, tensor, win, None, lut)
                                      if chr_ is not None else
                                      self.export_batch_into(pics, desc, ptrs, pitches, bstrides, os_, st, sc, tensor, win) if lut is None else
                                      self.export_colour_into(pics, desc, lut, ptrs, pitches, bstrides, os_, st, sc, tensor, win),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
+                                     warp=wrp,
                                      pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
+                                     self.export_warp_into(pics, desc, wrp, [ptr], [pitch], [bstride], os_, st, tensor, win, px, lut, chr_)
+                                     if wrp is not None else
                                      self.export_chroma_into(pics, desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px, lut)
                                      if chr_ is not None else
                                      self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, os_, st, sc, tensor, win) if lut is None else

@@ -193,6 +193,66 @@ def chroma_stage(chroma, chroma_loc, default_loc=0):
     return make_export_chroma(chroma, default_loc if chroma_loc is None else chroma_loc)
 
 
+WARP_NEAREST, WARP_BILINEAR = 0, 1
+WARP_EDGE, WARP_FILL = 0, 1
+WARP_FILTERS = {"nearest": WARP_NEAREST, "bilinear": WARP_BILINEAR}
+WARP_BORDERS = {"edge": WARP_EDGE, "fill": WARP_FILL}
+
+
+class ExportWarp(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("border", C.c_int32), ("fill", C.c_int32 * 3),
+                ("reserved", C.c_int32 * 5)]
+
+
+class WarpMap(C.Structure):
+    _fields_ = [("m", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
+
+
+def make_export_warp(width, height, filter=WARP_BILINEAR, border=WARP_EDGE, fill=(0, 0, 0)):
+    """filter: WARP_NEAREST / WARP_BILINEAR or its name; border: WARP_EDGE / WARP_FILL or its name; fill: (r, g, b) code values"""
+    w = ExportWarp()
+    w.width, w.height = int(width), int(height)
+    w.filter, w.border = int(WARP_FILTERS.get(filter, filter)), int(WARP_BORDERS.get(border, border))
+    for k in range(3):
+        w.fill[k] = int(fill[k])
+    return w
+
+
+def warp_map_array(maps):
+    """n maps of six Q16 ints (a sequence of sequences or an [n, 6] integer array) as a WarpMap array; None: a null pointer"""
+    if maps is None:
+        return None
+    rows = [[int(v) for v in m] for m in maps]
+    if any(len(m) != 6 for m in rows):
+        raise ValueError("warp: six ints per map")
+    arr = (WarpMap * len(rows))()
+    for i, m in enumerate(rows):
+        for k in range(6):
+            if not -(1 << 31) <= m[k] < (1 << 31):
+                raise ValueError("warp: map values are int32 (Q16)")
+            arr[i].m[k] = m[k]
+    return arr
+
+
+def warp_stage(warp, size, filter, border, fill, n):
+    """warp= / size= / filter= / border= / fill= of the Python exports: None without warp, else (ExportWarp, WarpMap array) of n maps"""
+    if warp is None:
+        if border != "edge" or fill is not None:
+            raise ValueError("border / fill need warp=")
+        return None
+    if size is None:
+        raise ValueError("warp: size=(height, width) is required, the output size")
+    if filter not in WARP_FILTERS:
+        raise ValueError("warp: filter \"bilinear\" or \"nearest\"")
+    if border not in WARP_BORDERS:
+        raise ValueError("warp: border \"edge\" or \"fill\"")
+    maps = warp_map_array(warp)
+    if len(maps) != n:
+        raise ValueError("warp: one map per picture (%d pictures, %d maps)" % (n, len(maps)))
+    h, w = (int(v) for v in size)
+    return make_export_warp(w, h, filter, border, (0, 0, 0) if fill is None else tuple(fill)), maps
+
+
 MOTION_BLOCKS, MOTION_DENSE = 0, 1
 MOTION_NO_REF = -(1 << 31)
 MOTION_DST_MV0, MOTION_DST_MV1, MOTION_DST_REF, MOTION_DST_BLOCK, MOTION_DSTS = 0, 1, 2, 3, 4

@@ -525,6 +525,31 @@ void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipSt
 void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch);
 // the RGB layout with the chroma stage (ChromaSite) in the stage step, and the colour stage as well where lut is not null
 void launch_export_scaled_chroma(const ScaleArgs& a, const ChromaSite& cs, const ColourLut* lut, int elem, int n, hipStream_t s, int nch);
+// affine warp export (k_export_warp.hip, hmgpu_pictures_export_warp; include/hmgpu.h "affine warp export"): the RGB layout, planes or
+// packed pixels, each picture through its own inverse map.  Per picture (grid y), in device memory of the window ring: the Q16 map
+// and the source window in plane coordinates
+struct WarpPic { int32_t m[6]; int32_t x0, y0, ws, hs; int32_t pad_[2]; };
+constexpr int kWarpTileW = 64, kWarpTileH = 16;   // outputs of one workgroup: a lane has four adjacent columns of one row
+struct WarpArgs {
+  const WarpPic* pics;             // [grid y]
+  const int16_t* src[kMaxExportBatch][2];   // per picture: sample (0, 0) of the luma plane and of the pair plane (Cb)
+  int32_t pitch_y, pitch_c;        // int16 elements
+  int32_t mono, csx, csy;
+  int32_t w, h, tiles_x;           // the output of every picture; 64-column tiles per tile row
+  int32_t filter, border;          // HMGPU_WARP_*
+  uint32_t fill[3];                // HMGPU_WARP_FILL: R, G, B
+  int32_t sh[2], maxv[2], msb[2];  // bit-depth rule per channel type (as ExportArgs)
+  int32_t vec;                     // every group of 4 output samples may be one store (alignment of dst and pitches; packed: px.vst)
+  uint32_t flip;                   // bit i: picture i is mirrored (every output row reversed)
+  uint8_t* dst[3];
+  int64_t pitch[3];                // bytes
+  int64_t bstride[3];              // bytes between the planes of consecutive pictures
+  float scale[3], bias[3];         // float elements: per output plane
+  int32_t coef[16];                // hmgpu_export_plan.coef
+  PxOrder px;                      // packed pixels (nch below): dst[0] / pitch[0] / bstride[0] the one destination
+};
+// n pictures; elem: kElem*; nch: 0, or 3 / 4 elements per packed pixel; cs: null, or the chroma stage; lut: null, or the colour stage
+void launch_export_warp(const WarpArgs& a, const ChromaSite* cs, const ColourLut* lut, int elem, int n, int nch, hipStream_t s);
 // motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
 // arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
 // dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.

@@ -1,7 +1,8 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
-// slots, window tables, colour LUTs, the chroma stage's rules and weights, export_resolve under export_impl and the picture destination checks, strided_dst_ok under the motion / block
+// slots, window tables, colour LUTs, the chroma stage's rules and weights, export_resolve under export_impl and the picture destination checks, the warp export's rules and its
+// per-call maps, strided_dst_ok under the motion / block
 // and residual exports and the reference planes of the picture metrics (k_export.hip, k_export_px.hip, k_export_scale.hip,
-// k_motion.hip, k_residual.hip, k_metrics.hip).
+// k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -642,7 +643,7 @@ hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmg
 // call's status).  differ: the windows are not all equal; shapes (scaled): one per window then, else one for all.
 static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
                                  int n, const hmgpu_export_window* win, hmgpu_export_plan* out, std::vector<ScaleShape>* shapes, int* elem,
-                                 bool* differ) {
+                                 bool* differ, bool any_size = false) {
   if (!seq || !d || !out) return HMGPU_EINVAL;
   memset(out, 0, sizeof(*out));
   if (!win || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
@@ -662,7 +663,8 @@ static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export
     if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
     if (shapes && sc) shapes->push_back(s);
     if (!i) { *out = plan; continue; }
-    if (plan.width[0] != out->width[0] || plan.height[0] != out->height[0]) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }   // (unscaled)
+    // (unscaled; any_size: the warp export, whose output size is not the windows')
+    if (!any_size && (plan.width[0] != out->width[0] || plan.height[0] != out->height[0])) { memset(out, 0, sizeof(*out)); return HMGPU_EINVAL; }
     out->coef[12] = std::max(out->coef[12], plan.coef[12]);
     out->coef[13] = std::max(out->coef[13], plan.coef[13]);
   }
@@ -974,6 +976,99 @@ hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* c, int32_t n, cons
   return export_resolve(c, n, d, sc, t, windows, px, dst3, pitch3, bstride3, false, &r);
 }
 
+// ------------------------------------------------------------------------------------------------ affine warp export (k_export_warp.hip)
+// whether `wp` names an output size (the plan and the destination check need one before the warp rules have their turn)
+static bool warp_sized(const hmgpu_export_warp* wp) {
+  return wp && wp->width >= 1 && wp->width <= 16384 && wp->height >= 1 && wp->height <= 16384;
+}
+
+// the rules a warp export adds behind the validation of the matching call, in the order include/hmgpu.h "affine warp export" gives
+static hmgpu_status warp_rules(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int n, const hmgpu_export_warp* wp, const hmgpu_warp_map* maps) {
+  if (!wp || !maps) return HMGPU_EINVAL;
+  for (int k = 0; k < 5; k++) if (wp->reserved[k]) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (maps[i].reserved[0] || maps[i].reserved[1]) return HMGPU_EINVAL;
+  if (!warp_sized(wp)) return HMGPU_EINVAL;
+  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (wp->border == HMGPU_WARP_FILL) {
+    int ob[2];
+    out_depths(seq, d, ob);
+    for (int k = 0; k < 3; k++) if (wp->fill[k] < 0 || wp->fill[k] > (1 << ob[0]) - 1) return HMGPU_EINVAL;
+  }
+  if (wp->filter != HMGPU_WARP_NEAREST && wp->filter != HMGPU_WARP_BILINEAR) return HMGPU_EUNSUPPORTED;
+  if (wp->border != HMGPU_WARP_EDGE && wp->border != HMGPU_WARP_FILL) return HMGPU_EUNSUPPORTED;
+  return HMGPU_OK;
+}
+
+// the plan of the matching planar or packed call with scale null -- windows of any size -- and, once `wp` names a size, every plane
+// of the RGB layout width x height
+static hmgpu_status warp_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int n,
+                              const hmgpu_export_window* win, const hmgpu_export_pixel* px, const hmgpu_export_warp* wp,
+                              hmgpu_export_plan* out, int* elem, PxOrder* po, uint32_t* flip) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  bool differ = false;
+  if (win) {
+    const hmgpu_status st = windows_plan(seq, d, nullptr, t, n, win, out, nullptr, elem, &differ, true);
+    if (st != HMGPU_OK) return st;
+    for (int i = 0; i < n; i++) *flip |= (uint32_t)(win[i].flip & 1) << i;
+  } else {
+    memset(out, 0, sizeof(*out));
+    if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+    const hmgpu_status st = tensor_plan(seq, d, nullptr, t, out, nullptr, elem);
+    if (st != HMGPU_OK) return st;
+  }
+  if (warp_sized(wp) && d->layout == HMGPU_EXPORT_RGB)
+    for (int k = 0; k < out->planes; k++) {
+      out->row_bytes[k] = out->row_bytes[k] / out->width[k] * wp->width;
+      out->width[k] = wp->width; out->height[k] = wp->height;
+    }
+  return px ? pixel_plan(seq, d, *elem, px, out, po) : HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_warp_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int32_t n,
+                                        const hmgpu_export_window win[], const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld,
+                                        const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp, const hmgpu_warp_map maps[],
+                                        hmgpu_export_plan* out) {
+  int elem = 0;
+  uint32_t flip = 0;
+  PxOrder po;
+  hmgpu_status st = warp_plan(seq, d, t, n, win, px, wp, out, &elem, &po, &flip);
+  if (st != HMGPU_OK) return st;
+  if (ld) st = d->layout != HMGPU_EXPORT_RGB || !colour_desc_ok(ld) ? HMGPU_EINVAL : colour_rules(seq, d, ld->depth);
+  if (st == HMGPU_OK && ch) st = chroma_rules(d, ch);
+  if (st == HMGPU_OK) st = warp_rules(seq, d, n, wp, maps);
+  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// what hmgpu_pictures_export_warp and its destination check resolve their arguments to: export_resolve's part for a call without
+// scale, the destination against the warp's plan, then the colour, chroma and warp rules
+static hmgpu_status warp_resolve(hmgpu_ctx* c, int n, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, const hmgpu_export_window* win,
+                                 const hmgpu_export_pixel* px, hmgpu_lut lut, const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp,
+                                 const hmgpu_warp_map* maps, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
+                                 ExportCall* r, hmgpu_ctx::ColourSlot** cs) {
+  { const hmgpu_status st = warp_plan(&c->seq, d, t, n, win, px, wp, &r->plan, &r->elem, &r->po, &r->flip); if (st != HMGPU_OK) return st; }
+  r->d = *d;
+  if (px) r->nch = px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
+  if (warp_sized(wp)) {                               // (no size: refused below, by the warp rules at the latest)
+    const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs);
+    if (st != HMGPU_OK) return st;
+  }
+  if (px) r->po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || r->bs[0] % 4 == 0);
+  if (lut) { const hmgpu_status st = colour_resolve(c, d, lut, cs); if (st != HMGPU_OK) return st; }
+  if (ch) { const hmgpu_status st = chroma_rules(d, ch); if (st != HMGPU_OK) return st; }
+  return warp_rules(&c->seq, d, n, wp, maps);
+}
+
+hmgpu_status hmgpu_export_warp_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_tensor* t,
+                                                 const hmgpu_export_window windows[], const hmgpu_export_pixel* px, hmgpu_lut lut,
+                                                 const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp, const hmgpu_warp_map maps[],
+                                                 void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  hmgpu_ctx::ColourSlot* cs = nullptr;
+  return warp_resolve(c, n, d, t, windows, px, lut, ch, wp, maps, dst, pitch_bytes, batch_stride_bytes, &r, &cs);
+}
+
 }  // extern "C"
 
 // what ExportArgs and ScaleArgs share behind their sources: the depth rule, the destination, the float conversion, the plan's constants
@@ -1187,6 +1282,62 @@ hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* c, int32_t n, const hmgpu_p
                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
   if (!batch_stride_bytes) return HMGPU_EINVAL;
   return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, lut ? &lut : nullptr, true, chroma);
+}
+
+// the warp export: n pictures of the RGB layout, each through its own map; one launch, the maps and windows in one copy through the
+// window ring
+hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                        const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                        hmgpu_lut lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* wp,
+                                        const hmgpu_warp_map maps[], void* const dst[3], const int64_t pitch_bytes[3],
+                                        const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || !batch_stride_bytes ||
+      (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+  ExportCall r;
+  hmgpu_ctx::ColourSlot* cs = nullptr;
+  { const hmgpu_status st = warp_resolve(c, n, desc, t, windows, px, lut, chroma, wp, maps, dst, pitch_bytes, batch_stride_bytes, &r, &cs);
+    if (st != HMGPU_OK) return st; }
+  // the chroma stage: 4:4:4 and 4:0:0, where it is the identity, and HMGPU_CHROMA_REPLICATE run the instances without it
+  ChromaSite site;
+  const bool linear = chroma && chroma->filter == HMGPU_CHROMA_LINEAR && (c->seq.chroma_format == 1 || c->seq.chroma_format == 2);
+  if (linear) chroma_site(c->seq, *chroma, &site);
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::TableBuf* wb = &c->window_buf[c->window_next];
+  c->window_next = (c->window_next + 1) % hmgpu_ctx::kWindowBufs;
+  // (the export that read the buffer last may still be in flight)
+  const size_t bytes = (size_t)n * sizeof(WarpPic);
+  { const hmgpu_status st = table_room(c, wb, bytes, 4096); if (st != HMGPU_OK) return st; }
+  WarpArgs a;
+  memset(&a, 0, sizeof(a));
+  WarpPic* wpic = reinterpret_cast<WarpPic*>(wb->host);
+  for (int i = 0; i < n; i++) {
+    const Picture& p = c->pics[pics[i]];
+    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+    a.src[i][0] = src[0]; a.src[i][1] = src[1];
+    const int32_t* cr = windows ? windows[i].crop : desc->crop;
+    WarpPic& k = wpic[i];
+    memset(&k, 0, sizeof(k));
+    memcpy(k.m, maps[i].m, sizeof(k.m));
+    k.x0 = cr[0]; k.y0 = cr[2];
+    k.ws = c->seq.width - cr[0] - cr[1]; k.hs = c->seq.height - cr[2] - cr[3];
+  }
+  HIP_TRY(c, hipMemcpyAsync(wb->dev, wb->host, bytes, hipMemcpyHostToDevice, hs));
+  a.pics = reinterpret_cast<const WarpPic*>(wb->dev);
+  a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
+  a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+  a.w = wp->width; a.h = wp->height; a.tiles_x = (wp->width + kWarpTileW - 1) / kWarpTileW;
+  a.filter = wp->filter; a.border = wp->border;
+  for (int k = 0; k < 3; k++) a.fill[k] = wp->border == HMGPU_WARP_FILL ? (uint32_t)wp->fill[k] : 0;
+  a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
+  if (px) a.px = r.po;
+  export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
+  launch_export_warp(a, linear ? &site : nullptr, cs ? &cs->lut : nullptr, r.elem, n, r.nch, hs);
+  if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
+  HIP_TRY(c, hipEventRecord(wb->done, hs));
+  wb->pending = true;
+  return export_end(c, n, pics, on_stream, hs);
 }
 
 // ------------------------------------------------------------------------------------------------ side information: what motion and residual share

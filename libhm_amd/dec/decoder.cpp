@@ -1003,8 +1003,13 @@ hmgpu_status Decoder::export_picture(PicData* pic, const hmgpu_export_desc* desc
 // after the one before): one device call each, a single run when one context holds every picture.  windows: null, or one per picture
 // (each run carries those of its own slots).
 namespace {
-struct ExportRun { int home, first, step, n; hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH]; hmgpu_export_window w[HMGPU_EXPORT_MAX_BATCH]; };
-std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_export_window* windows) {
+struct ExportRun {
+  int home, first, step, n;
+  hmgpu_pic h[HMGPU_EXPORT_MAX_BATCH];
+  hmgpu_export_window w[HMGPU_EXPORT_MAX_BATCH];
+  hmgpu_warp_map m[HMGPU_EXPORT_MAX_BATCH];                                // export_warp: the maps of the run's slots
+};
+std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_export_window* windows, const hmgpu_warp_map* maps = nullptr) {
   std::vector<ExportRun> runs;
   std::vector<bool> taken((size_t)n, false);
   for (int i = 0; i < n; i++) {
@@ -1019,6 +1024,7 @@ std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_expo
     for (size_t q = 0; q < m; q++) {
       r.h[q] = pics[idx[q]]->handle;
       if (windows) r.w[q] = windows[idx[q]];
+      if (maps) r.m[q] = maps[idx[q]];
       taken[(size_t)idx[q]] = true;
     }
     runs.push_back(r);
@@ -1113,6 +1119,40 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_e
     const hmgpu_status st = pixel ? hmgpu_pictures_export_pixels(c, r.n, r.h, desc, scale, tensor, windows ? r.w : nullptr, pixel, d[0], pitch_bytes[0], bs[0], on_stream, stream)
                           : windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
                                     : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
+// hmgpu_pictures_export_warp under the rules of export_pictures: the whole batch validated once in the first picture's context, then
+// one call per run of slots with the run's own windows and maps, each with the LUT's handle in its own context
+hmgpu_status Decoder::export_warp(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
+                                  const hmgpu_export_window* windows, const hmgpu_export_pixel* pixel, int64_t lut,
+                                  const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map* maps,
+                                  void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
+                                  void* stream) {
+  if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  auto it = lut ? luts_.find(lut) : luts_.end();
+  if (lut && it == luts_.end()) return HMGPU_EINVAL;
+  const bool col = it != luts_.end();
+  hmgpu_lut h = 0;
+  if (col) { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = hmgpu_export_warp_destination_check(ctx_of(pics[0]), n, desc, tensor, windows, pixel, h, chroma, warp, maps, dst,
+                                                                pitch_bytes, batch_stride_bytes);
+    if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, windows, maps);
+  if (col) for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
+  for (const ExportRun& r : runs) {
+    void* d[3];
+    int64_t bs[3];
+    for (int k = 0; k < 3; k++) {
+      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
+      bs[k] = batch_stride_bytes[k] * r.step;
+    }
+    if (col) (void)colour_lut_on(it->second, r.home, &h);
+    const hmgpu_status st = hmgpu_pictures_export_warp(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, tensor,
+                                                       windows ? r.w : nullptr, pixel, h, chroma, warp, r.m, d, pitch_bytes, bs, on_stream, stream);
     if (st != HMGPU_OK) return st;
   }
   return HMGPU_OK;

@@ -78,6 +78,12 @@ class Decoder {
                                const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr,
                                const hmgpu_export_pixel* pixel = nullptr, const int64_t* lut = nullptr,
                                const hmgpu_export_chroma* const* chroma = nullptr);   // chroma: hmgpu_pictures_export_chroma (*lut 0: no colour stage)
+  // hmgpu_pictures_export_warp under the rules of export_pictures (lut 0: no colour stage; chroma nullptr: replicate); each run of
+  // slots carries its own windows and maps
+  hmgpu_status export_warp(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
+                           const hmgpu_export_window* windows, const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma,
+                           const hmgpu_export_warp* warp, const hmgpu_warp_map* maps, void* const dst[3], const int64_t pitch_bytes[3],
+                           const int64_t batch_stride_bytes[3], int on_stream, void* stream);
   // colour LUTs (hmgpu_colour_lut_create): the host copy lives here, the device copies are made per context when an export first
   // needs one (lut of export_pictures: hmgpu_pictures_export_colour) and go with the contexts of a sequence that ends
   hmgpu_status colour_lut_create(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice, int64_t* out);

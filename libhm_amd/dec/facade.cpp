@@ -366,6 +366,17 @@ int hmdec_pictures_export_chroma(libHMDec_context* ctx, int n, libHMDec_picture*
   for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
   return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut, &chroma);
 }
+int hmdec_pictures_export_warp(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                               const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel,
+                               int64_t lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map maps[],
+                               void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
+                               void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_warp(n, p, desc, tensor, windows, pixel, lut, chroma, warp, maps, dst, pitch_bytes,
+                                                     batch_stride_bytes, on_stream, stream);
+}
 int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_motion_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,
                                  void* dst_block, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],

@@ -230,6 +230,102 @@ def random_resized_crop(n, width, height, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4
     return windows, flips
 
 
+# ------------------------------------------------------------------------------------------------ warp maps (include/hmgpu.h "affine warp export")
+# A map is six Q16 ints m: source sample index (x, y) = (m0*ox + m1*oy + m2, m3*ox + m4*oy + m5) / 65536 for the output pixel
+# (ox, oy); the source is the window of the slot.  Sizes are (height, width), as size= of the exports.
+WARP_IDENTITY = (65536, 0, 0, 0, 65536, 0)
+
+
+def _q16(v):
+    """round half away from zero to Q16"""
+    import math
+    v = float(v) * 65536.0
+    return int(math.floor(v + 0.5)) if v >= 0 else -int(math.floor(-v + 0.5))
+
+
+def one_map(warp):
+    """warp= of the single-picture exports: None, one map of six ints, or a list / [1, 6] array of one map; returns None or [map]"""
+    if warp is None:
+        return None
+    warp = list(warp)
+    return [warp] if len(warp) == 6 and not hasattr(warp[0], "__len__") else warp
+
+
+def affine_map(out_size, src_size, angle=0.0, scale=1.0, shear=(0.0, 0.0), translate=(0.0, 0.0), centre=None):
+    """the inverse map of torchvision's affine parameterisation -- the picture sheared (degrees, x then y), scaled, rotated by
+    `angle` degrees about `centre` (counter-clockwise positive, as F.rotate), then moved by translate=(tx, ty) output samples -- from
+    the out_size (height, width) output onto the src_size source.  centre: (cx, cy) in source samples, a sample's centre at
+    index + 0.5; None: the middle of the source, which lands in the middle of the output.  The inverse is computed in float64 with
+    the half-sample centres folded in (source index = A (o + 0.5) + b - 0.5) and each value rounded half away from zero to Q16."""
+    import math
+    oh, ow = (float(v) for v in out_size)
+    sh, sw = (float(v) for v in src_size)
+    cx, cy = (sw / 2.0, sh / 2.0) if centre is None else (float(centre[0]), float(centre[1]))
+    if not isinstance(shear, (tuple, list)):
+        shear = (shear, 0.0)
+    rot, sx, sy = -math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    inv = (d / scale, -b / scale, -c / scale, a / scale)
+    px, py = 0.5 - ow / 2.0 - float(translate[0]), 0.5 - oh / 2.0 - float(translate[1])
+    bx = inv[0] * px + inv[1] * py + cx - 0.5
+    by = inv[2] * px + inv[3] * py + cy - 0.5
+    return tuple(_q16(v) for v in (inv[0], inv[1], bx, inv[2], inv[3], by))
+
+
+def random_affine(n, out_size, src_size, degrees=0.0, translate=None, scale=None, shear=None, generator=None):
+    """n maps (affine_map) sampled as torchvision's RandomAffine.get_params samples them: angle uniform in degrees (a number d:
+    (-d, d)); translate (a, b): tx, ty uniform within a, b times the output width, height and rounded; scale (lo, hi): uniform;
+    shear: a number s (x in (-s, s)), (lo, hi) (x), or (xlo, xhi, ylo, yhi).  Deterministic for a seeded torch.Generator (CPU)."""
+    import torch
+
+    def uniform(lo, hi):
+        return float(torch.empty(1).uniform_(float(lo), float(hi), generator=generator).item())
+
+    deg = (-float(degrees), float(degrees)) if not isinstance(degrees, (tuple, list)) else tuple(degrees)
+    if shear is not None and not isinstance(shear, (tuple, list)):
+        shear = (-float(shear), float(shear))
+    maps = []
+    for _ in range(n):
+        angle = uniform(deg[0], deg[1])
+        tx = ty = 0.0
+        if translate is not None:
+            mx, my = float(translate[0]) * out_size[1], float(translate[1]) * out_size[0]
+            tx, ty = float(round(uniform(-mx, mx))), float(round(uniform(-my, my)))
+        sc = uniform(scale[0], scale[1]) if scale is not None else 1.0
+        shx = shy = 0.0
+        if shear is not None:
+            shx = uniform(shear[0], shear[1])
+            if len(shear) == 4:
+                shy = uniform(shear[2], shear[3])
+        maps.append(affine_map(out_size, src_size, angle, sc, (shx, shy), (tx, ty)))
+    return maps
+
+
+def orientation_map(k, vflip=False, hflip=False, src_size=None):
+    """(map, out_size) of a display orientation: the src_size (height, width) source mirrored (vflip: top to bottom, hflip: left to
+    right), then turned by k quarter turns counter-clockwise (torch.rot90's k).  Built in integers: every value is an exact multiple
+    of 65536, so the export is a permutation of the source under either filter.  k = 1 with hflip is the transpose."""
+    h, w = (int(v) for v in src_size)
+    k %= 4
+    # the source (x, y) in the mirrored picture as (a, b, c): a*ox + b*oy + c
+    if k == 0:
+        fx, fy, out = (1, 0, 0), (0, 1, 0), (h, w)
+    elif k == 1:
+        fx, fy, out = (0, -1, w - 1), (1, 0, 0), (w, h)
+    elif k == 2:
+        fx, fy, out = (-1, 0, w - 1), (0, -1, h - 1), (h, w)
+    else:
+        fx, fy, out = (0, 1, 0), (-1, 0, h - 1), (w, h)
+    if hflip:
+        fx = (-fx[0], -fx[1], w - 1 - fx[2])
+    if vflip:
+        fy = (-fy[0], -fy[1], h - 1 - fy[2])
+    return tuple(65536 * v for v in fx + fy), out
+
+
 def plane_shapes(plan, desc):
     """the shape of every plane tensor: [H, W], or [H, W, 2] for the CbCr plane of the semi-planar layout"""
     return [(plan.height[k], plan.width[k], 2) if desc.layout == abi.EXPORT_SEMIPLANAR and k == 1 else (plan.height[k], plan.width[k])
@@ -373,16 +469,22 @@ def out_pixels(out, plan, desc, px, device, n=None, dtype=None):
 
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
                    filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None,
-                   pixel=None, alpha=None, memory_format=None, pixel_call=None):
+                   pixel=None, alpha=None, memory_format=None, pixel_call=None, warp=None):
     """allocate with torch on `device` (or take `out`) and run `call(desc, scale, tensor, ptrs, pitches, bstrides, stream)` on torch's
     current stream.  scale: None (size None), else the abi.ExportScale of size (height, width) and filter; tensor: None (dtype None),
     else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); bstrides: None for one picture
     (n None), else the bytes between the batch entries of every plane of the n pictures.  windows: None, or the abi.ExportWindow of
     every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0).
     pixel / alpha / memory_format (make_pixel): packed pixels, ONE tensor [H, W, C] ([N, H, W, C]; channels-last [N, 3, H, W]) through
-    `pixel_call(desc, scale, tensor, pixel, ptr, pitch, bstride, stream)`; bstride of one picture: the extent of its rows."""
+    `pixel_call(desc, scale, tensor, pixel, ptr, pitch, bstride, stream)`; bstride of one picture: the extent of its rows.
+    warp: None, or (abi.ExportWarp, abi.WarpMap array) of abi.warp_stage: size and filter belong to it, the calls get no scale and the
+    plan is hmgpu_export_warp_plan_for's."""
     import torch
-    from . import export_pixels_plan, export_tensor_plan, export_windows_plan
+    from . import export_pixels_plan, export_tensor_plan, export_warp_plan, export_windows_plan
+    if warp is not None:
+        if layout_code(layout) != abi.EXPORT_RGB:
+            raise ValueError("warp needs layout=\"rgb\"")
+        size = None
     px = make_pixel(pixel, alpha, memory_format, layout, dtype, n)
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
     desc = make_desc(layout, bit_depth, crop if windows is None else (0, 0, 0, 0), matrix, full_range, msb_aligned,
@@ -390,7 +492,8 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
     sc = make_scale(size, filter)
     tensor = make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias)
     if px is not None:
-        plan = export_pixels_plan(seq, desc, sc, tensor, windows, px)
+        plan = (export_pixels_plan(seq, desc, sc, tensor, windows, px) if warp is None else
+                export_warp_plan(seq, desc, tensor, windows, px, None, None, warp[0], warp[1], n or 1))
         with torch.cuda.device(device):
             if out is None:
                 out = alloc_pixels(plan, desc, px, device, n, dtype, memory_format is not None)
@@ -400,7 +503,10 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
             stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
             pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, stream)
         return out
-    plan = export_tensor_plan(seq, desc, sc, tensor) if windows is None else export_windows_plan(seq, desc, sc, tensor, windows)
+    if warp is not None:
+        plan = export_warp_plan(seq, desc, tensor, windows, None, None, None, warp[0], warp[1], n or 1)
+    else:
+        plan = export_tensor_plan(seq, desc, sc, tensor) if windows is None else export_windows_plan(seq, desc, sc, tensor, windows)
     with torch.cuda.device(device):
         if out is None:
             out = alloc_outputs(plan, desc, device, n, dtype)

@@ -91,6 +91,10 @@ def lib():
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                    C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma), C.POINTER(C.c_void_p),
                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_warp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                 C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel),
+                                                 C.c_int64, C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_picture_chroma_loc.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_pictures_export_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MotionDesc),
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.c_void_p,
@@ -247,7 +251,7 @@ class Picture:
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None, lut=None,
-               chroma="replicate", chroma_loc=None):
+               chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
@@ -260,9 +264,14 @@ class Picture:
         from the stream's own colour description (VUI primaries and transfer; unspecified codes raise) to BT.709 with the sRGB
         curve, tone-mapped with BT.2390, made once per decoder, source and depth.  chroma (layout "rgb"): "replicate", or "linear":
         Cb and Cr interpolated to the luma grid before the matrix at chroma_loc, a chroma_sample_loc_type 0 .. 5 or None: the
-        stream's own (chroma_loc()["top_field"], 0 when absent).  Valid until the next push into the decoder."""
+        stream's own (chroma_loc()["top_field"], 0 when absent).  warp (layout "rgb"): one inverse affine map of six Q16 ints
+        (export.affine_map, export.orientation_map) from the size= output, then required, onto the crop; filter "bilinear" or
+        "nearest", border "edge" or "fill" with fill=(r, g, b) (hmdec_pictures_export_warp).  Valid until the next push into the
+        decoder."""
+        from . import export
         return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias,
-                       pixel=pixel, alpha=alpha, lut=lut, chroma=chroma, chroma_loc=chroma_loc)
+                       pixel=pixel, alpha=alpha, lut=lut, chroma=chroma, chroma_loc=chroma_loc, warp=export.one_map(warp), border=border,
+                       fill=fill)
 
     def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
         """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
@@ -387,17 +396,19 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
             scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None, lut=None,
-            chroma="replicate", chroma_loc=None):
+            chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
     the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
     windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
     (export.make_pixel, hmdec_pictures_export_pixels); lut: a DecoderColourLut, a raw handle or "sdr"
     (hmdec_pictures_export_colour); chroma / chroma_loc: "linear" goes through hmdec_pictures_export_chroma, with the first picture's
-    VUI sample location for chroma_loc None; "replicate" through the entries it always took"""
-    from . import HmgpuError, export, export_tensor_plan
+    VUI sample location for chroma_loc None; "replicate" through the entries it always took; warp / border / fill: one map per
+    picture (abi.warp_stage) through hmdec_pictures_export_warp, whatever the other stages"""
+    from . import HmgpuError, export, export_tensor_plan, export_warp_plan
     first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
     chr_ = abi.chroma_stage(chroma, chroma_loc, first.chroma_loc()["top_field"])
+    wrp = abi.warp_stage(warp, size, filter, border, fill, n if not enqueue else len(pictures))
     if isinstance(lut, str):
         if lut != "sdr":
             raise ValueError("lut: a colour LUT of the decoder, or \"sdr\"")
@@ -406,6 +417,13 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     handle = getattr(lut, "handle", lut)
 
     def colour_call(desc, sc, tensor, px, ptrs, pitches, bstrides, st):
+        if wrp is not None:
+            r = lib().hmdec_pictures_export_warp(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(tensor),
+                                                 abi.window_array(win), abi.ref(px), handle or 0, abi.ref(chr_), C.byref(wrp[0]), wrp[1],
+                                                 abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
+            if r != 0:
+                raise HmgpuError(r, "hmdec_pictures_export_warp")
+            return
         if chr_ is not None:
             r = lib().hmdec_pictures_export_chroma(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
                                                    abi.window_array(win), abi.ref(px), handle or 0, C.byref(chr_), abi.ptr_array(ptrs),
@@ -425,12 +443,13 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
         if not enqueue:
             return None
-        if tensor is None and bstrides is None and lut is None and chr_ is None:
+        if tensor is None and bstrides is None and lut is None and chr_ is None and wrp is None:
             return first.export_into(desc, ptrs, pitches, 1, st, sc)
         if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
-            plan = export_tensor_plan(seq, desc, sc, tensor)
+            plan = (export_tensor_plan(seq, desc, sc, tensor) if wrp is None else
+                    export_warp_plan(seq, desc, tensor, win, None, None, None, wrp[0], wrp[1], 1))
             bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-        if lut is not None or chr_ is not None:
+        if lut is not None or chr_ is not None or wrp is not None:
             return colour_call(desc, sc, tensor, None, ptrs, pitches, bstrides, st)
         head = (first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor))
         tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
@@ -444,7 +463,7 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
         if not enqueue:
             return None
-        if lut is not None or chr_ is not None:
+        if lut is not None or chr_ is not None or wrp is not None:
             return colour_call(desc, sc, tensor, px, [ptr], [pitch], [bstride], st)
         r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
                                                abi.window_array(win), C.byref(px), abi.addr(ptr), pitch, bstride, 1, abi.addr(st))
@@ -452,12 +471,13 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
             raise HmgpuError(r, "hmdec_pictures_export_pixels")
     return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,
                                  dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
-                                 pixel_call=pixel_call)
+                                 pixel_call=pixel_call, warp=wrp)
 
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                  filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
-                 pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None):
+                 pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge",
+                 fill=None):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
@@ -466,13 +486,14 @@ def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix
     pixel / alpha: one [N, H, W, C] tensor of packed pixels, memory_format=torch.channels_last: [N, 3, H, W] with channels-last
     strides -- hmdec_pictures_export_pixels; lut: a colour LUT of the pictures' decoder, Decoder.colour_lut, or "sdr" as in
     Picture.export -- hmdec_pictures_export_colour; chroma / chroma_loc as in Picture.export, the sample location that of the first
-    picture -- hmdec_pictures_export_chroma)."""
+    picture -- hmdec_pictures_export_chroma; warp / border / fill as in Context.export_batch: one inverse affine map per picture,
+    size= the output size, the windows of any sizes -- hmdec_pictures_export_warp)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
                    scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format, lut=lut, chroma=chroma,
-                   chroma_loc=chroma_loc)
+                   chroma_loc=chroma_loc, warp=warp, border=border, fill=fill)
 
 
 class DecoderColourLut:
@@ -644,7 +665,10 @@ class Decoder:
         dense form the windows and flips fn(n) returned, and size=, apply to both.  motion=None leaves the items as they were.
         residual (batch=N only): True, or a dict of export_residual_batch arguments (form, components, dtype, scale, ...): the
         residual dict is appended to the items in the same way -- (pocs, tensors, residual dict), or (pocs, tensors, motion dict,
-        residual dict) with motion= -- and its dense form takes each call's windows, flips and size= like the pixels and the motion."""
+        residual dict) with motion= -- and its dense form takes each call's windows, flips and size= like the pixels and the motion.
+        warp (with size=, border=, fill= among the export arguments): one map per picture as in Picture.export; with batch=N a
+        function, fn(n) returns the maps of the n pictures of one batched call (export.random_affine with the sizes bound).  The
+        dense motion and residual forms cannot be aligned with a warp and are refused with it."""
         if windows is not None and batch is None:
             raise ValueError("frames(windows=) needs batch=")
         if motion is not None and motion is not False and batch is None:
@@ -665,7 +689,10 @@ class Decoder:
                         p = self.get_picture()
                         if p is None:
                             break
-                        yield p.poc, p.export(**export_kw)
+                        if callable(export_kw.get("warp")):      # fn(n), as with batch=N: the map of this picture
+                            yield p.poc, p.export(**dict(export_kw, warp=list(export_kw["warp"](1))))
+                        else:
+                            yield p.poc, p.export(**export_kw)
                 if not new_pic:
                     break
 
@@ -677,6 +704,12 @@ class Decoder:
         kw = dict(layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                   filter="bilinear", out=None)
         kw.update(export_kw)
+        warp = export_kw.get("warp")                  # a function: fn(n) returns the maps of one batched call's n pictures
+        if callable(warp):
+            export_kw = {k: v for k, v in export_kw.items() if k != "warp"}
+        from . import export as _export_mod
+        if warp is not None:                          # (the item's allocation: any n maps do)
+            kw["warp"] = [_export_mod.WARP_IDENTITY] * batch
         mkw = None
         from . import motion as _motion
         if motion is not None:
@@ -687,6 +720,8 @@ class Decoder:
                                      "from frames(windows=fn))" % key)
             mkw["form"] = _motion.form_code(mkw.get("form", "blocks"))
             if mkw["form"] == abi.MOTION_DENSE:
+                if warp is not None:
+                    raise ValueError("frames(warp=): the dense motion form cannot be aligned with a warp")
                 mkw.setdefault("size", kw["size"])
                 mkw.setdefault("crop", kw["crop"])
         rkw = None
@@ -699,6 +734,8 @@ class Decoder:
                                      "from frames(windows=fn))" % key)
             rkw["form"] = _residual.form_code(rkw.get("form", "planes"))
             if rkw["form"] == abi.RESIDUAL_DENSE:
+                if warp is not None:
+                    raise ValueError("frames(warp=): the dense residual form cannot be aligned with a warp")
                 rkw.setdefault("size", kw["size"])
                 rkw.setdefault("crop", kw["crop"])
         sides = lambda: tuple(t for t in (mitem if mkw is not None else None, ritem if rkw is not None else None) if t is not None)
@@ -721,9 +758,14 @@ class Decoder:
                         if windows is not None:      # the windows and flips of this call's pictures
                             w, f = windows(len(take))
                             wkw = dict(windows=list(w), flip=None if f is None else list(f))
-                        if item is None:             # the first picture of an item allocates all N slots
+                        pkw = dict(wkw)              # the picture export's own: the maps of this call's pictures
+                        if callable(warp):
+                            pkw["warp"] = list(warp(len(take)))
+                        elif warp is not None:
+                            raise ValueError("frames(batch=, warp=): a function, fn(n) returns the maps of n pictures")
+                        if item is None:            # the first picture of an item allocates all N slots
                             item = _export(take[:1], batch, enqueue=False, windows=[wkw["windows"][0]] * batch if wkw else None, **kw)
-                        export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **wkw, **export_kw)
+                        export_batch(take, out=_slots(item, len(pocs), len(pocs) + len(take)), **pkw, **export_kw)
                         if mkw is not None:
                             mw = wkw if mkw["form"] == abi.MOTION_DENSE else {}
                             if mitem is None:
