@@ -98,6 +98,7 @@ typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
+typedef struct hmgpu_histogram_desc hmgpu_histogram_desc;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
 int hmdec_picture_export(libHMDec_context* ctx, libHMDec_picture* pic, const hmgpu_export_desc* desc, void* const dst[3],
@@ -185,6 +186,14 @@ int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_pictur
 int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc, const void* const ref[3],
                            const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* results,
                            int64_t results_batch_stride_bytes, int on_stream, void* stream);
+/* What up to 16 output pictures kept on the device contain: histograms and moments of Y, Cb, Cr and maxRGB (hmgpu_pictures_histogram:
+ * description, destinations, strides and statuses as there, desc->crop in luma samples of the coded picture), under the rules of
+ * hmdec_pictures_metrics: everything is validated before any context is given work (hmgpu_histogram_check), then each context gets
+ * one call per run of equally spaced slots.  The pictures must be kept on the device (hmdec_set_device_output): without it the call
+ * is refused (HMGPU_EINVAL, hmdec_last_error says why). */
+int hmdec_pictures_histogram(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_histogram_desc* desc, void* const hist[4],
+                             const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes, int on_stream,
+                             void* stream);
 unsigned long long hmdec_download_bytes(libHMDec_context* ctx);
 int hmdec_picture_device(libHMDec_picture* pic);                             /* GPU ordinal that holds the picture's samples, -1: none */
 /* VUI colour description of the picture's SPS (E.2.1; absent: the E.3.1 defaults): video_full_range_flag, colour_primaries,

@@ -897,6 +897,70 @@ hmgpu_status hmgpu_metrics_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics
                                  const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
                                  const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes);
 
+/* ------------------------------------------------------------------------------------------------ picture histograms
+ * What finished pictures contain: per picture and channel a histogram of the sample values and one 64-byte record of
+ * their moments and extrema.  Up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_histogram.hip) behind the memsets
+ * that zero the destinations.  Everything is an integer sum, a minimum or a maximum: two calls on the same inputs give the same bytes.
+ *
+ * Channels (bit c of desc->channels):
+ *   0 Y, 1 Cb, 2 Cr   the final samples of pics[i] -- the plane set the exports read -- inside desc->crop (left, right, top, bottom in
+ *                     luma samples, whole chroma samples, as in hmgpu_metrics_desc), each component at its own resolution; the depth
+ *                     D_c is the coding depth of its channel type
+ *   3 maxRGB          one value per luma sample of the crop, max(R, G, B), where R, G, B are bit for bit what hmgpu_picture_export
+ *                     writes for HMGPU_EXPORT_RGB with the same crop, matrix and full_range and bit_depth[0] = desc->rgb_bit_depth
+ *                     (0: the luma coding depth; 8 .. 12, above 12 HMGPU_EUNSUPPORTED: the bins live in the LDS): chroma replicated,
+ *                     no LUT, before any msb_aligned shift.  D_3 is that depth.  4:0:0 and matrix 0 as in the export (Cb = Cr = mid;
+ *                     the identity is 4:4:4 only).  matrix and full_range are read only when bit 3 is set; a matrix the export does
+ *                     not know is HMGPU_EUNSUPPORTED.
+ * The chroma bits of a 4:0:0 sequence are ignored; at least one channel must remain.
+ * Bins: desc->log2_bins 0: b_c = D_c, one bin per code value; 4 .. 12: b_c = min(log2_bins, D_c).  The bin of a value v is
+ * v >> (D_c - b_c); counts are uint32.  The histogram of picture i, channel c is 2^b_c counts at hist[c] + i * hist_batch_stride_bytes[c]:
+ * 4-byte aligned, the stride at least 4 << b_c and a multiple of 4, all n inside one allocation of the context's device; hist[c] is NULL
+ * exactly for the channels that are not computed.  desc->histogram 0 is a records-only call: every hist[c] must be NULL (hist itself
+ * and hist_batch_stride_bytes may then be NULL).
+ * Records: hmgpu_histogram_result (i, c) at records + i * records_batch_stride_bytes + c * 64 (8-byte aligned, stride >= 256, a
+ * multiple of 8, all n * 4 inside one allocation), always written, over the values v and not the bins -- exact when bins are reduced.
+ * The record of a channel that is not computed is all zero.
+ * Everything is validated before anything is enqueued and a refused call leaves hist and records untouched.  Stream ordering is that of
+ * hmgpu_picture_export, once per call.  The launch is not accounted in hmgpu_stats. */
+enum { HMGPU_HISTOGRAM_Y = 0, HMGPU_HISTOGRAM_CB = 1, HMGPU_HISTOGRAM_CR = 2, HMGPU_HISTOGRAM_MAXRGB = 3 };
+typedef struct hmgpu_histogram_desc {
+  int32_t channels;            /* bit c: channel c (HMGPU_HISTOGRAM_*); at least one */
+  int32_t log2_bins;           /* 0: one bin per code value; 4 .. 12: at most 2^log2_bins bins per channel */
+  int32_t histogram;           /* 1: histograms and records; 0: records only */
+  int32_t rgb_bit_depth;       /* maxRGB: the depth of R, G, B, 8 .. 12; 0 = the luma coding depth */
+  int32_t matrix, full_range;  /* maxRGB: as in hmgpu_export_desc; not read without bit 3 */
+  int32_t crop[4];             /* left, right, top, bottom in luma samples; must cover whole chroma samples */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_histogram_desc;
+typedef struct hmgpu_histogram_result {   /* 64 bytes, one per picture and channel */
+  uint64_t samples;            /* values counted: w_c * h_c */
+  uint64_t sum;                /* sum v */
+  uint64_t sum_sq;             /* sum v^2 */
+  uint32_t min, max;           /* least and greatest v */
+  uint32_t reserved[8];        /* 0 */
+} hmgpu_histogram_result;
+typedef struct hmgpu_histogram_plan {
+  int32_t channels[4];         /* per channel: 1 = computed (selected, and the format has it), 0 = its record is all zero */
+  int32_t width[4], height[4]; /* the cropped plane the channel counts (maxRGB: the luma one) */
+  int32_t depth[4];            /* D_c */
+  int32_t log2_bins[4];        /* b_c */
+  int32_t hist_bytes[4];       /* 4 << b_c, the least hist_batch_stride_bytes; 0 when desc->histogram == 0 */
+  int32_t record_bytes;        /* per picture: 4 * sizeof(hmgpu_histogram_result), the least records_batch_stride_bytes */
+  int32_t coef[16];            /* maxRGB: hmgpu_export_plan.coef of the equivalent RGB descriptor; else 0 */
+  int32_t reserved[3];         /* 0 */
+} hmgpu_histogram_plan;
+/* validates a call's description and reports what it counts; host code, no device needed.  HMGPU_EUNSUPPORTED for a cropped luma plane
+ * of 2^31 samples or more (every count and the int32 views of them stay below 2^31) */
+hmgpu_status hmgpu_histogram_plan_for(const hmgpu_seq_params* seq, const hmgpu_histogram_desc* desc, hmgpu_histogram_plan* out);
+hmgpu_status hmgpu_pictures_histogram(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* desc,
+                                      void* const hist[4], const int64_t hist_batch_stride_bytes[4], void* records,
+                                      int64_t records_batch_stride_bytes, int32_t on_stream, void* stream);
+/* the validation of hmgpu_pictures_histogram alone, nothing enqueued: the status that call would give */
+hmgpu_status hmgpu_histogram_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* desc,
+                                   void* const hist[4], const int64_t hist_batch_stride_bytes[4], void* records,
+                                   int64_t records_batch_stride_bytes);
+
 /* ------------------------------------------------------------------------------------------------ call 1
  * Replaces the reconstruction half of TDecGop::decompressSlice -> TDecSlice::decompressSlice ->
  * TDecCu::decompressCU (TDecSlice.cpp:334, TDecCu.cpp:142,373) for the CTUs [first_ctu, first_ctu+num_ctus) of

@@ -178,6 +178,10 @@ def lib():
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                              C.c_int32, C.c_void_p]
         L.hmgpu_metrics_check.argtypes = L.hmgpu_pictures_metrics.argtypes[:10]
+        L.hmgpu_histogram_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.HistogramDesc), C.POINTER(abi.HistogramPlan)]
+        L.hmgpu_pictures_histogram.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.HistogramDesc),
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.hmgpu_histogram_check.argtypes = L.hmgpu_pictures_histogram.argtypes[:8]
         L.hmgpu_stream.argtypes = [C.c_void_p]
         L.hmgpu_stream.restype = C.c_void_p
         L.hmgpu_decompress_slice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(abi.SliceParams), C.POINTER(abi.CtuMeta),
@@ -414,6 +418,14 @@ def metrics_plan(seq, reference="pictures", components=(0, 1, 2), ssim=True, cro
     desc = abi.make_metrics_desc(abi.METRICS_REF_PLANES if planes else abi.METRICS_REF_PICTURES, metrics.components_mask(components),
                                  1 if ssim else 0, ref_bytes_per_sample if planes else 0, crop)
     return metrics.plan_for(seq, desc)
+
+
+def histogram_plan(seq, channels=("y", "cb", "cr"), bins=None, crop=(0, 0, 0, 0), matrix=None, full_range=None, rgb_bit_depth=0,
+                   histogram=True):
+    """what Context.histogram with these arguments counts (hmgpu_histogram_plan_for: host code, no GPU): an abi.HistogramPlan -- per
+    channel width, height, depth, log2 of the bins, the bytes of a histogram, and the RGB constants of maxRGB"""
+    from . import histogram as hg
+    return hg.plan_for(seq, hg.describe(channels, bins, crop, matrix, full_range, rgb_bit_depth, histogram))
 
 
 def export_scale_taps(seq, desc, scale, chroma, axis):
@@ -868,6 +880,35 @@ class Context:
         return metrics.metrics(lambda desc, rp, ptrs, pitches, bstrides, res, rs, st:
                                self.metrics_into(pics, desc, res, rs, rp, ptrs, pitches, bstrides, 1 if on_stream else 0, st),
                                self.seq, self.device, len(pics), None if ref_pics is None else list(ref_pics), ref, components, ssim, crop)
+
+    def histogram_into(self, pics, desc, records, records_stride, ptrs=None, strides=None, on_stream=0, stream=0):
+        """hmgpu_pictures_histogram into device memory the caller owns: `records` the address of [n][4] records, records_stride bytes
+        from picture to picture; ptrs / strides: per channel the address of its n histograms and the bytes from one to the next"""
+        from . import histogram as hg
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_histogram(self._h, len(pics), abi.handle_array(pics), C.byref(desc), *hg.c_args(ptrs, strides),
+                                                 abi.addr(records), records_stride, on_stream, abi.addr(stream)), "hmgpu_pictures_histogram")
+
+    def histogram_status(self, pics, desc, records, records_stride, ptrs=None, strides=None):
+        """hmgpu_histogram_check: the status hmgpu_pictures_histogram would give these arguments; enqueues nothing"""
+        from . import histogram as hg
+        pics = list(pics)
+        return lib().hmgpu_histogram_check(self._h, len(pics), abi.handle_array(pics), C.byref(desc), *hg.c_args(ptrs, strides),
+                                           abi.addr(records), records_stride)
+
+    def histogram(self, pics, channels=("y", "cb", "cr"), bins=None, crop=(0, 0, 0, 0), matrix=None, full_range=None, rgb_bit_depth=0,
+                  histogram=True, on_stream=True):
+        """what up to 16 pictures contain, counted on this context's GPU: {"y": {...}, "cb": {...}, "cr": {...}, "maxrgb": {...}}, per
+        channel "hist" (int32 [n, bins]; one bin per code value, or bins= a power of two 16 .. 4096; absent with histogram=False) and
+        tensors [n] of samples, sum, sum_sq (int64), min and max (int32) over the values (libhm_amd.histogram; its mean / variance / percentile /
+        distance / light_level read them).  "maxrgb" is max(R, G, B) of the RGB export with the same crop, matrix and full_range (None:
+        BT.709, limited) at rgb_bit_depth bits (0: the luma coding depth).  One launch on torch's current stream (on_stream) or the
+        context's own; nothing synchronises."""
+        from . import histogram as hg
+        pics = list(pics)
+        return hg.histogram(lambda desc, ptrs, strides, rec, rs, st:
+                            self.histogram_into(pics, desc, rec, rs, ptrs, strides, 1 if on_stream else 0, st),
+                            self.seq, self.device, len(pics), channels, bins, crop, matrix, full_range, rgb_bit_depth, histogram)
 
     def download_packed(self, pic, bytes_per_sample, crop=(0, 0, 0, 0)):
         """the picture as 8- or 16-bit planes cropped by (left, right, top, bottom) luma samples"""

@@ -330,6 +330,36 @@ def make_metrics_desc(reference, components=7, ssim=1, ref_bytes_per_sample=0, c
     return d
 
 
+HISTOGRAM_Y, HISTOGRAM_CB, HISTOGRAM_CR, HISTOGRAM_MAXRGB = 0, 1, 2, 3
+
+
+class HistogramDesc(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("log2_bins", C.c_int32), ("histogram", C.c_int32), ("rgb_bit_depth", C.c_int32),
+                ("matrix", C.c_int32), ("full_range", C.c_int32), ("crop", C.c_int32 * 4), ("reserved", C.c_int32 * 6)]
+
+
+class HistogramResult(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class HistogramPlan(C.Structure):
+    _fields_ = [("channels", C.c_int32 * 4), ("width", C.c_int32 * 4), ("height", C.c_int32 * 4), ("depth", C.c_int32 * 4),
+                ("log2_bins", C.c_int32 * 4), ("hist_bytes", C.c_int32 * 4), ("record_bytes", C.c_int32), ("coef", C.c_int32 * 16),
+                ("reserved", C.c_int32 * 3)]
+
+
+def make_histogram_desc(channels=7, log2_bins=0, histogram=1, rgb_bit_depth=0, matrix=1, full_range=0, crop=(0, 0, 0, 0)):
+    """channels: the mask (bit c: channel c, HISTOGRAM_*); log2_bins: 0 (one bin per code value) or 4 .. 12; histogram: 0 for the
+    records alone; rgb_bit_depth / matrix / full_range: of maxRGB, as in make_export_desc; crop: (left, right, top, bottom) in luma samples"""
+    d = HistogramDesc()
+    d.channels, d.log2_bins, d.histogram, d.rgb_bit_depth = int(channels), int(log2_bins), int(histogram), int(rgb_bit_depth)
+    d.matrix, d.full_range = int(matrix), int(full_range)
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    return d
+
+
 def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, crop=(0, 0, 0, 0), matrix=1, full_range=0):
     d = ExportDesc()
     d.layout = layout

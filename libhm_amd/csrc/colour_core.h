@@ -9,6 +9,28 @@
 
 namespace hmgpu {
 
+// One sample's R'G'B' by the rule of the RGB exports (k_export.hip: the integer matrix of hmgpu_export_plan.coef, or the identity's
+// bit-depth rule per channel type when coef[10] is set), for callers that hold the plan's constants without an ExportArgs
+// (k_histogram.hip).  sh / maxv: output depth minus coding depth, and 2^depth - 1, per channel type.
+__device__ inline int colour_depth_conv(int v, int sh, int maxv) {
+  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
+}
+__device__ inline void colour_rgb(const int32_t* coef, const int32_t* sh, const int32_t* maxv, int y, int u, int v, uint32_t* R, uint32_t* G,
+                                  uint32_t* B) {
+  if (coef[10]) {
+    *G = (uint32_t)colour_depth_conv(y, sh[0], maxv[0]);
+    *B = (uint32_t)colour_depth_conv(u, sh[1], maxv[1]);
+    *R = (uint32_t)colour_depth_conv(v, sh[1], maxv[1]);
+  } else {
+    const int S = coef[0], M = coef[9];
+    const int t = coef[4] * (y - coef[2]) + coef[1];
+    const int cu = u - coef[3], cv = v - coef[3];
+    *R = (uint32_t)min(M, max(0, (t + coef[5] * cv) >> S));
+    *G = (uint32_t)min(M, max(0, (t + coef[6] * cu + coef[7] * cv) >> S));
+    *B = (uint32_t)min(M, max(0, (t + coef[8] * cu) >> S));
+  }
+}
+
 // position 0 .. 65535 of the code value v of channel c.  A lane converts four columns even where the row ends sooner; what it read
 // beyond the row is margin of any content, so v is bounded here before it indexes anything.
 __device__ inline uint32_t colour_pos(const ColourLut& l, int c, uint32_t v) {

@@ -625,6 +625,30 @@ struct MetricsArgs {
   uint32_t bvec;                          // REF_PLANES, bit c: the same for the planes of component c
 };
 void launch_metrics(const MetricsArgs& a, int ref_kind, bool ssim, hipStream_t s);   // ref_kind: 0 pictures, 1 uint8 planes, 2 uint16 planes
+// picture histograms (k_histogram.hip, hmgpu_pictures_histogram): everything by value, validated on the host.  Plane class 0 walks the
+// cropped luma plane and counts Y (channel 0) and maxRGB (channel 3) of a sample together, class 1 the chroma pair plane (channels 1
+// and 2 from one load); a class with no selected channel has no tiles.  Work items and tiles as in MetricsArgs without SSIM.
+constexpr int kHistTileW = 256, kHistTileH = 8;
+constexpr int kHistMaxBins = 4096;          // 2^12: a channel's bins in the LDS, two channels per class
+constexpr int kHistGrid = 1024;             // four workgroups per CU: what 32 KB of LDS each leaves room for
+struct HistogramArgs {
+  const int16_t* y[kMaxExportBatch];      // per picture: luma sample (crop left, crop top)
+  const int16_t* c[kMaxExportBatch];      // Cb of the same chroma sample in the pair plane
+  uint8_t* hist[4];                       // per channel: histogram of picture i at hist[c] + i * hstride[c], zeroed before the launch
+  int64_t hstride[4];
+  uint8_t* records;                       // record (i, c) at records + i * rstride + c * 64, zeroed before the launch
+  int64_t rstride;
+  int32_t n, chans;                       // pictures; the channel mask (only channels that are computed)
+  int32_t do_hist;                        // 0: records only
+  int32_t w[2], h[2], pitch[2];           // per class: the cropped plane in samples; the source pitch in int16 elements
+  int32_t tiles_x[2], tiles[2];           // per class: tiles per tile row, tiles per picture (0: class not selected)
+  int32_t per, total;                     // items per workgroup, items of the call
+  int32_t shift[4], log2_bins[4];         // per channel: D_c - b_c, b_c
+  uint32_t yvec, cvec, rvec;              // bit i: picture i takes whole loads of 4 luma samples / of 4 chroma pairs / of the chroma of 4 luma samples
+  int32_t csx, csy, mono;                 // maxRGB: chroma subsampling; 4:0:0
+  int32_t coef[16], sh[2], maxv[2];       // maxRGB: hmgpu_export_plan.coef and the depth rule of the identity, as ExportArgs
+};
+void launch_histogram(const HistogramArgs& a, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);

@@ -1,8 +1,8 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
 // slots, window tables, colour LUTs, the chroma stage's rules and weights, export_resolve under export_impl and the picture destination checks, the warp export's rules and its
 // per-call maps, strided_dst_ok under the motion / block
-// and residual exports and the reference planes of the picture metrics (k_export.hip, k_export_px.hip, k_export_scale.hip,
-// k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip).
+// and residual exports and the reference planes of the picture metrics, the picture histograms (k_export.hip, k_export_px.hip,
+// k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip, k_histogram.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -1736,6 +1736,148 @@ hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* c, int32_t n, const hmgpu_pic pic
   else HIP_TRY(c, hipMemset2DAsync(results, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
   launch_metrics(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
   if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+// ------------------------------------------------------------------------------------------------ picture histograms (k_histogram.hip)
+static hmgpu_status histogram_plan(const hmgpu_seq_params* seq, const hmgpu_histogram_desc* d, hmgpu_histogram_plan* out) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const int fmt = seq->chroma_format, bd[2] = {seq->bit_depth_luma, seq->bit_depth_chroma};
+  if (fmt < 0 || fmt > 3 || bd[0] < 8 || bd[0] > 12 || bd[1] < 8 || bd[1] > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->channels < 1 || d->channels > 15 || (d->histogram != 0 && d->histogram != 1)) return HMGPU_EINVAL;
+  if (d->log2_bins != 0 && (d->log2_bins < 4 || d->log2_bins > 12)) return HMGPU_EINVAL;
+  const int chans = fmt == 0 ? d->channels & 9 : d->channels;
+  if (!chans) return HMGPU_EINVAL;                                    // (4:0:0: the chroma bits alone select nothing)
+  int W, H, csx, csy;
+  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
+  if ((int64_t)W * H >= ((int64_t)1 << 31)) return HMGPU_EUNSUPPORTED;  // every count, and an int32 view of it, stays below 2^31
+  chroma_shifts(fmt, &csx, &csy);
+  int depth[4] = {bd[0], bd[1], bd[1], bd[0]};
+  if (chans & 8) {
+    if (d->rgb_bit_depth) {
+      if (d->rgb_bit_depth < 8) return HMGPU_EINVAL;
+      if (d->rgb_bit_depth > 12) return HMGPU_EUNSUPPORTED;            // the bins of a channel fit the LDS up to 2^12
+      depth[3] = d->rgb_bit_depth;
+    }
+    // the RGB export whose samples these are: its rules for matrix and full_range, and its constants
+    hmgpu_export_desc e;
+    memset(&e, 0, sizeof(e));
+    e.layout = HMGPU_EXPORT_RGB; e.bit_depth[0] = depth[3]; e.bytes_per_sample = 2;
+    memcpy(e.crop, d->crop, sizeof(e.crop));
+    e.matrix = d->matrix; e.full_range = d->full_range;
+    hmgpu_export_plan ep;
+    const hmgpu_status st = hmgpu_export_plan_for(seq, &e, &ep);
+    if (st != HMGPU_OK) return st;
+    memcpy(out->coef, ep.coef, sizeof(out->coef));
+  }
+  for (int k = 0; k < 4; k++) {
+    if (!((chans >> k) & 1)) continue;
+    const bool chroma = k == 1 || k == 2;
+    out->channels[k] = 1;
+    out->width[k] = chroma ? W >> csx : W; out->height[k] = chroma ? H >> csy : H;
+    out->depth[k] = depth[k];
+    out->log2_bins[k] = d->log2_bins ? std::min(d->log2_bins, depth[k]) : depth[k];
+    out->hist_bytes[k] = d->histogram ? 4 << out->log2_bins[k] : 0;
+  }
+  out->record_bytes = 4 * (int)sizeof(hmgpu_histogram_result);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_histogram_plan_for(const hmgpu_seq_params* seq, const hmgpu_histogram_desc* d, hmgpu_histogram_plan* out) {
+  const hmgpu_status st = histogram_plan(seq, d, out);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// everything hmgpu_pictures_histogram checks
+static hmgpu_status histogram_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_histogram_desc* d, void* const* hist,
+                                      const int64_t* hstride, void* records, int64_t rstride, hmgpu_histogram_plan* plan) {
+  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = histogram_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+  hipSetDevice(c->device);
+  if (d->histogram && (!hist || !hstride)) return HMGPU_EINVAL;
+  for (int k = 0; k < 4; k++) {
+    void* const p = hist ? hist[k] : nullptr;
+    if (!d->histogram || !plan->channels[k]) {
+      if (p) return HMGPU_EINVAL;                                      // a histogram this call does not compute
+      continue;
+    }
+    const int64_t bytes = plan->hist_bytes[k], s = hstride[k];
+    if (!p || (uintptr_t)p % 4 || s < bytes || s % 4 || s > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    if (!device_span_ok(p, (size_t)((n - 1) * s + bytes), c->device)) return HMGPU_EINVAL;
+  }
+  const int64_t rec = plan->record_bytes;
+  if (!records || (uintptr_t)records % 8 || rstride < rec || rstride % 8 || rstride > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+  if (!device_span_ok(records, (size_t)((n - 1) * rstride + rec), c->device)) return HMGPU_EINVAL;
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_histogram_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* d, void* const hist[4],
+                                   const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes) {
+  hmgpu_histogram_plan plan;
+  return histogram_resolve(c, n, pics, d, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes, &plan);
+}
+
+hmgpu_status hmgpu_pictures_histogram(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* d, void* const hist[4],
+                                      const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes,
+                                      int32_t on_stream, void* stream) {
+  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
+  hmgpu_histogram_plan plan;
+  { const hmgpu_status st = histogram_resolve(c, n, pics, d, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes, &plan);
+    if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  HistogramArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.do_hist = d->histogram;
+  a.records = static_cast<uint8_t*>(records); a.rstride = records_batch_stride_bytes;
+  for (int k = 0; k < 4; k++) {
+    if (!plan.channels[k]) continue;
+    a.chans |= 1 << k;
+    a.shift[k] = plan.depth[k] - plan.log2_bins[k]; a.log2_bins[k] = plan.log2_bins[k];
+    if (d->histogram) { a.hist[k] = static_cast<uint8_t*>(hist[k]); a.hstride[k] = hist_batch_stride_bytes[k]; }
+  }
+  for (int k = 0; k < 2; k++) {
+    const int ch = k ? (plan.channels[1] ? 1 : 2) : (plan.channels[0] ? 0 : 3);   // a channel of the class that is computed, if any
+    a.pitch[k] = c->pitch[k];
+    if (!plan.channels[ch]) continue;
+    a.w[k] = plan.width[ch]; a.h[k] = plan.height[ch];
+    a.tiles_x[k] = (a.w[k] + kHistTileW - 1) / kHistTileW;
+    a.tiles[k] = a.tiles_x[k] * ((a.h[k] + kHistTileH - 1) / kHistTileH);
+  }
+  a.csx = c->csx; a.csy = c->csy; a.mono = c->seq.chroma_format == 0;
+  memcpy(a.coef, plan.coef, sizeof(a.coef));
+  for (int k = 0; k < 2; k++) {                                        // maxRGB: the depth rule of the export's identity, both types at D_3
+    a.sh[k] = plan.depth[3] - (k ? c->seq.bit_depth_chroma : c->seq.bit_depth_luma);
+    a.maxv[k] = (1 << plan.depth[3]) - 1;
+  }
+  const int x0 = d->crop[0], y0 = d->crop[2];
+  const size_t rg = c->csx ? 8 : 16;                                   // the chroma of 4 luma samples: 2 pairs or 4
+  for (int i = 0; i < n; i++) {
+    const Picture& p = c->pics[pics[i]];
+    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+    a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
+    a.c[i] = a.mono ? nullptr : src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+    if ((uintptr_t)a.y[i] % 8 == 0 && ((size_t)c->pitch[0] * 2) % 8 == 0) a.yvec |= 1u << i;
+    if (a.mono) continue;
+    if ((uintptr_t)a.c[i] % 16 == 0 && ((size_t)c->pitch[1] * 2) % 16 == 0) a.cvec |= 1u << i;
+    if ((uintptr_t)a.c[i] % rg == 0 && ((size_t)c->pitch[1] * 2) % rg == 0) a.rvec |= 1u << i;
+  }
+  a.total = n * (a.tiles[0] + a.tiles[1]);
+  a.per = (a.total + kHistGrid - 1) / kHistGrid;
+  const int64_t rec = plan.record_bytes;
+  if (n == 1 || a.rstride == rec) HIP_TRY(c, hipMemsetAsync(records, 0, (size_t)(n * rec), hs));
+  else HIP_TRY(c, hipMemset2DAsync(records, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
+  for (int k = 0; k < 4; k++) {
+    if (!a.hist[k]) continue;
+    const int64_t bytes = plan.hist_bytes[k];
+    if (n == 1 || a.hstride[k] == bytes) HIP_TRY(c, hipMemsetAsync(a.hist[k], 0, (size_t)(n * bytes), hs));
+    else HIP_TRY(c, hipMemset2DAsync(a.hist[k], (size_t)a.hstride[k], 0, (size_t)bytes, (size_t)n, hs));
+  }
+  launch_histogram(a, hs);
   return export_end(c, n, pics, on_stream, hs);
 }
 

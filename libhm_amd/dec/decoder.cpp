@@ -1281,6 +1281,41 @@ hmgpu_status Decoder::metrics(int n, PicData* const* pics, const hmgpu_metrics_d
   return HMGPU_OK;
 }
 
+// As metrics: the whole call validated once on the first run's context (its first handle standing for every slot), then every run's
+// handles, then one hmgpu_pictures_histogram per run of equally spaced slots.
+hmgpu_status Decoder::histogram(int n, PicData* const* pics, const hmgpu_histogram_desc* desc, void* const hist[4], const int64_t hist_batch_stride_bytes[4],
+                                void* records, int64_t records_batch_stride_bytes, int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  if (!device_output_) {
+    set_error("hmdec_pictures_histogram: the pictures must be kept on the device (hmdec_set_device_output)");
+    return HMGPU_EINVAL;
+  }
+  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, nullptr);
+  auto ctx_of_run = [&](const ExportRun& r) { return gpus_.empty() ? gpu_ : gpus_[(size_t)r.home]; };
+  {
+    hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
+    for (int i = 0; i < n; i++) all[i] = runs[0].h[0];
+    const hmgpu_status st = hmgpu_histogram_check(ctx_of_run(runs[0]), n, all, desc, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes);
+    if (st != HMGPU_OK) return st;
+  }
+  for (int pass = 0; pass < 2; pass++)
+    for (const ExportRun& r : runs) {
+      void* d[4] = {nullptr, nullptr, nullptr, nullptr};
+      int64_t bs[4] = {0, 0, 0, 0};
+      for (int k = 0; k < 4 && hist && hist_batch_stride_bytes; k++) {
+        d[k] = hist[k] ? static_cast<char*>(hist[k]) + (int64_t)r.first * hist_batch_stride_bytes[k] : nullptr;
+        bs[k] = hist_batch_stride_bytes[k] * r.step;
+      }
+      void* rec = static_cast<char*>(records) + (int64_t)r.first * records_batch_stride_bytes;
+      const int64_t rs = records_batch_stride_bytes * r.step;
+      const hmgpu_status st = pass == 0 ? hmgpu_histogram_check(ctx_of_run(r), r.n, r.h, desc, d, bs, rec, rs)
+                                        : hmgpu_pictures_histogram(ctx_of_run(r), r.n, r.h, desc, d, bs, rec, rs, on_stream, stream);
+      if (st != HMGPU_OK) return st;
+    }
+  return HMGPU_OK;
+}
+
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row
 bool Decoder::md5_plane_matches(const PicData* pic, int comp, int bd, const uint8_t want[16]) {
   Md5 md5;

@@ -100,6 +100,9 @@ class Decoder {
   // hmgpu_pictures_metrics against the caller's planes (HMGPU_METRICS_REF_PLANES), the pictures grouped by context as above
   hmgpu_status metrics(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const void* const ref[3], const int64_t ref_pitch_bytes[3],
                        const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes, int on_stream, void* stream);
+  // hmgpu_pictures_histogram, the pictures grouped by context as above; refused with a message without device output
+  hmgpu_status histogram(int n, PicData* const* pics, const hmgpu_histogram_desc* desc, void* const hist[4], const int64_t hist_batch_stride_bytes[4],
+                         void* records, int64_t records_batch_stride_bytes, int on_stream, void* stream);
   int device_of(const PicData* pic) const { return pic && pic->on_device && pic->owner == this ? devices_[pic->home] : -1; }
   uint64_t download_bytes() const { return download_bytes_; }
   int last_display_poc = -(1 << 30);

@@ -406,6 +406,14 @@ int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const
   return static_cast<Wrapper*>(ctx)->dec.metrics(n, p, desc, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes,
                                                  on_stream, stream);
 }
+int hmdec_pictures_histogram(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_histogram_desc* desc, void* const hist[4],
+                             const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes, int on_stream,
+                             void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.histogram(n, p, desc, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes, on_stream, stream);
+}
 int hmdec_picture_device(libHMDec_picture* pic) {
   if (!pic || !as_pic(pic)->owner) return -1;
   return static_cast<const Decoder*>(as_pic(pic)->owner)->device_of(as_pic(pic));

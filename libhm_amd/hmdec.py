@@ -105,6 +105,8 @@ def lib():
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        L.hmdec_pictures_histogram.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.HistogramDesc), C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
         L.hmdec_picture_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.hmdec_internal_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.POINTER(BlockValue))]
@@ -291,6 +293,12 @@ class Picture:
         out = metrics_batch([self], [None if t is None else t[None] for t in ref], components, ssim, crop)
         return {k: {f: t[0] for f, t in v.items()} for k, v in out.items()}
 
+    def histogram(self, channels=("y", "cb", "cr"), bins=None, crop="conformance", matrix=None, full_range=None, rgb_bit_depth=0,
+                  histogram=True):
+        """histogram_batch of this picture alone: the histograms and fields without the batch dimension"""
+        out = histogram_batch([self], channels, bins, crop, matrix, full_range, rgb_bit_depth, histogram)
+        return {k: {f: t[0] for f, t in v.items()} for k, v in out.items()}
+
 
 def _form_is_dense(form):
     from . import motion
@@ -368,6 +376,32 @@ def metrics_batch(pictures, ref, components=(0, 1, 2), ssim=True, crop=None):
             why = lib().hmdec_last_error(first.ctx).decode() if r == abi.HMGPU_EUNSUPPORTED else ""
             raise HmgpuError(r, "hmdec_pictures_metrics" + (": " + why if why else ""))
     return metrics.metrics(call, seq, dev, len(pictures), None, ref, components, ssim, crop)
+
+
+def histogram_batch(pictures, channels=("y", "cb", "cr"), bins=None, crop="conformance", matrix=None, full_range=None, rgb_bit_depth=0,
+                    histogram=True):
+    """What up to 16 pictures a decoder has put out with device output on (fetched since the last push, one sequence, one GPU)
+    contain (hmdec_pictures_histogram): the result dict of libhm_amd.histogram -- per channel "y", "cb", "cr", "maxrgb" the histogram
+    and samples, sum, sum_sq, min, max -- written on torch.cuda.current_stream().  crop: "conformance", None (the whole coded picture)
+    or (left, right, top, bottom); matrix / full_range of "maxrgb": None = from the VUI, as in the RGB exports."""
+    from . import HmgpuError, export
+    from . import histogram as hg
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("histogram_batch: no pictures")
+    first, seq, crop = _prologue(pictures, "histogram_batch", crop, lambda: (0, 0, 0, 0))
+    col = first.colour()
+    matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
+
+    def call(desc, ptrs, strides, rec, rs, st):
+        r = lib().hmdec_pictures_histogram(first.ctx, len(pictures), _handles(pictures), C.byref(desc), *hg.c_args(ptrs, strides), abi.addr(rec), rs,
+                                           1, abi.addr(st))
+        if r != 0:
+            why = lib().hmdec_last_error(first.ctx).decode() if r == abi.HMGPU_EINVAL else ""
+            raise HmgpuError(r, "hmdec_pictures_histogram" + (": " + why if why.startswith("hmdec_pictures_histogram") else ""))
+    # (a decoder without device output: the library's own refusal, with its message, rather than "not on a device")
+    dev = first.device if first.device >= 0 else 0
+    return hg.histogram(call, seq, dev, len(pictures), channels, bins, crop, matrix, full_range, rgb_bit_depth, histogram)
 
 
 def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, windows=None, flip=None, dtype=None, out=None, crop=None,
