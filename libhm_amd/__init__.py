@@ -341,6 +341,26 @@ def export_warp_plan(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, 
     return plan
 
 
+def export_stages_plan(seq, desc, stages, n=None):
+    """what an export of `stages` (export.Stages) writes per slot: the plan function of the narrowest entry that carries them, as
+    Context.export_stages_into chooses the export.  stages.lut: an abi.ColourLutDesc, or a colour LUT object, which knows its own; a
+    raw handle describes nothing and adds no rule.  n: the pictures of a warp (export_warp_status)"""
+    s, ld = stages, stages.lut
+    if ld is not None and not isinstance(ld, abi.ColourLutDesc):
+        ld = abi.make_colour_lut_desc(ld.depth, ld.size, ld.has_shaper) if hasattr(ld, "has_shaper") else None
+    if s.warp is not None:
+        return export_warp_plan(seq, desc, s.tensor, s.windows, s.pixel, ld, s.chroma, s.warp[0], s.warp[1], n)
+    if s.chroma is not None:
+        return export_chroma_plan(seq, desc, s.scale, s.tensor, s.windows, s.pixel, ld, s.chroma)
+    if ld is not None:
+        return export_colour_plan(seq, desc, s.scale, s.tensor, s.windows, s.pixel, ld)
+    if s.pixel is not None:
+        return export_pixels_plan(seq, desc, s.scale, s.tensor, s.windows, s.pixel)
+    if s.windows is not None:
+        return export_windows_plan(seq, desc, s.scale, s.tensor, s.windows)
+    return export_tensor_plan(seq, desc, s.scale, s.tensor)
+
+
 def colour_lut_arrays(lattice, shaper, depth):
     """(abi.ColourLutDesc, shaper, lattice) of a LUT as the C calls take it: lattice None or [L, L, L, 3] (b, g, r, channel), shaper
     None or [3, 2^depth], both converted to contiguous uint16 (values outside 0 .. 65535 raise)"""
@@ -686,6 +706,28 @@ class Context:
                                                             abi.ref(tensor), abi.window_array(windows), abi.ptr_array(ptrs),
                                                             abi.i64_array(pitches), abi.i64_array(bstrides))
 
+    def export_stages_into(self, pics, desc, stages, ptrs, pitches, bstrides, on_stream=0, stream=0):
+        """the export of `stages` (export.Stages) into device memory the caller owns, through the narrowest hmgpu_pictures_export*
+        entry that carries them: warp, else chroma, else colour, else pixels (ptrs[0] / pitches[0] / bstrides[0] the one destination),
+        else windows or the plain batch -- the only ones that take a YUV layout.  bstrides None: one picture, through
+        hmgpu_picture_export(_scaled) where it has integer elements and no further stage, else as a batch of one"""
+        s = stages
+        if bstrides is None:
+            if s[1:] == (None,) * 6:
+                return self.export_into(pics[0], desc, ptrs, pitches, on_stream, stream, s.scale)
+            from . import export
+            bstrides = export.stage_extents(export_stages_plan(self.seq, desc, s.shape_only(), 1), pitches)
+        if s.warp is not None:
+            return self.export_warp_into(pics, desc, s.warp, ptrs, pitches, bstrides, on_stream, stream, s.tensor, s.windows, s.pixel, s.lut, s.chroma)
+        if s.chroma is not None:
+            return self.export_chroma_into(pics, desc, s.chroma, ptrs, pitches, bstrides, on_stream, stream, s.scale, s.tensor, s.windows, s.pixel,
+                                           s.lut)
+        if s.lut is not None:
+            return self.export_colour_into(pics, desc, s.lut, ptrs, pitches, bstrides, on_stream, stream, s.scale, s.tensor, s.windows, s.pixel)
+        if s.pixel is not None:
+            return self.export_pixels_into(pics, desc, s.pixel, ptrs[0], pitches[0], bstrides[0], on_stream, stream, s.scale, s.tensor, s.windows)
+        return self.export_batch_into(pics, desc, ptrs, pitches, bstrides, on_stream, stream, s.scale, s.tensor, s.windows)
+
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
                lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None):
@@ -701,36 +743,12 @@ class Context:
         with fill=(r, g, b) (hmgpu_pictures_export_warp)"""
         from . import export
         os_ = 1 if on_stream else 0
-        chr_ = abi.chroma_stage(chroma, chroma_loc)
-        wrp = abi.warp_stage(export.one_map(warp), size, filter, border, fill, 1)
-
-        def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
-            if wrp is not None:
-                plan = export_warp_plan(self.seq, desc, tensor, None, None, None, None, wrp[0], wrp[1])
-                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-                return self.export_warp_into([pic], desc, wrp, ptrs, pitches, extent, os_, st, tensor, None, None, lut, chr_)
-            if chr_ is not None:
-                plan = export_tensor_plan(self.seq, desc, sc, tensor)
-                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-                return self.export_chroma_into([pic], desc, chr_, ptrs, pitches, extent, os_, st, sc, tensor, None, None, lut)
-            if lut is not None:
-                plan = export_tensor_plan(self.seq, desc, sc, tensor)
-                extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-                return self.export_colour_into([pic], desc, lut, ptrs, pitches, extent, os_, st, sc, tensor)
-            if tensor is None:
-                return self.export_into(pic, desc, ptrs, pitches, 1 if on_stream else 0, st, sc)
-            plan = export_tensor_plan(self.seq, desc, sc, tensor)
-            extent = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-            self.export_batch_into([pic], desc, ptrs, pitches, extent, 1 if on_stream else 0, st, sc, tensor)
-        return export.export_tensors(call, self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size,
-                                     filter, out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha, warp=wrp,
-                                     pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
-                                     self.export_warp_into([pic], desc, wrp, [ptr], [pitch], [bstride], os_, st, tensor, None, px, lut, chr_)
-                                     if wrp is not None else
-                                     self.export_chroma_into([pic], desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px, lut)
-                                     if chr_ is not None else
-                                     self.export_pixels_into([pic], desc, px, ptr, pitch, bstride, os_, st, sc, tensor) if lut is None else
-                                     self.export_colour_into([pic], desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, None, px))
+        return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                     self.export_stages_into([pic], desc, stages, ptrs, pitches, bstrides, os_, st),
+                                     self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
+                                     out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha, lut=lut,
+                                     chroma=abi.chroma_stage(chroma, chroma_loc),
+                                     warp=abi.warp_stage(export.one_map(warp), size, filter, border, fill, 1))
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
@@ -764,25 +782,12 @@ class Context:
         pics = list(pics)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         os_ = 1 if on_stream else 0
-        chr_ = abi.chroma_stage(chroma, chroma_loc)
-        wrp = abi.warp_stage(warp, size, filter, border, fill, len(pics))
-        return export.export_tensors(lambda desc, sc, tensor, ptrs, pitches, bstrides, st:
-                                     self.export_warp_into(pics, desc, wrp, ptrs, pitches, bstrides, os_, st, tensor, win, None, lut, chr_)
-                                     if wrp is not None else
-                                     self.export_chroma_into(pics, desc, chr_, ptrs, pitches, bstrides, os_, st, sc, tensor, win, None, lut)
-                                     if chr_ is not None else
-                                     self.export_batch_into(pics, desc, ptrs, pitches, bstrides, os_, st, sc, tensor, win) if lut is None else
-                                     self.export_colour_into(pics, desc, lut, ptrs, pitches, bstrides, os_, st, sc, tensor, win),
+        return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                     self.export_stages_into(pics, desc, stages, ptrs, pitches, bstrides, os_, st),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
-                                     warp=wrp,
-                                     pixel_call=lambda desc, sc, tensor, px, ptr, pitch, bstride, st:
-                                     self.export_warp_into(pics, desc, wrp, [ptr], [pitch], [bstride], os_, st, tensor, win, px, lut, chr_)
-                                     if wrp is not None else
-                                     self.export_chroma_into(pics, desc, chr_, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px, lut)
-                                     if chr_ is not None else
-                                     self.export_pixels_into(pics, desc, px, ptr, pitch, bstride, os_, st, sc, tensor, win) if lut is None else
-                                     self.export_colour_into(pics, desc, lut, [ptr], [pitch], [bstride], os_, st, sc, tensor, win, px))
+                                     lut=lut, chroma=abi.chroma_stage(chroma, chroma_loc),
+                                     warp=abi.warp_stage(warp, size, filter, border, fill, len(pics)))
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

@@ -1,6 +1,7 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
-// slots, window tables, colour LUTs, the chroma stage's rules and weights, export_resolve under export_impl and the picture destination checks, the warp export's rules and its
-// per-call maps, strided_dst_ok under the motion / block
+// slots, window tables, colour LUTs, the rules and weights of the chroma stage and the rules of the warp; ExportReq, the stages of one
+// picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
+// destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block
 // and residual exports and the reference planes of the picture metrics, the picture histograms (k_export.hip, k_export_px.hip,
 // k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip, k_histogram.hip).
 #include "hmgpu_host.h"
@@ -355,11 +356,6 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
 
 }  // namespace
 
-hmgpu_status hmgpu_export_scaled_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          hmgpu_export_plan* out) {
-  return scaled_plan(seq, d, sc, out, nullptr);
-}
-
 hmgpu_status hmgpu_export_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, int32_t chroma,
                                      int32_t axis, int32_t max_taps, int32_t* first, int32_t* count, int16_t* weights) {
   if (!first || !count || !weights || (chroma != 0 && chroma != 1) || (axis != 0 && axis != 1)) return HMGPU_EINVAL;
@@ -633,12 +629,6 @@ static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_
   return HMGPU_OK;
 }
 
-hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, hmgpu_export_plan* out) {
-  int elem = 0;
-  return tensor_plan(seq, d, sc, t, out, nullptr, &elem);
-}
-
 // hmgpu_pictures_export_windows: every window validated as the single call validates its crop, in order (the first failure is the
 // call's status).  differ: the windows are not all equal; shapes (scaled): one per window then, else one for all.
 static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
@@ -670,13 +660,6 @@ static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export
   }
   call_tabs_keep(tabs);
   return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                           const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[], hmgpu_export_plan* out) {
-  int elem = 0;
-  bool differ = false;
-  return windows_plan(seq, d, sc, t, n, windows, out, nullptr, &elem, &differ);
 }
 
 // every plane's destination, all n pictures of it, inside one allocation of the context's device (bstride null: one picture); vec is
@@ -729,62 +712,6 @@ static hmgpu_status pixel_plan(const hmgpu_seq_params* seq, const hmgpu_export_d
   p.row_bytes[0] = p.width[0] * C * elem_size(elem);
   for (int k = 1; k < 3; k++) p.width[k] = p.height[k] = p.row_bytes[k] = 0;
   *plan = p;
-  return HMGPU_OK;
-}
-
-// the plan of a packed call: the planar call's own (windows_plan / tensor_plan), then pixel_plan
-hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
-                                          const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
-  if (!seq || !d || !px || !out) return HMGPU_EINVAL;
-  int elem = 0;
-  bool differ = false;
-  PxOrder po;
-  const hmgpu_status st = win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
-  return st != HMGPU_OK ? st : pixel_plan(seq, d, elem, px, out, &po);
-}
-
-// what every picture export resolves its arguments to before anything is enqueued, and what the destination checks stop at: the
-// plan, the element, the shapes of a scaled call, the pixel order, and the destination checked against the plan
-namespace {
-struct ExportCall {
-  hmgpu_export_plan plan;
-  hmgpu_export_desc d;                               // the descriptor; windows that are all equal: with that window as its crop
-  int elem = 0, nch = 0;                             // nch: elements per packed pixel (0: planes)
-  bool differ = false;                               // the windows are not all equal
-  uint32_t flip = 0;
-  ScaleShape s;                                      // scaled: the output size and the depths (those of every window)
-  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
-  PxOrder po;
-  bool vec = true;
-  int64_t bs[3] = {0, 0, 0};
-};
-}  // namespace
-
-// bstride null: one picture, no batch stride to check; win null: desc->crop for every picture, no mirror; px: packed pixels, dst[0]
-// the one destination; shapes: the export itself asks (a check needs none)
-static hmgpu_status export_resolve(hmgpu_ctx* c, int n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
-                                   const hmgpu_export_window* win, const hmgpu_export_pixel* px, void* const dst[3],
-                                   const int64_t pitch_bytes[3], const int64_t* bstride, bool shapes, ExportCall* r) {
-  if (win) {
-    const hmgpu_status st = windows_plan(&c->seq, d, sc, t, n, win, &r->plan, shapes ? &r->shapes : nullptr, &r->elem, &r->differ);
-    if (st != HMGPU_OK) return st;
-    for (int i = 0; i < n; i++) r->flip |= (uint32_t)(win[i].flip & 1) << i;
-    if (sc && shapes) r->s = r->shapes[0];
-  } else {
-    const hmgpu_status st = tensor_plan(&c->seq, d, sc, t, &r->plan, shapes ? &r->s : nullptr, &r->elem);
-    if (st != HMGPU_OK) return st;
-  }
-  r->d = *d;
-  if (win && !r->differ) memcpy(r->d.crop, win[0].crop, sizeof(r->d.crop));
-  if (px) {
-    const hmgpu_status st = pixel_plan(&c->seq, d, r->elem, px, &r->plan, &r->po);
-    if (st != HMGPU_OK) return st;
-    r->nch = px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
-  }
-  { const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs); if (st != HMGPU_OK) return st; }
-  // packed pixels: a full group is a run of dwords where the destination is dword aligned; the loads have their own condition
-  if (px) r->po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || r->bs[0] % 4 == 0);
   return HMGPU_OK;
 }
 
@@ -865,38 +792,6 @@ static hmgpu_status colour_rules(const hmgpu_seq_params* seq, const hmgpu_export
   out_depths(seq, d, ob);
   return lut_depth == ob[0] ? HMGPU_OK : HMGPU_EINVAL;
 }
-static hmgpu_status colour_resolve(hmgpu_ctx* c, const hmgpu_export_desc* d, hmgpu_lut lut, hmgpu_ctx::ColourSlot** cs) {
-  if (d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
-  *cs = colour_find(c, lut);
-  return *cs ? colour_rules(&c->seq, d, (*cs)->lut.depth) : HMGPU_EINVAL;
-}
-
-hmgpu_status hmgpu_export_colour_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
-                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, hmgpu_export_plan* out) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  int elem = 0;
-  bool differ = false;
-  hmgpu_status st = px ? hmgpu_export_pixels_plan_for(seq, d, sc, t, n, win, px, out)
-                  : win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
-  if (st != HMGPU_OK) return st;
-  if (d->layout != HMGPU_EXPORT_RGB) st = HMGPU_EINVAL;
-  else if (!colour_desc_ok(ld)) st = HMGPU_EINVAL;
-  else st = colour_rules(seq, d, ld->depth);
-  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
-                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, void* const dst[3],
-                                                   const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  ExportCall r;
-  { const hmgpu_status st = export_resolve(c, n, d, sc, t, windows, px, dst, pitch_bytes, batch_stride_bytes, false, &r); if (st != HMGPU_OK) return st; }
-  hmgpu_ctx::ColourSlot* cs = nullptr;
-  return colour_resolve(c, d, lut, &cs);
-}
 
 // ------------------------------------------------------------------------------------------------ chroma stage (chroma_core.h)
 // the rules a chroma export adds behind the validation of the matching call, in the order include/hmgpu.h "chroma export" gives
@@ -919,61 +814,6 @@ static void chroma_site(const hmgpu_seq_params& seq, const hmgpu_export_chroma& 
   memcpy(s->vy, vy[f420 ? ch.loc >> 1 : 3], sizeof(s->vy));
   s->wc = seq.width >> 1;
   s->hc = seq.height >> (f420 ? 1 : 0);
-}
-
-hmgpu_status hmgpu_export_chroma_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
-                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, const hmgpu_export_chroma* ch,
-                                          hmgpu_export_plan* out) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  int elem = 0;
-  bool differ = false;
-  hmgpu_status st = ld ? hmgpu_export_colour_plan_for(seq, d, sc, t, n, win, px, ld, out)
-                  : px ? hmgpu_export_pixels_plan_for(seq, d, sc, t, n, win, px, out)
-                  : win ? windows_plan(seq, d, sc, t, n, win, out, nullptr, &elem, &differ) : tensor_plan(seq, d, sc, t, out, nullptr, &elem);
-  if (st != HMGPU_OK) return st;
-  st = chroma_rules(d, ch);
-  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-hmgpu_status hmgpu_export_chroma_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
-                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, const hmgpu_export_chroma* ch,
-                                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  ExportCall r;
-  { const hmgpu_status st = export_resolve(c, n, d, sc, t, windows, px, dst, pitch_bytes, batch_stride_bytes, false, &r); if (st != HMGPU_OK) return st; }
-  hmgpu_ctx::ColourSlot* cs = nullptr;
-  if (lut) { const hmgpu_status st = colour_resolve(c, d, lut, &cs); if (st != HMGPU_OK) return st; }
-  return chroma_rules(d, ch);
-}
-
-hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
-                                            const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  ExportCall r;
-  return export_resolve(c, n, d, sc, t, nullptr, nullptr, dst, pitch_bytes, batch_stride_bytes, false, &r);
-}
-
-hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
-                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
-  // (!windows: export_resolve would take null windows for a call without windows and check the wrong plan)
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !windows || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  ExportCall r;
-  return export_resolve(c, n, d, sc, t, windows, nullptr, dst, pitch_bytes, batch_stride_bytes, false, &r);
-}
-
-hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
-                                                   const hmgpu_export_pixel* px, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !px) return HMGPU_EINVAL;
-  void* const dst3[3] = {dst, nullptr, nullptr};
-  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
-  ExportCall r;
-  return export_resolve(c, n, d, sc, t, windows, px, dst3, pitch3, bstride3, false, &r);
 }
 
 // ------------------------------------------------------------------------------------------------ affine warp export (k_export_warp.hip)
@@ -999,74 +839,233 @@ static hmgpu_status warp_rules(const hmgpu_seq_params* seq, const hmgpu_export_d
   return HMGPU_OK;
 }
 
-// the plan of the matching planar or packed call with scale null -- windows of any size -- and, once `wp` names a size, every plane
-// of the RGB layout width x height
-static hmgpu_status warp_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int n,
-                              const hmgpu_export_window* win, const hmgpu_export_pixel* px, const hmgpu_export_warp* wp,
-                              hmgpu_export_plan* out, int* elem, PxOrder* po, uint32_t* flip) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  bool differ = false;
-  if (win) {
-    const hmgpu_status st = windows_plan(seq, d, nullptr, t, n, win, out, nullptr, elem, &differ, true);
+// ------------------------------------------------------------------------------------------------ the request record: one plan, one resolver
+namespace {
+// The stages of one picture export, as every layer under the public entries takes them; a stage the call does not have is null
+// (lut: 0).  The flags are everything the entries differ in: an entry fills the record and has no code of its own behind that.
+struct ExportReq {
+  ExportReq(const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t, const hmgpu_export_window* win = nullptr,
+            const hmgpu_export_pixel* px = nullptr) : d(d), sc(sc), t(t), win(win), px(px) {}
+  const hmgpu_export_desc* d;
+  const hmgpu_export_scale* sc;
+  const hmgpu_export_tensor* t;
+  const hmgpu_export_window* win;                    // null: d->crop for every picture, no mirror
+  const hmgpu_export_pixel* px;                      // packed pixels: dst[0] the one destination
+  hmgpu_lut lut = 0;                                 // the LUT of a call or check ...
+  const hmgpu_colour_lut_desc* ld = nullptr;         // ... and of a plan, which has no context to look a handle up in
+  const hmgpu_export_chroma* chroma = nullptr;
+  const hmgpu_export_warp* wp = nullptr;
+  const hmgpu_warp_map* maps = nullptr;
+  bool need_sc = false, need_win = false, need_px = false;   // the entry is refused without that stage
+  bool colour_stage = false;                         // the colour rules apply: the colour entries always, the wider ones with a LUT
+  bool chroma_stage = false;                         // the chroma rules apply: the chroma entries always, the warp ones with a descriptor
+  bool warp = false;                                 // the warp entries: n checked without windows too, windows of any size, every plane
+                                                     // wp's size, the destination checked once wp names one, the warp rules
+  bool single = false;                               // hmgpu_picture_export(_scaled): no batch stride
+};
+
+// what every picture export resolves its arguments to before anything is enqueued, and what the destination checks stop at: the
+// plan, the element, the shapes of a scaled call, the pixel order, the destination checked against the plan, the LUT's slot
+struct ExportCall {
+  hmgpu_export_plan plan;
+  hmgpu_export_desc d;                               // the descriptor; windows that are all equal: with that window as its crop
+  int elem = 0, nch = 0;                             // nch: elements per packed pixel (0: planes)
+  bool differ = false;                               // the windows are not all equal
+  uint32_t flip = 0;
+  ScaleShape s;                                      // scaled: the output size and the depths (those of every window)
+  std::vector<ScaleShape> shapes;                    // windows that differ, scaled: one per picture
+  PxOrder po;
+  bool vec = true;
+  int64_t bs[3] = {0, 0, 0};
+  hmgpu_ctx::ColourSlot* cs = nullptr;               // the colour stage (null: none)
+};
+
+// the stages behind the pixels of the entries in which each of them is optional (the plans: ld, the calls and checks: lut)
+void optional_stages(ExportReq* q, hmgpu_lut lut, const hmgpu_colour_lut_desc* ld, const hmgpu_export_chroma* ch, bool chroma_entry) {
+  q->lut = lut; q->ld = ld; q->chroma = ch;
+  q->colour_stage = lut || ld;
+  q->chroma_stage = chroma_entry || ch;
+}
+}  // namespace
+
+// Rules 1 and 2 of the order include/hmgpu.h documents: the base plan -- per window in order (windows_plan), else of the one crop
+// (tensor_plan) -- then pixel_plan.  shapes: the export itself asks for the scale shapes (a plan or a check needs none).
+static hmgpu_status export_plan(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
+  if (!seq || !q.d || !out || (q.need_sc && !q.sc) || (q.need_px && !q.px)) return HMGPU_EINVAL;
+  if (q.win || q.need_win) {
+    const hmgpu_status st = windows_plan(seq, q.d, q.sc, q.t, n, q.win, out, shapes ? &r->shapes : nullptr, &r->elem, &r->differ, q.warp);
     if (st != HMGPU_OK) return st;
-    for (int i = 0; i < n; i++) *flip |= (uint32_t)(win[i].flip & 1) << i;
+    for (int i = 0; i < n; i++) r->flip |= (uint32_t)(q.win[i].flip & 1) << i;
+    if (q.sc && shapes) r->s = r->shapes[0];
   } else {
     memset(out, 0, sizeof(*out));
-    if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-    const hmgpu_status st = tensor_plan(seq, d, nullptr, t, out, nullptr, elem);
+    if (q.warp && (n < 1 || n > HMGPU_EXPORT_MAX_BATCH)) return HMGPU_EINVAL;
+    const hmgpu_status st = tensor_plan(seq, q.d, q.sc, q.t, out, shapes ? &r->s : nullptr, &r->elem);
     if (st != HMGPU_OK) return st;
   }
-  if (warp_sized(wp) && d->layout == HMGPU_EXPORT_RGB)
+  if (q.warp && warp_sized(q.wp) && q.d->layout == HMGPU_EXPORT_RGB)
     for (int k = 0; k < out->planes; k++) {
-      out->row_bytes[k] = out->row_bytes[k] / out->width[k] * wp->width;
-      out->width[k] = wp->width; out->height[k] = wp->height;
+      out->row_bytes[k] = out->row_bytes[k] / out->width[k] * q.wp->width;
+      out->width[k] = q.wp->width; out->height[k] = q.wp->height;
     }
-  return px ? pixel_plan(seq, d, *elem, px, out, po) : HMGPU_OK;
+  if (!q.px) return HMGPU_OK;
+  r->nch = q.px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
+  return pixel_plan(seq, q.d, r->elem, q.px, out, &r->po);
+}
+
+// Rules 4 to 6, behind the plan and (a call or check) the destination: colour -- the RGB layout, the LUT found, its depth --, then
+// chroma, then warp.  c null: a plan function, which knows the LUT by its description.
+static hmgpu_status stage_rules(hmgpu_ctx* c, const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_ctx::ColourSlot** cs) {
+  if (q.colour_stage) {
+    if (q.d->layout != HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+    if (c) *cs = colour_find(c, q.lut);
+    if (c ? !*cs : !colour_desc_ok(q.ld)) return HMGPU_EINVAL;
+    const hmgpu_status st = colour_rules(seq, q.d, c ? (*cs)->lut.depth : q.ld->depth);
+    if (st != HMGPU_OK) return st;
+  }
+  if (q.chroma_stage) { const hmgpu_status st = chroma_rules(q.d, q.chroma); if (st != HMGPU_OK) return st; }
+  return q.warp ? warp_rules(seq, q.d, n, q.wp, q.maps) : HMGPU_OK;
+}
+
+// every plan function: export_plan, then the stage rules; a refused plan is all zero
+static hmgpu_status plan_for(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out) {
+  ExportCall r;
+  hmgpu_status st = export_plan(seq, n, q, out, &r, false);
+  if (st == HMGPU_OK && (st = stage_rules(nullptr, seq, n, q, nullptr)) != HMGPU_OK) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// every export and destination check: the plan, the destination against it (rule 3), the stage rules.  bstride null: one picture,
+// no batch stride to check
+static hmgpu_status export_resolve(hmgpu_ctx* c, int n, const ExportReq& q, void* const dst[3], const int64_t pitch_bytes[3],
+                                   const int64_t* bstride, bool shapes, ExportCall* r) {
+  { const hmgpu_status st = export_plan(&c->seq, n, q, &r->plan, r, shapes); if (st != HMGPU_OK) return st; }
+  r->d = *q.d;
+  if (q.win && !r->differ) memcpy(r->d.crop, q.win[0].crop, sizeof(r->d.crop));
+  if (!q.warp || warp_sized(q.wp)) {                  // (a warp without a size: refused below, by the warp rules at the latest)
+    const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs);
+    if (st != HMGPU_OK) return st;
+  }
+  // packed pixels: a full group is a run of dwords where the destination is dword aligned; the loads have their own condition
+  if (q.px) r->po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || r->bs[0] % 4 == 0);
+  return stage_rules(c, &c->seq, n, q, &r->cs);
+}
+
+static hmgpu_status destination_check(hmgpu_ctx* c, int n, const ExportReq& q, void* const dst[3], const int64_t pitch_bytes[3],
+                                      const int64_t batch_stride_bytes[3]) {
+  // (need_win: export_resolve would take null windows for a call without windows and check the wrong plan)
+  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !q.d || (q.need_win && !q.win) || (q.need_px && !q.px) || !dst || !pitch_bytes ||
+      !batch_stride_bytes) return HMGPU_EINVAL;
+  ExportCall r;
+  return export_resolve(c, n, q, dst, pitch_bytes, batch_stride_bytes, false, &r);
+}
+
+hmgpu_status hmgpu_export_scaled_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          hmgpu_export_plan* out) {
+  ExportReq q(d, sc, nullptr);
+  q.need_sc = true;
+  return plan_for(seq, 1, q, out);
+}
+
+hmgpu_status hmgpu_export_tensor_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, hmgpu_export_plan* out) {
+  return plan_for(seq, 1, ExportReq(d, sc, t), out);
+}
+
+hmgpu_status hmgpu_export_windows_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window windows[], hmgpu_export_plan* out) {
+  ExportReq q(d, sc, t, windows);
+  q.need_win = true;
+  return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_pixels_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, hmgpu_export_plan* out) {
+  ExportReq q(d, sc, t, win, px);
+  q.need_px = true;
+  return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_colour_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, hmgpu_export_plan* out) {
+  ExportReq q(d, sc, t, win, px);
+  q.ld = ld;
+  q.colour_stage = true;
+  return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_chroma_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld, const hmgpu_export_chroma* ch,
+                                          hmgpu_export_plan* out) {
+  ExportReq q(d, sc, t, win, px);
+  optional_stages(&q, 0, ld, ch, true);
+  return plan_for(seq, n, q, out);
 }
 
 hmgpu_status hmgpu_export_warp_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int32_t n,
                                         const hmgpu_export_window win[], const hmgpu_export_pixel* px, const hmgpu_colour_lut_desc* ld,
                                         const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp, const hmgpu_warp_map maps[],
                                         hmgpu_export_plan* out) {
-  int elem = 0;
-  uint32_t flip = 0;
-  PxOrder po;
-  hmgpu_status st = warp_plan(seq, d, t, n, win, px, wp, out, &elem, &po, &flip);
-  if (st != HMGPU_OK) return st;
-  if (ld) st = d->layout != HMGPU_EXPORT_RGB || !colour_desc_ok(ld) ? HMGPU_EINVAL : colour_rules(seq, d, ld->depth);
-  if (st == HMGPU_OK && ch) st = chroma_rules(d, ch);
-  if (st == HMGPU_OK) st = warp_rules(seq, d, n, wp, maps);
-  if (st != HMGPU_OK) memset(out, 0, sizeof(*out));
-  return st;
+  ExportReq q(d, nullptr, t, win, px);
+  optional_stages(&q, 0, ld, ch, false);
+  q.wp = wp; q.maps = maps; q.warp = true;
+  return plan_for(seq, n, q, out);
 }
 
-// what hmgpu_pictures_export_warp and its destination check resolve their arguments to: export_resolve's part for a call without
-// scale, the destination against the warp's plan, then the colour, chroma and warp rules
-static hmgpu_status warp_resolve(hmgpu_ctx* c, int n, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, const hmgpu_export_window* win,
-                                 const hmgpu_export_pixel* px, hmgpu_lut lut, const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp,
-                                 const hmgpu_warp_map* maps, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
-                                 ExportCall* r, hmgpu_ctx::ColourSlot** cs) {
-  { const hmgpu_status st = warp_plan(&c->seq, d, t, n, win, px, wp, &r->plan, &r->elem, &r->po, &r->flip); if (st != HMGPU_OK) return st; }
-  r->d = *d;
-  if (px) r->nch = px->order <= HMGPU_PIXEL_BGR ? 3 : 4;
-  if (warp_sized(wp)) {                               // (no size: refused below, by the warp rules at the latest)
-    const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs);
-    if (st != HMGPU_OK) return st;
-  }
-  if (px) r->po.vst = (uintptr_t)dst[0] % 4 == 0 && pitch_bytes[0] % 4 == 0 && (n == 1 || r->bs[0] % 4 == 0);
-  if (lut) { const hmgpu_status st = colour_resolve(c, d, lut, cs); if (st != HMGPU_OK) return st; }
-  if (ch) { const hmgpu_status st = chroma_rules(d, ch); if (st != HMGPU_OK) return st; }
-  return warp_rules(&c->seq, d, n, wp, maps);
+hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                            const int64_t batch_stride_bytes[3]) {
+  return destination_check(c, n, ExportReq(d, sc, t), dst, pitch_bytes, batch_stride_bytes);
+}
+
+hmgpu_status hmgpu_export_windows_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  ExportReq q(d, sc, t, windows);
+  q.need_win = true;
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
+}
+
+hmgpu_status hmgpu_export_pixels_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes) {
+  void* const dst3[3] = {dst, nullptr, nullptr};
+  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
+  ExportReq q(d, sc, t, windows, px);
+  q.need_px = true;
+  return destination_check(c, n, q, dst3, pitch3, bstride3);
+}
+
+hmgpu_status hmgpu_export_colour_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, void* const dst[3],
+                                                   const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  ExportReq q(d, sc, t, windows, px);
+  q.lut = lut;
+  q.colour_stage = true;
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
+}
+
+hmgpu_status hmgpu_export_chroma_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_pixel* px, hmgpu_lut lut, const hmgpu_export_chroma* ch,
+                                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  ExportReq q(d, sc, t, windows, px);
+  optional_stages(&q, lut, nullptr, ch, true);
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
 }
 
 hmgpu_status hmgpu_export_warp_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_tensor* t,
                                                  const hmgpu_export_window windows[], const hmgpu_export_pixel* px, hmgpu_lut lut,
                                                  const hmgpu_export_chroma* ch, const hmgpu_export_warp* wp, const hmgpu_warp_map maps[],
                                                  void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
-  if (!c || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !d || !dst || !pitch_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  ExportCall r;
-  hmgpu_ctx::ColourSlot* cs = nullptr;
-  return warp_resolve(c, n, d, t, windows, px, lut, ch, wp, maps, dst, pitch_bytes, batch_stride_bytes, &r, &cs);
+  ExportReq q(d, nullptr, t, windows, px);
+  optional_stages(&q, lut, nullptr, ch, false);
+  q.wp = wp; q.maps = maps; q.warp = true;
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
 }
 
 }  // extern "C"
@@ -1121,66 +1120,44 @@ static hmgpu_status strided_dst_ok(const hmgpu_ctx* c, const Plan& plan, int slo
 
 extern "C" {
 
-// every export: n pictures, unscaled (sc null) or scaled, unsigned (t null) or float elements; the arguments as export_resolve takes
-// them.  One launch, the stream ordering once.
-static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* sc,
-                                const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3], const int64_t* bstride,
-                                int32_t on_stream, void* stream, const hmgpu_export_window* win = nullptr,
-                                const hmgpu_export_pixel* px = nullptr, const hmgpu_lut* lut = nullptr, bool chroma_call = false,
-                                const hmgpu_export_chroma* chroma = nullptr) {
-  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-  ExportCall r;
-  { const hmgpu_status st = export_resolve(c, n, desc, sc, t, win, px, dst, pitch_bytes, bstride, true, &r); if (st != HMGPU_OK) return st; }
+// The three argument builders of export_impl -- unscaled, scaled, warp -- each from the resolved call to its launch on hs.  site:
+// the chroma stage's weights (null: the instances without it); *tables: the table buffer the launch reads, for export_impl to mark.
+static void launch_unscaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const ExportReq& q, const ExportCall& r, ChromaSite* site,
+                            void* const dst[3], const int64_t pitch_bytes[3], hipStream_t hs) {
   const hmgpu_export_desc* d = &r.d;
-  hmgpu_ctx::ColourSlot* cs = nullptr;                 // the colour stage (hmgpu_pictures_export_colour): its rules come last
-  if (lut) { const hmgpu_status st = colour_resolve(c, desc, *lut, &cs); if (st != HMGPU_OK) return st; }
-  // the chroma stage (hmgpu_pictures_export_chroma): its rules behind those; 4:4:4 and 4:0:0, where it is the identity, and
-  // HMGPU_CHROMA_REPLICATE run the instances without it
-  ChromaSite site;
-  bool linear = false;
-  if (chroma_call) {
-    const hmgpu_status st = chroma_rules(desc, chroma);
-    if (st != HMGPU_OK) return st;
-    linear = chroma->filter == HMGPU_CHROMA_LINEAR && (c->seq.chroma_format == 1 || c->seq.chroma_format == 2);
-    if (linear) chroma_site(c->seq, *chroma, &site);
+  ExportArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n; i++) {
+    const Picture& p = c->pics[pics[i]];
+    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+    const int x0 = r.differ ? q.win[i].crop[0] : d->crop[0], y0 = r.differ ? q.win[i].crop[2] : d->crop[2];
+    a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
+    a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
+    if ((r.vec || q.px) && (x0 & 3) == 0) a.vec |= 1u << i;               // (a batch may mix aligned and unaligned left edges)
+    if (site) { site->x0[i] = (int16_t)(x0 >> c->csx); site->y0[i] = (int16_t)(y0 >> c->csy); }
   }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
+  a.n = n; a.layout = d->layout; a.elem = r.elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
+  a.w = r.plan.width[0]; a.h = r.plan.height[0];
+  a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
+  export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
+  if (site) {
+    if (q.px) launch_export_px_chroma(a, r.po, *site, r.cs ? &r.cs->lut : nullptr, r.nch, hs);
+    else launch_export_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, hs);
+  } else if (r.cs) {
+    if (q.px) launch_export_px_colour(a, r.po, r.cs->lut, r.nch, hs);
+    else launch_export_colour(a, r.cs->lut, hs);
+  } else if (q.px) {
+    launch_export_px(a, r.po, r.nch, hs);
+  } else {
+    launch_export(a, hs);
+  }
+}
+
+static hmgpu_status launch_scaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const ExportReq& q, const ExportCall& r, const ChromaSite* site,
+                                  void* const dst[3], const int64_t pitch_bytes[3], hipStream_t hs, hmgpu_ctx::TableBuf** tables) {
+  const hmgpu_export_desc* d = &r.d;
   const bool rgb = d->layout == HMGPU_EXPORT_RGB;
-  if (!sc) {
-    ExportArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < n; i++) {
-      const Picture& p = c->pics[pics[i]];
-      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-      const int x0 = r.differ ? win[i].crop[0] : d->crop[0], y0 = r.differ ? win[i].crop[2] : d->crop[2];
-      a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
-      a.c[i] = src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
-      if ((r.vec || px) && (x0 & 3) == 0) a.vec |= 1u << i;               // (a batch may mix aligned and unaligned left edges)
-      if (linear) { site.x0[i] = (int16_t)(x0 >> c->csx); site.y0[i] = (int16_t)(y0 >> c->csy); }
-    }
-    a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
-    a.n = n; a.layout = d->layout; a.elem = r.elem; a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-    a.w = r.plan.width[0]; a.h = r.plan.height[0];
-    a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
-    export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-    if (linear) {
-      if (px) launch_export_px_chroma(a, r.po, site, cs ? &cs->lut : nullptr, r.nch, hs);
-      else launch_export_chroma(a, site, cs ? &cs->lut : nullptr, hs);
-      if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
-    } else if (cs) {
-      if (px) launch_export_px_colour(a, r.po, cs->lut, r.nch, hs);
-      else launch_export_colour(a, cs->lut, hs);
-      HIP_TRY(c, hipEventRecord(cs->done, hs));
-      cs->pending = true;
-    } else if (px) {
-      launch_export_px(a, r.po, r.nch, hs);
-    } else {
-      launch_export(a, hs);
-    }
-    return export_end(c, n, pics, on_stream, hs);
-  }
   const ScaleShape& s = r.s;
   // the tables' slot is keyed by the tiles the batch size leads to, not by the batch size: calls of varying n share a slot
   int tile[2][2] = {{0, 0}, {0, 0}};
@@ -1189,14 +1166,13 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
     scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
     tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
   }
-  hmgpu_ctx::TableBuf* tables = nullptr;
   ScaleArgs a;
   memset(&a, 0, sizeof(a));
   if (r.differ) {
-    const hmgpu_status st = window_tables(c, n, r.shapes, win, rgb, tile, hs, a.cls, &a.pic_cls, &tables);
+    const hmgpu_status st = window_tables(c, n, r.shapes, q.win, rgb, tile, hs, a.cls, &a.pic_cls, tables);
     if (st != HMGPU_OK) return st;
   } else {
-    const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], sc->width, sc->height, sc->filter, tkey};
+    const int32_t key[8] = {d->crop[0], d->crop[1], d->crop[2], d->crop[3], q.sc->width, q.sc->height, q.sc->filter, tkey};
     int x0c[2] = {d->crop[0], d->crop[0] >> c->csx};
     hmgpu_ctx::ScaleSlot* slot = nullptr;
     { const hmgpu_status st = scale_slot(c, key, s, rgb, x0c, tile, hs, &slot); if (st != HMGPU_OK) return st; }
@@ -1206,7 +1182,7 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
       a.cls[k].x0 = x0c[k];
       a.cls[k].y0 = k ? d->crop[2] >> c->csy : d->crop[2];
     }
-    tables = slot;
+    *tables = slot;
   }
   for (int i = 0; i < n; i++) {
     const Picture& p = c->pics[pics[i]];
@@ -1216,94 +1192,18 @@ static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, 
   a.pitch_c = c->pitch[1];
   a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
   a.e = r.plan.coef[11];
-  a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
-  if (px) a.px = r.po;
-  export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-  if (linear) {
-    launch_export_scaled_chroma(a, site, cs ? &cs->lut : nullptr, r.elem, n, hs, r.nch);
-    if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
-  } else if (cs) {
-    launch_export_scaled_colour(a, cs->lut, r.elem, n, hs, r.nch);
-    HIP_TRY(c, hipEventRecord(cs->done, hs));
-    cs->pending = true;
-  } else {
-    launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
-  }
-  HIP_TRY(c, hipEventRecord(tables->done, hs));
-  tables->pending = true;
-  return export_end(c, n, pics, on_stream, hs);
+  a.vec = q.px ? (int)r.po.vst : r.vec ? 1 : 0;
+  if (q.px) a.px = r.po;
+  export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
+  if (site) launch_export_scaled_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, r.elem, n, hs, r.nch);
+  else if (r.cs) launch_export_scaled_colour(a, r.cs->lut, r.elem, n, hs, r.nch);
+  else launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  return HMGPU_OK;
 }
 
-hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
-                                  int32_t on_stream, void* stream) {
-  return export_impl(c, 1, &pic, d, nullptr, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
-}
-
-hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
-  if (!sc) return HMGPU_EINVAL;
-  return export_impl(c, 1, &pic, d, sc, nullptr, dst, pitch_bytes, nullptr, on_stream, stream);
-}
-
-hmgpu_status hmgpu_pictures_export(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                   const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
-                                   const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
-  if (!batch_stride_bytes) return HMGPU_EINVAL;
-  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
-}
-
-hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                           const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
-                                           const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
-  if (!batch_stride_bytes || !windows) return HMGPU_EINVAL;
-  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
-}
-
-hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
-                                          void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int32_t on_stream, void* stream) {
-  if (!px) return HMGPU_EINVAL;
-  void* const dst3[3] = {dst, nullptr, nullptr};
-  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
-  return export_impl(c, n, pics, d, sc, t, dst3, pitch3, bstride3, on_stream, stream, windows, px);
-}
-
-hmgpu_status hmgpu_pictures_export_colour(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
-                                          hmgpu_lut lut, void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
-                                          int32_t on_stream, void* stream) {
-  if (!batch_stride_bytes) return HMGPU_EINVAL;
-  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, &lut);
-}
-
-hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
-                                          hmgpu_lut lut, const hmgpu_export_chroma* chroma, void* const dst[3], const int64_t pitch_bytes[3],
-                                          const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
-  if (!batch_stride_bytes) return HMGPU_EINVAL;
-  return export_impl(c, n, pics, d, sc, t, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, px, lut ? &lut : nullptr, true, chroma);
-}
-
-// the warp export: n pictures of the RGB layout, each through its own map; one launch, the maps and windows in one copy through the
-// window ring
-hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
-                                        const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
-                                        hmgpu_lut lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* wp,
-                                        const hmgpu_warp_map maps[], void* const dst[3], const int64_t pitch_bytes[3],
-                                        const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
-  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !desc || !dst || !pitch_bytes || !batch_stride_bytes ||
-      (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-  ExportCall r;
-  hmgpu_ctx::ColourSlot* cs = nullptr;
-  { const hmgpu_status st = warp_resolve(c, n, desc, t, windows, px, lut, chroma, wp, maps, dst, pitch_bytes, batch_stride_bytes, &r, &cs);
-    if (st != HMGPU_OK) return st; }
-  // the chroma stage: 4:4:4 and 4:0:0, where it is the identity, and HMGPU_CHROMA_REPLICATE run the instances without it
-  ChromaSite site;
-  const bool linear = chroma && chroma->filter == HMGPU_CHROMA_LINEAR && (c->seq.chroma_format == 1 || c->seq.chroma_format == 2);
-  if (linear) chroma_site(c->seq, *chroma, &site);
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+// n pictures of the RGB layout, each through its own map: the maps and windows in one copy through the window ring
+static hmgpu_status launch_warp(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const ExportReq& q, const ExportCall& r, const ChromaSite* site,
+                                void* const dst[3], const int64_t pitch_bytes[3], hipStream_t hs, hmgpu_ctx::TableBuf** tables) {
   hmgpu_ctx::TableBuf* wb = &c->window_buf[c->window_next];
   c->window_next = (c->window_next + 1) % hmgpu_ctx::kWindowBufs;
   // (the export that read the buffer last may still be in flight)
@@ -1316,10 +1216,10 @@ hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic
     const Picture& p = c->pics[pics[i]];
     int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
     a.src[i][0] = src[0]; a.src[i][1] = src[1];
-    const int32_t* cr = windows ? windows[i].crop : desc->crop;
+    const int32_t* cr = q.win ? q.win[i].crop : q.d->crop;
     WarpPic& k = wpic[i];
     memset(&k, 0, sizeof(k));
-    memcpy(k.m, maps[i].m, sizeof(k.m));
+    memcpy(k.m, q.maps[i].m, sizeof(k.m));
     k.x0 = cr[0]; k.y0 = cr[2];
     k.ws = c->seq.width - cr[0] - cr[1]; k.hs = c->seq.height - cr[2] - cr[3];
   }
@@ -1327,17 +1227,108 @@ hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic
   a.pics = reinterpret_cast<const WarpPic*>(wb->dev);
   a.pitch_y = c->pitch[0]; a.pitch_c = c->pitch[1];
   a.mono = c->seq.chroma_format == 0; a.csx = c->csx; a.csy = c->csy;
-  a.w = wp->width; a.h = wp->height; a.tiles_x = (wp->width + kWarpTileW - 1) / kWarpTileW;
-  a.filter = wp->filter; a.border = wp->border;
-  for (int k = 0; k < 3; k++) a.fill[k] = wp->border == HMGPU_WARP_FILL ? (uint32_t)wp->fill[k] : 0;
-  a.vec = px ? (int)r.po.vst : r.vec ? 1 : 0;
-  if (px) a.px = r.po;
-  export_args_tail(a, c->seq, r, t, dst, pitch_bytes);
-  launch_export_warp(a, linear ? &site : nullptr, cs ? &cs->lut : nullptr, r.elem, n, r.nch, hs);
-  if (cs) { HIP_TRY(c, hipEventRecord(cs->done, hs)); cs->pending = true; }
-  HIP_TRY(c, hipEventRecord(wb->done, hs));
-  wb->pending = true;
+  a.w = q.wp->width; a.h = q.wp->height; a.tiles_x = (q.wp->width + kWarpTileW - 1) / kWarpTileW;
+  a.filter = q.wp->filter; a.border = q.wp->border;
+  for (int k = 0; k < 3; k++) a.fill[k] = q.wp->border == HMGPU_WARP_FILL ? (uint32_t)q.wp->fill[k] : 0;
+  a.vec = q.px ? (int)r.po.vst : r.vec ? 1 : 0;
+  if (q.px) a.px = r.po;
+  export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
+  launch_export_warp(a, site, r.cs ? &r.cs->lut : nullptr, r.elem, n, r.nch, hs);
+  *tables = wb;
+  return HMGPU_OK;
+}
+
+// every export: n pictures of the request q, the destination as export_resolve takes it.  One launch, the stream ordering once.
+static hmgpu_status export_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const ExportReq& q, void* const dst[3],
+                                const int64_t pitch_bytes[3], const int64_t* bstride, int32_t on_stream, void* stream) {
+  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !q.d || (q.need_sc && !q.sc) || (q.need_win && !q.win) || (q.need_px && !q.px) ||
+      !dst || !pitch_bytes || (!q.single && !bstride) || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
+  ExportCall r;
+  { const hmgpu_status st = export_resolve(c, n, q, dst, pitch_bytes, bstride, true, &r); if (st != HMGPU_OK) return st; }
+  // the chroma stage: 4:4:4 and 4:0:0, where it is the identity, and HMGPU_CHROMA_REPLICATE run the instances without it
+  ChromaSite site;
+  const bool linear = q.chroma && q.chroma->filter == HMGPU_CHROMA_LINEAR && (c->seq.chroma_format == 1 || c->seq.chroma_format == 2);
+  if (linear) chroma_site(c->seq, *q.chroma, &site);
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  hmgpu_ctx::TableBuf* tables = nullptr;
+  hmgpu_status st = HMGPU_OK;
+  if (q.warp) st = launch_warp(c, n, pics, q, r, linear ? &site : nullptr, dst, pitch_bytes, hs, &tables);
+  else if (q.sc) st = launch_scaled(c, n, pics, q, r, linear ? &site : nullptr, dst, pitch_bytes, hs, &tables);
+  else launch_unscaled(c, n, pics, q, r, linear ? &site : nullptr, dst, pitch_bytes, hs);
+  if (st != HMGPU_OK) return st;
+  if (r.cs) { HIP_TRY(c, hipEventRecord(r.cs->done, hs)); r.cs->pending = true; }
+  if (tables) { HIP_TRY(c, hipEventRecord(tables->done, hs)); tables->pending = true; }
   return export_end(c, n, pics, on_stream, hs);
+}
+
+hmgpu_status hmgpu_picture_export(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, void* const dst[3], const int64_t pitch_bytes[3],
+                                  int32_t on_stream, void* stream) {
+  ExportReq q(d, nullptr, nullptr);
+  q.single = true;
+  return export_impl(c, 1, &pic, q, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_picture_export_scaled(hmgpu_ctx* c, hmgpu_pic pic, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                         void* const dst[3], const int64_t pitch_bytes[3], int32_t on_stream, void* stream) {
+  ExportReq q(d, sc, nullptr);
+  q.single = q.need_sc = true;
+  return export_impl(c, 1, &pic, q, dst, pitch_bytes, nullptr, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                   const hmgpu_export_tensor* t, void* const dst[3], const int64_t pitch_bytes[3],
+                                   const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  return export_impl(c, n, pics, ExportReq(d, sc, t), dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_windows(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, const hmgpu_export_window windows[], void* const dst[3],
+                                           const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  ExportReq q(d, sc, t, windows);
+  q.need_win = true;
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_pixels(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int32_t on_stream, void* stream) {
+  void* const dst3[3] = {dst, nullptr, nullptr};
+  const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
+  ExportReq q(d, sc, t, windows, px);
+  q.need_px = true;
+  return export_impl(c, n, pics, q, dst3, pitch3, bstride3, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_colour(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          hmgpu_lut lut, void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                          int32_t on_stream, void* stream) {
+  ExportReq q(d, sc, t, windows, px);
+  q.lut = lut;
+  q.colour_stage = true;
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                          hmgpu_lut lut, const hmgpu_export_chroma* chroma, void* const dst[3], const int64_t pitch_bytes[3],
+                                          const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  ExportReq q(d, sc, t, windows, px);
+  optional_stages(&q, lut, nullptr, chroma, true);
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d,
+                                        const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_pixel* px,
+                                        hmgpu_lut lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* wp,
+                                        const hmgpu_warp_map maps[], void* const dst[3], const int64_t pitch_bytes[3],
+                                        const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  ExportReq q(d, nullptr, t, windows, px);
+  optional_stages(&q, lut, nullptr, chroma, false);
+  q.wp = wp; q.maps = maps; q.warp = true;
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ side information: what motion and residual share

@@ -1031,6 +1031,17 @@ std::vector<ExportRun> export_runs(int n, PicData* const* pics, const hmgpu_expo
   }
   return runs;
 }
+
+// the destinations and batch strides of run r within those of the whole call: from slot r.first on, r.step slots apart.  A null
+// destination stays null; null arrays (a call without these destinations): null and 0
+template <int SLOTS>
+void run_span(const ExportRun& r, void* const* dst, const int64_t* stride, void** d, int64_t* bs) {
+  for (int k = 0; k < SLOTS; k++) {
+    const bool have = dst && stride;
+    d[k] = have && dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * stride[k] : nullptr;
+    bs[k] = have ? stride[k] * r.step : 0;
+  }
+}
 }  // namespace
 
 // what every batched export asks of its pictures: this decoder's, on the device and decoded (their device work enqueued first), one size, one GPU
@@ -1045,114 +1056,55 @@ hmgpu_status Decoder::export_pics_ok(int n, PicData* const* pics) {
   return HMGPU_OK;
 }
 
-hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
-                                       const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows,
-                                       const hmgpu_export_pixel* pixel, const int64_t* lut, const hmgpu_export_chroma* const* chroma) {
+// The whole batch is validated once, for all n slots at the caller's batch stride in the first picture's context, before any
+// context is given work; then one call of the same entry per run of slots (export_runs), each with its own windows and maps and with
+// the LUT's handle in its own context.
+hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const ExportRequest& q, void* const dst[3], const int64_t pitch_bytes[3],
+                                       const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
   if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
-  if (chroma) {
-    // the chroma stage (with a LUT: the colour stage behind it): validated once in the first picture's context, then one call per
-    // run of slots, as below
-    auto it = lut && *lut ? luts_.find(*lut) : luts_.end();
-    if (lut && *lut && it == luts_.end()) return HMGPU_EINVAL;
-    const bool col = it != luts_.end();
-    hmgpu_lut h = 0;
-    if (col) { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
-    { const hmgpu_status st = hmgpu_export_chroma_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, h, *chroma, dst, pitch_bytes, batch_stride_bytes);
-      if (st != HMGPU_OK) return st; }
-    const std::vector<ExportRun> runs = export_runs(n, pics, windows);
-    if (col) for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
-    for (const ExportRun& r : runs) {
-      void* d[3];
-      int64_t bs[3];
-      for (int k = 0; k < 3; k++) {
-        d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-        bs[k] = batch_stride_bytes[k] * r.step;
-      }
-      if (col) (void)colour_lut_on(it->second, r.home, &h);
-      const hmgpu_status st = hmgpu_pictures_export_chroma(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, scale, tensor,
-                                                           windows ? r.w : nullptr, pixel, h, *chroma, d, pitch_bytes, bs, on_stream, stream);
-      if (st != HMGPU_OK) return st;
-    }
-    return HMGPU_OK;
-  }
-  if (lut) {
-    // the colour stage: the whole batch validated once in the first picture's context, then one call per run of slots, each with the
-    // LUT's handle in its own context
-    auto it = luts_.find(*lut);
+  ColourLutHost* lut = nullptr;                                            // (the colour entry: 0 names no LUT)
+  if (q.entry == ExportRequest::COLOUR || q.lut) {
+    auto it = luts_.find(q.lut);
     if (it == luts_.end()) return HMGPU_EINVAL;
-    hmgpu_lut h = 0;
-    { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
-    { const hmgpu_status st = hmgpu_export_colour_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, h, dst, pitch_bytes, batch_stride_bytes);
-      if (st != HMGPU_OK) return st; }
-    const std::vector<ExportRun> runs = export_runs(n, pics, windows);
-    for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
-    for (const ExportRun& r : runs) {
-      void* d[3];
-      int64_t bs[3];
-      for (int k = 0; k < 3; k++) {
-        d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-        bs[k] = batch_stride_bytes[k] * r.step;
-      }
-      (void)colour_lut_on(it->second, r.home, &h);
-      const hmgpu_status st = hmgpu_pictures_export_colour(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, scale, tensor,
-                                                           windows ? r.w : nullptr, pixel, h, d, pitch_bytes, bs, on_stream, stream);
-      if (st != HMGPU_OK) return st;
-    }
-    return HMGPU_OK;
+    lut = &it->second;
   }
-  // The whole destination is validated once, for all n slots at the caller's batch stride, before any context is given work.  Then
-  // one hmgpu_pictures_export per run of slots (export_runs).
-  { const hmgpu_status st = pixel ? hmgpu_export_pixels_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, pixel, dst[0], pitch_bytes[0], batch_stride_bytes[0])
-                          : windows ? hmgpu_export_windows_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, windows, dst, pitch_bytes, batch_stride_bytes)
-                                    : hmgpu_export_destination_check(ctx_of(pics[0]), n, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes);
-    if (st != HMGPU_OK) return st; }
-  for (const ExportRun& r : export_runs(n, pics, windows)) {
-    void* d[3];
-    int64_t bs[3];
-    for (int k = 0; k < 3; k++) {
-      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-      bs[k] = batch_stride_bytes[k] * r.step;
-    }
-    hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
-    const hmgpu_status st = pixel ? hmgpu_pictures_export_pixels(c, r.n, r.h, desc, scale, tensor, windows ? r.w : nullptr, pixel, d[0], pitch_bytes[0], bs[0], on_stream, stream)
-                          : windows ? hmgpu_pictures_export_windows(c, r.n, r.h, desc, scale, tensor, r.w, d, pitch_bytes, bs, on_stream, stream)
-                                    : hmgpu_pictures_export(c, r.n, r.h, desc, scale, tensor, d, pitch_bytes, bs, on_stream, stream);
-    if (st != HMGPU_OK) return st;
-  }
-  return HMGPU_OK;
-}
-
-// hmgpu_pictures_export_warp under the rules of export_pictures: the whole batch validated once in the first picture's context, then
-// one call per run of slots with the run's own windows and maps, each with the LUT's handle in its own context
-hmgpu_status Decoder::export_warp(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
-                                  const hmgpu_export_window* windows, const hmgpu_export_pixel* pixel, int64_t lut,
-                                  const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map* maps,
-                                  void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
-                                  void* stream) {
-  if (!gpu_ || !pics || !dst || !pitch_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
-  auto it = lut ? luts_.find(lut) : luts_.end();
-  if (lut && it == luts_.end()) return HMGPU_EINVAL;
-  const bool col = it != luts_.end();
   hmgpu_lut h = 0;
-  if (col) { const hmgpu_status st = colour_lut_on(it->second, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = hmgpu_export_warp_destination_check(ctx_of(pics[0]), n, desc, tensor, windows, pixel, h, chroma, warp, maps, dst,
-                                                                pitch_bytes, batch_stride_bytes);
-    if (st != HMGPU_OK) return st; }
-  const std::vector<ExportRun> runs = export_runs(n, pics, windows, maps);
-  if (col) for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(it->second, r.home, &h); if (st != HMGPU_OK) return st; }
+  // the request's entry on context c: its destination check, or the export of rn pictures
+  auto entry = [&](hmgpu_ctx* c, bool check, int rn, const hmgpu_pic* rh, const hmgpu_export_window* w, const hmgpu_warp_map* m, void* const* d,
+                   const int64_t* bs) -> hmgpu_status {
+    switch (q.entry) {
+      case ExportRequest::WARP:
+        return check ? hmgpu_export_warp_destination_check(c, rn, q.desc, q.tensor, w, q.pixel, h, q.chroma, q.warp, m, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export_warp(c, rn, rh, q.desc, q.tensor, w, q.pixel, h, q.chroma, q.warp, m, d, pitch_bytes, bs, on_stream, stream);
+      case ExportRequest::CHROMA:
+        return check ? hmgpu_export_chroma_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, h, q.chroma, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export_chroma(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, h, q.chroma, d, pitch_bytes, bs, on_stream, stream);
+      case ExportRequest::COLOUR:
+        return check ? hmgpu_export_colour_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export_colour(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs, on_stream, stream);
+      default:
+        if (q.pixel)
+          return check ? hmgpu_export_pixels_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, d[0], pitch_bytes[0], bs[0])
+                       : hmgpu_pictures_export_pixels(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, d[0], pitch_bytes[0], bs[0], on_stream, stream);
+        if (w)
+          return check ? hmgpu_export_windows_destination_check(c, rn, q.desc, q.scale, q.tensor, w, d, pitch_bytes, bs)
+                       : hmgpu_pictures_export_windows(c, rn, rh, q.desc, q.scale, q.tensor, w, d, pitch_bytes, bs, on_stream, stream);
+        return check ? hmgpu_export_destination_check(c, rn, q.desc, q.scale, q.tensor, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export(c, rn, rh, q.desc, q.scale, q.tensor, d, pitch_bytes, bs, on_stream, stream);
+    }
+  };
+  if (lut) { const hmgpu_status st = colour_lut_on(*lut, pics[0]->home, &h); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = entry(ctx_of(pics[0]), true, n, nullptr, q.windows, q.maps, dst, batch_stride_bytes); if (st != HMGPU_OK) return st; }
+  const std::vector<ExportRun> runs = export_runs(n, pics, q.windows, q.maps);
+  // the LUT present in every run's context before any context is given work
+  if (lut) for (const ExportRun& r : runs) { const hmgpu_status st = colour_lut_on(*lut, r.home, &h); if (st != HMGPU_OK) return st; }
   for (const ExportRun& r : runs) {
     void* d[3];
     int64_t bs[3];
-    for (int k = 0; k < 3; k++) {
-      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-      bs[k] = batch_stride_bytes[k] * r.step;
-    }
-    if (col) (void)colour_lut_on(it->second, r.home, &h);
-    const hmgpu_status st = hmgpu_pictures_export_warp(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, desc, tensor,
-                                                       windows ? r.w : nullptr, pixel, h, chroma, warp, r.m, d, pitch_bytes, bs, on_stream, stream);
+    run_span<3>(r, dst, batch_stride_bytes, d, bs);
+    if (lut) (void)colour_lut_on(*lut, r.home, &h);
+    const hmgpu_status st = entry(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], false, r.n, r.h, q.windows ? r.w : nullptr, q.maps ? r.m : nullptr, d, bs);
     if (st != HMGPU_OK) return st;
   }
   return HMGPU_OK;
@@ -1193,30 +1145,25 @@ hmgpu_status Decoder::colour_lut_destroy(int64_t lut) {
   return HMGPU_OK;
 }
 
-// As export_pictures: the destination (and every window) validated once for all n slots, then one call per run of slots of one
-// context -- the context that decoded the pictures (PicData::home), the only one that holds their side information and residual
-// tiles.  Whether every picture has side information is asked of every context first, so that no context is given work when another
-// one's call would be refused.
+// As export_pictures: the whole call -- the destinations of all n slots at the caller's strides, and every window -- validated once
+// in the first picture's context, then every run of slots of one context checked (its handles; export_motion and export_residual:
+// whether they have side information, which only the context that decoded them, PicData::home, holds), so that no context is given
+// work when another one's call would be refused; then one call per run.
 template <int SLOTS, class Check, class Side, class Run>
 hmgpu_status Decoder::export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,
                                   Check check, Side side, Run run) {
   { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
   { const hmgpu_status st = check(ctx_of(pics[0])); if (st != HMGPU_OK) return st; }
   const std::vector<ExportRun> runs = export_runs(n, pics, windows);
-  for (const ExportRun& r : runs) {
-    const hmgpu_status st = side(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h);
-    if (st != HMGPU_OK) return st;
-  }
-  for (const ExportRun& r : runs) {
-    void* d[SLOTS];
-    int64_t bs[SLOTS];
-    for (int k = 0; k < SLOTS; k++) {
-      d[k] = dst[k] ? static_cast<char*>(dst[k]) + (int64_t)r.first * batch_stride_bytes[k] : nullptr;
-      bs[k] = batch_stride_bytes[k] * r.step;
+  for (int pass = 0; pass < 2; pass++)
+    for (const ExportRun& r : runs) {
+      void* d[SLOTS];
+      int64_t bs[SLOTS];
+      run_span<SLOTS>(r, dst, batch_stride_bytes, d, bs);
+      hmgpu_ctx* c = gpus_.empty() ? gpu_ : gpus_[(size_t)r.home];
+      const hmgpu_status st = pass == 0 ? side(c, r.n, r.h, d, bs) : run(c, r.n, r.h, windows ? r.w : nullptr, d, bs);
+      if (st != HMGPU_OK) return st;
     }
-    const hmgpu_status st = run(gpus_.empty() ? gpu_ : gpus_[(size_t)r.home], r.n, r.h, windows ? r.w : nullptr, d, bs);
-    if (st != HMGPU_OK) return st;
-  }
   return HMGPU_OK;
 }
 
@@ -1228,7 +1175,7 @@ hmgpu_status Decoder::export_motion(int n, PicData* const* pics, const hmgpu_mot
   void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
   return export_side<4>(n, pics, windows, dst, batch_stride_bytes,
       [&](hmgpu_ctx* c) { return hmgpu_motion_destination_check(c, n, desc, scale, windows, dst_mv, dst_ref, dst_block, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
-      hmgpu_pictures_motion_check,
+      [](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const*, const int64_t*) { return hmgpu_pictures_motion_check(c, rn, h); },
       [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window* w, void* const* d, const int64_t* bs) {
         return hmgpu_pictures_export_motion(c, rn, h, desc, scale, w, d, d[2], d[3], pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
@@ -1239,13 +1186,14 @@ hmgpu_status Decoder::export_residual(int n, PicData* const* pics, const hmgpu_r
   if (!gpu_ || !pics || !desc || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   return export_side<3>(n, pics, windows, dst, batch_stride_bytes,
       [&](hmgpu_ctx* c) { return hmgpu_residual_destination_check(c, n, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
-      hmgpu_pictures_residual_check,
+      [](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const*, const int64_t*) { return hmgpu_pictures_residual_check(c, rn, h); },
       [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window* w, void* const* d, const int64_t* bs) {
         return hmgpu_pictures_export_residual(c, rn, h, desc, scale, w, d, pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
-// The whole call -- description, reference planes and results of all n slots at the caller's strides -- is validated once on the first
-// run's context (its first handle standing for every slot), then every run's handles, then one hmgpu_pictures_metrics per run.
+// hmgpu_pictures_metrics through export_side, the results the fourth destination behind the reference planes: the whole call --
+// description, reference planes and results of all n slots -- validated once (the first handle standing for every slot), then every
+// run's handles, then one call per run.
 hmgpu_status Decoder::metrics(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const void* const ref[3], const int64_t ref_pitch_bytes[3],
                               const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes, int on_stream, void* stream) {
   if (!gpu_ || !pics || !desc || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
@@ -1254,35 +1202,20 @@ hmgpu_status Decoder::metrics(int n, PicData* const* pics, const hmgpu_metrics_d
     return HMGPU_EUNSUPPORTED;
   }
   if (!ref || !ref_pitch_bytes || !ref_batch_stride_bytes) return HMGPU_EINVAL;
-  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
-  const std::vector<ExportRun> runs = export_runs(n, pics, nullptr);
-  auto ctx_of_run = [&](const ExportRun& r) { return gpus_.empty() ? gpu_ : gpus_[(size_t)r.home]; };
-  {
-    hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
-    for (int i = 0; i < n; i++) all[i] = runs[0].h[0];
-    const hmgpu_status st = hmgpu_metrics_check(ctx_of_run(runs[0]), n, all, desc, nullptr, ref, ref_pitch_bytes, ref_batch_stride_bytes, results,
-                                                results_batch_stride_bytes);
-    if (st != HMGPU_OK) return st;
-  }
-  for (int pass = 0; pass < 2; pass++)
-    for (const ExportRun& r : runs) {
-      const void* d[3];
-      int64_t bs[3];
-      for (int k = 0; k < 3; k++) {
-        d[k] = ref[k] ? static_cast<const char*>(ref[k]) + (int64_t)r.first * ref_batch_stride_bytes[k] : nullptr;
-        bs[k] = ref_batch_stride_bytes[k] * r.step;
-      }
-      void* res = static_cast<char*>(results) + (int64_t)r.first * results_batch_stride_bytes;
-      const int64_t rs = results_batch_stride_bytes * r.step;
-      const hmgpu_status st = pass == 0 ? hmgpu_metrics_check(ctx_of_run(r), r.n, r.h, desc, nullptr, d, ref_pitch_bytes, bs, res, rs)
-                                        : hmgpu_pictures_metrics(ctx_of_run(r), r.n, r.h, desc, nullptr, d, ref_pitch_bytes, bs, res, rs, on_stream, stream);
-      if (st != HMGPU_OK) return st;
-    }
-  return HMGPU_OK;
+  void* const dst[4] = {const_cast<void*>(ref[0]), const_cast<void*>(ref[1]), const_cast<void*>(ref[2]), results};
+  const int64_t stride[4] = {ref_batch_stride_bytes[0], ref_batch_stride_bytes[1], ref_batch_stride_bytes[2], results_batch_stride_bytes};
+  return export_side<4>(n, pics, nullptr, dst, stride,
+      [&](hmgpu_ctx* c) {
+        hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
+        for (int i = 0; i < n; i++) all[i] = pics[0]->handle;
+        return hmgpu_metrics_check(c, n, all, desc, nullptr, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const* d, const int64_t* bs) {
+        return hmgpu_metrics_check(c, rn, h, desc, nullptr, d, ref_pitch_bytes, bs, d[3], bs[3]); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window*, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_metrics(c, rn, h, desc, nullptr, d, ref_pitch_bytes, bs, d[3], bs[3], on_stream, stream); });
 }
 
-// As metrics: the whole call validated once on the first run's context (its first handle standing for every slot), then every run's
-// handles, then one hmgpu_pictures_histogram per run of equally spaced slots.
+// hmgpu_pictures_histogram likewise, the records the fifth destination behind the histograms (null: a call without histograms)
 hmgpu_status Decoder::histogram(int n, PicData* const* pics, const hmgpu_histogram_desc* desc, void* const hist[4], const int64_t hist_batch_stride_bytes[4],
                                 void* records, int64_t records_batch_stride_bytes, int on_stream, void* stream) {
   if (!gpu_ || !pics || !desc || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
@@ -1290,30 +1223,18 @@ hmgpu_status Decoder::histogram(int n, PicData* const* pics, const hmgpu_histogr
     set_error("hmdec_pictures_histogram: the pictures must be kept on the device (hmdec_set_device_output)");
     return HMGPU_EINVAL;
   }
-  { const hmgpu_status st = export_pics_ok(n, pics); if (st != HMGPU_OK) return st; }
-  const std::vector<ExportRun> runs = export_runs(n, pics, nullptr);
-  auto ctx_of_run = [&](const ExportRun& r) { return gpus_.empty() ? gpu_ : gpus_[(size_t)r.home]; };
-  {
-    hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
-    for (int i = 0; i < n; i++) all[i] = runs[0].h[0];
-    const hmgpu_status st = hmgpu_histogram_check(ctx_of_run(runs[0]), n, all, desc, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes);
-    if (st != HMGPU_OK) return st;
-  }
-  for (int pass = 0; pass < 2; pass++)
-    for (const ExportRun& r : runs) {
-      void* d[4] = {nullptr, nullptr, nullptr, nullptr};
-      int64_t bs[4] = {0, 0, 0, 0};
-      for (int k = 0; k < 4 && hist && hist_batch_stride_bytes; k++) {
-        d[k] = hist[k] ? static_cast<char*>(hist[k]) + (int64_t)r.first * hist_batch_stride_bytes[k] : nullptr;
-        bs[k] = hist_batch_stride_bytes[k] * r.step;
-      }
-      void* rec = static_cast<char*>(records) + (int64_t)r.first * records_batch_stride_bytes;
-      const int64_t rs = records_batch_stride_bytes * r.step;
-      const hmgpu_status st = pass == 0 ? hmgpu_histogram_check(ctx_of_run(r), r.n, r.h, desc, d, bs, rec, rs)
-                                        : hmgpu_pictures_histogram(ctx_of_run(r), r.n, r.h, desc, d, bs, rec, rs, on_stream, stream);
-      if (st != HMGPU_OK) return st;
-    }
-  return HMGPU_OK;
+  void* dst[5] = {nullptr, nullptr, nullptr, nullptr, records};
+  int64_t stride[5] = {0, 0, 0, 0, records_batch_stride_bytes};
+  for (int k = 0; k < 4 && hist && hist_batch_stride_bytes; k++) { dst[k] = hist[k]; stride[k] = hist_batch_stride_bytes[k]; }
+  return export_side<5>(n, pics, nullptr, dst, stride,
+      [&](hmgpu_ctx* c) {
+        hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
+        for (int i = 0; i < n; i++) all[i] = pics[0]->handle;
+        return hmgpu_histogram_check(c, n, all, desc, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const* d, const int64_t* bs) {
+        return hmgpu_histogram_check(c, rn, h, desc, d, bs, d[4], bs[4]); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window*, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_histogram(c, rn, h, desc, d, bs, d[4], bs[4], on_stream, stream); });
 }
 
 // MD5 of one plane as the SEI defines it (TComPicYuvMD5.cpp:183-205): samples as 1 or 2 little-endian bytes, row by row

@@ -20,6 +20,22 @@
 
 namespace hmdec {
 
+// The stages of a batched picture export, as the hmdec_pictures_export* entries fill them and Decoder::export_pictures hands them to
+// the hmgpu entry of the same name.  entry: whose rules hold for an absent stage -- PLAIN: hmgpu_pictures_export, _windows (windows
+// set) or _pixels (pixel set); COLOUR: lut 0 is refused; CHROMA: lut 0 is no colour stage; WARP: chroma null is "replicate" too
+struct ExportRequest {
+  enum Entry { PLAIN, COLOUR, CHROMA, WARP } entry = PLAIN;
+  const hmgpu_export_desc* desc = nullptr;
+  const hmgpu_export_scale* scale = nullptr;
+  const hmgpu_export_tensor* tensor = nullptr;
+  const hmgpu_export_window* windows = nullptr;            // null, or one per picture
+  const hmgpu_export_pixel* pixel = nullptr;
+  int64_t lut = 0;                                         // a LUT of the decoder (colour_lut_create)
+  const hmgpu_export_chroma* chroma = nullptr;
+  const hmgpu_export_warp* warp = nullptr;
+  const hmgpu_warp_map* maps = nullptr;                    // one per picture
+};
+
 class Decoder {
  public:
   Decoder();
@@ -70,22 +86,13 @@ class Decoder {
   // scale: nullptr = hmgpu_picture_export, else hmgpu_picture_export_scaled
   hmgpu_status export_picture(PicData* pic, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, void* const dst[3], const int64_t pitch_bytes[3],
                               int on_stream, void* stream);
-  // hmgpu_pictures_export of pictures put out and still valid: one sequence, one GPU ordinal; one call per device context that holds some.
-  // windows: nullptr, or one per picture (hmgpu_pictures_export_windows; each run of slots carries its own); pixel: nullptr, or packed
-  // pixels (hmgpu_pictures_export_pixels: dst[0], pitch_bytes[0] and batch_stride_bytes[0] the one destination)
-  hmgpu_status export_pictures(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
-                               const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3],
-                               const int64_t batch_stride_bytes[3], int on_stream, void* stream, const hmgpu_export_window* windows = nullptr,
-                               const hmgpu_export_pixel* pixel = nullptr, const int64_t* lut = nullptr,
-                               const hmgpu_export_chroma* const* chroma = nullptr);   // chroma: hmgpu_pictures_export_chroma (*lut 0: no colour stage)
-  // hmgpu_pictures_export_warp under the rules of export_pictures (lut 0: no colour stage; chroma nullptr: replicate); each run of
-  // slots carries its own windows and maps
-  hmgpu_status export_warp(int n, PicData* const* pics, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
-                           const hmgpu_export_window* windows, const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma,
-                           const hmgpu_export_warp* warp, const hmgpu_warp_map* maps, void* const dst[3], const int64_t pitch_bytes[3],
-                           const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+  // a hmgpu_pictures_export* call (ExportRequest) of pictures put out and still valid: one sequence, one GPU ordinal; one call per
+  // device context that holds some, each run of slots with its own windows and maps.  pixel: dst[0], pitch_bytes[0] and
+  // batch_stride_bytes[0] the one destination
+  hmgpu_status export_pictures(int n, PicData* const* pics, const ExportRequest& q, void* const dst[3], const int64_t pitch_bytes[3],
+                               const int64_t batch_stride_bytes[3], int on_stream, void* stream);
   // colour LUTs (hmgpu_colour_lut_create): the host copy lives here, the device copies are made per context when an export first
-  // needs one (lut of export_pictures: hmgpu_pictures_export_colour) and go with the contexts of a sequence that ends
+  // needs one (lut of an ExportRequest) and go with the contexts of a sequence that ends
   hmgpu_status colour_lut_create(const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice, int64_t* out);
   hmgpu_status colour_lut_destroy(int64_t lut);
   // hmgpu_pictures_export_motion under the rules of export_pictures; the side information lies in the context that decoded a picture
@@ -122,8 +129,8 @@ class Decoder {
   void submit_picture(PicData* pic, int parsed_ctbs);     // marks of a completely parsed picture; its device work joins the batch
   void flush_batch();                                     // the device work of the pictures retired together (hmgpu_decompress_pictures / hmgpu_filter_pictures)
   __attribute__((visibility("hidden"))) hmgpu_status export_pics_ok(int n, PicData* const* pics);   // what every batched export asks of its pictures (their device work enqueued first)
-  // export_motion / export_residual: SLOTS destinations; check: the destination check on a context; side: the side-information check
-  // of a run's pictures; run: the export of one run (context, n, handles, windows, destinations, batch strides)
+  // export_motion / export_residual / metrics / histogram: SLOTS destinations; check: the whole call's check on a context; side: the
+  // check of one run (context, n, handles, destinations, batch strides); run: its export (..., handles, windows, destinations, ...)
   template <int SLOTS, class Check, class Side, class Run>
   hmgpu_status export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,
                            Check check, Side side, Run run);

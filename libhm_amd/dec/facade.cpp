@@ -312,32 +312,40 @@ int hmdec_picture_export_scaled(libHMDec_context* ctx, libHMDec_picture* pic, co
   if (!ctx || !pic || !scale) return HMGPU_EINVAL;
   return static_cast<Wrapper*>(ctx)->dec.export_picture(as_pic(pic), desc, scale, dst, pitch_bytes, on_stream, stream);
 }
-int hmdec_pictures_export(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
-                          const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
-                          int on_stream, void* stream) {
+// every hmdec_pictures_export* entry: the request it filled, on the decoder's pictures
+static int export_request(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const ExportRequest& q, void* const dst[3],
+                          const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
   if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
   PicData* p[HMGPU_EXPORT_MAX_BATCH];
   for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
-  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+static ExportRequest request(ExportRequest::Entry entry, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                             const hmgpu_export_window* windows = nullptr, const hmgpu_export_pixel* pixel = nullptr, int64_t lut = 0,
+                             const hmgpu_export_chroma* chroma = nullptr) {
+  ExportRequest q;
+  q.entry = entry; q.desc = desc; q.scale = scale; q.tensor = tensor; q.windows = windows; q.pixel = pixel; q.lut = lut; q.chroma = chroma;
+  return q;
+}
+int hmdec_pictures_export(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                          const hmgpu_export_tensor* tensor, void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                          int on_stream, void* stream) {
+  return export_request(ctx, n, pics, request(ExportRequest::PLAIN, desc, scale, tensor), dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 int hmdec_pictures_export_windows(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                                   const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                   void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
-  if (!ctx || !pics || !windows || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  PicData* p[HMGPU_EXPORT_MAX_BATCH];
-  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
-  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows);
+  if (!windows) return HMGPU_EINVAL;
+  return export_request(ctx, n, pics, request(ExportRequest::PLAIN, desc, scale, tensor, windows), dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 int hmdec_pictures_export_pixels(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, void* dst, int64_t pitch_bytes, int64_t batch_stride_bytes, int on_stream,
                                  void* stream) {
-  if (!ctx || !pics || !pixel || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  PicData* p[HMGPU_EXPORT_MAX_BATCH];
-  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  if (!pixel) return HMGPU_EINVAL;
   void* const dst3[3] = {dst, nullptr, nullptr};
   const int64_t pitch3[3] = {pitch_bytes, 0, 0}, bstride3[3] = {batch_stride_bytes, 0, 0};
-  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst3, pitch3, bstride3, on_stream, stream, windows, pixel);
+  return export_request(ctx, n, pics, request(ExportRequest::PLAIN, desc, scale, tensor, windows, pixel), dst3, pitch3, bstride3, on_stream, stream);
 }
 int hmdec_colour_lut_create(libHMDec_context* ctx, const hmgpu_colour_lut_desc* desc, const uint16_t* shaper, const uint16_t* lattice,
                             int64_t* out) {
@@ -352,30 +360,24 @@ int hmdec_pictures_export_colour(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, int64_t lut, void* const dst[3], const int64_t pitch_bytes[3],
                                  const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
-  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  PicData* p[HMGPU_EXPORT_MAX_BATCH];
-  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
-  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut);
+  return export_request(ctx, n, pics, request(ExportRequest::COLOUR, desc, scale, tensor, windows, pixel, lut), dst, pitch_bytes, batch_stride_bytes,
+                        on_stream, stream);
 }
 int hmdec_pictures_export_chroma(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_pixel* pixel, int64_t lut, const hmgpu_export_chroma* chroma, void* const dst[3],
                                  const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
-  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  PicData* p[HMGPU_EXPORT_MAX_BATCH];
-  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
-  return static_cast<Wrapper*>(ctx)->dec.export_pictures(n, p, desc, scale, tensor, dst, pitch_bytes, batch_stride_bytes, on_stream, stream, windows, pixel, &lut, &chroma);
+  return export_request(ctx, n, pics, request(ExportRequest::CHROMA, desc, scale, tensor, windows, pixel, lut, chroma), dst, pitch_bytes,
+                        batch_stride_bytes, on_stream, stream);
 }
 int hmdec_pictures_export_warp(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                                const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel,
                                int64_t lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map maps[],
                                void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream,
                                void* stream) {
-  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  PicData* p[HMGPU_EXPORT_MAX_BATCH];
-  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
-  return static_cast<Wrapper*>(ctx)->dec.export_warp(n, p, desc, tensor, windows, pixel, lut, chroma, warp, maps, dst, pitch_bytes,
-                                                     batch_stride_bytes, on_stream, stream);
+  ExportRequest q = request(ExportRequest::WARP, desc, nullptr, tensor, windows, pixel, lut, chroma);
+  q.warp = warp; q.maps = maps;
+  return export_request(ctx, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 int hmdec_pictures_export_motion(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_motion_desc* desc,
                                  const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref,

@@ -9,6 +9,7 @@ the kernel does not implement (anything but 0, 1, 5, 6, 9) are refused with HMGP
 Tensor output (export_batch, dtype=): float16 / bfloat16 / float32 elements take fl(fl(v * scale_k) + bias_k) of the integer v the
 export writes, with (scale, bias) from `affine`: v / (2^D - 1) normalised by a per-plane mean and std.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -467,20 +468,36 @@ def out_pixels(out, plan, desc, px, device, n=None, dtype=None):
     return out.data_ptr(), sy * es, st[0] * es if b else None
 
 
+class Stages(collections.namedtuple("Stages", "scale tensor windows pixel lut chroma warp", defaults=(None,) * 7)):
+    """the stages of one picture export, None where the call has none: scale an abi.ExportScale; tensor an abi.ExportTensor (float
+    elements); windows one abi.ExportWindow per picture; pixel an abi.ExportPixel (packed pixels: one destination); lut a colour LUT
+    of the context or decoder, or its raw handle; chroma an abi.ExportChroma; warp (abi.ExportWarp, abi.WarpMap array) of
+    abi.warp_stage.  libhm_amd.export_stages_plan, Context.export_stages_into and hmdec's dispatcher choose the entry from it."""
+    __slots__ = ()
+
+    def shape_only(self):
+        """without the colour and chroma stages, which change no plan: their rules are the export's own to report"""
+        return self if self.lut is None and self.chroma is None else self._replace(lut=None, chroma=None)
+
+
+def stage_extents(plan, pitches):
+    """the batch strides of one picture exported as a batch of one: every plane's extent"""
+    return [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
+
+
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
                    filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None,
-                   pixel=None, alpha=None, memory_format=None, pixel_call=None, warp=None):
-    """allocate with torch on `device` (or take `out`) and run `call(desc, scale, tensor, ptrs, pitches, bstrides, stream)` on torch's
-    current stream.  scale: None (size None), else the abi.ExportScale of size (height, width) and filter; tensor: None (dtype None),
-    else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); bstrides: None for one picture
-    (n None), else the bytes between the batch entries of every plane of the n pictures.  windows: None, or the abi.ExportWindow of
-    every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0).
-    pixel / alpha / memory_format (make_pixel): packed pixels, ONE tensor [H, W, C] ([N, H, W, C]; channels-last [N, 3, H, W]) through
-    `pixel_call(desc, scale, tensor, pixel, ptr, pitch, bstride, stream)`; bstride of one picture: the extent of its rows.
-    warp: None, or (abi.ExportWarp, abi.WarpMap array) of abi.warp_stage: size and filter belong to it, the calls get no scale and the
-    plan is hmgpu_export_warp_plan_for's."""
+                   pixel=None, alpha=None, memory_format=None, lut=None, chroma=None, warp=None):
+    """allocate with torch on `device` (or take `out`) and run `call(desc, stages, ptrs, pitches, bstrides, stream)` on torch's
+    current stream.  stages (Stages): scale None (size None), else the abi.ExportScale of size (height, width) and filter; tensor
+    None (dtype None), else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); windows None,
+    or the abi.ExportWindow of every picture (make_windows: `crop` is already part of them, so the descriptor's own crop is 0);
+    pixel from pixel / alpha / memory_format (make_pixel): packed pixels, ONE tensor [H, W, C] ([N, H, W, C]; channels-last
+    [N, 3, H, W]), the lists of its call one long, bstrides of one picture the extent of its rows; lut and chroma as given; warp
+    None, or (abi.ExportWarp, abi.WarpMap array) of abi.warp_stage: size and filter belong to it and the stages have no scale.
+    bstrides of planes: None for one picture (n None), else the bytes between the batch entries of every plane of the n pictures."""
     import torch
-    from . import export_pixels_plan, export_tensor_plan, export_warp_plan, export_windows_plan
+    from . import export_stages_plan
     if warp is not None:
         if layout_code(layout) != abi.EXPORT_RGB:
             raise ValueError("warp needs layout=\"rgb\"")
@@ -489,30 +506,20 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
     desc = make_desc(layout, bit_depth, crop if windows is None else (0, 0, 0, 0), matrix, full_range, msb_aligned,
                      seq if dtype is not None else None)
-    sc = make_scale(size, filter)
-    tensor = make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias)
-    if px is not None:
-        plan = (export_pixels_plan(seq, desc, sc, tensor, windows, px) if warp is None else
-                export_warp_plan(seq, desc, tensor, windows, px, None, None, warp[0], warp[1], n or 1))
-        with torch.cuda.device(device):
+    stages = Stages(make_scale(size, filter), make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias), windows, px,
+                    lut, chroma, warp)
+    plan = export_stages_plan(seq, desc, stages.shape_only(), n or 1)
+    with torch.cuda.device(device):
+        if px is not None:
             if out is None:
                 out = alloc_pixels(plan, desc, px, device, n, dtype, memory_format is not None)
             ptr, pitch, bstride = out_pixels(out, plan, desc, px, device, n, dtype)
-            if bstride is None:
-                bstride = pitch * (plan.height[0] - 1) + plan.row_bytes[0]
-            stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
-            pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, stream)
-        return out
-    if warp is not None:
-        plan = export_warp_plan(seq, desc, tensor, windows, None, None, None, warp[0], warp[1], n or 1)
-    else:
-        plan = export_tensor_plan(seq, desc, sc, tensor) if windows is None else export_windows_plan(seq, desc, sc, tensor, windows)
-    with torch.cuda.device(device):
-        if out is None:
-            out = alloc_outputs(plan, desc, device, n, dtype)
-        ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype)
-        stream = torch.cuda.current_stream(device).cuda_stream if on_stream else 0
-        call(desc, sc, tensor, ptrs, pitches, bstrides, stream)
+            ptrs, pitches, bstrides = [ptr], [pitch], [bstride] if bstride is not None else stage_extents(plan, [pitch])
+        else:
+            if out is None:
+                out = alloc_outputs(plan, desc, device, n, dtype)
+            ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype)
+        call(desc, stages, ptrs, pitches, bstrides, torch.cuda.current_stream(device).cuda_stream if on_stream else 0)
     return out
 
 

@@ -438,74 +438,54 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     (hmdec_pictures_export_colour); chroma / chroma_loc: "linear" goes through hmdec_pictures_export_chroma, with the first picture's
     VUI sample location for chroma_loc None; "replicate" through the entries it always took; warp / border / fill: one map per
     picture (abi.warp_stage) through hmdec_pictures_export_warp, whatever the other stages"""
-    from . import HmgpuError, export, export_tensor_plan, export_warp_plan
+    from . import export
     first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
+    count = n if not enqueue else len(pictures)
     chr_ = abi.chroma_stage(chroma, chroma_loc, first.chroma_loc()["top_field"])
-    wrp = abi.warp_stage(warp, size, filter, border, fill, n if not enqueue else len(pictures))
+    wrp = abi.warp_stage(warp, size, filter, border, fill, count)
     if isinstance(lut, str):
         if lut != "sdr":
             raise ValueError("lut: a colour LUT of the decoder, or \"sdr\"")
         depth = bit_depth if isinstance(bit_depth, int) else (bit_depth or (0, 0))[0]
         lut = _sdr_lut(first.ctx, export.vui_source(col["primaries"], col["transfer"]), depth or seq.bit_depth_luma) if enqueue else 0
-    handle = getattr(lut, "handle", lut)
-
-    def colour_call(desc, sc, tensor, px, ptrs, pitches, bstrides, st):
-        if wrp is not None:
-            r = lib().hmdec_pictures_export_warp(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(tensor),
-                                                 abi.window_array(win), abi.ref(px), handle or 0, abi.ref(chr_), C.byref(wrp[0]), wrp[1],
-                                                 abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
-            if r != 0:
-                raise HmgpuError(r, "hmdec_pictures_export_warp")
-            return
-        if chr_ is not None:
-            r = lib().hmdec_pictures_export_chroma(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
-                                                   abi.window_array(win), abi.ref(px), handle or 0, C.byref(chr_), abi.ptr_array(ptrs),
-                                                   abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
-            if r != 0:
-                raise HmgpuError(r, "hmdec_pictures_export_chroma")
-            return
-        r = lib().hmdec_pictures_export_colour(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
-                                               abi.window_array(win), abi.ref(px), handle, abi.ptr_array(ptrs), abi.i64_array(pitches),
-                                               abi.i64_array(bstrides), 1, abi.addr(st))
-        if r != 0:
-            raise HmgpuError(r, "hmdec_pictures_export_colour")
     matrix, full_range = export.resolve_colour(matrix, full_range, col["matrix"], col["full_range"])
-    dev = _device(first, "export")
-    win = export.make_windows(seq, crop, windows, flip, n if not enqueue else len(pictures))
+    return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                 _export_stages(pictures, seq, desc, stages, ptrs, pitches, bstrides, st) if enqueue else None,
+                                 seq, _device(first, "export"), layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter,
+                                 out, n, dtype, mean, std, scale, bias, export.make_windows(seq, crop, windows, flip, count), pixel=pixel,
+                                 alpha=alpha, memory_format=memory_format, lut=lut, chroma=chr_, warp=wrp)
 
-    def call(desc, sc, tensor, ptrs, pitches, bstrides, st):
-        if not enqueue:
-            return None
-        if tensor is None and bstrides is None and lut is None and chr_ is None and wrp is None:
-            return first.export_into(desc, ptrs, pitches, 1, st, sc)
-        if bstrides is None:                      # one picture, float elements: a batch of one, its stride the plane's extent
-            plan = (export_tensor_plan(seq, desc, sc, tensor) if wrp is None else
-                    export_warp_plan(seq, desc, tensor, win, None, None, None, wrp[0], wrp[1], 1))
-            bstrides = [pitches[k] * (plan.height[k] - 1) + plan.row_bytes[k] for k in range(plan.planes)]
-        if lut is not None or chr_ is not None or wrp is not None:
-            return colour_call(desc, sc, tensor, None, ptrs, pitches, bstrides, st)
-        head = (first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor))
-        tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(st))
-        if win is not None:
-            r, name = lib().hmdec_pictures_export_windows(*head, abi.window_array(win), *tail), "hmdec_pictures_export_windows"
-        else:
-            r, name = lib().hmdec_pictures_export(*head, *tail), "hmdec_pictures_export"
-        if r != 0:
-            raise HmgpuError(r, name)
 
-    def pixel_call(desc, sc, tensor, px, ptr, pitch, bstride, st):
-        if not enqueue:
-            return None
-        if lut is not None or chr_ is not None or wrp is not None:
-            return colour_call(desc, sc, tensor, px, [ptr], [pitch], [bstride], st)
-        r = lib().hmdec_pictures_export_pixels(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc), abi.ref(tensor),
-                                               abi.window_array(win), C.byref(px), abi.addr(ptr), pitch, bstride, 1, abi.addr(st))
-        if r != 0:
-            raise HmgpuError(r, "hmdec_pictures_export_pixels")
-    return export.export_tensors(call, seq, dev, layout, bit_depth, crop, matrix, full_range, msb_aligned, True, size, filter, out, n,
-                                 dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
-                                 pixel_call=pixel_call, warp=wrp)
+def _export_stages(pictures, seq, desc, stages, ptrs, pitches, bstrides, stream):
+    """the export of `stages` (export.Stages) on torch's stream `stream` through the narrowest hmdec_pictures_export* entry that
+    carries them, as libhm_amd.Context.export_stages_into chooses among hmgpu's.  bstrides None: one picture, through
+    hmdec_picture_export(_scaled) where it has integer elements and no further stage, else as a batch of one"""
+    from . import HmgpuError, export, export_stages_plan
+    s = stages
+    if bstrides is None:
+        if s[1:] == (None,) * 6:
+            return pictures[0].export_into(desc, ptrs, pitches, 1, stream, s.scale)
+        bstrides = export.stage_extents(export_stages_plan(seq, desc, s.shape_only(), 1), pitches)
+    head = (pictures[0].ctx, len(pictures), _handles(pictures), C.byref(desc))
+    mid = (abi.ref(s.scale), abi.ref(s.tensor), abi.window_array(s.windows), abi.ref(s.pixel))
+    tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(stream))
+    handle = getattr(s.lut, "handle", s.lut)
+    if s.warp is not None:
+        name, args = "hmdec_pictures_export_warp", head + mid[1:] + (handle or 0, abi.ref(s.chroma), C.byref(s.warp[0]), s.warp[1]) + tail
+    elif s.chroma is not None:
+        name, args = "hmdec_pictures_export_chroma", head + mid + (handle or 0, C.byref(s.chroma)) + tail
+    elif s.lut is not None:
+        name, args = "hmdec_pictures_export_colour", head + mid + (handle,) + tail
+    elif s.pixel is not None:
+        name, args = "hmdec_pictures_export_pixels", head + mid + (abi.addr(ptrs[0]), pitches[0], bstrides[0], 1, abi.addr(stream))
+    elif s.windows is not None:
+        name, args = "hmdec_pictures_export_windows", head + mid[:3] + tail
+    else:
+        name, args = "hmdec_pictures_export", head + mid[:2] + tail
+    r = getattr(lib(), name)(*args)
+    if r != 0:
+        raise HmgpuError(r, name)
 
 
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,

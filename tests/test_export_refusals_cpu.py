@@ -281,3 +281,99 @@ def test_residual_plan_sequence_before_everything():
     s, d, sc = _seq(2, 60, 48), _resid(), _scale(**NEAR)
     w, n = _wins([_win()])
     _refused(abi.ResidualPlan, lambda p: libhm_amd.lib().hmgpu_residual_plan_for(C.byref(s), C.byref(d), C.byref(sc), n, w, p), EINVAL)
+
+
+# ------------------------------------------------------------------------------------------------ a wider entry reproduces the narrower one
+# include/hmgpu.h: every wider plan entry validates what it shares with a narrower one "by the same code with the same statuses in the
+# same order".  Each wider entry is given the stages of a narrower one plus valid descriptors of its own, over a grid of inputs that
+# the narrower entry takes or refuses for every kind of reason: its answer is the narrower entry's refusal, else its own rule alone.
+GRID_DESCS = [dict(layout=RGB), dict(layout=RGB, matrix=2), dict(), dict(layout=RGB, crop=ODD_X),
+              dict(layout=RGB, bit_depth=(10, 10), bytes_per_sample=2)]
+GRID_SCALES = [None, dict(), TINY, dict(filter=9)]
+GRID_TENSORS = [None, dict(), dict(sample_type=9)]
+GRID_WINS = [None, [dict(crop=HALF), dict(crop=FULL)], [dict(crop=ODD_X)], [dict(crop=FULL), dict(crop=FULL, flip=2)],
+             [dict(crop=HALF), dict(crop=HALF, flip=1)]]
+GRID_PIXELS = [None, dict(), dict(order=99), dict(alpha=300)]
+TWO_SIZES = 1                                   # of GRID_WINS: the one list the warp entry, whose windows may differ in size, takes
+WARP_W, WARP_H = 40, 30
+
+
+def _plan_of(call):
+    plan = abi.ExportPlan()
+    C.memset(C.byref(plan), 0xFF, C.sizeof(plan))
+    return call(C.byref(plan)), bytes(plan)
+
+
+def _grid(fmt, scales):
+    """(case, seq, desc, scale, tensor, windows, n, pixel, the narrower entry's status and plan)"""
+    L = libhm_amd.lib()
+    s = _seq(fmt)
+    for di, dk in enumerate(GRID_DESCS):
+        for si, sk in enumerate(scales):
+            for ti, tk in enumerate(GRID_TENSORS):
+                for wi, wk in enumerate(GRID_WINS):
+                    for pi, pk in enumerate(GRID_PIXELS):
+                        d = _desc(**dk)
+                        sc, t = _scale(**sk) if sk is not None else None, _tensor(**tk) if tk is not None else None
+                        w, n = _wins(None if wk is None else [_win(**k) for k in wk])
+                        px = _pixel(**pk) if pk is not None else None
+                        if px is not None:
+                            base = _plan_of(lambda p: L.hmgpu_export_pixels_plan_for(C.byref(s), C.byref(d), _ref(sc), _ref(t), n, w, C.byref(px), p))
+                        elif w is not None:
+                            base = _plan_of(lambda p: L.hmgpu_export_windows_plan_for(C.byref(s), C.byref(d), _ref(sc), _ref(t), n, w, p))
+                        else:
+                            base = _plan_of(lambda p: L.hmgpu_export_tensor_plan_for(C.byref(s), C.byref(d), _ref(sc), _ref(t), p))
+                        yield (fmt, di, si, ti, wi, pi), s, d, sc, t, w, n, px, base
+
+
+def _own_rule(base, d, colour, chroma):
+    """what a colour and / or chroma entry answers where the narrower entry answered `base`: the colour rule first"""
+    st, plan = base
+    zero = bytes(len(plan))
+    if st != OK:
+        return st, zero
+    if d.layout != RGB:
+        return EINVAL, zero
+    if colour and (d.bit_depth[0] or 8) != 8:   # the LUT's depth is 8, the sequence's too
+        return EINVAL, zero
+    return OK, plan
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2, 3])
+def test_colour_and_chroma_plans_reproduce_the_narrower_entry(fmt):
+    L = libhm_amd.lib()
+    ld, ch = abi.make_colour_lut_desc(8, 17, False), abi.make_export_chroma(abi.CHROMA_LINEAR, 0)
+    bad, cases = [], 0
+    for case, s, d, sc, t, w, n, px, base in _grid(fmt, GRID_SCALES):
+        head = (C.byref(s), C.byref(d), _ref(sc), _ref(t), n, w, _ref(px))
+        got = {"colour": _plan_of(lambda p: L.hmgpu_export_colour_plan_for(*head, C.byref(ld), p)),
+               "chroma": _plan_of(lambda p: L.hmgpu_export_chroma_plan_for(*head, None, C.byref(ch), p)),
+               "both": _plan_of(lambda p: L.hmgpu_export_chroma_plan_for(*head, C.byref(ld), C.byref(ch), p))}
+        want = {"colour": _own_rule(base, d, True, False), "chroma": _own_rule(base, d, False, True), "both": _own_rule(base, d, True, True)}
+        bad += [(case, k, got[k][0], want[k][0]) for k in got if got[k] != want[k]]
+        cases += 1
+    assert cases == 1200 and not bad, bad[:10]
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2, 3])
+def test_warp_plan_reproduces_the_narrower_entry(fmt):
+    L = libhm_amd.lib()
+    ld, ch = abi.make_colour_lut_desc(8, 17, False), abi.make_export_chroma(abi.CHROMA_LINEAR, 0)
+    wp = abi.make_export_warp(WARP_W, WARP_H)
+    bad, cases = [], 0
+    for case, s, d, sc, t, w, n, px, base in _grid(fmt, [None]):
+        cases += 1
+        if case[4] == TWO_SIZES:
+            continue
+        maps = abi.warp_map_array([(65536, 0, 0, 0, 65536, 0)] * n)
+        for stages, colour in (((None, None), False), ((C.byref(ld), C.byref(ch)), True)):
+            st, plan = _plan_of(lambda p: L.hmgpu_export_warp_plan_for(C.byref(s), C.byref(d), _ref(t), n, w, _ref(px), *stages,
+                                                                       C.byref(wp), maps, p))
+            want = _own_rule(base, d, colour, colour)
+            if st != want[0] or (st != OK and plan != want[1]):
+                bad.append((case, colour, st, want[0]))
+            elif st == OK:
+                got, was = abi.ExportPlan.from_buffer_copy(plan), abi.ExportPlan.from_buffer_copy(base[1])
+                if got.planes != was.planes or any((got.width[k], got.height[k]) != (WARP_W, WARP_H) for k in range(got.planes)):
+                    bad.append((case, colour, "plan"))
+    assert cases == 300 and not bad, bad[:10]

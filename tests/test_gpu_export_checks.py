@@ -1,5 +1,5 @@
 """What the export side promises about its own bookkeeping, on the GPU: a destination check returns exactly the status the export
-gives the same destination (all five families), and the table slots of the scaled export give the same bits after an eviction as a
+gives the same destination (all eight families), and the table slots of the scaled export give the same bits after an eviction as a
 fresh context does.  What the other GPU tests hold of this: test_gpu_export_pixels has all four destination cases with the check
 next to the export; test_gpu_export_batch has the batch stride and the short allocation for the export and the batch stride for the
 check; test_gpu_export_windows the batch stride for the check; test_gpu_motion and test_gpu_residual the short allocation for both
@@ -42,6 +42,11 @@ def _families(ctx, pics, stream):
     mdesc = abi.make_motion_desc(abi.MOTION_BLOCKS, 3)
     rdesc = abi.make_residual_desc(abi.RESIDUAL_PLANES, 1)
     plane = W * H
+    axis = np.array([0, 255], np.uint16)
+    b, g, r = np.meshgrid(axis, axis, axis, indexing="ij")
+    lut = ctx.colour_lut(np.stack([r, g, b], axis=-1), None, 8)          # the identity, two nodes per axis
+    chroma = abi.make_export_chroma(abi.CHROMA_LINEAR, 0)
+    warp = (abi.make_export_warp(W, H), abi.warp_map_array([(65536, 0, 0, 0, 65536, 0)] * n))
 
     def planes(base, pitch, bstride):                # R and G of a picture side by side, then every picture's B: its pitch and batch stride vary
         ptrs = [None if base is None else base + k * plane for k in (0, 1, 2 * n)]
@@ -61,6 +66,21 @@ def _families(ctx, pics, stream):
         return (ctx.export_pixels_destination_status(n, rgb, px, base, pitch, bstride),
                 _status(lambda: ctx.export_pixels_into(pics, rgb, px, base, pitch, bstride, 1, stream)))
 
+    def colour(base, pitch, bstride):
+        a = planes(base, pitch, bstride)
+        return (ctx.export_colour_destination_status(n, rgb, lut, *a),
+                _status(lambda: ctx.export_colour_into(pics, rgb, lut, *a, 1, stream)))
+
+    def chroma_(base, pitch, bstride):
+        a = planes(base, pitch, bstride)
+        return (ctx.export_chroma_destination_status(n, rgb, chroma, *a),
+                _status(lambda: ctx.export_chroma_into(pics, rgb, chroma, *a, 1, stream)))
+
+    def warp_(base, pitch, bstride):
+        a = planes(base, pitch, bstride)
+        return (ctx.export_warp_destination_status(n, rgb, warp, *a),
+                _status(lambda: ctx.export_warp_into(pics, rgb, warp, *a, 1, stream)))
+
     def motion(base, pitch, bstride):                # ref_poc alone: int32 [n, 2, 16, 16]
         a = ([None, None, base, None], [0, 0, pitch, 0], [0, 0, 16 * 16 * 4, 0], [0, 0, bstride, 0])
         return (ctx.motion_destination_status(n, mdesc, *a),
@@ -73,11 +93,12 @@ def _families(ctx, pics, stream):
 
     # name: (both statuses, bytes of n pictures, the pitch, the batch stride)
     return {"batch": (batch, n * 3 * plane, W, plane), "windows": (windows, n * 3 * plane, W, plane),
-            "pixels": (pixels, n * plane * 4, W * 4, plane * 4), "motion": (motion, n * 2 * 16 * 16 * 4, 16 * 4, 2 * 16 * 16 * 4),
+            "pixels": (pixels, n * plane * 4, W * 4, plane * 4), "colour": (colour, n * 3 * plane, W, plane),
+            "chroma": (chroma_, n * 3 * plane, W, plane), "warp": (warp_, n * 3 * plane, W, plane), "motion": (motion, n * 2 * 16 * 16 * 4, 16 * 4, 2 * 16 * 16 * 4),
             "residual": (residual, n * plane * 2, W * 2, plane * 2)}
 
 
-@pytest.mark.parametrize("family", ["batch", "windows", "pixels", "motion", "residual"])
+@pytest.mark.parametrize("family", ["batch", "windows", "pixels", "colour", "chroma", "warp", "motion", "residual"])
 def test_destination_status_is_the_exports_status(family):
     """a destination that fits exactly, then a null pointer, a pitch one byte short, a batch stride one byte short, and an allocation
     that ends one byte before the last slot does: the check and the export agree every time, and a refusal writes nothing"""
