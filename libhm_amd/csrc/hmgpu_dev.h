@@ -189,10 +189,12 @@ struct Batch {
 // everything the motion-compensation kernels need about a batch, in kernel-argument memory: nothing stands between a workgroup's
 // start and the load of its tile records (k_mc.hip).  Filled by the host from its mirrors of the PicDev descriptors.
 struct McArgs {
-  int32_t n, mode, log2n, per;                 // pictures of the batch; grid mapping (launch_mc)
+  int32_t n, mode, log2n, pad0_;               // pictures of the batch; grid mapping (launch_mc)
   int32_t width, height, log2ctu, ctus_w;      // geometry (the same for every picture of a context)
   int32_t tw, pitch, bd, npics;                // TileMv grid width; pitch / bit depth of the component; entries of finals[]
-  int32_t first_ctu[kMaxBatch], num_ctus[kMaxBatch];
+  int32_t first_ctu[kMaxBatch], num_ctus[kMaxBatch];   // the call's CTU range per picture (what launch_mc reads)
+  // per blockIdx.x, precomputed by launch_mc: the raster range of CTUs that index walks (first CTU, count) and the CTU row it starts in
+  int32_t walk_lo[kMaxBatch], walk_n[kMaxBatch], walk_row[kMaxBatch];
   const TileMv* tmv[kMaxBatch];
   int16_t* dst[kMaxBatch];                     // luma: the picture's reconstruction plane; chroma: Cb
   int16_t* dst2[kMaxBatch];                    // chroma: Cr
@@ -250,6 +252,9 @@ __device__ inline BlkInfo ld_blk(const BlkInfo* p) { return __builtin_bit_cast(B
 // with its own L2.  For a batch of n pictures with nb workgroups each, picture p is served by the XCDs x with
 // x % n == p and each of those XCDs walks one contiguous band of the picture in raster order, so that neighbouring
 // tiles (which share reference-picture rows) hit in the same L2.  Returns false for padding workgroups.
+// (The motion-compensation launches keep this assignment but walk an XCD's range in bands of CTU columns: launch_mc, k_mc.hip.  The
+// same order inside this function's range was measured on k_filter_fused, whose halo is 5 % of its reads, and did not pay:
+// EXPERIMENTS.md round 8.)
 __device__ inline bool xcd_remap(int bid, int n, int nb, int& slot, int& lb) {
   if (n < 0) { n = -n; slot = bid % n; lb = bid / n; return lb < nb; }     // tuning knob: plain interleave
   if (n <= 8 && (8 % n) == 0) {

@@ -132,14 +132,24 @@ template <bool CHROMA> struct McLds {
 #endif
 };
 
-struct Square { int sx, sy, ext; };                           // luma origin, extent (min(CTU size, 64)) of the square
+// CTU columns of a band of the walk (launch_mc).  Narrow bands bring the squares that share reference lines close together; every band
+// border costs the columns within 71 samples of it a second fetch, (64 W + 142) / 64 W of the reference traffic.  Measured on the
+// 2160p P step (60 CTU columns), ms per step, medians of three alternating rounds (EXPERIMENTS.md round 8): one call raster order
+// 0.6849, W = 15 0.6744, 20 0.6756, 30 0.6784; another W = 10 0.6539, 12 0.6586, 15 0.6521.  15 was the fastest in every round of
+// both calls, and it divides the 60 and 30 columns of 2160p and 1080p pictures: no band is padding there.
+constexpr int kBandW = 15;
+struct Square { int sx, sy, ext; };                    // luma origin, extent (min(CTU size, 64)) of the square
+// The walk of launch_mc: blockIdx.x owns one raster range of CTUs (McArgs::walk_*), blockIdx.z is the band of kBandW CTU columns,
+// blockIdx.y the position inside the band, row by row.  Scalar arithmetic on kernel arguments only (the one division is by a
+// constant); a workgroup whose position lies outside the picture or outside the range pads the band and leaves before any load.
 __device__ inline bool square_of_block(const McArgs& a, int& slot, Square& g) {
-  int lb;
-  if (a.mode) { slot = blockIdx.x & (a.n - 1); lb = (int)(blockIdx.x >> a.log2n) * a.per + (int)blockIdx.y; }
-  else { slot = blockIdx.x; lb = blockIdx.y; }
-  if (lb >= a.num_ctus[slot]) return false;
-  const int ctu = a.first_ctu[slot] + lb, ctu_sz = 1 << a.log2ctu;
-  g.sx = (ctu % a.ctus_w) * ctu_sz; g.sy = (ctu / a.ctus_w) * ctu_sz; g.ext = min(ctu_sz, 64);
+  const int x = blockIdx.x;
+  slot = a.mode ? x & (a.n - 1) : x;
+  const int brow = (int)(blockIdx.y / (unsigned)kBandW), col = (int)blockIdx.z * kBandW + ((int)blockIdx.y - brow * kBandW);
+  const int row = a.walk_row[x] + brow;
+  const int lb = row * a.ctus_w + col - a.walk_lo[x];          // position in the range, raster order
+  if (col >= a.ctus_w || (unsigned)lb >= (unsigned)a.walk_n[x]) return false;
+  g.sx = col << a.log2ctu; g.sy = row << a.log2ctu; g.ext = min(1 << a.log2ctu, 64);
   return true;
 }
 
@@ -761,18 +771,30 @@ __global__ void __launch_bounds__(256, (WP && BI) ? 6 : MC_LB_CHROMA) k_mc_chrom
 }
 
 // grid: the blocks of one picture run on the XCDs x with x % n == picture (each XCD has its own L2; workgroups are dealt
-// round-robin to the 8 XCDs in dispatch order, x fastest), walking the picture's squares in raster order: the order of
-// xcd_remap(), without its divisions.  mode 1: blockIdx.x = XCD, blockIdx.y = position inside the XCD's band; mode 0: blockIdx.x = picture
+// round-robin to the 8 XCDs in dispatch order, x fastest): the assignment of xcd_remap(), without its divisions.  mode 1:
+// blockIdx.x = XCD, which owns one contiguous raster range of the picture's CTUs (the m-th part of the call's range when 8 / n = m
+// XCDs serve a picture); mode 0: blockIdx.x = picture, the range is the call's.  A range is NOT walked in raster order but in
+// vertical bands of kBandW CTU columns, top to bottom inside a band (blockIdx.y), band after band (blockIdx.z): squares above one
+// another, which want the same reference lines, are kBandW workgroups apart instead of a picture's width, so the line is still in
+// L2 when the second one asks.  Every range gets the grid of the tallest one, over the whole width of the picture: what lies
+// outside a range (it starts and ends in the middle of a CTU row) or beyond the last column is padding (square_of_block).
 template <typename K>
 static void launch_mc(K kernel, McArgs& a, int max_ctus, hipStream_t s) {
-  a.mode = 0; a.log2n = 0; a.per = 0;
-  dim3 grid((unsigned)a.n, (unsigned)max_ctus);
+  a.mode = 0; a.log2n = 0;
+  int nx = a.n, m = 1;
   if (a.n <= 8 && (8 % a.n) == 0) {
-    const int m = 8 / a.n;
-    a.mode = 1; a.per = (max_ctus + m - 1) / m;
+    m = 8 / a.n; nx = 8; a.mode = 1;
     while ((1 << a.log2n) < a.n) a.log2n++;
-    grid = dim3(8u, (unsigned)a.per);
   }
+  const int per = (max_ctus + m - 1) / m;
+  int rows = 1;
+  for (int x = 0; x < nx; x++) {
+    const int slot = a.mode ? x & (a.n - 1) : x, lo = a.first_ctu[slot] + (a.mode ? x >> a.log2n : 0) * per;
+    const int cnt = std::max(0, std::min(per, a.first_ctu[slot] + a.num_ctus[slot] - lo));
+    a.walk_lo[x] = lo; a.walk_n[x] = cnt; a.walk_row[x] = lo / a.ctus_w;
+    if (cnt > 0) rows = std::max(rows, (lo + cnt - 1) / a.ctus_w - lo / a.ctus_w + 1);
+  }
+  const dim3 grid((unsigned)nx, (unsigned)(kBandW * rows), (unsigned)((a.ctus_w + kBandW - 1) / kBandW));
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a);
 }
 // buffer-load windows while every byte of the slab of pictures has a 32-bit offset below kWinLimit (57 pictures of 3840x2160), plain addresses beyond
