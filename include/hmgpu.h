@@ -657,6 +657,85 @@ hmgpu_status hmgpu_export_warp_destination_check(hmgpu_ctx* ctx, int32_t n, cons
                                                  const hmgpu_warp_map maps[], void* const dst[3], const int64_t pitch_bytes[3],
                                                  const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ format export
+ * The planar and semi-planar layouts with Cb and Cr at a chroma format the caller chooses, where the calls above
+ * write them at the picture's own: three full-resolution planes from a 4:2:0 stream, NV12 / P010 from a 4:2:2 or 4:4:4 one.
+ * TVideoIOYuv::writePlane has the operation (fileFormat != srcFormat, TVideoIOYuv.cpp:362-483); its REPLICATE / DROP forms are
+ * writePlane's index arithmetic, the LINEAR ones interpolate and decimate at the signalled sample location.  Integer arithmetic that
+ * tests/export_format_ref.py restates exactly.
+ *
+ * Luma is written exactly as hmgpu_pictures_export(_windows) writes it.  Chroma is decided per axis, by comparing the subsampling of
+ * the source format with that of `chroma_format`; no conversion gains samples on one axis and loses them on the other.  With C one
+ * chroma component of the decoded picture (the whole decoded plane, not the crop or window) and j the output chroma index on the axis:
+ *   same on the axis      the sample j itself, weight 4
+ *   gain, REPLICATE       sample j >> 1, weight 4 (writePlane's src[x >> sx]; rows by the same rule -- writePlane's own row pointer runs
+ *                         one row ahead on odd rows there, a path HM's applications never take)
+ *   gain, LINEAR          the two taps of the table in "chroma export" for the luma coordinate j, with the siting of `loc`; a 4:2:2
+ *                         source or output is horizontally co-sited whatever loc says.  4:2:0 -> 4:4:4 gives exactly the c' of that
+ *                         section, 4:2:0 -> 4:2:2 uses its vertical taps only, 4:2:2 -> 4:4:4 its horizontal ones only
+ *   loss, DROP            sample 2j, weight 4 (writePlane's src[x << sx], a row written only when (y444 & mask) == 0); loc is ignored
+ *   loss, LINEAR          taps in quarters around j by the siting of the axis:
+ *                           co-sited (horizontal loc 0, 2, 4 and every 4:2:2 output; vertical loc 2, 3)    (2j - 1: 1, 2j: 2, 2j + 1: 1)
+ *                           centred (horizontal loc 1, 3, 5; vertical loc 0, 1)                           (2j: 2, 2j + 1: 2)
+ *                           co-sited with the odd row (vertical loc 4, 5)                                 (2j: 1, 2j + 1: 2, 2j + 2: 1)
+ * The converted value, at the coding chroma depth, is
+ *   c = (sum over the taps of wx * wy * C[iy][ix] + 8) >> 4
+ * with tap indices clamped to the decoded plane, 0 .. size - 1, so that the export of a window is the window of the whole picture's
+ * export.  The decimation taps are the inverses in siting of the interpolation ones: a constant plane stays constant, and REPLICATE
+ * followed by DROP returns the plane unchanged.  A 4:0:0 source with any other output writes Cb = Cr = 1 << (D - 1), D the chroma
+ * output depth (writePlane's `value`, TVideoIOYuv.cpp:387); output 4:0:0 writes Y only, one plane; an output format equal to the
+ * source's writes bit for bit what hmgpu_pictures_export / _windows writes.  The converted sample takes the place of the decoded
+ * one in everything the two layouts do afterwards: the bit-depth rule, msb_aligned, the float map, the mirror, the CbCr interleave
+ * (NV12 / NV16 / NV24, P010 / P016).
+ *
+ * With `scale`: Y is resampled as hmgpu_pictures_export resamples it; Cb / Cr are resampled straight from the cropped source chroma
+ * plane to (width >> csx_out) x (height >> csy_out) with the table rule of plane class 1 ("scaled export": in = the cropped source
+ * chroma size, out = that size, half-sample centres), each axis within the 32x / 8x limits.  up / down / loc are validated and then
+ * unused.  A 4:0:0 source still gives the constant.  hmgpu_export_format_scale_taps reports these tables.
+ *
+ * Validation, in this order, everything before anything is enqueued and a refused call leaving the destination untouched:
+ *   1. the rules of the matching existing call (hmgpu_pictures_export_windows; windows NULL: hmgpu_pictures_export), in their order
+ *      -- semi-planar float elements stay HMGPU_EUNSUPPORTED;
+ *   2. the RGB layout: HMGPU_EINVAL;
+ *   3. `format` NULL, a non-zero reserved word, chroma_format outside 0 .. 3 or loc outside 0 .. 5: HMGPU_EINVAL; a 4:0:0 source
+ *      whose chroma output depth the matching call did not have to look at (1 .. 16, within the container; float elements: the
+ *      container the depths need): HMGPU_EINVAL;
+ *   4. an unknown `up` or `down`: HMGPU_EUNSUPPORTED;
+ *   5. a crop or window whose left / top edge or size, or a scaled output size, does not cover whole chroma samples of the output
+ *      format as well: HMGPU_EINVAL; (scaled) a chroma axis beyond the scaling limits: HMGPU_EUNSUPPORTED;
+ *   6. the destination against the plan of the output format.
+ * One launch per call (a scaled call from a 4:0:0 source: two); the stream ordering, the table slots and the window ring of the
+ * existing calls; not accounted in hmgpu_stats. */
+enum { HMGPU_DOWN_DROP = 0, HMGPU_DOWN_LINEAR = 1 };
+typedef struct hmgpu_export_format {
+  int32_t chroma_format;       /* output: 0 4:0:0, 1 4:2:0, 2 4:2:2, 3 4:4:4 */
+  int32_t up;                  /* HMGPU_CHROMA_REPLICATE | HMGPU_CHROMA_LINEAR, where an axis gains samples */
+  int32_t down;                /* HMGPU_DOWN_*, where an axis loses samples */
+  int32_t loc;                 /* chroma_sample_loc_type 0 .. 5 of the 4:2:0 side of the conversion */
+  int32_t reserved[4];         /* 0 */
+} hmgpu_export_format;
+/* the plan of the output format: the plane sizes of `format`->chroma_format (semi-planar: plane 1 in CbCr pairs, row_bytes of both
+ * components); windows NULL: the plan of desc's crop (n ignored); host code, no device needed */
+hmgpu_status hmgpu_export_format_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                          const hmgpu_export_tensor* tensor, int32_t n, const hmgpu_export_window windows[],
+                                          const hmgpu_export_format* format, hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_format(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                          const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                          const hmgpu_export_window windows[], const hmgpu_export_format* format, void* const dst[3],
+                                          const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream,
+                                          void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_format: the status it would give these arguments; enqueues nothing */
+hmgpu_status hmgpu_export_format_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                                   const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_format* format, void* const dst[3], const int64_t pitch_bytes[3],
+                                                   const int64_t batch_stride_bytes[3]);
+/* hmgpu_export_scale_taps for a scaled format export of desc's crop: the table of plane class `chroma` and `axis` as that export
+ * uses it (class 1: from the cropped source chroma size to the output format's).  No chroma class where the source or the output
+ * is 4:0:0 (HMGPU_EINVAL). */
+hmgpu_status hmgpu_export_format_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_scale* scale,
+                                            const hmgpu_export_format* format, int32_t chroma, int32_t axis, int32_t max_taps,
+                                            int32_t* first, int32_t* count, int16_t* weights);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

@@ -140,6 +140,20 @@ def lib():
                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                             C.POINTER(abi.ExportPixel), C.c_int64, C.POINTER(abi.ExportChroma),
                                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_export_format_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                   C.POINTER(abi.ExportTensor), C.c_int32, C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportFormat), C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_format.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                   C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                   C.POINTER(abi.ExportFormat), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_format_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                            C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                            C.POINTER(abi.ExportFormat), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                            C.POINTER(C.c_int64)]
+        L.hmgpu_export_format_scale_taps.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                     C.POINTER(abi.ExportFormat), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int16)]
         L.hmgpu_export_warp_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportTensor), C.c_int32,
                                                  C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel), C.POINTER(abi.ColourLutDesc),
                                                  C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
@@ -320,6 +334,42 @@ def export_chroma_plan(seq, desc, scale, tensor, windows, pixel, lut_desc, chrom
     return plan
 
 
+def export_format_status(seq, desc, scale, tensor, windows, format, n=None):
+    """(status, plan) of hmgpu_export_format_plan_for (host code, no GPU): the planes of format.chroma_format; windows None: the
+    plan of desc's crop; format: an abi.ExportFormat or None; n: another count than len(windows)"""
+    plan = abi.ExportPlan()
+    windows = list(windows) if windows is not None else None
+    if n is None:
+        n = len(windows) if windows is not None else 1
+    st = lib().hmgpu_export_format_plan_for(C.byref(seq), C.byref(desc), abi.ref(scale), abi.ref(tensor), n, abi.window_array(windows),
+                                            abi.ref(format), C.byref(plan))
+    return st, plan
+
+
+def export_format_plan(seq, desc, scale, tensor, windows, format):
+    """what a format export writes per slot: export_format_status, a refusal raised"""
+    st, plan = export_format_status(seq, desc, scale, tensor, windows, format)
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_format_plan_for")
+    return plan
+
+
+def export_format_scale_taps(seq, desc, scale, format, chroma, axis):
+    """(first, count, weights[out, taps]) of one resampling table of a scaled format export (hmgpu_export_format_scale_taps):
+    export_scale_taps with plane class 1 going from the cropped source chroma plane to the output format's chroma size"""
+    import numpy as np
+    plan = export_format_plan(seq, desc, scale, None, None, format)
+    out = (plan.width, plan.height)[axis][1 if chroma else 0]
+    taps = max(plan.coef[12 + axis], 1)
+    first, count, w = np.zeros(out, np.int32), np.zeros(out, np.int32), np.zeros((out, taps), np.int16)
+    st = lib().hmgpu_export_format_scale_taps(C.byref(seq), C.byref(desc), C.byref(scale), abi.ref(format), chroma, axis, taps,
+                                              first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              w.ctypes.data_as(C.POINTER(C.c_int16)))
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_format_scale_taps")
+    return first, count, w
+
+
 def export_warp_status(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, maps, n=None):
     """(status, plan) of hmgpu_export_warp_plan_for (host code, no GPU): the plan of the matching planar or packed call with every
     plane warp.width x warp.height.  warp: an abi.ExportWarp or None; maps: an abi.WarpMap array (abi.warp_map_array) or None;
@@ -348,6 +398,8 @@ def export_stages_plan(seq, desc, stages, n=None):
     s, ld = stages, stages.lut
     if ld is not None and not isinstance(ld, abi.ColourLutDesc):
         ld = abi.make_colour_lut_desc(ld.depth, ld.size, ld.has_shaper) if hasattr(ld, "has_shaper") else None
+    if s.format is not None:
+        return export_format_plan(seq, desc, s.scale, s.tensor, s.windows, s.format)
     if s.warp is not None:
         return export_warp_plan(seq, desc, s.tensor, s.windows, s.pixel, ld, s.chroma, s.warp[0], s.warp[1], n)
     if s.chroma is not None:
@@ -676,6 +728,20 @@ class Context:
                                                            abi.ref(pixel), getattr(lut, "handle", lut) or 0, abi.ref(chroma),
                                                            abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides))
 
+    def export_format_into(self, pics, desc, format, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
+        """hmgpu_pictures_export_format into device memory the caller owns: export_batch_into with Cb / Cr at the chroma format of
+        `format`, an abi.ExportFormat"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_format(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale), abi.ref(tensor),
+                                                     abi.window_array(windows), abi.ref(format), abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                                     abi.i64_array(bstrides), on_stream, abi.addr(stream)), "hmgpu_pictures_export_format")
+
+    def export_format_destination_status(self, n, desc, format, ptrs, pitches, bstrides, scale=None, tensor=None, windows=None):
+        """hmgpu_export_format_destination_check: the status hmgpu_pictures_export_format would give; enqueues nothing"""
+        return lib().hmgpu_export_format_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
+                                                           abi.ref(format), abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                                           abi.i64_array(bstrides))
+
     def export_warp_into(self, pics, desc, warp, ptrs, pitches, bstrides, on_stream=0, stream=0, tensor=None, windows=None, pixel=None,
                          lut=None, chroma=None):
         """hmgpu_pictures_export_warp into device memory the caller owns: export_chroma_into without a scale (chroma None: replicate),
@@ -708,15 +774,17 @@ class Context:
 
     def export_stages_into(self, pics, desc, stages, ptrs, pitches, bstrides, on_stream=0, stream=0):
         """the export of `stages` (export.Stages) into device memory the caller owns, through the narrowest hmgpu_pictures_export*
-        entry that carries them: warp, else chroma, else colour, else pixels (ptrs[0] / pitches[0] / bstrides[0] the one destination),
+        entry that carries them: format (the YUV layouts at another chroma format), else warp, else chroma, else colour, else pixels (ptrs[0] / pitches[0] / bstrides[0] the one destination),
         else windows or the plain batch -- the only ones that take a YUV layout.  bstrides None: one picture, through
         hmgpu_picture_export(_scaled) where it has integer elements and no further stage, else as a batch of one"""
         s = stages
         if bstrides is None:
-            if s[1:] == (None,) * 6:
+            if s[1:] == (None,) * 7:
                 return self.export_into(pics[0], desc, ptrs, pitches, on_stream, stream, s.scale)
             from . import export
             bstrides = export.stage_extents(export_stages_plan(self.seq, desc, s.shape_only(), 1), pitches)
+        if s.format is not None:
+            return self.export_format_into(pics, desc, s.format, ptrs, pitches, bstrides, on_stream, stream, s.scale, s.tensor, s.windows)
         if s.warp is not None:
             return self.export_warp_into(pics, desc, s.warp, ptrs, pitches, bstrides, on_stream, stream, s.tensor, s.windows, s.pixel, s.lut, s.chroma)
         if s.chroma is not None:
@@ -730,7 +798,7 @@ class Context:
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
-               lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None):
+               lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop"):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
         gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
@@ -740,20 +808,23 @@ class Context:
         chroma_sample_loc_type 0 .. 5 (None: 0), before the matrix (hmgpu_pictures_export_chroma).
         warp (layout "rgb"): one inverse affine map of six Q16 ints (export.affine_map, export.orientation_map), as export_batch
         takes one per picture; size is then required and is the output size, filter "bilinear" or "nearest", border "edge" or "fill"
-        with fill=(r, g, b) (hmgpu_pictures_export_warp)"""
+        with fill=(r, g, b) (hmgpu_pictures_export_warp).
+        chroma_format (layouts "planar" / "semiplanar"): None, or "400" / "420" / "422" / "444" (0 .. 3) -- Cb and Cr at that chroma
+        format (hmgpu_pictures_export_format), as export_batch describes; planar with "444" returns ONE [3, H, W] tensor"""
         from . import export
         os_ = 1 if on_stream else 0
+        fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc)
         return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
                                      self.export_stages_into([pic], desc, stages, ptrs, pitches, bstrides, os_, st),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, None, dtype, mean, std, scale, bias, pixel=pixel, alpha=alpha, lut=lut,
-                                     chroma=abi.chroma_stage(chroma, chroma_loc),
-                                     warp=abi.warp_stage(export.one_map(warp), size, filter, border, fill, 1))
+                                     chroma=abi.chroma_stage(chroma, chroma_loc) if fmt is None else None,
+                                     warp=abi.warp_stage(export.one_map(warp), size, filter, border, fill, 1), format=fmt)
 
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
                      pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge",
-                     fill=None):
+                     fill=None, chroma_format=None, chroma_down="drop"):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -777,17 +848,27 @@ class Context:
         (export.affine_map, export.random_affine, export.orientation_map) -- rotation, shear, zoom, sub-sample shifts and the display
         orientations, still in the one launch (hmgpu_pictures_export_warp).  size is then required and is the output size; the
         windows, the source of each map, may differ in size; filter "bilinear" or "nearest"; border "edge", or "fill" with
-        fill=(r, g, b) code values of the output depth.  There is no prefilter: resize by more than about 2x with size= alone."""
+        fill=(r, g, b) code values of the output depth.  There is no prefilter: resize by more than about 2x with size= alone.
+        chroma_format (layouts "planar" / "semiplanar"; with size, windows, flip, dtype and out): None -- Cb and Cr at the picture's
+        own chroma format, through the entries above -- or "400" / "420" / "422" / "444" (0 .. 3): at that format
+        (hmgpu_pictures_export_format), still one launch.  Where an axis gains samples chroma= decides: "replicate", or "linear" at
+        chroma_loc as for layout "rgb"; where it loses them chroma_down= does: "drop" (every second sample), or "linear" (taps in
+        quarters at the same sample location).  4:0:0 pictures give Cb = Cr = half scale, "400" gives Y alone.  The planar layout
+        with "444" returns ONE [N, 3, H, W] tensor, Y, Cb and Cr its channels (dtype / mean / std per channel) -- the input of a
+        model that takes Y'CbCr; every other case the tuples of the YUV layouts with the new chroma shapes (semi-planar "420" is
+        NV12 / P010).  With size= chroma is resampled straight to the output format's chroma size and chroma / chroma_down /
+        chroma_loc have no part."""
         from . import export
         pics = list(pics)
+        fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         os_ = 1 if on_stream else 0
         return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
                                      self.export_stages_into(pics, desc, stages, ptrs, pitches, bstrides, os_, st),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
-                                     lut=lut, chroma=abi.chroma_stage(chroma, chroma_loc),
-                                     warp=abi.warp_stage(warp, size, filter, border, fill, len(pics)))
+                                     lut=lut, chroma=abi.chroma_stage(chroma, chroma_loc) if fmt is None else None,
+                                     warp=abi.warp_stage(warp, size, filter, border, fill, len(pics)), format=fmt)
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

@@ -193,6 +193,40 @@ def chroma_stage(chroma, chroma_loc, default_loc=0):
     return make_export_chroma(chroma, default_loc if chroma_loc is None else chroma_loc)
 
 
+DOWN_DROP, DOWN_LINEAR = 0, 1
+DOWN_FILTERS = {"drop": DOWN_DROP, "linear": DOWN_LINEAR}
+CHROMA_FORMATS = {"400": 0, "420": 1, "422": 2, "444": 3}
+
+
+class ExportFormat(C.Structure):
+    _fields_ = [("chroma_format", C.c_int32), ("up", C.c_int32), ("down", C.c_int32), ("loc", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def make_export_format(chroma_format, up=CHROMA_REPLICATE, down=DOWN_DROP, loc=0):
+    """chroma_format: 0 .. 3 or "400" / "420" / "422" / "444"; up: CHROMA_* or its name; down: DOWN_* or its name; loc:
+    chroma_sample_loc_type 0 .. 5 of the 4:2:0 side of the conversion"""
+    f = ExportFormat()
+    f.chroma_format = int(CHROMA_FORMATS.get(chroma_format, chroma_format))
+    f.up, f.down, f.loc = int(CHROMA_FILTERS.get(up, up)), int(DOWN_FILTERS.get(down, down)), int(loc)
+    return f
+
+
+def format_stage(chroma_format, chroma, chroma_down, chroma_loc, default_loc=0):
+    """chroma_format= / chroma= / chroma_down= / chroma_loc= of the Python exports: None for chroma_format None (the existing
+    entries), else the ExportFormat of the format export; chroma_loc None: default_loc"""
+    if chroma_format is None:
+        if chroma_down != "drop":
+            raise ValueError("chroma_down needs chroma_format=")
+        return None
+    if not isinstance(chroma_format, int) and chroma_format not in CHROMA_FORMATS:
+        raise ValueError("chroma_format: None, 0 .. 3 or one of %s" % sorted(CHROMA_FORMATS))
+    if chroma not in CHROMA_FILTERS:
+        raise ValueError("chroma: one of %s" % sorted(CHROMA_FILTERS))
+    if chroma_down not in DOWN_FILTERS:
+        raise ValueError("chroma_down: one of %s" % sorted(DOWN_FILTERS))
+    return make_export_format(chroma_format, chroma, chroma_down, default_loc if chroma_loc is None else chroma_loc)
+
+
 WARP_NEAREST, WARP_BILINEAR = 0, 1
 WARP_EDGE, WARP_FILL = 0, 1
 WARP_FILTERS = {"nearest": WARP_NEAREST, "bilinear": WARP_BILINEAR}

@@ -487,6 +487,26 @@ struct ChromaSite {
 // the RGB layout of `a` with the chroma stage, and with the colour stage as well where lut is not null
 void launch_export_chroma(const ExportArgs& a, const ChromaSite& cs, const ColourLut* lut, hipStream_t s);
 void launch_export_px_chroma(const ExportArgs& a, const PxOrder& po, const ChromaSite& cs, const ColourLut* lut, int nch, hipStream_t s);
+// format export (k_export_fmt.hip, hmgpu_pictures_export_format; include/hmgpu.h "format export"): the chroma rows of the YUV layouts
+// read the pair plane of the source format and write one of another.  ExportArgs as launch_export takes it, with cw / ch the OUTPUT
+// chroma size (csx / csy stay the source's).  A class per shape of the loads; the host's weights make REPLICATE and DROP exact in the
+// same instances (a single weight 4 per axis: (4 * 4 * C + 8) >> 4 = C).
+enum {
+  kFmtConst = 0,                   // 4:0:0 source: Cb = Cr = constant, no loads
+  kFmtUp = 1,                      // the horizontal axis gains (the vertical one gains or stays): chroma_core.h with cs's weights
+  kFmtVert = 2,                    // the horizontal axis stays, the vertical one gains or loses: the group on one to three rows
+  kFmtDown = 3                     // the horizontal axis loses (the vertical one loses or stays): 8 pairs and the one left of them, one to three rows
+};
+struct FmtConv {
+  ChromaSite cs;                   // kFmtUp: the weights of the horizontal axis (hx) and of a vertical gain (vy).  Every class: wc / hc, the decoded
+                                   // source chroma plane, and x0 / y0 per picture, the source chroma sample ExportArgs::c points at
+  int32_t cls;                     // kFmt*
+  int32_t vgain, vloss;            // the vertical axis gains / loses samples (neither: it stays)
+  int32_t dv0, dv[3];              // vertical loss: the first row relative to 2j (-1 / 0) and the weights of rows dv0, dv0 + 1, dv0 + 2
+  int32_t dh[3];                   // kFmtDown: the weights of source columns 2j - 1, 2j, 2j + 1
+  int32_t constant;                // kFmtConst: the sample at the chroma output depth
+};
+void launch_export_fmt(const ExportArgs& a, const FmtConv& f, hipStream_t s);
 // scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
 // memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
 // tap-major (w[tap * n + i], zero beyond count[i])

@@ -1,5 +1,6 @@
 // hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
-// slots, window tables, colour LUTs, the rules and weights of the chroma stage and the rules of the warp; ExportReq, the stages of one
+// slots, window tables, colour LUTs, the rules and weights of the chroma stage, the weights and rules of the format export and the
+// rules of the warp; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
 // destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block
 // and residual exports and the reference planes of the picture metrics, the picture histograms (k_export.hip, k_export_px.hip,
@@ -307,17 +308,34 @@ bool scale_sums_fit(const ScaleTab& x, const ScaleTab& y, int D, int E) {
   return vmax <= INT32_MAX && vmin >= INT32_MIN;
 }
 
+// a YUV plan at the output chroma format fo of a format export: the chroma planes and their sizes from plane 0's
+void plan_set_format(const hmgpu_export_desc* d, int fo, hmgpu_export_plan* out) {
+  int osx, osy;
+  chroma_shifts(fo, &osx, &osy);
+  const int W = out->width[0], H = out->height[0], B = d->bytes_per_sample;
+  out->planes = fo == 0 ? 1 : d->layout == HMGPU_EXPORT_PLANAR ? 3 : 2;
+  for (int k = 1; k < 3; k++) {
+    const bool has = k < out->planes;
+    out->width[k] = has ? W >> osx : 0; out->height[k] = has ? H >> osy : 0;
+    out->row_bytes[k] = has ? (d->layout == HMGPU_EXPORT_PLANAR ? 1 : 2) * out->width[k] * B : 0;
+  }
+}
+
+// fmt_out: -1, or the output chroma format of a format export (YUV layouts): plane class 1 then goes from the cropped source chroma
+// plane to the chroma size of that format
 hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, hmgpu_export_plan* out,
-                         ScaleShape* shape, CallTabs* call_tabs = nullptr) {
+                         ScaleShape* shape, CallTabs* call_tabs = nullptr, int fmt_out = -1) {
   if (!seq || !d || !sc || !out) return HMGPU_EINVAL;
   memset(out, 0, sizeof(*out));
   { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
   hmgpu_export_plan base;
   { const hmgpu_status st = hmgpu_export_plan_for(seq, d, &base); if (st != HMGPU_OK) return st; }
-  const bool rgb = d->layout == HMGPU_EXPORT_RGB, chroma = !rgb && base.planes > 1;
-  int csx, csy;
+  if (fmt_out >= 0) plan_set_format(d, fmt_out, &base);
+  const bool rgb = d->layout == HMGPU_EXPORT_RGB, chroma = !rgb && base.planes > 1 && seq->chroma_format != 0;
+  int csx, csy, osx, osy;
   chroma_shifts(seq->chroma_format, &csx, &csy);
-  if (chroma && ((sc->width & ((1 << csx) - 1)) || (sc->height & ((1 << csy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
+  chroma_shifts(fmt_out >= 0 ? fmt_out : seq->chroma_format, &osx, &osy);
+  if (chroma && ((sc->width & ((1 << osx) - 1)) || (sc->height & ((1 << osy) - 1)))) return HMGPU_EINVAL;   // whole chroma samples
   ScaleShape s;
   s.classes = chroma ? 2 : 1;
   const int W = base.width[0], H = base.height[0];
@@ -325,7 +343,7 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
   for (int k = 0; k < s.classes; k++) {
     const int sx = k ? csx : 0, sy = k ? csy : 0;
     s.in[k][0] = W >> sx; s.in[k][1] = H >> sy;
-    s.out[k][0] = sc->width >> sx; s.out[k][1] = sc->height >> sy;
+    s.out[k][0] = sc->width >> (k ? osx : 0); s.out[k][1] = sc->height >> (k ? osy : 0);
     for (int ax = 0; ax < 2; ax++) if (!scale_ratio_ok(s.in[k][ax], s.out[k][ax])) return HMGPU_EUNSUPPORTED;
   }
   const int D = std::max(s.depth[0], s.depth[chroma ? 1 : 0]);
@@ -345,7 +363,7 @@ hmgpu_status scaled_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d
   *out = base;
   for (int p = 0; p < out->planes; p++) {
     const int k = rgb || p == 0 ? 0 : 1;
-    const int w = k ? sc->width >> csx : sc->width, h = k ? sc->height >> csy : sc->height;
+    const int w = k ? sc->width >> osx : sc->width, h = k ? sc->height >> osy : sc->height;
     out->row_bytes[p] = out->row_bytes[p] / out->width[p] * w;
     out->width[p] = w; out->height[p] = h;
   }
@@ -619,9 +637,11 @@ static hmgpu_status export_elem(const hmgpu_seq_params* seq, const hmgpu_export_
 static int elem_size(int elem) { return elem == kElemU8 ? 1 : elem == kElemF32 ? 4 : 2; }
 
 static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
-                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem, CallTabs* call_tabs = nullptr) {
+                                const hmgpu_export_tensor* t, hmgpu_export_plan* out, ScaleShape* shape, int* elem, CallTabs* call_tabs = nullptr,
+                                int fmt_out = -1) {
   if (!seq || !d || !out) return HMGPU_EINVAL;
-  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape, call_tabs) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = sc ? scaled_plan(seq, d, sc, out, shape, call_tabs, fmt_out) : hmgpu_export_plan_for(seq, d, out); if (st != HMGPU_OK) return st; }
+  if (!sc && fmt_out >= 0) plan_set_format(d, fmt_out, out);
   const hmgpu_status st = export_elem(seq, d, t, elem);
   if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
   if (*elem >= kElemF16)
@@ -633,7 +653,7 @@ static hmgpu_status tensor_plan(const hmgpu_seq_params* seq, const hmgpu_export_
 // call's status).  differ: the windows are not all equal; shapes (scaled): one per window then, else one for all.
 static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
                                  int n, const hmgpu_export_window* win, hmgpu_export_plan* out, std::vector<ScaleShape>* shapes, int* elem,
-                                 bool* differ, bool any_size = false) {
+                                 bool* differ, bool any_size = false, int fmt_out = -1) {
   if (!seq || !d || !out) return HMGPU_EINVAL;
   memset(out, 0, sizeof(*out));
   if (!win || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
@@ -649,7 +669,7 @@ static hmgpu_status windows_plan(const hmgpu_seq_params* seq, const hmgpu_export
     hmgpu_export_desc dd = *d;
     memcpy(dd.crop, win[i].crop, sizeof(dd.crop));
     ScaleShape s;
-    const hmgpu_status st = tensor_plan(seq, &dd, sc, t, &plan, &s, elem, *differ && sc ? &tabs : nullptr);
+    const hmgpu_status st = tensor_plan(seq, &dd, sc, t, &plan, &s, elem, *differ && sc ? &tabs : nullptr, fmt_out);
     if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
     if (shapes && sc) shapes->push_back(s);
     if (!i) { *out = plan; continue; }
@@ -816,6 +836,44 @@ static void chroma_site(const hmgpu_seq_params& seq, const hmgpu_export_chroma& 
   s->hc = seq.height >> (f420 ? 1 : 0);
 }
 
+// ------------------------------------------------------------------------------------------------ format export (k_export_fmt.hip)
+// the class and the weights of a validated conversion from the sequence's format to another one with chroma (include/hmgpu.h "format
+// export"); ob1: the chroma output depth.  REPLICATE and DROP are a single weight 4 on the axis, which the rounding returns exactly.
+static void fmt_conv(const hmgpu_seq_params& seq, const hmgpu_export_format& f, int ob1, FmtConv* v) {
+  memset(v, 0, sizeof(*v));
+  const int fs = seq.chroma_format, fo = f.chroma_format;
+  int ssx, ssy, osx, osy;
+  chroma_shifts(fs, &ssx, &ssy);
+  chroma_shifts(fo, &osx, &osy);
+  if (fs == 0) { v->cls = kFmtConst; v->constant = 1 << (ob1 - 1); return; }
+  const int gx = ssx - osx, gy = ssy - osy;                      // per axis: 1 gains samples, -1 loses them
+  if (gx > 0 || gy > 0) {
+    hmgpu_export_chroma ch;
+    memset(&ch, 0, sizeof(ch));
+    ch.filter = HMGPU_CHROMA_LINEAR; ch.loc = f.loc;
+    chroma_site(seq, ch, &v->cs);                                // the siting of the source, the 4:2:0 (or 4:2:2) side
+    if (f.up == HMGPU_CHROMA_REPLICATE) {
+      const int32_t hx[2][3] = {{0, 4, 0}, {0, 4, 0}}, vy[2][2] = {{0, 4}, {0, 4}};
+      memcpy(v->cs.hx, hx, sizeof(hx));
+      memcpy(v->cs.vy, vy, sizeof(vy));
+    }
+    v->vgain = gy > 0;
+    v->cls = gx > 0 ? kFmtUp : kFmtVert;
+  } else {
+    const bool lin = f.down == HMGPU_DOWN_LINEAR;
+    const int32_t dh[3][3] = {{0, 4, 0}, {1, 2, 1}, {0, 2, 2}};                   // drop, co-sited, centred
+    const int32_t dv[4][4] = {{0, 4, 0, 0}, {0, 2, 2, 0}, {-1, 1, 2, 1}, {0, 1, 2, 1}};   // drop, centred, co-sited, bottom: first row, weights
+    memcpy(v->dh, dh[!lin ? 0 : fo == 1 && (f.loc & 1) ? 2 : 1], sizeof(v->dh));
+    const int32_t* w = dv[lin ? 1 + (f.loc >> 1) : 0];
+    v->dv0 = w[0];
+    memcpy(v->dv, w + 1, sizeof(v->dv));
+    v->vloss = gy < 0;
+    v->cls = gx < 0 ? kFmtDown : kFmtVert;
+  }
+  v->cs.wc = seq.width >> ssx;
+  v->cs.hc = seq.height >> ssy;
+}
+
 // ------------------------------------------------------------------------------------------------ affine warp export (k_export_warp.hip)
 // whether `wp` names an output size (the plan and the destination check need one before the warp rules have their turn)
 static bool warp_sized(const hmgpu_export_warp* wp) {
@@ -856,6 +914,8 @@ struct ExportReq {
   const hmgpu_export_chroma* chroma = nullptr;
   const hmgpu_export_warp* wp = nullptr;
   const hmgpu_warp_map* maps = nullptr;
+  const hmgpu_export_format* fmt = nullptr;
+  bool format_stage = false;                         // the format entries: the format rules apply and the plan is the output format's
   bool need_sc = false, need_win = false, need_px = false;   // the entry is refused without that stage
   bool colour_stage = false;                         // the colour rules apply: the colour entries always, the wider ones with a LUT
   bool chroma_stage = false;                         // the chroma rules apply: the chroma entries always, the warp ones with a descriptor
@@ -878,6 +938,7 @@ struct ExportCall {
   bool vec = true;
   int64_t bs[3] = {0, 0, 0};
   hmgpu_ctx::ColourSlot* cs = nullptr;               // the colour stage (null: none)
+  int fmt_out = -1;                                  // a format export: the output chroma format (-1: the picture's own)
 };
 
 // the stages behind the pixels of the entries in which each of them is optional (the plans: ld, the calls and checks: lut)
@@ -890,18 +951,59 @@ void optional_stages(ExportReq* q, hmgpu_lut lut, const hmgpu_colour_lut_desc* l
 
 // Rules 1 and 2 of the order include/hmgpu.h documents: the base plan -- per window in order (windows_plan), else of the one crop
 // (tensor_plan) -- then pixel_plan.  shapes: the export itself asks for the scale shapes (a plan or a check needs none).
-static hmgpu_status export_plan(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
-  if (!seq || !q.d || !out || (q.need_sc && !q.sc) || (q.need_px && !q.px)) return HMGPU_EINVAL;
+static hmgpu_status base_plan(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
   if (q.win || q.need_win) {
-    const hmgpu_status st = windows_plan(seq, q.d, q.sc, q.t, n, q.win, out, shapes ? &r->shapes : nullptr, &r->elem, &r->differ, q.warp);
+    const hmgpu_status st = windows_plan(seq, q.d, q.sc, q.t, n, q.win, out, shapes ? &r->shapes : nullptr, &r->elem, &r->differ, q.warp,
+                                         r->fmt_out);
     if (st != HMGPU_OK) return st;
     for (int i = 0; i < n; i++) r->flip |= (uint32_t)(q.win[i].flip & 1) << i;
     if (q.sc && shapes) r->s = r->shapes[0];
   } else {
     memset(out, 0, sizeof(*out));
     if (q.warp && (n < 1 || n > HMGPU_EXPORT_MAX_BATCH)) return HMGPU_EINVAL;
-    const hmgpu_status st = tensor_plan(seq, q.d, q.sc, q.t, out, shapes ? &r->s : nullptr, &r->elem);
+    const hmgpu_status st = tensor_plan(seq, q.d, q.sc, q.t, out, shapes ? &r->s : nullptr, &r->elem, nullptr, r->fmt_out);
     if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
+// The rules a format export adds behind the plan of the matching call (`out`, already made), in the order include/hmgpu.h "format
+// export" gives; then the plan again, of the output format.  They stand in front of the destination check, which needs that plan.
+static hmgpu_status format_rules(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
+  const hmgpu_export_desc* d = q.d;
+  const hmgpu_export_format* f = q.fmt;
+  if (d->layout == HMGPU_EXPORT_RGB) return HMGPU_EINVAL;
+  if (!f || f->chroma_format < 0 || f->chroma_format > 3 || f->loc < 0 || f->loc > 5) return HMGPU_EINVAL;
+  for (int k = 0; k < 4; k++) if (f->reserved[k]) return HMGPU_EINVAL;
+  if (seq->chroma_format == 0 && f->chroma_format != 0) {         // the chroma output depth, which the matching call did not look at
+    int ob[2];
+    out_depths(seq, d, ob);
+    if (ob[1] < 1 || ob[1] > 16 || (d->bytes_per_sample == 1 && ob[1] > 8)) return HMGPU_EINVAL;
+    if (r->elem >= kElemF16 && d->bytes_per_sample != (std::max(ob[0], ob[1]) <= 8 ? 1 : 2)) return HMGPU_EINVAL;
+  }
+  if (f->up != HMGPU_CHROMA_REPLICATE && f->up != HMGPU_CHROMA_LINEAR) return HMGPU_EUNSUPPORTED;
+  if (f->down != HMGPU_DOWN_DROP && f->down != HMGPU_DOWN_LINEAR) return HMGPU_EUNSUPPORTED;
+  int osx, osy;
+  chroma_shifts(f->chroma_format, &osx, &osy);
+  if (f->chroma_format != 0) {
+    const int mx = (1 << osx) - 1, my = (1 << osy) - 1;
+    for (int i = 0; i < (q.win ? n : 1); i++) {
+      const int32_t* cr = q.win ? q.win[i].crop : d->crop;
+      const int W = seq->width - cr[0] - cr[1], H = seq->height - cr[2] - cr[3];
+      if (((cr[0] | W) & mx) || ((cr[2] | H) & my)) return HMGPU_EINVAL;
+    }
+    if (q.sc && ((q.sc->width & mx) || (q.sc->height & my))) return HMGPU_EINVAL;
+  }
+  r->fmt_out = f->chroma_format;
+  return base_plan(seq, n, q, out, r, shapes);
+}
+
+static hmgpu_status export_plan(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
+  if (!seq || !q.d || !out || (q.need_sc && !q.sc) || (q.need_px && !q.px)) return HMGPU_EINVAL;
+  { const hmgpu_status st = base_plan(seq, n, q, out, r, shapes); if (st != HMGPU_OK) return st; }
+  if (q.format_stage) {
+    const hmgpu_status st = format_rules(seq, n, q, out, r, shapes);
+    if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
   }
   if (q.warp && warp_sized(q.wp) && q.d->layout == HMGPU_EXPORT_RGB)
     for (int k = 0; k < out->planes; k++) {
@@ -1013,6 +1115,45 @@ hmgpu_status hmgpu_export_warp_plan_for(const hmgpu_seq_params* seq, const hmgpu
   optional_stages(&q, 0, ld, ch, false);
   q.wp = wp; q.maps = maps; q.warp = true;
   return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_format_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, int32_t n, const hmgpu_export_window win[],
+                                          const hmgpu_export_format* fmt, hmgpu_export_plan* out) {
+  ExportReq q(d, sc, t, win);
+  q.fmt = fmt; q.format_stage = true;
+  return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_format_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                            const hmgpu_export_format* fmt, int32_t chroma, int32_t axis, int32_t max_taps,
+                                            int32_t* first, int32_t* count, int16_t* weights) {
+  if (!first || !count || !weights || !sc || (chroma != 0 && chroma != 1) || (axis != 0 && axis != 1)) return HMGPU_EINVAL;
+  ExportReq q(d, sc, nullptr);
+  q.fmt = fmt; q.format_stage = true;
+  hmgpu_export_plan plan;
+  ExportCall r;
+  { const hmgpu_status st = export_plan(seq, 1, q, &plan, &r, true); if (st != HMGPU_OK) return st; }
+  if (chroma >= r.s.classes) return HMGPU_EINVAL;
+  const ScaleTab& t = *r.s.tab[chroma][axis];
+  if (max_taps < t.taps) return HMGPU_EINVAL;
+  const int n = r.s.out[chroma][axis];
+  memcpy(first, t.first.data(), sizeof(int32_t) * (size_t)n);
+  memcpy(count, t.count.data(), sizeof(int32_t) * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    memset(weights + (size_t)i * max_taps, 0, sizeof(int16_t) * (size_t)max_taps);
+    memcpy(weights + (size_t)i * max_taps, t.w.data() + (size_t)i * t.taps, sizeof(int16_t) * (size_t)t.taps);
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_export_format_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                   const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                   const hmgpu_export_format* fmt, void* const dst[3], const int64_t pitch_bytes[3],
+                                                   const int64_t batch_stride_bytes[3]) {
+  ExportReq q(d, sc, t, windows);
+  q.fmt = fmt; q.format_stage = true;
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
 }
 
 hmgpu_status hmgpu_export_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
@@ -1141,6 +1282,19 @@ static void launch_unscaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const Ex
   a.w = r.plan.width[0]; a.h = r.plan.height[0];
   a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
   export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
+  if (r.fmt_out >= 0 && r.fmt_out != c->seq.chroma_format) {
+    // a format export that converts: Y alone through the 4:0:0 path of k_export, else the chroma rows of the output format
+    if (r.fmt_out == 0) { a.mono = 1; launch_export(a, hs); return; }
+    FmtConv f;
+    fmt_conv(c->seq, *q.fmt, a.sh[1] + c->seq.bit_depth_chroma, &f);
+    for (int i = 0; i < n; i++) {
+      const int x0 = r.differ ? q.win[i].crop[0] : d->crop[0], y0 = r.differ ? q.win[i].crop[2] : d->crop[2];
+      f.cs.x0[i] = (int16_t)(x0 >> c->csx); f.cs.y0[i] = (int16_t)(y0 >> c->csy);
+    }
+    a.cw = r.plan.width[1]; a.ch = r.plan.height[1];
+    launch_export_fmt(a, f, hs);
+    return;
+  }
   if (site) {
     if (q.px) launch_export_px_chroma(a, r.po, *site, r.cs ? &r.cs->lut : nullptr, r.nch, hs);
     else launch_export_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, hs);
@@ -1166,6 +1320,7 @@ static hmgpu_status launch_scaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, co
     scale_tile_start(s.out[k][0], s.out[k][1], n, &tile[k][0], &tile[k][1]);
     tkey |= (__builtin_ctz((unsigned)tile[k][0]) | __builtin_ctz((unsigned)tile[k][1]) << 3) << (1 + 7 * k);
   }
+  tkey |= (r.fmt_out + 1) << 24;                      // (a format export: class 1 has the tables of its output format)
   ScaleArgs a;
   memset(&a, 0, sizeof(a));
   if (r.differ) {
@@ -1198,6 +1353,18 @@ static hmgpu_status launch_scaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, co
   if (site) launch_export_scaled_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, r.elem, n, hs, r.nch);
   else if (r.cs) launch_export_scaled_colour(a, r.cs->lut, r.elem, n, hs, r.nch);
   else launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  if (r.fmt_out > 0 && c->seq.chroma_format == 0) {
+    // a format export of a 4:0:0 picture with chroma planes: nothing to resample, the constant through k_export_fmt's chroma rows
+    ExportArgs e;
+    memset(&e, 0, sizeof(e));
+    e.n = n; e.layout = d->layout; e.elem = r.elem;
+    e.cw = r.plan.width[1]; e.ch = r.plan.height[1];
+    e.vec = r.vec ? (n >= 32 ? ~0u : (1u << n) - 1) : 0;
+    export_args_tail(e, c->seq, r, q.t, dst, pitch_bytes);
+    FmtConv f;
+    fmt_conv(c->seq, *q.fmt, e.sh[1] + c->seq.bit_depth_chroma, &f);
+    launch_export_fmt(e, f, hs);
+  }
   return HMGPU_OK;
 }
 
@@ -1317,6 +1484,15 @@ hmgpu_status hmgpu_pictures_export_chroma(hmgpu_ctx* c, int32_t n, const hmgpu_p
                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
   ExportReq q(d, sc, t, windows, px);
   optional_stages(&q, lut, nullptr, chroma, true);
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_format(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                          const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_format* fmt,
+                                          void* const dst[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                          int32_t on_stream, void* stream) {
+  ExportReq q(d, sc, t, windows);
+  q.fmt = fmt; q.format_stage = true;
   return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 

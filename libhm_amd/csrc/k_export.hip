@@ -11,28 +11,11 @@
 // and the store (hmgpu_pictures_export_colour), and a third with the chroma stage of chroma_core.h in place of the replicated chroma
 // (hmgpu_pictures_export_chroma), with or without the colour stage.
 #include "hmgpu_dev.h"
+#include "export_core.h"
 #include "colour_core.h"
 #include "chroma_core.h"
 
 namespace hmgpu {
-
-namespace {
-
-__device__ inline int depth_conv(int v, int sh, int maxv) {
-  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
-}
-
-// 4 consecutive int16 samples: one 8-byte load, or four 2-byte ones where the group is not 8-byte aligned
-__device__ inline void load4(const int16_t* p, bool vec, int v[4]) {
-  if (vec) {
-    const u32x2 w = ldg2(p);
-    v[0] = (int16_t)(w.x & 0xffff); v[1] = (int16_t)(w.x >> 16); v[2] = (int16_t)(w.y & 0xffff); v[3] = (int16_t)(w.y >> 16);
-  } else {
-    for (int i = 0; i < 4; i++) v[i] = ldg(p + i);
-  }
-}
-
-}  // namespace
 
 // X: nothing, or the stages of the RGB layout, each an instance family of its own -- a ColourLut: the colour stage (colour_core.h)
 // between the clip and the store (launch_export_colour); a ChromaSite, before it: the chroma stage (chroma_core.h) in place of the

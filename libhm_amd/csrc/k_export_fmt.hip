@@ -1,0 +1,138 @@
+// k_export_fmt.hip -- the planar and semi-planar exports with Cb / Cr at a chroma format other than the picture's
+// (hmgpu_pictures_export_format, include/hmgpu.h "format export"; TVideoIOYuv::writePlane with fileFormat != srcFormat,
+// TVideoIOYuv.cpp:362-483, and its siting-aware linear forms).
+// k_export's shape: memory-bound, one lane per 4 output samples of a row (luma) or 4 output CbCr pairs (chroma), rows along the
+// grid's y -- the luma rows, then the chroma rows of the OUTPUT format --, the pictures of a batch along z with their own origin,
+// alignment and mirror flag, no LDS.  Luma rows are k_export's (export_core.h).  A chroma row reads the pair plane of the source
+// format: its one to three source rows are chosen and clamped to the decoded plane before the loads (uniform per workgroup; a row
+// without weight is not loaded), every load's address is known before the first load is consumed, and columns are clamped as selects
+// behind whole-group loads (chroma_core.h's argument: a column outside the plane is read from the plane's margin, whatever it holds,
+// and replaced by the edge sample before use).  The furthest a lane reaches: one pair left of pair 0 (kFmtUp, kFmtDown) and, the
+// last lane of a row, 5 pairs beyond the last source pair of the window (kFmtDown: pairs 2x .. 2x + 7 for x <= cw - 1) or 2 (the
+// others); the pair planes keep 128 >> csx pairs of margin on both sides, 128 for the 4:4:4 planes kFmtDown reads.
+// One instance per layout, output element and class (FmtConv), so nothing per sample branches on the format or the filter: REPLICATE
+// and DROP are the same instances with a single weight 4 per axis, which the rounding returns exactly.
+#include "hmgpu_dev.h"
+#include "export_core.h"
+#include "chroma_core.h"
+
+namespace hmgpu {
+
+namespace {
+
+// the source rows (plane coordinates, clamped) of output chroma row Y (plane coordinates of the output format) and their weights in
+// quarters, which sum to 4; a row without weight repeats the one before it
+__device__ inline void fmt_rows(const FmtConv& f, int Y, int ri[3], int rw[3]) {
+  if (f.vgain) {
+    chroma_rows(f.cs, Y, 1, &ri[0], &ri[1], &rw[0]);
+    rw[1] = 4 - rw[0]; rw[2] = 0;
+  } else if (f.vloss) {
+    for (int k = 0; k < 3; k++) { ri[k] = min(f.cs.hc - 1, max(0, 2 * Y + f.dv0 + k)); rw[k] = f.dv[k]; }
+  } else {
+    ri[0] = Y; rw[0] = 4; rw[1] = rw[2] = 0;
+  }
+  if (!rw[1]) ri[1] = ri[0];
+  if (!rw[2]) ri[2] = ri[1];
+}
+
+}  // namespace
+
+template <int LAYOUT, int ELEM, int CLS>
+__global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const FmtConv f) {
+  const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
+  const int r = blockIdx.y, pic = blockIdx.z;
+  const bool vec = (a.vec >> pic) & 1, flip = (a.flip >> pic) & 1;
+  uint8_t* const d0 = a.dst[0] + pic * a.bstride[0];
+  uint8_t* const d1 = a.dst[1] + pic * a.bstride[1];
+  uint8_t* const d2 = a.dst[2] + pic * a.bstride[2];
+  if (r < a.h) {
+    if (x >= a.w) return;
+    int yv[4];
+    load4(a.y[pic] + (ptrdiff_t)r * a.pitch_y + x, vec, yv);
+    export_luma_row<ELEM>(a, d0, r, x, min(4, a.w - x), yv, vec, flip);
+    return;
+  }
+  // a chroma row of the output format: four CbCr pairs per lane
+  const int rc = r - a.h;
+  if (x >= a.cw) return;
+  const int n = min(4, a.cw - x);
+  uint32_t o[8];
+  if constexpr (CLS == kFmtConst) {
+    for (int i = 0; i < 8; i++) o[i] = (uint32_t)f.constant;
+  } else {
+    const int16_t* const ac = a.c[pic];
+    const int x0 = f.cs.x0[pic], y0 = f.cs.y0[pic];
+    int ri[3], rw[3];
+    fmt_rows(f, (f.vgain ? y0 << 1 : f.vloss ? y0 >> 1 : y0) + rc, ri, rw);
+    int c[8];
+    if constexpr (CLS == kFmtUp) {
+      // source pairs J - 1 .. J + 2 (J = the pair of output pair x) of two rows, six loads none of which waits for another
+      const int16_t* pa = ac + (ptrdiff_t)(ri[0] - y0) * a.pitch_c + kCStep * (x >> 1);
+      const int16_t* pb = ac + (ptrdiff_t)(ri[1] - y0) * a.pitch_c + kCStep * (x >> 1);
+      int ma[4], mb[4], ua[4], ub[4], va[4], vb[4], u[4], v[4];
+      load4(pa, vec, ma);
+      load4(pb, vec, mb);
+      chroma_pair(pa - kCStep, &ua[0], &va[0]);
+      chroma_pair(pb - kCStep, &ub[0], &vb[0]);
+      chroma_pair(pa + 2 * kCStep, &ua[3], &va[3]);
+      chroma_pair(pb + 2 * kCStep, &ub[3], &vb[3]);
+      ua[1] = ma[0]; va[1] = ma[1]; ua[2] = ma[2]; va[2] = ma[3];
+      ub[1] = mb[0]; vb[1] = mb[1]; ub[2] = mb[2]; vb[2] = mb[3];
+      chroma_line<2>(f.cs, x0 + (x >> 1), rw[0], ua, ub, u);
+      chroma_line<2>(f.cs, x0 + (x >> 1), rw[0], va, vb, v);
+      for (int i = 0; i < 4; i++) { c[2 * i] = u[i]; c[2 * i + 1] = v[i]; }
+    } else if constexpr (CLS == kFmtVert) {
+      // the group's own four pairs on every row that has a weight
+      int p[3][8];
+      for (int k = 0; k < 3; k++) {
+        for (int i = 0; i < 8; i++) p[k][i] = 0;
+        if (rw[k]) {
+          const int16_t* cp = ac + (ptrdiff_t)(ri[k] - y0) * a.pitch_c + kCStep * x;
+          load8(cp, vec, p[k]);
+        }
+      }
+      for (int i = 0; i < 8; i++) c[i] = (4 * (rw[0] * p[0][i] + rw[1] * p[1][i] + rw[2] * p[2][i]) + 8) >> 4;
+    } else {
+      // kFmtDown: source pairs 2x - 1 .. 2x + 7 on every row that has a weight
+      int p[3][18];
+      for (int k = 0; k < 3; k++) {
+        for (int i = 0; i < 18; i++) p[k][i] = 0;
+        if (rw[k]) {
+          const int16_t* cp = ac + (ptrdiff_t)(ri[k] - y0) * a.pitch_c + kCStep * 2 * x;
+          load8(cp, vec, p[k] + 2);
+          load8(cp + 8, vec, p[k] + 10);
+          chroma_pair(cp - kCStep, &p[k][0], &p[k][1]);
+        }
+      }
+      int v[18];
+      for (int i = 0; i < 18; i++) v[i] = rw[0] * p[0][i] + rw[1] * p[1][i] + rw[2] * p[2][i];
+      if (x0 + 2 * x == 0) { v[0] = v[2]; v[1] = v[3]; }         // the plane's first column has no left neighbour
+      for (int j = 0; j < 4; j++)
+        for (int e = 0; e < 2; e++)
+          c[2 * j + e] = (f.dh[0] * v[4 * j + e] + f.dh[1] * v[4 * j + 2 + e] + f.dh[2] * v[4 * j + 4 + e] + 8) >> 4;
+    }
+    for (int i = 0; i < 8; i++) o[i] = (uint32_t)depth_conv(c[i], a.sh[1], a.maxv[1]);
+  }
+  export_chroma_out<LAYOUT, ELEM>(a, d1, d2, rc, x, n, o, vec, flip);
+}
+
+void launch_export_fmt(const ExportArgs& a, const FmtConv& f, hipStream_t s) {
+  const int groups = (std::max(a.w, a.cw) + 3) / 4;
+  const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)(a.h + a.ch), (unsigned)a.n), block(256);
+#define HMGPU_EXPORT_FMT_CASE(L, E, K) \
+  if (a.layout == L && a.elem == E && f.cls == K) hipLaunchKernelGGL((k_export_fmt<L, E, K>), grid, block, 0, s, a, f);
+#define HMGPU_EXPORT_FMT_CLASSES(L, E) \
+  HMGPU_EXPORT_FMT_CASE(L, E, kFmtConst) HMGPU_EXPORT_FMT_CASE(L, E, kFmtUp) HMGPU_EXPORT_FMT_CASE(L, E, kFmtVert) HMGPU_EXPORT_FMT_CASE(L, E, kFmtDown)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemU8)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemU16)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_SEMIPLANAR, kElemU8)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_SEMIPLANAR, kElemU16)
+  // float elements: the planar layout (the host refuses semi-planar)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemF16)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemBF16)
+  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemF32)
+#undef HMGPU_EXPORT_FMT_CLASSES
+#undef HMGPU_EXPORT_FMT_CASE
+}
+
+}  // namespace hmgpu

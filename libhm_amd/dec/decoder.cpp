@@ -1080,6 +1080,9 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const ExportR
       case ExportRequest::CHROMA:
         return check ? hmgpu_export_chroma_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, h, q.chroma, d, pitch_bytes, bs)
                      : hmgpu_pictures_export_chroma(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, h, q.chroma, d, pitch_bytes, bs, on_stream, stream);
+      case ExportRequest::FORMAT:
+        return check ? hmgpu_export_format_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.format, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export_format(c, rn, rh, q.desc, q.scale, q.tensor, w, q.format, d, pitch_bytes, bs, on_stream, stream);
       case ExportRequest::COLOUR:
         return check ? hmgpu_export_colour_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs)
                      : hmgpu_pictures_export_colour(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs, on_stream, stream);

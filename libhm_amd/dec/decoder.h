@@ -22,9 +22,10 @@ namespace hmdec {
 
 // The stages of a batched picture export, as the hmdec_pictures_export* entries fill them and Decoder::export_pictures hands them to
 // the hmgpu entry of the same name.  entry: whose rules hold for an absent stage -- PLAIN: hmgpu_pictures_export, _windows (windows
-// set) or _pixels (pixel set); COLOUR: lut 0 is refused; CHROMA: lut 0 is no colour stage; WARP: chroma null is "replicate" too
+// set) or _pixels (pixel set); COLOUR: lut 0 is refused; CHROMA: lut 0 is no colour stage; WARP: chroma null is "replicate" too;
+// FORMAT: the YUV layouts at the chroma format of `format`, windows null or set
 struct ExportRequest {
-  enum Entry { PLAIN, COLOUR, CHROMA, WARP } entry = PLAIN;
+  enum Entry { PLAIN, COLOUR, CHROMA, WARP, FORMAT } entry = PLAIN;
   const hmgpu_export_desc* desc = nullptr;
   const hmgpu_export_scale* scale = nullptr;
   const hmgpu_export_tensor* tensor = nullptr;
@@ -34,6 +35,7 @@ struct ExportRequest {
   const hmgpu_export_chroma* chroma = nullptr;
   const hmgpu_export_warp* warp = nullptr;
   const hmgpu_warp_map* maps = nullptr;                    // one per picture
+  const hmgpu_export_format* format = nullptr;
 };
 
 class Decoder {

@@ -51,23 +51,25 @@ def layout_code(layout):
         raise ValueError("unknown export layout %r (one of %s)" % (layout, ", ".join(sorted(LAYOUTS))))
 
 
-def make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned=False, seq=None):
+def make_desc(layout, bit_depth, crop, matrix, full_range, msb_aligned=False, seq=None, chroma_format=None):
     """bit_depth: an int for every channel type, a (luma, chroma) pair, or None / 0 for the coding bit depths.  seq (float output):
-    the container is the one the output depths need (1 byte when none exceeds 8), the coding depths taken from the sequence"""
+    the container is the one the output depths need (1 byte when none exceeds 8), the coding depths taken from the sequence;
+    chroma_format: the output format of a format export (plane_depths)"""
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
     if seq is not None:
-        nbytes = 2 if max(plane_depths(seq, layout_code(layout), bd)) > 8 else 1
+        nbytes = 2 if max(plane_depths(seq, layout_code(layout), bd, chroma_format)) > 8 else 1
     else:
         nbytes = 2 if msb_aligned or max(bd) > 8 or min(bd) == 0 else 1
     return abi.make_export_desc(layout_code(layout), bd, nbytes, msb_aligned, tuple(crop), matrix, full_range)
 
 
-def plane_depths(seq, layout, bd):
-    """the integer depth D of every output plane: RGB the luma output depth three times; YUV luma, chroma, chroma (4:0:0: luma)"""
+def plane_depths(seq, layout, bd, chroma_format=None):
+    """the integer depth D of every output plane: RGB the luma output depth three times; YUV luma, chroma, chroma (4:0:0: luma).
+    chroma_format: None, or the output format of a format export, which decides whether there is chroma"""
     y = bd[0] or seq.bit_depth_luma
     if layout == abi.EXPORT_RGB:
         return (y, y, y)
-    if seq.chroma_format == 0:
+    if (seq.chroma_format if chroma_format is None else chroma_format) == 0:
         return (y,)
     c = bd[1] or seq.bit_depth_chroma
     return (y, c, c)
@@ -344,18 +346,20 @@ def _check_tensor(t, desc, device, dtype=None):
         raise ValueError("out: on device %d, the picture is on %d" % (t.get_device(), device))
 
 
-def out_spans(out, plan, desc, device, n=None, dtype=None):
+def out_spans(out, plan, desc, device, n=None, dtype=None, stacked=False):
     """a caller's destination as (pointers, pitches in bytes, batch strides in bytes or None) per plane.  n None, one picture: RGB
     one [3, H, W] tensor or three planes, YUV a tuple of planes.  n pictures: the same with a leading dimension of n ([n, 3, H, W];
     planes [n, H, W], [n, Hc, Wc, 2]).  Each plane has the planned shape and dtype on the device and its samples dense within a
     row; rows, planes and batch entries may be any stride apart (e.g. a view batch[i]).  Reads only shapes, strides and pointers:
-    no views are made."""
+    no views are made.  stacked: the planar layout at 4:4:4 (a format export), Y, Cb and Cr as the channels of one tensor like R, G, B."""
     import torch
     shapes = plane_shapes(plan, desc)
     lead = () if n is None else (n,)
     b = len(lead)
+    if stacked and not isinstance(out, torch.Tensor):
+        raise ValueError("out: the planar layout at chroma_format 4:4:4 takes one %s tensor" % (lead + (3,) + shapes[0],))
     if isinstance(out, torch.Tensor):
-        if desc.layout != abi.EXPORT_RGB:
+        if desc.layout != abi.EXPORT_RGB and not stacked:
             raise ValueError("out: the planar / semi-planar layouts take a tuple of planes")
         h, w = shapes[0]
         if out.shape != lead + (3, h, w):
@@ -385,14 +389,14 @@ def out_spans(out, plan, desc, device, n=None, dtype=None):
     return ptrs, pitches, bstrides if b else None
 
 
-def alloc_outputs(plan, desc, device, n=None, dtype=None):
+def alloc_outputs(plan, desc, device, n=None, dtype=None, stacked=False):
     """torch tensors for what `plan` describes: RGB [3, H, W]; planar (Y, Cb, Cr) 2-D; semi-planar (Y [H, W], CbCr [Hc, Wc, 2]);
     with n, each with a leading dimension of n.  dtype None: the unsigned type of the container."""
     import torch
     dt = torch_dtype(desc.bytes_per_sample) if dtype is None else dtype
     dev = torch.device("cuda", device)
     lead = () if n is None else (n,)
-    if desc.layout == abi.EXPORT_RGB:
+    if desc.layout == abi.EXPORT_RGB or stacked:
         return torch.empty(lead + (3, plan.height[0], plan.width[0]), dtype=dt, device=dev)
     return tuple(torch.empty(lead + shape, dtype=dt, device=dev) for shape in plane_shapes(plan, desc))
 
@@ -468,11 +472,11 @@ def out_pixels(out, plan, desc, px, device, n=None, dtype=None):
     return out.data_ptr(), sy * es, st[0] * es if b else None
 
 
-class Stages(collections.namedtuple("Stages", "scale tensor windows pixel lut chroma warp", defaults=(None,) * 7)):
+class Stages(collections.namedtuple("Stages", "scale tensor windows pixel lut chroma warp format", defaults=(None,) * 8)):
     """the stages of one picture export, None where the call has none: scale an abi.ExportScale; tensor an abi.ExportTensor (float
     elements); windows one abi.ExportWindow per picture; pixel an abi.ExportPixel (packed pixels: one destination); lut a colour LUT
     of the context or decoder, or its raw handle; chroma an abi.ExportChroma; warp (abi.ExportWarp, abi.WarpMap array) of
-    abi.warp_stage.  libhm_amd.export_stages_plan, Context.export_stages_into and hmdec's dispatcher choose the entry from it."""
+    abi.warp_stage; format an abi.ExportFormat (the YUV layouts at another chroma format).  libhm_amd.export_stages_plan, Context.export_stages_into and hmdec's dispatcher choose the entry from it."""
     __slots__ = ()
 
     def shape_only(self):
@@ -487,7 +491,7 @@ def stage_extents(plan, pitches):
 
 def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_range, msb_aligned=False, on_stream=True, size=None,
                    filter="bilinear", out=None, n=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None,
-                   pixel=None, alpha=None, memory_format=None, lut=None, chroma=None, warp=None):
+                   pixel=None, alpha=None, memory_format=None, lut=None, chroma=None, warp=None, format=None):
     """allocate with torch on `device` (or take `out`) and run `call(desc, stages, ptrs, pitches, bstrides, stream)` on torch's
     current stream.  stages (Stages): scale None (size None), else the abi.ExportScale of size (height, width) and filter; tensor
     None (dtype None), else the abi.ExportTensor of the float dtype and mean / std (or explicit scale / bias triples); windows None,
@@ -495,6 +499,8 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
     pixel from pixel / alpha / memory_format (make_pixel): packed pixels, ONE tensor [H, W, C] ([N, H, W, C]; channels-last
     [N, 3, H, W]), the lists of its call one long, bstrides of one picture the extent of its rows; lut and chroma as given; warp
     None, or (abi.ExportWarp, abi.WarpMap array) of abi.warp_stage: size and filter belong to it and the stages have no scale.
+    format None, or the abi.ExportFormat of a format export (abi.format_stage): the planes of its chroma format; the planar layout at
+    4:4:4 is ONE tensor [3, H, W] ([N, 3, H, W]) with Y, Cb and Cr as its channels.
     bstrides of planes: None for one picture (n None), else the bytes between the batch entries of every plane of the n pictures."""
     import torch
     from . import export_stages_plan
@@ -504,10 +510,12 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
         size = None
     px = make_pixel(pixel, alpha, memory_format, layout, dtype, n)
     bd = (0, 0) if bit_depth is None else (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
+    fo = None if format is None else format.chroma_format
     desc = make_desc(layout, bit_depth, crop if windows is None else (0, 0, 0, 0), matrix, full_range, msb_aligned,
-                     seq if dtype is not None else None)
-    stages = Stages(make_scale(size, filter), make_tensor(dtype, plane_depths(seq, desc.layout, bd), mean, std, scale, bias), windows, px,
-                    lut, chroma, warp)
+                     seq if dtype is not None else None, fo)
+    stages = Stages(make_scale(size, filter), make_tensor(dtype, plane_depths(seq, desc.layout, bd, fo), mean, std, scale, bias), windows, px,
+                    lut, chroma, warp, format)
+    stacked = fo == 3 and desc.layout == abi.EXPORT_PLANAR
     plan = export_stages_plan(seq, desc, stages.shape_only(), n or 1)
     with torch.cuda.device(device):
         if px is not None:
@@ -517,8 +525,8 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
             ptrs, pitches, bstrides = [ptr], [pitch], [bstride] if bstride is not None else stage_extents(plan, [pitch])
         else:
             if out is None:
-                out = alloc_outputs(plan, desc, device, n, dtype)
-            ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype)
+                out = alloc_outputs(plan, desc, device, n, dtype, stacked)
+            ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype, stacked)
         call(desc, stages, ptrs, pitches, bstrides, torch.cuda.current_stream(device).cuda_stream if on_stream else 0)
     return out
 
