@@ -99,6 +99,7 @@ typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
+typedef struct hmgpu_metrics_map_desc hmgpu_metrics_map_desc;
 typedef struct hmgpu_histogram_desc hmgpu_histogram_desc;
 #endif
 void hmdec_set_device_output(libHMDec_context* ctx, int on);
@@ -195,6 +196,14 @@ int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_pictur
 int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc, const void* const ref[3],
                            const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* results,
                            int64_t results_batch_stride_bytes, int on_stream, void* stream);
+/* The same comparison kept per block (hmgpu_pictures_metrics_map with HMGPU_METRICS_REF_PLANES: description, maps, strides and statuses as
+ * there), under the rules of hmdec_pictures_metrics: everything is validated before any context is given work
+ * (hmgpu_metrics_map_check), then each context gets one call per run of equally spaced slots.  HMGPU_METRICS_REF_PICTURES is refused
+ * (HMGPU_EUNSUPPORTED, hmdec_last_error says why). */
+int hmdec_pictures_metrics_map(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc,
+                               const hmgpu_metrics_map_desc* map, const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                               const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
+                               const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3], int on_stream, void* stream);
 /* What up to 16 output pictures kept on the device contain: histograms and moments of Y, Cb, Cr and maxRGB (hmgpu_pictures_histogram:
  * description, destinations, strides and statuses as there, desc->crop in luma samples of the coded picture), under the rules of
  * hmdec_pictures_metrics: everything is validated before any context is given work (hmgpu_histogram_check), then each context gets

@@ -976,6 +976,65 @@ hmgpu_status hmgpu_metrics_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics
                                  const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
                                  const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes);
 
+/* ------------------------------------------------------------------------------------------------ picture metric maps
+ * The sums of "picture metrics" kept per block instead of per picture: where two pictures differ, as device tensors
+ * aligned with the picture.  Up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_metrics_map.hip), nothing zeroed and
+ * no atomics: every map element is written exactly once, so two calls on the same inputs give the same bytes.
+ *
+ * desc is the hmgpu_metrics_desc of hmgpu_pictures_metrics with its meaning unchanged -- the reference as pictures or as uint8 / uint16
+ * planes, components, ssim, crop -- and a, b, d = a - b, w_c, h_c are those of that section; its rules, and the order of the refusals
+ * among its fields, are those of that call.  map->log2_block (3 .. 6, else HMGPU_EINVAL, as is a non-zero reserved word; both checked
+ * after the refusals of desc) gives square blocks of B = 8, 16, 32 or 64 LUMA samples; the block of a chroma component is
+ * bw_c x bh_c = (B >> csx) x (B >> csy) of its samples.
+ * The block grid starts at the top-left sample of the cropped plane: blocks_x = ceil(W / B), blocks_y = ceil(H / B) with W x H the
+ * cropped luma size, the same grid for all three components.  Block (bx, by) of component c covers its samples
+ * [bx * bw_c, min((bx + 1) * bw_c, w_c)) x [by * bh_c, min((by + 1) * bh_c, h_c)): the blocks of the last column and row may be partial.
+ * With no crop the grid is aligned with the CTUs and with the 4x4 grid of the motion export.
+ * Fields (HMGPU_METRICS_MAP_*), int64 each:
+ *   SSE, SAD, DIFFERING, MAX_ABS   sum d^2, sum |d|, #(d != 0), max |d| over the block's samples
+ *   SSIM_Q32, SSIM_WINDOWS        the windows are the picture's own -- top-left at (4i, 4j) of the cropped component plane,
+ *                                 4i + 8 <= w_c, 4j + 8 <= h_c -- each counted in the block that holds its top-left sample (it reads up to
+ *                                 7 samples into the next block); the value of a window is the expression of "picture metrics", bit for
+ *                                 bit.  Only with desc->ssim 1: without, a map has the first four fields.
+ * Sum rule: for every picture and component the sum over the blocks of a field equals that field of hmgpu_metrics_result for the
+ * same desc; for MAX_ABS it is the maximum.
+ * Output: element (i, c, f, by, bx) at maps[c] + i * map_batch_stride_bytes[c] + f * map_field_stride_bytes[c] + by * map_pitch_bytes[c]
+ * + bx * 8.  maps[c] must be given for every selected component the format has and be NULL for every other one (else HMGPU_EINVAL;
+ * nothing is written for those).  Alignment 8 for the address and every stride; pitch >= row_bytes, field stride >= pitch *
+ * (blocks_y - 1) + row_bytes, batch stride >= field stride * (fields - 1) + that; all n maps of a component inside one allocation of the
+ * context's device.  Memory between rows, fields and pictures under padded strides is never touched.
+ * Everything is validated before anything is enqueued and a refused call leaves the maps untouched.  Stream ordering is that of
+ * hmgpu_pictures_metrics.  The launch is not accounted in hmgpu_stats. */
+typedef struct hmgpu_metrics_map_desc {
+  int32_t log2_block;          /* 3 .. 6: square blocks of 8, 16, 32, 64 LUMA samples; chroma blocks are (B >> csx) x (B >> csy) */
+  int32_t reserved[7];         /* 0 */
+} hmgpu_metrics_map_desc;
+enum { HMGPU_METRICS_MAP_SSE = 0, HMGPU_METRICS_MAP_SAD, HMGPU_METRICS_MAP_DIFFERING, HMGPU_METRICS_MAP_MAX_ABS,
+       HMGPU_METRICS_MAP_SSIM_Q32, HMGPU_METRICS_MAP_SSIM_WINDOWS, HMGPU_METRICS_MAP_FIELDS };   /* 6 */
+typedef struct hmgpu_metrics_map_plan {
+  int32_t blocks_x, blocks_y;  /* the map of every component */
+  int32_t block_w[3], block_h[3]; /* bw_c, bh_c in samples of the component; 0 for a component that is not compared */
+  int32_t width[3], height[3]; /* w_c, h_c of the cropped component plane */
+  int32_t channels[3];         /* per component: 1 = compared (selected, and the format has it): maps[c] is written */
+  int32_t fields;              /* 4 without SSIM, 6 with */
+  int32_t row_bytes;           /* blocks_x * 8: the least pitch */
+  int32_t reserved[5];         /* 0 */
+} hmgpu_metrics_map_plan;
+/* validates a call's description and reports what it writes; host code, no device needed */
+hmgpu_status hmgpu_metrics_map_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* desc, const hmgpu_metrics_map_desc* map,
+                                        hmgpu_metrics_map_plan* out);
+hmgpu_status hmgpu_pictures_metrics_map(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* desc,
+                                        const hmgpu_metrics_map_desc* map, const hmgpu_pic ref_pics[], const void* const ref[3],
+                                        const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* const maps[3],
+                                        const int64_t map_pitch_bytes[3], const int64_t map_field_stride_bytes[3],
+                                        const int64_t map_batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* the validation of hmgpu_pictures_metrics_map alone, nothing enqueued: the status that call would give */
+hmgpu_status hmgpu_metrics_map_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* desc,
+                                     const hmgpu_metrics_map_desc* map, const hmgpu_pic ref_pics[], const void* const ref[3],
+                                     const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* const maps[3],
+                                     const int64_t map_pitch_bytes[3], const int64_t map_field_stride_bytes[3],
+                                     const int64_t map_batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ picture histograms
  * What finished pictures contain: per picture and channel a histogram of the sample values and one 64-byte record of
  * their moments and extrema.  Up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_histogram.hip) behind the memsets

@@ -192,6 +192,13 @@ def lib():
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                              C.c_int32, C.c_void_p]
         L.hmgpu_metrics_check.argtypes = L.hmgpu_pictures_metrics.argtypes[:10]
+        L.hmgpu_metrics_map_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MetricsDesc), C.POINTER(abi.MetricsMapDesc),
+                                                 C.POINTER(abi.MetricsMapPlan)]
+        L.hmgpu_pictures_metrics_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.MetricsDesc),
+                                                 C.POINTER(abi.MetricsMapDesc), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_metrics_map_check.argtypes = L.hmgpu_pictures_metrics_map.argtypes[:13]
         L.hmgpu_histogram_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.HistogramDesc), C.POINTER(abi.HistogramPlan)]
         L.hmgpu_pictures_histogram.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.HistogramDesc),
                                                C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -490,6 +497,16 @@ def metrics_plan(seq, reference="pictures", components=(0, 1, 2), ssim=True, cro
     desc = abi.make_metrics_desc(abi.METRICS_REF_PLANES if planes else abi.METRICS_REF_PICTURES, metrics.components_mask(components),
                                  1 if ssim else 0, ref_bytes_per_sample if planes else 0, crop)
     return metrics.plan_for(seq, desc)
+
+
+def metrics_map_plan(seq, block=16, reference="pictures", components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), ref_bytes_per_sample=2):
+    """what Context.metrics_map with these arguments writes (hmgpu_metrics_map_plan_for: host code, no GPU): an abi.MetricsMapPlan -- the
+    block grid, per component the block and the cropped plane, the fields of a map"""
+    from . import metrics
+    planes = {"pictures": False, "planes": True}[reference]
+    desc = abi.make_metrics_desc(abi.METRICS_REF_PLANES if planes else abi.METRICS_REF_PICTURES, metrics.components_mask(components),
+                                 1 if ssim else 0, ref_bytes_per_sample if planes else 0, crop)
+    return metrics.map_plan_for(seq, desc, abi.make_metrics_map_desc(block))
 
 
 def histogram_plan(seq, channels=("y", "cb", "cr"), bins=None, crop=(0, 0, 0, 0), matrix=None, full_range=None, rgb_bit_depth=0,
@@ -966,6 +983,40 @@ class Context:
         return metrics.metrics(lambda desc, rp, ptrs, pitches, bstrides, res, rs, st:
                                self.metrics_into(pics, desc, res, rs, rp, ptrs, pitches, bstrides, 1 if on_stream else 0, st),
                                self.seq, self.device, len(pics), None if ref_pics is None else list(ref_pics), ref, components, ssim, crop)
+
+    def metrics_map_into(self, pics, desc, map_desc, maps, map_pitches, map_fstrides, map_bstrides, ref_pics=None, ptrs=None, pitches=None,
+                         bstrides=None, on_stream=0, stream=0):
+        """hmgpu_pictures_metrics_map into device memory the caller owns: maps the addresses of the three components' maps (None: not
+        written), map_pitches / map_fstrides / map_bstrides the bytes from row to row, field to field and picture to picture; the
+        reference as for metrics_into"""
+        from . import metrics
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_metrics_map(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(map_desc),
+                                                   *metrics.c_args(ref_pics, ptrs, pitches, bstrides),
+                                                   *metrics.map_c_args(maps, map_pitches, map_fstrides, map_bstrides), on_stream, abi.addr(stream)),
+                  "hmgpu_pictures_metrics_map")
+
+    def metrics_map_status(self, pics, desc, map_desc, maps, map_pitches, map_fstrides, map_bstrides, ref_pics=None, ptrs=None, pitches=None,
+                           bstrides=None):
+        """hmgpu_metrics_map_check: the status hmgpu_pictures_metrics_map would give these arguments; enqueues nothing"""
+        from . import metrics
+        pics = list(pics)
+        return lib().hmgpu_metrics_map_check(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(map_desc),
+                                             *metrics.c_args(ref_pics, ptrs, pitches, bstrides),
+                                             *metrics.map_c_args(maps, map_pitches, map_fstrides, map_bstrides))
+
+    def metrics_map(self, pics, ref_pics=None, ref=None, block=16, components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), on_stream=True):
+        """where up to 16 pictures differ from their reference (given as for metrics): per block of block x block luma samples (8, 16, 32
+        or 64; a chroma block covers the same area) {"y": {"sse": [n, Hb, Wb], "sad", "differing", "max_abs", "ssim_q32",
+        "ssim_windows"}, "cb": ..., "cr": ...}, int64 tensors on the device (libhm_amd.metrics: map_psnr, map_ssim, mismatch_blocks).
+        Summed over the blocks a field is the field Context.metrics gives.  One launch on torch's current stream (on_stream) or the
+        context's own; nothing synchronises."""
+        from . import metrics
+        pics = list(pics)
+        return metrics.metrics_map(lambda desc, md, rp, ptrs, pitches, bstrides, maps, mp, mf, mb, st:
+                                   self.metrics_map_into(pics, desc, md, maps, mp, mf, mb, rp, ptrs, pitches, bstrides, 1 if on_stream else 0, st),
+                                   self.seq, self.device, len(pics), None if ref_pics is None else list(ref_pics), ref, block, components, ssim,
+                                   crop)
 
     def histogram_into(self, pics, desc, records, records_stride, ptrs=None, strides=None, on_stream=0, stream=0):
         """hmgpu_pictures_histogram into device memory the caller owns: `records` the address of [n][4] records, records_stride bytes

@@ -364,6 +364,29 @@ def make_metrics_desc(reference, components=7, ssim=1, ref_bytes_per_sample=0, c
     return d
 
 
+METRICS_MAP_SSE, METRICS_MAP_SAD, METRICS_MAP_DIFFERING, METRICS_MAP_MAX_ABS, METRICS_MAP_SSIM_Q32, METRICS_MAP_SSIM_WINDOWS = range(6)
+METRICS_MAP_FIELDS = 6
+
+
+class MetricsMapDesc(C.Structure):
+    _fields_ = [("log2_block", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class MetricsMapPlan(C.Structure):
+    _fields_ = [("blocks_x", C.c_int32), ("blocks_y", C.c_int32), ("block_w", C.c_int32 * 3), ("block_h", C.c_int32 * 3),
+                ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("channels", C.c_int32 * 3), ("fields", C.c_int32),
+                ("row_bytes", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def make_metrics_map_desc(block=16):
+    """block: the side of a block in luma samples; the call takes 8, 16, 32 or 64 (log2_block 3 .. 6).  Any other size becomes a
+    log2_block the library refuses"""
+    d = MetricsMapDesc()
+    block = int(block)
+    d.log2_block = block.bit_length() - 1 if block > 0 and block & (block - 1) == 0 else -1
+    return d
+
+
 HISTOGRAM_Y, HISTOGRAM_CB, HISTOGRAM_CR, HISTOGRAM_MAXRGB = 0, 1, 2, 3
 
 

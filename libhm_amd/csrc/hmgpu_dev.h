@@ -650,6 +650,30 @@ struct MetricsArgs {
   uint32_t bvec;                          // REF_PLANES, bit c: the same for the planes of component c
 };
 void launch_metrics(const MetricsArgs& a, int ref_kind, bool ssim, hipStream_t s);   // ref_kind: 0 pictures, 1 uint8 planes, 2 uint16 planes
+// picture metric maps (k_metrics_map.hip, hmgpu_pictures_metrics_map): everything by value, validated on the host.  Classes as in
+// MetricsArgs.  A workgroup owns one region of one class of one picture: 64 x 64 luma samples from the crop origin, or the matching
+// (64 >> csx) x (64 >> csy) positions of the pair plane -- (64 / B)^2 whole blocks of either class; work item = (picture, class, region).
+constexpr int kMapRegion = 64;              // luma samples: one block of the largest size
+constexpr int kMapFields = 6;               // HMGPU_METRICS_MAP_FIELDS
+struct MetricsMapArgs {
+  const int16_t* a[kMaxExportBatch][2];   // as MetricsArgs
+  const int16_t* bp[kMaxExportBatch][2];
+  const uint8_t* bq[3];
+  int64_t bpitch[3], bstride[3];
+  uint8_t* maps[3];                       // per component (null: not compared): element (i, f, by, bx) at maps + i * mbstride + f * mfstride + by * mpitch + bx * 8
+  int64_t mpitch[3], mfstride[3], mbstride[3];
+  int64_t c1[2], c2[2];                   // SSIM constants per channel type
+  int32_t n, comps;                       // pictures; the component mask (only components the format has)
+  int32_t w[2], h[2], pitch[2];           // per class: the cropped plane in samples; the source pitch in int16 elements
+  int32_t regions_x[2], regions[2];       // per class: regions per row of them, regions per picture (0: class not selected)
+  int32_t log2_rw[2], log2_rh[2];         // per class: the region in samples, 64 or 32 a side
+  int32_t log2_bw[2], log2_bh[2];         // per class: the block in samples, 4 .. 64 a side
+  int32_t log2_nb;                        // blocks per side of a region: 6 - log2_block
+  int32_t blocks_x, blocks_y;             // the map
+  uint32_t avec[2];                       // as MetricsArgs
+  uint32_t bvec;
+};
+void launch_metrics_map(const MetricsMapArgs& a, int ref_kind, bool ssim, hipStream_t s);   // ref_kind as launch_metrics
 // picture histograms (k_histogram.hip, hmgpu_pictures_histogram): everything by value, validated on the host.  Plane class 0 walks the
 // cropped luma plane and counts Y (channel 0) and maxRGB (channel 3) of a sample together, class 1 the chroma pair plane (channels 1
 // and 2 from one load); a class with no selected channel has no tiles.  Work items and tiles as in MetricsArgs without SSIM.

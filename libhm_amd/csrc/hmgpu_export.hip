@@ -3,8 +3,8 @@
 // rules of the warp; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
 // destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block
-// and residual exports and the reference planes of the picture metrics, the picture histograms (k_export.hip, k_export_px.hip,
-// k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip, k_histogram.hip).
+// and residual exports, the reference planes of the picture metrics and the picture metric maps, the picture histograms (k_export.hip,
+// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip, k_metrics_map.hip, k_histogram.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -1259,6 +1259,46 @@ static hmgpu_status strided_dst_ok(const hmgpu_ctx* c, const Plan& plan, int slo
   return any ? HMGPU_OK : HMGPU_EINVAL;
 }
 
+// what MetricsArgs and MetricsMapArgs share: the SSIM constants, per plane class the cropped plane, per picture the first sample of
+// both sides and whether its groups of 4 take one load, the caller's planes
+template <class Args>
+static void metrics_sources(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
+                            const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, const hmgpu_metrics_plan& plan, int vec,
+                            Args* out) {
+  Args& a = *out;
+  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
+  a.n = n;
+  const int bd[2] = {c->seq.bit_depth_luma, c->seq.bit_depth_chroma};
+  for (int k = 0; k < 2; k++) {
+    const double maxv = (double)((1 << bd[k]) - 1);
+    a.c1[k] = (int64_t)(.01 * .01 * maxv * maxv * 64 + .5);
+    a.c2[k] = (int64_t)(.03 * .03 * maxv * maxv * 64 * 63 + .5);
+    const int comp = k ? (plan.channels[1] ? 1 : 2) : 0;             // a component of the class that is compared, if any
+    if (!plan.channels[comp]) continue;
+    a.w[k] = plan.width[comp]; a.h[k] = plan.height[comp]; a.pitch[k] = c->pitch[k];
+  }
+  for (int k = 0; k < 3; k++) {
+    if (!plan.channels[k]) continue;
+    a.comps |= 1 << k;
+    if (planes) { a.bq[k] = static_cast<const uint8_t*>(ref[k]); a.bpitch[k] = ref_pitch[k]; a.bstride[k] = ref_bstride[k]; }
+  }
+  a.bvec = (uint32_t)vec;
+  const int x0 = d->crop[0], y0 = d->crop[2];
+  for (int i = 0; i < n; i++) {
+    for (int side = 0; side < (planes ? 1 : 2); side++) {
+      const Picture& p = c->pics[side ? ref_pics[i] : pics[i]];
+      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
+      const int16_t* org[2] = {src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0, src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx)};
+      for (int k = 0; k < 2; k++) {
+        (side ? a.bp : a.a)[i][k] = org[k];
+        const size_t g = k ? 16 : 8;                                   // a group of 4 samples, of 4 pairs
+        if (side == 0) a.avec[k] |= 1u << i;
+        if ((uintptr_t)org[k] % g || ((size_t)c->pitch[k] * 2) % g) a.avec[k] &= ~(1u << i);
+      }
+    }
+  }
+}
+
 extern "C" {
 
 // The three argument builders of export_impl -- unscaled, scaled, warp -- each from the resolved call to its launch on hs.  site:
@@ -1816,12 +1856,11 @@ double hmgpu_metrics_psnr(const hmgpu_metrics_result* r, int32_t bit_depth) {
   return 10.0 * std::log10(ref / (double)r->sse);
 }
 
-// everything hmgpu_pictures_metrics checks; vec: bit c: the planes of component c take whole loads of 4 elements
-static hmgpu_status metrics_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
-                                    const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, void* results, int64_t rstride,
-                                    hmgpu_metrics_plan* plan, int* vec) {
-  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  { const hmgpu_status st = metrics_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
+// what hmgpu_pictures_metrics and hmgpu_pictures_metrics_map check of their pictures and of the reference, behind the description's plan;
+// vec: bit c: the planes of component c take whole loads of 4 elements
+static hmgpu_status metrics_inputs_ok(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
+                                      const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, const hmgpu_metrics_plan* plan,
+                                      int* vec) {
   for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
   *vec = 0;
   if (d->reference == HMGPU_METRICS_REF_PICTURES) {
@@ -1834,6 +1873,16 @@ static hmgpu_status metrics_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pi
     const hmgpu_status st = strided_dst_ok(c, *plan, 3, n, const_cast<void* const*>(ref), ref_pitch, nullptr, ref_bstride, 0, vec);
     if (st != HMGPU_OK) return st;
   }
+  return HMGPU_OK;
+}
+
+// everything hmgpu_pictures_metrics checks
+static hmgpu_status metrics_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
+                                    const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, void* results, int64_t rstride,
+                                    hmgpu_metrics_plan* plan, int* vec) {
+  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = metrics_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = metrics_inputs_ok(c, n, pics, d, ref_pics, ref, ref_pitch, ref_bstride, plan, vec); if (st != HMGPU_OK) return st; }
   const int64_t rec = plan->result_bytes;
   if (!results || (uintptr_t)results % 8 || rstride < rec || rstride % 8 || rstride > ((int64_t)1 << 40)) return HMGPU_EINVAL;
   if (!device_span_ok(results, (size_t)((n - 1) * rstride + rec), c->device)) return HMGPU_EINVAL;
@@ -1861,39 +1910,13 @@ hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* c, int32_t n, const hmgpu_pic pic
   const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
   MetricsArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = n;
   a.results = static_cast<uint8_t*>(results); a.rstride = results_batch_stride_bytes;
-  const int bd[2] = {c->seq.bit_depth_luma, c->seq.bit_depth_chroma};
+  metrics_sources(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, plan, vec, &a);
   for (int k = 0; k < 2; k++) {
-    const double maxv = (double)((1 << bd[k]) - 1);
-    a.c1[k] = (int64_t)(.01 * .01 * maxv * maxv * 64 + .5);
-    a.c2[k] = (int64_t)(.03 * .03 * maxv * maxv * 64 * 63 + .5);
-    const int comp = k ? (plan.channels[1] ? 1 : 2) : 0;             // a component of the class that is compared, if any
-    if (!plan.channels[comp]) continue;
-    a.w[k] = plan.width[comp]; a.h[k] = plan.height[comp]; a.pitch[k] = c->pitch[k];
+    if (!a.w[k]) continue;
     const int tw = d->ssim ? kMetricsTileW : kMetricsRowTileW, th = d->ssim ? kMetricsTileH : kMetricsRowTileH;
     a.tiles_x[k] = (a.w[k] + tw - 1) / tw;
     a.tiles[k] = a.tiles_x[k] * ((a.h[k] + th - 1) / th);
-  }
-  for (int k = 0; k < 3; k++) {
-    if (!plan.channels[k]) continue;
-    a.comps |= 1 << k;
-    if (planes) { a.bq[k] = static_cast<const uint8_t*>(ref[k]); a.bpitch[k] = ref_pitch_bytes[k]; a.bstride[k] = ref_batch_stride_bytes[k]; }
-  }
-  a.bvec = (uint32_t)vec;
-  const int x0 = d->crop[0], y0 = d->crop[2];
-  for (int i = 0; i < n; i++) {
-    for (int side = 0; side < (planes ? 1 : 2); side++) {
-      const Picture& p = c->pics[side ? ref_pics[i] : pics[i]];
-      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-      const int16_t* org[2] = {src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0, src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx)};
-      for (int k = 0; k < 2; k++) {
-        (side ? a.bp : a.a)[i][k] = org[k];
-        const size_t g = k ? 16 : 8;                                   // a group of 4 samples, of 4 pairs
-        if (side == 0) a.avec[k] |= 1u << i;
-        if ((uintptr_t)org[k] % g || ((size_t)c->pitch[k] * 2) % g) a.avec[k] &= ~(1u << i);
-      }
-    }
   }
   a.total = n * (a.tiles[0] + a.tiles[1]);
   const int grid = d->ssim ? kMetricsGridSsim : kMetricsGrid;
@@ -1902,6 +1925,110 @@ hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* c, int32_t n, const hmgpu_pic pic
   if (n == 1 || a.rstride == rec) HIP_TRY(c, hipMemsetAsync(results, 0, (size_t)(n * rec), hs));
   else HIP_TRY(c, hipMemset2DAsync(results, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
   launch_metrics(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
+  if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+// ------------------------------------------------------------------------------------------------ picture metric maps (k_metrics_map.hip)
+// what strided_dst_ok needs to know of the maps: per component `fields` planes of blocks_y rows of blocks_x int64 elements
+struct MapDstPlan { int32_t channels[3], height[3], elem_bytes[3], row_bytes[3]; };
+
+// hmgpu_metrics_map_plan_for: the refusals of the metrics description first (mp: its plan), then those of the map's own
+static hmgpu_status metrics_map_plan(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
+                                     hmgpu_metrics_plan* mp, hmgpu_metrics_map_plan* out) {
+  if (!out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  { const hmgpu_status st = metrics_plan(seq, d, mp); if (st != HMGPU_OK) return st; }
+  if (!md || md->log2_block < 3 || md->log2_block > 6) return HMGPU_EINVAL;
+  for (int k = 0; k < 7; k++) if (md->reserved[k]) return HMGPU_EINVAL;
+  int W, H, csx, csy;
+  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
+  chroma_shifts(seq->chroma_format, &csx, &csy);
+  const int B = 1 << md->log2_block;
+  out->blocks_x = (W + B - 1) / B; out->blocks_y = (H + B - 1) / B;
+  for (int k = 0; k < 3; k++) {
+    if (!mp->channels[k]) continue;
+    out->channels[k] = 1; out->width[k] = mp->width[k]; out->height[k] = mp->height[k];
+    out->block_w[k] = k ? B >> csx : B; out->block_h[k] = k ? B >> csy : B;
+  }
+  out->fields = d->ssim ? HMGPU_METRICS_MAP_FIELDS : 4;
+  out->row_bytes = out->blocks_x * 8;
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_metrics_map_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
+                                        hmgpu_metrics_map_plan* out) {
+  hmgpu_metrics_plan mp;
+  const hmgpu_status st = metrics_map_plan(seq, d, md, &mp, out);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// everything hmgpu_pictures_metrics_map checks
+static hmgpu_status metrics_map_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
+                                        const hmgpu_pic* ref_pics, const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride,
+                                        void* const* maps, const int64_t* pitch, const int64_t* fstride, const int64_t* bstride,
+                                        hmgpu_metrics_plan* mp, hmgpu_metrics_map_plan* plan, int* vec) {
+  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  { const hmgpu_status st = metrics_map_plan(&c->seq, d, md, mp, plan); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = metrics_inputs_ok(c, n, pics, d, ref_pics, ref, ref_pitch, ref_bstride, mp, vec); if (st != HMGPU_OK) return st; }
+  if (!maps || !pitch || !fstride || !bstride) return HMGPU_EINVAL;
+  MapDstPlan dp;
+  memset(&dp, 0, sizeof(dp));
+  for (int k = 0; k < 3; k++) {
+    if (!plan->channels[k]) continue;                                  // (a map of a component that is not compared: strided_dst_ok refuses it)
+    if (!maps[k]) return HMGPU_EINVAL;
+    dp.channels[k] = plan->fields; dp.height[k] = plan->blocks_y; dp.elem_bytes[k] = 8; dp.row_bytes[k] = plan->row_bytes;
+  }
+  int mvec = 0;
+  return strided_dst_ok(c, dp, 3, n, maps, pitch, fstride, bstride, 8, &mvec);
+}
+
+hmgpu_status hmgpu_metrics_map_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
+                                     const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                                     const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
+                                     const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3]) {
+  hmgpu_metrics_plan mp;
+  hmgpu_metrics_map_plan plan;
+  int vec = 0;
+  return metrics_map_resolve(c, n, pics, d, md, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes, map_field_stride_bytes,
+                             map_batch_stride_bytes, &mp, &plan, &vec);
+}
+
+hmgpu_status hmgpu_pictures_metrics_map(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
+                                        const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                                        const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
+                                        const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3], int32_t on_stream,
+                                        void* stream) {
+  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
+  hmgpu_metrics_plan mp;
+  hmgpu_metrics_map_plan plan;
+  int vec = 0;
+  { const hmgpu_status st = metrics_map_resolve(c, n, pics, d, md, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes,
+                                                map_field_stride_bytes, map_batch_stride_bytes, &mp, &plan, &vec);
+    if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  MetricsMapArgs a;
+  memset(&a, 0, sizeof(a));
+  metrics_sources(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, mp, vec, &a);
+  for (int k = 0; k < 3; k++) {
+    if (!plan.channels[k]) continue;
+    a.maps[k] = static_cast<uint8_t*>(maps[k]);
+    a.mpitch[k] = map_pitch_bytes[k]; a.mfstride[k] = map_field_stride_bytes[k]; a.mbstride[k] = map_batch_stride_bytes[k];
+  }
+  for (int k = 0; k < 2; k++) {
+    a.log2_rw[k] = 6 - (k ? c->csx : 0); a.log2_rh[k] = 6 - (k ? c->csy : 0);
+    a.log2_bw[k] = md->log2_block - (k ? c->csx : 0); a.log2_bh[k] = md->log2_block - (k ? c->csy : 0);
+    if (!a.w[k]) continue;
+    const int rw = 1 << a.log2_rw[k], rh = 1 << a.log2_rh[k];
+    a.regions_x[k] = (a.w[k] + rw - 1) / rw;
+    a.regions[k] = a.regions_x[k] * ((a.h[k] + rh - 1) / rh);
+  }
+  a.log2_nb = 6 - md->log2_block;
+  a.blocks_x = plan.blocks_x; a.blocks_y = plan.blocks_y;
+  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
+  launch_metrics_map(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
   if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
   return export_end(c, n, pics, on_stream, hs);
 }

@@ -15,12 +15,11 @@
 // a window is the sum of a 2x2 group of blocks.  The apron is left out of the distortion terms.  desc->ssim == 0 is an instance of its
 // own: row-major lanes on 256 x 8 tiles (a wave's load is one run of 512 bytes of a luma row), no apron, no LDS staging.
 #include "hmgpu_dev.h"
+#include "metrics_core.h"
 
 namespace hmgpu {
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kBlocksX = kMetricsTileW / 4 + 1, kBlocksY = kMetricsTileH / 4 + 1;   // 4x4 blocks of a tile and its apron: 17 x 9
 constexpr int kUnitsSsim = kBlocksX * kBlocksY * 4;                                  // groups of 4 samples, block-major: 612
@@ -31,54 +30,12 @@ struct Acc {                      // what one lane has seen of one component sin
   u64 sse, sad; long long ssim;
   uint32_t samples, differing, windows, max_abs, first;   // first: y * w + x, below 2^32 - 1 (metrics_plan); ~0u: none
 };
-struct BlockSum { u64 ss, s12; uint32_t s1, s2; };   // of one 4x4 block: sum (a^2 + b^2), sum ab, sum a, sum b
 
 __device__ inline void acc_clear(Acc& c) { c.sse = c.sad = 0; c.first = ~0u; c.ssim = 0; c.samples = c.differing = c.windows = c.max_abs = 0; }
 
-// a 24-bit by 24-bit product, low 32 bits, unsigned (the intrinsic's result type is not relied on)
-__device__ inline uint32_t mul24(uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); }
-__device__ inline uint32_t xor32(uint32_t v, int m) { return (uint32_t)__shfl_xor((int)v, m, 64); }
-__device__ inline u64 xor64(u64 v, int m) { return ((u64)xor32((uint32_t)(v >> 32), m) << 32) | xor32((uint32_t)v, m); }
 __device__ inline u64 wave_sum(u64 v) { for (int m = 32; m; m >>= 1) v += xor64(v, m); return v; }
 __device__ inline u64 wave_min(u64 v) { for (int m = 32; m; m >>= 1) { const u64 o = xor64(v, m); v = o < v ? o : v; } return v; }
 __device__ inline uint32_t wave_max(uint32_t v) { for (int m = 32; m; m >>= 1) v = max(v, xor32(v, m)); return v; }
-
-// 4 samples of one component (NC 1) or 4 Cb / Cr pairs (NC 2) at p: one load where the group is whole and aligned, else sample by
-// sample up to nv; the rest stays 0
-template <int NC>
-__device__ inline void load_pic(const int16_t* p, bool vec, int nv, int v[NC][4]) {
-  if (vec) {
-    if (NC == 1) {
-      const u32x2 q = ldg2(p);
-      v[0][0] = (int16_t)(q.x & 0xffff); v[0][1] = (int16_t)(q.x >> 16); v[0][2] = (int16_t)(q.y & 0xffff); v[0][3] = (int16_t)(q.y >> 16);
-    } else {
-      const u32x4 q = ldg4(p);
-      const uint32_t d[4] = {q.x, q.y, q.z, q.w};
-      for (int j = 0; j < 4; j++) { v[0][j] = (int16_t)(d[j] & 0xffff); v[NC - 1][j] = (int16_t)(d[j] >> 16); }
-    }
-  } else {
-    for (int j = 0; j < 4; j++)
-      if (j < nv)
-        for (int k = 0; k < NC; k++) v[k][j] = ldg(p + NC * j + k);
-  }
-}
-
-// 4 elements of a caller's plane: uint8 (ES 1) or uint16 (ES 2)
-template <int ES>
-__device__ inline void load_plane(const uint8_t* p, bool vec, int nv, int v[4]) {
-  if (vec) {
-    if (ES == 1) {
-      const uint32_t q = ldg(reinterpret_cast<const uint32_t*>(p));
-      for (int j = 0; j < 4; j++) v[j] = (int)((q >> (8 * j)) & 0xff);
-    } else {
-      const u32x2 q = ldg2(p);
-      v[0] = (int)(q.x & 0xffff); v[1] = (int)(q.x >> 16); v[2] = (int)(q.y & 0xffff); v[3] = (int)(q.y >> 16);
-    }
-  } else {
-    for (int j = 0; j < 4; j++)
-      if (j < nv) v[j] = ES == 1 ? (int)ldg(p + j) : (int)ldg(reinterpret_cast<const uint16_t*>(p) + j);
-  }
-}
 
 // One tile of plane class CLS of picture `pic`: NC = 1 + CLS components at once.  blk: the block sums of the SSIM instance.
 template <int REF, bool SSIM, int CLS>
@@ -148,16 +105,8 @@ __device__ inline void tile_pass(const MetricsArgs& a, int pic, int tile, Acc ac
     }
     if (SSIM) {
       for (int k = 0; k < NC; k++) {
-        uint32_t s1 = 0, s2 = 0;
-        u64 ss = 0, s12 = 0;
-        for (int j = 0; j < 4; j++) {
-          const uint32_t p = (uint32_t)va[k][j], q = (uint32_t)vb[k][j];
-          s1 += p; s2 += q;
-          ss += (u64)mul24(p, p) + (u64)mul24(q, q);
-          s12 += (u64)mul24(p, q);
-        }
-        for (int m = 1; m <= 2; m <<= 1) { s1 += xor32(s1, m); s2 += xor32(s2, m); ss += xor64(ss, m); s12 += xor64(s12, m); }
-        if ((u & 3) == 0 && u < kUnitsSsim) { BlockSum& o = blk[k][b4]; o.ss = ss; o.s12 = s12; o.s1 = s1; o.s2 = s2; }
+        const BlockSum sums = block_sums(va[k], vb[k]);
+        if ((u & 3) == 0 && u < kUnitsSsim) blk[k][b4] = sums;
       }
     }
   }
@@ -168,15 +117,7 @@ __device__ inline void tile_pass(const MetricsArgs& a, int pic, int tile, Acc ac
       if (tx0 + 4 * bx + 8 <= w && ty0 + 4 * by + 8 <= h) {
         const long long c1 = a.c1[CLS], c2 = a.c2[CLS];
         for (int k = 0; k < NC; k++) {
-          long long s1 = 0, s2 = 0, ss = 0, s12 = 0;
-          for (int q = 0; q < 4; q++) {
-            const BlockSum& b = blk[k][(by + (q >> 1)) * kBlocksX + bx + (q & 1)];
-            s1 += b.s1; s2 += b.s2; ss += (long long)b.ss; s12 += (long long)b.s12;
-          }
-          const long long vars = 64 * ss - s1 * s1 - s2 * s2, covar = 64 * s12 - s1 * s2;
-          const double num = (double)(2 * s1 * s2 + c1) * (double)(2 * covar + c2);
-          const double den = (double)(s1 * s1 + s2 * s2 + c1) * (double)(vars + c2);
-          acc[k].ssim += __double2ll_rn((num / den) * 4294967296.0);
+          acc[k].ssim += window_q32(&blk[k][by * kBlocksX + bx], 1, kBlocksX, c1, c2);
           acc[k].windows++;
         }
       }

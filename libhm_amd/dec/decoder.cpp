@@ -1218,6 +1218,33 @@ hmgpu_status Decoder::metrics(int n, PicData* const* pics, const hmgpu_metrics_d
         return hmgpu_pictures_metrics(c, rn, h, desc, nullptr, d, ref_pitch_bytes, bs, d[3], bs[3], on_stream, stream); });
 }
 
+// hmgpu_pictures_metrics_map likewise, the maps the destinations behind the reference planes
+hmgpu_status Decoder::metrics_map(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const hmgpu_metrics_map_desc* map, const void* const ref[3],
+                                  const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* const maps[3],
+                                  const int64_t map_pitch_bytes[3], const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3],
+                                  int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  if (desc->reference != HMGPU_METRICS_REF_PLANES) {
+    set_error("hmdec_pictures_metrics_map: decoded pictures are compared with planes of the caller (HMGPU_METRICS_REF_PLANES) only");
+    return HMGPU_EUNSUPPORTED;
+  }
+  if (!ref || !ref_pitch_bytes || !ref_batch_stride_bytes || !maps || !map_batch_stride_bytes) return HMGPU_EINVAL;
+  void* const dst[6] = {const_cast<void*>(ref[0]), const_cast<void*>(ref[1]), const_cast<void*>(ref[2]), maps[0], maps[1], maps[2]};
+  const int64_t stride[6] = {ref_batch_stride_bytes[0], ref_batch_stride_bytes[1], ref_batch_stride_bytes[2],
+                             map_batch_stride_bytes[0], map_batch_stride_bytes[1], map_batch_stride_bytes[2]};
+  return export_side<6>(n, pics, nullptr, dst, stride,
+      [&](hmgpu_ctx* c) {
+        hmgpu_pic all[HMGPU_EXPORT_MAX_BATCH];
+        for (int i = 0; i < n; i++) all[i] = pics[0]->handle;
+        return hmgpu_metrics_map_check(c, n, all, desc, map, nullptr, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes,
+                                       map_field_stride_bytes, map_batch_stride_bytes); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const* d, const int64_t* bs) {
+        return hmgpu_metrics_map_check(c, rn, h, desc, map, nullptr, d, ref_pitch_bytes, bs, d + 3, map_pitch_bytes, map_field_stride_bytes, bs + 3); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window*, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_metrics_map(c, rn, h, desc, map, nullptr, d, ref_pitch_bytes, bs, d + 3, map_pitch_bytes, map_field_stride_bytes, bs + 3,
+                                          on_stream, stream); });
+}
+
 // hmgpu_pictures_histogram likewise, the records the fifth destination behind the histograms (null: a call without histograms)
 hmgpu_status Decoder::histogram(int n, PicData* const* pics, const hmgpu_histogram_desc* desc, void* const hist[4], const int64_t hist_batch_stride_bytes[4],
                                 void* records, int64_t records_batch_stride_bytes, int on_stream, void* stream) {

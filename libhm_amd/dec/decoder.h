@@ -109,6 +109,10 @@ class Decoder {
   // hmgpu_pictures_metrics against the caller's planes (HMGPU_METRICS_REF_PLANES), the pictures grouped by context as above
   hmgpu_status metrics(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const void* const ref[3], const int64_t ref_pitch_bytes[3],
                        const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes, int on_stream, void* stream);
+  // hmgpu_pictures_metrics_map likewise
+  hmgpu_status metrics_map(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const hmgpu_metrics_map_desc* map, const void* const ref[3],
+                           const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
+                           const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3], int on_stream, void* stream);
   // hmgpu_pictures_histogram, the pictures grouped by context as above; refused with a message without device output
   hmgpu_status histogram(int n, PicData* const* pics, const hmgpu_histogram_desc* desc, void* const hist[4], const int64_t hist_batch_stride_bytes[4],
                          void* records, int64_t records_batch_stride_bytes, int on_stream, void* stream);
@@ -131,7 +135,7 @@ class Decoder {
   void submit_picture(PicData* pic, int parsed_ctbs);     // marks of a completely parsed picture; its device work joins the batch
   void flush_batch();                                     // the device work of the pictures retired together (hmgpu_decompress_pictures / hmgpu_filter_pictures)
   __attribute__((visibility("hidden"))) hmgpu_status export_pics_ok(int n, PicData* const* pics);   // what every batched export asks of its pictures (their device work enqueued first)
-  // export_motion / export_residual / metrics / histogram: SLOTS destinations; check: the whole call's check on a context; side: the
+  // export_motion / export_residual / metrics / metrics_map / histogram: SLOTS destinations; check: the whole call's check on a context; side: the
   // check of one run (context, n, handles, destinations, batch strides); run: its export (..., handles, windows, destinations, ...)
   template <int SLOTS, class Check, class Side, class Run>
   hmgpu_status export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,

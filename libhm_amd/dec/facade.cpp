@@ -416,6 +416,16 @@ int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const
   return static_cast<Wrapper*>(ctx)->dec.metrics(n, p, desc, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes,
                                                  on_stream, stream);
 }
+int hmdec_pictures_metrics_map(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc,
+                               const hmgpu_metrics_map_desc* map, const void* const ref[3], const int64_t ref_pitch_bytes[3],
+                               const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
+                               const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.metrics_map(n, p, desc, map, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes,
+                                                     map_field_stride_bytes, map_batch_stride_bytes, on_stream, stream);
+}
 int hmdec_pictures_histogram(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_histogram_desc* desc, void* const hist[4],
                              const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes, int on_stream,
                              void* stream) {

@@ -109,6 +109,10 @@ def lib():
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        L.hmdec_pictures_metrics_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc),
+                                                 C.POINTER(abi.MetricsMapDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                                 C.c_void_p]
         L.hmdec_pictures_histogram.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.HistogramDesc), C.POINTER(C.c_void_p),
                                                C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_picture_device.argtypes = [C.c_void_p]
@@ -300,6 +304,11 @@ class Picture:
         out = metrics_batch([self], [None if t is None else t[None] for t in ref], components, ssim, crop)
         return {k: {f: t[0] for f, t in v.items()} for k, v in out.items()}
 
+    def metrics_map(self, ref, block=16, components=(0, 1, 2), ssim=True, crop=None):
+        """metrics_map_batch of this picture alone: ref the planes [h_c, w_c] per component; the maps [Hb, Wb] without the batch dimension"""
+        out = metrics_map_batch([self], [None if t is None else t[None] for t in ref], block, components, ssim, crop)
+        return {k: {f: t[0] for f, t in v.items()} for k, v in out.items()}
+
     def histogram(self, channels=("y", "cb", "cr"), bins=None, crop="conformance", matrix=None, full_range=None, rgb_bit_depth=0,
                   histogram=True):
         """histogram_batch of this picture alone: the histograms and fields without the batch dimension"""
@@ -383,6 +392,27 @@ def metrics_batch(pictures, ref, components=(0, 1, 2), ssim=True, crop=None):
             why = lib().hmdec_last_error(first.ctx).decode() if r == abi.HMGPU_EUNSUPPORTED else ""
             raise HmgpuError(r, "hmdec_pictures_metrics" + (": " + why if why else ""))
     return metrics.metrics(call, seq, dev, len(pictures), None, ref, components, ssim, crop)
+
+
+def metrics_map_batch(pictures, ref, block=16, components=(0, 1, 2), ssim=True, crop=None):
+    """The comparison of metrics_batch kept per block of block x block luma samples (hmdec_pictures_metrics_map): the pictures, ref and
+    crop as there; the result dict of libhm_amd.metrics.metrics_map, maps [n, Hb, Wb] per component and field, written on
+    torch.cuda.current_stream()."""
+    from . import HmgpuError, metrics
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("metrics_map_batch: no pictures")
+    first, seq, crop = _prologue(pictures, "metrics_map_batch", crop, lambda: (0, 0, 0, 0))
+    dev = _device(first, "metrics_map_batch")
+
+    def call(desc, md, ref_pics, ptrs, pitches, bstrides, maps, mp, mf, mb, st):
+        r = lib().hmdec_pictures_metrics_map(first.ctx, len(pictures), _handles(pictures), C.byref(desc), C.byref(md),
+                                             *metrics.c_args(None, ptrs, pitches, bstrides)[1:], *metrics.map_c_args(maps, mp, mf, mb), 1,
+                                             abi.addr(st))
+        if r != 0:
+            why = lib().hmdec_last_error(first.ctx).decode() if r == abi.HMGPU_EUNSUPPORTED else ""
+            raise HmgpuError(r, "hmdec_pictures_metrics_map" + (": " + why if why else ""))
+    return metrics.metrics_map(call, seq, dev, len(pictures), None, ref, block, components, ssim, crop)
 
 
 def histogram_batch(pictures, channels=("y", "cb", "cr"), bins=None, crop="conformance", matrix=None, full_range=None, rgb_bit_depth=0,
