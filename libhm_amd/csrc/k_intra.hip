@@ -29,20 +29,11 @@ namespace {
 
 
 // coherent accesses to the picture being reconstructed
-#if defined(INTRA_EXP) && (INTRA_EXP & 64)      // experiment (stale samples possible): plain loads
-__device__ inline uint32_t ld_coh(const uint32_t* p) { return *p; }
-#else
 __device__ inline uint32_t ld_coh(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
-#if defined(INTRA_EXP) && (INTRA_EXP & 32)      // experiment (other CTUs may read stale samples): plain stores
-__device__ inline void st_coh(uint32_t* p, uint32_t v) { *p = v; }
-__device__ inline void st_coh2(uint32_t* p, uint32_t v0, uint32_t v1) { *(unsigned long long*)p = (unsigned long long)v0 | ((unsigned long long)v1 << 32); }
-#else
 __device__ inline void st_coh(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void st_coh2(uint32_t* p, uint32_t v0, uint32_t v1) {         // four samples, p 8-byte aligned
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v0 | ((unsigned long long)v1 << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#endif
 // chroma (hmgpu_dev.h "chroma planes": Cb and Cr alternate in one plane, another workgroup writes the other component of every dword): the
 // pairs of two positions in one 8-byte access, this component's halves out of them; stores go sample by sample
 __device__ inline uint32_t ld_coh_c2(const int16_t* pair, int half) {              // pair: 8-byte aligned, the (Cb, Cr) of two positions
@@ -50,10 +41,6 @@ __device__ inline uint32_t ld_coh_c2(const int16_t* pair, int half) {           
   return __builtin_amdgcn_perm((uint32_t)(w >> 32), (uint32_t)w, half ? 0x07060302u : 0x05040100u);
 }
 __device__ inline void st_coh_c2(int16_t* p, uint32_t v) {                         // two samples of one component, kCStep apart
-#if defined(INTRA_EXP) && (INTRA_EXP & 32)
-  *(uint16_t*)p = (uint16_t)(v & 0xffffu); *(uint16_t*)(p + kCStep) = (uint16_t)(v >> 16);
-  return;
-#endif
   __hip_atomic_store(reinterpret_cast<uint16_t*>(p), (uint16_t)(v & 0xffffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(reinterpret_cast<uint16_t*>(p + kCStep), (uint16_t)(v >> 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -63,33 +50,18 @@ __device__ inline int ld_sample(const int16_t* p) {
   return (int)(int16_t)((a & 2) ? (w >> 16) : (w & 0xffffu));
 }
 
-#ifndef INTRA_LEAN_OCC
-#define INTRA_LEAN_OCC 4                 // waves per SIMD the LEAN kernel is compiled for (128 VGPRs; it would take 130)
-#endif
-#ifndef INTRA_MANY_OCC
-#define INTRA_MANY_OCC 4                 // ... and the three-wave kernel of batches (128 VGPRs and 44 bytes of scratch instead of 147: a fifth workgroup per CU,
-#endif                                   // sixteen I pictures 7.38 -> 6.82 ms; the eight-wave kernel of single pictures is latency, not residency: left alone)
-#ifndef INTRA_SPARSE_MAX
-#define INTRA_SPARSE_MAX 16              // in 64ths of a CTU's 8x8 areas: at most this share intra -> the CTU is not staged (k_intra)
-#endif
+constexpr int kIntraLeanOcc = 4;         // waves per SIMD the LEAN kernel is compiled for (128 VGPRs; it would take 130)
+constexpr int kIntraManyOcc = 4;         // ... and the three-wave kernel of batches (128 VGPRs and 44 bytes of scratch instead of 147: a fifth workgroup per CU,
+                                         // sixteen I pictures 7.38 -> 6.82 ms; the eight-wave kernel of single pictures is latency, not residency: left alone)
+constexpr int kIntraSparseMax = 16;      // in 64ths of a CTU's 8x8 areas: at most this share intra -> the CTU is not staged (k_intra)
 
 struct IntraScratch {                    // what ONE TU in flight needs: one per wave
   int line[4 * 32 + 4];                  // reference line: [0,2N) left column bottom-up, [2N] corner, (2N,4N] row above
   int filt[4 * 32 + 4];                  // the same after smoothing
   int proj[3 * 32 + 4];                  // angular modes: main reference incl. the projected side samples, index k + 32
-#ifdef INTRA_TIMING2                 // diagnostic build: shader-clock cycles per phase of the TU path, summed per wave (printed by k_intra)
-  unsigned tm[16];
-#endif
 };
-// LEAN: the kernel for calls whose CTUs are ALL taken as sparse (k_intra): no copy of the samples and of the residual at all
-#ifdef INTRA_TIMING2
-#define TK_START() long long tk0 = clock64()
-#define TK(k) { const long long tkc = clock64(); if ((threadIdx.x & 63) == 0) W.tm[k] += (unsigned)(tkc - tk0); tk0 = tkc; }
-#else
-#define TK_START()
-#define TK(k)
-#endif
 
+// LEAN: the kernel for calls whose CTUs are ALL taken as sparse (k_intra): no copy of the samples and of the residual at all
 template <bool LEAN>
 struct IntraLdsT {
   static constexpr bool lean = LEAN;
@@ -164,7 +136,6 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
 
   const int n = lane & (N - 1);
   const bool active = lane < N;
-  TK_START();
 
   // the residual of row n: from the CTU's staged tiles (D.); a sparse CTU has none: from the picture's tiles, on its way while the
   // reference line is built (k_itx computed it in an earlier launch; RExt rotation / RDPCM included)
@@ -228,18 +199,13 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
     W.line[i] = v;
   }
   wave_lds_sync();
-  TK(0)
 
   // ---- B. smoothing (filteringIntraReferenceSamples + initAdiPatternChType); most TUs are not smoothed (chroma, 4x4, DC,
   // the modes near horizontal / vertical) and predict straight from line[]: one LDS round trip less on the serial chain
   const int thr = LOG2N == 2 ? 10 : LOG2N == 3 ? 7 : LOG2N == 4 ? 1 : 0;
   // (filterIntraReferenceSamples, TComChromaFormat.h:150-153: luma, and chroma where it is not subsampled)
   const bool filt = (comp == 0 || t.fmt == 3) && t.mode != 1 && min(abs(t.mode - 10), abs(t.mode - 26)) > thr && !(t.rext & HMGPU_REXT_INTRA_SMOOTHING_DISABLED);
-#if defined(INTRA_EXP) && (INTRA_EXP & 2)      // experiment: no smoothing pass
-  if (false) {
-#else
   if (filt) {
-#endif
     bool strong = false;
     int bl = 0, tl = 0, tr = 0;
     if (N == 32 && t.strong && comp == 0) {                 // (strong smoothing: luma only, TComPattern.cpp:196)
@@ -265,25 +231,14 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
     }
     wave_lds_sync();
   }
-  TK(1)
 
   // ---- C. prediction of row n by lane n
-#if defined(INTRA_EXP) && (INTRA_EXP & 2)
-  const int* f = W.line;
-#else
   const int* f = filt ? W.filt : W.line;
-#endif
 
   const bool edge = comp == 0 && N <= 16;                   // MAXIMUM_INTRA_FILTERED_WIDTH (TypeDef.h:117)
   // implicit RDPCM in a lossless CU: horizontal / vertical prediction without its edge filter (TComPrediction.cpp:476)
   const bool edge_ang = edge && !(t.bypass && (t.rext & HMGPU_REXT_IMPLICIT_RDPCM));
   int p[N];
-#if defined(INTRA_EXP) && (INTRA_EXP & 8)      // experiment (wrong samples): the row above copied down -- what the mode-specific prediction code costs
-  if (true) {
-#pragma unroll
-    for (int x = 0; x < N; x++) p[x] = f[corner + 1 + x];
-  } else
-#endif
   if (t.mode == 0) {
     const int left = f[corner - 1 - n], bl = f[corner - 1 - N], tr = f[corner + 1 + N];
 #pragma unroll
@@ -377,13 +332,8 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
     }
   }
 
-  TK(2)
   // ---- D. residual of row n: from the CTU's staged tiles
-#if defined(INTRA_EXP) && (INTRA_EXP & 1)      // experiment: no residual (wrong samples)
-  if (false) {
-#else
   if (!sparse && t.cbf && active) {
-#endif
     const int rx = t.x0 - t.cx0, ry = t.y0 - t.cy0 + n;                    // inside the CTU, component samples
     const int tpr = ((1 << t.log2ctu) >> cs) >> 3;                          // tiles per CTU row
     const int16_t* r = &L.res[((ry >> 3) * tpr + (rx >> 3)) * 64 + resid_slot(ry) * 8];
@@ -394,7 +344,6 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
     }
   }
 
-  TK(3)
   // ---- E. reconstruction of row n: into the LDS copy (what later TUs of this CTU predict from) and, two samples per
   // coherent dword store, into the picture (what other CTUs and the loop filters read; nobody here waits for it)
   if (active) {
@@ -423,7 +372,6 @@ __device__ __attribute__((always_inline)) inline void intra_tu(const PicDev& P, 
   // (sparse CTU: whoever predicts from this TU next -- this wave or another -- loads its samples from the picture: acknowledged first)
   if (sparse) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_lds_sync();
-  TK(4)
 }
 
 template <class IntraLds>
@@ -532,10 +480,6 @@ struct IntraSchedT {
   uint32_t pend[8];                  // list entries nobody has taken yet (bit i & 31 of pend[i >> 5]); a wave takes one with an atomic AND
   uint8_t member[64][4];             // list entries of the four 4x4 luma TUs of every 8x8 area (kinds 2 and 3), by z >> 2 and z & 3
   int32_t n_tus;                     // list length
-#ifdef INTRA_TIMING                  // diagnostic build: where the time of a CTU goes (printed by k_intra for one CTU row)
-  unsigned long long t_tu, t_claim, t_post, t_idle, t_first, t_last, t_a, t_b, t_c;
-  uint32_t n_run, n_idle;
-#endif
 };
 
 struct Neighbours {
@@ -656,9 +600,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
     x4 = zscan_x(e.z); y4 = zscan_y(e.z);
     U = e.kind ? (1 << (e.log2n - 2)) : max(1, ((1 << e.log2n) << cs) >> 2);
   };
-#if defined(INTRA_STOP) && INTRA_STOP == 6
-  if (IntraLds::lean && pw > 0 && nb_same >= 0 && h_plane != nullptr && h_resid != nullptr) return;
-#endif
   // mode | coded << 6 | lossless << 7 of the TU of list entry e (IntraSched::put)
   auto tu_desc = [&](const TuRun& e) -> uint32_t {
     if (e.kind == 1) return 0u;
@@ -713,9 +654,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
         }
       }
     }
-#if defined(INTRA_STOP) && INTRA_STOP == 7
-    if (IntraLds::lean && pw > 0) { if (cnt) Q.tu[lane] = e; return; }
-#endif
     // the done masks per row / column of UNITS: an area's bit for both of its units
     const unsigned long long m0 = __builtin_amdgcn_ballot_w64(preset[0]), m1 = __builtin_amdgcn_ballot_w64(preset[1]);
     if (lane < pw) {
@@ -739,12 +677,9 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
     n_tus = n_sched + 3 * __popcll(c4);
   }
   wave_lds_sync();
-#if defined(INTRA_STOP) && INTRA_STOP == 4     // (LEAN kernel only: one wave, nobody is left at the barrier)
-  if (IntraLds::lean && pw > 0) return;
-#endif
   // ---- 2. what each TU depends on.  A short list (scattered intra CUs in a P picture, a CTU of a few large TUs): the TUs one after the other, the
   // lanes over the units of each -- a 32x32 TU has 33 reference units and as many column / row units to test, which one lane walking them
-  // alone made the longest part of a sparse CTU's life (6-8 of ~18 us, INTRA_TIMING).  A long list: the lanes over the TUs, as before.
+  // alone made the longest part of a sparse CTU's life (6-8 of ~18 us, measured with clock probes).  A long list: the lanes over the TUs, as before.
   if (n_tus <= 12) {
     for (int i = 0; i < n_tus; i++) {
       const TuRun e = __builtin_bit_cast(TuRun, (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_bit_cast(uint32_t, Q.tu[i])));
@@ -764,11 +699,7 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
         if (u < 2 * U) { px = lx - 4; py = ly + 4 * (2 * U - 1 - u); }
         else if (u == 2 * U) { px = lx - 4; py = ly - 4; }
         else { px = lx + 4 * (u - 2 * U - 1); py = ly - 4; }
-#if defined(INTRA_EXP) && (INTRA_EXP & 4)
-        ab = px >= 0 && py >= 0;
-#else
         ab = intra_avail(P, ctu, e.z, px, py, cip != 0, (unsigned)nb_same, L.m_pred);
-#endif
       }
       const uint32_t nc = (uint32_t)__builtin_amdgcn_ballot_w64(colbit);
       const uint64_t nr = __builtin_amdgcn_ballot_w64(rowbit), am = __builtin_amdgcn_ballot_w64(ab);
@@ -810,11 +741,7 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
         if (u < 2 * U) { px = lx - 4; py = ly + 4 * (2 * U - 1 - u); }
         else if (u == 2 * U) { px = lx - 4; py = ly - 4; }
         else { px = lx + 4 * (u - 2 * U - 1); py = ly - 4; }
-#if defined(INTRA_EXP) && (INTRA_EXP & 4)      // experiment (wrong samples): every unit counts as available
-        if (px >= 0 && py >= 0) am |= 1ull << u;
-#else
         if (intra_avail(P, ctu, e.z, px, py, cip != 0, (unsigned)nb_same, L.m_pred)) am |= 1ull << u;
-#endif
       }
     }
     // fillReferenceSamples pads unavailable samples from the nearest available one before them (the first available one for those in front):
@@ -832,9 +759,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
     Q.put(i, nc, nr, am, cl, tu_desc(e));
   }
   wave_lds_sync();
-#if defined(INTRA_STOP) && INTRA_STOP == 5
-  if (IntraLds::lean && pw > 0) return;
-#endif
     // ---- 3. what is final before anything ran (the neighbours may pass inter areas at once), the pending mask
     if (lane < 8) Q.pend[lane] = n_sched >= 32 * (lane + 1) ? 0xffffffffu : (n_sched > 32 * lane ? (1u << (n_sched - 32 * lane)) - 1u : 0u);
     if (lane == 0) Q.n_tus = n_sched;                          // (what the scans look at: the entries behind are reached through Q.member only)
@@ -843,14 +767,8 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
     const uint32_t word0 = Q.done_c[pw - 1] | (Q.done_r[pw - 1] << 16);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0 && word0) __hip_atomic_fetch_or(nb.prog + ctu, word0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef INTRA_TIMING
-    if (lane == 0) Q.t_c = wall_clock64();
-#endif
   }
   __syncthreads();
-#if defined(INTRA_STOP) && INTRA_STOP == 3
-  if (pw > 0) return;
-#endif
   const int n_tus = Q.n_tus;
   uint32_t spins = 0;
   // A list of up to 64 entries is one scan round, lane c = entry c: what does not change while the CTU runs -- the entry, its column and row
@@ -860,15 +778,8 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
   uint32_t my_e = 0, my_col = 0;
   uint64_t my_row = 0;
   if (cached && lane < n_tus) { my_e = __builtin_bit_cast(uint32_t, Q.tu[lane]); my_col = Q.e_col[lane]; my_row = Q.need_row(lane); }
-#ifdef INTRA_TIMING
-  unsigned long long tm0 = wall_clock64();
-#define TM_ADD(field) { const unsigned long long tm1 = wall_clock64(); if (lane == 0) atomicAdd(&Q.field, tm1 - tm0); tm0 = tm1; }
-#else
-#define TM_ADD(field)
-#endif
   if (!sparse && wv == (int)(blockDim.x >> 6) - 1) fetch_border(org, h_pitch, comp, cs, nb.ext_col, nb.ext_row, Q, L);   // what is final next door already
   for (;;) {
-    TK_START();
     // the scheduler words in LDS (pend, done_c, done_r, got) are updated by the other waves with atomics: read them afresh in every round
     asm volatile("" ::: "memory");
     // the first list entry that is pending and ready (the list is in priority order); the pending masks may be stale by the time the
@@ -904,9 +815,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
       // nothing this wave can run: either another wave is inside a TU whose units will make one ready, or the neighbours have to get further
       __builtin_amdgcn_s_sleep(4);
       ++spins;
-#ifdef INTRA_TIMING
-      if (lane == 0) atomicAdd(&Q.n_idle, 1u);
-#endif
       // (every fourth round; a count of the waves inside a TU used to decide between every round and every sixteenth -- two LDS atomics per
       // TU on the chain for a distinction the picture does not feel: 2.6 % of an I picture)
       if ((spins & 3) == 0) {
@@ -914,10 +822,8 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
         poll_neighbours(P, nb, pw);
         if (!sparse) fetch_border(org, h_pitch, comp, cs, nb.ext_col, nb.ext_row, Q, L);   // whatever has become final next door
       }
-      TM_ADD(t_idle)
       continue;
     }
-    TK(5)
     // claim it
     uint32_t old = 0;
     if (lane == 0) {
@@ -925,7 +831,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
     }
     old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
     if (!((old >> (i & 31)) & 1)) continue;                  // another wave was faster
-    TK(6)
     // everything about the TU is the same in all lanes, but it comes out of LDS into vector registers: moved to scalar ones, what is derived
     // from it (coordinates, the mode's angle, branch conditions) runs on the scalar unit beside the lanes' own work
     auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
@@ -971,36 +876,24 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
         }
         t.cbf = (int)((colw >> 30) & 1u);
         t.bypass = (int)(colw >> 31);
-        TK(7)
         intra_tu_any(P, t, L, W);
-#ifdef INTRA_TIMING2
-        tk0 = clock64();
-#endif
       };
       if (!sparse && (x4 == 0 || y4 == 0))                      // (a TU inside the CTU reads nothing from next door; a group: what an 8x8 TU would read)
         fetch_border(org, h_pitch, comp, cs, x4 == 0 ? (e_colw & 0xffffu) : 0u, y4 == 0 ? e_roww : 0ull, Q, L);
-#ifdef INTRA_TIMING
-      if (lane == 0) { atomicMin(&Q.t_first, wall_clock64()); atomicAdd(&Q.n_run, 1u); }
-#endif
-      TM_ADD(t_claim)
-      {
-        // one TU -- or the four 4x4 luma TUs of the area, in z order (each predicts from the ones before it; intra_tu ends with the hand-off that
-        // puts its samples into the CTU copy).  The area's units are published together: whatever waits for one of them -- the TUs to the right,
-        // below and below-left -- waits for the fourth TU too.  (One call site: the TU code is the bulk of this kernel's 47 KB.)
-        const int last = e.kind == 2 ? 3 : 0;
-        const uint32_t mem = e.kind == 2 ? (uint32_t)uni((int)*reinterpret_cast<const uint32_t*>(Q.member[zc >> 2])) : (uint32_t)i;
-        for (int j = 0; j <= last; j++) {
-          const int idx = (int)((mem >> (8 * j)) & 0xff);
-          // (a group's other three TUs: their own entries' words)
-          run_tu(idx, zc + j, x4 + (j & 1), y4 + (j >> 1), j == 0 ? e_colw : (uint32_t)uni((int)Q.e_col[idx]));
-        }
-        if (last) U = 2;                                     // the common exit publishes the 2 x 2 units of the area
+      // one TU -- or the four 4x4 luma TUs of the area, in z order (each predicts from the ones before it; intra_tu ends with the hand-off that
+      // puts its samples into the CTU copy).  The area's units are published together: whatever waits for one of them -- the TUs to the right,
+      // below and below-left -- waits for the fourth TU too.  (One call site: the TU code is the bulk of this kernel's 47 KB.)
+      const int last = e.kind == 2 ? 3 : 0;
+      const uint32_t mem = e.kind == 2 ? (uint32_t)uni((int)*reinterpret_cast<const uint32_t*>(Q.member[zc >> 2])) : (uint32_t)i;
+      for (int j = 0; j <= last; j++) {
+        const int idx = (int)((mem >> (8 * j)) & 0xff);
+        // (a group's other three TUs: their own entries' words)
+        run_tu(idx, zc + j, x4 + (j & 1), y4 + (j >> 1), j == 0 ? e_colw : (uint32_t)uni((int)Q.e_col[idx]));
       }
-      TM_ADD(t_tu)
+      if (last) U = 2;                                       // the common exit publishes the 2 x 2 units of the area
     }
     if (sparse) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (sparse CTU: the samples are in the picture, where the CTU's other TUs read them)
     wave_lds_sync();                                         // the TU's samples are in the CTU copy before its units count as final
-    TK(8)
     mark_done(x4, y4, U);
     if (x4 + U == pw || y4 + U == pw) {
       // the neighbours are shown THIS TU's border units, once its stores are acknowledged
@@ -1008,14 +901,6 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_or(nb.prog + ctu, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#ifdef INTRA_TIMING
-    if (lane == 0) atomicMax(&Q.t_last, wall_clock64());
-#endif
-    TM_ADD(t_post)
-    TK(9)
-#ifdef INTRA_TIMING2
-    if (lane == 0) W.tm[15] += 1u;
-#endif
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -1030,12 +915,8 @@ __device__ __attribute__((always_inline)) inline void intra_ctu(const PicDev& P,
 // before it (no deadlock however few blocks are resident), and the blocks resident at any time are the wavefront itself.
 // LEAN: every CTU on the unstaged path (below), in a third of the LDS: the variant for calls without I slices
 template <int WAVES, bool LEAN>          // waves per CTU and component: they run the CTU's ready TUs side by side (intra_ctu)
-__global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(LEAN ? INTRA_LEAN_OCC : (WAVES <= 4 ? INTRA_MANY_OCC : 1)))) k_intra(const PicDev* __restrict__ pics, Batch b, const int32_t* __restrict__ order) {
+__global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(LEAN ? kIntraLeanOcc : (WAVES <= 4 ? kIntraManyOcc : 1)))) k_intra(const PicDev* __restrict__ pics, Batch b, const int32_t* __restrict__ order) {
   __shared__ IntraLdsT<LEAN> L;
-#ifdef INTRA_LDS_PAD                     // experiment: fewer workgroups per CU
-  __shared__ uint32_t lds_pad[INTRA_LDS_PAD / 4];
-  if (blockIdx.x == 0xffffffffu) lds_pad[threadIdx.x] = 1;
-#endif
   __shared__ IntraSchedT<LEAN> Q;
   __shared__ IntraScratch W[WAVES];
   const int slot = blockIdx.x / 3, comp = blockIdx.x % 3, ctu = ldg(order + blockIdx.y);
@@ -1043,15 +924,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   const int first = b.first_ctu[slot], last = first + b.num_ctus[slot] - 1;
   if (!P.has_intra_dir || ctu < first || ctu > last || !ldg(P.ctu_intra + ctu) || (comp && (P.mono || P.fmt == 2))) return;      // (4:2:2 chroma: k_intra_chroma_422)
   if (ctu == P.debug_skip_ctu) return;                         // (test hook: its neighbours run into the bounded wait)
-#if defined(INTRA_EXP) && (INTRA_EXP & 16)    // experiment (no chroma): the luma wavefront alone
-  if (comp) return;
-#endif
   uint32_t* done = P.intra_done + (size_t)comp * P.num_ctus;
   const int cx = ctu % P.ctus_w, cy = ctu / P.ctus_w;
-#ifdef INTRA_TIMING
-  const unsigned long long tk0 = wall_clock64();
-  if (threadIdx.x == 0) { Q.t_tu = Q.t_claim = Q.t_post = Q.t_idle = 0; Q.t_first = ~0ull; Q.t_last = 0; Q.n_run = Q.n_idle = 0; }
-#endif
   const int nb[4] = {cx > 0 ? ctu - 1 : -1, (cx > 0 && cy > 0) ? ctu - P.ctus_w - 1 : -1, cy > 0 ? ctu - P.ctus_w : -1,
                      (cy > 0 && cx + 1 < P.ctus_w) ? ctu - P.ctus_w + 1 : -1};
   // which borders matter: an intra CU reads neighbouring samples only across a border it touches, and only the samples of the
@@ -1075,9 +949,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   // A CTU with few intra CUs (scattered ones in a P picture) does not stage at all: 16 KB of samples and residual per CTU and component
   // for a handful of TUs was most of what such a picture's intra CUs cost.  Its TUs take their reference samples and residual from the
   // picture (intra_tu), one round trip each on a chain of a few TUs.
-  const bool sparse = LEAN || (int)ldg(P.ctu_intra + ctu) * 64 <= INTRA_SPARSE_MAX * (P.parts >> 2);
+  const bool sparse = LEAN || (int)ldg(P.ctu_intra + ctu) * 64 <= kIntraSparseMax * (P.parts >> 2);
   const int wv = threadIdx.x >> 6;
-  {
   if (!sparse) {
     const int cs = (comp && P.csx) ? 1 : 0;
     const int tpr = ((1 << P.log2ctu) >> cs) >> 3, rtw = (P.grid_w / 2) >> cs;           // tiles per CTU row / per picture row
@@ -1089,13 +962,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     }
   }
   intra_stage(P, comp, ctu, L, !sparse);
-  }
-#ifdef INTRA_TIMING
-  if (threadIdx.x == 0) Q.t_a = wall_clock64();
-#endif
-#if defined(INTRA_STOP) && INTRA_STOP == 1      // experiment (no reconstruction): the time of the launch up to here
-  if (pw > 0) return;
-#endif
   unsigned my_l, my_r, my_t, my_b;
   border_mask(ctu, my_l, my_r, my_t, my_b);
   Neighbours nbs;
@@ -1110,9 +976,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     // left: my first column against its last column; above-left: the corner (covered by column and row tests, conservatively);
     // above and above-right: my first row against its last row
     nbs.wait[k] = k == 0 ? (my_l && n_r) : k == 1 ? ((my_l || my_t) && n_r && n_b) : (my_t && n_b);
-#ifdef INTRA_NOWAIT
-    nbs.wait[k] = false;                                     // experiment: no CTU waits for another (wrong samples, the time of the work alone)
-#endif
   }
   // The waits (intra_ctu's polling) cannot deadlock as long as workgroups are dispatched in linear order (the neighbours lie on earlier
   // anti-diagonals, i.e. at smaller block indices: they are resident or finished when this block runs, and never wait for this one).
@@ -1120,31 +983,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   // at its next sync) instead of hanging the device.
   poll_neighbours(P, nbs, P.pw);
   wave_lds_sync();
-#if defined(INTRA_STOP) && INTRA_STOP == 2
-  if (pw > 0) return;
-#endif
-#ifdef INTRA_TIMING
-  if (threadIdx.x == 0) Q.t_b = wall_clock64();
-#endif
-#ifdef INTRA_TIMING2
-  if ((threadIdx.x & 63) < 16) W[wv].tm[threadIdx.x & 63] = 0;
-  wave_lds_sync();
-#endif
   intra_ctu(P, comp, ctu, sparse, L, Q, W[wv], nbs);
   __syncthreads();                                           // every wave's stores are acknowledged (intra_ctu ends with the wait)
-#ifdef INTRA_TIMING
-  if (threadIdx.x == 0 && comp == 0 && slot == 0 && (cy == 10 || cy == 11) && cx >= 20 && cx < 32)
-    printf("TM cy %d cx %d start %llu first %llu last %llu end %llu ntu %u tu %llu claim %llu post %llu idle %llu nidle %u stage %llu nbrs %llu list %llu\n", cy, cx, tk0, Q.t_first, Q.t_last,
-           wall_clock64(), Q.n_run, Q.t_tu, Q.t_claim, Q.t_post, Q.t_idle, Q.n_idle, Q.t_a - tk0, Q.t_b - Q.t_a, Q.t_c - Q.t_b);
-#endif
-#ifdef INTRA_TIMING2
-  if (threadIdx.x == 0 && comp == 0 && slot == 0 && (cy == 10 || cy == 11) && cx >= 20 && cx < 32) {
-    unsigned sum[16];
-    for (int k = 0; k < 16; k++) { sum[k] = 0; for (int w = 0; w < WAVES; w++) sum[k] += W[w].tm[k]; }
-    printf("TK cy %d cx %d tus %u line %u filt %u pred %u resid %u store %u scan %u claim %u setup %u sync %u post %u\n", cy, cx, sum[15], sum[0], sum[1], sum[2], sum[3], sum[4],
-           sum[5], sum[6], sum[7], sum[8], sum[9]);
-  }
-#endif
   // (No release fence in front of the last word: every store to the picture is a write-through atomic store that has been acknowledged by now --
   // intra_ctu ends with the wait.  An agent-scope release fence writes the L2 back: one per workgroup, ~98 000 of them in sixteen 2160p P
   // pictures with scattered intra CUs, was HALF of this kernel's time there -- 0.65 of 1.33 ms, found by cutting the kernel short phase by phase.)
@@ -1308,27 +1148,22 @@ void launch_intra_chroma_422(const PicDev* pics, const Batch& b, hipStream_t s) 
   hipLaunchKernelGGL(k_intra_chroma_422, dim3((unsigned)b.n * 2), dim3(64), 0, s, pics, b);
 }
 
+// Waves per CTU and component of a single picture / of a batch of four pictures and more.
+// measured on 2160p I pictures: one picture 17.9 / 11.6 / 9.7 ms with 1 / 2 / 4 waves per CTU, sixteen at once 19.4 / 13.5 / 17.7;
+// with the residual from k_itx (140 instead of 212 VGPRs: three waves per SIMD) 8.7 ms (4 or 6 waves), sixteen 11.4 / 10.8 / 11.7 (2 / 3 / 4);
+// after the trims of the TU chain: 7.78 / 7.41 / 7.27 / 7.15 ms with 3 / 4 / 6 / 8 waves, sixteen 9.93 / 9.66 / 10.7 (2 / 3 / 4)
+constexpr int kIntraWavesOne = 8;
+constexpr int kIntraWavesMany = 3;
+// Many pictures without I slices (P / B pictures with scattered intra CUs): independent CTUs in plenty, each with a handful of TUs.  What counts
+// is how many of them a CU holds at a time: one wave per CTU and no staging (LEAN), a third of the LDS and of the wave slots of the general kernel
+// -- 2160p x 16 with 5 / 10 / 25 % intra CUs: see DESIGN.md 4.12 for the two kernels side by side.
+constexpr int kIntraWavesLean = 1;
+
 void launch_intra(const PicDev* pics, const Batch& b, const int32_t* order, int num_ctus, bool lean, hipStream_t s) {
-  // measured on 2160p I pictures: one picture 17.9 / 11.6 / 9.7 ms with 1 / 2 / 4 waves per CTU, sixteen at once 19.4 / 13.5 / 17.7;
-  // with the residual from k_itx (140 instead of 212 VGPRs: three waves per SIMD) 8.7 ms (4 or 6 waves), sixteen 11.4 / 10.8 / 11.7 (2 / 3 / 4);
-  // after the trims of the TU chain: 7.78 / 7.41 / 7.27 / 7.15 ms with 3 / 4 / 6 / 8 waves, sixteen 9.93 / 9.66 / 10.7 (2 / 3 / 4)
-#ifndef INTRA_WAVES_ONE
-#define INTRA_WAVES_ONE 8
-#define INTRA_WAVES_MANY 3
-#endif
-  // Many pictures without I slices (P / B pictures with scattered intra CUs): independent CTUs in plenty, each with a handful of TUs.  What counts
-  // is how many of them a CU holds at a time: one wave per CTU and no staging (LEAN), a third of the LDS and of the wave slots of the general kernel
-  // -- 2160p x 16 with 5 / 10 / 25 % intra CUs: see DESIGN.md 4.12 for the two kernels side by side.
-#ifndef INTRA_WAVES_LEAN
-#define INTRA_WAVES_LEAN 1
-#endif
   const dim3 grid((unsigned)b.n * 3, (unsigned)num_ctus);
-#ifdef INTRA_NO_LEAN                     // experiment: the general kernel for every call
-  lean = false;
-#endif
-  if (b.n >= 4 && lean) hipLaunchKernelGGL((k_intra<INTRA_WAVES_LEAN, true>), grid, dim3(64 * INTRA_WAVES_LEAN), 0, s, pics, b, order);
-  else if (b.n >= 4) hipLaunchKernelGGL((k_intra<INTRA_WAVES_MANY, false>), grid, dim3(64 * INTRA_WAVES_MANY), 0, s, pics, b, order);
-  else hipLaunchKernelGGL((k_intra<INTRA_WAVES_ONE, false>), grid, dim3(64 * INTRA_WAVES_ONE), 0, s, pics, b, order);
+  if (b.n >= 4 && lean) hipLaunchKernelGGL((k_intra<kIntraWavesLean, true>), grid, dim3(64 * kIntraWavesLean), 0, s, pics, b, order);
+  else if (b.n >= 4) hipLaunchKernelGGL((k_intra<kIntraWavesMany, false>), grid, dim3(64 * kIntraWavesMany), 0, s, pics, b, order);
+  else hipLaunchKernelGGL((k_intra<kIntraWavesOne, false>), grid, dim3(64 * kIntraWavesOne), 0, s, pics, b, order);
 }
 
 }  // namespace hmgpu

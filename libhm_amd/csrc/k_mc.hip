@@ -41,19 +41,9 @@
 namespace hmgpu {
 
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
-#if defined(MC_EXP) && (MC_EXP & 1)         // experiment: no window loads
-__device__ inline u32x4 ldg4_a4(const void* p) { const uint32_t v = (uint32_t)(uintptr_t)p; return u32x4{v, v + 1, v + 2, v + 3}; }
-#elif defined(MC_NT)
-__device__ inline u32x4 ldg4_a4(const void* p) { return __builtin_nontemporal_load((const u32x4_a4 HMGPU_AS1*)p); }
-#else
 __device__ inline u32x4 ldg4_a4(const void* p) { return *(const u32x4_a4 HMGPU_AS1*)p; }
-#endif
-#ifndef MC_LB_LUMA
-#define MC_LB_LUMA 7      // waves per SIMD the uni-prediction kernel is held to (72 registers; 8 would spill the residual rows)
-#endif
-#ifndef MC_LB_CHROMA
-#define MC_LB_CHROMA 8
-#endif
+constexpr int kLbLuma = 7;      // waves per SIMD the uni-prediction kernel is held to (72 registers; 8 would spill the residual rows)
+constexpr int kLbChroma = 8;
 
 __device__ inline uint32_t pk_sub(uint32_t a, uint32_t b) {                           // per half: a - b (wrapping)
   return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) - __builtin_bit_cast(short2v, b));
@@ -127,9 +117,6 @@ template <bool CHROMA> struct McLds {
   struct { uint32_t body[2 * ROW_DW], halo[2 * ROW_DW]; } w[4];   // halo: the first 8 (4) window rows of run tops, at the top tile's position
   uint32_t taps[144];                           // the tap table (every wave writes the same values, reads its own)
   uint32_t htap[CHROMA ? 36 : 1];               // chroma H pass: the halved taps of fraction f as (c/2, c/2) pairs at [4 f], f = 8: the identity at tap 0
-#ifdef MC_LDS_PAD
-  uint32_t pad[MC_LDS_PAD / 4];                               // experiment: fewer workgroups per CU
-#endif
 };
 
 // CTU columns of a band of the walk (launch_mc).  Narrow bands bring the squares that share reference lines close together; every band
@@ -228,9 +215,6 @@ __device__ inline void finish_rows(int (&v6)[2][W], uint32_t (&park)[W], int pas
       // ClipBD on the packed pair (the saturating pack only matters for weighted prediction: everything else fits 16 bits)
       res[r][x / 2] = pk_clip_u(cvt_pk_sat(o[0], o[1]), maxv2);
     }
-#if defined(MC_EXP) && (MC_EXP & 2)         // experiment: no stores (unless a value nobody produces shows up)
-  if (res[0][0] != 0x7fff7fffu) return;
-#endif
 #pragma unroll
   for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -304,16 +288,6 @@ template <> struct Win<false> {
   __device__ inline u32x4 load(ref p) const { return ldg4_a4(p); }
 };
 
-// second piece of a window row from the lane to the right (its first piece) in the lanes where `take` holds: a DPP move (row_shl:1 =
-// the value of lane + 1; lanes without one, the last of a row of 16, read 0) that the compiler folds into the select (v_cndmask_b32_dpp)
-__device__ inline uint32_t from_right(uint32_t own, uint32_t first, bool take) {
-  const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)first, 0x101, 0xf, 0xf, true);
-  return take ? t : own;
-}
-__device__ inline u32x4 from_right(const u32x4 own, const u32x4 first, bool take) {
-  return u32x4{from_right(own.x, first.x, take), from_right(own.y, first.y, take), from_right(own.z, first.z, take), from_right(own.w, first.w, take)};
-}
-
 // ======================================================================================================== luma
 // H pass work item: window rows (2i, 2i+1) x 8 columns.  r[0..1] = first row (8 dwords = 16 samples), r[2..3] = second row;
 // tap = the item's tap table entry.  out (LDS): piece c at out[c * 64] = (row 2i | row 2i+1 << 16) of columns 2c, 2c+1
@@ -372,19 +346,12 @@ __device__ inline const char* low_half(const char* p, int lane) {
 //     the window starts one row higher (identity at tap 4 instead of 3), so the block's rows are window rows 4..11 -- the second half
 //     of the halo item's rows and the first half of the body item's; the tile shares nothing with its neighbours and is its own run.
 //     Horizontal: the window starts at the block's first column (identity at tap 0): one 16-byte piece per row if that column is even.
-//   * (experiment MC_DEDUP) the second 16-byte piece of a row when the tile to the right has the same motion and loads the same rows:
-//     it IS that lane's first piece (from_right).
 //   * window row 15 of a tile that no tile of the strip continues (a tile needs rows 0..14, row 15 is the first row of the next tile's share).
 // Rows and pieces that are not loaded only ever meet zero taps.
-#ifndef MC_NO_F0
-#define MC_F0 1
-#endif
-// (MC_DEDUP, off: see DESIGN.md -- the move + select per dword cost the arithmetic-bound large PUs what the loads saved)
-#ifndef MC_NO_R15
-#define MC_R15 1
-#endif
+// (Taking a row's second 16-byte piece from the lane to the right when both tiles share their motion: tried and dropped, see
+// profiles/EXPERIMENTS.md.)
 template <bool WP, bool BI, bool BUF>
-__global__ void __launch_bounds__(256, (WP || BI) ? 1 : MC_LB_LUMA) k_mc_luma(const McArgs a) {
+__global__ void __launch_bounds__(256, (WP || BI) ? 1 : kLbLuma) k_mc_luma(const McArgs a) {
   __shared__ __attribute__((aligned(16))) McLds<false> S;
   int slot; Square g;
   if (!square_of_block(a, slot, g)) return;
@@ -399,26 +366,9 @@ __global__ void __launch_bounds__(256, (WP || BI) ? 1 : MC_LB_LUMA) k_mc_luma(co
   const uint32_t flags = tm.z >> 24, rmask = (tm.w >> 8) & 0xff;
   const bool active = (flags & TM_ACTIVE) != 0;
   if (!__ballot(active)) return;
-#if defined(MC_EXP) && (MC_EXP & 64)        // experiment (wrong samples): what sharing rows ACROSS strips would save -- a first-row tile whose
-  // upper neighbour in the strip above has the same record does not start a run (its upper rows are read from wherever)
-  bool top = tile_is_top(tm, r, lane ^ 32);
-  if (wave > 0) {
-    const u32x4 up = load_tile_rec(a, slot, g, x0, y0 - 8);
-    if (r == 0 && up.x == tm.x && up.y == tm.y && up.z == tm.z) top = false;
-  }
-#else
   const bool top = tile_is_top(tm, r, lane ^ 32);
-#endif
-#ifdef MC_DEDUP
-  const bool same_right = tx < 7 && !tile_is_top(tm, 1, lane + 1);          // the tile to the right: same lists, pictures, vectors
-#else
-  const bool same_right = false;
-#endif
   const bool any_bi = BI && __ballot((flags & TM_BI) != 0) != 0;
   wave_lds_sync();
-#ifdef MC_LDS_PAD
-  if (a.n < 0) S.pad[tid] = 1;                               // (keeps the padding allocated)
-#endif
   const int npass = any_bi ? 2 : 1;
   const int head = bd >= 12 ? 2 : 14 - bd;
   const int sh1 = 6 - head;
@@ -450,11 +400,7 @@ __global__ void __launch_bounds__(256, (WP || BI) ? 1 : MC_LB_LUMA) k_mc_luma(co
     const bool bact = active && (pass == 0 || (flags & TM_BI));
     const uint32_t mv = pass ? tm.y : tm.x;
     const uint32_t fr = (tm.z >> (4 * pass)) & 15;
-#ifdef MC_F0
     const bool yz = (fr & 12) == 0, xz = (fr & 3) == 0;
-#else
-    const bool yz = false, xz = false;
-#endif
     const bool ptop = top || yz;
     const bool bon = bact && (!yz || q < 2), hon = bact && ptop && (!yz || q >= 2);
     const int xs = x0 + (int)(int16_t)(mv & 0xffff) - (xz ? 0 : 3);
@@ -463,44 +409,27 @@ __global__ void __launch_bounds__(256, (WP || BI) ? 1 : MC_LB_LUMA) k_mc_luma(co
     // window row 2q of the tile (the halo item's first row; the body item's is 8 rows down)
     const wref pw = win.at(win.plane(a, (int)((tm.z >> (8 + 8 * pass)) & (kMaxPics - 1))), y0 + ((int)mv >> 16) - (yz ? 4 : 3) + 2 * q, pitch, xs & ~1);
     const uint32_t vidx = yz ? 5u : (fr >> 2) & 3;
-    const uint64_t bon_m = __ballot(bon), hon_m = __ballot(hon);
-    // the lane to the right loads the same rows of the same window, 16 bytes on: its first piece is this lane's second
-#ifdef MC_R15
+    const uint64_t hon_m = __ballot(hon);
     // window row 15 (the body item's second row in lanes with q == 3) is only ever read by a tile of the second strip row that continues this one
     const bool b2on = bon && (q != 3 || (r == 0 && !((__ballot(ptop) >> (lane + 32)) & 1)));
-#else
-    const bool b2on = bon;
-#endif
-    const uint64_t b2on_m = __ballot(b2on);
-    const bool rb_shared = same_right && ((bon_m >> (lane + 1)) & 1), rb2_shared = same_right && ((b2on_m >> (lane + 1)) & 1);
-    const bool rh_shared = same_right && ((hon_m >> (lane + 1)) & 1);
     // the H pass of the lane's body item and, in waves that hold run tops, of its halo item.  Loads are unconditional (lanes without
     // an item read nowhere): values that are only defined in some lanes would have to be initialised in the others
     auto h_phase = [&](auto with_halo) {
       constexpr bool HALO = decltype(with_halo)::value;
       u32x4 rb[4], rh[4];
       {
-        const wref p0 = bon ? pw + pitch * 16 : nowhere, p1 = bon && two && !rb_shared ? p0 + 16 : nowhere;
+        const wref p0 = bon ? pw + pitch * 16 : nowhere, p1 = bon && two ? p0 + 16 : nowhere;
         rb[0] = win.load(p0); rb[1] = win.load(p1);
-        rb[2] = win.load(b2on ? p0 + pitch * 2 : nowhere); rb[3] = win.load(b2on && two && !rb2_shared ? p0 + pitch * 2 + 16 : nowhere);
+        rb[2] = win.load(b2on ? p0 + pitch * 2 : nowhere); rb[3] = win.load(b2on && two ? p0 + pitch * 2 + 16 : nowhere);
       }
       if constexpr (HALO) {
-        const wref p0 = hon ? pw : nowhere, p1 = hon && two && !rh_shared ? p0 + 16 : nowhere;
+        const wref p0 = hon ? pw : nowhere, p1 = hon && two ? p0 + 16 : nowhere;
         rh[0] = win.load(p0); rh[1] = win.load(p1);
-        rh[2] = win.load(hon ? p0 + pitch * 2 : nowhere); rh[3] = win.load(hon && two && !rh_shared ? p0 + pitch * 2 + 16 : nowhere);
+        rh[2] = win.load(hon ? p0 + pitch * 2 : nowhere); rh[3] = win.load(hon && two ? p0 + pitch * 2 + 16 : nowhere);
       }
-#ifdef MC_DEDUP
-      {
-        rb[1] = from_right(rb[1], rb[0], rb_shared); rb[3] = from_right(rb[3], rb[2], rb2_shared);
-      }
-      if constexpr (HALO) {
-        rh[1] = from_right(rh[1], rh[0], rh_shared); rh[3] = from_right(rh[3], rh[2], rh_shared);
-      }
-#endif
       if (bon) h_item_luma(rb, tap, sh1, body_t + q * 16);
       if constexpr (HALO) { if (hon) h_item_luma(rh, tap, sh1, halo_t + q * 16); }
     };
-#ifndef MC_NO_SPLIT
     // Run tops in the strip's first tile row only (any PU 16 rows tall or more): their halo items would keep half of the lanes busy with
     // two rows each.  Shared out instead: the lane below (lane + 32: same tile column, same row pair) takes the item's second row --
     // half the arithmetic and two window loads instead of four per lane -- and hands its eight sums up (v_permlane32_swap).
@@ -526,9 +455,9 @@ __global__ void __launch_bounds__(256, (WP || BI) ? 1 : MC_LB_LUMA) k_mc_luma(co
           *reinterpret_cast<u32x2*>(halo_t + q * 16 + c * 64) = u32x2{pack_shr(sum[2 * c], up[2 * c], sh1), pack_shr(sum[2 * c + 1], up[2 * c + 1], sh1)};
       }
     };
-    if (hon_m && !(hon_m >> 32)) h_phase_split(); else
-#endif
-    if (hon_m) h_phase(std::true_type()); else h_phase(std::false_type());
+    if (hon_m && !(hon_m >> 32)) h_phase_split();
+    else if (hon_m) h_phase(std::true_type());
+    else h_phase(std::false_type());
     wave_lds_sync();
     if (bact) {
       // output rows 2q, 2q+1 of the tile: window row pairs q .. q+4, the first four of a tile's eight pairs belong to the tile above
@@ -649,7 +578,7 @@ __device__ inline void h_item_chroma(const u32x4 (&r)[4], const uint32_t* __rest
 // passes.  H item: lanes 0..31 window rows 4+2hq, 5+2hq ("body"), lanes 32..63 rows 2hq, 2hq+1 ("halo", tiles that start a run) of
 // both planes, hq = (lane >> 3) & 1.  V item: plane vp = lane >> 5, output rows 2k, 2k+1 with k = (lane >> 3) & 1.
 template <bool WP, bool BI, bool BUF>
-__global__ void __launch_bounds__(256, (WP && BI) ? 6 : MC_LB_CHROMA) k_mc_chroma(const McArgs a) {
+__global__ void __launch_bounds__(256, (WP && BI) ? 6 : kLbChroma) k_mc_chroma(const McArgs a) {
   __shared__ __attribute__((aligned(16))) McLds<true> S;
   int slot; Square g;
   if (!square_of_block(a, slot, g)) return;
@@ -698,42 +627,23 @@ __global__ void __launch_bounds__(256, (WP && BI) ? 6 : MC_LB_CHROMA) k_mc_chrom
     const int ix = (int)(int16_t)(mv & 0xffff), iy = (int)mv >> 16;
     // chroma vector = luma vector in eighth samples: integer part ix >> 1, fraction (ix & 1) * 4 + quarter fraction
     const int yf = ((iy & 1) << 2) | ((fr >> 2) & 3);
-#ifdef MC_F0
     // no vertical interpolation (an eighth of the vectors): the window starts one row higher (identity at tap 2), the block's four rows are
     // window rows 2..5 -- the halo item's second row pair and the body item's first; the tile is its own run (as in k_mc_luma)
     const bool yz = yf == 0;
-#else
-    const bool yz = false;
-#endif
     const bool ptop = top || yz;
     const bool hact = vact && (hi == 0 ? (!yz || hq == 0) : (ptop && (!yz || hq == 1)));
-#ifdef MC_R15
     // window row 7 (the second row of the body item with hq == 1) is only ever read by a tile of the second strip row that continues this one
     const bool row2 = hi != 0 || hq == 0 || (r == 0 && !((__ballot(ptop) >> (lane | 16)) & 1));
-#else
-    const bool row2 = true;
-#endif
     if (hact) {
       const int xf = ((ix & 1) << 2) | (fr & 3);
-#ifdef MC_F0
       const bool xz = xf == 0;          // no horizontal interpolation: the window starts at the block's first column (identity at tap 0), one piece per row
-#else
-      const bool xz = false;
-#endif
       const int xs = (x0 >> 1) + (ix >> 1) - (xz ? 0 : 1), ys = (y0 >> 1) + (iy >> 1) - (yz ? 2 : 1) + (hi ? 0 : 4) + 2 * hq;
       // a window row = the (Cb, Cr) pairs xs .. xs + 6 of one plane row: two 16-byte pieces of ONE line (hmgpu_dev.h "chroma planes")
       const wref p0 = win.at(win.plane(a, (int)((tm.z >> (8 + 8 * pass)) & (kMaxPics - 1))), ys, pitch, kCStep * xs);
       const int rowb = pitch * 2;
       u32x4 rr[4];
-#if defined(MC_CEXP) && (MC_CEXP & 1)       // experiment: no halo rows
-      const bool ld = hi == 0;
-#elif defined(MC_CEXP) && (MC_CEXP & 2)     // experiment: no window loads at all
-      const bool ld = false;
-#else
-      const bool ld = true;
-#endif
-      rr[0] = win.load(ld ? p0 : win.nowhere()); rr[1] = win.load(ld && !xz ? p0 + 16 : win.nowhere());
-      rr[2] = win.load(ld && row2 ? p0 + rowb : win.nowhere()); rr[3] = win.load(ld && row2 && !xz ? p0 + rowb + 16 : win.nowhere());
+      rr[0] = win.load(p0); rr[1] = win.load(!xz ? p0 + 16 : win.nowhere());
+      rr[2] = win.load(row2 ? p0 + rowb : win.nowhere()); rr[3] = win.load(row2 && !xz ? p0 + rowb + 16 : win.nowhere());
       h_item_chroma(rr, &S.htap[(xz ? 8 : xf) * 4], sh1, hout);
     }
     wave_lds_sync();
@@ -798,11 +708,7 @@ static void launch_mc(K kernel, McArgs& a, int max_ctus, hipStream_t s) {
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a);
 }
 // buffer-load windows while every byte of the slab of pictures has a 32-bit offset below kWinLimit (57 pictures of 3840x2160), plain addresses beyond
-#ifdef MC_FORCE_PTR
-static bool win_buf(const McArgs& a) { return false; }
-#else
 static bool win_buf(const McArgs& a) { return a.slab_bytes < (uint64_t)kWinLimit; }
-#endif
 void launch_mc_luma(McArgs& a, int max_ctus, bool wp, bool bi, hipStream_t s) {
   if (win_buf(a)) {
     if (wp) { if (bi) launch_mc(k_mc_luma<true, true, true>, a, max_ctus, s); else launch_mc(k_mc_luma<true, false, true>, a, max_ctus, s); }

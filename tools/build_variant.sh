@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <name> [-DFLAG ...]  -- libhmgpu.so built with extra flags into libhm_amd/variants/<name>/ (experiments;
+# usage: tools/build_variant.sh <name> [extra compiler flags]  -- libhmgpu.so built with extra compiler flags into libhm_amd/variants/<name>/ (experiments;
 # tools/exp_variants.sh swaps it in on the GPU box).  Only the MC kernels are recompiled, the other objects come from libhm_amd/build/.
 set -e
 name=$1; shift
