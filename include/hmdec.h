@@ -98,6 +98,7 @@ typedef struct hmgpu_export_warp hmgpu_export_warp;
 typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
+typedef struct hmgpu_transform_desc hmgpu_transform_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
 typedef struct hmgpu_metrics_map_desc hmgpu_metrics_map_desc;
 typedef struct hmgpu_histogram_desc hmgpu_histogram_desc;
@@ -188,6 +189,14 @@ int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_pictur
                                    const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
                                    const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
                                    int on_stream, void* stream);
+/* The quantised levels or de-quantised transform coefficients of up to 16 pictures and their transform-unit info grid in one call
+ * (hmgpu_pictures_export_transform: destinations, strides and statuses as there), under the rules of hmdec_pictures_export_motion:
+ * levels and arrays lie in the device context that decoded a picture, everything is validated before any context is given work
+ * (hmgpu_transform_destination_check, hmgpu_pictures_transform_check), then each context gets one call per run of equally spaced
+ * slots. */
+int hmdec_pictures_export_transform(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_transform_desc* desc,
+                                    void* const dst[3], void* dst_info, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                    const int64_t batch_stride_bytes[4], int on_stream, void* stream);
 /* Up to 16 output pictures kept on the device compared with planes the caller holds in device memory -- decoded against original
  * (hmgpu_pictures_metrics with HMGPU_METRICS_REF_PLANES: records, reference planes, strides and statuses as there), under the rules of
  * hmdec_pictures_export_residual: everything is validated before any context is given work (hmgpu_metrics_check), then each context

@@ -902,6 +902,93 @@ hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* ctx, int32_t n, const h
                                               const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
                                               const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ transform export
+ * The frequency-domain side of finished pictures -- the quantised levels as parsed, or the de-quantised transform coefficients, and
+ * the transform-unit structure needed to read them -- written on the device straight into caller-owned device memory (DESIGN.md
+ * §9q): up to HMGPU_EXPORT_MAX_BATCH pictures and one kernel launch per call (k_transform.hip).  The source is what the decompress
+ * calls staged for the picture and what lives as long as its handle: the levels (hmgpu_coeffs, dense or compact), HM's per-partition
+ * arrays, the slice table and the picture's scaling-list matrices.  All four chroma formats (coefficients are taken before the
+ * transform: cross-component prediction does not touch them), 8 .. 12 bits, CTUs of 16 / 32 / 64 samples.  There is no crop: the
+ * planes are the coded picture, and a conformance crop is a tensor slice on the caller's side.
+ *
+ * Coefficient planes: dst[0] [n][H][W], dst[c] [n][H >> csy][W >> csx] for c = 1, 2 (csx / csy: the format's chroma subsampling).
+ * For a 4:0:0 picture the chroma bits of `components` are ignored and nothing is written for them (dst[1] / dst[2] are ignored).
+ * A block is coded by the rule of hmgpu_coeffs and hmgpu_pack_levels: the partition is decoded (part_size != HMGPU_SIZE_NONE), its
+ * cbf bits are set down to the unit's transform depth, (cbf & chain) == chain with chain = (1 << (tr_idx + 1)) - 1, the transform size
+ * is 4 .. 32; the 4x4 chroma block under four 4x4 luma units is flagged at the first of them; in 4:2:2 a chroma block is two squares,
+ * the upper one first, each with its own flag one depth below (bit tr_idx + 1 at the first partition of the upper / lower half of the
+ * block's partitions).  Element v * size + u of the level block of such a block of component c with top-left component sample
+ * (x0, y0) goes to plane element (y0 + v, x0 + u).  Every element that no coded block covers is exactly 0, and so is every element
+ * under a PCM CU (ipcm: PCM CUs carry cbf = 1 and their "levels" are not levels).  Nothing is rotated or accumulated: rotation and
+ * RDPCM act after this stage.  Codedness comes from the arrays alone, never from what the level buffers hold.  The value, by
+ * desc->value:
+ *   HMGPU_TRANSFORM_LEVELS  the int16 level as the parser delivered it
+ *   HMGPU_TRANSFORM_COEFFS  the output of TComTrQuant::xDeQuant for the block (TComTrQuant.cpp:1203-1311): QpParam from the QP at the
+ *                           CU's first partition, the slice's Cb / Cr offsets and the chroma table of the picture's format; flat scaling,
+ *                           or the picture's scaling-list matrix 3 * inter + component, which a transform-skip block takes only when it
+ *                           is 4x4 (getUseScalingList); the level clip, the rounding shift or left shift and the clip to
+ *                           [-32768, 32767] are xDeQuant's.  Transform-skip blocks get the same function: their values are scaled
+ *                           spatial samples, which is why the info grid carries the flag.  cu_transquant_bypass blocks have no
+ *                           de-quantisation in HM: the value is the level.
+ *   sample_type HMGPU_SAMPLE_UINT: int16, the value v itself.  F16 / BF16 / F32 with either value: convert(fmul((float)v,
+ *   desc->scale[c])), the rule and conversion of the dense residual form; every scale of a selected component finite.
+ * Intra CUs are exported whether or not the picture was decoded with intra_dir[] -- the levels are staged either way and
+ * de-quantisation needs only pred_mode; this differs from the residual export.  The flag group (transform_skip / transquant_bypass /
+ * ipcm) is read only for a picture it was staged for.
+ *
+ * Info grid: dst_info int8 [n][HMGPU_TRANSFORM_INFO_CHANNELS][H / 4][W / 4], the motion export's grid of 4x4 luma blocks with the same
+ * (bx, by) -> (CTU, z) map.  A block that is not decoded has -1 in all six channels; otherwise
+ *   0  log2 of the luma transform size, log2_ctu_size - depth - tr_idx
+ *   1  tr_idx
+ *   2  bit c set iff the planes hold coefficients for the block of component c that covers this 4x4 luma block (the rule above, PCM
+ *      excluded; 4:2:2: the square that covers it); chroma bits 0 in 4:0:0
+ *   3  bits 0-2 transform_skip[c] & 1, read at the first partition of the covering block (4:2:0 / 4:2:2 chroma: of the 8x8 node under
+ *      four 4x4 luma units; 4:2:2: of the covering square; chroma bits 0 in 4:0:0); bit 3 transquant_bypass; bit 4 ipcm; all 0 when the
+ *      flag group was not staged for the picture
+ *   4  intra_dir[0] for intra CUs of a picture all of whose decompress calls came with intra_dir[]; -1 otherwise
+ *   5  intra_dir[1] as HM holds it (36 = derived from luma) under the same condition; -1 otherwise and in 4:0:0
+ * Skip and merge flags are not part of hmgpu_ctu_meta: they stay with hmdec_internal_info.
+ *
+ * A picture qualifies under the coverage rule of the motion and residual exports (else HMGPU_EINVAL).  Destinations: slots 0 .. 2
+ * the planes, 3 the info grid (HMGPU_TRANSFORM_DST_INFO) index pitch_bytes, plane_stride_bytes (info: channel to channel; ignored for
+ * the planes) and batch_stride_bytes.  Any destination may be NULL (not written), at least one must be given, and the destination of
+ * a component that is not selected must be NULL.  Each must be aligned to its element, as must its strides; pitch >= row_bytes, plane
+ * stride >= pitch * (height - 1) + row_bytes, batch stride >= plane stride * (channels - 1) + that; all n pictures of it must lie
+ * inside one allocation of the context's device.  Everything is validated before anything is enqueued, in the order of the residual
+ * export, and a refused call leaves every destination untouched: n outside 1 .. HMGPU_EXPORT_MAX_BATCH, an unknown value, components
+ * outside 1 .. 7, non-zero reserved words, a non-finite scale, an invalid handle, a picture without coverage and every destination rule
+ * give HMGPU_EINVAL, an unknown sample_type HMGPU_EUNSUPPORTED.  Stream ordering is that of hmgpu_picture_export, once per call.  The
+ * launch is not accounted in hmgpu_stats. */
+enum { HMGPU_TRANSFORM_LEVELS = 0, HMGPU_TRANSFORM_COEFFS = 1 };
+enum { HMGPU_TRANSFORM_DST_INFO = 3, HMGPU_TRANSFORM_DSTS = 4, HMGPU_TRANSFORM_INFO_CHANNELS = 6 };
+typedef struct hmgpu_transform_desc {
+  int32_t value;               /* HMGPU_TRANSFORM_* */
+  int32_t components;          /* bit 0: Y, bit 1: Cb, bit 2: Cr */
+  int32_t sample_type;         /* HMGPU_SAMPLE_UINT: int16; HMGPU_SAMPLE_F16 / BF16 / F32 */
+  float scale[3];              /* float types: per component */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_transform_desc;
+typedef struct hmgpu_transform_plan {
+  int32_t channels[4];         /* per destination slot (Y, Cb, Cr, info): planes per picture, 0 = the slot does not exist */
+  int32_t width[4], height[4]; /* of every plane, in elements */
+  int32_t elem_bytes[4];
+  int32_t row_bytes[4];        /* width * elem_bytes: the least pitch */
+  int32_t reserved[4];
+} hmgpu_transform_plan;
+/* validates a call's description and reports what it writes; host code, no device needed */
+hmgpu_status hmgpu_transform_plan_for(const hmgpu_seq_params* seq, const hmgpu_transform_desc* desc, int32_t n, hmgpu_transform_plan* out);
+hmgpu_status hmgpu_pictures_export_transform(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_transform_desc* desc,
+                                             void* const dst[3], void* dst_info, const int64_t pitch_bytes[4],
+                                             const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
+                                             void* stream);
+/* the two halves of that validation, nothing enqueued (libhmdec: pictures in several contexts of a GPU): HMGPU_OK when pics[0 .. n)
+ * are all valid handles of pictures that decompress calls have covered; the status hmgpu_pictures_export_transform would give a
+ * description and a destination for n pictures */
+hmgpu_status hmgpu_pictures_transform_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[]);
+hmgpu_status hmgpu_transform_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_transform_desc* desc, void* const dst[3],
+                                               void* dst_info, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                               const int64_t batch_stride_bytes[4]);
+
 /* ------------------------------------------------------------------------------------------------ picture metrics
  * Finished pictures compared on the device, sample by sample, with other pictures of the context or with planes the caller holds in
  * device memory: up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_metrics.hip) behind one

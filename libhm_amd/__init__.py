@@ -185,6 +185,13 @@ def lib():
         L.hmgpu_residual_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ResidualDesc), C.POINTER(abi.ExportScale),
                                                        C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_transform_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.TransformDesc), C.c_int32, C.POINTER(abi.TransformPlan)]
+        L.hmgpu_pictures_export_transform.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.TransformDesc),
+                                                      C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                      C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_pictures_transform_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.hmgpu_transform_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.TransformDesc), C.POINTER(C.c_void_p), C.c_void_p,
+                                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_metrics_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MetricsDesc), C.POINTER(abi.MetricsPlan)]
         L.hmgpu_metrics_psnr.argtypes = [C.POINTER(abi.MetricsResult), C.c_int32]
         L.hmgpu_metrics_psnr.restype = C.c_double
@@ -487,6 +494,12 @@ def residual_plan(seq, form="planes", components=(0, 1, 2), size=None, windows=N
     """what Context.export_residual with these arguments writes per picture (libhm_amd.residual.residual_plan: host code, no GPU)"""
     from . import residual
     return residual.residual_plan(seq, form, components, size, windows, flip, dtype, scale, crop, n)
+
+
+def transform_plan(seq, value="levels", components=(0, 1, 2), dtype=None, scale=None, n=1):
+    """what Context.export_transform with these arguments writes per picture (libhm_amd.transform.transform_plan: host code, no GPU)"""
+    from . import transform
+    return transform.transform_plan(seq, value, components, dtype, scale, n)
 
 
 def metrics_plan(seq, reference="pictures", components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), ref_bytes_per_sample=2):
@@ -951,6 +964,39 @@ class Context:
         return residual.export_residual(lambda desc, sc, win, ptrs, pitches, pstrides, bstrides, st:
                                         self.export_residual_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st, sc, win),
                                         self.seq, self.device, len(pics), form, components, size, windows, flip, dtype, scale, out, crop)
+
+    def export_transform_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0):
+        """hmgpu_pictures_export_transform into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per
+        destination slot (0 .. 2 the component planes, 3 the info grid; a pointer None / 0 = not written)"""
+        from . import transform
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_transform(self._h, len(pics), abi.handle_array(pics), C.byref(desc),
+                                                        *transform.c_args(ptrs, pitches, pstrides, bstrides), on_stream, abi.addr(stream)),
+                  "hmgpu_pictures_export_transform")
+
+    def transform_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides):
+        """hmgpu_transform_destination_check: the status hmgpu_pictures_export_transform would give this destination; enqueues nothing"""
+        from . import transform
+        return lib().hmgpu_transform_destination_check(self._h, n, C.byref(desc), *transform.c_args(ptrs, pitches, pstrides, bstrides))
+
+    def transform_status(self, pics):
+        """hmgpu_pictures_transform_check: HMGPU_OK when every picture of the list has levels and arrays to export; enqueues nothing"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_transform_check(self._h, len(pics), abi.handle_array(pics))
+
+    def export_transform(self, pics, value="levels", components=(0, 1, 2), dtype=None, scale=None, out=None, on_stream=True):
+        """the quantised levels ("levels") or the de-quantised transform coefficients ("coeffs") of up to 16 decoded pictures and their
+        transform-unit structure as a dict of torch tensors on this context's GPU (libhm_amd.transform), one launch, written on
+        torch.cuda.current_stream() (on_stream) or on the context's own stream: "y" [N, H, W], "cb" / "cr" at the format's chroma
+        resolution (every block's coefficients at the block's position, 0 elsewhere), "info" int8 [N, 6, H / 4, W / 4].  dtype None
+        (int16) or torch.float16 / bfloat16 / float32 with scale (one factor per component).  out: a dict with some of those keys
+        (only they are written).  All four chroma formats; pictures that were uploaded, received or only partly decoded give
+        HMGPU_EINVAL."""
+        from . import transform
+        pics = list(pics)
+        return transform.export_transform(lambda desc, ptrs, pitches, pstrides, bstrides, st:
+                                          self.export_transform_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st),
+                                          self.seq, self.device, len(pics), value, components, dtype, scale, out)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

@@ -335,6 +335,29 @@ def make_residual_desc(form, components=7, sample_type=SAMPLE_UINT, crop=(0, 0, 
     return d
 
 
+TRANSFORM_LEVELS, TRANSFORM_COEFFS = 0, 1
+TRANSFORM_DST_INFO, TRANSFORM_DSTS, TRANSFORM_INFO_CHANNELS = 3, 4, 6
+
+
+class TransformDesc(C.Structure):
+    _fields_ = [("value", C.c_int32), ("components", C.c_int32), ("sample_type", C.c_int32), ("scale", C.c_float * 3),
+                ("reserved", C.c_int32 * 6)]
+
+
+class TransformPlan(C.Structure):
+    _fields_ = [("channels", C.c_int32 * 4), ("width", C.c_int32 * 4), ("height", C.c_int32 * 4), ("elem_bytes", C.c_int32 * 4),
+                ("row_bytes", C.c_int32 * 4), ("reserved", C.c_int32 * 4)]
+
+
+def make_transform_desc(value=TRANSFORM_LEVELS, components=7, sample_type=SAMPLE_UINT, scale=(1.0, 1.0, 1.0)):
+    """value: TRANSFORM_LEVELS / TRANSFORM_COEFFS; components: the mask (bit c: component c); scale: per component, the float types"""
+    d = TransformDesc()
+    d.value, d.components, d.sample_type = int(value), int(components), int(sample_type)
+    for k in range(3):
+        d.scale[k] = float(scale[k])
+    return d
+
+
 METRICS_REF_PICTURES, METRICS_REF_PLANES = 0, 1
 METRICS_NO_DIFF = (1 << 64) - 1
 

@@ -627,6 +627,35 @@ struct ResidArgs {
 };
 void launch_residual_planes(const ResidArgs& a, hipStream_t s);
 void launch_residual_dense(const ResidArgs& a, int elem, hipStream_t s);   // elem: kElemU16 (int16) / kElemF16 / kElemBF16 / kElemF32
+// transform export (k_transform.hip, hmgpu_pictures_export_transform): everything by value, validated on the host.  The levels of every
+// picture of the call (PicDev::coef: HM's dense layout, or compact behind coef_start), the HM arrays that say where a coded block lies
+// and how it is de-quantised, the slice table (chroma QP offsets) and the scaling-list matrices.  `gate` as in ResidSrc: the flag group
+// is read only where it was staged; kTransDir: every call of the picture came with intra_dir[] (info channels 4 / 5).
+// Destination slots: 0 .. 2 the component planes, 3 the info grid (HMGPU_TRANSFORM_DST_INFO).
+enum { kTransDir = 1, kTransFlags = 2 };
+struct TransformSrc {
+  const uint8_t* depth; const int8_t* part_size; const int8_t* pred_mode; const int8_t* qp; const uint8_t* tr_idx;
+  const uint8_t* cbf[3]; const uint8_t* tskip[3]; const uint8_t* bypass; const uint8_t* ipcm;
+  const uint8_t* intra_dir[2];
+  const uint16_t* slice_idx; const SliceDev* slices;
+  const int16_t* coef[3];
+  const uint32_t* coef_start[3];   // compact levels: the CTUs' starts, else null
+  const uint8_t* sl_m;             // PicDev::sl_m, or null (flat scaling)
+  int32_t gate, pad_;
+};
+struct TransformArgs {
+  TransformSrc src[kMaxExportBatch];
+  int32_t n, comps;                // pictures; the component mask (chroma bits cleared for 4:0:0 pictures)
+  int32_t mono, fmt, csx, csy;     // 4:0:0; chroma_format_idc (0 kept as 1) and its subsampling
+  int32_t log2ctu, ctus_w, parts;  // geometry of the context
+  int32_t width, height, bd[3];    // luma samples; bit depth per component
+  int32_t vec;                     // bit k: plane k may take 16-byte stores (alignment of dst and strides)
+  float scale[3];                  // float elements: per component
+  uint8_t* dst[4];
+  int64_t pitch[4], pstride[4], bstride[4];   // bytes: row to row, channel to channel (info), picture to picture
+};
+// coeffs: HMGPU_TRANSFORM_COEFFS (else the levels); elem: kElemU16 (int16) / kElemF16 / kElemBF16 / kElemF32
+void launch_transform(const TransformArgs& a, bool coeffs, int elem, int num_ctus, hipStream_t s);
 // picture metrics (k_metrics.hip, hmgpu_pictures_metrics): everything by value, validated on the host.  Plane class 0 is luma, class 1
 // the chroma pair (Cb and Cr from one load of the pair plane); a class with no selected component has no tiles.  Work items are
 // (picture, class, tile) in that order; workgroup g walks items [g * per, (g + 1) * per).  A tile is 2048 samples: 64 x 32 with SSIM (the

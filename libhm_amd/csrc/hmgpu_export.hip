@@ -2,9 +2,9 @@
 // slots, window tables, colour LUTs, the rules and weights of the chroma stage, the weights and rules of the format export and the
 // rules of the warp; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
-// destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block
-// and residual exports, the reference planes of the picture metrics and the picture metric maps, the picture histograms (k_export.hip,
-// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_metrics.hip, k_metrics_map.hip, k_histogram.hip).
+// destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block,
+// residual and transform exports, the reference planes of the picture metrics and the picture metric maps, the picture histograms (k_export.hip,
+// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_transform.hip, k_metrics.hip, k_metrics_map.hip, k_histogram.hip).
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -1808,6 +1808,127 @@ hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu
     }
     launch_residual_dense(a, elem, hs);
   }
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+// ------------------------------------------------------------------------------------------------ transform export (k_transform.hip)
+// hmgpu_transform_plan_for and what the entry point needs beyond the plan: the output element (kElem*; kElemU16 stands for int16)
+static hmgpu_status transform_plan(const hmgpu_seq_params* seq, const hmgpu_transform_desc* d, int n, hmgpu_transform_plan* out, int* elem) {
+  if (!seq || !d || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  *elem = kElemU16;
+  const int fmt = seq->chroma_format;
+  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 7) || (seq->height & 7)) return HMGPU_EINVAL;
+  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
+  if (d->value != HMGPU_TRANSFORM_LEVELS && d->value != HMGPU_TRANSFORM_COEFFS) return HMGPU_EINVAL;
+  if (d->components < 1 || d->components > 7) return HMGPU_EINVAL;
+  if (d->sample_type < HMGPU_SAMPLE_UINT || d->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EUNSUPPORTED;
+  *elem = d->sample_type == HMGPU_SAMPLE_UINT ? kElemU16 : d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
+  if (*elem != kElemU16)
+    for (int k = 0; k < 3; k++) if (((d->components >> k) & 1) && !std::isfinite(d->scale[k])) return HMGPU_EINVAL;
+  const int csx = (fmt == 1 || fmt == 2) ? 1 : 0, csy = fmt == 1 ? 1 : 0, es = *elem == kElemF32 ? 4 : 2;
+  for (int k = 0; k < 3; k++) {
+    if (!((d->components >> k) & 1) || (k && fmt == 0)) continue;
+    out->channels[k] = 1; out->elem_bytes[k] = es;
+    out->width[k] = k ? seq->width >> csx : seq->width; out->height[k] = k ? seq->height >> csy : seq->height;
+    out->row_bytes[k] = out->width[k] * es;
+  }
+  const int I = HMGPU_TRANSFORM_DST_INFO;
+  out->channels[I] = HMGPU_TRANSFORM_INFO_CHANNELS; out->elem_bytes[I] = 1;
+  out->width[I] = seq->width / 4; out->height[I] = seq->height / 4; out->row_bytes[I] = out->width[I];
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_transform_plan_for(const hmgpu_seq_params* seq, const hmgpu_transform_desc* d, int32_t n, hmgpu_transform_plan* out) {
+  int elem = 0;
+  const hmgpu_status st = transform_plan(seq, d, n, out, &elem);
+  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+// the destinations of a call: the planes as the residual export's (one plane per slot, 16-byte stores where aligned; the chroma
+// destinations of a 4:0:0 picture are ignored), the info grid with its channel stride; at least one of the four
+struct TransformInfoPlan { int32_t channels[1], height[1], elem_bytes[1], row_bytes[1]; };
+static hmgpu_status transform_dst_ok(const hmgpu_ctx* c, const hmgpu_transform_plan& plan, int n, void* const dst[3], void* dst_info,
+                                     const int64_t* pitch, const int64_t* pstride, const int64_t* bstride, int* vec) {
+  const int slots = c->seq.chroma_format == 0 ? 1 : 3, I = HMGPU_TRANSFORM_DST_INFO;
+  bool planes = false;
+  for (int k = 0; k < slots; k++) planes = planes || dst[k];
+  *vec = 0;
+  if (!planes && !dst_info) return HMGPU_EINVAL;
+  if (planes) { const hmgpu_status st = strided_dst_ok(c, plan, slots, n, dst, pitch, nullptr, bstride, 16, vec); if (st != HMGPU_OK) return st; }
+  if (dst_info) {
+    const TransformInfoPlan ip = {{plan.channels[I]}, {plan.height[I]}, {plan.elem_bytes[I]}, {plan.row_bytes[I]}};
+    void* const di[1] = {dst_info};
+    int v = 0;
+    const hmgpu_status st = strided_dst_ok(c, ip, 1, n, di, pitch + I, pstride + I, bstride + I, 0, &v);
+    if (st != HMGPU_OK) return st;
+  }
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_transform_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_transform_desc* d, void* const dst[3], void* dst_info,
+                                               const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
+                                               const int64_t batch_stride_bytes[4]) {
+  if (!c || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
+  hmgpu_transform_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = transform_plan(&c->seq, d, n, &plan, &elem); if (st != HMGPU_OK) return st; }
+  return transform_dst_ok(c, plan, n, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
+}
+
+hmgpu_status hmgpu_pictures_transform_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
+  return hmgpu_pictures_motion_check(c, n, pics);                      // the same record: every CTU covered by decompress calls
+}
+
+hmgpu_status hmgpu_pictures_export_transform(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_transform_desc* d,
+                                             void* const dst[3], void* dst_info, const int64_t pitch_bytes[4],
+                                             const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
+                                             void* stream) {
+  if (!c || !pics || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  hmgpu_transform_plan plan;
+  int elem = 0, vec = 0;
+  { const hmgpu_status st = transform_plan(&c->seq, d, n, &plan, &elem); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = hmgpu_pictures_transform_check(c, n, pics); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = transform_dst_ok(c, plan, n, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  TransformArgs a;
+  memset(&a, 0, sizeof(a));
+  const bool mono = c->seq.chroma_format == 0;
+  a.n = n; a.mono = mono; a.comps = mono ? d->components & 1 : d->components;
+  a.fmt = c->fmt; a.csx = c->csx; a.csy = c->csy;
+  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
+  a.width = c->seq.width; a.height = c->seq.height;
+  a.bd[0] = c->seq.bit_depth_luma; a.bd[1] = a.bd[2] = c->seq.bit_depth_chroma;
+  for (int i = 0; i < n; i++) {
+    const Picture& pic = c->pics[pics[i]];
+    const PicDev& p = pic.dev;
+    TransformSrc& s = a.src[i];
+    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.qp = p.qp; s.tr_idx = p.tr_idx;
+    for (int k = 0; k < 3; k++) { s.cbf[k] = p.cbf[k]; s.tskip[k] = p.tskip[k]; s.coef[k] = p.coef[k]; s.coef_start[k] = p.coef_start[k]; }
+    s.bypass = p.bypass; s.ipcm = p.ipcm;
+    s.intra_dir[0] = p.intra_dir[0]; s.intra_dir[1] = p.intra_dir[1];
+    s.slice_idx = p.slice_idx; s.slices = p.slices; s.sl_m = p.sl_m;
+    // the intra modes are the picture's only when EVERY call that covers it came with intra_dir[] (the residual export's rule)
+    bool dir = !pic.calls.empty();
+    for (const SliceCall& sc : pic.calls) dir = dir && sc.dir;
+    s.gate = (dir ? kTransDir : 0) | (pic.flags_staged ? kTransFlags : 0);
+  }
+  for (int k = 0; k < (mono ? 1 : 3); k++) {
+    if (!dst[k]) continue;
+    a.dst[k] = static_cast<uint8_t*>(dst[k]);
+    a.pitch[k] = pitch_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
+    a.scale[k] = d->scale[k];
+  }
+  if (dst_info) {
+    const int I = HMGPU_TRANSFORM_DST_INFO;
+    a.dst[I] = static_cast<uint8_t*>(dst_info);
+    a.pitch[I] = pitch_bytes[I]; a.pstride[I] = plane_stride_bytes[I]; a.bstride[I] = batch_stride_bytes[I];
+  }
+  a.vec = vec;
+  launch_transform(a, d->value == HMGPU_TRANSFORM_COEFFS, elem, c->num_ctus, hs);
   return export_end(c, n, pics, on_stream, hs);
 }
 

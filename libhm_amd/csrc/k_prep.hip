@@ -12,28 +12,12 @@
 //     whether the left/top border of a partition is a CU, TU or PU edge follows from depth, tr_idx and part_size.
 #include "hmgpu_dev.h"
 #include "filter_core.h"
+#include "quant_core.h"                            // qp_param: QpParam of a block, shared with k_transform.hip
 
 namespace hmgpu {
 
-__constant__ uint8_t c_chroma_scale_420[58] = {   // HM g_aucChromaScale[CHROMA_420], TComRom.cpp:503
-    0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
-    29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51};
-
 __constant__ uint8_t c_chroma422_mode[36] = {      // g_chroma422IntraAngleMappingTable, TComRom.cpp:534-536
     0, 1, 2, 2, 2, 2, 3, 5, 7, 8, 10, 12, 13, 15, 17, 18, 19, 20, 21, 22, 23, 23, 24, 24, 25, 25, 26, 27, 27, 28, 28, 29, 29, 30, 31, 36};
-
-// QpParam (TComTrQuant.cpp:71-100); fmt: chroma_format_idc -- the 4:2:0 table, min(qPi, 51) otherwise (g_aucChromaScale, TComRom.cpp:499-506)
-__device__ inline void qp_param(int qp_y, int comp, int bd, int chroma_off, int fmt, int8_t& per, int8_t& rem) {
-  const int bdo = 6 * (bd - 8);
-  int base;
-  if (comp == 0) base = qp_y + bdo;
-  else {
-    base = clip3(-bdo, 57, qp_y + chroma_off);
-    base = base < 0 ? base + bdo : (fmt == 1 ? c_chroma_scale_420[base] : min(base, 51)) + bdo;
-  }
-  per = (int8_t)(base / 6);
-  rem = (int8_t)(base % 6);
-}
 
 // One thread handles the four partitions of one 8x8 luma area (z = 4q .. 4q+3: consecutive in HM's z-scan), so every
 // byte array is read as one dword per thread and both MV fields as one 16-byte vector.  8x8 is the minimum CU size,

@@ -13,6 +13,7 @@
 //           tiles, so every 128-byte line a wave loads is used up by it, and eight lanes store 128 contiguous bytes of a row
 //   DENSE   one lane per eight output samples of a row; a slot (and its two flags) is loaded once per run of samples that share it
 #include "hmgpu_dev.h"
+#include "quant_core.h"                            // resid_elem: the output element, shared with k_transform.hip
 
 namespace hmgpu {
 
@@ -58,22 +59,6 @@ __device__ inline u32x4 load_slot(const ResidSrc& s, const ResidArgs& a, int com
 __device__ inline int slot_sample(const u32x4& v, int i) {
   const uint32_t w = (i & 4) ? ((i & 2) ? v.w : v.z) : ((i & 2) ? v.y : v.x);
   return (int16_t)((i & 1) ? (w >> 16) : (w & 0xffffu));
-}
-
-// the output element of residual r: int16 as it is, or convert((float)r * sc) -- one binary32 product, then the conversion of the
-// batched tensor export (float16 / bfloat16: nearest even)
-template <int ELEM> __device__ inline uint32_t resid_elem(int r, float sc) {
-  if constexpr (ELEM == kElemU16) return (uint32_t)r & 0xffffu;
-  else {
-    float f = (float)r * sc;
-    // the product is rounded to binary32 and keeps its sign when it is zero: without this fence the compiler folds product and
-    // conversion into one mixed-precision fma with a +0 addend, which turns -0 (r = 0, sc < 0) into +0
-    if constexpr (ELEM == kElemF16) asm("" : "+v"(f));
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if constexpr (ELEM == kElemF32) return u;
-    else if constexpr (ELEM == kElemF16) return __builtin_bit_cast(uint16_t, (_Float16)f);
-    else return ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16) & 0xffffu;       // (f is never a NaN: r and sc are finite)
-  }
 }
 
 }  // namespace

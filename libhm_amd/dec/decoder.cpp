@@ -1194,6 +1194,18 @@ hmgpu_status Decoder::export_residual(int n, PicData* const* pics, const hmgpu_r
         return hmgpu_pictures_export_residual(c, rn, h, desc, scale, w, d, pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
+hmgpu_status Decoder::export_transform(int n, PicData* const* pics, const hmgpu_transform_desc* desc, void* const dst[3], void* dst_info,
+                                        const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4],
+                                        int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  void* const all[4] = {dst[0], dst[1], dst[2], dst_info};
+  return export_side<4>(n, pics, nullptr, all, batch_stride_bytes,
+      [&](hmgpu_ctx* c) { return hmgpu_transform_destination_check(c, n, desc, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
+      [](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const*, const int64_t*) { return hmgpu_pictures_transform_check(c, rn, h); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window*, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_export_transform(c, rn, h, desc, d, d[3], pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
+}
+
 // hmgpu_pictures_metrics through export_side, the results the fourth destination behind the reference planes: the whole call --
 // description, reference planes and results of all n slots -- validated once (the first handle standing for every slot), then every
 // run's handles, then one call per run.

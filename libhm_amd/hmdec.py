@@ -107,6 +107,9 @@ def lib():
         L.hmdec_pictures_export_residual.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ResidualDesc),
                                                      C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_transform.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.TransformDesc),
+                                                      C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                      C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc),
@@ -299,6 +302,11 @@ class Picture:
                                     [flip] if flip or window is not None else None, dtype, scale, None, crop)
         return {k: t[0] for k, t in out.items()}
 
+    def transform(self, value="levels", components=(0, 1, 2), dtype=None, scale=None):
+        """export_transform_batch of this picture alone, the tensors without the batch dimension"""
+        out = export_transform_batch([self], value, components, dtype, scale)
+        return {k: t[0] for k, t in out.items()}
+
     def metrics(self, ref, components=(0, 1, 2), ssim=True, crop=None):
         """metrics_batch of this picture alone: ref the planes [h_c, w_c] per component; the fields without the batch dimension"""
         out = metrics_batch([self], [None if t is None else t[None] for t in ref], components, ssim, crop)
@@ -371,6 +379,26 @@ def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=No
             raise HmgpuError(r, "hmdec_pictures_export_residual")
     return residual.export_residual(call, seq, dev, len(pictures) if n is None else n, form, components, size, windows, flip, dtype, scale, out,
                                     crop, enqueue)
+
+
+def export_transform_batch(pictures, value="levels", components=(0, 1, 2), dtype=None, scale=None, out=None):
+    """The quantised levels ("levels") or de-quantised transform coefficients ("coeffs") of up to 16 pictures a decoder has put out
+    (fetched since the last push, one sequence, one GPU: hmdec_pictures_export_transform) and their transform-unit info grid as a
+    dict of torch tensors with a leading batch dimension, written on torch.cuda.current_stream(): libhm_amd.transform describes the
+    keys.  The planes are the coded picture; a conformance crop is a slice of the tensors."""
+    from . import HmgpuError, transform
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("export_transform_batch: no pictures")
+    first, seq, _ = _prologue(pictures, "export_transform_batch", (0, 0, 0, 0), None)
+    dev = _device(first, "export_transform_batch")
+
+    def call(desc, ptrs, pitches, pstrides, bstrides, st):
+        r = lib().hmdec_pictures_export_transform(first.ctx, len(pictures), _handles(pictures), C.byref(desc),
+                                                  *transform.c_args(ptrs, pitches, pstrides, bstrides), 1, abi.addr(st))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_transform")
+    return transform.export_transform(call, seq, dev, len(pictures), value, components, dtype, scale, out)
 
 
 def metrics_batch(pictures, ref, components=(0, 1, 2), ssim=True, crop=None):
