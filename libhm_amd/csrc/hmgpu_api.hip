@@ -1,6 +1,6 @@
 // hmgpu_api.hip -- core of the host runtime of libhmgpu.so: the context and its event rings, device pictures (the DPB lives in HBM),
 // kernel sequencing (run_recon, run_filter, stage_sao), stats / profiling / replay and the KAT entry points.  Input staging, output and
-// export live in hmgpu_input.hip, hmgpu_output.hip and hmgpu_export.hip; hmgpu_host.h holds what the units share.
+// export live in hmgpu_input.hip, hmgpu_output.hip, hmgpu_export.hip, hmgpu_side.hip and hmgpu_analysis.hip; hmgpu_host.h holds what the units share.
 //
 // Host-side counterpart of TDecGop/TDecSlice/TDecCu's control flow (TDecGop.cpp:105-217), reduced to what is left
 // once every traversal runs on the device: copy arrays, launch kernels, keep per-picture state.  The only serial

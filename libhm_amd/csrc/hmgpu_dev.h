@@ -245,6 +245,20 @@ __host__ __device__ inline int zscan_x(int z) {   // HM g_auiZscanToRaster colum
   int x = z & 0x5555; x = (x | (x >> 1)) & 0x3333; x = (x | (x >> 2)) & 0x0f0f; x = (x | (x >> 4)) & 0x00ff; return x;
 }
 __host__ __device__ inline int zscan_y(int z) { return zscan_x(z >> 1); }
+// ... and its inverse: the low four bits of v on the even bit positions (HM's z-scan: column bits even, row bits odd)
+__device__ inline int spread4(int v) { v = (v | (v << 2)) & 0x33; v = (v | (v << 1)) & 0x55; return v; }
+// the 4x4 luma block (bx, by) in HM's per-partition arrays (CTU raster, z-scan inside a CTU): element (size_t)ctu * parts + z
+struct Part { int ctu, z; };
+__device__ inline Part part_of(int bx, int by, int log2ctu, int ctus_w) {
+  const int sh = log2ctu - 2, m = (1 << sh) - 1;
+  return {(by >> sh) * ctus_w + (bx >> sh), spread4(bx & m) | (spread4(by & m) << 1)};
+}
+// nearest-exact in integers, `in` samples to `out`: min(floor((2 o + 1) * in / (2 * out)), in - 1); (2 o + 1) * in < 2^32 for o < 16384 and in < 2^17
+__device__ inline int nearest_src(int o, int in, int out) { return min((int)(((2u * o + 1u) * (uint32_t)in) / (2u * (uint32_t)out)), in - 1); }
+// is the transform block at transform depth tr coded, of a partition whose cbf byte is `cbf`?  cbf bit d of a partition = cbf of its
+// ancestor TU node at transform depth d (TComDataCU.h:310); HM descends only while every node on the way has its bit set
+// (TComTrQuant.cpp:1558-1564).  The one rule under k_prep's TU lists, hmgpu_pack_levels and the residual and transform exports.
+__host__ __device__ inline bool cbf_coded(uint32_t cbf, int tr) { const uint32_t chain = (1u << (tr + 1)) - 1u; return (cbf & chain) == chain; }
 __device__ inline int clip3(int lo, int hi, int v) { return min(hi, max(lo, v)); }
 __device__ inline BlkInfo ld_blk(const BlkInfo* p) { return __builtin_bit_cast(BlkInfo, ldg4(p)); }
 
@@ -584,7 +598,8 @@ struct MotionSrc {
   const uint16_t* slice_idx;
   const SliceDev* slices;
 };
-struct MotionWin { int32_t left, top, w, h; float kx, ky; };   // dense form: window in luma samples, quarter samples -> output samples
+struct SideWin { int32_t left, top, w, h; };                   // dense forms: a picture's window in luma samples
+struct MotionWin : SideWin { float kx, ky; };                  // ... and quarter samples -> output samples
 struct MotionArgs {
   MotionSrc src[kMaxExportBatch];
   MotionWin win[kMaxExportBatch];
@@ -609,10 +624,9 @@ struct ResidSrc {
   const int16_t* resid[3];
   int32_t gate, pad_;
 };
-struct ResidWin { int32_t left, top, w, h; };   // dense form: window in luma samples
 struct ResidArgs {
   ResidSrc src[kMaxExportBatch];
-  ResidWin win[kMaxExportBatch];
+  SideWin win[kMaxExportBatch];    // dense form
   int32_t n, comps, mono;          // pictures; the component mask (bit c; chroma bits cleared for 4:0:0 pictures); 4:0:0
   int32_t log2ctu, ctus_w, parts;  // geometry of the context
   int32_t rtw[3];                  // residual tiles per tile row of the component

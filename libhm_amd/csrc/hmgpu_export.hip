@@ -1,10 +1,10 @@
-// hmgpu_export.hip -- device export of the host runtime: the shared validation rules under the export plans, scale tables and their
+// hmgpu_export.hip -- picture export of the host runtime: the shared validation rules under the export plans, scale tables and their
 // slots, window tables, colour LUTs, the rules and weights of the chroma stage, the weights and rules of the format export and the
 // rules of the warp; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
-// destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps); strided_dst_ok under the motion / block,
-// residual and transform exports, the reference planes of the picture metrics and the picture metric maps, the picture histograms (k_export.hip,
-// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_motion.hip, k_residual.hip, k_transform.hip, k_metrics.hip, k_metrics_map.hip, k_histogram.hip).
+// destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps) (k_export.hip,
+// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_export_fmt.hip).  Also the rules and the stream bracket that the
+// side-information exports (hmgpu_side.hip) and the picture analyses (hmgpu_analysis.hip) take from here: hmgpu_host.h.
 #include "hmgpu_host.h"
 
 #include <algorithm>
@@ -17,21 +17,13 @@
 #include <tuple>
 #include <vector>
 
-extern "C" {
-
-// ------------------------------------------------------------------------------------------------ device export (k_export.hip)
-static long long round_half_away(double v) { return v < 0 ? -(long long)std::floor(-v + 0.5) : (long long)std::floor(v + 0.5); }
+// ------------------------------------------------------------------------------------------------ shared with hmgpu_side.hip and hmgpu_analysis.hip (hmgpu_host.h)
+namespace hmgpu_host __attribute__((visibility("hidden"))) {
 
 // the chroma subsampling of a chroma_format_idc
-static void chroma_shifts(int fmt, int* csx, int* csy) { *csx = fmt == 3 ? 0 : 1; *csy = fmt == 1 || fmt == 0 ? 1 : 0; }
+void chroma_shifts(int fmt, int* csx, int* csy) { *csx = fmt == 3 ? 0 : 1; *csy = fmt == 1 || fmt == 0 ? 1 : 0; }
 
-// the output depth per channel type (a 0 of the descriptor: the coding depth); RGB: the first one for both
-static void out_depths(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int ob[2]) {
-  ob[0] = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
-  ob[1] = d->layout == HMGPU_EXPORT_RGB ? ob[0] : d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma;
-}
-
-static hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc) {
+hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc) {
   for (int k = 0; k < 5; k++) if (sc->reserved[k]) return HMGPU_EINVAL;
   if (sc->filter < HMGPU_SCALE_NEAREST || sc->filter > HMGPU_SCALE_AREA || sc->width <= 0 || sc->height <= 0) return HMGPU_EINVAL;
   return HMGPU_OK;
@@ -41,7 +33,7 @@ static hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc) {
 static bool scale_ratio_ok(long long in, long long out) { return out <= 16384 && in <= 32 * out && out <= 8 * in; }
 
 // a crop of the coded picture, w x h: nothing negative, not empty, whole chroma samples, and (sc) within the limits of scaling to sc
-static hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], const hmgpu_export_scale* sc, int* w, int* h) {
+hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], const hmgpu_export_scale* sc, int* w, int* h) {
   if (cr[0] < 0 || cr[1] < 0 || cr[2] < 0 || cr[3] < 0) return HMGPU_EINVAL;
   *w = seq->width - cr[0] - cr[1]; *h = seq->height - cr[2] - cr[3];
   if (*w <= 0 || *h <= 0) return HMGPU_EINVAL;
@@ -54,8 +46,62 @@ static hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], co
 
 // a window: its own fields, then its crop
 static bool window_fields_ok(const hmgpu_export_window& win) { return !((win.flip & ~1) || win.reserved[0] || win.reserved[1] || win.reserved[2]); }
-static hmgpu_status window_ok(const hmgpu_seq_params* seq, const hmgpu_export_window& win, const hmgpu_export_scale* sc, int* w, int* h) {
+hmgpu_status window_ok(const hmgpu_seq_params* seq, const hmgpu_export_window& win, const hmgpu_export_scale* sc, int* w, int* h) {
   return window_fields_ok(win) ? crop_ok(seq, win.crop, sc, w, h) : HMGPU_EINVAL;
+}
+
+// true if [p, p + bytes) lies inside one device allocation of `device`
+bool device_span_ok(const void* p, size_t bytes, int device) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (at.type != hipMemoryTypeDevice || at.device != device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+  return q >= b && q - b + bytes <= size;
+}
+
+// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device and then waits
+// for everything enqueued for the pictures
+hmgpu_status export_open(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
+  *hs = c->stream;
+  if (!on_stream) return HMGPU_OK;
+  *hs = (hipStream_t)stream;
+  if (*hs) {
+    hipDevice_t dev = -1;
+    if (hipStreamGetDevice(*hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
+    if ((int)dev != c->device) return HMGPU_EINVAL;
+  }
+  for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                   // behind everything enqueued for the picture ...
+  HIP_TRY(c, hipStreamWaitEvent(*hs, c->exp_ev[0], 0));                  // ... and behind what is already on the caller's stream
+  return HMGPU_OK;
+}
+
+// after the export's launch
+hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs) {
+  HIP_TRY(c, hipGetLastError());
+  if (on_stream) {
+    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
+  }
+  for (int i = 0; i < n; i++) touch(c, pics[i]);
+  commit_use(c);
+  return HMGPU_OK;
+}
+
+}  // namespace hmgpu_host
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ device export (k_export.hip)
+static long long round_half_away(double v) { return v < 0 ? -(long long)std::floor(-v + 0.5) : (long long)std::floor(v + 0.5); }
+
+// the output depth per channel type (a 0 of the descriptor: the coding depth); RGB: the first one for both
+static void out_depths(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, int ob[2]) {
+  ob[0] = d->bit_depth[0] ? d->bit_depth[0] : seq->bit_depth_luma;
+  ob[1] = d->layout == HMGPU_EXPORT_RGB ? ob[0] : d->bit_depth[1] ? d->bit_depth[1] : seq->bit_depth_chroma;
 }
 
 // H.273 Kr / Kb of the matrix_coefficients codes the export takes (Table 4): false for any other code
@@ -123,47 +169,6 @@ hmgpu_status hmgpu_export_plan_for(const hmgpu_seq_params* seq, const hmgpu_expo
     out->width[k] = W >> csx; out->height[k] = H >> csy;
     out->row_bytes[k] = (d->layout == HMGPU_EXPORT_PLANAR ? 1 : 2) * out->width[k] * B;
   }
-  return HMGPU_OK;
-}
-
-// true if [p, p + bytes) lies inside one device allocation of `device`
-static bool device_span_ok(const void* p, size_t bytes, int device) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (at.type != hipMemoryTypeDevice || at.device != device) return false;
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
-  return q >= b && q - b + bytes <= size;
-}
-
-// the stream an export runs on: the context's (on_stream 0) or the caller's, which must belong to the context's device and then waits
-// for everything enqueued for the pictures
-static hmgpu_status export_open(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs) {
-  *hs = c->stream;
-  if (!on_stream) return HMGPU_OK;
-  *hs = (hipStream_t)stream;
-  if (*hs) {
-    hipDevice_t dev = -1;
-    if (hipStreamGetDevice(*hs, &dev) != hipSuccess) { (void)hipGetLastError(); return HMGPU_EINVAL; }
-    if ((int)dev != c->device) return HMGPU_EINVAL;
-  }
-  for (int k = 0; k < 2; k++) if (!c->exp_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->exp_ev[k], hipEventDisableTiming));
-  HIP_TRY(c, hipEventRecord(c->exp_ev[0], c->stream));                   // behind everything enqueued for the picture ...
-  HIP_TRY(c, hipStreamWaitEvent(*hs, c->exp_ev[0], 0));                  // ... and behind what is already on the caller's stream
-  return HMGPU_OK;
-}
-
-// after the export's launch
-static hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs) {
-  HIP_TRY(c, hipGetLastError());
-  if (on_stream) {
-    HIP_TRY(c, hipEventRecord(c->exp_ev[1], hs));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->exp_ev[1], 0));          // whatever the context does next with the picture waits for the export
-  }
-  for (int i = 0; i < n; i++) touch(c, pics[i]);
-  commit_use(c);
   return HMGPU_OK;
 }
 
@@ -1229,76 +1234,6 @@ static void export_args_tail(Args& a, const hmgpu_seq_params& seq, const ExportC
   memcpy(a.coef, r.plan.coef, sizeof(a.coef));
 }
 
-// the destinations of a side-information export, `slots` of them, a null one not written: element alignment, strides against the extents
-// they step over (pstride null: one plane per slot), and the whole span of n pictures inside one allocation of the context's device,
-// which it makes the current one.
-// vec: bit k set when slot k may take stores of `granule` bytes (0: four elements)
-template <class Plan>
-static hmgpu_status strided_dst_ok(const hmgpu_ctx* c, const Plan& plan, int slots, int n, void* const* dst, const int64_t* pitch,
-                                   const int64_t* pstride, const int64_t* bstride, int granule, int* vec) {
-  hipSetDevice(c->device);
-  bool any = false;
-  *vec = 0;
-  for (int k = 0; k < slots; k++) {
-    if (!dst[k]) continue;
-    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
-    any = true;
-    const int64_t es = plan.elem_bytes[k], g = granule ? granule : 4 * es;
-    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
-    int64_t pic = plane;
-    if (pstride) {
-      if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48) || pstride[k] % es) return HMGPU_EINVAL;
-      pic = pstride[k] * (plan.channels[k] - 1) + plane;
-    }
-    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
-    if ((uintptr_t)dst[k] % es || pitch[k] % es || bstride[k] % es) return HMGPU_EINVAL;
-    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
-    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && bstride[k] % g == 0 && (!pstride || pstride[k] % g == 0)) *vec |= 1 << k;
-  }
-  return any ? HMGPU_OK : HMGPU_EINVAL;
-}
-
-// what MetricsArgs and MetricsMapArgs share: the SSIM constants, per plane class the cropped plane, per picture the first sample of
-// both sides and whether its groups of 4 take one load, the caller's planes
-template <class Args>
-static void metrics_sources(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
-                            const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, const hmgpu_metrics_plan& plan, int vec,
-                            Args* out) {
-  Args& a = *out;
-  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
-  a.n = n;
-  const int bd[2] = {c->seq.bit_depth_luma, c->seq.bit_depth_chroma};
-  for (int k = 0; k < 2; k++) {
-    const double maxv = (double)((1 << bd[k]) - 1);
-    a.c1[k] = (int64_t)(.01 * .01 * maxv * maxv * 64 + .5);
-    a.c2[k] = (int64_t)(.03 * .03 * maxv * maxv * 64 * 63 + .5);
-    const int comp = k ? (plan.channels[1] ? 1 : 2) : 0;             // a component of the class that is compared, if any
-    if (!plan.channels[comp]) continue;
-    a.w[k] = plan.width[comp]; a.h[k] = plan.height[comp]; a.pitch[k] = c->pitch[k];
-  }
-  for (int k = 0; k < 3; k++) {
-    if (!plan.channels[k]) continue;
-    a.comps |= 1 << k;
-    if (planes) { a.bq[k] = static_cast<const uint8_t*>(ref[k]); a.bpitch[k] = ref_pitch[k]; a.bstride[k] = ref_bstride[k]; }
-  }
-  a.bvec = (uint32_t)vec;
-  const int x0 = d->crop[0], y0 = d->crop[2];
-  for (int i = 0; i < n; i++) {
-    for (int side = 0; side < (planes ? 1 : 2); side++) {
-      const Picture& p = c->pics[side ? ref_pics[i] : pics[i]];
-      int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-      const int16_t* org[2] = {src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0, src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx)};
-      for (int k = 0; k < 2; k++) {
-        (side ? a.bp : a.a)[i][k] = org[k];
-        const size_t g = k ? 16 : 8;                                   // a group of 4 samples, of 4 pairs
-        if (side == 0) a.avec[k] |= 1u << i;
-        if ((uintptr_t)org[k] % g || ((size_t)c->pitch[k] * 2) % g) a.avec[k] &= ~(1u << i);
-      }
-    }
-  }
-}
-
 extern "C" {
 
 // The three argument builders of export_impl -- unscaled, scaled, warp -- each from the resolved call to its launch on hs.  site:
@@ -1545,755 +1480,6 @@ hmgpu_status hmgpu_pictures_export_warp(hmgpu_ctx* c, int32_t n, const hmgpu_pic
   optional_stages(&q, lut, nullptr, chroma, false);
   q.wp = wp; q.maps = maps; q.warp = true;
   return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ side information: what motion and residual share
-// the windows of a dense form, in order (the first failure is the call's status); w x h: the output -- sc's size, or (unscaled) the one
-// size every window has
-static hmgpu_status dense_windows_ok(const hmgpu_seq_params* seq, const hmgpu_export_scale* sc, int n, const hmgpu_export_window* win, int* w, int* h) {
-  for (int i = 0; i < n; i++) {
-    int ww, wh;
-    { const hmgpu_status st = window_ok(seq, win[i], sc, &ww, &wh); if (st != HMGPU_OK) return st; }
-    if (sc) continue;
-    if (!i) { *w = ww; *h = wh; }
-    if (ww != *w || wh != *h) return HMGPU_EINVAL;
-    if (ww > 16384 || wh > 16384) return HMGPU_EUNSUPPORTED;
-  }
-  if (sc) { *w = sc->width; *h = sc->height; }
-  return HMGPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ motion and block export (k_motion.hip)
-// hmgpu_motion_plan_for and what the entry point needs beyond the plan: the output element of the dense form (kElem*)
-static hmgpu_status motion_plan(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int n,
-                                const hmgpu_export_window* win, hmgpu_motion_plan* out, int* elem) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  *elem = kElemU16;
-  const int fmt = seq->chroma_format;
-  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 3) || (seq->height & 3)) return HMGPU_EINVAL;
-  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int k = 0; k < 5; k++) if (d->reserved[k]) return HMGPU_EINVAL;
-  if (d->form != HMGPU_MOTION_BLOCKS && d->form != HMGPU_MOTION_DENSE) return HMGPU_EINVAL;
-  if (d->lists < 1 || d->lists > 3) return HMGPU_EINVAL;
-  const int L = (d->lists & 1) + (d->lists >> 1);
-  int w = 0, h = 0;
-  if (d->form == HMGPU_MOTION_BLOCKS) {
-    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
-    if ((d->crop[0] | d->crop[1] | d->crop[2] | d->crop[3]) & 3) return HMGPU_EINVAL;         // whole blocks (a negative crop: crop_ok)
-    if (crop_ok(seq, d->crop, nullptr, &w, &h) != HMGPU_OK) return HMGPU_EINVAL;
-    w /= 4; h /= 4;
-    out->channels[HMGPU_MOTION_DST_MV0] = 2 * L;
-    out->elem_bytes[HMGPU_MOTION_DST_MV0] = 2;
-  } else {
-    if (!win) return HMGPU_EINVAL;
-    if (d->sample_type != HMGPU_SAMPLE_F16 && d->sample_type != HMGPU_SAMPLE_BF16 && d->sample_type != HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
-    if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;            // the window is the crop
-    *elem = d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
-    if (sc) {
-      { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
-      if (sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                       // vectors are not interpolated
-    }
-    { const hmgpu_status st = dense_windows_ok(seq, sc, n, win, &w, &h); if (st != HMGPU_OK) return st; }
-    const int es = *elem == kElemF32 ? 4 : 2;
-    for (int l = 0; l < 2; l++) if ((d->lists >> l) & 1) { out->channels[l] = 2; out->elem_bytes[l] = es; }
-  }
-  out->lists = L;
-  out->channels[HMGPU_MOTION_DST_REF] = L; out->elem_bytes[HMGPU_MOTION_DST_REF] = 4;
-  out->channels[HMGPU_MOTION_DST_BLOCK] = 4; out->elem_bytes[HMGPU_MOTION_DST_BLOCK] = 1;
-  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
-    if (!out->channels[k]) { out->elem_bytes[k] = 0; continue; }
-    out->width[k] = w; out->height[k] = h; out->row_bytes[k] = w * out->elem_bytes[k];
-  }
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_motion_plan_for(const hmgpu_seq_params* seq, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc, int32_t n,
-                                   const hmgpu_export_window windows[], hmgpu_motion_plan* out) {
-  int elem = 0;
-  const hmgpu_status st = motion_plan(seq, d, sc, n, windows, out, &elem);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-hmgpu_status hmgpu_motion_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_motion_desc* d, const hmgpu_export_scale* sc,
-                                            const hmgpu_export_window windows[], void* const dst_mv[2], void* dst_ref, void* dst_block,
-                                            const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
-                                            const int64_t batch_stride_bytes[4]) {
-  if (!c || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  hmgpu_motion_plan plan;
-  int elem = 0, vec = 0;
-  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
-  return strided_dst_ok(c, plan, HMGPU_MOTION_DSTS, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, 0, &vec);
-}
-
-hmgpu_status hmgpu_pictures_motion_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
-  if (!c || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int i = 0; i < n; i++) {
-    if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-    if (c->pics[pics[i]].covered_ctus != c->num_ctus) return HMGPU_EINVAL;       // no side information (uploaded, received, partly decoded)
-  }
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_pictures_export_motion(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_motion_desc* d,
-                                          const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst_mv[2],
-                                          void* dst_ref, void* dst_block, const int64_t pitch_bytes[4],
-                                          const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
-                                          void* stream) {
-  if (!c || !pics || !d || !dst_mv || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  { const hmgpu_status st = hmgpu_pictures_motion_check(c, n, pics); if (st != HMGPU_OK) return st; }
-  hmgpu_motion_plan plan;
-  int elem = 0, vec = 0;
-  { const hmgpu_status st = motion_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  void* const dst[4] = {dst_mv[0], dst_mv[1], dst_ref, dst_block};
-  { const hmgpu_status st = strided_dst_ok(c, plan, HMGPU_MOTION_DSTS, n, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, 0, &vec); if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  MotionArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n = n; a.lists = d->lists; a.nlists = plan.lists;
-  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
-  for (int i = 0; i < n; i++) {
-    const PicDev& p = c->pics[pics[i]].dev;
-    MotionSrc& s = a.src[i];
-    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.qp = p.qp;
-    for (int l = 0; l < 2; l++) { s.mv[l] = p.mv[l]; s.ref_idx[l] = p.ref_idx[l]; }
-    s.slice_idx = p.slice_idx; s.slices = p.slices;
-  }
-  for (int k = 0; k < HMGPU_MOTION_DSTS; k++) {
-    if (!dst[k]) continue;
-    a.dst[k] = static_cast<uint8_t*>(dst[k]);
-    a.pitch[k] = pitch_bytes[k]; a.pstride[k] = plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
-  }
-  a.vec = vec;
-  if (d->form == HMGPU_MOTION_BLOCKS) {
-    a.x4 = d->crop[0] / 4; a.y4 = d->crop[2] / 4; a.w4 = plan.width[HMGPU_MOTION_DST_REF]; a.h4 = plan.height[HMGPU_MOTION_DST_REF];
-    if (a.x4 & 3) a.vec = 0;                         // a lane's four blocks are aligned in the picture, not in the crop
-    launch_motion_blocks(a, hs);
-  } else {
-    a.W = plan.width[HMGPU_MOTION_DST_REF]; a.H = plan.height[HMGPU_MOTION_DST_REF];
-    for (int i = 0; i < n; i++) {
-      const int* cr = windows[i].crop;
-      MotionWin& w = a.win[i];
-      w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
-      a.flip |= (uint32_t)(windows[i].flip & 1) << i;
-      w.kx = (float)((double)a.W / (4.0 * w.w)); w.ky = (float)((double)a.H / (4.0 * w.h));     // quarter luma samples -> output samples
-    }
-    launch_motion_dense(a, elem, hs);
-  }
-  return export_end(c, n, pics, on_stream, hs);
-}
-
-// ------------------------------------------------------------------------------------------------ residual export (k_residual.hip)
-// hmgpu_residual_plan_for and what the entry point needs beyond the plan: the output element (kElem*; kElemU16 stands for int16)
-static hmgpu_status residual_plan(const hmgpu_seq_params* seq, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc, int n,
-                                  const hmgpu_export_window* win, hmgpu_residual_plan* out, int* elem) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  *elem = kElemU16;
-  const int fmt = seq->chroma_format;
-  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 7) || (seq->height & 7)) return HMGPU_EINVAL;
-  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
-  if (d->form != HMGPU_RESIDUAL_PLANES && d->form != HMGPU_RESIDUAL_DENSE) return HMGPU_EINVAL;
-  if (d->components < 1 || d->components > 7) return HMGPU_EINVAL;
-  if (sc) { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
-  if (fmt >= 2) return HMGPU_EUNSUPPORTED;          // k_ccp rewrites their chroma tiles in place; 4:2:2 blocks are two squares
-  const bool mono = fmt == 0;
-  if (d->form == HMGPU_RESIDUAL_PLANES) {
-    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
-    if ((d->crop[0] | d->crop[1] | d->crop[2] | d->crop[3]) & 7) return HMGPU_EINVAL;         // whole 8x8 tiles (a negative crop: crop_ok)
-    int w, h;
-    if (crop_ok(seq, d->crop, nullptr, &w, &h) != HMGPU_OK) return HMGPU_EINVAL;
-    for (int k = 0; k < 3; k++) {
-      if (!((d->components >> k) & 1) || (k && mono)) continue;
-      out->channels[k] = 1; out->elem_bytes[k] = 2;
-      out->width[k] = k ? w / 2 : w; out->height[k] = k ? h / 2 : h; out->row_bytes[k] = out->width[k] * 2;
-    }
-    return HMGPU_OK;
-  }
-  if (!win) return HMGPU_EINVAL;
-  if (d->sample_type < HMGPU_SAMPLE_UINT || d->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EINVAL;
-  if (d->crop[0] || d->crop[1] || d->crop[2] || d->crop[3]) return HMGPU_EINVAL;              // the window is the crop
-  *elem = d->sample_type == HMGPU_SAMPLE_UINT ? kElemU16 : d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
-  if (*elem != kElemU16)
-    for (int k = 0; k < 3; k++) if (((d->components >> k) & 1) && !std::isfinite(d->scale[k])) return HMGPU_EINVAL;
-  if (sc && sc->filter != HMGPU_SCALE_NEAREST) return HMGPU_EUNSUPPORTED;                    // a residual is not interpolated
-  int w = 0, h = 0;
-  { const hmgpu_status st = dense_windows_ok(seq, sc, n, win, &w, &h); if (st != HMGPU_OK) return st; }
-  out->channels[0] = (d->components & 1) + ((d->components >> 1) & 1) + ((d->components >> 2) & 1);
-  out->elem_bytes[0] = *elem == kElemF32 ? 4 : 2;
-  out->width[0] = w; out->height[0] = h; out->row_bytes[0] = w * out->elem_bytes[0];
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_residual_plan_for(const hmgpu_seq_params* seq, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc, int32_t n,
-                                     const hmgpu_export_window windows[], hmgpu_residual_plan* out) {
-  int elem = 0;
-  const hmgpu_status st = residual_plan(seq, d, sc, n, windows, out, &elem);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-hmgpu_status hmgpu_residual_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_residual_desc* d, const hmgpu_export_scale* sc,
-                                              const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
-                                              const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]) {
-  if (!c || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  hmgpu_residual_plan plan;
-  int elem = 0, vec = 0;
-  { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  const bool planes = d->form == HMGPU_RESIDUAL_PLANES;
-  const int slots = planes && c->seq.chroma_format == 0 ? 1 : 3;       // (the chroma destinations of a 4:0:0 picture's planes are ignored)
-  return strided_dst_ok(c, plan, slots, n, dst, pitch_bytes, planes ? nullptr : plane_stride_bytes, batch_stride_bytes, 16, &vec);
-}
-
-hmgpu_status hmgpu_pictures_residual_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
-  return hmgpu_pictures_motion_check(c, n, pics);                      // the same record: every CTU covered by decompress calls
-}
-
-hmgpu_status hmgpu_pictures_export_residual(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_residual_desc* d,
-                                            const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst[3],
-                                            const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3],
-                                            const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
-  if (!c || !pics || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  hmgpu_residual_plan plan;
-  int elem = 0, vec = 0;
-  // (the format's refusal comes first: it does not depend on the pictures)
-  { const hmgpu_status st = residual_plan(&c->seq, d, sc, n, windows, &plan, &elem); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = hmgpu_pictures_residual_check(c, n, pics); if (st != HMGPU_OK) return st; }
-  const bool planes = d->form == HMGPU_RESIDUAL_PLANES;
-  const int slots = planes && c->seq.chroma_format == 0 ? 1 : 3;       // (the chroma destinations of a 4:0:0 picture's planes are ignored)
-  { const hmgpu_status st = strided_dst_ok(c, plan, slots, n, dst, pitch_bytes, planes ? nullptr : plane_stride_bytes, batch_stride_bytes, 16, &vec); if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  ResidArgs a;
-  memset(&a, 0, sizeof(a));
-  const bool mono = c->seq.chroma_format == 0;
-  a.n = n; a.mono = mono; a.comps = mono ? d->components & 1 : d->components;
-  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
-  for (int k = 0; k < 3; k++) a.rtw[k] = (c->grid_w / 2) >> (k ? c->csx : 0);
-  for (int i = 0; i < n; i++) {
-    const Picture& pic = c->pics[pics[i]];
-    const PicDev& p = pic.dev;
-    ResidSrc& s = a.src[i];
-    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.tr_idx = p.tr_idx; s.ipcm = p.ipcm;
-    for (int k = 0; k < 3; k++) { s.cbf[k] = p.cbf[k]; s.resid[k] = p.resid[k]; }
-    // intra CUs carry a residual only when EVERY call that covers the picture came with intra_dir[]: a picture whose slice calls
-    // disagree exports its intra CUs as 0 (k_prep listed no TU for those of the calls without the modes: their tiles are stale)
-    bool dir = !pic.calls.empty();
-    for (const SliceCall& sc : pic.calls) dir = dir && sc.dir;
-    s.gate = (dir ? kResidIntra : 0) | (pic.flags_staged ? kResidFlags : 0);
-  }
-  for (int k = 0; k < slots; k++) {
-    if (!dst[k]) continue;
-    a.dst[k] = static_cast<uint8_t*>(dst[k]);
-    a.pitch[k] = pitch_bytes[k]; a.pstride[k] = planes ? 0 : plane_stride_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
-  }
-  a.vec = vec;
-  if (planes) {
-    a.x0 = d->crop[0]; a.y0 = d->crop[2]; a.w = c->seq.width - d->crop[0] - d->crop[1]; a.h = c->seq.height - d->crop[2] - d->crop[3];
-    if (a.x0 & 15) a.vec &= 1;                       // a chroma lane's eight samples are aligned in the picture, not in the crop
-    launch_residual_planes(a, hs);
-  } else {
-    a.W = plan.width[0]; a.H = plan.height[0];
-    int ch = 0;
-    for (int k = 0; k < 3; k++) { a.chan[k] = ch; if ((d->components >> k) & 1) ch++; a.scale[k] = d->scale[k]; }
-    for (int i = 0; i < n; i++) {
-      const int* cr = windows[i].crop;
-      ResidWin& w = a.win[i];
-      w.left = cr[0]; w.top = cr[2]; w.w = c->seq.width - cr[0] - cr[1]; w.h = c->seq.height - cr[2] - cr[3];
-      a.flip |= (uint32_t)(windows[i].flip & 1) << i;
-    }
-    launch_residual_dense(a, elem, hs);
-  }
-  return export_end(c, n, pics, on_stream, hs);
-}
-
-// ------------------------------------------------------------------------------------------------ transform export (k_transform.hip)
-// hmgpu_transform_plan_for and what the entry point needs beyond the plan: the output element (kElem*; kElemU16 stands for int16)
-static hmgpu_status transform_plan(const hmgpu_seq_params* seq, const hmgpu_transform_desc* d, int n, hmgpu_transform_plan* out, int* elem) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  *elem = kElemU16;
-  const int fmt = seq->chroma_format;
-  if (fmt < 0 || fmt > 3 || seq->width <= 0 || seq->height <= 0 || (seq->width & 7) || (seq->height & 7)) return HMGPU_EINVAL;
-  if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
-  if (d->value != HMGPU_TRANSFORM_LEVELS && d->value != HMGPU_TRANSFORM_COEFFS) return HMGPU_EINVAL;
-  if (d->components < 1 || d->components > 7) return HMGPU_EINVAL;
-  if (d->sample_type < HMGPU_SAMPLE_UINT || d->sample_type > HMGPU_SAMPLE_F32) return HMGPU_EUNSUPPORTED;
-  *elem = d->sample_type == HMGPU_SAMPLE_UINT ? kElemU16 : d->sample_type == HMGPU_SAMPLE_F16 ? kElemF16 : d->sample_type == HMGPU_SAMPLE_BF16 ? kElemBF16 : kElemF32;
-  if (*elem != kElemU16)
-    for (int k = 0; k < 3; k++) if (((d->components >> k) & 1) && !std::isfinite(d->scale[k])) return HMGPU_EINVAL;
-  const int csx = (fmt == 1 || fmt == 2) ? 1 : 0, csy = fmt == 1 ? 1 : 0, es = *elem == kElemF32 ? 4 : 2;
-  for (int k = 0; k < 3; k++) {
-    if (!((d->components >> k) & 1) || (k && fmt == 0)) continue;
-    out->channels[k] = 1; out->elem_bytes[k] = es;
-    out->width[k] = k ? seq->width >> csx : seq->width; out->height[k] = k ? seq->height >> csy : seq->height;
-    out->row_bytes[k] = out->width[k] * es;
-  }
-  const int I = HMGPU_TRANSFORM_DST_INFO;
-  out->channels[I] = HMGPU_TRANSFORM_INFO_CHANNELS; out->elem_bytes[I] = 1;
-  out->width[I] = seq->width / 4; out->height[I] = seq->height / 4; out->row_bytes[I] = out->width[I];
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_transform_plan_for(const hmgpu_seq_params* seq, const hmgpu_transform_desc* d, int32_t n, hmgpu_transform_plan* out) {
-  int elem = 0;
-  const hmgpu_status st = transform_plan(seq, d, n, out, &elem);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-// the destinations of a call: the planes as the residual export's (one plane per slot, 16-byte stores where aligned; the chroma
-// destinations of a 4:0:0 picture are ignored), the info grid with its channel stride; at least one of the four
-struct TransformInfoPlan { int32_t channels[1], height[1], elem_bytes[1], row_bytes[1]; };
-static hmgpu_status transform_dst_ok(const hmgpu_ctx* c, const hmgpu_transform_plan& plan, int n, void* const dst[3], void* dst_info,
-                                     const int64_t* pitch, const int64_t* pstride, const int64_t* bstride, int* vec) {
-  const int slots = c->seq.chroma_format == 0 ? 1 : 3, I = HMGPU_TRANSFORM_DST_INFO;
-  bool planes = false;
-  for (int k = 0; k < slots; k++) planes = planes || dst[k];
-  *vec = 0;
-  if (!planes && !dst_info) return HMGPU_EINVAL;
-  if (planes) { const hmgpu_status st = strided_dst_ok(c, plan, slots, n, dst, pitch, nullptr, bstride, 16, vec); if (st != HMGPU_OK) return st; }
-  if (dst_info) {
-    const TransformInfoPlan ip = {{plan.channels[I]}, {plan.height[I]}, {plan.elem_bytes[I]}, {plan.row_bytes[I]}};
-    void* const di[1] = {dst_info};
-    int v = 0;
-    const hmgpu_status st = strided_dst_ok(c, ip, 1, n, di, pitch + I, pstride + I, bstride + I, 0, &v);
-    if (st != HMGPU_OK) return st;
-  }
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_transform_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_transform_desc* d, void* const dst[3], void* dst_info,
-                                               const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
-                                               const int64_t batch_stride_bytes[4]) {
-  if (!c || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes) return HMGPU_EINVAL;
-  hmgpu_transform_plan plan;
-  int elem = 0, vec = 0;
-  { const hmgpu_status st = transform_plan(&c->seq, d, n, &plan, &elem); if (st != HMGPU_OK) return st; }
-  return transform_dst_ok(c, plan, n, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec);
-}
-
-hmgpu_status hmgpu_pictures_transform_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[]) {
-  return hmgpu_pictures_motion_check(c, n, pics);                      // the same record: every CTU covered by decompress calls
-}
-
-hmgpu_status hmgpu_pictures_export_transform(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_transform_desc* d,
-                                             void* const dst[3], void* dst_info, const int64_t pitch_bytes[4],
-                                             const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4], int32_t on_stream,
-                                             void* stream) {
-  if (!c || !pics || !d || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
-  hmgpu_transform_plan plan;
-  int elem = 0, vec = 0;
-  { const hmgpu_status st = transform_plan(&c->seq, d, n, &plan, &elem); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = hmgpu_pictures_transform_check(c, n, pics); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = transform_dst_ok(c, plan, n, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  TransformArgs a;
-  memset(&a, 0, sizeof(a));
-  const bool mono = c->seq.chroma_format == 0;
-  a.n = n; a.mono = mono; a.comps = mono ? d->components & 1 : d->components;
-  a.fmt = c->fmt; a.csx = c->csx; a.csy = c->csy;
-  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.parts = c->parts;
-  a.width = c->seq.width; a.height = c->seq.height;
-  a.bd[0] = c->seq.bit_depth_luma; a.bd[1] = a.bd[2] = c->seq.bit_depth_chroma;
-  for (int i = 0; i < n; i++) {
-    const Picture& pic = c->pics[pics[i]];
-    const PicDev& p = pic.dev;
-    TransformSrc& s = a.src[i];
-    s.depth = p.depth; s.part_size = p.part_size; s.pred_mode = p.pred_mode; s.qp = p.qp; s.tr_idx = p.tr_idx;
-    for (int k = 0; k < 3; k++) { s.cbf[k] = p.cbf[k]; s.tskip[k] = p.tskip[k]; s.coef[k] = p.coef[k]; s.coef_start[k] = p.coef_start[k]; }
-    s.bypass = p.bypass; s.ipcm = p.ipcm;
-    s.intra_dir[0] = p.intra_dir[0]; s.intra_dir[1] = p.intra_dir[1];
-    s.slice_idx = p.slice_idx; s.slices = p.slices; s.sl_m = p.sl_m;
-    // the intra modes are the picture's only when EVERY call that covers it came with intra_dir[] (the residual export's rule)
-    bool dir = !pic.calls.empty();
-    for (const SliceCall& sc : pic.calls) dir = dir && sc.dir;
-    s.gate = (dir ? kTransDir : 0) | (pic.flags_staged ? kTransFlags : 0);
-  }
-  for (int k = 0; k < (mono ? 1 : 3); k++) {
-    if (!dst[k]) continue;
-    a.dst[k] = static_cast<uint8_t*>(dst[k]);
-    a.pitch[k] = pitch_bytes[k]; a.bstride[k] = batch_stride_bytes[k];
-    a.scale[k] = d->scale[k];
-  }
-  if (dst_info) {
-    const int I = HMGPU_TRANSFORM_DST_INFO;
-    a.dst[I] = static_cast<uint8_t*>(dst_info);
-    a.pitch[I] = pitch_bytes[I]; a.pstride[I] = plane_stride_bytes[I]; a.bstride[I] = batch_stride_bytes[I];
-  }
-  a.vec = vec;
-  launch_transform(a, d->value == HMGPU_TRANSFORM_COEFFS, elem, c->num_ctus, hs);
-  return export_end(c, n, pics, on_stream, hs);
-}
-
-// ------------------------------------------------------------------------------------------------ picture metrics (k_metrics.hip)
-// hmgpu_metrics_plan_for; the plan's channels / elem_bytes / row_bytes / height describe the reference planes to strided_dst_ok
-static hmgpu_status metrics_plan(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, hmgpu_metrics_plan* out) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  const int fmt = seq->chroma_format, bd[2] = {seq->bit_depth_luma, seq->bit_depth_chroma};
-  if (fmt < 0 || fmt > 3 || bd[0] < 8 || bd[0] > 12 || bd[1] < 8 || bd[1] > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
-  for (int k = 0; k < 7; k++) if (d->reserved[k]) return HMGPU_EINVAL;
-  if (d->reference != HMGPU_METRICS_REF_PICTURES && d->reference != HMGPU_METRICS_REF_PLANES) return HMGPU_EINVAL;
-  if (d->components < 1 || d->components > 7 || (d->ssim != 0 && d->ssim != 1)) return HMGPU_EINVAL;
-  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
-  const int B = d->ref_bytes_per_sample;
-  if (planes ? (B != 1 && B != 2) : B != 0) return HMGPU_EINVAL;
-  const int comps = fmt == 0 ? d->components & 1 : d->components;
-  if (!comps) return HMGPU_EINVAL;                                    // (4:0:0: the chroma bits alone select nothing)
-  int W, H, csx, csy;
-  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
-  chroma_shifts(fmt, &csx, &csy);
-  for (int k = 0; k < 3; k++) {
-    if (!((comps >> k) & 1)) continue;
-    if (B == 1 && bd[k ? 1 : 0] > 8) return HMGPU_EINVAL;
-    const int w = k ? W >> csx : W, h = k ? H >> csy : H;
-    if ((int64_t)w * h >= 0xffffffffll) return HMGPU_EUNSUPPORTED;     // a lane of k_metrics keeps y * w + x in 32 bits, all ones: none
-    out->channels[k] = 1; out->width[k] = w; out->height[k] = h;
-    out->elem_bytes[k] = B; out->row_bytes[k] = w * B;
-    out->ssim_windows[k] = d->ssim && w >= 8 && h >= 8 ? (int64_t)((w >> 2) - 1) * ((h >> 2) - 1) : 0;
-  }
-  out->result_bytes = 3 * (int)sizeof(hmgpu_metrics_result);
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_metrics_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, hmgpu_metrics_plan* out) {
-  const hmgpu_status st = metrics_plan(seq, d, out);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-double hmgpu_metrics_psnr(const hmgpu_metrics_result* r, int32_t bit_depth) {
-  if (!r || bit_depth < 8 || bit_depth > 16) return NAN;
-  if (!r->sse) return 999.99;
-  const int maxval = 255 << (bit_depth - 8);
-  const double ref = (double)maxval * maxval * (double)r->samples;     // (fRefValue of TEncGOP::xCalculateAddPSNR)
-  return 10.0 * std::log10(ref / (double)r->sse);
-}
-
-// what hmgpu_pictures_metrics and hmgpu_pictures_metrics_map check of their pictures and of the reference, behind the description's plan;
-// vec: bit c: the planes of component c take whole loads of 4 elements
-static hmgpu_status metrics_inputs_ok(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
-                                      const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, const hmgpu_metrics_plan* plan,
-                                      int* vec) {
-  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-  *vec = 0;
-  if (d->reference == HMGPU_METRICS_REF_PICTURES) {
-    if (!ref_pics || ref || ref_pitch || ref_bstride) return HMGPU_EINVAL;
-    for (int i = 0; i < n; i++) if (!valid_pic(c, ref_pics[i])) return HMGPU_EINVAL;
-    hipSetDevice(c->device);
-  } else {
-    if (ref_pics || !ref || !ref_pitch || !ref_bstride) return HMGPU_EINVAL;
-    for (int k = 0; k < 3; k++) if (plan->channels[k] && !ref[k]) return HMGPU_EINVAL;   // (one that is not compared: strided_dst_ok refuses it)
-    const hmgpu_status st = strided_dst_ok(c, *plan, 3, n, const_cast<void* const*>(ref), ref_pitch, nullptr, ref_bstride, 0, vec);
-    if (st != HMGPU_OK) return st;
-  }
-  return HMGPU_OK;
-}
-
-// everything hmgpu_pictures_metrics checks
-static hmgpu_status metrics_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_pic* ref_pics,
-                                    const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride, void* results, int64_t rstride,
-                                    hmgpu_metrics_plan* plan, int* vec) {
-  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  { const hmgpu_status st = metrics_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = metrics_inputs_ok(c, n, pics, d, ref_pics, ref, ref_pitch, ref_bstride, plan, vec); if (st != HMGPU_OK) return st; }
-  const int64_t rec = plan->result_bytes;
-  if (!results || (uintptr_t)results % 8 || rstride < rec || rstride % 8 || rstride > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-  if (!device_span_ok(results, (size_t)((n - 1) * rstride + rec), c->device)) return HMGPU_EINVAL;
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_metrics_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_pic ref_pics[],
-                                 const void* const ref[3], const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3],
-                                 void* results, int64_t results_batch_stride_bytes) {
-  hmgpu_metrics_plan plan;
-  int vec = 0;
-  return metrics_resolve(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes, &plan, &vec);
-}
-
-hmgpu_status hmgpu_pictures_metrics(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_pic ref_pics[],
-                                    const void* const ref[3], const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3],
-                                    void* results, int64_t results_batch_stride_bytes, int32_t on_stream, void* stream) {
-  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
-  hmgpu_metrics_plan plan;
-  int vec = 0;
-  { const hmgpu_status st = metrics_resolve(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, results, results_batch_stride_bytes, &plan, &vec);
-    if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
-  MetricsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.results = static_cast<uint8_t*>(results); a.rstride = results_batch_stride_bytes;
-  metrics_sources(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, plan, vec, &a);
-  for (int k = 0; k < 2; k++) {
-    if (!a.w[k]) continue;
-    const int tw = d->ssim ? kMetricsTileW : kMetricsRowTileW, th = d->ssim ? kMetricsTileH : kMetricsRowTileH;
-    a.tiles_x[k] = (a.w[k] + tw - 1) / tw;
-    a.tiles[k] = a.tiles_x[k] * ((a.h[k] + th - 1) / th);
-  }
-  a.total = n * (a.tiles[0] + a.tiles[1]);
-  const int grid = d->ssim ? kMetricsGridSsim : kMetricsGrid;
-  a.per = (a.total + grid - 1) / grid;
-  const int64_t rec = plan.result_bytes;
-  if (n == 1 || a.rstride == rec) HIP_TRY(c, hipMemsetAsync(results, 0, (size_t)(n * rec), hs));
-  else HIP_TRY(c, hipMemset2DAsync(results, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
-  launch_metrics(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
-  if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
-  return export_end(c, n, pics, on_stream, hs);
-}
-
-// ------------------------------------------------------------------------------------------------ picture metric maps (k_metrics_map.hip)
-// what strided_dst_ok needs to know of the maps: per component `fields` planes of blocks_y rows of blocks_x int64 elements
-struct MapDstPlan { int32_t channels[3], height[3], elem_bytes[3], row_bytes[3]; };
-
-// hmgpu_metrics_map_plan_for: the refusals of the metrics description first (mp: its plan), then those of the map's own
-static hmgpu_status metrics_map_plan(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
-                                     hmgpu_metrics_plan* mp, hmgpu_metrics_map_plan* out) {
-  if (!out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  { const hmgpu_status st = metrics_plan(seq, d, mp); if (st != HMGPU_OK) return st; }
-  if (!md || md->log2_block < 3 || md->log2_block > 6) return HMGPU_EINVAL;
-  for (int k = 0; k < 7; k++) if (md->reserved[k]) return HMGPU_EINVAL;
-  int W, H, csx, csy;
-  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
-  chroma_shifts(seq->chroma_format, &csx, &csy);
-  const int B = 1 << md->log2_block;
-  out->blocks_x = (W + B - 1) / B; out->blocks_y = (H + B - 1) / B;
-  for (int k = 0; k < 3; k++) {
-    if (!mp->channels[k]) continue;
-    out->channels[k] = 1; out->width[k] = mp->width[k]; out->height[k] = mp->height[k];
-    out->block_w[k] = k ? B >> csx : B; out->block_h[k] = k ? B >> csy : B;
-  }
-  out->fields = d->ssim ? HMGPU_METRICS_MAP_FIELDS : 4;
-  out->row_bytes = out->blocks_x * 8;
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_metrics_map_plan_for(const hmgpu_seq_params* seq, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
-                                        hmgpu_metrics_map_plan* out) {
-  hmgpu_metrics_plan mp;
-  const hmgpu_status st = metrics_map_plan(seq, d, md, &mp, out);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-// everything hmgpu_pictures_metrics_map checks
-static hmgpu_status metrics_map_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
-                                        const hmgpu_pic* ref_pics, const void* const* ref, const int64_t* ref_pitch, const int64_t* ref_bstride,
-                                        void* const* maps, const int64_t* pitch, const int64_t* fstride, const int64_t* bstride,
-                                        hmgpu_metrics_plan* mp, hmgpu_metrics_map_plan* plan, int* vec) {
-  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  { const hmgpu_status st = metrics_map_plan(&c->seq, d, md, mp, plan); if (st != HMGPU_OK) return st; }
-  { const hmgpu_status st = metrics_inputs_ok(c, n, pics, d, ref_pics, ref, ref_pitch, ref_bstride, mp, vec); if (st != HMGPU_OK) return st; }
-  if (!maps || !pitch || !fstride || !bstride) return HMGPU_EINVAL;
-  MapDstPlan dp;
-  memset(&dp, 0, sizeof(dp));
-  for (int k = 0; k < 3; k++) {
-    if (!plan->channels[k]) continue;                                  // (a map of a component that is not compared: strided_dst_ok refuses it)
-    if (!maps[k]) return HMGPU_EINVAL;
-    dp.channels[k] = plan->fields; dp.height[k] = plan->blocks_y; dp.elem_bytes[k] = 8; dp.row_bytes[k] = plan->row_bytes;
-  }
-  int mvec = 0;
-  return strided_dst_ok(c, dp, 3, n, maps, pitch, fstride, bstride, 8, &mvec);
-}
-
-hmgpu_status hmgpu_metrics_map_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
-                                     const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
-                                     const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
-                                     const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3]) {
-  hmgpu_metrics_plan mp;
-  hmgpu_metrics_map_plan plan;
-  int vec = 0;
-  return metrics_map_resolve(c, n, pics, d, md, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes, map_field_stride_bytes,
-                             map_batch_stride_bytes, &mp, &plan, &vec);
-}
-
-hmgpu_status hmgpu_pictures_metrics_map(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_metrics_desc* d, const hmgpu_metrics_map_desc* md,
-                                        const hmgpu_pic ref_pics[], const void* const ref[3], const int64_t ref_pitch_bytes[3],
-                                        const int64_t ref_batch_stride_bytes[3], void* const maps[3], const int64_t map_pitch_bytes[3],
-                                        const int64_t map_field_stride_bytes[3], const int64_t map_batch_stride_bytes[3], int32_t on_stream,
-                                        void* stream) {
-  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
-  hmgpu_metrics_plan mp;
-  hmgpu_metrics_map_plan plan;
-  int vec = 0;
-  { const hmgpu_status st = metrics_map_resolve(c, n, pics, d, md, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, maps, map_pitch_bytes,
-                                                map_field_stride_bytes, map_batch_stride_bytes, &mp, &plan, &vec);
-    if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  MetricsMapArgs a;
-  memset(&a, 0, sizeof(a));
-  metrics_sources(c, n, pics, d, ref_pics, ref, ref_pitch_bytes, ref_batch_stride_bytes, mp, vec, &a);
-  for (int k = 0; k < 3; k++) {
-    if (!plan.channels[k]) continue;
-    a.maps[k] = static_cast<uint8_t*>(maps[k]);
-    a.mpitch[k] = map_pitch_bytes[k]; a.mfstride[k] = map_field_stride_bytes[k]; a.mbstride[k] = map_batch_stride_bytes[k];
-  }
-  for (int k = 0; k < 2; k++) {
-    a.log2_rw[k] = 6 - (k ? c->csx : 0); a.log2_rh[k] = 6 - (k ? c->csy : 0);
-    a.log2_bw[k] = md->log2_block - (k ? c->csx : 0); a.log2_bh[k] = md->log2_block - (k ? c->csy : 0);
-    if (!a.w[k]) continue;
-    const int rw = 1 << a.log2_rw[k], rh = 1 << a.log2_rh[k];
-    a.regions_x[k] = (a.w[k] + rw - 1) / rw;
-    a.regions[k] = a.regions_x[k] * ((a.h[k] + rh - 1) / rh);
-  }
-  a.log2_nb = 6 - md->log2_block;
-  a.blocks_x = plan.blocks_x; a.blocks_y = plan.blocks_y;
-  const bool planes = d->reference == HMGPU_METRICS_REF_PLANES;
-  launch_metrics_map(a, planes ? d->ref_bytes_per_sample : 0, d->ssim != 0, hs);
-  if (!planes) for (int i = 0; i < n; i++) touch(c, ref_pics[i]);      // (the reference pictures are read too)
-  return export_end(c, n, pics, on_stream, hs);
-}
-
-// ------------------------------------------------------------------------------------------------ picture histograms (k_histogram.hip)
-static hmgpu_status histogram_plan(const hmgpu_seq_params* seq, const hmgpu_histogram_desc* d, hmgpu_histogram_plan* out) {
-  if (!seq || !d || !out) return HMGPU_EINVAL;
-  memset(out, 0, sizeof(*out));
-  const int fmt = seq->chroma_format, bd[2] = {seq->bit_depth_luma, seq->bit_depth_chroma};
-  if (fmt < 0 || fmt > 3 || bd[0] < 8 || bd[0] > 12 || bd[1] < 8 || bd[1] > 12 || seq->width <= 0 || seq->height <= 0) return HMGPU_EINVAL;
-  for (int k = 0; k < 6; k++) if (d->reserved[k]) return HMGPU_EINVAL;
-  if (d->channels < 1 || d->channels > 15 || (d->histogram != 0 && d->histogram != 1)) return HMGPU_EINVAL;
-  if (d->log2_bins != 0 && (d->log2_bins < 4 || d->log2_bins > 12)) return HMGPU_EINVAL;
-  const int chans = fmt == 0 ? d->channels & 9 : d->channels;
-  if (!chans) return HMGPU_EINVAL;                                    // (4:0:0: the chroma bits alone select nothing)
-  int W, H, csx, csy;
-  { const hmgpu_status st = crop_ok(seq, d->crop, nullptr, &W, &H); if (st != HMGPU_OK) return st; }
-  if ((int64_t)W * H >= ((int64_t)1 << 31)) return HMGPU_EUNSUPPORTED;  // every count, and an int32 view of it, stays below 2^31
-  chroma_shifts(fmt, &csx, &csy);
-  int depth[4] = {bd[0], bd[1], bd[1], bd[0]};
-  if (chans & 8) {
-    if (d->rgb_bit_depth) {
-      if (d->rgb_bit_depth < 8) return HMGPU_EINVAL;
-      if (d->rgb_bit_depth > 12) return HMGPU_EUNSUPPORTED;            // the bins of a channel fit the LDS up to 2^12
-      depth[3] = d->rgb_bit_depth;
-    }
-    // the RGB export whose samples these are: its rules for matrix and full_range, and its constants
-    hmgpu_export_desc e;
-    memset(&e, 0, sizeof(e));
-    e.layout = HMGPU_EXPORT_RGB; e.bit_depth[0] = depth[3]; e.bytes_per_sample = 2;
-    memcpy(e.crop, d->crop, sizeof(e.crop));
-    e.matrix = d->matrix; e.full_range = d->full_range;
-    hmgpu_export_plan ep;
-    const hmgpu_status st = hmgpu_export_plan_for(seq, &e, &ep);
-    if (st != HMGPU_OK) return st;
-    memcpy(out->coef, ep.coef, sizeof(out->coef));
-  }
-  for (int k = 0; k < 4; k++) {
-    if (!((chans >> k) & 1)) continue;
-    const bool chroma = k == 1 || k == 2;
-    out->channels[k] = 1;
-    out->width[k] = chroma ? W >> csx : W; out->height[k] = chroma ? H >> csy : H;
-    out->depth[k] = depth[k];
-    out->log2_bins[k] = d->log2_bins ? std::min(d->log2_bins, depth[k]) : depth[k];
-    out->hist_bytes[k] = d->histogram ? 4 << out->log2_bins[k] : 0;
-  }
-  out->record_bytes = 4 * (int)sizeof(hmgpu_histogram_result);
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_histogram_plan_for(const hmgpu_seq_params* seq, const hmgpu_histogram_desc* d, hmgpu_histogram_plan* out) {
-  const hmgpu_status st = histogram_plan(seq, d, out);
-  if (st != HMGPU_OK && out) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-// everything hmgpu_pictures_histogram checks
-static hmgpu_status histogram_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_histogram_desc* d, void* const* hist,
-                                      const int64_t* hstride, void* records, int64_t rstride, hmgpu_histogram_plan* plan) {
-  if (!c || !pics || !d || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
-  { const hmgpu_status st = histogram_plan(&c->seq, d, plan); if (st != HMGPU_OK) return st; }
-  for (int i = 0; i < n; i++) if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
-  hipSetDevice(c->device);
-  if (d->histogram && (!hist || !hstride)) return HMGPU_EINVAL;
-  for (int k = 0; k < 4; k++) {
-    void* const p = hist ? hist[k] : nullptr;
-    if (!d->histogram || !plan->channels[k]) {
-      if (p) return HMGPU_EINVAL;                                      // a histogram this call does not compute
-      continue;
-    }
-    const int64_t bytes = plan->hist_bytes[k], s = hstride[k];
-    if (!p || (uintptr_t)p % 4 || s < bytes || s % 4 || s > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-    if (!device_span_ok(p, (size_t)((n - 1) * s + bytes), c->device)) return HMGPU_EINVAL;
-  }
-  const int64_t rec = plan->record_bytes;
-  if (!records || (uintptr_t)records % 8 || rstride < rec || rstride % 8 || rstride > ((int64_t)1 << 40)) return HMGPU_EINVAL;
-  if (!device_span_ok(records, (size_t)((n - 1) * rstride + rec), c->device)) return HMGPU_EINVAL;
-  return HMGPU_OK;
-}
-
-hmgpu_status hmgpu_histogram_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* d, void* const hist[4],
-                                   const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes) {
-  hmgpu_histogram_plan plan;
-  return histogram_resolve(c, n, pics, d, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes, &plan);
-}
-
-hmgpu_status hmgpu_pictures_histogram(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_histogram_desc* d, void* const hist[4],
-                                      const int64_t hist_batch_stride_bytes[4], void* records, int64_t records_batch_stride_bytes,
-                                      int32_t on_stream, void* stream) {
-  if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
-  hmgpu_histogram_plan plan;
-  { const hmgpu_status st = histogram_resolve(c, n, pics, d, hist, hist_batch_stride_bytes, records, records_batch_stride_bytes, &plan);
-    if (st != HMGPU_OK) return st; }
-  hipStream_t hs = c->stream;
-  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
-  HistogramArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n = n; a.do_hist = d->histogram;
-  a.records = static_cast<uint8_t*>(records); a.rstride = records_batch_stride_bytes;
-  for (int k = 0; k < 4; k++) {
-    if (!plan.channels[k]) continue;
-    a.chans |= 1 << k;
-    a.shift[k] = plan.depth[k] - plan.log2_bins[k]; a.log2_bins[k] = plan.log2_bins[k];
-    if (d->histogram) { a.hist[k] = static_cast<uint8_t*>(hist[k]); a.hstride[k] = hist_batch_stride_bytes[k]; }
-  }
-  for (int k = 0; k < 2; k++) {
-    const int ch = k ? (plan.channels[1] ? 1 : 2) : (plan.channels[0] ? 0 : 3);   // a channel of the class that is computed, if any
-    a.pitch[k] = c->pitch[k];
-    if (!plan.channels[ch]) continue;
-    a.w[k] = plan.width[ch]; a.h[k] = plan.height[ch];
-    a.tiles_x[k] = (a.w[k] + kHistTileW - 1) / kHistTileW;
-    a.tiles[k] = a.tiles_x[k] * ((a.h[k] + kHistTileH - 1) / kHistTileH);
-  }
-  a.csx = c->csx; a.csy = c->csy; a.mono = c->seq.chroma_format == 0;
-  memcpy(a.coef, plan.coef, sizeof(a.coef));
-  for (int k = 0; k < 2; k++) {                                        // maxRGB: the depth rule of the export's identity, both types at D_3
-    a.sh[k] = plan.depth[3] - (k ? c->seq.bit_depth_chroma : c->seq.bit_depth_luma);
-    a.maxv[k] = (1 << plan.depth[3]) - 1;
-  }
-  const int x0 = d->crop[0], y0 = d->crop[2];
-  const size_t rg = c->csx ? 8 : 16;                                   // the chroma of 4 luma samples: 2 pairs or 4
-  for (int i = 0; i < n; i++) {
-    const Picture& p = c->pics[pics[i]];
-    int16_t* const* src = p.sao_applied ? p.dev.sao : p.dev.rec;
-    a.y[i] = src[0] + (ptrdiff_t)y0 * c->pitch[0] + x0;
-    a.c[i] = a.mono ? nullptr : src[1] + (ptrdiff_t)(y0 >> c->csy) * c->pitch[1] + kCStep * (x0 >> c->csx);
-    if ((uintptr_t)a.y[i] % 8 == 0 && ((size_t)c->pitch[0] * 2) % 8 == 0) a.yvec |= 1u << i;
-    if (a.mono) continue;
-    if ((uintptr_t)a.c[i] % 16 == 0 && ((size_t)c->pitch[1] * 2) % 16 == 0) a.cvec |= 1u << i;
-    if ((uintptr_t)a.c[i] % rg == 0 && ((size_t)c->pitch[1] * 2) % rg == 0) a.rvec |= 1u << i;
-  }
-  a.total = n * (a.tiles[0] + a.tiles[1]);
-  a.per = (a.total + kHistGrid - 1) / kHistGrid;
-  const int64_t rec = plan.record_bytes;
-  if (n == 1 || a.rstride == rec) HIP_TRY(c, hipMemsetAsync(records, 0, (size_t)(n * rec), hs));
-  else HIP_TRY(c, hipMemset2DAsync(records, (size_t)a.rstride, 0, (size_t)rec, (size_t)n, hs));
-  for (int k = 0; k < 4; k++) {
-    if (!a.hist[k]) continue;
-    const int64_t bytes = plan.hist_bytes[k];
-    if (n == 1 || a.hstride[k] == bytes) HIP_TRY(c, hipMemsetAsync(a.hist[k], 0, (size_t)(n * bytes), hs));
-    else HIP_TRY(c, hipMemset2DAsync(a.hist[k], (size_t)a.hstride[k], 0, (size_t)bytes, (size_t)n, hs));
-  }
-  launch_histogram(a, hs);
-  return export_end(c, n, pics, on_stream, hs);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// hmgpu_host.h -- what the units of the host runtime (hmgpu_api.hip, hmgpu_input.hip, hmgpu_output.hip, hmgpu_export.hip) share: the
-// context and its pictures, the small tools every unit uses, and the helpers that more than one unit calls.  Internal: not installed,
-// not included by any kernel file.
+// hmgpu_host.h -- what the units of the host runtime (hmgpu_api.hip, hmgpu_input.hip, hmgpu_output.hip, hmgpu_export.hip,
+// hmgpu_side.hip, hmgpu_analysis.hip) share: the context and its pictures, the small tools every unit uses, and the helpers that
+// more than one unit calls.  Internal: not installed, not included by any kernel file.
 #pragma once
 #include "hmgpu_dev.h"
 
@@ -252,5 +252,44 @@ hmgpu_status run_recon(hmgpu_ctx* c, const Batch& b, bool any_intra, bool any_wp
 hmgpu_status run_filter(hmgpu_ctx* c, const Batch& b, int stages, bool* fused);   // *fused: the fused kernel ran and wrote the margins
 hmgpu_status stage_sao(hmgpu_ctx* c, Picture& p, const hmgpu_pic_params* pp, const hmgpu_sao_param* sao,
                        const std::vector<uint16_t>& slice_idx, const std::vector<uint16_t>& tile_idx);
+
+// validation rules and the stream bracket of the exports (hmgpu_export.hip), shared with hmgpu_side.hip and hmgpu_analysis.hip
+void chroma_shifts(int fmt, int* csx, int* csy);
+hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc);
+hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], const hmgpu_export_scale* sc, int* w, int* h);
+hmgpu_status window_ok(const hmgpu_seq_params* seq, const hmgpu_export_window& win, const hmgpu_export_scale* sc, int* w, int* h);
+bool device_span_ok(const void* p, size_t bytes, int device);
+hmgpu_status export_open(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs);
+hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs);
+
+// the destinations of a side-information export, `slots` of them, a null one not written: element alignment, strides against the extents
+// they step over (pstride null: one plane per slot), and the whole span of n pictures inside one allocation of the context's device,
+// which it makes the current one.
+// vec: bit k set when slot k may take stores of `granule` bytes (0: four elements)
+template <class Plan>
+hmgpu_status strided_dst_ok(const hmgpu_ctx* c, const Plan& plan, int slots, int n, void* const* dst, const int64_t* pitch,
+                            const int64_t* pstride, const int64_t* bstride, int granule, int* vec) {
+  hipSetDevice(c->device);
+  bool any = false;
+  *vec = 0;
+  for (int k = 0; k < slots; k++) {
+    if (!dst[k]) continue;
+    if (!plan.channels[k]) return HMGPU_EINVAL;                       // a slot this call does not have
+    any = true;
+    const int64_t es = plan.elem_bytes[k], g = granule ? granule : 4 * es;
+    if (pitch[k] < plan.row_bytes[k] || pitch[k] > ((int64_t)1 << 40)) return HMGPU_EINVAL;
+    const int64_t plane = pitch[k] * (plan.height[k] - 1) + plan.row_bytes[k];
+    int64_t pic = plane;
+    if (pstride) {
+      if (pstride[k] < plane || pstride[k] > ((int64_t)1 << 48) || pstride[k] % es) return HMGPU_EINVAL;
+      pic = pstride[k] * (plan.channels[k] - 1) + plane;
+    }
+    if (bstride[k] < pic || bstride[k] > ((int64_t)1 << 56)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % es || pitch[k] % es || bstride[k] % es) return HMGPU_EINVAL;
+    if (!device_span_ok(dst[k], (size_t)((n - 1) * bstride[k] + pic), c->device)) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[k] % g == 0 && pitch[k] % g == 0 && bstride[k] % g == 0 && (!pstride || pstride[k] % g == 0)) *vec |= 1 << k;
+  }
+  return any ? HMGPU_OK : HMGPU_EINVAL;
+}
 
 }  // namespace hmgpu_host

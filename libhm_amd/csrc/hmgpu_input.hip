@@ -352,7 +352,6 @@ hmgpu_status hmgpu_pack_levels(const hmgpu_seq_params* seq, const hmgpu_ctu_meta
       if (cx + 4 * x4 >= seq->width || cy + 4 * y4 >= seq->height || m->part_size[idx] == HMGPU_SIZE_NONE) continue;
       const int tr = m->tr_idx[idx], log2tu = log2ctu - m->depth[idx] - tr;
       if (log2tu > 5) continue;
-      const unsigned chain = (1u << (tr + 1)) - 1;
       auto emit = [&](int comp, size_t src_off, uint32_t n) {
         memcpy(out_level[comp] + pos[comp], dense->level[comp] + src_off, n * sizeof(int16_t));
         pos[comp] += n;
@@ -361,13 +360,13 @@ hmgpu_status hmgpu_pack_levels(const hmgpu_seq_params* seq, const hmgpu_ctu_meta
       if (log2tu > 2) {
         const int tu_parts = 1 << (log2tu - 2);
         if ((x4 & (tu_parts - 1)) || (y4 & (tu_parts - 1))) continue;
-        if ((m->cbf[0][idx] & chain) == chain) emit(0, base_l + 16 * (size_t)z0, 1u << (2 * log2tu));
-        if ((m->cbf[1][idx] & chain) == chain) emit(1, base_c + 4 * (size_t)z0, 1u << (2 * log2tu - 2));
-        if ((m->cbf[2][idx] & chain) == chain) emit(2, base_c + 4 * (size_t)z0, 1u << (2 * log2tu - 2));
+        if (cbf_coded(m->cbf[0][idx], tr)) emit(0, base_l + 16 * (size_t)z0, 1u << (2 * log2tu));
+        if (cbf_coded(m->cbf[1][idx], tr)) emit(1, base_c + 4 * (size_t)z0, 1u << (2 * log2tu - 2));
+        if (cbf_coded(m->cbf[2][idx], tr)) emit(2, base_c + 4 * (size_t)z0, 1u << (2 * log2tu - 2));
       } else {
-        for (int j = 0; j < 4; j++) if ((m->cbf[0][idx + j] & chain) == chain) emit(0, base_l + 16 * (size_t)(z0 + j), 16);
-        if ((m->cbf[1][idx] & chain) == chain) emit(1, base_c + 4 * (size_t)z0, 16);
-        if ((m->cbf[2][idx] & chain) == chain) emit(2, base_c + 4 * (size_t)z0, 16);
+        for (int j = 0; j < 4; j++) if (cbf_coded(m->cbf[0][idx + j], tr)) emit(0, base_l + 16 * (size_t)(z0 + j), 16);
+        if (cbf_coded(m->cbf[1][idx], tr)) emit(1, base_c + 4 * (size_t)z0, 16);
+        if (cbf_coded(m->cbf[2][idx], tr)) emit(2, base_c + 4 * (size_t)z0, 16);
       }
     }
   }

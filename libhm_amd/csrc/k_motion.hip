@@ -22,9 +22,6 @@ struct MotionRec {
   int32_t info[4];          // mode, log2 CU size, part_size, QP
 };
 
-// the low four bits of v on the even bit positions (HM's z-scan: column bits even, row bits odd)
-__device__ inline int spread4(int v) { v = (v | (v << 2)) & 0x33; v = (v | (v << 1)) & 0x55; return v; }
-
 template <int N> __device__ inline uint32_t ld_bytes(const void* p) {
   if constexpr (N == 1) return ldg(static_cast<const uint8_t*>(p));
   else return ldg(static_cast<const uint16_t*>(p));                       // (z is even: 2-byte aligned)
@@ -101,12 +98,10 @@ __global__ void __launch_bounds__(256) k_motion_blocks(const MotionArgs a) {
   if (by >= a.y4 + a.h4 || bx0 >= a.x4 + a.w4) return;
   const MotionSrc& s = a.src[pic];
   const bool want_motion = a.dst[0] || a.dst[2], want_block = a.dst[3] != nullptr;
-  const int sh = a.log2ctu - 2, m = (1 << sh) - 1;
-  const int ctu = (by >> sh) * a.ctus_w + (bx0 >> sh);                            // (a CTU is at least four blocks wide: one CTU per lane)
-  const int z0 = spread4(bx0 & m) | (spread4(by & m) << 1);
+  const Part p = part_of(bx0, by, a.log2ctu, a.ctus_w);                            // (a CTU is at least four blocks wide: one CTU per lane)
   MotionRec r[4];
-  load_recs<2>(s, a, ctu, z0, want_motion, want_block, r);
-  load_recs<2>(s, a, ctu, z0 + 4, want_motion, want_block, r + 2);
+  load_recs<2>(s, a, p.ctu, p.z, want_motion, want_block, r);
+  load_recs<2>(s, a, p.ctu, p.z + 4, want_motion, want_block, r + 2);
   // the lane's columns of the cropped grid: c0 .. c0 + 3, those inside [0, w4) are written (d may point in front of the row: masked)
   const int row = by - a.y4, c0 = bx0 - a.x4;
   uint32_t mask = 0;
@@ -163,9 +158,7 @@ __global__ void __launch_bounds__(256) k_motion_dense(const MotionArgs a) {
   const bool flip = (a.flip >> pic) & 1;
   const bool want_motion = a.dst[0] || a.dst[1] || a.dst[2], want_block = a.dst[3] != nullptr;
   const int sh = a.log2ctu - 2, m = (1 << sh) - 1;
-  // nearest-exact in integers: min(floor((2 o + 1) * in / (2 * out)), in - 1); (2 o + 1) * in < 2^32 for o < 16384 and in < 2^17
-  const int sy = min((int)(((2u * oy + 1u) * (uint32_t)w.h) / (2u * (uint32_t)a.H)), w.h - 1);
-  const int by = (w.top + sy) >> 2;
+  const int by = (w.top + nearest_src(oy, w.h, a.H)) >> 2;
   const int n = min(8, a.W - c0);
   int32_t dx[2][8], dy[2][8], poc[2][8], info[4][8];
   MotionRec r = {};
@@ -174,10 +167,9 @@ __global__ void __launch_bounds__(256) k_motion_dense(const MotionArgs a) {
   for (int j = 0; j < 8; j++) {
     const int ox = flip ? a.W - 1 - (c0 + j) : c0 + j;                             // the mirror acts on the output: column c shows sample W - 1 - c
     if (j < n) {
-      const int sx = min((int)(((2u * ox + 1u) * (uint32_t)w.w) / (2u * (uint32_t)a.W)), w.w - 1);
-      const int bx = (w.left + sx) >> 2;
+      const int bx = (w.left + nearest_src(ox, w.w, a.W)) >> 2;
       if (bx != last) {
-        const int ctu = (by >> sh) * a.ctus_w + (bx >> sh);
+        const int ctu = (by >> sh) * a.ctus_w + (bx >> sh);                        // (part_of written out: sh and m stay outside the unrolled loop)
         load_recs<1>(s, a, ctu, spread4(bx & m) | (spread4(by & m) << 1), want_motion, want_block, &r);
         last = bx;
       }

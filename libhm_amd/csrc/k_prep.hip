@@ -414,8 +414,8 @@ __global__ void __launch_bounds__(256) k_prep(const PicDev* __restrict__ pics, B
     }
     // ---- which transform units originate in this 8x8 area.  The TUs of intra CUs are listed too (not those of PCM CUs): their residual
     // does not depend on the neighbours, k_itx computes it ahead of k_intra, which walks the TUs in dependency order and only adds it.
-    // cbf bit d of a partition = cbf of its ancestor TU node at transform depth d (TComDataCU.h:310); HM descends only
-    // while every node on the way has its bit set (TComTrQuant.cpp:1558-1564)
+    // Which of them are coded: the cbf chain of cbf_coded (hmgpu_dev.h), kept written out here with one `chain` per section, hoisted out
+    // of the branches.
     if (q.valid && q.log2tu <= 5 && (!q.intra || (P.has_intra_dir && !(pcm4 & 0xff)))) {
       const uint32_t chain = (1u << (q.tr + 1)) - 1;
       if (q.log2tu > 2) {

@@ -19,15 +19,12 @@ namespace hmgpu {
 
 namespace {
 
-__device__ inline int spread4(int v) { v = (v | (v << 2)) & 0x33; v = (v | (v << 1)) & 0x55; return v; }
-
 // is the transform block over partition i coded?  ps / pm / dp / tr / cbf / pcm: the partition's bytes
 __device__ inline bool coded(int log2ctu, int gate, int ps, int pm, int dp, int tr, int cbf, int pcm) {
   const int log2tu = log2ctu - dp - tr;
   const bool intra = pm == HMGPU_MODE_INTRA;
   const bool listed = ps != HMGPU_SIZE_NONE && log2tu >= 2 && log2tu <= 5 && (!intra || ((gate & kResidIntra) && !pcm));
-  const int chain = (1 << ((tr & 7) + 1)) - 1;
-  return listed && (cbf & chain) == chain;
+  return listed && cbf_coded(cbf, tr & 7);
 }
 
 // the row slot of component `comp` that holds component sample (8 * sx8 .. 8 * sx8 + 7, y), with the halves no coded block covers zeroed.
@@ -39,8 +36,8 @@ __device__ inline u32x4 load_slot(const ResidSrc& s, const ResidArgs& a, int com
   const u32x4 v = ldg4(tiles + ((size_t)((y >> 3) * rtw + sx8) * 8 + resid_slot(y)) * 8);
   // the two 4x4 blocks of the slot: luma blocks (2 sx8, y >> 2), (2 sx8 + 1, y >> 2); chroma: the 8x8 luma areas at (4 sx8, (y >> 2) * 2), (4 sx8 + 2, ..)
   const int bx = comp ? 4 * sx8 : 2 * sx8, by = comp ? (y >> 2) * 2 : y >> 2, dz = comp ? 4 : 1;
-  const int sh = a.log2ctu - 2, m = (1 << sh) - 1;
-  const size_t p = (size_t)((by >> sh) * a.ctus_w + (bx >> sh)) * a.parts + (spread4(bx & m) | (spread4(by & m) << 1));
+  const Part pt = part_of(bx, by, a.log2ctu, a.ctus_w);
+  const size_t p = (size_t)pt.ctu * a.parts + pt.z;
   int ps[2], pm[2], dp[2], tr[2], cb[2], pc[2] = {0, 0};
 #pragma unroll
   for (int i = 0; i < 2; i++) {
@@ -106,16 +103,15 @@ __global__ void __launch_bounds__(256) k_residual_dense(const ResidArgs a) {
   const int oy = blockIdx.y * 8 + (threadIdx.x >> 5);
   if (c0 >= a.W || oy >= a.H) return;
   const ResidSrc& s = a.src[pic];
-  const ResidWin w = a.win[pic];
+  const SideWin w = a.win[pic];
   const bool flip = (a.flip >> pic) & 1;
-  // nearest-exact in integers: min(floor((2 o + 1) * in / (2 * out)), in - 1); (2 o + 1) * in < 2^32 for o < 16384 and in < 2^17
-  const int sy = w.top + min((int)(((2u * oy + 1u) * (uint32_t)w.h) / (2u * (uint32_t)a.H)), w.h - 1);
+  const int sy = w.top + nearest_src(oy, w.h, a.H);
   const int n = min(8, a.W - c0);
   int sx[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int ox = flip ? a.W - 1 - (c0 + j) : c0 + j;                         // the mirror acts on the source index: stores ascend
-    sx[j] = w.left + min((int)(((2u * max(ox, 0) + 1u) * (uint32_t)w.w) / (2u * (uint32_t)a.W)), w.w - 1);
+    sx[j] = w.left + nearest_src(max(ox, 0), w.w, a.W);
   }
 #pragma unroll
   for (int comp = 0; comp < 3; comp++) {

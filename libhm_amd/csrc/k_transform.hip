@@ -7,7 +7,7 @@
 // Nothing here reads PicDev::tu[]: those lists belong to the last k_prep call, hold neither PCM CUs nor intra CUs without modes, and a
 // picture built slice by slice keeps only its last call's.  Codedness comes from the arrays alone -- a dense level array holds stale
 // values outside the current picture's coded blocks -- by the rule of hmgpu_pack_levels (hmgpu_input.hip), whose set the compact
-// offsets have to reproduce exactly.
+// offsets have to reproduce exactly: both test the cbf chain through cbf_coded (hmgpu_dev.h).
 //
 // One 256-lane workgroup per CTU and component class (grid y: 0 luma and the info grid, 1 Cb + Cr), grid z the picture.
 //   phase 1  lane z = partition z.  Its bytes go to LDS so that every lane can read the flags at the FIRST partition of the block that
@@ -27,8 +27,6 @@
 namespace hmgpu {
 
 namespace {
-
-__device__ inline int spread4(int v) { v = (v | (v << 2)) & 0x33; v = (v | (v << 1)) & 0x55; return v; }
 
 // the block of component c that covers partition z of a unit of 2^log2tu luma samples: zo its first partition, zf the partition its
 // own flags are stored at (4:2:2: the lower square's are half the block on), log2n its size
@@ -102,7 +100,6 @@ __global__ void __launch_bounds__(256) k_transform(const TransformArgs a) {
   const int log2tu = decoded ? log2ctu - dp - (tr & 7) : 6;
   const bool sized = decoded && log2tu >= 2 && log2tu <= 5;
   const bool intra = pm == HMGPU_MODE_INTRA;
-  const uint32_t chain = (1u << ((tr & 7) + 1)) - 1u;
   uint32_t coded_mask = 0, ts_mask = 0;
   uint32_t cnt[2] = {0, 0};
   Cover cv[2] = {{0, 0, 2, 0}, {0, 0, 2, 0}};
@@ -111,7 +108,7 @@ __global__ void __launch_bounds__(256) k_transform(const TransformArgs a) {
     if (c && a.mono) break;
     const Cover v = cover(c, z, clip3(2, 6, log2tu), a.fmt);
     const uint32_t fo = s_flag[v.zo], ff = s_flag[v.zf];
-    bool coded = sized && (((fo >> (8 * c)) & 0xffu) & chain) == chain;
+    bool coded = sized && cbf_coded((fo >> (8 * c)) & 0xffu, tr & 7);
     if (c && a.fmt == 2) coded = coded && ((ff >> (8 * c + (tr & 7) + 1)) & 1u);
     if (decoded) ts_mask |= ((ff >> (24 + c)) & 1u) << c;
     const int k = c - c_lo;

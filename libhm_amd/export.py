@@ -96,6 +96,15 @@ def sample_type(dtype):
         raise ValueError("dtype %r: None (unsigned integers), torch.float16, torch.bfloat16 or torch.float32" % (dtype,))
 
 
+def side_dtype(code, dtype):
+    """the torch element type of a side-information export whose description says abi.SAMPLE_* `code`: int16 for the integer type, else
+    `dtype` itself -- a torch float dtype, or its abi.SAMPLE_* code"""
+    import torch
+    if code == abi.SAMPLE_UINT:
+        return torch.int16
+    return {abi.SAMPLE_F16: torch.float16, abi.SAMPLE_BF16: torch.bfloat16, abi.SAMPLE_F32: torch.float32}[dtype] if isinstance(dtype, int) else dtype
+
+
 def make_tensor(dtype, depths, mean=None, std=None, scale=None, bias=None):
     """the abi.ExportTensor of a float dtype (None for dtype None): `affine` of the planes' depths, or an explicit scale / bias"""
     if dtype is None:

@@ -70,9 +70,7 @@ def export_residual(call, seq, device, n, form="planes", components=(0, 1, 2), s
     desc, sc, win = describe(seq, n, form, components, size, windows, flip, dtype, scale, crop)
     plan = plan_for(seq, desc, sc, win, n)
     planes = desc.form == abi.RESIDUAL_PLANES
-    elem = torch.int16 if desc.sample_type == abi.SAMPLE_UINT else dtype
-    if isinstance(elem, int):
-        elem = {abi.SAMPLE_F16: torch.float16, abi.SAMPLE_BF16: torch.bfloat16, abi.SAMPLE_F32: torch.float32}[elem]
+    elem = export.side_dtype(desc.sample_type, dtype)
     names = {k: NAMES[k] for k in range(3) if plan.channels[k]} if planes else {0: "residual"}
 
     def shape(k):

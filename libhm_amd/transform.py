@@ -53,9 +53,7 @@ def export_transform(call, seq, device, n, value="levels", components=(0, 1, 2),
     import torch
     desc = describe(value, components, dtype, scale)
     plan = plan_for(seq, desc, n)
-    elem = torch.int16 if desc.sample_type == abi.SAMPLE_UINT else dtype
-    if isinstance(elem, int):
-        elem = {abi.SAMPLE_F16: torch.float16, abi.SAMPLE_BF16: torch.bfloat16, abi.SAMPLE_F32: torch.float32}[elem]
+    elem = export.side_dtype(desc.sample_type, dtype)
     info = abi.TRANSFORM_DST_INFO
     names = {k: NAMES[k] for k in range(abi.TRANSFORM_DSTS) if plan.channels[k]}
 

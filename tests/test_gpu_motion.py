@@ -360,6 +360,18 @@ def test_refusals_leave_the_destination_untouched():
         assert c.ctx.motion_destination_status(1, desc, [None, dst["mv"].data_ptr(), None, None], [0, w4 * 2, 0, 0], [0, h4 * w4 * 2, 0, 0],
                                                [0, 4 * h4 * w4 * 2, 0, 0]) == abi.HMGPU_EINVAL      # (BLOCKS has no second vector slot)
         assert untouched()
+        # the pictures are checked before the plan: a dense export of the uploaded picture whose scale asks for a filter the export does
+        # not have (by the plan alone: HMGPU_EUNSUPPORTED)
+        dense = abi.make_motion_desc(abi.MOTION_DENSE, 3, abi.SAMPLE_F32)
+        whole = [abi.make_export_window((0, 0, 0, 0))]
+        bilinear = abi.make_export_scale(w4, h4, abi.SCALE_BILINEAR)
+        with pytest.raises(libhm_amd.HmgpuError) as e:
+            c.ctx.export_motion_into([uploaded], dense, ok, *args, 1, stream, bilinear, whole)
+        assert e.value.status == abi.HMGPU_EINVAL
+        with pytest.raises(libhm_amd.HmgpuError) as e:
+            c.ctx.export_motion_into([good], dense, ok, *args, 1, stream, bilinear, whole)
+        assert e.value.status == abi.HMGPU_EUNSUPPORTED
+        assert untouched()
         # the good picture still exports
         c.check_blocks(good, p)
 

@@ -550,6 +550,11 @@ def test_refusals_leave_the_destinations_untouched():
             with pytest.raises(libhm_amd.HmgpuError) as e:
                 c.ctx.export_residual_into([good, good], desc_d, *dargs, 1, stream, abi.make_export_scale(48, 32, f), whole)
             assert e.value.status == abi.HMGPU_EUNSUPPORTED
+        # ... which is refused before the pictures are looked at: the same call for a picture without a residual
+        with pytest.raises(libhm_amd.HmgpuError) as e:
+            c.ctx.export_residual_into([uploaded], desc_d, *dargs, 1, stream, abi.make_export_scale(48, 32, abi.SCALE_BILINEAR), whole[:1])
+        assert e.value.status == abi.HMGPU_EUNSUPPORTED
+        assert untouched()
         assert c.ctx.residual_destination_status(2, desc_d, *dargs, scale=abi.make_export_scale(48, 32, abi.SCALE_NEAREST), windows=whole) == abi.HMGPU_OK
         # a destination that does not lie inside one allocation: room for two pictures less one element; a pointer of no device
         desc = abi.make_residual_desc(abi.RESIDUAL_PLANES, 1)

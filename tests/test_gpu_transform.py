@@ -381,6 +381,9 @@ def test_refusals_leave_the_destinations_untouched():
             with pytest.raises(libhm_amd.HmgpuError) as e:
                 c.ctx.export_transform_into([good, good], d, ptrs, *args, 1, stream)
             assert e.value.status == status
+        with pytest.raises(libhm_amd.HmgpuError) as e:                                            # the plan comes before the pictures
+            c.ctx.export_transform_into([uploaded], desc(sample_type=9), ptrs, *args, 1, stream)
+        assert e.value.status == abi.HMGPU_EUNSUPPORTED
         with pytest.raises(libhm_amd.HmgpuError) as e:                                            # 17 pictures
             c.ctx.export_transform_into([good] * 17, ok, ptrs, *args, 1, stream)
         assert e.value.status == abi.HMGPU_EINVAL
