@@ -99,6 +99,7 @@ typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
 typedef struct hmgpu_residual_desc hmgpu_residual_desc;
 typedef struct hmgpu_transform_desc hmgpu_transform_desc;
+typedef struct hmgpu_loopfilter_desc hmgpu_loopfilter_desc;
 typedef struct hmgpu_metrics_desc hmgpu_metrics_desc;
 typedef struct hmgpu_metrics_map_desc hmgpu_metrics_map_desc;
 typedef struct hmgpu_histogram_desc hmgpu_histogram_desc;
@@ -197,6 +198,15 @@ int hmdec_pictures_export_residual(libHMDec_context* ctx, int n, libHMDec_pictur
 int hmdec_pictures_export_transform(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_transform_desc* desc,
                                     void* const dst[3], void* dst_info, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
                                     const int64_t batch_stride_bytes[4], int on_stream, void* stream);
+/* The loop-filter decisions of up to 16 pictures -- the edge grid and the SAO grid, or their dense form -- in one call
+ * (hmgpu_pictures_export_loopfilter: destinations, strides and statuses as there), under the rules of hmdec_pictures_export_motion:
+ * the edge records and SAO parameters lie in the device context that decoded a picture, everything is validated before any context is
+ * given work (hmgpu_loopfilter_destination_check, hmgpu_pictures_loopfilter_check), then each context gets one call per run of
+ * equally spaced slots. */
+int hmdec_pictures_export_loopfilter(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_loopfilter_desc* desc,
+                                     const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                     const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
+                                     int on_stream, void* stream);
 /* Up to 16 output pictures kept on the device compared with planes the caller holds in device memory -- decoded against original
  * (hmgpu_pictures_metrics with HMGPU_METRICS_REF_PLANES: records, reference planes, strides and statuses as there), under the rules of
  * hmdec_pictures_export_residual: everything is validated before any context is given work (hmgpu_metrics_check), then each context

@@ -989,6 +989,93 @@ hmgpu_status hmgpu_transform_destination_check(hmgpu_ctx* ctx, int32_t n, const 
                                                void* dst_info, const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4],
                                                const int64_t batch_stride_bytes[4]);
 
+/* ------------------------------------------------------------------------------------------------ loop-filter export
+ * What the decoder decided for the loop filters of finished pictures -- boundary strength, mean QP, tc and beta of every deblocking
+ * edge unit, the exemptions of its two sides, and the reconstructed SAO parameters of every CTB -- written on the device straight
+ * into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one kernel launch per call
+ * (k_lfinfo.hip).  The source lives as long as the picture's handle: the edge-unit records the decompress calls derived for the
+ * deblocking kernels, the slice table, and the SAO parameters the last filter call resolved.  All four chroma formats, 8 .. 12 bits,
+ * CTUs of 16 / 32 / 64 samples.  The sample-dependent decisions (filter off / weak / strong, dE, dEp, dEq) are not exported: they
+ * need the samples in front of deblocking, which a picture filtered in place no longer has.
+ *
+ * HMGPU_LOOPFILTER_GRIDS: two grids, each optional.
+ * Edge grid: dst_edge int16 [n][HMGPU_LOOPFILTER_EDGE_CHANNELS][h4][w4] on the motion export's grid of 4x4 luma blocks; desc->crop
+ * (left, right, top, bottom in luma samples, each a multiple of 8, else HMGPU_EINVAL; 0,0,0,0 = the coded picture) selects w4 x h4
+ * blocks.  The VERTICAL unit of block (bx, by) is the 4-sample edge unit on its left border and exists where bx is even (x % 8 == 0),
+ * its HORIZONTAL unit the one on its top border, where by is even; a block off the 8x8 grid in a direction holds 0 in every channel
+ * of that direction.  Bs > 0 means the unit is filtered; Bs is 0 where there is no PU / TU edge, where deblocking is disabled for the
+ * slice of the Q side (the block itself), where the P side (left / above) is not available across a slice or tile border, and where
+ * xGetBoundaryStrengthSingle gives 0.  The slice constants of a unit are those of the CTU the Q side lies in.
+ *   0, 1    BS_VER, BS_HOR        0 .. 2
+ *   2, 3    QP_VER, QP_HOR        (QP_P + QP_Q + 1) >> 1 where Bs > 0, else 0
+ *   4, 5    TC_VER, TC_HOR        luma tc: tcTable[clip(0, 53, qp + 2 * (Bs - 1) + 2 * tc_offset_div2)] << (bit_depth_luma - 8); 0 where Bs is 0
+ *   6, 7    BETA_VER, BETA_HOR    betaTable[clip(0, 51, qp + 2 * beta_offset_div2)] << (bit_depth_luma - 8); 0 where Bs is 0
+ *   8 .. 11 TC_CB_VER, TC_CB_HOR, TC_CR_VER, TC_CR_HOR: chroma tc (xEdgeFilterChroma): qPi = qp + pps_cb / cr_qp_offset through the
+ *           chroma QP mapping of the format (the 4:2:0 table, min(qPi, 51) otherwise), tcTable[clip(0, 53, QpC + 2 + 2 * tc_offset_div2)]
+ *           << (bit_depth_chroma - 8).  Non-zero only where the chroma filter acts: Bs is 2 and the unit lies on the 8-sample grid of
+ *           the chroma plane (every 16 luma samples across a subsampled direction, every 8 otherwise); 0 everywhere in 4:0:0
+ *   12      FLAGS  bit 0 / 1: the P / Q side of the vertical unit is exempt from the loop filters (lossless CU, PCM CU with
+ *           pcm_loop_filter_disabled); bit 2 / 3: the same of the horizontal unit; 0 where Bs is 0
+ * SAO grid: dst_sao int8 [n][3][HMGPU_LOOPFILTER_SAO_CHANNELS][ctus_h][ctus_w], per component and CTB, always the whole picture
+ * (the crop does not apply).  The two leading dimensions are one run of 18 planes, plane_stride_bytes apart.
+ *   0       TYPE   -1 off, else HMGPU_SAO_EO_0 .. HMGPU_SAO_BO (merge candidates resolved)
+ *   1       BAND   BO: the first band; 0 otherwise
+ *   2 .. 5  OFF0 .. OFF3: the offsets as applied (after << sao_offset_shift).  EO: categories 1, 2, 3, 4; BO: bands BAND + 0 .. 3; 0 when off
+ * The chroma components of a 4:0:0 picture are left untouched.  A picture whose last filter call ran no SAO stage (sao_enabled 0, or
+ * `stages` without bit 2) exports TYPE -1 and zeros: that is decided on the host, never from what the parameter buffer holds.
+ *
+ * HMGPU_LOOPFILTER_DENSE: dst_dense [n][3][H][W], one value per output sample of hmgpu_pictures_export_windows with the same windows,
+ * output size and flips, by the integer nearest rule of the dense motion export (scale: filter HMGPU_SCALE_NEAREST, else
+ * HMGPU_EUNSUPPORTED; or windows of one size; desc->crop 0).  For the source luma position (x, y) of an output sample:
+ *   0  Bs of the vertical unit at column e = (x + 4) & ~7, row y >> 2 -- the edge whose filter can reach the sample (three samples
+ *      modified and a fourth read on either side); 0 when e == 0 or e >= width
+ *   1  the same with x and y exchanged
+ *   2  TYPE + 1 of the luma SAO parameters of the sample's CTB (0 = off)
+ * A mirrored slot has its positions reversed and its values unchanged.  sample_type HMGPU_SAMPLE_UINT: uint8, the value v itself;
+ * F16 / BF16 / F32: convert(fmul((float)v, desc->scale[c])), the rule and conversion of the dense residual form; every scale finite.
+ *
+ * Which pictures qualify: the edge grid and dense channels 0 / 1 need the coverage rule of the motion export (decompress calls have
+ * covered every CTU since the picture was acquired).  The SAO grid and the dense form need a filter call
+ * (hmgpu_filter_pictures / hmgpu_filter_picture[_stages]) on the current occupant of the handle as well: acquire, upload, a received
+ * picture and every later decompress call on the handle clear that record.  Else HMGPU_EINVAL, nothing written.
+ * Destinations: slots 0 edge, 1 SAO, 2 dense index pitch_bytes, plane_stride_bytes and batch_stride_bytes.  A NULL destination is
+ * not written, at least one must be given, and a destination of the other form must be NULL.  Alignment, stride and allocation rules,
+ * the untouched destinations of a refused call and stream ordering are those of the motion export. */
+enum { HMGPU_LOOPFILTER_GRIDS = 0, HMGPU_LOOPFILTER_DENSE = 1 };
+enum { HMGPU_LOOPFILTER_DST_EDGE = 0, HMGPU_LOOPFILTER_DST_SAO = 1, HMGPU_LOOPFILTER_DST_DENSE = 2, HMGPU_LOOPFILTER_DSTS = 3 };
+enum { HMGPU_LOOPFILTER_EDGE_CHANNELS = 13, HMGPU_LOOPFILTER_SAO_CHANNELS = 6 };
+enum { HMGPU_LF_BS_VER = 0, HMGPU_LF_BS_HOR, HMGPU_LF_QP_VER, HMGPU_LF_QP_HOR, HMGPU_LF_TC_VER, HMGPU_LF_TC_HOR, HMGPU_LF_BETA_VER,
+       HMGPU_LF_BETA_HOR, HMGPU_LF_TC_CB_VER, HMGPU_LF_TC_CB_HOR, HMGPU_LF_TC_CR_VER, HMGPU_LF_TC_CR_HOR, HMGPU_LF_FLAGS };
+enum { HMGPU_LF_SAO_TYPE = 0, HMGPU_LF_SAO_BAND = 1, HMGPU_LF_SAO_OFF0 = 2 };
+typedef struct hmgpu_loopfilter_desc {
+  int32_t form;                /* HMGPU_LOOPFILTER_* */
+  int32_t sample_type;         /* DENSE: HMGPU_SAMPLE_UINT (uint8) / F16 / BF16 / F32; GRIDS: HMGPU_SAMPLE_UINT */
+  int32_t crop[4];             /* GRIDS: left, right, top, bottom in luma samples, multiples of 8 (edge grid); DENSE: 0 */
+  float scale[3];              /* DENSE, float types: per channel */
+  int32_t reserved[7];         /* 0 */
+} hmgpu_loopfilter_desc;
+typedef struct hmgpu_loopfilter_plan {
+  int32_t channels[3];         /* per destination slot (HMGPU_LOOPFILTER_DST_*): planes per picture, 0 = the slot does not exist */
+  int32_t width[3], height[3]; /* of every plane, in elements */
+  int32_t elem_bytes[3];
+  int32_t row_bytes[3];        /* width * elem_bytes: the least pitch */
+  int32_t reserved[1];
+} hmgpu_loopfilter_plan;
+/* validates a call's description and reports what it writes; host code, no device needed.  scale / windows: NULL for GRIDS */
+hmgpu_status hmgpu_loopfilter_plan_for(const hmgpu_seq_params* seq, const hmgpu_loopfilter_desc* desc, const hmgpu_export_scale* scale,
+                                       int32_t n, const hmgpu_export_window windows[], hmgpu_loopfilter_plan* out);
+hmgpu_status hmgpu_pictures_export_loopfilter(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_loopfilter_desc* desc,
+                                              const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                              const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3],
+                                              const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* the two halves of that validation, nothing enqueued (libhmdec: pictures in several contexts of a GPU): HMGPU_OK when pics[0 .. n)
+ * are all valid handles of covered pictures and, with need_filter != 0 (the SAO grid or the dense form is asked for), of pictures a
+ * filter call has run on; the status hmgpu_pictures_export_loopfilter would give a description and a destination for n pictures */
+hmgpu_status hmgpu_pictures_loopfilter_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], int32_t need_filter);
+hmgpu_status hmgpu_loopfilter_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_loopfilter_desc* desc, const hmgpu_export_scale* scale,
+                                                const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
+                                                const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ picture metrics
  * Finished pictures compared on the device, sample by sample, with other pictures of the context or with planes the caller holds in
  * device memory: up to HMGPU_EXPORT_MAX_BATCH pictures, one kernel launch per call (k_metrics.hip) behind one

@@ -192,6 +192,15 @@ def lib():
         L.hmgpu_pictures_transform_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.hmgpu_transform_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.TransformDesc), C.POINTER(C.c_void_p), C.c_void_p,
                                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_loopfilter_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.LoopfilterDesc), C.POINTER(abi.ExportScale), C.c_int32,
+                                                C.POINTER(abi.ExportWindow), C.POINTER(abi.LoopfilterPlan)]
+        L.hmgpu_pictures_export_loopfilter.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.LoopfilterDesc),
+                                                       C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
+                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_pictures_loopfilter_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+        L.hmgpu_loopfilter_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.LoopfilterDesc), C.POINTER(abi.ExportScale),
+                                                         C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_metrics_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.MetricsDesc), C.POINTER(abi.MetricsPlan)]
         L.hmgpu_metrics_psnr.argtypes = [C.POINTER(abi.MetricsResult), C.c_int32]
         L.hmgpu_metrics_psnr.restype = C.c_double
@@ -500,6 +509,12 @@ def transform_plan(seq, value="levels", components=(0, 1, 2), dtype=None, scale=
     """what Context.export_transform with these arguments writes per picture (libhm_amd.transform.transform_plan: host code, no GPU)"""
     from . import transform
     return transform.transform_plan(seq, value, components, dtype, scale, n)
+
+
+def loopfilter_plan(seq, form="grids", size=None, windows=None, flip=None, dtype=None, scale=None, crop=(0, 0, 0, 0), n=None):
+    """what Context.export_loopfilter with these arguments writes per picture (libhm_amd.loopfilter.loopfilter_plan: host code, no GPU)"""
+    from . import loopfilter
+    return loopfilter.loopfilter_plan(seq, form, size, windows, flip, dtype, scale, crop, n)
 
 
 def metrics_plan(seq, reference="pictures", components=(0, 1, 2), ssim=True, crop=(0, 0, 0, 0), ref_bytes_per_sample=2):
@@ -997,6 +1012,44 @@ class Context:
         return transform.export_transform(lambda desc, ptrs, pitches, pstrides, bstrides, st:
                                           self.export_transform_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st),
                                           self.seq, self.device, len(pics), value, components, dtype, scale, out)
+
+    def export_loopfilter_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
+        """hmgpu_pictures_export_loopfilter into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per
+        destination slot (0 the edge grid, 1 the SAO grid, 2 the dense form; a pointer None / 0 = not written)"""
+        from . import loopfilter
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_loopfilter(self._h, len(pics), abi.handle_array(pics), C.byref(desc), abi.ref(scale),
+                                                         abi.window_array(windows), *loopfilter.c_args(ptrs, pitches, pstrides, bstrides),
+                                                         on_stream, abi.addr(stream)), "hmgpu_pictures_export_loopfilter")
+
+    def loopfilter_destination_status(self, n, desc, ptrs, pitches, pstrides, bstrides, scale=None, windows=None):
+        """hmgpu_loopfilter_destination_check: the status hmgpu_pictures_export_loopfilter would give this destination; enqueues nothing"""
+        from . import loopfilter
+        return lib().hmgpu_loopfilter_destination_check(self._h, n, C.byref(desc), abi.ref(scale), abi.window_array(windows),
+                                                        *loopfilter.c_args(ptrs, pitches, pstrides, bstrides))
+
+    def loopfilter_status(self, pics, need_filter=True):
+        """hmgpu_pictures_loopfilter_check: HMGPU_OK when every picture of the list is covered by decompress calls and (need_filter: the
+        SAO grid, the dense form) a filter call has run on it; enqueues nothing"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_loopfilter_check(self._h, len(pics), abi.handle_array(pics), 1 if need_filter else 0)
+
+    def export_loopfilter(self, pics, form="grids", grids=("edge", "sao"), size=None, windows=None, flip=None, dtype=None, scale=None,
+                          out=None, crop=(0, 0, 0, 0), on_stream=True):
+        """the loop-filter decisions of up to 16 decoded pictures as a dict of torch tensors on this context's GPU (libhm_amd.loopfilter),
+        one launch, written on torch.cuda.current_stream() (on_stream) or on the context's own stream.  form "grids": "edge" int16
+        [N, 13, H / 4, W / 4] (Bs, mean QP, tc, beta, chroma tc and exemptions of the edge units on every 4x4 block's left and top
+        border; crop in multiples of 8 luma samples) and "sao" int8 [N, 3, 6, ctus_h, ctus_w] (type, band and offsets per CTB and
+        component); grids= selects one of them.  form "dense": "loopfilter" [N, 3, H, W], one value per output sample of
+        export_batch(windows=, flip=, size=, filter="nearest"): Bs of the vertical / horizontal edge that can reach the sample and the
+        luma SAO type + 1; dtype None (uint8) or torch.float16 / bfloat16 / float32 with scale (one factor per channel).  out: a dict
+        with some of those keys (only they are written).  Pictures that were uploaded, received or only partly decoded give
+        HMGPU_EINVAL, and so do the SAO grid and the dense form of a picture no filter call has run on."""
+        from . import loopfilter
+        pics = list(pics)
+        return loopfilter.export_loopfilter(lambda desc, sc, win, ptrs, pitches, pstrides, bstrides, st:
+                                            self.export_loopfilter_into(pics, desc, ptrs, pitches, pstrides, bstrides, 1 if on_stream else 0, st, sc, win),
+                                            self.seq, self.device, len(pics), form, grids, size, windows, flip, dtype, scale, out, crop)
 
     def set_streams(self, n):
         """lanes of replay(): 1 = serial kernels, 2 = two half-batches on two streams"""

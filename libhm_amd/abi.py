@@ -358,6 +358,36 @@ def make_transform_desc(value=TRANSFORM_LEVELS, components=7, sample_type=SAMPLE
     return d
 
 
+LOOPFILTER_GRIDS, LOOPFILTER_DENSE = 0, 1
+LOOPFILTER_DST_EDGE, LOOPFILTER_DST_SAO, LOOPFILTER_DST_DENSE, LOOPFILTER_DSTS = 0, 1, 2, 3
+LOOPFILTER_EDGE_CHANNELS, LOOPFILTER_SAO_CHANNELS = 13, 6
+(LF_BS_VER, LF_BS_HOR, LF_QP_VER, LF_QP_HOR, LF_TC_VER, LF_TC_HOR, LF_BETA_VER, LF_BETA_HOR, LF_TC_CB_VER, LF_TC_CB_HOR, LF_TC_CR_VER,
+ LF_TC_CR_HOR, LF_FLAGS) = range(13)
+LF_SAO_TYPE, LF_SAO_BAND, LF_SAO_OFF0 = 0, 1, 2
+
+
+class LoopfilterDesc(C.Structure):
+    _fields_ = [("form", C.c_int32), ("sample_type", C.c_int32), ("crop", C.c_int32 * 4), ("scale", C.c_float * 3),
+                ("reserved", C.c_int32 * 7)]
+
+
+class LoopfilterPlan(C.Structure):
+    _fields_ = [("channels", C.c_int32 * 3), ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("elem_bytes", C.c_int32 * 3),
+                ("row_bytes", C.c_int32 * 3), ("reserved", C.c_int32 * 1)]
+
+
+def make_loopfilter_desc(form=LOOPFILTER_GRIDS, sample_type=SAMPLE_UINT, crop=(0, 0, 0, 0), scale=(1.0, 1.0, 1.0)):
+    """form: LOOPFILTER_GRIDS / LOOPFILTER_DENSE; crop: (left, right, top, bottom) in multiples of 8, GRIDS only; sample_type and scale
+    (per channel): the element of DENSE"""
+    d = LoopfilterDesc()
+    d.form, d.sample_type = int(form), int(sample_type)
+    for i in range(4):
+        d.crop[i] = int(crop[i])
+    for k in range(3):
+        d.scale[k] = float(scale[k])
+    return d
+
+
 METRICS_REF_PICTURES, METRICS_REF_PLANES = 0, 1
 METRICS_NO_DIFF = (1 << 64) - 1
 

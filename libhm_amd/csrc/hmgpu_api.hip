@@ -634,6 +634,7 @@ hmgpu_status hmgpu_picture_acquire(hmgpu_ctx* c, hmgpu_pic* out) {
       p.in_use = true; p.sao_applied = false; p.filter_ready = false; p.sao_any = false; p.calls.clear(); p.max_slice = -1;
       p.extended = false;
       coverage_clear(p);
+      filter_forget(p);
       p.dev.sao_applied = 0; p.dev.any_nofilt = 0;
       *out = (hmgpu_pic)i;
       hmgpu_status st = push_final(c, (int)i, c->stream);
@@ -653,6 +654,7 @@ hmgpu_status hmgpu_picture_upload(hmgpu_ctx* c, hmgpu_pic pic, const int16_t* co
   if (!c || !valid_pic(c, pic) || !planes || !strides) return HMGPU_EINVAL;
   Picture& p = c->pics[pic];
   coverage_clear(p);                   // (uploaded samples come without side information)
+  filter_forget(p);
   if (p.sao_applied) {                 // uploaded samples ARE the picture: back to the reconstruction planes
     p.sao_applied = false; p.dev.sao_applied = 0;
     hmgpu_status st = push_final(c, pic, c->stream);
@@ -749,6 +751,7 @@ hmgpu_status hmgpu_picture_device_region(hmgpu_ctx* c, hmgpu_pic pic, int32_t wh
       if (st != HMGPU_OK) return st;
     }
     p.extended = false;
+    filter_forget(p);
     *base = p.planes;
   }
   *bytes = (int64_t)plane_bytes;
@@ -760,6 +763,7 @@ hmgpu_status hmgpu_picture_commit_received(hmgpu_ctx* c, hmgpu_pic pic) {
   Picture& p = c->pics[pic];
   if (p.sao_applied) return HMGPU_EINVAL;          // hmgpu_picture_device_region(RECEIVE) was not called
   coverage_clear(p);                               // (only the planes travelled)
+  filter_forget(p);
   p.extended = true;                               // the margins travelled with the planes
   return HMGPU_OK;
 }

@@ -670,6 +670,34 @@ struct TransformArgs {
 };
 // coeffs: HMGPU_TRANSFORM_COEFFS (else the levels); elem: kElemU16 (int16) / kElemF16 / kElemBF16 / kElemF32
 void launch_transform(const TransformArgs& a, bool coeffs, int elem, int num_ctus, hipStream_t s);
+// loop-filter export (k_lfinfo.hip, hmgpu_pictures_export_loopfilter): everything by value, validated on the host.  The edge-unit records
+// k_prep derived for the picture (PicDev::edges), the slice table behind the per-CTU slice index, and the SAO parameters the last filter
+// call resolved.  `gate` is what the host knows about those: without kLfSao the parameter buffer is never read (no filter call with an
+// SAO stage on the handle's current picture) and every CTB is exported as off.
+// Destination slots: 0 the edge grid, 1 the SAO grid, 2 the dense form (HMGPU_LOOPFILTER_DST_*).
+enum { kLfSao = 1 };
+struct LfSrc {
+  const EdgeRec* edges; const SaoDev* saoprm;
+  const uint16_t* slice_idx; const SliceDev* slices;
+  int32_t gate, pad_;
+};
+struct LfArgs {
+  LfSrc src[kMaxExportBatch];
+  SideWin win[kMaxExportBatch];    // dense form
+  int32_t n, mono, fmt, csx, csy;  // pictures; 4:0:0; chroma_format_idc (0 kept as 1) and its subsampling
+  int32_t log2ctu, ctus_w, ctus_h; // geometry of the context
+  int32_t ew;                      // EdgeRec records per row of the grid (grid_w / 2)
+  int32_t width, height, bd[2];    // luma samples; bit depth of luma / chroma
+  int32_t x8, y8, w8, h8;          // grids form: first 8x8 area and size of the cropped edge grid in areas
+  int32_t W, H;                    // dense form: output size
+  uint32_t flip;                   // dense form: bit i: slot i is mirrored
+  int32_t vec;                     // bit k: destination k may take dword stores (alignment of dst and strides)
+  float scale[3];                  // dense form, float elements: per channel
+  uint8_t* dst[3];
+  int64_t pitch[3], pstride[3], bstride[3];   // bytes: row to row, plane to plane, picture to picture
+};
+void launch_lfinfo_grids(const LfArgs& a, hipStream_t s);
+void launch_lfinfo_dense(const LfArgs& a, int elem, hipStream_t s);   // elem: kElemU8 / kElemF16 / kElemBF16 / kElemF32
 // picture metrics (k_metrics.hip, hmgpu_pictures_metrics): everything by value, validated on the host.  Plane class 0 is luma, class 1
 // the chroma pair (Cb and Cr from one load of the pair plane); a class with no selected component has no tiles.  Work items are
 // (picture, class, tile) in that order; workgroup g walks items [g * per, (g + 1) * per).  A tile is 2048 samples: 64 x 32 with SSIM (the

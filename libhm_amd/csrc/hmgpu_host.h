@@ -26,6 +26,9 @@ struct Picture {
   bool filter_ready = false;            // SAO parameters staged
   bool sao_any = false;
   bool extended = false;                // margins of the final planes hold the replicated border
+  // loop-filter export: a filter call has run on the handle's current picture, and that call staged SAO parameters (an SAO stage with
+  // sao_enabled).  Cleared with sao_applied: acquire, upload, a received picture, and every later decompress call (filter_forget)
+  bool lf_called = false, lf_sao = false;
   std::vector<SliceCall> calls;
   // device allocations (owned)
   void* planes = nullptr;               // rec[3] + sao[3]
@@ -244,6 +247,7 @@ hmgpu_status push_picdev(hmgpu_ctx* c, int pic);
 hmgpu_status push_final(hmgpu_ctx* c, int pic, hipStream_t hs);
 bool valid_pic(const hmgpu_ctx* c, hmgpu_pic pic);
 void coverage_clear(Picture& p);
+inline void filter_forget(Picture& p) { p.lf_called = false; p.lf_sao = false; }
 void coverage_add(const hmgpu_ctx* c, Picture& p, int first_ctu, int num_ctus);
 hmgpu_status ensure_extended(hmgpu_ctx* c, int pic);
 

@@ -299,6 +299,7 @@ static bool meta_complete(const hmgpu_ctu_meta* m, const hmgpu_coeffs* co) {
 
 static hmgpu_status reopen_picture(hmgpu_ctx* c, hmgpu_pic cur, hipStream_t hs) {
   Picture& p = c->pics[cur];
+  filter_forget(p);                    // (whatever a filter call left belongs to what the handle held before this call)
   if (p.sao_applied) {                 // picture buffer decoded again without release/acquire: reconstruction planes again
     p.sao_applied = false; p.dev.sao_applied = 0;
     return push_final(c, cur, hs);
@@ -664,6 +665,7 @@ hmgpu_status hmgpu_filter_pictures(hmgpu_ctx* c, int32_t n, const hmgpu_filter_j
       if (st != HMGPU_OK) return st;
     }
     p.filter_ready = true;
+    p.lf_called = true; p.lf_sao = jobs[i].pp->sao_enabled != 0;
     b.pic[i] = jobs[i].pic; b.first_ctu[i] = 0; b.num_ctus[i] = c->num_ctus;
   }
   }
@@ -697,6 +699,7 @@ hmgpu_status hmgpu_filter_picture_stages(hmgpu_ctx* c, hmgpu_pic cur, const hmgp
     if (st != HMGPU_OK) return st;
   }
   p.filter_ready = true;
+  p.lf_called = true; p.lf_sao = (stages & 4) && pp->sao_enabled;
   Batch b; memset(&b, 0, sizeof(b));
   b.n = 1; b.pic[0] = cur; b.first_ctu[0] = 0; b.num_ctus[0] = c->num_ctus;
   bool fused = false;

@@ -1,11 +1,12 @@
-// hmgpu_side.hip -- side-information export of the host runtime: the motion / block, residual and transform exports.  Per family one
-// plan, one *_resolve under the destination check and the launching entry, and the kernel's arguments (k_motion / k_residual / k_transform.hip).
+// hmgpu_side.hip -- side-information export of the host runtime: the motion / block, residual, transform and loop-filter exports.  Per
+// family one plan, one *_resolve under the destination check and the launching entry, and the kernel's arguments (k_motion / k_residual /
+// k_transform / k_lfinfo.hip).
 #include "hmgpu_host.h"
 
 #include <cmath>
 #include <cstring>
 
-// ------------------------------------------------------------------------------------------------ what the three families share
+// ------------------------------------------------------------------------------------------------ what the families share
 // the preamble of every plan: *out zeroed (a plan writes it only behind its last refusal: a refused plan is all zero); the sequence's
 // geometry (sizes whole in size_mask + 1 samples), n, reserved[]
 template <class Desc, class Plan>
@@ -373,6 +374,112 @@ hmgpu_status hmgpu_pictures_export_transform(hmgpu_ctx* c, int32_t n, const hmgp
   }
   for (int k = 0; k < (mono ? 1 : 3); k++) if (dst[k]) a.scale[k] = d->scale[k];
   launch_transform(a, d->value == HMGPU_TRANSFORM_COEFFS, side_elem(d->sample_type, true), c->num_ctus, hs);
+  return export_end(c, n, pics, on_stream, hs);
+}
+
+
+// ------------------------------------------------------------------------------------------------ loop-filter export (k_lfinfo.hip)
+hmgpu_status hmgpu_loopfilter_plan_for(const hmgpu_seq_params* seq, const hmgpu_loopfilter_desc* d, const hmgpu_export_scale* sc, int32_t n,
+                                       const hmgpu_export_window win[], hmgpu_loopfilter_plan* out) {
+  if (!side_plan_open(seq, d, 7, n, out)) return HMGPU_EINVAL;
+  if (d->form != HMGPU_LOOPFILTER_GRIDS && d->form != HMGPU_LOOPFILTER_DENSE) return HMGPU_EINVAL;
+  if (d->form == HMGPU_LOOPFILTER_GRIDS) {
+    if (sc || win || d->sample_type != HMGPU_SAMPLE_UINT) return HMGPU_EINVAL;
+    if ((d->crop[0] | d->crop[1] | d->crop[2] | d->crop[3]) & 7) return HMGPU_EINVAL;         // whole 8x8 areas (a negative crop: crop_ok)
+    int w, h;
+    if (crop_ok(seq, d->crop, nullptr, &w, &h) != HMGPU_OK) return HMGPU_EINVAL;
+    const int E = HMGPU_LOOPFILTER_DST_EDGE, S = HMGPU_LOOPFILTER_DST_SAO, ctu = 1 << seq->log2_ctu_size;
+    out->channels[E] = HMGPU_LOOPFILTER_EDGE_CHANNELS; out->elem_bytes[E] = 2;
+    out->width[E] = w / 4; out->height[E] = h / 4; out->row_bytes[E] = out->width[E] * 2;
+    out->channels[S] = 3 * HMGPU_LOOPFILTER_SAO_CHANNELS; out->elem_bytes[S] = 1;               // the CTBs of the whole picture
+    out->width[S] = (seq->width + ctu - 1) / ctu; out->height[S] = (seq->height + ctu - 1) / ctu; out->row_bytes[S] = out->width[S];
+    return HMGPU_OK;
+  }
+  const int elem = side_elem(d->sample_type, true);                                            // (the integer element is uint8 here)
+  if (elem < 0 || !side_scale_ok(elem, 7, d->scale)) return HMGPU_EINVAL;
+  if (sc) { const hmgpu_status st = scale_desc_ok(sc); if (st != HMGPU_OK) return st; }
+  int w = 0, h = 0;
+  { const hmgpu_status st = dense_form_ok(seq, d->crop, sc, n, win, &w, &h); if (st != HMGPU_OK) return st; }
+  const int D = HMGPU_LOOPFILTER_DST_DENSE;
+  out->channels[D] = 3; out->elem_bytes[D] = elem == kElemU16 ? 1 : elem == kElemF32 ? 4 : 2;
+  out->width[D] = w; out->height[D] = h; out->row_bytes[D] = w * out->elem_bytes[D];
+  return HMGPU_OK;
+}
+
+// the pictures of a call: covered like every side-information export's; need_filter (the SAO grid, the dense form): a filter call has
+// run on the handle's current picture, so that what the SAO parameters are -- resolved by that call, or known to be off -- is on record
+static hmgpu_status loopfilter_pictures_ok(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, bool need_filter) {
+  { const hmgpu_status st = side_pictures_ok(c, n, pics); if (st != HMGPU_OK) return st; }
+  for (int i = 0; i < n && need_filter; i++) if (!c->pics[pics[i]].lf_called) return HMGPU_EINVAL;
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_pictures_loopfilter_check(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], int32_t need_filter) {
+  return loopfilter_pictures_ok(c, n, pics, need_filter != 0);
+}
+
+// everything hmgpu_pictures_export_loopfilter checks: the plan, the pictures (pics null: hmgpu_loopfilter_destination_check, which has
+// none), the destinations -- those of the other form must be null --; and what these give the kernel: *a zero but for its slots and vec
+static hmgpu_status loopfilter_resolve(hmgpu_ctx* c, int32_t n, const hmgpu_pic* pics, const hmgpu_loopfilter_desc* d, const hmgpu_export_scale* sc,
+                                       const hmgpu_export_window* windows, void* const dst[3], const int64_t* pitch, const int64_t* pstride,
+                                       const int64_t* bstride, hmgpu_loopfilter_plan* plan, LfArgs* a) {
+  if (!c || !d || !dst || !pitch || !pstride || !bstride) return HMGPU_EINVAL;
+  { const hmgpu_status st = hmgpu_loopfilter_plan_for(&c->seq, d, sc, n, windows, plan); if (st != HMGPU_OK) return st; }
+  const bool dense = d->form == HMGPU_LOOPFILTER_DENSE;
+  if (pics) {
+    const hmgpu_status st = loopfilter_pictures_ok(c, n, pics, dense || dst[HMGPU_LOOPFILTER_DST_SAO] != nullptr);
+    if (st != HMGPU_OK) return st;
+  }
+  memset(a, 0, sizeof(*a));
+  // dword stores: two int16 of the edge grid, four elements of the dense form
+  { const hmgpu_status st = strided_dst_ok(c, *plan, HMGPU_LOOPFILTER_DSTS, n, dst, pitch, pstride, bstride, dense ? 0 : 4, &a->vec);
+    if (st != HMGPU_OK) return st; }
+  side_destinations(a, HMGPU_LOOPFILTER_DSTS, dst, pitch, pstride, bstride);
+  return HMGPU_OK;
+}
+
+hmgpu_status hmgpu_loopfilter_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_loopfilter_desc* d, const hmgpu_export_scale* sc,
+                                                const hmgpu_export_window windows[], void* const dst[3], const int64_t pitch_bytes[3],
+                                                const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3]) {
+  hmgpu_loopfilter_plan plan;
+  LfArgs a;
+  return loopfilter_resolve(c, n, nullptr, d, sc, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &plan, &a);
+}
+
+hmgpu_status hmgpu_pictures_export_loopfilter(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_loopfilter_desc* d,
+                                              const hmgpu_export_scale* sc, const hmgpu_export_window windows[], void* const dst[3],
+                                              const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3],
+                                              const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  if (!pics || (on_stream != 0 && on_stream != 1)) return HMGPU_EINVAL;
+  hmgpu_loopfilter_plan plan;
+  LfArgs a;
+  { const hmgpu_status st = loopfilter_resolve(c, n, pics, d, sc, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes, &plan, &a);
+    if (st != HMGPU_OK) return st; }
+  hipStream_t hs = c->stream;
+  { const hmgpu_status st = export_open(c, on_stream, stream, &hs); if (st != HMGPU_OK) return st; }
+  a.n = n; a.mono = c->seq.chroma_format == 0; a.fmt = c->fmt; a.csx = c->csx; a.csy = c->csy;
+  a.log2ctu = c->seq.log2_ctu_size; a.ctus_w = c->ctus_w; a.ctus_h = c->ctus_h; a.ew = c->grid_w / 2;
+  a.width = c->seq.width; a.height = c->seq.height;
+  a.bd[0] = c->seq.bit_depth_luma; a.bd[1] = c->seq.bit_depth_chroma;
+  for (int i = 0; i < n; i++) {
+    const Picture& pic = c->pics[pics[i]];
+    const PicDev& p = pic.dev;
+    LfSrc& s = a.src[i];
+    s.edges = p.edges; s.saoprm = p.saoprm; s.slice_idx = p.slice_idx; s.slices = p.slices;
+    s.gate = pic.lf_sao ? kLfSao : 0;               // (the parameter buffer of a picture filtered without an SAO stage is stale: never read)
+  }
+  if (d->form == HMGPU_LOOPFILTER_GRIDS) {
+    a.x8 = d->crop[0] / 8; a.y8 = d->crop[2] / 8;
+    a.w8 = plan.width[HMGPU_LOOPFILTER_DST_EDGE] / 2; a.h8 = plan.height[HMGPU_LOOPFILTER_DST_EDGE] / 2;
+    launch_lfinfo_grids(a, hs);
+  } else {
+    const int D = HMGPU_LOOPFILTER_DST_DENSE;
+    a.W = plan.width[D]; a.H = plan.height[D];
+    for (int k = 0; k < 3; k++) a.scale[k] = d->scale[k];
+    for (int i = 0; i < n; i++) dense_window(c->seq, windows, i, &a.win[i], &a.flip);
+    const int elem = side_elem(d->sample_type, true);
+    launch_lfinfo_dense(a, elem == kElemU16 ? kElemU8 : elem, hs);
+  }
   return export_end(c, n, pics, on_stream, hs);
 }
 

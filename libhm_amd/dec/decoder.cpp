@@ -1206,6 +1206,19 @@ hmgpu_status Decoder::export_transform(int n, PicData* const* pics, const hmgpu_
         return hmgpu_pictures_export_transform(c, rn, h, desc, d, d[3], pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
 }
 
+// (the pictures of a run need a filter call where the run writes the SAO grid or the dense form: hmgpu_pictures_loopfilter_check)
+hmgpu_status Decoder::export_loopfilter(int n, PicData* const* pics, const hmgpu_loopfilter_desc* desc, const hmgpu_export_scale* scale,
+                                         const hmgpu_export_window* windows, void* const dst[3], const int64_t pitch_bytes[3],
+                                         const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  if (!gpu_ || !pics || !desc || !dst || !pitch_bytes || !plane_stride_bytes || !batch_stride_bytes || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  const bool need_filter = desc->form == HMGPU_LOOPFILTER_DENSE || dst[HMGPU_LOOPFILTER_DST_SAO] != nullptr;
+  return export_side<3>(n, pics, windows, dst, batch_stride_bytes,
+      [&](hmgpu_ctx* c) { return hmgpu_loopfilter_destination_check(c, n, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, void* const*, const int64_t*) { return hmgpu_pictures_loopfilter_check(c, rn, h, need_filter ? 1 : 0); },
+      [&](hmgpu_ctx* c, int rn, const hmgpu_pic* h, const hmgpu_export_window* w, void* const* d, const int64_t* bs) {
+        return hmgpu_pictures_export_loopfilter(c, rn, h, desc, scale, w, d, pitch_bytes, plane_stride_bytes, bs, on_stream, stream); });
+}
+
 // hmgpu_pictures_metrics through export_side, the results the fourth destination behind the reference planes: the whole call --
 // description, reference planes and results of all n slots -- validated once (the first handle standing for every slot), then every
 // run's handles, then one call per run.

@@ -110,6 +110,10 @@ class Decoder {
   hmgpu_status export_transform(int n, PicData* const* pics, const hmgpu_transform_desc* desc, void* const dst[3], void* dst_info,
                                 const int64_t pitch_bytes[4], const int64_t plane_stride_bytes[4], const int64_t batch_stride_bytes[4],
                                 int on_stream, void* stream);
+  // hmgpu_pictures_export_loopfilter under the same rules
+  hmgpu_status export_loopfilter(int n, PicData* const* pics, const hmgpu_loopfilter_desc* desc, const hmgpu_export_scale* scale,
+                                 const hmgpu_export_window* windows, void* const dst[3], const int64_t pitch_bytes[3],
+                                 const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
   // hmgpu_pictures_metrics against the caller's planes (HMGPU_METRICS_REF_PLANES), the pictures grouped by context as above
   hmgpu_status metrics(int n, PicData* const* pics, const hmgpu_metrics_desc* desc, const void* const ref[3], const int64_t ref_pitch_bytes[3],
                        const int64_t ref_batch_stride_bytes[3], void* results, int64_t results_batch_stride_bytes, int on_stream, void* stream);

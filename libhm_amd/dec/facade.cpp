@@ -416,6 +416,16 @@ int hmdec_pictures_export_transform(libHMDec_context* ctx, int n, libHMDec_pictu
   return static_cast<Wrapper*>(ctx)->dec.export_transform(n, p, desc, dst, dst_info, pitch_bytes, plane_stride_bytes, batch_stride_bytes,
                                                           on_stream, stream);
 }
+int hmdec_pictures_export_loopfilter(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_loopfilter_desc* desc,
+                                     const hmgpu_export_scale* scale, const hmgpu_export_window windows[], void* const dst[3],
+                                     const int64_t pitch_bytes[3], const int64_t plane_stride_bytes[3], const int64_t batch_stride_bytes[3],
+                                     int on_stream, void* stream) {
+  if (!ctx || !pics || n < 1 || n > HMGPU_EXPORT_MAX_BATCH) return HMGPU_EINVAL;
+  PicData* p[HMGPU_EXPORT_MAX_BATCH];
+  for (int i = 0; i < n; i++) { if (!pics[i]) return HMGPU_EINVAL; p[i] = as_pic(pics[i]); }
+  return static_cast<Wrapper*>(ctx)->dec.export_loopfilter(n, p, desc, scale, windows, dst, pitch_bytes, plane_stride_bytes, batch_stride_bytes,
+                                                           on_stream, stream);
+}
 int hmdec_pictures_metrics(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_metrics_desc* desc, const void* const ref[3],
                            const int64_t ref_pitch_bytes[3], const int64_t ref_batch_stride_bytes[3], void* results,
                            int64_t results_batch_stride_bytes, int on_stream, void* stream) {

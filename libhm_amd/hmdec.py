@@ -110,6 +110,9 @@ def lib():
         L.hmdec_pictures_export_transform.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.TransformDesc),
                                                       C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                       C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_loopfilter.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.LoopfilterDesc),
+                                                       C.POINTER(abi.ExportScale), C.POINTER(abi.ExportWindow), C.POINTER(C.c_void_p),
+                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.hmdec_pictures_metrics_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.MetricsDesc),
@@ -307,6 +310,13 @@ class Picture:
         out = export_transform_batch([self], value, components, dtype, scale)
         return {k: t[0] for k, t in out.items()}
 
+    def loopfilter(self, form="grids", grids=("edge", "sao"), size=None, window=None, flip=False, dtype=None, scale=None, crop=None):
+        """export_loopfilter_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None.
+        window and flip belong to form="dense": with form="grids" they are refused (ValueError), as by Context.export_loopfilter"""
+        out = export_loopfilter_batch([self], form, grids, size, None if window is None else [window],
+                                      [flip] if flip or window is not None else None, dtype, scale, None, crop)
+        return {k: t[0] for k, t in out.items()}
+
     def metrics(self, ref, components=(0, 1, 2), ssim=True, crop=None):
         """metrics_batch of this picture alone: ref the planes [h_c, w_c] per component; the fields without the batch dimension"""
         out = metrics_batch([self], [None if t is None else t[None] for t in ref], components, ssim, crop)
@@ -379,6 +389,29 @@ def export_residual_batch(pictures, form="planes", components=(0, 1, 2), size=No
             raise HmgpuError(r, "hmdec_pictures_export_residual")
     return residual.export_residual(call, seq, dev, len(pictures) if n is None else n, form, components, size, windows, flip, dtype, scale, out,
                                     crop, enqueue)
+
+
+def export_loopfilter_batch(pictures, form="grids", grids=("edge", "sao"), size=None, windows=None, flip=None, dtype=None, scale=None,
+                            out=None, crop=None):
+    """The loop-filter decisions of up to 16 pictures a decoder has put out (fetched since the last push, one sequence, one GPU:
+    hmdec_pictures_export_loopfilter) as a dict of torch tensors with a leading batch dimension, written on
+    torch.cuda.current_stream(): libhm_amd.loopfilter describes the forms and keys.  crop: None = the whole coded picture for
+    form="grids" and the conformance window for form="dense" (what export_batch shows: the same windows, flips and size give aligned
+    pixels and edge strengths), "conformance", or (left, right, top, bottom)."""
+    from . import HmgpuError, loopfilter
+    pictures = list(pictures)
+    if not pictures:
+        raise ValueError("export_loopfilter_batch: no pictures")
+    first, seq, crop = _prologue(pictures, "export_loopfilter_batch", crop,
+                                 lambda: (0, 0, 0, 0) if loopfilter.form_code(form) == abi.LOOPFILTER_GRIDS else "conformance")
+    dev = _device(first, "export_loopfilter_batch")
+
+    def call(desc, sc, win, ptrs, pitches, pstrides, bstrides, st):
+        r = lib().hmdec_pictures_export_loopfilter(first.ctx, len(pictures), _handles(pictures), C.byref(desc), abi.ref(sc),
+                                                   abi.window_array(win), *loopfilter.c_args(ptrs, pitches, pstrides, bstrides), 1, abi.addr(st))
+        if r != 0:
+            raise HmgpuError(r, "hmdec_pictures_export_loopfilter")
+    return loopfilter.export_loopfilter(call, seq, dev, len(pictures), form, grids, size, windows, flip, dtype, scale, out, crop)
 
 
 def export_transform_batch(pictures, value="levels", components=(0, 1, 2), dtype=None, scale=None, out=None):
