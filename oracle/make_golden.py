@@ -8,6 +8,7 @@ oracle/_ref/libhmref.so = HM's TDecTop + TLibCommon to decode them and to answer
 Fixtures are DATA only (inputs + HM's outputs); no reference source text is stored.
 
   python oracle/make_golden.py streams     # P1/P2: picture-level dumps of small real streams
+  python oracle/make_golden.py streams NAME...   # only the named ones, e.g. one of STREAMS_INTRA (directional content for the intra search)
   python oracle/make_golden.py kats        # K1/K3/K4: kernel-level known-answer tests
   python oracle/make_golden.py dbk_kats    # the pel filters of the deblocking filter (a file of its own: dbk_kats.npz)
   python oracle/make_golden.py all
@@ -74,6 +75,89 @@ def synth_clip(w, h, frames, bit_depth, seed, novel=False, fade=False, noisy=Fal
         V = np.clip(np.round((0.5 + 0.2 * np.cos((yy[:ch, :cw] * (2 >> (1 - csy)) / 2.0 - 2 * f) / 17.0)
                               + 0.1 * ysub) * maxv), 0, maxv).astype(np.uint16)
         out.append((Y, U, V))
+    return out
+
+
+# intraPredAngle of the angular modes 2..34 (HEVC table 8-4)
+INTRA_ANGLES = [32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -17, -21, -26, -32, -26, -21, -17, -13, -9, -5, -2, 0, 2, 5, 9, 13, 17, 21, 26, 32]
+# what a region of intra_clip is made of, by its running number (7 and the 33 angular modes are coprime: over the fixtures every mode meets every kind)
+INTRA_KINDS = ["texture", "texture", "ramp", "texture", "texture", "kink", "texture"]
+
+
+def intra_region(rng, count, xx, yy, x0, y0, modes=None):
+    """one region of directional content, values 0..1: region number `count` gets the angular mode 2 + count % 33 (or the next of `modes`) and a signal that
+    is constant along that mode's prediction direction (luma g(t), t = y + x * angle / 32 for the horizontal modes 2..17 and
+    x + y * angle / 32 for the vertical modes 18..34; g = 0.5 + three sinusoids with seeded periods of 9..30 samples), so that HM's
+    RD search finds that mode at any block size.  Kinds: "texture" at full amplitude; "ramp": a plane a*x + b*y + c (second
+    difference 0: the bilinear test of strong intra smoothing, |p[0] + p[64] - 2 p[32]| < 1 << (bd - 5), passes along rows and
+    columns) under the texture at 1/30 of its amplitude; "kink": a triangle wave of 64 samples across, aligned to the 32-sample
+    grid, whose second difference over 64 samples is 1.5 times that threshold, under the same faint texture: references that
+    fail the test.  Returns (luma, chroma): chroma is None where it follows luma (the derived mode), else a pattern of its own by the
+    region number: horizontal, vertical or diagonal stripes, or flat with a slope (4:2:2 and 4:4:4 need it to leave the derived mode)"""
+    mode = 2 + count % 33 if modes is None else modes[count % len(modes)]
+    a = INTRA_ANGLES[mode - 2]
+    x, y = (xx - x0).astype(np.float64), (yy - y0).astype(np.float64)
+    t = y + x * a / 32.0 if mode < 18 else x + y * a / 32.0
+    tex = np.zeros_like(t)
+    for amp in (0.22, 0.12, 0.08):
+        tex += amp * np.sin(2 * np.pi * t / rng.uniform(9.0, 30.0) + rng.uniform(0, 2 * np.pi))
+    kind = INTRA_KINDS[count % len(INTRA_KINDS)]
+    cpat, chroma = count % 8, None
+    if cpat >= 4:
+        ct = [y, x, x + y, 0.01 * (x + 2 * y)][cpat - 4]
+        chroma = 0.5 + (0.2 * np.sin(2 * np.pi * ct / rng.uniform(9.0, 30.0) + rng.uniform(0, 2 * np.pi)) if cpat < 7 else ct - 0.3)
+    if kind == "texture":
+        return 0.5 + tex, chroma
+    thr = 1.0 / 32.0                                                   # 1 << (bd - 5) of full scale
+    sx, sy = rng.uniform(-0.0022, 0.0022, size=2)
+    hh, ww = t.shape
+    base = rng.uniform(0.35, 0.65) + sx * (x - ww / 2.0) + sy * (y - hh / 2.0)
+    if kind == "kink":
+        u = xx if count % 2 else yy                                     # (absolute position: the kinks sit on the 32-sample grid)
+        base = base + 0.75 * thr * np.abs(((u + 1) % 64) - 32.0) / 32.0
+    return base + tex / 30.0, chroma
+
+
+def intra_clip(w, h, frames, bit_depth, seed, csx=1, csy=1, region=(104, 64), start=None, modes=None, fresh=False):
+    """directional content for the intra fixtures: the picture cut into regions, each made for one angular mode (intra_region).
+    fresh: a clip for P pictures -- frame 0 repeated under new noise, with two new regions per frame at places no earlier frame
+    predicts (intra CUs among inter CUs).  start: the number of the first region (seeded if None); modes: the angular modes
+    the regions get in turn, where a fixture is to fill what others lack.  Cb = Y / 2 + max / 4 or the region's
+    own chroma pattern, subsampled; Cr = max - Cb.  Returns a list of (Y, U, V) uint16"""
+    rng = np.random.RandomState(seed)
+    maxv = (1 << bit_depth) - 1
+    rw, rh = region
+    cols, rows = -(-w // rw), -(-h // rh)
+    yy, xx = np.mgrid[0:h, 0:w]
+    count = int(rng.randint(0, 33 * len(INTRA_KINDS))) if start is None else start
+    out, img = [], None
+
+    def paint(sl, x0, y0):
+        luma, chroma = intra_region(rng, count, xx[sl], yy[sl], x0, y0, modes)
+        img[sl] = luma
+        cimg[sl] = 0.5 * luma + 0.25 if chroma is None else chroma
+
+    for f in range(frames):
+        if img is None or not fresh:
+            img, cimg = np.empty((h, w), dtype=np.float64), np.empty((h, w), dtype=np.float64)
+            for r in range(rows * cols):
+                x0, y0 = (r % cols) * rw, (r // cols) * rh
+                sl = (slice(y0, min(y0 + rh, h)), slice(x0, min(x0 + rw, w)))
+                paint(sl, x0, y0)
+                count += 1
+        else:
+            img, cimg = img.copy(), cimg.copy()
+            for j in range(2):                                          # 96 x 64 on the 32-sample grid, another place every frame
+                x0 = 32 * ((3 * f + 5 * j + 1) % max((w - 96) // 32, 1))
+                y0 = 32 * ((2 * f + 3 * j) % max((h - 64) // 32 + 1, 1))
+                sl = (slice(y0, min(y0 + 64, h)), slice(x0, min(x0 + 96, w)))
+                paint(sl, x0, y0)
+                count += 1
+        pic = img + 0.004 * rng.randn(h, w)
+        Y = np.clip(np.round(pic * maxv), 0, maxv).astype(np.uint16)
+        csub = (cimg + 0.5 * (pic - img))[::1 << csy, ::1 << csx]
+        U = np.clip(np.round(csub * maxv), 0, maxv).astype(np.uint16)
+        out.append((Y, U, (maxv - U).astype(np.uint16)))
     return out
 
 
@@ -167,12 +251,51 @@ STREAMS.update({
 })
 
 
+# Intra fixtures: intra_clip content, so that HM's encoder picks every luma mode at 16x16 and 32x32 and strong intra smoothing decides
+# samples at every bit depth (tests/test_intra_census_cpu.py counts what they hold).  LARGE: a minimum CU of 32 with one transform split,
+# every luma TU 32x32 or 16x16 (coded height a multiple of 32)
+LARGE = ["--MaxPartitionDepth=2", "--QuadtreeTUMaxDepthIntra=1"]
+STREAMS_INTRA = {
+    "imodes_large_main8_416x256": ("encoder_intra_main.cfg", 416, 256, 2, 8, 8, 32, LARGE),
+    "imodes_large_main12_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 1, 12, 12, 32, CF420 + LARGE),
+    # (a 4:4:4 picture of this size at 10 bits is most of the size a fixture may have: one frame per file)
+    "imodes_large_a_444_ccp_main10_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 1, 10, 10, 32, CF444 + LARGE),
+    "imodes_large_b_444_ccp_main10_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 1, 10, 10, 32, CF444 + LARGE),
+    "imodes_large_c_444_ccp_main10_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 1, 10, 10, 32, CF444 + LARGE),
+    "imodes_large_a_422_main8_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 2, 8, 8, 32, CF422 + LARGE),
+    "imodes_large_b_422_main8_416x256": ("encoder_intra_main_rext.cfg", 416, 256, 2, 8, 8, 32, CF422 + LARGE),
+    # every TU size: default depth, smaller regions
+    "imodes_all_main10_416x240": ("encoder_intra_main10.cfg", 416, 240, 2, 10, 10, 37, []),
+    # constrained intra prediction among inter CUs: one I picture, four P pictures with new regions in each
+    "imodes_cip_ldp_main10_224x128": ("encoder_lowdelay_P_main10.cfg", 224, 128, 5, 10, 10, 32, ["--ConstrainedIntraPred=1"] + LARGE),
+    # neither strong smoothing nor any reference smoothing
+    "imodes_nosmooth_422_main12_224x128": ("encoder_intra_main_rext.cfg", 224, 128, 2, 12, 12, 32,
+                                           CF422 + ["--ExtendedPrecision=0", "--StrongIntraSmoothing=0", "--IntraReferenceSmoothing=0"] + LARGE),
+}
+# arguments of intra_clip where they are not its defaults: region size, number of the first region, modes of the regions (the last file of a
+# format gets the modes that the census found missing in the others)
+INTRA_CLIP = {
+    "imodes_large_main12_416x256": dict(start=2),
+    "imodes_large_a_444_ccp_main10_416x256": dict(start=0),
+    "imodes_large_b_444_ccp_main10_416x256": dict(start=16),
+    "imodes_large_c_444_ccp_main10_416x256": dict(start=0, modes=[14, 18, 25, 5, 16, 7, 11, 21, 28]),
+    "imodes_large_a_422_main8_416x256": dict(start=0),
+    "imodes_large_b_422_main8_416x256": dict(start=32),
+    "imodes_all_main10_416x240": dict(region=(52, 32), start=2),
+    "imodes_cip_ldp_main10_224x128": dict(start=0, modes=[30, 14, 18, 25]),
+}
+STREAMS.update(STREAMS_INTRA)
+
+
 def encode(name, tmp):
     cfg, w, h, frames, ibd, bd, qp, extra = STREAMS[name]
     yuv = os.path.join(tmp, name + ".yuv")
     csx, csy = chroma_scale_of(name)
-    clip = synth_clip(w, h, frames, ibd, seed=0x484D + sum(map(ord, name)), novel="cip" in name, fade="wp" in name, noisy="pcm" in name or "lossless" in name,
-                      csx=csx, csy=csy)
+    if name in STREAMS_INTRA:
+        clip = intra_clip(w, h, frames, ibd, seed=0x484D + sum(map(ord, name)), csx=csx, csy=csy, fresh="cip" in name, **INTRA_CLIP.get(name, {}))
+    else:
+        clip = synth_clip(w, h, frames, ibd, seed=0x484D + sum(map(ord, name)), novel="cip" in name, fade="wp" in name, noisy="pcm" in name or "lossless" in name,
+                          csx=csx, csy=csy)
     mono = "mono" in name                                               # 4:0:0: luma only in, luma only out
     write_yuv(yuv, clip, ibd, mono)
     bs = os.path.join(tmp, name + ".bin")

@@ -37,6 +37,13 @@ LITE_CF = ["ldb_444_main10_208x120", "ldb_444_lossless_main8_208x120", "intra_44
 STREAMS_BD12 = ["ldb_main12_208x120", "intra_main12_208x120"]
 LITE_BD12 = ["ldb_ts32_main12_208x120", "ldb_wp_main12_208x120", "ldb_sl_main12_208x120", "intra_qp4_main12_208x120", "ldb_bd12_10_208x120",
              "ldb_444_ccp_main12_208x120", "ldb_422_main12_208x120"]
+# directional content made for HM's encoder to pick every luma intra mode at 16x16 and 32x32, with and without strong intra smoothing
+# (oracle/make_golden.py STREAMS_INTRA; tests/test_intra_census_cpu.py counts what they hold)
+STREAMS_INTRA = ["imodes_large_main8_416x256", "imodes_large_main12_416x256", "imodes_large_a_444_ccp_main10_416x256",
+                 "imodes_large_b_444_ccp_main10_416x256", "imodes_large_c_444_ccp_main10_416x256", "imodes_large_a_422_main8_416x256",
+                 "imodes_large_b_422_main8_416x256", "imodes_all_main10_416x240", "imodes_cip_ldp_main10_224x128",
+                 "imodes_nosmooth_422_main12_224x128"]
+STREAMS_INTRA_420 = [n for n in STREAMS_INTRA if "_444" not in n and "_422" not in n]
 STREAMS_EXT = STREAMS_CF + STREAMS_BD12          # beyond Main / Main10: other chroma formats, 12 bits
 LITE_EXT = LITE_CF + LITE_BD12
 # HM-encoded streams rewritten at the bit level (oracle/make_surgery.py) for syntax HM's encoder never writes; expected pictures = HM's own

@@ -10,7 +10,7 @@ from tests import synth
 
 pytestmark = pytest.mark.gpu
 
-FIXTURES_420 = gu.STREAMS + gu.STREAMS_BD12
+FIXTURES_420 = gu.STREAMS + gu.STREAMS_BD12 + gu.STREAMS_INTRA_420
 
 
 @pytest.mark.parametrize("name", FIXTURES_420)

@@ -25,9 +25,12 @@ def _run_stream(name, check):
 
 # 4:4:4 (with cross-component prediction) and 4:2:2 on the device
 STREAMS_444 = gu.STREAMS_EXT
+# HM's encoder on directional content: every luma mode at 16x16 and 32x32 in every chroma format, strong intra smoothing at 8, 10 and 12 bits
+# (tests/test_intra_census_cpu.py); the 4:2:2 ones reach k_intra_chroma_422
+STREAMS_INTRA = gu.STREAMS_INTRA
 
 
-@pytest.mark.parametrize("name", gu.STREAMS + STREAMS_444)
+@pytest.mark.parametrize("name", gu.STREAMS + STREAMS_444 + STREAMS_INTRA)
 def test_full_chain_matches_hm(name):
     """decompress_slice + filter_picture from the parsed data alone: every sample of every picture, inter and intra CUs
     (I pictures included), is produced on the GPU"""
@@ -76,7 +79,7 @@ def test_single_call_filter_picture_matches_hm(name):
     _run_stream(name, check2)
 
 
-@pytest.mark.parametrize("name", gu.STREAMS + STREAMS_444)
+@pytest.mark.parametrize("name", gu.STREAMS + STREAMS_444 + STREAMS_INTRA)
 def test_device_hash_and_packed_output_match_hm(name):
     """f-4: the decoded-picture-hash check (MD5, CRC, checksum) and the output packing (8/16-bit, conformance window) happen on the
     device; the hashes are the ones HM computed, the packed planes are HM's planes cropped (TVideoIOYuv.cpp:706-790)"""

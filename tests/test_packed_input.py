@@ -18,7 +18,7 @@ HEADER_WORDS = 8                      # magic, version, num_ctus, parts, groups,
 S_CTU, S_LSTART, S_LTAB, S_LDATA = 0, 16, 17, 18
 BENCH_SEED = 0x484D3136
 # the fixtures with HM's metadata in 4:0:0 / 4:2:0
-FIXTURES_420 = gu.STREAMS + gu.STREAMS_BD12
+FIXTURES_420 = gu.STREAMS + gu.STREAMS_BD12 + gu.STREAMS_INTRA_420
 COMPARED = ["depth", "part_size", "pred_mode", "qp", "tr_idx", "cbf_y", "cbf_u", "cbf_v", "ts_y", "ts_u", "ts_v", "mv0", "mv1",
             "ref_idx0", "ref_idx1", "intra_dir_l", "intra_dir_c", "bypass", "ipcm", "slice_idx", "tile_idx"]
 
