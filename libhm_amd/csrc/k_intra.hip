@@ -107,7 +107,11 @@ __device__ __attribute__((always_inline)) inline bool intra_avail(const PicDev& 
     return !cip || m_pred[nz] == HMGPU_MODE_INTRA;
   }
   if (nctu > ctu) return false;
-  const int k = nctu == ctu - 1 ? 0 : nctu == ctu - P.ctus_w - 1 ? 1 : nctu == ctu - P.ctus_w ? 2 : 3;
+  // which neighbour (0 left, 1 above-left, 2 above, 3 above-right), from the distance in CTU addresses.  In a picture one CTU wide
+  // ctu - 1 is the CTU above (there is none to the left); in one two CTUs wide it is the CTU to the left of the second column and the
+  // one above and to the right of the first: the neighbour's own column (0 or 1) tells them apart
+  const int d = ctu - nctu, w = P.ctus_w;
+  const int k = d == w ? 2 : d == w + 1 ? 1 : (d == 1 && !(w == 2 && (px >> P.log2ctu) == 1)) ? 0 : 3;
   if (!((nb_same >> k) & 1)) return false;
   if (cip && ldg(P.pred_mode + (size_t)nctu * P.parts + nz) != HMGPU_MODE_INTRA) return false;
   return true;

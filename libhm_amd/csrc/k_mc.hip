@@ -707,7 +707,9 @@ static void launch_mc(K kernel, McArgs& a, int max_ctus, hipStream_t s) {
   const dim3 grid((unsigned)nx, (unsigned)(kBandW * rows), (unsigned)((a.ctus_w + kBandW - 1) / kBandW));
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a);
 }
-// buffer-load windows while every byte of the slab of pictures has a 32-bit offset below kWinLimit (57 pictures of 3840x2160), plain addresses beyond
+// buffer-load windows while every byte of the slab of pictures has a 32-bit offset below kWinLimit, plain addresses beyond.  A picture
+// takes two plane sets (plane_set_bytes): 58.9 MB at 3840x2160 in 4:2:0, so kMaxPics of them, 3.77 GB, still take buffer loads; plain
+// addresses begin at 64 pictures of 4096x2368 (67.6 MB each, 4.33 GB) or 20 pictures of 7680x4320 (tests/test_gpu_geometry.py runs the former)
 static bool win_buf(const McArgs& a) { return a.slab_bytes < (uint64_t)kWinLimit; }
 void launch_mc_luma(McArgs& a, int max_ctus, bool wp, bool bi, hipStream_t s) {
   if (win_buf(a)) {
