@@ -736,6 +736,108 @@ hmgpu_status hmgpu_export_format_scale_taps(const hmgpu_seq_params* seq, const h
                                             const hmgpu_export_format* format, int32_t chroma, int32_t axis, int32_t max_taps,
                                             int32_t* first, int32_t* count, int16_t* weights);
 
+/* ------------------------------------------------------------------------------------------------ picture import
+ * The way in from device memory: planar or semi-planar YUV, or RGB as three planes or as packed pixels, in
+ * caller-owned memory of the context's GPU becomes the samples of up to HMGPU_EXPORT_MAX_BATCH acquired pictures -- one kernel
+ * launch per call, no host copy, no wait.  It is the inverse direction of the exports above and restates TVideoIOYuv::read
+ * (TVideoIOYuv.cpp:633-696) with readPlane (:227-349) and scalePlane (:70-87).  Integer arithmetic that tests/import_ref.py
+ * restates exactly.  The descriptor describes the SOURCE:
+ *
+ * layout / order   HMGPU_EXPORT_PLANAR (Y, Cb, Cr planes), HMGPU_EXPORT_SEMIPLANAR (Y + one interleaved CbCr plane) or
+ *                  HMGPU_EXPORT_RGB.  order = -1: planes (RGB: src[0] R, src[1] G, src[2] B); RGB with order = HMGPU_PIXEL_*: packed
+ *                  pixels in src[0], 3 or 4 elements each, the A element read over.  The YUV layouts need order = -1.
+ * width, height    the source size in luma samples, 0 = the picture's coded size; at most the coded size, and whole chroma samples
+ *                  of the source's and of the picture's chroma format.  Padding (readPlane :333-345): with the converted planes
+ *                  width x height (chroma: (width >> csx) x (height >> csy) of the PICTURE's format), sample (x, y) of the picture is
+ *                  converted sample (min(x, width - 1), min(y, height - 1)) of its plane: the last column repeated, then the last row.
+ * bit_depth[2]     the source depth D per channel type, luma / chroma (RGB: [0] for all three), 1 .. 16; 0 = the coding depth.
+ * bytes_per_sample, msb_aligned, sample_type
+ *                  HMGPU_SAMPLE_UINT: elements of 1 byte (D <= 8) or 2 bytes, LSB-aligned, or shifted left by 16 - D with
+ *                  msb_aligned (2 bytes only; the element is shifted right by 16 - D).  An element above 2^D - 1 is read as 2^D - 1.
+ *                  A float type (float16 / bfloat16 / float32 elements; msb_aligned 0, bytes_per_sample what the depths need, as in
+ *                  hmgpu_export_tensor): element x of plane (RGB: colour) k becomes the integer
+ *                    v = clip(rint(fadd(fmul((float)x, scale[k]), bias[k])), 0, 2^D - 1),  D = bit_depth[k ? 1 : 0] (RGB: [0])
+ *                  -- the product and the sum two separately rounded binary32 operations (never one fma), rint to nearest with
+ *                  ties to even, NaN gives 0, infinities the ends of the range.  numpy's float32 `*`, `+`, np.rint and np.clip
+ *                  restate it.  Float elements: RGB and planar only (semi-planar: HMGPU_EUNSUPPORTED).
+ * chroma_format    (YUV layouts) the source's format 0 .. 3, which may differ from the picture's; decided per axis by comparing
+ *                  the subsampling of both, C a chroma component of the source at the source depth, j the picture's chroma index:
+ *                    same on the axis                  the sample j itself
+ *                    the picture has more samples      sample j >> 1 (readPlane :324)
+ *                    the picture has fewer, DROP       sample 2j (:307; rows :286 / :297)
+ *                    the picture has fewer, LINEAR     the decimation taps of "format export" (loss, LINEAR) at the siting of `loc`,
+ *                                                      the picture's format in the place of the output's: c = (sum over the taps
+ *                                                      of wx * wy * C[iy][ix] + 8) >> 4, tap indices clamped to the source plane
+ *                  A 4:0:0 source gives Cb = Cr = 1 << (D - 1), D the source chroma depth (:263).  A 4:0:0 picture takes luma only.
+ * bit-depth rule   per channel type after the conversion, scalePlane with CLIP_TO_709_RANGE 0; s = coding depth - D:
+ *                    s >= 0: v << s;   s < 0: Clip3(0, 2^coding depth - 1, (v + (1 << (-s - 1))) >> -s)
+ * matrix, full_range (RGB)   H.273's Kr / Kb equations forward, codes 1, 5, 6, 9 as in hmgpu_export_desc; code 0: Y = G, Cb = B,
+ *                  Cr = R through the bit-depth rule, 4:4:4 pictures only (else HMGPU_EINVAL); other codes HMGPU_EUNSUPPORTED.
+ *                  With M = 2^D - 1, ys = 219 << (bdY - 8) and cs = 224 << (bdC - 8) (limited) or 2^bdY - 1 and 2^bdC - 1 (full),
+ *                  yo = 16 << (bdY - 8) or 0, co = 1 << (bdC - 1), Kg = 1 - Kr - Kb, rnd = round half away from zero, in double:
+ *                    yR = rnd(Kr * ys / M * 2^S)   yB = rnd(Kb * ys / M * 2^S)   yG = rnd(ys / M * 2^S) - yR - yB
+ *                    bB = rnd(cs / (2 M) * 2^S)    bR = rnd(-Kr / (1 - Kb) * cs / (2 M) * 2^S)    bG = -(bR + bB)
+ *                    rR = rnd(cs / (2 M) * 2^S)    rB = rnd(-Kb / (1 - Kr) * cs / (2 M) * 2^S)    rG = -(rR + rB)
+ *                    Y  = Clip3(0, 2^bdY - 1, ((yR * R + yG * G + yB * B + (1 << (S - 1))) >> S) + yo)
+ *                    Cb = Clip3(0, 2^bdC - 1, ((bR * R + bG * G + bB * B + (1 << (S - 1))) >> S) + co)     Cr likewise with r*
+ *                  (>> arithmetic), in 32-bit integers: S is the largest shift <= 30 for which, for every R, G, B in 0 .. M, no
+ *                  sum leaves the int32 range: M * max(sum of the positive, -sum of the negative coefficients of a row) +
+ *                  (1 << (S - 1)) <= 2^31 - 1.  S >= 17 always, so that M * (yR + yG + yB) is within 2^(S - 1) of ys * 2^S: black
+ *                  and peak white give yo and yo + ys exactly; the chroma rows sum to 0, so R = G = B gives Cb = Cr = co exactly;
+ *                  yR, yG, yB >= 0, so Y never falls when R, G or B rises.  Published in hmgpu_import_plan.coef:
+ *                    coef[0] S   coef[1] 1 << (S - 1)   coef[2] yo   coef[3] co   coef[4..6] yR yG yB   coef[7..9] bR bG bB
+ *                    coef[10..12] rR rG rB   coef[13] M   coef[14] 1: identity (matrix 0; coef[0..12] 0)   coef[15] 0
+ *                  Cb and Cr are formed at every pixel and brought to the picture's format as a 4:4:4 source's are (`down`, `loc`).
+ *
+ * The plan: planes read (planar 3, semi-planar 2, a 4:0:0 source or picture 1 for the YUV layouts; RGB planes 3, packed pixels 1),
+ * per plane width and height in samples (semi-planar CbCr: pairs; packed: pixels) and row_bytes, the least pitch.
+ * Plane k of picture i is read from src[k] + i * batch_stride_bytes[k], rows pitch_bytes[k] apart: one [N, 3, H, W] tensor as well
+ * as a tuple of planes.  Validation, in this order, everything before anything is enqueued, a refused call leaving every picture
+ * untouched:
+ *   1. the descriptor: NULL, a non-zero reserved word, layout, order, depths, container, a scale or bias that is not finite
+ *      (float types), the size rules, chroma_format outside 0 .. 3, loc outside 0 .. 5, full_range, matrix 0 outside 4:4:4: HMGPU_EINVAL;
+ *   2. an unknown matrix, `down` or sample type, semi-planar float elements: HMGPU_EUNSUPPORTED;
+ *   3. n outside 1 .. HMGPU_EXPORT_MAX_BATCH: HMGPU_EINVAL;
+ *   4. an invalid handle, or one handle twice (two writers): HMGPU_EINVAL;
+ *   5. the source: a plane of the plan missing, an address, pitch or batch stride that is no multiple of the element size, a pitch
+ *      below row_bytes, a batch stride below pitch * (height - 1) + row_bytes, a span of the n pictures that does not lie inside
+ *      one allocation of the context's device: HMGPU_EINVAL;
+ *   6. the stream, under the rules of hmgpu_picture_export.
+ * The source is only read.  The picture is left as hmgpu_picture_upload leaves it, without the wait: it lives in the reconstruction
+ * planes, carries no side information and no loop-filter record (the motion, residual, transform and loop-filter exports refuse
+ * it), and its margins are filled when it is first used as a reference.  The kernel writes the picture's samples and nothing else.
+ * Stream ordering is that of hmgpu_pictures_export, once per call: the kernel runs after all work enqueued for the pictures --
+ * kernels that still read their old contents included -- and after everything already on `stream`, and every later operation of the
+ * context waits for it.  Not accounted in hmgpu_stats. */
+typedef struct hmgpu_import_desc {
+  int32_t layout;              /* HMGPU_EXPORT_* of the source */
+  int32_t order;               /* -1: planes; RGB: or HMGPU_PIXEL_*, packed pixels */
+  int32_t width, height;       /* source size in luma samples; 0 = the coded size */
+  int32_t bit_depth[2];        /* source depth luma / chroma (RGB: [0]); 1 .. 16, 0 = the coding depth */
+  int32_t bytes_per_sample;    /* unsigned elements: 1 (depth <= 8) or 2 */
+  int32_t msb_aligned;         /* 2-byte unsigned elements shifted left by 16 - depth */
+  int32_t sample_type;         /* HMGPU_SAMPLE_* */
+  float scale[3], bias[3];     /* float types: per source plane (Y, Cb, Cr) or colour (R, G, B) */
+  int32_t chroma_format;       /* YUV layouts: the source's format 0 .. 3 */
+  int32_t down, loc;           /* HMGPU_DOWN_* where the picture has fewer chroma samples; chroma_sample_loc_type 0 .. 5 */
+  int32_t matrix, full_range;  /* RGB: matrix_coefficients and video_full_range_flag of the picture to make */
+  int32_t reserved[8];         /* 0 */
+} hmgpu_import_desc;
+typedef struct hmgpu_import_plan {
+  int32_t planes;              /* planes read: 1 .. 3 */
+  int32_t width[3], height[3]; /* per plane, in samples (semi-planar CbCr: pairs; packed pixels: pixels) */
+  int32_t row_bytes[3];        /* bytes of one row: the least pitch */
+  int32_t coef[16];            /* RGB: see above; else 0 */
+} hmgpu_import_plan;
+/* validates a descriptor against a sequence (steps 1 and 2) and reports what an import reads; host code, no device needed */
+hmgpu_status hmgpu_import_plan_for(const hmgpu_seq_params* seq, const hmgpu_import_desc* desc, hmgpu_import_plan* out);
+hmgpu_status hmgpu_pictures_import(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* desc,
+                                   const void* const src[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                   int32_t on_stream, void* stream);
+/* steps 1, 2, 3 and 5 of the validation and nothing else: nothing is enqueued and no picture is named */
+hmgpu_status hmgpu_import_source_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_import_desc* desc, const void* const src[3],
+                                       const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

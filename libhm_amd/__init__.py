@@ -239,6 +239,11 @@ def lib():
                                          C.POINTER(C.c_void_p)]
         L.hmgpu_decompress_pictures_packed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.PackedJob)]
         L.hmgpu_packed_wait.argtypes = [C.c_void_p, C.c_void_p]
+        L.hmgpu_import_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ImportDesc), C.POINTER(abi.ImportPlan)]
+        L.hmgpu_pictures_import.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ImportDesc), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_import_source_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ImportDesc), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_host_alloc.argtypes = [C.c_size_t]
         L.hmgpu_host_alloc.restype = C.c_void_p
         L.hmgpu_host_free.argtypes = [C.c_void_p]
@@ -280,6 +285,21 @@ def export_plan(seq, desc):
     st = lib().hmgpu_export_plan_for(C.byref(seq), C.byref(desc), C.byref(plan))
     if st != 0:
         raise HmgpuError(st, "hmgpu_export_plan_for")
+    return plan
+
+
+def import_status(seq, desc):
+    """(status, plan) of hmgpu_import_plan_for: host code, no GPU"""
+    plan = abi.ImportPlan()
+    return lib().hmgpu_import_plan_for(C.byref(seq), abi.ref(desc), C.byref(plan)), plan
+
+
+def import_plan(seq, desc=None, **kw):
+    """what a picture import reads for pictures of `seq` (hmgpu_import_plan_for: host code, no GPU); desc: an abi.ImportDesc, or
+    the keywords of abi.make_import_desc"""
+    st, plan = import_status(seq, abi.make_import_desc(**kw) if desc is None else desc)
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_import_plan_for")
     return plan
 
 
@@ -914,6 +934,49 @@ class Context:
                                      out, len(pics), dtype, mean, std, scale, bias, win, pixel=pixel, alpha=alpha, memory_format=memory_format,
                                      lut=lut, chroma=abi.chroma_stage(chroma, chroma_loc) if fmt is None else None,
                                      warp=abi.warp_stage(warp, size, filter, border, fill, len(pics)), format=fmt)
+
+    # ---- picture import
+    def import_into(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0):
+        """hmgpu_pictures_import from device memory the caller owns: plane k of picture i at ptrs[k] + i * bstrides[k] (bytes), rows
+        pitches[k] apart; desc: an abi.ImportDesc"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_import(self._h, len(pics), abi.handle_array(pics), abi.ref(desc), abi.ptr_array(ptrs),
+                                              abi.i64_array(pitches), abi.i64_array(bstrides), on_stream, abi.addr(stream)),
+                  "hmgpu_pictures_import")
+
+    def import_status(self, pics, desc, ptrs, pitches, bstrides, on_stream=0, stream=0):
+        """import_into, the status returned instead of raised"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_import(self._h, len(pics), abi.handle_array(pics), abi.ref(desc), abi.ptr_array(ptrs),
+                                           abi.i64_array(pitches), abi.i64_array(bstrides), on_stream, abi.addr(stream))
+
+    def import_source_status(self, n, desc, ptrs, pitches, bstrides):
+        """hmgpu_import_source_check: the status hmgpu_pictures_import would give this descriptor and source; enqueues nothing"""
+        return lib().hmgpu_import_source_check(self._h, n, abi.ref(desc), abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                               abi.i64_array(bstrides))
+
+    def import_batch(self, pics, tensors, layout="rgb", pixel=None, bit_depth=None, chroma_format=None, chroma_down="drop", chroma_loc=0,
+                     matrix=1, full_range=0, msb_aligned=False, scale=None, bias=None, mean=None, std=None, size=None, on_stream=True):
+        """torch tensors on this context's GPU become the samples of up to 16 acquired pictures (hmgpu_pictures_import: one launch,
+        no host copy, no wait), read on torch's current stream (on_stream) or on the context's own.  `tensors` is what export_batch
+        returns for the same keywords: layout "rgb" one [N, 3, H, W] tensor (channels-last strides go through the packed path) or
+        a tuple of three [N, H, W] planes, with pixel= ("rgb", "bgr", "rgba", "bgra", "argb", "abgr") one [N, H, W, C] tensor;
+        "planar" a tuple (Y, Cb, Cr) or one [N, 3, H, W] tensor of a 4:4:4 source; "semiplanar" (Y [N, H, W], CbCr [N, Hc, Wc, 2]).
+        The element type is the tensors' dtype: uint8, uint16 / int16, or float16 / bfloat16 / float32, which become integers of
+        bit_depth as rint(x * scale_k + bias_k) -- scale= / bias= triples, or the inverse of export_batch's mean= / std= convention,
+        scale_k = (2^D - 1) * std_k, bias_k = (2^D - 1) * mean_k (defaults: values in [0, 1]).  bit_depth: the source depth, an int
+        or (luma, chroma); None: the coding depths.  chroma_format ("400" / "420" / "422" / "444", 0 .. 3; None: the context's):
+        the source's format; where the picture has fewer chroma samples chroma_down decides, "drop" or "linear" at chroma_loc.
+        size (height, width): the source size when it is smaller than the coded picture (None: the tensors' own), the last column
+        and row repeated.  matrix / full_range: of the picture made from RGB.  The pictures are left as `upload` leaves them."""
+        from . import imports
+        imports.import_tensors(self, list(pics), tensors, layout, pixel, bit_depth, chroma_format, chroma_down, chroma_loc, matrix,
+                               full_range, msb_aligned, scale, bias, mean, std, size, on_stream)
+
+    def import_picture(self, pic, tensors, **kw):
+        """import_batch of one picture, its tensors without the batch dimension"""
+        from . import imports
+        self.import_batch([pic], imports.unsqueeze(tensors), **kw)
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

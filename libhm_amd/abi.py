@@ -227,6 +227,36 @@ def format_stage(chroma_format, chroma, chroma_down, chroma_loc, default_loc=0):
     return make_export_format(chroma_format, chroma, chroma_down, default_loc if chroma_loc is None else chroma_loc)
 
 
+class ImportDesc(C.Structure):
+    _fields_ = [("layout", C.c_int32), ("order", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32 * 2),
+                ("bytes_per_sample", C.c_int32), ("msb_aligned", C.c_int32), ("sample_type", C.c_int32), ("scale", C.c_float * 3),
+                ("bias", C.c_float * 3), ("chroma_format", C.c_int32), ("down", C.c_int32), ("loc", C.c_int32), ("matrix", C.c_int32),
+                ("full_range", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class ImportPlan(C.Structure):
+    _fields_ = [("planes", C.c_int32), ("width", C.c_int32 * 3), ("height", C.c_int32 * 3), ("row_bytes", C.c_int32 * 3),
+                ("coef", C.c_int32 * 16)]
+
+
+def make_import_desc(layout, order=-1, size=(0, 0), bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0, sample_type=SAMPLE_UINT,
+                     scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), chroma_format=1, down=DOWN_DROP, loc=0, matrix=1, full_range=0):
+    """the source of a picture import (hmgpu_import_desc).  size: (width, height) in luma samples, 0 = the coded size; bit_depth: an
+    int or (luma, chroma), 0 = the coding depth; chroma_format: 0 .. 3 or its name; down: DOWN_* or its name"""
+    d = ImportDesc()
+    d.layout, d.order = int(layout), int(order)
+    d.width, d.height = int(size[0]), int(size[1])
+    bd = (bit_depth, bit_depth) if isinstance(bit_depth, int) else tuple(bit_depth)
+    d.bit_depth[0], d.bit_depth[1] = bd
+    d.bytes_per_sample, d.msb_aligned, d.sample_type = int(bytes_per_sample), int(msb_aligned), int(sample_type)
+    for k in range(3):
+        d.scale[k], d.bias[k] = float(scale[k]), float(bias[k])
+    d.chroma_format = int(CHROMA_FORMATS.get(chroma_format, chroma_format))
+    d.down, d.loc = int(DOWN_FILTERS.get(down, down)), int(loc)
+    d.matrix, d.full_range = int(matrix), int(full_range)
+    return d
+
+
 WARP_NEAREST, WARP_BILINEAR = 0, 1
 WARP_EDGE, WARP_FILL = 0, 1
 WARP_FILTERS = {"nearest": WARP_NEAREST, "bilinear": WARP_BILINEAR}

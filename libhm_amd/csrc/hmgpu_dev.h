@@ -769,6 +769,36 @@ struct HistogramArgs {
   int32_t coef[16], sh[2], maxv[2];       // maxRGB: hmgpu_export_plan.coef and the depth rule of the identity, as ExportArgs
 };
 void launch_histogram(const HistogramArgs& a, hipStream_t s);
+// picture import (k_import.hip, hmgpu_pictures_import; include/hmgpu.h "picture import"): the way in from device memory.  A chroma
+// sample (jx, jy) of the picture is clamped to the converted source (ccw x cch, the padding rule) and then read through up to 3 x 3
+// taps of the source's chroma plane (scw x sch; RGB: Cb / Cr at every pixel): column ((jx << hl) >> hr) + h0 + t with weight hw[t],
+// rows likewise, weights in quarters, (sum + 8) >> 4 -- the sample itself, sample j >> 1, sample 2j and the decimation taps of the
+// format export are all of this shape.
+struct ImportArgs {
+  int16_t* y[kMaxExportBatch];     // per picture: luma sample (0, 0) of the reconstruction planes
+  int16_t* c[kMaxExportBatch];     // Cb of chroma sample (0, 0) in the pair plane (Cr one element on)
+  int32_t pitch_y, pitch_c;        // int16 elements
+  int32_t n;                       // pictures
+  int32_t layout, elem;            // HMGPU_EXPORT_* of the source; element: 0 uint8, 1 uint16, 2 float16, 3 bfloat16, 4 float32
+  int32_t nch, pos[3];             // RGB: 0 three planes, else 3 / 4 elements per packed pixel and where R, G, B stand in it
+  int32_t w, h, sw, sh;            // the coded picture and the source, luma samples
+  int32_t mono, psx, psy;          // the picture: no chroma (then psx = psy = 0); chroma subsampling
+  int32_t smono, same, drop;       // the source: 4:0:0; its chroma planes have the picture's shape; no tap but one of weight 4 per axis
+  int32_t ccw, cch, scw, sch;      // converted chroma size (sw >> psx, sh >> psy); the source's chroma plane
+  int32_t hl, hr, h0, hw[3];       // horizontal taps
+  int32_t vl, vr, v0, vw[3];       // vertical taps
+  int32_t dsh[2], maxv[2];         // bit-depth rule per channel type: coding - source depth, 2^coding - 1
+  int32_t smax[2], msb[2];        // 2^source depth - 1; container shift (msb_aligned: 16 - source depth)
+  int32_t cconst;                  // 4:0:0 source: 1 << (source chroma depth - 1)
+  uint32_t vec;                    // bit k: rows of source plane k start on multiples of eight elements; bit 8: rows of both
+                                   // destination planes on multiples of 16 bytes
+  const uint8_t* src[3];
+  int64_t pitch[3];                // bytes
+  int64_t bstride[3];              // bytes between the planes of consecutive pictures
+  float scale[3], bias[3];         // float elements: per source plane / colour
+  int32_t coef[16];                // hmgpu_import_plan.coef
+};
+void launch_import(const ImportArgs& a, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter
 // cell, chroma deblocking on the format's own grid; fmt = chroma_format_idc
 void launch_ccp(const PicDev* pics, const Batch& b, int max_ctus, hipStream_t s);
