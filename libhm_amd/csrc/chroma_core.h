@@ -1,6 +1,7 @@
 // chroma_core.h -- the chroma stage of the RGB exports (hmgpu_pictures_export_chroma, include/hmgpu.h "chroma export"): Cb and Cr
-// linearly interpolated to the luma grid at the signalled chroma sample location, in the chroma fetch of k_export.hip,
-// k_export_px.hip and k_export_scale.hip, before the matrix.  Integer arithmetic, exact: two taps per axis with weights in quarters,
+// linearly interpolated to the luma grid at the signalled chroma sample location, before the matrix: the arithmetic of the stage.  The fetch
+// that feeds it is export_core.h's export_chroma_sited (k_export.hip, k_export_fmt.hip's kFmtUp); k_export_scale.hip keeps its own 8-sample
+// text of that fetch, and k_export_warp.hip's tap gathers its 2 x 2 pairs itself with these rows and weights.  Integer arithmetic, exact: two taps per axis with weights in quarters,
 //   c' = (sum over the 2x2 taps of wx * wy * C[iy][ix] + 8) >> 4
 // The two rows are combined first (a lane's rows are the same for all its columns), then the columns; the sum is the same integer.
 // Tap indices are clamped to the decoded plane: the rows as indices before the loads (a row index is uniform per workgroup in the
@@ -11,18 +12,7 @@
 #pragma once
 #include "hmgpu_dev.h"
 
-#include <type_traits>
-
 namespace hmgpu {
-
-// the kernels' optional stages travel as a parameter pack behind their first argument (ChromaSite, ColourLut, in that order):
-// whether the pack holds a T, and that T
-template <class T, class... X> constexpr bool pack_has = (std::is_same_v<T, X> || ...);
-template <class T, class U, class... X>
-__device__ inline const T& pack_get(const U& u, const X&... x) {
-  if constexpr (std::is_same_v<T, U>) return u;
-  else return pack_get<T>(x...);
-}
 
 // the two chroma rows of luma row y (plane coordinates) and the weight of the first; the second has 4 - w
 __device__ inline void chroma_rows(const ChromaSite& s, int y, int csy, int* ia, int* ib, int* w) {

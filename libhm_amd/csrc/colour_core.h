@@ -1,6 +1,8 @@
 // colour_core.h -- the colour stage of the RGB exports (hmgpu_pictures_export_colour, include/hmgpu.h "colour export"): a lane's four
-// (R, G, B) triples through the per-channel shaper and the 3D lattice with tetrahedral interpolation, in the epilogues of k_export.hip,
-// k_export_px.hip and k_export_scale.hip, between the final clip and the store.  Integer arithmetic only, unsigned 32-bit; the
+// (R, G, B) triples through the per-channel shaper and the 3D lattice with tetrahedral interpolation, between the final clip and the
+// store: the first half of export_core.h's export_store_rgb, the epilogue of k_export.hip, and of the epilogues of k_export_scale.hip and
+// k_export_warp.hip.
+// Only the LUT stage lives here; the conversion to R'G'B' is export_core.h's export_rgb.  Integer arithmetic only, unsigned 32-bit; the
 // table's nodes are 8 bytes {R | G << 16, B} in device memory, so a vertex is one load, and the sixteen vertex loads of a lane's four
 // pixels are issued before the first is consumed.  Never indexes past node L - 1: the cell index is at most L - 2
 // (u <= 65535, so u * (L - 1) >> 16 <= L - 2).
@@ -8,28 +10,6 @@
 #include "hmgpu_dev.h"
 
 namespace hmgpu {
-
-// One sample's R'G'B' by the rule of the RGB exports (k_export.hip: the integer matrix of hmgpu_export_plan.coef, or the identity's
-// bit-depth rule per channel type when coef[10] is set), for callers that hold the plan's constants without an ExportArgs
-// (k_histogram.hip).  sh / maxv: output depth minus coding depth, and 2^depth - 1, per channel type.
-__device__ inline int colour_depth_conv(int v, int sh, int maxv) {
-  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
-}
-__device__ inline void colour_rgb(const int32_t* coef, const int32_t* sh, const int32_t* maxv, int y, int u, int v, uint32_t* R, uint32_t* G,
-                                  uint32_t* B) {
-  if (coef[10]) {
-    *G = (uint32_t)colour_depth_conv(y, sh[0], maxv[0]);
-    *B = (uint32_t)colour_depth_conv(u, sh[1], maxv[1]);
-    *R = (uint32_t)colour_depth_conv(v, sh[1], maxv[1]);
-  } else {
-    const int S = coef[0], M = coef[9];
-    const int t = coef[4] * (y - coef[2]) + coef[1];
-    const int cu = u - coef[3], cv = v - coef[3];
-    *R = (uint32_t)min(M, max(0, (t + coef[5] * cv) >> S));
-    *G = (uint32_t)min(M, max(0, (t + coef[6] * cu + coef[7] * cv) >> S));
-    *B = (uint32_t)min(M, max(0, (t + coef[8] * cu) >> S));
-  }
-}
 
 // position 0 .. 65535 of the code value v of channel c.  A lane converts four columns even where the row ends sooner; what it read
 // beyond the row is margin of any content, so v is bounded here before it indexes anything.

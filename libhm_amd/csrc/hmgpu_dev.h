@@ -390,7 +390,7 @@ __device__ inline void export_store_pairs(uint8_t* row, int x, int cw, const uin
   export_store4<ELEM>(d, r, min(4, 2 * n), vv, msb, 0.f, 0.f);
   if (n > 2) export_store4<ELEM>(d + 4 * elem_bytes<ELEM>(), r + 4, 2 * n - 4, vv, msb, 0.f, 0.f);
 }
-// packed pixels (k_export_px.hip, k_export_scale.hip; include/hmgpu.h "packed pixel export"): the channel order as two launch-uniform
+// packed pixels (k_export.hip, k_export_scale.hip, k_export_warp.hip; include/hmgpu.h "packed pixel export"): the channel order as two launch-uniform
 // flags, the A element's bits, and whether dst, the pitch and the batch stride are multiples of 4 bytes (dword stores possible)
 struct PxOrder {
   int32_t swap;                    // B first, R third (BGR, BGRA, ABGR)
@@ -477,19 +477,12 @@ struct ExportArgs {
   float scale[3], bias[3];         // float elements: per output plane
   int32_t coef[16];                // hmgpu_export_plan.coef
 };
-void launch_export(const ExportArgs& a, hipStream_t s);
-// the RGB export of `a` as packed pixels (k_export_px.hip): one destination, dst[0] / pitch[0] / bstride[0]; a.vec: the loads only;
-// nch: 3 or 4 elements per pixel
-void launch_export_px(const ExportArgs& a, const PxOrder& po, int nch, hipStream_t s);
 // the colour stage of the RGB exports (colour_core.h, hmgpu_pictures_export_colour): one table in device memory of the context
 struct ColourLut {
   const uint16_t* shaper;          // null, or [3][2^depth] positions 0 .. 65535 (size 0: output code values)
   const u32x2* nodes;              // null (size 0), or [size^3] nodes {R | G << 16, B}, R fastest
   int32_t size, depth;             // nodes per axis (0, 2 .. 65); the depth of the code values in and out
 };
-// the RGB layout of `a` with the colour stage: planes (nch 0, k_export.hip) or packed pixels (nch 3 / 4, k_export_px.hip)
-void launch_export_colour(const ExportArgs& a, const ColourLut& lut, hipStream_t s);
-void launch_export_px_colour(const ExportArgs& a, const PxOrder& po, const ColourLut& lut, int nch, hipStream_t s);
 // the chroma stage of the RGB exports (chroma_core.h, hmgpu_pictures_export_chroma) for 4:2:0 and 4:2:2: the weights of the signalled
 // sample location in quarters, and what clamping a tap to the decoded plane needs
 struct ChromaSite {
@@ -498,9 +491,9 @@ struct ChromaSite {
   int32_t wc, hc;                  // the decoded chroma plane, samples
   int16_t x0[kMaxExportBatch], y0[kMaxExportBatch];   // unscaled: per picture, the chroma sample ExportArgs::c points at
 };
-// the RGB layout of `a` with the chroma stage, and with the colour stage as well where lut is not null
-void launch_export_chroma(const ExportArgs& a, const ChromaSite& cs, const ColourLut* lut, hipStream_t s);
-void launch_export_px_chroma(const ExportArgs& a, const PxOrder& po, const ChromaSite& cs, const ColourLut* lut, int nch, hipStream_t s);
+// The export of `a` (k_export.hip).  po: null, or (RGB) the channel order of packed pixels of nch (3 / 4) elements, written to the one
+// destination dst[0] / pitch[0] / bstride[0] (a.vec then speaks of the loads only); cs / lut: null, or (RGB) the chroma / colour stage
+void launch_export(const ExportArgs& a, const PxOrder* po, int nch, const ChromaSite* cs, const ColourLut* lut, hipStream_t s);
 // format export (k_export_fmt.hip, hmgpu_pictures_export_format; include/hmgpu.h "format export"): the chroma rows of the YUV layouts
 // read the pair plane of the source format and write one of another.  ExportArgs as launch_export takes it, with cw / ch the OUTPUT
 // chroma size (csx / csy stay the source's).  A class per shape of the loads; the host's weights make REPLICATE and DROP exact in the
@@ -558,12 +551,9 @@ struct ScaleArgs {
   int32_t coef[16];                // hmgpu_export_plan.coef
   PxOrder px;                      // packed pixels (nch below): dst[0] / pitch[0] / bstride[0] the one destination, vec = px.vst
 };
-// n pictures; elem: kElem*; nch: 0, or (RGB) 3 / 4 elements per packed pixel
-void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch = 0);
-// the RGB layout with the colour stage (ColourLut) in the epilogue
-void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch);
-// the RGB layout with the chroma stage (ChromaSite) in the stage step, and the colour stage as well where lut is not null
-void launch_export_scaled_chroma(const ScaleArgs& a, const ChromaSite& cs, const ColourLut* lut, int elem, int n, hipStream_t s, int nch);
+// n pictures; elem: kElem*; nch: 0, or (RGB) 3 / 4 elements per packed pixel; cs / lut: null, or (RGB) the chroma stage in the stage
+// step / the colour stage in the epilogue
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, int nch, const ChromaSite* cs, const ColourLut* lut, hipStream_t s);
 // affine warp export (k_export_warp.hip, hmgpu_pictures_export_warp; include/hmgpu.h "affine warp export"): the RGB layout, planes or
 // packed pixels, each picture through its own inverse map.  Per picture (grid y), in device memory of the window ring: the Q16 map
 // and the source window in plane coordinates
@@ -588,7 +578,7 @@ struct WarpArgs {
   PxOrder px;                      // packed pixels (nch below): dst[0] / pitch[0] / bstride[0] the one destination
 };
 // n pictures; elem: kElem*; nch: 0, or 3 / 4 elements per packed pixel; cs: null, or the chroma stage; lut: null, or the colour stage
-void launch_export_warp(const WarpArgs& a, const ChromaSite* cs, const ColourLut* lut, int elem, int n, int nch, hipStream_t s);
+void launch_export_warp(const WarpArgs& a, int elem, int n, int nch, const ChromaSite* cs, const ColourLut* lut, hipStream_t s);
 // motion and block export (k_motion.hip, hmgpu_pictures_export_motion): everything by value, validated on the host.  The raw HM
 // arrays of every picture of the call (PicDev's own pointers: fixed for the life of a picture) and, per slot, the source window of the
 // dense form.  Destination slots: 0 / 1 the vectors, 2 ref_poc, 3 block (HMGPU_MOTION_DST_*); a null destination is not written.

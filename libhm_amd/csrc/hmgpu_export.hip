@@ -3,7 +3,7 @@
 // rules of the warp; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
 // destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps) (k_export.hip,
-// k_export_px.hip, k_export_scale.hip, k_export_warp.hip, k_export_fmt.hip).  Also the rules and the stream bracket that the
+// k_export_scale.hip, k_export_warp.hip, k_export_fmt.hip).  Also the rules and the stream bracket that the
 // side-information exports (hmgpu_side.hip) and the picture analyses (hmgpu_analysis.hip) take from here: hmgpu_host.h.
 #include "hmgpu_host.h"
 
@@ -1259,7 +1259,7 @@ static void launch_unscaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const Ex
   export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
   if (r.fmt_out >= 0 && r.fmt_out != c->seq.chroma_format) {
     // a format export that converts: Y alone through the 4:0:0 path of k_export, else the chroma rows of the output format
-    if (r.fmt_out == 0) { a.mono = 1; launch_export(a, hs); return; }
+    if (r.fmt_out == 0) { a.mono = 1; launch_export(a, nullptr, 0, nullptr, nullptr, hs); return; }
     FmtConv f;
     fmt_conv(c->seq, *q.fmt, a.sh[1] + c->seq.bit_depth_chroma, &f);
     for (int i = 0; i < n; i++) {
@@ -1270,17 +1270,7 @@ static void launch_unscaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const Ex
     launch_export_fmt(a, f, hs);
     return;
   }
-  if (site) {
-    if (q.px) launch_export_px_chroma(a, r.po, *site, r.cs ? &r.cs->lut : nullptr, r.nch, hs);
-    else launch_export_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, hs);
-  } else if (r.cs) {
-    if (q.px) launch_export_px_colour(a, r.po, r.cs->lut, r.nch, hs);
-    else launch_export_colour(a, r.cs->lut, hs);
-  } else if (q.px) {
-    launch_export_px(a, r.po, r.nch, hs);
-  } else {
-    launch_export(a, hs);
-  }
+  launch_export(a, q.px ? &r.po : nullptr, r.nch, site, r.cs ? &r.cs->lut : nullptr, hs);
 }
 
 static hmgpu_status launch_scaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const ExportReq& q, const ExportCall& r, const ChromaSite* site,
@@ -1325,9 +1315,7 @@ static hmgpu_status launch_scaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, co
   a.vec = q.px ? (int)r.po.vst : r.vec ? 1 : 0;
   if (q.px) a.px = r.po;
   export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
-  if (site) launch_export_scaled_chroma(a, *site, r.cs ? &r.cs->lut : nullptr, r.elem, n, hs, r.nch);
-  else if (r.cs) launch_export_scaled_colour(a, r.cs->lut, r.elem, n, hs, r.nch);
-  else launch_export_scaled(a, d->layout, r.elem, n, hs, r.nch);
+  launch_export_scaled(a, d->layout, r.elem, n, r.nch, site, r.cs ? &r.cs->lut : nullptr, hs);
   if (r.fmt_out > 0 && c->seq.chroma_format == 0) {
     // a format export of a 4:0:0 picture with chroma planes: nothing to resample, the constant through k_export_fmt's chroma rows
     ExportArgs e;
@@ -1375,7 +1363,7 @@ static hmgpu_status launch_warp(hmgpu_ctx* c, int n, const hmgpu_pic* pics, cons
   a.vec = q.px ? (int)r.po.vst : r.vec ? 1 : 0;
   if (q.px) a.px = r.po;
   export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
-  launch_export_warp(a, site, r.cs ? &r.cs->lut : nullptr, r.elem, n, r.nch, hs);
+  launch_export_warp(a, r.elem, n, r.nch, site, r.cs ? &r.cs->lut : nullptr, hs);
   *tables = wb;
   return HMGPU_OK;
 }

@@ -3,7 +3,7 @@
 // TVideoIOYuv.cpp:362-483, and its siting-aware linear forms).
 // k_export's shape: memory-bound, one lane per 4 output samples of a row (luma) or 4 output CbCr pairs (chroma), rows along the
 // grid's y -- the luma rows, then the chroma rows of the OUTPUT format --, the pictures of a batch along z with their own origin,
-// alignment and mirror flag, no LDS.  Luma rows are k_export's (export_core.h).  A chroma row reads the pair plane of the source
+// alignment and mirror flag, no LDS.  Luma rows are k_export's, and kFmtUp's fetch is the RGB exports' sited chroma (export_core.h).  A chroma row reads the pair plane of the source
 // format: its one to three source rows are chosen and clamped to the decoded plane before the loads (uniform per workgroup; a row
 // without weight is not loaded), every load's address is known before the first load is consumed, and columns are clamped as selects
 // behind whole-group loads (chroma_core.h's argument: a column outside the plane is read from the plane's margin, whatever it holds,
@@ -14,7 +14,6 @@
 // and DROP are the same instances with a single weight 4 per axis, which the rounding returns exactly.
 #include "hmgpu_dev.h"
 #include "export_core.h"
-#include "chroma_core.h"
 
 namespace hmgpu {
 
@@ -66,20 +65,10 @@ __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const Fm
     fmt_rows(f, (f.vgain ? y0 << 1 : f.vloss ? y0 >> 1 : y0) + rc, ri, rw);
     int c[8];
     if constexpr (CLS == kFmtUp) {
-      // source pairs J - 1 .. J + 2 (J = the pair of output pair x) of two rows, six loads none of which waits for another
-      const int16_t* pa = ac + (ptrdiff_t)(ri[0] - y0) * a.pitch_c + kCStep * (x >> 1);
-      const int16_t* pb = ac + (ptrdiff_t)(ri[1] - y0) * a.pitch_c + kCStep * (x >> 1);
-      int ma[4], mb[4], ua[4], ub[4], va[4], vb[4], u[4], v[4];
-      load4(pa, vec, ma);
-      load4(pb, vec, mb);
-      chroma_pair(pa - kCStep, &ua[0], &va[0]);
-      chroma_pair(pb - kCStep, &ub[0], &vb[0]);
-      chroma_pair(pa + 2 * kCStep, &ua[3], &va[3]);
-      chroma_pair(pb + 2 * kCStep, &ub[3], &vb[3]);
-      ua[1] = ma[0]; va[1] = ma[1]; ua[2] = ma[2]; va[2] = ma[3];
-      ub[1] = mb[0]; vb[1] = mb[1]; ub[2] = mb[2]; vb[2] = mb[3];
-      chroma_line<2>(f.cs, x0 + (x >> 1), rw[0], ua, ub, u);
-      chroma_line<2>(f.cs, x0 + (x >> 1), rw[0], va, vb, v);
+      // source pairs J - 1 .. J + 2 (J = the pair of output pair x) of two rows: the sited fetch of four luma samples
+      int u[4], v[4];
+      export_chroma_sited<4>(f.cs, ac + (ptrdiff_t)(ri[0] - y0) * a.pitch_c + kCStep * (x >> 1), ac + (ptrdiff_t)(ri[1] - y0) * a.pitch_c + kCStep * (x >> 1),
+                             x0 + (x >> 1), rw[0], vec, u, v);
       for (int i = 0; i < 4; i++) { c[2 * i] = u[i]; c[2 * i + 1] = v[i]; }
     } else if constexpr (CLS == kFmtVert) {
       // the group's own four pairs on every row that has a weight
@@ -119,20 +108,9 @@ __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const Fm
 void launch_export_fmt(const ExportArgs& a, const FmtConv& f, hipStream_t s) {
   const int groups = (std::max(a.w, a.cw) + 3) / 4;
   const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)(a.h + a.ch), (unsigned)a.n), block(256);
-#define HMGPU_EXPORT_FMT_CASE(L, E, K) \
-  if (a.layout == L && a.elem == E && f.cls == K) hipLaunchKernelGGL((k_export_fmt<L, E, K>), grid, block, 0, s, a, f);
-#define HMGPU_EXPORT_FMT_CLASSES(L, E) \
-  HMGPU_EXPORT_FMT_CASE(L, E, kFmtConst) HMGPU_EXPORT_FMT_CASE(L, E, kFmtUp) HMGPU_EXPORT_FMT_CASE(L, E, kFmtVert) HMGPU_EXPORT_FMT_CASE(L, E, kFmtDown)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemU8)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemU16)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_SEMIPLANAR, kElemU8)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_SEMIPLANAR, kElemU16)
-  // float elements: the planar layout (the host refuses semi-planar)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemF16)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemBF16)
-  HMGPU_EXPORT_FMT_CLASSES(HMGPU_EXPORT_PLANAR, kElemF32)
-#undef HMGPU_EXPORT_FMT_CLASSES
-#undef HMGPU_EXPORT_FMT_CASE
+  export_yuv_instance(a.layout, a.elem, [&](auto l, auto e) {
+    export_pick<kFmtConst, kFmtUp, kFmtVert, kFmtDown>(f.cls, [&](auto k) { hipLaunchKernelGGL((k_export_fmt<l(), e(), k()>), grid, block, 0, s, a, f); });
+  });
 }
 
 }  // namespace hmgpu

@@ -18,23 +18,21 @@
 // (hmgpu_pictures_export_colour): k_export_scale_colour, the RGB layout with colour_core.h's colour_map4 between the clip and the store.
 // The chroma stage (hmgpu_pictures_export_chroma): k_export_scale_chroma, whose stage step interpolates the chroma of a 16-byte group
 // (chroma_core.h) where the others replicate it; one pair left and right of the group's four come from neighbouring groups' lines.
+// The depth rule and the 16-byte unpack are export_core.h's, and so is the dispatch of launch_export_scaled.  The stage step keeps its
+// own 8-sample text of the chroma fetches, the conversion and the store choice, and the three __global__ wrappers stay: with those
+// taken from export_core.h (export_chroma_replicated<8> / export_chroma_sited<8>, export_rgb<8>, export_store_rgb, one __global__ over
+// a stage pack) no instance had scratch or lost occupancy, but scaled 1080p bicubic uint8 planes measured 0.2 - 0.3 % slower than the
+// parent in two jobs (profiles/EXPERIMENTS.md), and sharing the fetches alone already changes 15 to 45 instances' instructions.  As
+// it stands every instance's instructions are those from before the shared core.  A change to the matrix or to the sited fetch is
+// made here as well as in export_core.h.
 // Source loads may reach up to 7 samples left and right of the crop window (16-byte groups): the planes keep 64 or more samples of
 // margin on both sides, and the tables never point at them.
 #include "hmgpu_dev.h"
-#include "colour_core.h"
-#include "chroma_core.h"
+#include "export_core.h"
 
 namespace hmgpu {
 
 namespace {
-
-__device__ inline int depth_conv(int v, int sh, int maxv) {
-  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
-}
-
-__device__ inline void unpack8(const u32x4 w, int v[8]) {
-  for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(w[i] & 0xffff); v[2 * i + 1] = (int16_t)(w[i] >> 16); }
-}
 
 // C channels: 3 = RGB from the luma grid, 1 = Y, 2 = Cb and Cr from the pair plane; NCH: 0, or (C = 3) the elements of a packed pixel;
 // COL (C = 3): the colour stage (colour_core.h) between the final clip and the store; CHR (C = 3): the chroma stage (chroma_core.h)
@@ -247,66 +245,25 @@ __global__ void __launch_bounds__(256) k_export_scale_chroma(const ScaleArgs a, 
   scale_tile<HMGPU_EXPORT_RGB, ELEM, 3, NCH, COL, true>(a, k, blockIdx.x, lds, &lut, &site);
 }
 
-void launch_export_scaled_chroma(const ScaleArgs& a, const ChromaSite& cs, const ColourLut* lut, int elem, int n, hipStream_t s, int nch) {
-  const dim3 grid((unsigned)a.cls[0].blocks, (unsigned)n), block(256);
-  const ColourLut none = {};
-#define HMGPU_SCALE_CHROMA_CASE(E, N) \
-  if (elem == E && nch == N && !lut) hipLaunchKernelGGL((k_export_scale_chroma<E, N, false>), grid, block, 0, s, a, cs, none); \
-  if (elem == E && nch == N && lut) hipLaunchKernelGGL((k_export_scale_chroma<E, N, true>), grid, block, 0, s, a, cs, *lut);
-#define HMGPU_SCALE_CHROMA_ELEM(E) HMGPU_SCALE_CHROMA_CASE(E, 0) HMGPU_SCALE_CHROMA_CASE(E, 3) HMGPU_SCALE_CHROMA_CASE(E, 4)
-  HMGPU_SCALE_CHROMA_ELEM(kElemU8)
-  HMGPU_SCALE_CHROMA_ELEM(kElemU16)
-  HMGPU_SCALE_CHROMA_ELEM(kElemF16)
-  HMGPU_SCALE_CHROMA_ELEM(kElemBF16)
-  HMGPU_SCALE_CHROMA_ELEM(kElemF32)
-#undef HMGPU_SCALE_CHROMA_ELEM
-#undef HMGPU_SCALE_CHROMA_CASE
-}
-
-void launch_export_scaled_colour(const ScaleArgs& a, const ColourLut& lut, int elem, int n, hipStream_t s, int nch) {
-  const dim3 grid((unsigned)a.cls[0].blocks, (unsigned)n), block(256);
-#define HMGPU_SCALE_COLOUR_CASE(E) \
-  if (elem == E && nch == 0) hipLaunchKernelGGL((k_export_scale_colour<E, 0>), grid, block, 0, s, a, lut); \
-  if (elem == E && nch == 3) hipLaunchKernelGGL((k_export_scale_colour<E, 3>), grid, block, 0, s, a, lut); \
-  if (elem == E && nch == 4) hipLaunchKernelGGL((k_export_scale_colour<E, 4>), grid, block, 0, s, a, lut);
-  HMGPU_SCALE_COLOUR_CASE(kElemU8)
-  HMGPU_SCALE_COLOUR_CASE(kElemU16)
-  HMGPU_SCALE_COLOUR_CASE(kElemF16)
-  HMGPU_SCALE_COLOUR_CASE(kElemBF16)
-  HMGPU_SCALE_COLOUR_CASE(kElemF32)
-#undef HMGPU_SCALE_COLOUR_CASE
-}
-
-void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, hipStream_t s, int nch) {
-  const dim3 grid((unsigned)(a.cls[0].blocks + (layout == HMGPU_EXPORT_RGB ? 0 : a.cls[1].blocks)), (unsigned)n), block(256);
-  if (nch) {                                  // packed pixels (RGB only)
-#define HMGPU_SCALE_PX_CASE(E) \
-    if (elem == E && nch == 3) hipLaunchKernelGGL((k_export_scale<HMGPU_EXPORT_RGB, E, 3>), grid, block, 0, s, a); \
-    if (elem == E && nch == 4) hipLaunchKernelGGL((k_export_scale<HMGPU_EXPORT_RGB, E, 4>), grid, block, 0, s, a);
-    HMGPU_SCALE_PX_CASE(kElemU8)
-    HMGPU_SCALE_PX_CASE(kElemU16)
-    HMGPU_SCALE_PX_CASE(kElemF16)
-    HMGPU_SCALE_PX_CASE(kElemBF16)
-    HMGPU_SCALE_PX_CASE(kElemF32)
-#undef HMGPU_SCALE_PX_CASE
+// n pictures; nch: 0, or (RGB) 3 / 4 elements per packed pixel (a.px); cs / lut: null, or the stage (RGB only)
+void launch_export_scaled(const ScaleArgs& a, int layout, int elem, int n, int nch, const ChromaSite* cs, const ColourLut* lut, hipStream_t s) {
+  const bool rgb = layout == HMGPU_EXPORT_RGB;
+  const dim3 grid((unsigned)(a.cls[0].blocks + (rgb ? 0 : a.cls[1].blocks)), (unsigned)n), block(256);
+  if (!rgb) {
+    export_yuv_instance(layout, elem, [&](auto l, auto e) { hipLaunchKernelGGL((k_export_scale<l(), e()>), grid, block, 0, s, a); });
     return;
   }
-#define HMGPU_SCALE_CASE(L, E) \
-  if (layout == L && elem == E) hipLaunchKernelGGL((k_export_scale<L, E>), grid, block, 0, s, a);
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemU8)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemU16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR, kElemU8)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_SEMIPLANAR, kElemU16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemU8)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemU16)
-  // float elements: the planar and RGB layouts (the host refuses semi-planar)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemF16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemBF16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_PLANAR, kElemF32)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemF16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemBF16)
-  HMGPU_SCALE_CASE(HMGPU_EXPORT_RGB, kElemF32)
-#undef HMGPU_SCALE_CASE
+  // (the chroma kernel has one signature for both of its instance families: without the colour stage it is given an empty table)
+  export_rgb_instance(elem, nch, cs, lut, [&](auto e, auto c, const auto&... st) {
+    if constexpr (pack_has<ChromaSite, std::decay_t<decltype(st)>...>) {
+      if constexpr (sizeof...(st) == 2) hipLaunchKernelGGL((k_export_scale_chroma<e(), c(), true>), grid, block, 0, s, a, st...);
+      else hipLaunchKernelGGL((k_export_scale_chroma<e(), c(), false>), grid, block, 0, s, a, st..., ColourLut{});
+    } else if constexpr (sizeof...(st) == 1) {
+      hipLaunchKernelGGL((k_export_scale_colour<e(), c()>), grid, block, 0, s, a, st...);
+    } else {
+      hipLaunchKernelGGL((k_export_scale<HMGPU_EXPORT_RGB, e(), c()>), grid, block, 0, s, a);
+    }
+  });
 }
 
 }  // namespace hmgpu

@@ -12,17 +12,18 @@
 // weights) the 2 x 2 pairs of its two rows and two columns, clamped to the decoded plane -- then the matrix and the clip of
 // hmgpu_export_plan.coef; the four results are blended with weights that sum to 65536.  Filter and border are launch-uniform branches.
 // One instance per output element, planes / packed pixel size, colour stage and chroma stage.
+// The depth rule and the dispatch of launch_export_warp are export_core.h's.  The tap keeps its own one-sample text of the replicated
+// chroma and of the conversion, and the epilogue its own store choice: with those taken from export_core.h
+// (export_chroma_replicated<1>, export_rgb<1>, export_store_rgb, the stages as a pack) the bilinear uint8 planes case at 2160p measured
+// slower than the parent by more than the parent's own spread in two whole jobs (+1.0 and +4.7 us in 1316; profiles/EXPERIMENTS.md),
+// and sharing either piece alone changes most instances' instructions.  As it stands every instance's instructions are those from
+// before the shared core.  A change to the matrix is made here as well as in export_core.h.
 #include "hmgpu_dev.h"
-#include "colour_core.h"
-#include "chroma_core.h"
+#include "export_core.h"
 
 namespace hmgpu {
 
 namespace {
-
-__device__ inline int depth_conv(int v, int sh, int maxv) {
-  return sh >= 0 ? v << sh : min(maxv, max(0, (v + (1 << (-sh - 1))) >> -sh));
-}
 
 // v clamped to 0 .. hi, still 64 bits wide
 __device__ inline long long clamp64(long long v, long long hi) { return v < 0 ? 0 : v > hi ? hi : v; }
@@ -127,23 +128,13 @@ __global__ void __launch_bounds__(256) k_export_warp(const WarpArgs a, const Chr
   }
 }
 
-void launch_export_warp(const WarpArgs& a, const ChromaSite* cs, const ColourLut* lut, int elem, int n, int nch, hipStream_t s) {
+void launch_export_warp(const WarpArgs& a, int elem, int n, int nch, const ChromaSite* cs, const ColourLut* lut, hipStream_t s) {
   const dim3 grid((unsigned)(a.tiles_x * ((a.h + kWarpTileH - 1) / kWarpTileH)), (unsigned)n), block(256);
-  const ChromaSite no_site = {};
-  const ColourLut no_lut = {};
-#define HMGPU_WARP_CASE(E, N) \
-  if (elem == E && nch == N && !cs && !lut) hipLaunchKernelGGL((k_export_warp<E, N, false, false>), grid, block, 0, s, a, no_site, no_lut); \
-  if (elem == E && nch == N && !cs && lut) hipLaunchKernelGGL((k_export_warp<E, N, true, false>), grid, block, 0, s, a, no_site, *lut); \
-  if (elem == E && nch == N && cs && !lut) hipLaunchKernelGGL((k_export_warp<E, N, false, true>), grid, block, 0, s, a, *cs, no_lut); \
-  if (elem == E && nch == N && cs && lut) hipLaunchKernelGGL((k_export_warp<E, N, true, true>), grid, block, 0, s, a, *cs, *lut);
-#define HMGPU_WARP_ELEM(E) HMGPU_WARP_CASE(E, 0) HMGPU_WARP_CASE(E, 3) HMGPU_WARP_CASE(E, 4)
-  HMGPU_WARP_ELEM(kElemU8)
-  HMGPU_WARP_ELEM(kElemU16)
-  HMGPU_WARP_ELEM(kElemF16)
-  HMGPU_WARP_ELEM(kElemBF16)
-  HMGPU_WARP_ELEM(kElemF32)
-#undef HMGPU_WARP_ELEM
-#undef HMGPU_WARP_CASE
+  // (the kernel has one signature for its four instance families: a stage it does not have is given an empty record)
+  export_rgb_instance(elem, nch, cs, lut, [&](auto e, auto c, const auto&... st) {
+    constexpr bool chr = pack_has<ChromaSite, std::decay_t<decltype(st)>...>, col = pack_has<ColourLut, std::decay_t<decltype(st)>...>;
+    hipLaunchKernelGGL((k_export_warp<e(), c(), col, chr>), grid, block, 0, s, a, cs ? *cs : ChromaSite{}, lut ? *lut : ColourLut{});
+  });
 }
 
 }  // namespace hmgpu

@@ -5,7 +5,7 @@
 // contiguous run of 256 x 8 tiles (HistogramArgs) with one lane per group of 4 samples of a row -- 8-byte loads on luma, 16-byte ones
 // on the chroma pair plane, which give Cb and Cr of a group at once; sample by sample where the crop leaves a group unaligned or the row
 // ends inside it.  Plane class 0 counts Y and maxRGB of a luma sample together (one luma load for both; the maxRGB instance adds the
-// chroma of the same samples and k_export's matrix, colour_core.h colour_rgb), class 1 Cb and Cr.
+// chroma of the same samples and k_export's conversion, export_core.h export_rgb), class 1 Cb and Cr.
 // The histogram of a workgroup's run lives in the LDS, 2^b_c counts per channel of the class (2 x 16 KB at 12 bits): zeroed once, filled
 // with ds_add_u32, and its nonzero bins flushed -- global atomicAdd on uint32 -- once per workgroup and (picture, class), which zeroes
 // them for the next.  Moments and extrema stay in registers across the tiles and go the way of k_metrics: wave reduction by __shfl_xor,
@@ -18,7 +18,7 @@
 // gfx950, build.py's flags: k_histogram<false> 61 VGPRs, k_histogram<true> (maxRGB) 71; 32 928 bytes of LDS each (2 x 4096 bins and the
 // hand-over), which leaves room for four workgroups per CU: kHistGrid; no vector register spills, no scratch.
 #include "hmgpu_dev.h"
-#include "colour_core.h"
+#include "export_core.h"
 
 namespace hmgpu {
 
@@ -158,7 +158,8 @@ __device__ inline void tile_pass(const HistogramArgs& a, int pic, int tile, Acc 
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           uint32_t R, G, B;
-          colour_rgb(a.coef, a.sh, a.maxv, g[pass].y[j], (int16_t)(g[pass].p[j] & 0xffff), (int16_t)(g[pass].p[j] >> 16), &R, &G, &B);
+          const int u = (int16_t)(g[pass].p[j] & 0xffff), w = (int16_t)(g[pass].p[j] >> 16);
+          export_rgb<1>(a, &g[pass].y[j], &u, &w, &R, &G, &B);
           v[j] = (int)max(R, max(G, B));
         }
         count(a, 3, v, nv[pass], acc[1], bins[1]);

@@ -168,6 +168,14 @@ def test_float_elements(pair, loc):
         for form in (None, "argb", "cl"):
             got, want = pair.both(loc, dtype=dtype, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD, **form_kw(form))
             assert got.dtype == dtype and same(got, want), (loc, dtype, form)
+    # the scaled kernel: every element, planes and both pixel sizes, two pictures with the second mirrored, from a window whose
+    # chroma offset is odd and whose width is no multiple of 4
+    geo = dict(idx=[0, 1], windows=[(2, 6, 42, 26)] * 2, flip=[False, True], size=(20, 30))
+    for dtype in (None, torch.float16, torch.bfloat16, torch.float32):
+        kw = dict(geo) if dtype is None else dict(geo, dtype=dtype, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD)
+        for form in (None, "bgr", "argb"):
+            got, want = pair.both(loc, **kw, **form_kw(form))
+            assert same(got, want), (loc, dtype, form, "scaled")
 
 
 @pytest.mark.parametrize("shaper", [False, True])
@@ -182,6 +190,17 @@ def test_colour_lut_behind_the_chroma_stage(pair, shaper):
             want = pair.ctx444.export_batch([pair.pics444[i, loc] for i in range(3)], "rgb", depth, lut=b, **kw)
             plain = pair.ctx444.export_batch([pair.pics444[i, loc] for i in range(3)], "rgb", depth, **kw)
             assert same(got, want) and not same(got, plain), (loc, kw)
+        # every element and form behind both stages, unscaled and scaled: two pictures, the second mirrored, from a window whose
+        # chroma offset is odd and whose width is no multiple of 4
+        torch = _torch()
+        geo = dict(windows=[(2, 6, 42, 26)] * 2, flip=[False, True])
+        for dtype in (None, torch.float16, torch.bfloat16, torch.float32):
+            kw = dict(geo) if dtype is None else dict(geo, dtype=dtype, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD)
+            for form in (None, "bgr", "argb"):
+                for size in (None, (20, 30)):
+                    got = pair.ctx.export_batch(pair.pics[:2], "rgb", depth, chroma="linear", chroma_loc=3, lut=a, size=size, **kw, **form_kw(form))
+                    want = pair.ctx444.export_batch([pair.pics444[i, 3] for i in range(2)], "rgb", depth, lut=b, size=size, **kw, **form_kw(form))
+                    assert same(got, want), (dtype, form, size)
 
 
 WINDOWS = [(2, 6, 44, 26), (6, 2, 44, 26), (28, 14, 44, 26)]      # left / top 2 and 6: odd chroma offsets, groups not 8-byte aligned

@@ -218,7 +218,8 @@ def test_unscaled(fmt, bd):
 
 
 def test_every_kind_and_form():
-    """the full product of element kinds and forms on one LUT of 17 nodes with a shaper, three pictures, 94 columns, mirrored"""
+    """the full product of element kinds and forms on one LUT of 17 nodes with a shaper, three pictures, 94 columns, mirrored;
+    unscaled and scaled"""
     with Pictures(1, count=3) as P:
         windows = [ORIGINS[94][i] + (94, 40) for i in (1, 4, 6)]
         flips = [True, False, True]
@@ -228,6 +229,14 @@ def test_every_kind_and_form():
                 for form in FORMS:
                     alpha = interior_alpha(kind, form)
                     P.compare(P.export(P.pics, windows, flips, kind, form, alpha, h), P.pics, windows, flips, kind, form, alpha, lut)
+            # and through the scaled kernel: 30 x 20 outputs of the same windows
+            size, filt = (20, 30), abi.SCALE_BILINEAR
+            lut = make_lut(kind[0], 17, True, P.entering(P.pics, windows, kind[0], size=size, filt=filt), kind[0])
+            with P.ctx.colour_lut(lut[1], lut[2], lut[0]) as h:
+                for form in FORMS:
+                    alpha = interior_alpha(kind, form)
+                    got = P.export(P.pics, windows, flips, kind, form, alpha, h, size=size, filt=filt)
+                    P.compare(got, P.pics, windows, flips, kind, form, alpha, lut, size=size, filt=filt)
 
 
 def test_one_picture_and_the_crop_of_the_descriptor():

@@ -261,6 +261,9 @@ def test_scaled(filt, fmt):
             for kind, order, alpha in ((U8, "rgb", None), (U8, "bgra", 100), (F16, "bgr", None), (F16, "abgr", 0.3)):
                 P.run(pics, windows, flips, kind, order, alpha, size=size, filt=filt)
             P.run(pics, windows, flips, U10, ORDERS[(j + filt) % 6], None, colour=(9, 1), size=size, filt=filt)
+        if filt == abi.SCALE_BILINEAR:                       # bfloat16 packed pixels of the scaled kernel, 3 and 4 channels
+            P.run(pics, windows, flips, BF16, "rgb", None, size=size, filt=filt)
+            P.run(pics, windows, flips, BF16, "argb", BF16[3], size=size, filt=filt)
         windows = LARGE[:4]
         P.run(pics[:4], windows, flips[:4], U8, "rgb", None, size=(224, 224), filt=filt)
         P.run(pics[:4], windows, flips[:4], F16, "rgba", None, size=(224, 224), filt=filt)

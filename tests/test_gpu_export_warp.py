@@ -131,6 +131,9 @@ def test_identity_map_is_the_existing_export_in_every_form(box):
                 dict(dtype=torch.float32, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD), dict(matrix=9, full_range=1)]
     if box.bd == 10:
         variants.append(dict(msb_aligned=True))
+    # the chroma stage under every float element
+    variants += [dict(chroma="linear", chroma_loc=2, dtype=t, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD)
+                 for t in (torch.float16, torch.bfloat16, torch.float32)]
     for v, kw in enumerate(variants):
         for f, form in enumerate(FORMS):
             filt = FILTERS[(v + f) & 1]
@@ -152,6 +155,16 @@ def test_identity_behind_a_colour_lut(box):
             got = box.warp([0, 1], [ID] * 2, (H, W), lut=lut, chroma="linear", chroma_loc=1, **form_kw(form))
             want = box.existing([0, 1], lut=lut, chroma="linear", chroma_loc=1, **form_kw(form))
             assert same(got, want) and not same(got, box.existing([0, 1], chroma="linear", chroma_loc=1, **form_kw(form))), form
+        # every element and form, without and with the chroma stage: two pictures, the second mirrored, from a window whose chroma
+        # offset is odd and whose width is no multiple of 4
+        torch = _torch()
+        geo = dict(windows=[(2, 6, 42, 26)] * 2, flip=[False, True])
+        for d, dtype in enumerate((None, torch.float16, torch.bfloat16, torch.float32)):
+            kw = dict(geo) if dtype is None else dict(geo, dtype=dtype, mean=bref.IMAGENET_MEAN, std=bref.IMAGENET_STD)
+            for f, form in enumerate((None, "bgr", "argb")):
+                for c, chroma in enumerate((dict(), dict(chroma="linear", chroma_loc=4))):
+                    got = box.warp([0, 1], [ID] * 2, (26, 42), filter=FILTERS[(d + f + c) & 1], lut=lut, **kw, **chroma, **form_kw(form))
+                    assert same(got, box.existing([0, 1], lut=lut, **kw, **chroma, **form_kw(form))), (dtype, form, chroma)
 
 
 @pytest.mark.parametrize("size", OUTS)
