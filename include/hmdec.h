@@ -94,6 +94,7 @@ typedef struct hmgpu_export_pixel hmgpu_export_pixel;
 typedef struct hmgpu_colour_lut_desc hmgpu_colour_lut_desc;
 typedef struct hmgpu_export_chroma hmgpu_export_chroma;
 typedef struct hmgpu_export_format hmgpu_export_format;
+typedef struct hmgpu_export_yuvpack hmgpu_export_yuvpack;
 typedef struct hmgpu_export_warp hmgpu_export_warp;
 typedef struct hmgpu_warp_map hmgpu_warp_map;
 typedef struct hmgpu_motion_desc hmgpu_motion_desc;
@@ -162,6 +163,13 @@ int hmdec_pictures_export_format(libHMDec_context* ctx, int n, libHMDec_picture*
                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
                                  const hmgpu_export_format* format, void* const dst[3], const int64_t pitch_bytes[3],
                                  const int64_t batch_stride_bytes[3], int on_stream, void* stream);
+/* Y, Cb and Cr interleaved into the words of `pack` (hmgpu_pictures_export_yuvpack; include/hmgpu.h "packed YUV"): the arguments of
+ * hmdec_pictures_export_format and the word format, dst[0] the one destination.  The whole batch is validated once
+ * (hmgpu_export_yuvpack_destination_check), then each run of slots of a device context is one call. */
+int hmdec_pictures_export_yuvpack(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                  const hmgpu_export_format* format, const hmgpu_export_yuvpack* pack, void* const dst[3],
+                                  const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream);
 /* The RGB exports through one inverse affine map per picture (hmgpu_pictures_export_warp; include/hmgpu.h "affine warp export"): the
  * arguments of hmdec_pictures_export_chroma without `scale` (chroma NULL: replicate; lut 0: no colour stage), then the warp
  * descriptor and n maps.  The whole batch is validated once (hmgpu_export_warp_destination_check), then each run of slots of a device

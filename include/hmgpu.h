@@ -736,6 +736,77 @@ hmgpu_status hmgpu_export_format_scale_taps(const hmgpu_seq_params* seq, const h
                                             const hmgpu_export_format* format, int32_t chroma, int32_t axis, int32_t max_taps,
                                             int32_t* first, int32_t* count, int16_t* weights);
 
+/* ------------------------------------------------------------------------------------------------ packed YUV
+ * Y, Cb and Cr interleaved into words: the layouts of capture cards, SDI and the display and encode APIs.  All words
+ * are little endian; D is the depth of a format and cf its chroma format; values are D-bit unsigned integers.
+ *
+ *   format  cf     D   memory, per unit                                                              bytes per unit
+ *   UYVY    4:2:2  8   bytes Cb Y0 Cr Y1 per two pixels                                              4
+ *   YUY2    4:2:2  8   bytes Y0 Cb Y1 Cr per two pixels                                              4
+ *   Y210    4:2:2  10  uint16 Y0 Cb Y1 Cr, each v << 6 (low six bits 0)                              8
+ *   Y216    4:2:2  16  uint16 Y0 Cb Y1 Cr                                                            8
+ *   V210    4:2:2  10  six pixels in four uint32, three values per word at bits 0-9, 10-19, 20-29,   16
+ *                      bits 30-31 zero
+ *   AYUV    4:4:4  8   bytes Cr Cb Y A per pixel                                                     4
+ *   Y410    4:4:4  10  uint32 Cb | Y << 10 | Cr << 20 | A << 30 per pixel                            4
+ *   Y416    4:4:4  16  uint16 Cb Y Cr A per pixel                                                    8
+ *
+ * V210, for the group of pixels 6g .. 6g + 5 with Cbm = Cb[3g + m] and Crm = Cr[3g + m]:
+ *   w0 = Cb0 | Y0 << 10 | Cr0 << 20     w1 = Y1 | Cb1 << 10 | Y2 << 20     w2 = Cr1 | Y3 << 10 | Cb2 << 20     w3 = Y4 | Cr2 << 10 | Y5 << 20
+ * A V210 row is ceil(W / 6) * 16 bytes: that is row_bytes, the least pitch.  A luma or chroma value whose pixel index is at or beyond
+ * the output width is written as 0 inside the last group; bytes between the end of the last group and the pitch are never written.
+ * The customary 128-byte row alignment (48 pixels) is the caller's choice of pitch.
+ * A is a constant of the call: `alpha` is 0 .. 255 for AYUV, 0 .. 3 for Y410, 0 .. 65535 for Y416, and must be 0 for the 4:2:2 formats.
+ *
+ * hmgpu_pictures_export_yuvpack.  Let P be what hmgpu_pictures_export_format writes for the same pictures, crop or windows, flips and
+ * `format` (up, down, loc) with layout HMGPU_EXPORT_PLANAR, format->chroma_format = cf, bit_depth {D, D}, unsigned elements of the
+ * container D needs and msb_aligned 0: Y, Cb and Cr after the chroma-format conversion, the bit-depth rule and the mirror.  The
+ * packed output holds exactly the values of P in the layout above; nothing else is computed.  So a 4:0:0 source gives Cb = Cr =
+ * 1 << (D - 1), every source chroma format works with every word format, the export of a window is the window of the whole
+ * picture's export, and the mirror reverses pixels (the pair Y0, Y1 of a 4:2:2 unit swaps with the unit; V210 groups are those of
+ * the mirrored row).  Every argument but `pack` has the type and meaning it has in hmgpu_pictures_export_format.
+ *
+ * Validation, in this order, everything before anything is enqueued and a refused call leaving the destination untouched:
+ *   1. `pack` NULL or a non-zero reserved word: HMGPU_EINVAL; an unknown pack->format: HMGPU_EUNSUPPORTED (the format names D and
+ *      cf, which every later rule needs);
+ *   2. `desc` NULL, desc->layout other than HMGPU_EXPORT_PLANAR, a desc->bit_depth[] that is neither 0 nor D, a bytes_per_sample that is neither 0
+ *      nor the container of D, msb_aligned other than 0: HMGPU_EINVAL;
+ *   3. `format` NULL or format->chroma_format other than cf: HMGPU_EINVAL;
+ *   4. alpha outside the format's range (the 4:2:2 formats: other than 0): HMGPU_EINVAL;
+ *   5. `scale` not NULL: HMGPU_EUNSUPPORTED (the scaled kernels resample planes separately); `tensor` with a float sample type:
+ *      HMGPU_EUNSUPPORTED;
+ *   6. the rules of hmgpu_pictures_export_format for the call that defines P, in their order: among them n, the crop or every
+ *      window covering whole chroma samples of the source format and of cf (even left edges and widths for the 4:2:2 formats), one
+ *      size for all windows, an unknown up or down;
+ *   7. the destination against the plan: dst[1] or dst[2] not NULL; an address, pitch or batch stride that is no multiple of 1
+ *      (UYVY, YUY2, AYUV), 2 (Y210, Y216, Y416) or 4 (V210, Y410) bytes; a pitch below row_bytes, a batch stride below
+ *      pitch * (H - 1) + row_bytes, a span of the n pictures outside one allocation of the context's device: HMGPU_EINVAL.
+ * The plan has one plane: width[0] / height[0] in pixels, row_bytes[0] as above.  Picture i is written at dst[0] +
+ * i * batch_stride_bytes.  Up to HMGPU_EXPORT_MAX_BATCH pictures, handles may repeat, one launch per call (k_export_yuvpack.hip),
+ * the stream ordering of hmgpu_pictures_export; not accounted in hmgpu_stats. */
+enum { HMGPU_YUVPACK_UYVY = 0, HMGPU_YUVPACK_YUY2 = 1, HMGPU_YUVPACK_Y210 = 2, HMGPU_YUVPACK_Y216 = 3, HMGPU_YUVPACK_V210 = 4,
+       HMGPU_YUVPACK_AYUV = 5, HMGPU_YUVPACK_Y410 = 6, HMGPU_YUVPACK_Y416 = 7 };
+typedef struct hmgpu_export_yuvpack {
+  int32_t format;              /* HMGPU_YUVPACK_* */
+  int32_t alpha;               /* A of AYUV / Y410 / Y416; 0 for the 4:2:2 formats */
+  int32_t reserved[6];         /* 0 */
+} hmgpu_export_yuvpack;
+/* the one-plane plan; windows NULL: the plan of desc's crop (n ignored); host code, no device needed */
+hmgpu_status hmgpu_export_yuvpack_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* desc, const hmgpu_export_tensor* tensor,
+                                           int32_t n, const hmgpu_export_window windows[], const hmgpu_export_format* format,
+                                           const hmgpu_export_yuvpack* pack, hmgpu_export_plan* out);
+hmgpu_status hmgpu_pictures_export_yuvpack(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* desc,
+                                           const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                           const hmgpu_export_window windows[], const hmgpu_export_format* format,
+                                           const hmgpu_export_yuvpack* pack, void* const dst[3], const int64_t pitch_bytes[3],
+                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* hmgpu_export_destination_check for hmgpu_pictures_export_yuvpack: the status it would give these arguments; enqueues nothing */
+hmgpu_status hmgpu_export_yuvpack_destination_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_export_desc* desc,
+                                                    const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor,
+                                                    const hmgpu_export_window windows[], const hmgpu_export_format* format,
+                                                    const hmgpu_export_yuvpack* pack, void* const dst[3], const int64_t pitch_bytes[3],
+                                                    const int64_t batch_stride_bytes[3]);
+
 /* ------------------------------------------------------------------------------------------------ picture import
  * The way in from device memory: planar or semi-planar YUV, or RGB as three planes or as packed pixels, in
  * caller-owned memory of the context's GPU becomes the samples of up to HMGPU_EXPORT_MAX_BATCH acquired pictures -- one kernel
@@ -837,6 +908,35 @@ hmgpu_status hmgpu_pictures_import(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pi
 /* steps 1, 2, 3 and 5 of the validation and nothing else: nothing is enqueued and no picture is named */
 hmgpu_status hmgpu_import_source_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_import_desc* desc, const void* const src[3],
                                        const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]);
+
+/* hmgpu_pictures_import_yuvpack: the words of "packed YUV" on the way in.  The source is unpacked by that section's table into planes
+ * Y, Cb, Cr of D-bit values -- V210 fields are (w >> s) & 0x3ff, Y210 elements e >> 6, A is read over, bits 30-31 of V210 words are
+ * ignored, and so is everything in a V210 row's last group at or beyond the width -- and the pictures then receive exactly what
+ * hmgpu_pictures_import gives for those planes with layout HMGPU_EXPORT_PLANAR, order -1, chroma_format cf, bit_depth {D, D},
+ * unsigned LSB-aligned elements and the same width, height, down and loc: the padding rule, the down rule, the depth rule and the
+ * picture state afterwards are those of that call.  Validation, in this order, a refused call leaving every picture untouched:
+ *   1. `pack` NULL or a non-zero reserved word: HMGPU_EINVAL; an unknown pack->format: HMGPU_EUNSUPPORTED;
+ *   2. `desc` NULL, a layout other than HMGPU_EXPORT_PLANAR, an order other than -1, a chroma_format other than cf, a bit_depth[]
+ *      that is neither 0 nor D, a bytes_per_sample that is neither 0 nor the container of D, a sample_type other than
+ *      HMGPU_SAMPLE_UINT, msb_aligned other than 0: HMGPU_EINVAL;
+ *   3. the remaining steps of hmgpu_pictures_import for that planar source, in its order (reserved words, sizes, loc: HMGPU_EINVAL;
+ *      an unknown `down`: HMGPU_EUNSUPPORTED; n; the handles; the source; the stream).  The source is one plane, src[0] (src[1] and
+ *      src[2] must be NULL), whose address, pitch and batch stride are multiples of the format's element (1, 2 or 4 bytes, as for
+ *      the export), with the pitch and stride rules of the plan: width[0] / height[0] in pixels, row_bytes[0] the bytes of a row. */
+typedef struct hmgpu_import_yuvpack {
+  int32_t format;              /* HMGPU_YUVPACK_* */
+  int32_t reserved[7];         /* 0 */
+} hmgpu_import_yuvpack;
+/* steps 1 to 3 up to the descriptor's own rules, and the one-plane plan; host code, no device needed */
+hmgpu_status hmgpu_import_yuvpack_plan_for(const hmgpu_seq_params* seq, const hmgpu_import_desc* desc, const hmgpu_import_yuvpack* pack,
+                                           hmgpu_import_plan* out);
+hmgpu_status hmgpu_pictures_import_yuvpack(hmgpu_ctx* ctx, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* desc,
+                                           const hmgpu_import_yuvpack* pack, const void* const src[3], const int64_t pitch_bytes[3],
+                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream);
+/* the validation without the handles and the stream: nothing is enqueued and no picture is named */
+hmgpu_status hmgpu_import_yuvpack_source_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_import_desc* desc, const hmgpu_import_yuvpack* pack,
+                                               const void* const src[3], const int64_t pitch_bytes[3],
+                                               const int64_t batch_stride_bytes[3]);
 
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --

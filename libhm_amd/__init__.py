@@ -154,6 +154,17 @@ def lib():
         L.hmgpu_export_format_scale_taps.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
                                                      C.POINTER(abi.ExportFormat), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                      C.POINTER(C.c_int32), C.POINTER(C.c_int16)]
+        L.hmgpu_export_yuvpack_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportTensor), C.c_int32,
+                                                    C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportFormat), C.POINTER(abi.ExportYuvPack),
+                                                    C.POINTER(abi.ExportPlan)]
+        L.hmgpu_pictures_export_yuvpack.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ExportDesc),
+                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                    C.POINTER(abi.ExportFormat), C.POINTER(abi.ExportYuvPack), C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_export_yuvpack_destination_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportScale),
+                                                             C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                             C.POINTER(abi.ExportFormat), C.POINTER(abi.ExportYuvPack),
+                                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_export_warp_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ExportDesc), C.POINTER(abi.ExportTensor), C.c_int32,
                                                  C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel), C.POINTER(abi.ColourLutDesc),
                                                  C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
@@ -244,6 +255,13 @@ def lib():
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
         L.hmgpu_import_source_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ImportDesc), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_import_yuvpack_plan_for.argtypes = [C.POINTER(abi.SeqParams), C.POINTER(abi.ImportDesc), C.POINTER(abi.ImportYuvPack),
+                                                    C.POINTER(abi.ImportPlan)]
+        L.hmgpu_pictures_import_yuvpack.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(abi.ImportDesc),
+                                                    C.POINTER(abi.ImportYuvPack), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                    C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        L.hmgpu_import_yuvpack_source_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ImportDesc), C.POINTER(abi.ImportYuvPack),
+                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.hmgpu_host_alloc.argtypes = [C.c_size_t]
         L.hmgpu_host_alloc.restype = C.c_void_p
         L.hmgpu_host_free.argtypes = [C.c_void_p]
@@ -292,6 +310,12 @@ def import_status(seq, desc):
     """(status, plan) of hmgpu_import_plan_for: host code, no GPU"""
     plan = abi.ImportPlan()
     return lib().hmgpu_import_plan_for(C.byref(seq), abi.ref(desc), C.byref(plan)), plan
+
+
+def import_yuvpack_status(seq, desc, yuvpack):
+    """(status, plan) of hmgpu_import_yuvpack_plan_for: host code, no GPU; yuvpack: an abi.ImportYuvPack or None"""
+    plan = abi.ImportPlan()
+    return lib().hmgpu_import_yuvpack_plan_for(abi.ref(seq), abi.ref(desc), abi.ref(yuvpack), C.byref(plan)), plan
 
 
 def import_plan(seq, desc=None, **kw):
@@ -413,6 +437,26 @@ def export_format_scale_taps(seq, desc, scale, format, chroma, axis):
     return first, count, w
 
 
+def export_yuvpack_status(seq, desc, tensor, windows, format, yuvpack, n=None):
+    """(status, plan) of hmgpu_export_yuvpack_plan_for (host code, no GPU): the one plane of words; windows None: the plan of desc's
+    crop; format: an abi.ExportFormat or None; yuvpack: an abi.ExportYuvPack or None; n: another count than len(windows)"""
+    windows = None if windows is None else list(windows)
+    if n is None:
+        n = len(windows) if windows is not None else 1
+    plan = abi.ExportPlan()
+    st = lib().hmgpu_export_yuvpack_plan_for(abi.ref(seq), abi.ref(desc), abi.ref(tensor), n, abi.window_array(windows), abi.ref(format),
+                                             abi.ref(yuvpack), C.byref(plan))
+    return st, plan
+
+
+def export_yuvpack_plan(seq, desc, tensor, windows, format, yuvpack):
+    """what a packed YUV export writes per slot: export_yuvpack_status, a refusal raised"""
+    st, plan = export_yuvpack_status(seq, desc, tensor, windows, format, yuvpack)
+    if st != abi.HMGPU_OK:
+        raise HmgpuError(st, "hmgpu_export_yuvpack_plan_for")
+    return plan
+
+
 def export_warp_status(seq, desc, tensor, windows, pixel, lut_desc, chroma, warp, maps, n=None):
     """(status, plan) of hmgpu_export_warp_plan_for (host code, no GPU): the plan of the matching planar or packed call with every
     plane warp.width x warp.height.  warp: an abi.ExportWarp or None; maps: an abi.WarpMap array (abi.warp_map_array) or None;
@@ -441,6 +485,8 @@ def export_stages_plan(seq, desc, stages, n=None):
     s, ld = stages, stages.lut
     if ld is not None and not isinstance(ld, abi.ColourLutDesc):
         ld = abi.make_colour_lut_desc(ld.depth, ld.size, ld.has_shaper) if hasattr(ld, "has_shaper") else None
+    if s.yuvpack is not None:
+        return export_yuvpack_plan(seq, desc, s.tensor, s.windows, s.format, s.yuvpack)
     if s.format is not None:
         return export_format_plan(seq, desc, s.scale, s.tensor, s.windows, s.format)
     if s.warp is not None:
@@ -807,6 +853,29 @@ class Context:
                                                            abi.ref(format), abi.ptr_array(ptrs), abi.i64_array(pitches),
                                                            abi.i64_array(bstrides))
 
+    def export_yuvpack_into(self, pics, desc, format, yuvpack, ptr, pitch, bstride, on_stream=0, stream=0, scale=None, tensor=None, windows=None):
+        """hmgpu_pictures_export_yuvpack into device memory the caller owns: picture i's words at ptr + i * bstride (bytes), rows
+        pitch apart; format: the abi.ExportFormat of the words' chroma format, yuvpack: an abi.ExportYuvPack"""
+        pics = list(pics)
+        self._chk(lib().hmgpu_pictures_export_yuvpack(self._h, len(pics), abi.handle_array(pics), abi.ref(desc), abi.ref(scale), abi.ref(tensor),
+                                                      abi.window_array(windows), abi.ref(format), abi.ref(yuvpack), abi.ptr_array([ptr]),
+                                                      abi.i64_array([pitch]), abi.i64_array([bstride]), on_stream, abi.addr(stream)),
+                  "hmgpu_pictures_export_yuvpack")
+
+    def export_yuvpack_status(self, pics, desc, format, yuvpack, ptrs, pitches, bstrides, on_stream=0, stream=0, scale=None, tensor=None,
+                              windows=None):
+        """hmgpu_pictures_export_yuvpack, the status returned instead of raised; ptrs / pitches / bstrides: up to three each"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_export_yuvpack(self._h, len(pics), abi.handle_array(pics), abi.ref(desc), abi.ref(scale), abi.ref(tensor),
+                                                   abi.window_array(windows), abi.ref(format), abi.ref(yuvpack), abi.ptr_array(ptrs),
+                                                   abi.i64_array(pitches), abi.i64_array(bstrides), on_stream, abi.addr(stream))
+
+    def export_yuvpack_destination_status(self, n, desc, format, yuvpack, ptrs, pitches, bstrides, scale=None, tensor=None, windows=None):
+        """hmgpu_export_yuvpack_destination_check: the status hmgpu_pictures_export_yuvpack would give; enqueues nothing"""
+        return lib().hmgpu_export_yuvpack_destination_check(self._h, n, abi.ref(desc), abi.ref(scale), abi.ref(tensor), abi.window_array(windows),
+                                                            abi.ref(format), abi.ref(yuvpack), abi.ptr_array(ptrs), abi.i64_array(pitches),
+                                                            abi.i64_array(bstrides))
+
     def export_warp_into(self, pics, desc, warp, ptrs, pitches, bstrides, on_stream=0, stream=0, tensor=None, windows=None, pixel=None,
                          lut=None, chroma=None):
         """hmgpu_pictures_export_warp into device memory the caller owns: export_chroma_into without a scale (chroma None: replicate),
@@ -839,15 +908,20 @@ class Context:
 
     def export_stages_into(self, pics, desc, stages, ptrs, pitches, bstrides, on_stream=0, stream=0):
         """the export of `stages` (export.Stages) into device memory the caller owns, through the narrowest hmgpu_pictures_export*
-        entry that carries them: format (the YUV layouts at another chroma format), else warp, else chroma, else colour, else pixels (ptrs[0] / pitches[0] / bstrides[0] the one destination),
+        entry that carries them: yuvpack (YUV interleaved into words: ptrs[0] / pitches[0] / bstrides[0] the one destination), else
+        format (the YUV layouts at another chroma format), else warp, else chroma, else colour, else pixels (ptrs[0] / pitches[0] /
+        bstrides[0] the one destination),
         else windows or the plain batch -- the only ones that take a YUV layout.  bstrides None: one picture, through
         hmgpu_picture_export(_scaled) where it has integer elements and no further stage, else as a batch of one"""
         s = stages
         if bstrides is None:
-            if s[1:] == (None,) * 7:
+            if s[1:] == (None,) * 8:
                 return self.export_into(pics[0], desc, ptrs, pitches, on_stream, stream, s.scale)
             from . import export
             bstrides = export.stage_extents(export_stages_plan(self.seq, desc, s.shape_only(), 1), pitches)
+        if s.yuvpack is not None:
+            return self.export_yuvpack_into(pics, desc, s.format, s.yuvpack, ptrs[0], pitches[0], bstrides[0], on_stream, stream, s.scale, s.tensor,
+                                            s.windows)
         if s.format is not None:
             return self.export_format_into(pics, desc, s.format, ptrs, pitches, bstrides, on_stream, stream, s.scale, s.tensor, s.windows)
         if s.warp is not None:
@@ -863,7 +937,8 @@ class Context:
 
     def export(self, pic, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None,
-               lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop"):
+               lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop",
+               yuv=None, row_align=1):
         """the picture as torch tensors on this context's GPU (libhm_amd.export.export_tensors), written on torch's current stream
         (on_stream) or on the context's own; size (height, width) resizes (filter), out receives it.  dtype: a torch float dtype
         gives normalised float elements (export_batch with one picture, without the batch dimension).  pixel ("rgb", "bgr", "rgba",
@@ -875,9 +950,19 @@ class Context:
         takes one per picture; size is then required and is the output size, filter "bilinear" or "nearest", border "edge" or "fill"
         with fill=(r, g, b) (hmgpu_pictures_export_warp).
         chroma_format (layouts "planar" / "semiplanar"): None, or "400" / "420" / "422" / "444" (0 .. 3) -- Cb and Cr at that chroma
-        format (hmgpu_pictures_export_format), as export_batch describes; planar with "444" returns ONE [3, H, W] tensor"""
+        format (hmgpu_pictures_export_format), as export_batch describes; planar with "444" returns ONE [3, H, W] tensor.
+        yuv / alpha / row_align: YUV interleaved into words, as export_batch describes, without the batch dimension"""
         from . import export
         os_ = 1 if on_stream else 0
+        if yuv is None and row_align != 1:
+            raise ValueError("row_align belongs to yuv=")
+        if yuv is not None:
+            export.yuvpack_only(size=size, dtype=dtype, mean=mean, std=std, scale=scale, bias=bias, pixel=pixel, lut=lut, warp=warp, fill=fill,
+                                chroma_format=chroma_format, msb_aligned=msb_aligned)
+            return export.export_yuvpack(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                         self.export_stages_into([pic], desc, stages, ptrs, pitches, bstrides, os_, st),
+                                         self.seq, self.device, yuv, alpha, crop, None, chroma, chroma_down, chroma_loc, on_stream, out, None,
+                                         row_align)
         fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc)
         return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
                                      self.export_stages_into([pic], desc, stages, ptrs, pitches, bstrides, os_, st),
@@ -889,7 +974,7 @@ class Context:
     def export_batch(self, pics, layout="rgb", bit_depth=8, crop=(0, 0, 0, 0), matrix=1, full_range=0, msb_aligned=False, on_stream=True,
                      size=None, filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
                      pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge",
-                     fill=None, chroma_format=None, chroma_down="drop"):
+                     fill=None, chroma_format=None, chroma_down="drop", yuv=None, row_align=1):
         """up to 16 pictures in one call (hmgpu_pictures_export: one launch, the stream ordering once) as one torch tensor per plane
         with a leading batch dimension: RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).
         dtype None: the unsigned integers of `export`; torch.float16 / bfloat16 / float32: fl(fl(v * scale_k) + bias_k) with
@@ -922,12 +1007,30 @@ class Context:
         with "444" returns ONE [N, 3, H, W] tensor, Y, Cb and Cr its channels (dtype / mean / std per channel) -- the input of a
         model that takes Y'CbCr; every other case the tuples of the YUV layouts with the new chroma shapes (semi-planar "420" is
         NV12 / P010).  With size= chroma is resampled straight to the output format's chroma size and chroma / chroma_down /
-        chroma_loc have no part."""
+        chroma_loc have no part.
+        yuv ("uyvy", "yuy2", "y210", "y216", "v210", "ayuv", "y410", "y416"; with crop, windows, flip, chroma, chroma_down, chroma_loc,
+        out and on_stream, and nothing else): Y, Cb and Cr interleaved into the words of that format (hmgpu_pictures_export_yuvpack,
+        include/hmgpu.h "packed YUV"), one launch: the values of the planar export at the format's chroma format ("422" / "444") and
+        depth (8, 10 or 16), converted by chroma / chroma_down / chroma_loc where the picture's format differs.  alpha: the A of
+        "ayuv" (0 .. 255), "y410" (0 .. 3) and "y416" (0 .. 65535); None: 0.  ONE tensor: uint8 [N, H, W, 2] ("uyvy", "yuy2") or
+        [N, H, W, 4] ("ayuv"); 16-bit [N, H, W, 2] ("y210", "y216") or [N, H, W, 4] ("y416") in the dtype of the 16-bit exports; int32
+        [N, H, W] ("y410"); int32 [N, H, P / 4] ("v210") with P the row's ceil(W / 6) * 16 bytes rounded up to row_align -- 128 gives
+        the customary stride (v210 rows are whole dwords: row_align is 1 or a multiple of 4, and 1 rounds to 4); bytes behind the last
+        group of a row are not written."""
         from . import export
         pics = list(pics)
-        fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc)
         win = export.make_windows(self.seq, crop, windows, flip, len(pics))
         os_ = 1 if on_stream else 0
+        if yuv is None and row_align != 1:
+            raise ValueError("row_align belongs to yuv=")
+        if yuv is not None:
+            export.yuvpack_only(size=size, dtype=dtype, mean=mean, std=std, scale=scale, bias=bias, pixel=pixel, memory_format=memory_format,
+                                lut=lut, warp=warp, fill=fill, chroma_format=chroma_format, msb_aligned=msb_aligned)
+            return export.export_yuvpack(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                         self.export_stages_into(pics, desc, stages, ptrs, pitches, bstrides, os_, st),
+                                         self.seq, self.device, yuv, alpha, crop, win, chroma, chroma_down, chroma_loc, on_stream, out,
+                                         len(pics), row_align)
+        fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc)
         return export.export_tensors(lambda desc, stages, ptrs, pitches, bstrides, st:
                                      self.export_stages_into(pics, desc, stages, ptrs, pitches, bstrides, os_, st),
                                      self.seq, self.device, layout, bit_depth, crop, matrix, full_range, msb_aligned, on_stream, size, filter,
@@ -955,8 +1058,26 @@ class Context:
         return lib().hmgpu_import_source_check(self._h, n, abi.ref(desc), abi.ptr_array(ptrs), abi.i64_array(pitches),
                                                abi.i64_array(bstrides))
 
+    def import_yuvpack_status(self, pics, desc, yuvpack, ptrs, pitches, bstrides, on_stream=0, stream=0):
+        """hmgpu_pictures_import_yuvpack, the status returned: the words of yuvpack (an abi.ImportYuvPack) in ptrs[0], picture i at
+        ptrs[0] + i * bstrides[0] (bytes), rows pitches[0] apart; desc: the abi.ImportDesc of the planar source they stand for"""
+        pics = list(pics)
+        return lib().hmgpu_pictures_import_yuvpack(self._h, len(pics), abi.handle_array(pics), abi.ref(desc), abi.ref(yuvpack),
+                                                   abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), on_stream,
+                                                   abi.addr(stream))
+
+    def import_yuvpack_into(self, pics, desc, yuvpack, ptr, pitch, bstride, on_stream=0, stream=0):
+        """import_yuvpack_status of one source, a refusal raised"""
+        self._chk(self.import_yuvpack_status(pics, desc, yuvpack, [ptr], [pitch], [bstride], on_stream, stream), "hmgpu_pictures_import_yuvpack")
+
+    def import_yuvpack_source_status(self, n, desc, yuvpack, ptrs, pitches, bstrides):
+        """hmgpu_import_yuvpack_source_check: the status the import would give this descriptor and source; enqueues nothing"""
+        return lib().hmgpu_import_yuvpack_source_check(self._h, n, abi.ref(desc), abi.ref(yuvpack), abi.ptr_array(ptrs),
+                                                       abi.i64_array(pitches), abi.i64_array(bstrides))
+
     def import_batch(self, pics, tensors, layout="rgb", pixel=None, bit_depth=None, chroma_format=None, chroma_down="drop", chroma_loc=0,
-                     matrix=1, full_range=0, msb_aligned=False, scale=None, bias=None, mean=None, std=None, size=None, on_stream=True):
+                     matrix=1, full_range=0, msb_aligned=False, scale=None, bias=None, mean=None, std=None, size=None, on_stream=True,
+                     yuv=None):
         """torch tensors on this context's GPU become the samples of up to 16 acquired pictures (hmgpu_pictures_import: one launch,
         no host copy, no wait), read on torch's current stream (on_stream) or on the context's own.  `tensors` is what export_batch
         returns for the same keywords: layout "rgb" one [N, 3, H, W] tensor (channels-last strides go through the packed path) or
@@ -968,8 +1089,16 @@ class Context:
         or (luma, chroma); None: the coding depths.  chroma_format ("400" / "420" / "422" / "444", 0 .. 3; None: the context's):
         the source's format; where the picture has fewer chroma samples chroma_down decides, "drop" or "linear" at chroma_loc.
         size (height, width): the source size when it is smaller than the coded picture (None: the tensors' own), the last column
-        and row repeated.  matrix / full_range: of the picture made from RGB.  The pictures are left as `upload` leaves them."""
+        and row repeated.  matrix / full_range: of the picture made from RGB.  The pictures are left as `upload` leaves them.
+        yuv ("uyvy" ... "y416"; with chroma_down, chroma_loc, size and on_stream only): `tensors` is the ONE tensor of words
+        export_batch(yuv=) returns (hmgpu_pictures_import_yuvpack); a "v210" tensor [N, H, P / 4] needs size= where the width is
+        not the 6 * P / 16 pixels its rows have room for."""
         from . import imports
+        if yuv is not None:
+            from . import export
+            export.yuvpack_only(pixel=pixel, bit_depth=bit_depth, chroma_format=chroma_format, msb_aligned=msb_aligned, scale=scale, bias=bias,
+                                mean=mean, std=std)
+            return imports.import_yuvpack(self, list(pics), tensors, yuv, chroma_down, chroma_loc, size, on_stream)
         imports.import_tensors(self, list(pics), tensors, layout, pixel, bit_depth, chroma_format, chroma_down, chroma_loc, matrix,
                                full_range, msb_aligned, scale, bias, mean, std, size, on_stream)
 

@@ -227,6 +227,49 @@ def format_stage(chroma_format, chroma, chroma_down, chroma_loc, default_loc=0):
     return make_export_format(chroma_format, chroma, chroma_down, default_loc if chroma_loc is None else chroma_loc)
 
 
+# packed YUV (include/hmgpu.h "packed YUV"): per word format its chroma format, depth, bytes per element of the returned tensor and A's range
+YUVPACK_UYVY, YUVPACK_YUY2, YUVPACK_Y210, YUVPACK_Y216, YUVPACK_V210, YUVPACK_AYUV, YUVPACK_Y410, YUVPACK_Y416 = range(8)
+YUVPACKS = {"uyvy": YUVPACK_UYVY, "yuy2": YUVPACK_YUY2, "y210": YUVPACK_Y210, "y216": YUVPACK_Y216, "v210": YUVPACK_V210,
+            "ayuv": YUVPACK_AYUV, "y410": YUVPACK_Y410, "y416": YUVPACK_Y416}
+YUVPACK_CHROMA = {YUVPACK_UYVY: 2, YUVPACK_YUY2: 2, YUVPACK_Y210: 2, YUVPACK_Y216: 2, YUVPACK_V210: 2, YUVPACK_AYUV: 3, YUVPACK_Y410: 3,
+                  YUVPACK_Y416: 3}
+YUVPACK_DEPTH = {YUVPACK_UYVY: 8, YUVPACK_YUY2: 8, YUVPACK_Y210: 10, YUVPACK_Y216: 16, YUVPACK_V210: 10, YUVPACK_AYUV: 8, YUVPACK_Y410: 10,
+                 YUVPACK_Y416: 16}
+YUVPACK_ELEMENT = {YUVPACK_UYVY: 1, YUVPACK_YUY2: 1, YUVPACK_Y210: 2, YUVPACK_Y216: 2, YUVPACK_V210: 4, YUVPACK_AYUV: 1, YUVPACK_Y410: 4,
+                   YUVPACK_Y416: 2}
+
+
+def yuvpack_code(yuv):
+    """HMGPU_YUVPACK_* of a name ("uyvy" ... "y416") or of the code itself"""
+    if isinstance(yuv, int):
+        return yuv
+    if not isinstance(yuv, str) or yuv.lower() not in YUVPACKS:
+        raise ValueError("yuv: one of %s" % sorted(YUVPACKS))
+    return YUVPACKS[yuv.lower()]
+
+
+class ExportYuvPack(C.Structure):
+    _fields_ = [("format", C.c_int32), ("alpha", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+def make_export_yuvpack(yuv, alpha=0):
+    """yuv: YUVPACK_* or its name; alpha: the A of AYUV / Y410 / Y416"""
+    p = ExportYuvPack()
+    p.format, p.alpha = yuvpack_code(yuv), int(alpha)
+    return p
+
+
+class ImportYuvPack(C.Structure):
+    _fields_ = [("format", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+def make_import_yuvpack(yuv):
+    """yuv: YUVPACK_* or its name"""
+    p = ImportYuvPack()
+    p.format = yuvpack_code(yuv)
+    return p
+
+
 class ImportDesc(C.Structure):
     _fields_ = [("layout", C.c_int32), ("order", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32 * 2),
                 ("bytes_per_sample", C.c_int32), ("msb_aligned", C.c_int32), ("sample_type", C.c_int32), ("scale", C.c_float * 3),

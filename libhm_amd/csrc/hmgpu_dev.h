@@ -514,6 +514,26 @@ struct FmtConv {
   int32_t constant;                // kFmtConst: the sample at the chroma output depth
 };
 void launch_export_fmt(const ExportArgs& a, const FmtConv& f, hipStream_t s);
+// packed YUV export (k_export_yuvpack.hip, hmgpu_pictures_export_yuvpack; include/hmgpu.h "packed YUV"): Y, Cb and Cr of the format
+// export at 4:2:2 or 4:4:4, interleaved into words of the one destination dst[0] / pitch[0] / bstride[0].  ExportArgs as
+// launch_export_fmt takes it (w / h the output size in pixels; cw / ch are not read) and the conversion's FmtConv: kFmtConst for a
+// 4:0:0 source, kFmtVert without gain or loss where the source has the words' own chroma format.  A family per shape of the word
+// unit, what tells its members apart uniform:
+enum {
+  kPack422x8 = 0,                  // UYVY, YUY2: 4 bytes per 2 pixels, a lane 8 pixels
+  kPack422x16 = 1,                 // Y210, Y216: 4 uint16 per 2 pixels, a lane 4 pixels
+  kPackV210 = 2,                   // V210: 4 uint32 per 6 pixels, a lane one group
+  kPackAYUV = 3,                   // 4 bytes per pixel, a lane 4 pixels
+  kPackY410 = 4,                   // a uint32 per pixel, a lane 4 pixels
+  kPackY416 = 5                    // 4 uint16 per pixel, a lane 2 pixels
+};
+struct YuvPackArgs {
+  int32_t fam;                     // kPack*
+  int32_t yfirst;                  // kPack422x8: Y before its chroma sample (YUY2), else behind it (UYVY)
+  int32_t shift;                   // kPack422x16: every element shifted left (Y210: 6, Y216: 0)
+  uint32_t alpha;                  // the 4:4:4 families: A
+};
+void launch_export_yuvpack(const ExportArgs& a, const FmtConv& f, const YuvPackArgs& p, hipStream_t s);
 // scaled device export (k_export_scale.hip, hmgpu_picture_export_scaled).  One resampling table per axis of a plane class, in device
 // memory of the context: first[n], count[n], span[tiles][2] (the source samples [lo, hi) a tile of outputs reads), then the Q14 weights
 // tap-major (w[tap * n + i], zero beyond count[i])
@@ -769,7 +789,8 @@ struct ImportArgs {
   int16_t* c[kMaxExportBatch];     // Cb of chroma sample (0, 0) in the pair plane (Cr one element on)
   int32_t pitch_y, pitch_c;        // int16 elements
   int32_t n;                       // pictures
-  int32_t layout, elem;            // HMGPU_EXPORT_* of the source; element: 0 uint8, 1 uint16, 2 float16, 3 bfloat16, 4 float32
+  int32_t layout, elem;            // HMGPU_EXPORT_* of the source; element: 0 uint8, 1 uint16, 2 float16, 3 bfloat16, 4 float32;
+                                   // packed YUV words in src[0] (layout planar): 5 of 1-byte, 6 of 2-byte elements, 7 of dwords
   int32_t nch, pos[3];             // RGB: 0 three planes, else 3 / 4 elements per packed pixel and where R, G, B stand in it
   int32_t w, h, sw, sh;            // the coded picture and the source, luma samples
   int32_t mono, psx, psy;          // the picture: no chroma (then psx = psy = 0); chroma subsampling
@@ -787,6 +808,9 @@ struct ImportArgs {
   int64_t bstride[3];              // bytes between the planes of consecutive pictures
   float scale[3], bias[3];         // float elements: per source plane / colour
   int32_t coef[16];                // hmgpu_import_plan.coef
+  int32_t pk_ls, pk_lo;            // packed YUV, elements 5 / 6: luma sample x is element pk_ls * x + pk_lo of its row,
+  int32_t pk_cs, pk_co[2];         // chroma sample x of Cb / Cr element pk_cs * x + pk_co[0 / 1] (msb: the shift of Y210)
+  int32_t pk_v210;                 // element 7: V210 (else Y410)
 };
 void launch_import(const ImportArgs& a, hipStream_t s);
 // chroma of 4:2:2 / 4:4:4 pictures (k_cfmt.hip): cross-component prediction on the residual tiles, motion compensation of every inter

@@ -1,9 +1,9 @@
 // hmgpu_export.hip -- picture export of the host runtime: the shared validation rules under the export plans, scale tables and their
 // slots, window tables, colour LUTs, the rules and weights of the chroma stage, the weights and rules of the format export and the
-// rules of the warp; ExportReq, the stages of one
+// rules of the warp and of the packed YUV words; ExportReq, the stages of one
 // picture export as a record, with export_plan under every plan function and export_resolve under export_impl and every picture
 // destination check; export_impl's three argument builders (unscaled, scaled, warp with its per-call maps) (k_export.hip,
-// k_export_scale.hip, k_export_warp.hip, k_export_fmt.hip).  Also the rules and the stream bracket that the
+// k_export_scale.hip, k_export_warp.hip, k_export_fmt.hip, k_export_yuvpack.hip).  Also the rules and the stream bracket that the
 // side-information exports (hmgpu_side.hip) and the picture analyses (hmgpu_analysis.hip) take from here: hmgpu_host.h.
 #include "hmgpu_host.h"
 
@@ -89,6 +89,19 @@ hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_s
   for (int i = 0; i < n; i++) touch(c, pics[i]);
   commit_use(c);
   return HMGPU_OK;
+}
+
+// packed YUV: the table of the word formats (hmgpu_host.h)
+bool yuvpack_format(int format, YuvPackFormat* p) {
+  static const YuvPackFormat tab[8] = {
+    {2, 8, 1, kPack422x8, 0, 0, 0}, {2, 8, 1, kPack422x8, 1, 0, 0}, {2, 10, 2, kPack422x16, 0, 6, 0}, {2, 16, 2, kPack422x16, 0, 0, 0},
+    {2, 10, 4, kPackV210, 0, 0, 0}, {3, 8, 1, kPackAYUV, 0, 0, 255}, {3, 10, 4, kPackY410, 0, 0, 3}, {3, 16, 2, kPackY416, 0, 0, 65535}};
+  if (format < HMGPU_YUVPACK_UYVY || format > HMGPU_YUVPACK_Y416) return false;
+  *p = tab[format];
+  return true;
+}
+int yuvpack_row_bytes(const YuvPackFormat& p, int w) {
+  return p.fam == kPackV210 ? (w + 5) / 6 * 16 : p.fam == kPack422x8 ? 2 * w : p.fam == kPackY416 ? 8 * w : 4 * w;
 }
 
 }  // namespace hmgpu_host
@@ -920,6 +933,7 @@ struct ExportReq {
   const hmgpu_export_warp* wp = nullptr;
   const hmgpu_warp_map* maps = nullptr;
   const hmgpu_export_format* fmt = nullptr;
+  const hmgpu_export_yuvpack* pack = nullptr;        // packed YUV: validated by yuvpack_rules, d the planar call that defines its values
   bool format_stage = false;                         // the format entries: the format rules apply and the plan is the output format's
   bool need_sc = false, need_win = false, need_px = false;   // the entry is refused without that stage
   bool colour_stage = false;                         // the colour rules apply: the colour entries always, the wider ones with a LUT
@@ -1003,12 +1017,42 @@ static hmgpu_status format_rules(const hmgpu_seq_params* seq, int n, const Expor
   return base_plan(seq, n, q, out, r, shapes);
 }
 
+// Rules 1 to 5 of a packed YUV export, in the order include/hmgpu.h "packed YUV" gives, in front of the rules of the format export
+// that defines its values; *dd: the descriptor of that export (the planar layout at depth D in the container D needs)
+static hmgpu_status yuvpack_rules(const hmgpu_export_desc* d, const hmgpu_export_scale* sc, const hmgpu_export_tensor* t,
+                                  const hmgpu_export_format* f, const hmgpu_export_yuvpack* pack, hmgpu_export_desc* dd) {
+  if (!pack) return HMGPU_EINVAL;
+  for (int k = 0; k < 6; k++) if (pack->reserved[k]) return HMGPU_EINVAL;
+  YuvPackFormat pf;
+  if (!yuvpack_format(pack->format, &pf)) return HMGPU_EUNSUPPORTED;
+  const int B = pf.depth <= 8 ? 1 : 2;
+  if (!d || d->layout != HMGPU_EXPORT_PLANAR) return HMGPU_EINVAL;
+  for (int k = 0; k < 2; k++) if (d->bit_depth[k] != 0 && d->bit_depth[k] != pf.depth) return HMGPU_EINVAL;
+  if ((d->bytes_per_sample != 0 && d->bytes_per_sample != B) || d->msb_aligned != 0) return HMGPU_EINVAL;
+  if (!f || f->chroma_format != pf.cf) return HMGPU_EINVAL;
+  if (pack->alpha < 0 || pack->alpha > pf.amax) return HMGPU_EINVAL;
+  if (sc) return HMGPU_EUNSUPPORTED;
+  if (t && t->sample_type >= HMGPU_SAMPLE_F16 && t->sample_type <= HMGPU_SAMPLE_F32) return HMGPU_EUNSUPPORTED;
+  *dd = *d;
+  dd->bit_depth[0] = dd->bit_depth[1] = pf.depth;
+  dd->bytes_per_sample = B;
+  return HMGPU_OK;
+}
+
 static hmgpu_status export_plan(const hmgpu_seq_params* seq, int n, const ExportReq& q, hmgpu_export_plan* out, ExportCall* r, bool shapes) {
   if (!seq || !q.d || !out || (q.need_sc && !q.sc) || (q.need_px && !q.px)) return HMGPU_EINVAL;
   { const hmgpu_status st = base_plan(seq, n, q, out, r, shapes); if (st != HMGPU_OK) return st; }
   if (q.format_stage) {
     const hmgpu_status st = format_rules(seq, n, q, out, r, shapes);
     if (st != HMGPU_OK) { memset(out, 0, sizeof(*out)); return st; }
+  }
+  if (q.pack) {                                        // the planes of the format export become the one plane of words
+    YuvPackFormat pf;
+    yuvpack_format(q.pack->format, &pf);                // (accepted by yuvpack_rules in every entry: cannot fail)
+    const int W = out->width[0], H = out->height[0];
+    memset(out, 0, sizeof(*out));
+    out->planes = 1;
+    out->width[0] = W; out->height[0] = H; out->row_bytes[0] = yuvpack_row_bytes(pf, W);
   }
   if (q.warp && warp_sized(q.wp) && q.d->layout == HMGPU_EXPORT_RGB)
     for (int k = 0; k < out->planes; k++) {
@@ -1049,6 +1093,12 @@ static hmgpu_status export_resolve(hmgpu_ctx* c, int n, const ExportReq& q, void
   { const hmgpu_status st = export_plan(&c->seq, n, q, &r->plan, r, shapes); if (st != HMGPU_OK) return st; }
   r->d = *q.d;
   if (q.win && !r->differ) memcpy(r->d.crop, q.win[0].crop, sizeof(r->d.crop));
+  if (q.pack) {                                       // words: the unused planes, and the alignment of the format's element
+    YuvPackFormat pf;
+    yuvpack_format(q.pack->format, &pf);                // (accepted by yuvpack_rules in every entry: cannot fail)
+    if (dst[1] || dst[2]) return HMGPU_EINVAL;
+    if ((uintptr_t)dst[0] % pf.align || pitch_bytes[0] % pf.align || (bstride && bstride[0] % pf.align)) return HMGPU_EINVAL;
+  }
   if (!q.warp || warp_sized(q.wp)) {                  // (a warp without a size: refused below, by the warp rules at the latest)
     const hmgpu_status st = export_dst_ok(c, r->plan, elem_size(r->elem), n, dst, pitch_bytes, bstride, &r->vec, r->bs);
     if (st != HMGPU_OK) return st;
@@ -1128,6 +1178,29 @@ hmgpu_status hmgpu_export_format_plan_for(const hmgpu_seq_params* seq, const hmg
   ExportReq q(d, sc, t, win);
   q.fmt = fmt; q.format_stage = true;
   return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_yuvpack_plan_for(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_tensor* t, int32_t n,
+                                           const hmgpu_export_window win[], const hmgpu_export_format* fmt,
+                                           const hmgpu_export_yuvpack* pack, hmgpu_export_plan* out) {
+  if (!seq || !out) return HMGPU_EINVAL;
+  memset(out, 0, sizeof(*out));
+  hmgpu_export_desc dd;
+  { const hmgpu_status st = yuvpack_rules(d, nullptr, t, fmt, pack, &dd); if (st != HMGPU_OK) return st; }
+  ExportReq q(&dd, nullptr, t, win);
+  q.fmt = fmt; q.format_stage = true; q.pack = pack;
+  return plan_for(seq, n, q, out);
+}
+
+hmgpu_status hmgpu_export_yuvpack_destination_check(hmgpu_ctx* c, int32_t n, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                                    const hmgpu_export_tensor* t, const hmgpu_export_window windows[],
+                                                    const hmgpu_export_format* fmt, const hmgpu_export_yuvpack* pack, void* const dst[3],
+                                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  hmgpu_export_desc dd;
+  { const hmgpu_status st = yuvpack_rules(d, sc, t, fmt, pack, &dd); if (st != HMGPU_OK) return st; }
+  ExportReq q(&dd, nullptr, t, windows);
+  q.fmt = fmt; q.format_stage = true; q.pack = pack;
+  return destination_check(c, n, q, dst, pitch_bytes, batch_stride_bytes);
 }
 
 hmgpu_status hmgpu_export_format_scale_taps(const hmgpu_seq_params* seq, const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
@@ -1257,6 +1330,27 @@ static void launch_unscaled(hmgpu_ctx* c, int n, const hmgpu_pic* pics, const Ex
   a.w = r.plan.width[0]; a.h = r.plan.height[0];
   a.cw = r.plan.width[0] >> c->csx; a.ch = r.plan.height[0] >> c->csy;
   export_args_tail(a, c->seq, r, q.t, dst, pitch_bytes);
+  if (q.pack) {
+    // packed YUV: the conversion of the format export (none: one row of weight 4 through kFmtVert), then the words
+    YuvPackFormat pf;
+    yuvpack_format(q.pack->format, &pf);                // (accepted by yuvpack_rules in every entry: cannot fail)
+    FmtConv f;
+    if (pf.cf == c->seq.chroma_format) {
+      memset(&f, 0, sizeof(f));
+      f.cls = kFmtVert;
+      f.cs.wc = c->seq.width >> c->csx; f.cs.hc = c->seq.height >> c->csy;
+    } else {
+      fmt_conv(c->seq, *q.fmt, pf.depth, &f);
+    }
+    for (int i = 0; i < n; i++) {
+      const int x0 = r.differ ? q.win[i].crop[0] : d->crop[0], y0 = r.differ ? q.win[i].crop[2] : d->crop[2];
+      f.cs.x0[i] = (int16_t)(x0 >> c->csx); f.cs.y0[i] = (int16_t)(y0 >> c->csy);
+    }
+    YuvPackArgs pk;
+    pk.fam = pf.fam; pk.yfirst = pf.yfirst; pk.shift = pf.shift; pk.alpha = (uint32_t)q.pack->alpha;
+    launch_export_yuvpack(a, f, pk, hs);
+    return;
+  }
   if (r.fmt_out >= 0 && r.fmt_out != c->seq.chroma_format) {
     // a format export that converts: Y alone through the 4:0:0 path of k_export, else the chroma rows of the output format
     if (r.fmt_out == 0) { a.mono = 1; launch_export(a, nullptr, 0, nullptr, nullptr, hs); return; }
@@ -1456,6 +1550,17 @@ hmgpu_status hmgpu_pictures_export_format(hmgpu_ctx* c, int32_t n, const hmgpu_p
                                           int32_t on_stream, void* stream) {
   ExportReq q(d, sc, t, windows);
   q.fmt = fmt; q.format_stage = true;
+  return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+hmgpu_status hmgpu_pictures_export_yuvpack(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_export_desc* d, const hmgpu_export_scale* sc,
+                                           const hmgpu_export_tensor* t, const hmgpu_export_window windows[], const hmgpu_export_format* fmt,
+                                           const hmgpu_export_yuvpack* pack, void* const dst[3], const int64_t pitch_bytes[3],
+                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  hmgpu_export_desc dd;
+  { const hmgpu_status st = yuvpack_rules(d, sc, t, fmt, pack, &dd); if (st != HMGPU_OK) return st; }
+  ExportReq q(&dd, nullptr, t, windows);
+  q.fmt = fmt; q.format_stage = true; q.pack = pack;
   return export_impl(c, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
 

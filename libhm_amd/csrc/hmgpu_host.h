@@ -263,6 +263,13 @@ hmgpu_status scale_desc_ok(const hmgpu_export_scale* sc);
 hmgpu_status crop_ok(const hmgpu_seq_params* seq, const int32_t cr[4], const hmgpu_export_scale* sc, int* w, int* h);
 hmgpu_status window_ok(const hmgpu_seq_params* seq, const hmgpu_export_window& win, const hmgpu_export_scale* sc, int* w, int* h);
 bool device_span_ok(const void* p, size_t bytes, int device);
+// packed YUV (include/hmgpu.h "packed YUV"): what a word format is made of -- chroma format, depth, the alignment of its element, the
+// kernel family of the export (kPack*) with what tells its members apart, the largest A; false: no such format.  The export and the
+// import entries look a format up after their rules have accepted it (yuvpack_rules, import_yuvpack_rules): the later look-ups of a
+// call cannot fail.  yuvpack_row_bytes: the bytes of a row of w pixels
+struct YuvPackFormat { int cf, depth, align, fam, yfirst, shift, amax; };
+bool yuvpack_format(int format, YuvPackFormat* p);
+int yuvpack_row_bytes(const YuvPackFormat& p, int w);
 hmgpu_status export_open(hmgpu_ctx* c, int32_t on_stream, void* stream, hipStream_t* hs);
 hmgpu_status export_end(hmgpu_ctx* c, int n, const hmgpu_pic* pics, int32_t on_stream, hipStream_t hs);
 

@@ -156,9 +156,73 @@ void axis_taps(int gain, bool linear, int siting, int32_t* l, int32_t* r, int32_
   }
 }
 
+// Steps 1 and 2 of a packed YUV import (include/hmgpu.h), in front of the steps of the planar import that defines it; *dd: the
+// descriptor of that import, *pf: the word format
+hmgpu_status import_yuvpack_rules(const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack, hmgpu_import_desc* dd, YuvPackFormat* pf) {
+  if (!pack) return HMGPU_EINVAL;
+  for (int k = 0; k < 7; k++) if (pack->reserved[k]) return HMGPU_EINVAL;
+  if (!yuvpack_format(pack->format, pf)) return HMGPU_EUNSUPPORTED;
+  const int B = pf->depth <= 8 ? 1 : 2;
+  if (!d || d->layout != HMGPU_EXPORT_PLANAR || d->order != -1 || d->chroma_format != pf->cf) return HMGPU_EINVAL;
+  for (int k = 0; k < 2; k++) if (d->bit_depth[k] != 0 && d->bit_depth[k] != pf->depth) return HMGPU_EINVAL;
+  if ((d->bytes_per_sample != 0 && d->bytes_per_sample != B) || d->sample_type != HMGPU_SAMPLE_UINT || d->msb_aligned != 0) return HMGPU_EINVAL;
+  *dd = *d;
+  dd->bit_depth[0] = dd->bit_depth[1] = pf->depth;
+  dd->bytes_per_sample = B;
+  return HMGPU_OK;
+}
+
+// import_rules of a packed YUV source: the planar plan becomes the one plane of words
+hmgpu_status import_yuvpack_plan(const hmgpu_seq_params* seq, const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack,
+                                 hmgpu_import_plan* out, ImportRules* r, hmgpu_import_desc* dd, YuvPackFormat* pf) {
+  if (out) memset(out, 0, sizeof(*out));
+  if (!seq || !out) return HMGPU_EINVAL;
+  { const hmgpu_status st = import_yuvpack_rules(d, pack, dd, pf); if (st != HMGPU_OK) return st; }
+  { const hmgpu_status st = import_rules(seq, dd, out, r); if (st != HMGPU_OK) return st; }
+  const int sw = out->width[0], sh = out->height[0];
+  memset(out, 0, sizeof(*out));
+  out->planes = 1;
+  out->width[0] = sw; out->height[0] = sh; out->row_bytes[0] = yuvpack_row_bytes(*pf, sw);
+  return HMGPU_OK;
+}
+
+// the unused planes of a packed source
+bool only_plane_0(const void* const src[3]) { return !src || (!src[1] && !src[2]); }
+
 }  // namespace
 
 extern "C" {
+
+static hmgpu_status import_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack,
+                                bool packed, const void* const src[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                int32_t on_stream, void* stream);
+
+hmgpu_status hmgpu_import_yuvpack_plan_for(const hmgpu_seq_params* seq, const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack,
+                                           hmgpu_import_plan* out) {
+  ImportRules r;
+  hmgpu_import_desc dd;
+  YuvPackFormat pf;
+  return import_yuvpack_plan(seq, d, pack, out, &r, &dd, &pf);
+}
+
+hmgpu_status hmgpu_import_yuvpack_source_check(hmgpu_ctx* c, int32_t n, const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack,
+                                               const void* const src[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3]) {
+  if (!c) return HMGPU_EINVAL;
+  hmgpu_import_plan plan;
+  ImportRules r;
+  hmgpu_import_desc dd;
+  YuvPackFormat pf;
+  { const hmgpu_status st = import_yuvpack_plan(&c->seq, d, pack, &plan, &r, &dd, &pf); if (st != HMGPU_OK) return st; }
+  uint32_t vec;
+  { const hmgpu_status st = source_ok(c, n, plan, pf.align, src, pitch_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  return only_plane_0(src) ? HMGPU_OK : HMGPU_EINVAL;
+}
+
+hmgpu_status hmgpu_pictures_import_yuvpack(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* d,
+                                           const hmgpu_import_yuvpack* pack, const void* const src[3], const int64_t pitch_bytes[3],
+                                           const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  return import_impl(c, n, pics, d, pack, true, src, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
 
 hmgpu_status hmgpu_import_plan_for(const hmgpu_seq_params* seq, const hmgpu_import_desc* d, hmgpu_import_plan* out) {
   return import_rules(seq, d, out, nullptr);
@@ -176,10 +240,27 @@ hmgpu_status hmgpu_import_source_check(hmgpu_ctx* c, int32_t n, const hmgpu_impo
 
 hmgpu_status hmgpu_pictures_import(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* d, const void* const src[3],
                                    const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int32_t on_stream, void* stream) {
+  return import_impl(c, n, pics, d, nullptr, false, src, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
+
+// both imports: planes (packed false), or the words of `pack` in src[0], which are the planar source of the descriptor dd
+static hmgpu_status import_impl(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics[], const hmgpu_import_desc* d, const hmgpu_import_yuvpack* pack,
+                                bool packed, const void* const src[3], const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3],
+                                int32_t on_stream, void* stream) {
   if (!c) return HMGPU_EINVAL;
   hmgpu_import_plan plan;
   ImportRules r;
-  { const hmgpu_status st = import_rules(&c->seq, d, &plan, &r); if (st != HMGPU_OK) return st; }
+  hmgpu_import_desc dd;
+  YuvPackFormat pf;
+  if (packed) {
+    const hmgpu_status st = import_yuvpack_plan(&c->seq, d, pack, &plan, &r, &dd, &pf);
+    if (st != HMGPU_OK) return st;
+    d = &dd;
+    r.ES = pf.align;
+  } else {
+    const hmgpu_status st = import_rules(&c->seq, d, &plan, &r);
+    if (st != HMGPU_OK) return st;
+  }
   if (n < 1 || n > HMGPU_EXPORT_MAX_BATCH || !pics) return HMGPU_EINVAL;
   for (int i = 0; i < n; i++) {
     if (!valid_pic(c, pics[i])) return HMGPU_EINVAL;
@@ -187,6 +268,7 @@ hmgpu_status hmgpu_pictures_import(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics
   }
   uint32_t vec = 0;
   { const hmgpu_status st = source_ok(c, n, plan, r.ES, src, pitch_bytes, batch_stride_bytes, &vec); if (st != HMGPU_OK) return st; }
+  if (packed && !only_plane_0(src)) return HMGPU_EINVAL;
   if (on_stream != 0 && on_stream != 1) return HMGPU_EINVAL;
   if (on_stream && stream) {                                   // (export_open makes the same check, behind the picture state)
     hipDevice_t dev = -1;
@@ -218,6 +300,17 @@ hmgpu_status hmgpu_pictures_import(hmgpu_ctx* c, int32_t n, const hmgpu_pic pics
     a.msb[t] = d->msb_aligned ? 16 - r.D[t] : 0;
   }
   a.cconst = 1 << (r.D[1] - 1);
+  if (packed) {                                                // the accessor of the words; no whole-group loads of planes
+    // per format: luma stride and offset, chroma stride, Cb and Cr offsets, in elements
+    static const int8_t kAt[8][5] = {{2, 1, 4, 0, 2}, {2, 0, 4, 1, 3}, {2, 0, 4, 1, 3}, {2, 0, 4, 1, 3}, {0, 0, 0, 0, 0},
+                                     {4, 2, 4, 1, 0}, {0, 0, 0, 0, 0}, {4, 1, 4, 0, 2}};
+    const int8_t* at = kAt[pack->format];
+    a.elem = pf.align == 1 ? 5 : pf.align == 2 ? 6 : 7;
+    a.pk_ls = at[0]; a.pk_lo = at[1]; a.pk_cs = at[2]; a.pk_co[0] = at[3]; a.pk_co[1] = at[4];
+    a.pk_v210 = pack->format == HMGPU_YUVPACK_V210;
+    a.msb[0] = a.msb[1] = pf.shift;
+    vec = 0;
+  }
   for (int k = 0; k < 3; k++) {
     a.scale[k] = d->scale[k]; a.bias[k] = d->bias[k];
     if (k < plan.planes) { a.src[k] = (const uint8_t*)src[k]; a.pitch[k] = pitch_bytes[k]; a.bstride[k] = batch_stride_bytes[k]; }

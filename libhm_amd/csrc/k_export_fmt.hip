@@ -7,34 +7,17 @@
 // format: its one to three source rows are chosen and clamped to the decoded plane before the loads (uniform per workgroup; a row
 // without weight is not loaded), every load's address is known before the first load is consumed, and columns are clamped as selects
 // behind whole-group loads (chroma_core.h's argument: a column outside the plane is read from the plane's margin, whatever it holds,
-// and replaced by the edge sample before use).  The furthest a lane reaches: one pair left of pair 0 (kFmtUp, kFmtDown) and, the
+// and replaced by the edge sample before use).  The rows and the arithmetic of the classes are fmt_core.h's, shared with
+// k_export_yuvpack.hip.  The furthest a lane reaches: one pair left of pair 0 (kFmtUp, kFmtDown) and, the
 // last lane of a row, 5 pairs beyond the last source pair of the window (kFmtDown: pairs 2x .. 2x + 7 for x <= cw - 1) or 2 (the
 // others); the pair planes keep 128 >> csx pairs of margin on both sides, 128 for the 4:4:4 planes kFmtDown reads.
 // One instance per layout, output element and class (FmtConv), so nothing per sample branches on the format or the filter: REPLICATE
 // and DROP are the same instances with a single weight 4 per axis, which the rounding returns exactly.
 #include "hmgpu_dev.h"
 #include "export_core.h"
+#include "fmt_core.h"
 
 namespace hmgpu {
-
-namespace {
-
-// the source rows (plane coordinates, clamped) of output chroma row Y (plane coordinates of the output format) and their weights in
-// quarters, which sum to 4; a row without weight repeats the one before it
-__device__ inline void fmt_rows(const FmtConv& f, int Y, int ri[3], int rw[3]) {
-  if (f.vgain) {
-    chroma_rows(f.cs, Y, 1, &ri[0], &ri[1], &rw[0]);
-    rw[1] = 4 - rw[0]; rw[2] = 0;
-  } else if (f.vloss) {
-    for (int k = 0; k < 3; k++) { ri[k] = min(f.cs.hc - 1, max(0, 2 * Y + f.dv0 + k)); rw[k] = f.dv[k]; }
-  } else {
-    ri[0] = Y; rw[0] = 4; rw[1] = rw[2] = 0;
-  }
-  if (!rw[1]) ri[1] = ri[0];
-  if (!rw[2]) ri[2] = ri[1];
-}
-
-}  // namespace
 
 template <int LAYOUT, int ELEM, int CLS>
 __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const FmtConv f) {
@@ -62,7 +45,7 @@ __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const Fm
     const int16_t* const ac = a.c[pic];
     const int x0 = f.cs.x0[pic], y0 = f.cs.y0[pic];
     int ri[3], rw[3];
-    fmt_rows(f, (f.vgain ? y0 << 1 : f.vloss ? y0 >> 1 : y0) + rc, ri, rw);
+    fmt_rows_at(f, y0, rc, ri, rw);
     int c[8];
     if constexpr (CLS == kFmtUp) {
       // source pairs J - 1 .. J + 2 (J = the pair of output pair x) of two rows: the sited fetch of four luma samples
@@ -80,7 +63,7 @@ __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const Fm
           load8(cp, vec, p[k]);
         }
       }
-      for (int i = 0; i < 8; i++) c[i] = (4 * (rw[0] * p[0][i] + rw[1] * p[1][i] + rw[2] * p[2][i]) + 8) >> 4;
+      fmt_vert<4>(rw, p, c);
     } else {
       // kFmtDown: source pairs 2x - 1 .. 2x + 7 on every row that has a weight
       int p[3][18];
@@ -93,12 +76,7 @@ __global__ void __launch_bounds__(256) k_export_fmt(const ExportArgs a, const Fm
           chroma_pair(cp - kCStep, &p[k][0], &p[k][1]);
         }
       }
-      int v[18];
-      for (int i = 0; i < 18; i++) v[i] = rw[0] * p[0][i] + rw[1] * p[1][i] + rw[2] * p[2][i];
-      if (x0 + 2 * x == 0) { v[0] = v[2]; v[1] = v[3]; }         // the plane's first column has no left neighbour
-      for (int j = 0; j < 4; j++)
-        for (int e = 0; e < 2; e++)
-          c[2 * j + e] = (f.dh[0] * v[4 * j + e] + f.dh[1] * v[4 * j + 2 + e] + f.dh[2] * v[4 * j + 4 + e] + 8) >> 4;
+      fmt_down<4>(f, rw, p, x0 + 2 * x, c);
     }
     for (int i = 0; i < 8; i++) o[i] = (uint32_t)depth_conv(c[i], a.sh[1], a.maxv[1]);
   }

@@ -7,13 +7,15 @@
 // bytes of a plane row.  A run of eight source elements -- of eight packed pixels -- that lies inside the source and whose plane
 // is aligned to eight elements (ImportArgs::vec) is read with whole 8- or 16-byte loads; every other element -- unaligned planes, the
 // ragged last group, the columns and rows the padding rule repeats, the taps of a chroma conversion -- is loaded on its own with its
-// index clamped to the source.  The kernel writes the coded w x h samples of each plane and nothing else: no margin, no other picture.  No LDS, no scratch.
+// index clamped to the source.  Packed YUV words (hmgpu_pictures_import_yuvpack) are three more element kinds of the YUV instance: a
+// sample is fetched from its word by a per-format accessor (pk_raw), element by element with the same clamped indices, and everything
+// behind the fetch is the code of the planar source.  The kernel writes the coded w x h samples of each plane and nothing else: no margin, no other picture.  No LDS, no scratch.
 #include "hmgpu_dev.h"
 
 namespace hmgpu {
 namespace {
 
-enum { kImpU8 = 0, kImpU16 = 1, kImpF16 = 2, kImpBF16 = 3, kImpF32 = 4 };
+enum { kImpU8 = 0, kImpU16 = 1, kImpF16 = 2, kImpBF16 = 3, kImpF32 = 4, kImpPk8 = 5, kImpPk16 = 6, kImpPk32 = 7 };
 template <int EL> constexpr int kElemBytes = EL == kImpU8 ? 1 : EL == kImpF32 ? 4 : 2;
 
 // element idx of a row, as its bits
@@ -72,10 +74,29 @@ __device__ inline void raw8_px(const uint8_t* row, int idx, const int32_t pos[3]
   }
 }
 
+// packed YUV: sample x of component comp (0 Y, 1 Cb, 2 Cr; x in that component's plane) of a row of words, as its bits.  Elements:
+// at a uniform stride and offset.  V210: field p of the group's twelve (Y i: 2 i + 1, Cb m: 4 m, Cr m: 4 m + 2), three to a dword
+// from bit 0.  Y410: Cb, Y, Cr from bits 0, 10, 20 of the pixel's dword
+template <int EL>
+__device__ inline uint32_t pk_raw(const ImportArgs& a, const uint8_t* row, int x, int comp) {
+  if constexpr (EL == kImpPk32) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(row);
+    if (a.pk_v210) {
+      const int per = comp ? 3 : 6, g = x / per, i = x - g * per, p = comp ? 4 * i + 2 * (comp - 1) : 2 * i + 1;
+      return (ldg(w + 4 * g + p / 3) >> (10 * (p % 3))) & 0x3ff;
+    }
+    return (ldg(w + x) >> (comp == 0 ? 10 : comp == 1 ? 0 : 20)) & 0x3ff;
+  } else {
+    const int idx = comp ? a.pk_cs * x + a.pk_co[comp - 1] : a.pk_ls * x + a.pk_lo;
+    if constexpr (EL == kImpPk8) return ldg(row + idx);
+    else return ldg(reinterpret_cast<const uint16_t*>(row) + idx);
+  }
+}
+
 // the integer of an element at the source depth of channel type t; k: the plane (colour) whose scale and bias a float element takes
 template <int EL>
 __device__ inline int code_of(const ImportArgs& a, uint32_t raw, int t, int k) {
-  if constexpr (EL == kImpU8 || EL == kImpU16) {
+  if constexpr (EL == kImpU8 || EL == kImpU16 || EL >= kImpPk8) {
     return min((int)(raw >> a.msb[t]), a.smax[t]);
   } else {
     float f;
@@ -101,14 +122,19 @@ __device__ inline const uint8_t* src_row(const ImportArgs& a, int k, int pic, in
 // luma sample (x, y) of the source, both inside it
 template <int EL>
 __device__ inline int yuv_luma(const ImportArgs& a, int pic, int x, int y) {
-  return to_coding(a, code_of<EL>(a, raw_at<EL>(src_row(a, 0, pic, y), x), 0, 0), 0);
+  if constexpr (EL >= kImpPk8) return to_coding(a, code_of<EL>(a, pk_raw<EL>(a, src_row(a, 0, pic, y), x, 0), 0, 0), 0);
+  else return to_coding(a, code_of<EL>(a, raw_at<EL>(src_row(a, 0, pic, y), x), 0, 0), 0);
 }
 // chroma sample (x, y) of component comp (1 / 2) of the source's own format, both inside its plane, at the source depth
 template <int EL>
 __device__ inline int yuv_chroma_src(const ImportArgs& a, int pic, int comp, int x, int y) {
-  const bool semi = a.layout == HMGPU_EXPORT_SEMIPLANAR;
-  const uint8_t* row = src_row(a, semi ? 1 : comp, pic, y);
-  return code_of<EL>(a, raw_at<EL>(row, semi ? 2 * x + comp - 1 : x), 1, comp);
+  if constexpr (EL >= kImpPk8) {
+    return code_of<EL>(a, pk_raw<EL>(a, src_row(a, 0, pic, y), x, comp), 1, comp);
+  } else {
+    const bool semi = a.layout == HMGPU_EXPORT_SEMIPLANAR;
+    const uint8_t* row = src_row(a, semi ? 1 : comp, pic, y);
+    return code_of<EL>(a, raw_at<EL>(row, semi ? 2 * x + comp - 1 : x), 1, comp);
+  }
 }
 
 // ---- RGB sources
@@ -212,7 +238,7 @@ __global__ __launch_bounds__(256) void k_import(const ImportArgs a) {
         }
       }
     } else {
-      if (inside && (a.vec & 1)) {
+      if (EL < kImpPk8 && inside && (a.vec & 1)) {
         uint32_t q[8];
         raw8<EL>(src_row(a, 0, pic, ys), X0, q);
         for (int i = 0; i < 8; i++) yv[r][i] = to_coding(a, code_of<EL>(a, q[i], 0, 0), 0);
@@ -230,7 +256,7 @@ __global__ __launch_bounds__(256) void k_import(const ImportArgs a) {
         if (j >= np) break;
         cv[2 * j] = fcb[0][j << a.psx]; cv[2 * j + 1] = fcr[0][j << a.psx];
       }
-    } else if (!RGB && inside && a.same && a.layout == HMGPU_EXPORT_SEMIPLANAR && (a.vec & 2)) {
+    } else if (!RGB && EL < kImpPk8 && inside && a.same && a.layout == HMGPU_EXPORT_SEMIPLANAR && (a.vec & 2)) {
       // the source's pair plane has the picture's shape: np pairs are 2 * np consecutive elements
 #pragma unroll
       for (int g = 0; g < 2; g++) {
@@ -279,7 +305,10 @@ void launch_import(const ImportArgs& a, hipStream_t s) {
   const dim3 block(32, 8);
   const int groups = (a.w + 7) / 8, units = a.h >> a.psy;
   const dim3 grid((groups + 31) / 32, (units + 7) / 8, a.n);
-  if (a.layout != HMGPU_EXPORT_RGB) launch_elem<false, false>(a, grid, block, s);
+  if (a.elem == kImpPk8) hipLaunchKernelGGL((k_import<kImpPk8, false, false>), grid, block, 0, s, a);
+  else if (a.elem == kImpPk16) hipLaunchKernelGGL((k_import<kImpPk16, false, false>), grid, block, 0, s, a);
+  else if (a.elem == kImpPk32) hipLaunchKernelGGL((k_import<kImpPk32, false, false>), grid, block, 0, s, a);
+  else if (a.layout != HMGPU_EXPORT_RGB) launch_elem<false, false>(a, grid, block, s);
   else if (a.nch) launch_elem<true, true>(a, grid, block, s);
   else launch_elem<true, false>(a, grid, block, s);
 }

@@ -1083,6 +1083,9 @@ hmgpu_status Decoder::export_pictures(int n, PicData* const* pics, const ExportR
       case ExportRequest::FORMAT:
         return check ? hmgpu_export_format_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.format, d, pitch_bytes, bs)
                      : hmgpu_pictures_export_format(c, rn, rh, q.desc, q.scale, q.tensor, w, q.format, d, pitch_bytes, bs, on_stream, stream);
+      case ExportRequest::YUVPACK:
+        return check ? hmgpu_export_yuvpack_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.format, q.pack, d, pitch_bytes, bs)
+                     : hmgpu_pictures_export_yuvpack(c, rn, rh, q.desc, q.scale, q.tensor, w, q.format, q.pack, d, pitch_bytes, bs, on_stream, stream);
       case ExportRequest::COLOUR:
         return check ? hmgpu_export_colour_destination_check(c, rn, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs)
                      : hmgpu_pictures_export_colour(c, rn, rh, q.desc, q.scale, q.tensor, w, q.pixel, h, d, pitch_bytes, bs, on_stream, stream);

@@ -23,9 +23,9 @@ namespace hmdec {
 // The stages of a batched picture export, as the hmdec_pictures_export* entries fill them and Decoder::export_pictures hands them to
 // the hmgpu entry of the same name.  entry: whose rules hold for an absent stage -- PLAIN: hmgpu_pictures_export, _windows (windows
 // set) or _pixels (pixel set); COLOUR: lut 0 is refused; CHROMA: lut 0 is no colour stage; WARP: chroma null is "replicate" too;
-// FORMAT: the YUV layouts at the chroma format of `format`, windows null or set
+// FORMAT: the YUV layouts at the chroma format of `format`, windows null or set; YUVPACK: FORMAT's values as the words of `pack`
 struct ExportRequest {
-  enum Entry { PLAIN, COLOUR, CHROMA, WARP, FORMAT } entry = PLAIN;
+  enum Entry { PLAIN, COLOUR, CHROMA, WARP, FORMAT, YUVPACK } entry = PLAIN;
   const hmgpu_export_desc* desc = nullptr;
   const hmgpu_export_scale* scale = nullptr;
   const hmgpu_export_tensor* tensor = nullptr;
@@ -36,6 +36,7 @@ struct ExportRequest {
   const hmgpu_export_warp* warp = nullptr;
   const hmgpu_warp_map* maps = nullptr;                    // one per picture
   const hmgpu_export_format* format = nullptr;
+  const hmgpu_export_yuvpack* pack = nullptr;
 };
 
 class Decoder {

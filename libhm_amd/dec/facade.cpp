@@ -378,6 +378,14 @@ int hmdec_pictures_export_format(libHMDec_context* ctx, int n, libHMDec_picture*
   q.format = format;
   return export_request(ctx, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
 }
+int hmdec_pictures_export_yuvpack(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
+                                  const hmgpu_export_scale* scale, const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[],
+                                  const hmgpu_export_format* format, const hmgpu_export_yuvpack* pack, void* const dst[3],
+                                  const int64_t pitch_bytes[3], const int64_t batch_stride_bytes[3], int on_stream, void* stream) {
+  ExportRequest q = request(ExportRequest::YUVPACK, desc, scale, tensor, windows);
+  q.format = format; q.pack = pack;
+  return export_request(ctx, n, pics, q, dst, pitch_bytes, batch_stride_bytes, on_stream, stream);
+}
 int hmdec_pictures_export_warp(libHMDec_context* ctx, int n, libHMDec_picture* const pics[], const hmgpu_export_desc* desc,
                                const hmgpu_export_tensor* tensor, const hmgpu_export_window windows[], const hmgpu_export_pixel* pixel,
                                int64_t lut, const hmgpu_export_chroma* chroma, const hmgpu_export_warp* warp, const hmgpu_warp_map maps[],

@@ -481,11 +481,13 @@ def out_pixels(out, plan, desc, px, device, n=None, dtype=None):
     return out.data_ptr(), sy * es, st[0] * es if b else None
 
 
-class Stages(collections.namedtuple("Stages", "scale tensor windows pixel lut chroma warp format", defaults=(None,) * 8)):
+class Stages(collections.namedtuple("Stages", "scale tensor windows pixel lut chroma warp format yuvpack", defaults=(None,) * 9)):
     """the stages of one picture export, None where the call has none: scale an abi.ExportScale; tensor an abi.ExportTensor (float
     elements); windows one abi.ExportWindow per picture; pixel an abi.ExportPixel (packed pixels: one destination); lut a colour LUT
     of the context or decoder, or its raw handle; chroma an abi.ExportChroma; warp (abi.ExportWarp, abi.WarpMap array) of
-    abi.warp_stage; format an abi.ExportFormat (the YUV layouts at another chroma format).  libhm_amd.export_stages_plan, Context.export_stages_into and hmdec's dispatcher choose the entry from it."""
+    abi.warp_stage; format an abi.ExportFormat (the YUV layouts at another chroma format); yuvpack an abi.ExportYuvPack (YUV interleaved
+    into words: one destination, with the format stage of the words' chroma format).  libhm_amd.export_stages_plan,
+    Context.export_stages_into and hmdec's dispatcher choose the entry from it."""
     __slots__ = ()
 
     def shape_only(self):
@@ -537,6 +539,84 @@ def export_tensors(call, seq, device, layout, bit_depth, crop, matrix, full_rang
                 out = alloc_outputs(plan, desc, device, n, dtype, stacked)
             ptrs, pitches, bstrides = out_spans(out, plan, desc, device, n, dtype, stacked)
         call(desc, stages, ptrs, pitches, bstrides, torch.cuda.current_stream(device).cuda_stream if on_stream else 0)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ packed YUV (include/hmgpu.h "packed YUV")
+def yuvpack_shape(code, plan, row_align=1):
+    """(shape, torch dtype, pitch in bytes) of one picture's tensor of words: [H, W, 2] / [H, W, 4] elements of 1 or 2 bytes, [H, W]
+    int32 (Y410), [H, P / 4] int32 (V210) with P = row_bytes rounded up to row_align (a multiple of 4)"""
+    import torch
+    h, w, rb = plan.height[0], plan.width[0], plan.row_bytes[0]
+    es = abi.YUVPACK_ELEMENT[code]
+    dt = torch.int32 if es == 4 else torch_dtype(es)
+    if code == abi.YUVPACK_V210:
+        row_align = int(row_align)
+        if row_align < 1 or row_align % 4:
+            if row_align != 1:
+                raise ValueError("row_align: 1 or a multiple of 4 bytes")
+            row_align = 4
+        p = (rb + row_align - 1) // row_align * row_align
+        return (h, p // 4), dt, p
+    if row_align != 1:
+        raise ValueError("row_align belongs to yuv=\"v210\"")
+    if code == abi.YUVPACK_Y410:
+        return (h, w), dt, rb
+    return (h, w, rb // (w * es)), dt, rb
+
+
+def yuvpack_span(t, code, plan, device, n=None, row_align=1):
+    """a caller's tensor of words as (pointer, pitch in bytes, batch stride in bytes or None): the shape and dtype of yuvpack_shape
+    (16-bit: int16 as well), the words of a row dense, rows and batch entries any stride apart"""
+    import torch
+    shape, dt, _ = yuvpack_shape(code, plan, row_align)
+    lead = () if n is None else (n,)
+    b = len(lead)
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != lead + shape:
+        raise ValueError("a %s tensor of shape %s" % (dt, lead + shape))
+    if t.dtype != dt and not (t.element_size() == 2 and t.dtype == torch.int16 and abi.YUVPACK_ELEMENT[code] == 2):
+        raise ValueError("dtype %s, the words are %s" % (t.dtype, dt))
+    if t.get_device() != device:
+        raise ValueError("on device %d, the context is on %d" % (t.get_device(), device))
+    st, es = t.stride(), t.element_size()
+    inner = (1,) if len(shape) == 2 else (shape[2], 1)
+    row = shape[1] * inner[0]
+    if tuple(st[b + 1:]) != inner or (shape[0] > 1 and st[b] < row) or (b and n > 1 and st[0] < st[b] * (shape[0] - 1) + row):
+        raise ValueError("the words of a row must be dense, rows and batch entries apart (stride %s)" % (st,))
+    return t.data_ptr(), st[b] * es, st[0] * es if b else None
+
+
+def yuvpack_only(**others):
+    """yuv= of the Python exports goes with crop, windows, flip, alpha, chroma, chroma_down, chroma_loc, out, row_align and on_stream:
+    any other keyword that was given (not None / False) is refused"""
+    given = sorted(k for k, v in others.items() if v is not None and v is not False)
+    if given:
+        raise ValueError("yuv= does not go with %s" % ", ".join(given))
+
+
+def yuvpack_stages(yuv, alpha, windows, chroma, chroma_down, chroma_loc):
+    """(code, Stages) of yuv= / alpha= and the conversion keywords"""
+    code = abi.yuvpack_code(yuv)
+    fmt = abi.format_stage(abi.YUVPACK_CHROMA[code], chroma, chroma_down, chroma_loc)
+    return code, Stages(windows=windows, format=fmt, yuvpack=abi.make_export_yuvpack(code, 0 if alpha is None else alpha))
+
+
+def export_yuvpack(call, seq, device, yuv, alpha, crop, windows, chroma, chroma_down, chroma_loc, on_stream=True, out=None, n=None, row_align=1):
+    """export_tensors for YUV interleaved into words: allocate the one tensor (or take `out`) and run `call`; windows: None, or the
+    abi.ExportWindow of every picture (`crop` already part of them)"""
+    import torch
+    from . import export_stages_plan
+    code, stages = yuvpack_stages(yuv, alpha, windows, chroma, chroma_down, chroma_loc)
+    d = abi.YUVPACK_DEPTH[code]
+    desc = abi.make_export_desc(abi.EXPORT_PLANAR, (d, d), 1 if d <= 8 else 2, False, tuple(crop) if windows is None else (0, 0, 0, 0), 1, 0)
+    plan = export_stages_plan(seq, desc, stages, n or 1)
+    with torch.cuda.device(device):
+        if out is None:
+            shape, dt, _ = yuvpack_shape(code, plan, row_align)
+            out = torch.empty((() if n is None else (n,)) + shape, dtype=dt, device=torch.device("cuda", device))
+        ptr, pitch, bstride = yuvpack_span(out, code, plan, device, n, row_align)
+        call(desc, stages, [ptr], [pitch], [bstride] if bstride is not None else stage_extents(plan, [pitch]),
+             torch.cuda.current_stream(device).cuda_stream if on_stream else 0)
     return out
 
 

@@ -95,6 +95,10 @@ def lib():
                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
                                                    C.POINTER(abi.ExportFormat), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                    C.POINTER(C.c_int64), C.c_int, C.c_void_p]
+        L.hmdec_pictures_export_yuvpack.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
+                                                    C.POINTER(abi.ExportScale), C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow),
+                                                    C.POINTER(abi.ExportFormat), C.POINTER(abi.ExportYuvPack), C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p]
         L.hmdec_pictures_export_warp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(abi.ExportDesc),
                                                  C.POINTER(abi.ExportTensor), C.POINTER(abi.ExportWindow), C.POINTER(abi.ExportPixel),
                                                  C.c_int64, C.POINTER(abi.ExportChroma), C.POINTER(abi.ExportWarp), C.POINTER(abi.WarpMap),
@@ -267,7 +271,8 @@ class Picture:
 
     def export(self, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, pixel=None, alpha=None, lut=None,
-               chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop"):
+               chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop", yuv=None,
+               row_align=1):
         """The picture converted on its GPU into new torch tensors, written on torch.cuda.current_stream() (libhm_amd.export):
         RGB [3, H, W]; planar (Y, Cb, Cr); semi-planar (Y, CbCr [H, W, 2]).  bit_depth: int, (luma, chroma) or None (coding depths);
         crop: "conformance", None (whole picture) or (left, right, top, bottom) luma samples; matrix / full_range: None = from the
@@ -285,12 +290,13 @@ class Picture:
         "nearest", border "edge" or "fill" with fill=(r, g, b) (hmdec_pictures_export_warp).  chroma_format (layouts "planar" /
         "semiplanar"): None, or "400" / "420" / "422" / "444" (0 .. 3): Cb and Cr at that chroma format (hmdec_pictures_export_format)
         -- chroma "replicate" / "linear" where an axis gains samples, chroma_down "drop" / "linear" where it loses them, at
-        chroma_loc as above; planar with "444" returns ONE [3, H, W] tensor (Y, Cb, Cr), as Context.export does.  Valid until the
-        next push into the decoder."""
+        chroma_loc as above; planar with "444" returns ONE [3, H, W] tensor (Y, Cb, Cr), as Context.export does.  yuv ("uyvy" ... "y416"), with
+        alpha and row_align: Y, Cb and Cr interleaved into words, one tensor, as Context.export_batch describes
+        (hmdec_pictures_export_yuvpack).  Valid until the next push into the decoder."""
         from . import export
         return _export([self], None, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std, scale, bias,
                        pixel=pixel, alpha=alpha, lut=lut, chroma=chroma, chroma_loc=chroma_loc, warp=export.one_map(warp), border=border,
-                       fill=fill, chroma_format=chroma_format, chroma_down=chroma_down)
+                       fill=fill, chroma_format=chroma_format, chroma_down=chroma_down, yuv=yuv, row_align=row_align)
 
     def motion(self, form="blocks", lists=(0, 1), size=None, window=None, flip=False, dtype=None, crop=None):
         """export_motion_batch of this picture alone, the tensors without the batch dimension; window: one (x, y, w, h) or None"""
@@ -528,7 +534,8 @@ def export_motion_batch(pictures, form="blocks", lists=(0, 1), size=None, window
 
 def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype=None, mean=None, std=None,
             scale=None, bias=None, enqueue=True, windows=None, flip=None, pixel=None, alpha=None, memory_format=None, lut=None,
-            chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop"):
+            chroma="replicate", chroma_loc=None, warp=None, border="edge", fill=None, chroma_format=None, chroma_down="drop", yuv=None,
+            row_align=1):
     """Picture.export (n None: pictures[0], no batch dimension) and export_batch (n = len(pictures)): geometry, crop and colour from
     the first picture; libhm_amd.export.export_tensors does the rest.  enqueue False: only the tensors of n pictures are allocated.
     windows / flip: per picture, relative to crop (export.make_windows); pixel / alpha / memory_format: packed pixels
@@ -537,11 +544,22 @@ def _export(pictures, n, layout, bit_depth, crop, matrix, full_range, msb_aligne
     VUI sample location for chroma_loc None; "replicate" through the entries it always took; warp / border / fill: one map per
     picture (abi.warp_stage) through hmdec_pictures_export_warp, whatever the other stages; chroma_format / chroma_down: the YUV
     layouts at another chroma format through hmdec_pictures_export_format, chroma= then its up-conversion, the sample location
-    found as for chroma "linear\""""
+    found as for chroma "linear"; yuv / alpha / row_align: YUV interleaved into words through hmdec_pictures_export_yuvpack
+    (export.export_yuvpack), the conversion keywords as for chroma_format"""
     from . import export
     first, seq, crop = _prologue(pictures, "export", crop, lambda: (0, 0, 0, 0))
     col = first.colour()
     count = n if not enqueue else len(pictures)
+    if yuv is None and row_align != 1:
+        raise ValueError("row_align belongs to yuv=")
+    if yuv is not None:
+        export.yuvpack_only(size=size, dtype=dtype, mean=mean, std=std, scale=scale, bias=bias, pixel=pixel, memory_format=memory_format, lut=lut,
+                            warp=warp, fill=fill, chroma_format=chroma_format, msb_aligned=msb_aligned)
+        return export.export_yuvpack(lambda desc, stages, ptrs, pitches, bstrides, st:
+                                     _export_stages(pictures, seq, desc, stages, ptrs, pitches, bstrides, st) if enqueue else None,
+                                     seq, _device(first, "export"), yuv, alpha, crop, export.make_windows(seq, crop, windows, flip, count),
+                                     chroma, chroma_down, first.chroma_loc()["top_field"] if chroma_loc is None else chroma_loc, True, out, n,
+                                     row_align)
     fmt = abi.format_stage(chroma_format, chroma, chroma_down, chroma_loc, first.chroma_loc()["top_field"] if chroma_format is not None else 0)
     chr_ = abi.chroma_stage(chroma, chroma_loc, first.chroma_loc()["top_field"]) if fmt is None else None
     wrp = abi.warp_stage(warp, size, filter, border, fill, count)
@@ -565,14 +583,16 @@ def _export_stages(pictures, seq, desc, stages, ptrs, pitches, bstrides, stream)
     from . import HmgpuError, export, export_stages_plan
     s = stages
     if bstrides is None:
-        if s[1:] == (None,) * 7:
+        if s[1:] == (None,) * 8:
             return pictures[0].export_into(desc, ptrs, pitches, 1, stream, s.scale)
         bstrides = export.stage_extents(export_stages_plan(seq, desc, s.shape_only(), 1), pitches)
     head = (pictures[0].ctx, len(pictures), _handles(pictures), C.byref(desc))
     mid = (abi.ref(s.scale), abi.ref(s.tensor), abi.window_array(s.windows), abi.ref(s.pixel))
     tail = (abi.ptr_array(ptrs), abi.i64_array(pitches), abi.i64_array(bstrides), 1, abi.addr(stream))
     handle = getattr(s.lut, "handle", s.lut)
-    if s.format is not None:
+    if s.yuvpack is not None:
+        name, args = "hmdec_pictures_export_yuvpack", head + mid[:3] + (abi.ref(s.format), C.byref(s.yuvpack)) + tail
+    elif s.format is not None:
         name, args = "hmdec_pictures_export_format", head + mid[:3] + (C.byref(s.format),) + tail
     elif s.warp is not None:
         name, args = "hmdec_pictures_export_warp", head + mid[1:] + (handle or 0, abi.ref(s.chroma), C.byref(s.warp[0]), s.warp[1]) + tail
@@ -594,7 +614,7 @@ def _export_stages(pictures, seq, desc, stages, ptrs, pitches, bstrides, stream)
 def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix=None, full_range=None, msb_aligned=False, size=None,
                  filter="bilinear", out=None, dtype=None, mean=None, std=None, scale=None, bias=None, windows=None, flip=None,
                  pixel=None, alpha=None, memory_format=None, lut=None, chroma="replicate", chroma_loc=None, warp=None, border="edge",
-                 fill=None, chroma_format=None, chroma_down="drop"):
+                 fill=None, chroma_format=None, chroma_down="drop", yuv=None, row_align=1):
     """Up to 16 pictures a decoder has put out (and that are still valid: fetched since the last push), of one sequence and on one
     GPU, converted in one call (hmdec_pictures_export) into tensors with a leading batch dimension, written on
     torch.cuda.current_stream(): RGB [N, 3, H, W]; planar ([N, H, W], ...); semi-planar ([N, H, W], [N, Hc, Wc, 2]).  The arguments
@@ -605,13 +625,16 @@ def export_batch(pictures, layout="rgb", bit_depth=8, crop="conformance", matrix
     Picture.export -- hmdec_pictures_export_colour; chroma / chroma_loc as in Picture.export, the sample location that of the first
     picture -- hmdec_pictures_export_chroma; warp / border / fill as in Context.export_batch: one inverse affine map per picture,
     size= the output size, the windows of any sizes -- hmdec_pictures_export_warp; chroma_format / chroma_down as in
-    Picture.export: the YUV layouts at another chroma format, planar "444" as ONE [N, 3, H, W] tensor -- hmdec_pictures_export_format)."""
+    Picture.export: the YUV layouts at another chroma format, planar "444" as ONE [N, 3, H, W] tensor --
+    hmdec_pictures_export_format; yuv / alpha / row_align as in Context.export_batch: YUV interleaved into words, one tensor --
+    hmdec_pictures_export_yuvpack)."""
     pictures = list(pictures)
     if not pictures:
         raise ValueError("export_batch: no pictures")
     return _export(pictures, len(pictures), layout, bit_depth, crop, matrix, full_range, msb_aligned, size, filter, out, dtype, mean, std,
                    scale, bias, windows=windows, flip=flip, pixel=pixel, alpha=alpha, memory_format=memory_format, lut=lut, chroma=chroma,
-                   chroma_loc=chroma_loc, warp=warp, border=border, fill=fill, chroma_format=chroma_format, chroma_down=chroma_down)
+                   chroma_loc=chroma_loc, warp=warp, border=border, fill=fill, chroma_format=chroma_format, chroma_down=chroma_down, yuv=yuv,
+                   row_align=row_align)
 
 
 class DecoderColourLut:

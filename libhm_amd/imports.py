@@ -118,6 +118,38 @@ def on_device(t, device):
     return t.is_cuda and t.device.index == device
 
 
+def import_yuvpack(ctx, pics, t, yuv, chroma_down, chroma_loc, size, on_stream):
+    """Context.import_batch(yuv=): the one tensor of words export_batch(yuv=) returns, [N, H, W, 2 or 4] elements, [N, H, W] int32
+    (Y410) or [N, H, P / 4] int32 (V210: rows of P bytes, the width from size=, else all the pixels P has room for)"""
+    import torch
+    code = abi.yuvpack_code(yuv)
+    n, es = len(pics), abi.YUVPACK_ELEMENT[code]
+    if not isinstance(t, torch.Tensor) or not on_device(t, ctx.device):
+        raise ValueError("tensors: one tensor of words on the context's GPU (cuda:%d)" % ctx.device)
+    per = {abi.YUVPACK_UYVY: 2, abi.YUVPACK_YUY2: 2, abi.YUVPACK_Y210: 2, abi.YUVPACK_Y216: 2, abi.YUVPACK_AYUV: 4, abi.YUVPACK_Y416: 4}.get(code)
+    if t.element_size() != es or t.is_floating_point() or t.dim() != (4 if per else 3) or t.shape[0] != n or (per and t.shape[3] != per):
+        raise ValueError("tensors: the [%d, H, ...] tensor of %d-byte words that export_batch(yuv=%r) returns" % (n, es, yuv))
+    st = t.stride()
+    if (per and (st[3] != 1 or (t.shape[2] > 1 and st[2] != per))) or (not per and t.shape[2] > 1 and st[2] != 1):
+        raise ValueError("tensors: the words of a row must be dense")
+    h = t.shape[1]
+    w = t.shape[2] * 4 // 16 * 6 if code == abi.YUVPACK_V210 else t.shape[2]
+    if size is not None:
+        if size[0] > h or size[1] > w:
+            raise ValueError("size: at most the tensor's own (%d, %d)" % (h, w))
+        h, w = size
+    if chroma_down not in abi.DOWN_FILTERS:
+        raise ValueError("chroma_down: one of %s" % sorted(abi.DOWN_FILTERS))
+    row = t.shape[2] * (per or 1) * es
+    pitch = st[1] * es if t.shape[1] > 1 else row
+    d = abi.YUVPACK_DEPTH[code]
+    desc = abi.make_import_desc(abi.EXPORT_PLANAR, -1, (w, h), (d, d), 1 if d <= 8 else 2, 0, abi.SAMPLE_UINT,
+                                chroma_format=abi.YUVPACK_CHROMA[code], down=chroma_down, loc=chroma_loc)
+    stream = torch.cuda.current_stream(ctx.device).cuda_stream if on_stream else 0
+    ctx.import_yuvpack_into(pics, desc, abi.make_import_yuvpack(code), t.data_ptr(), pitch, st[0] * es if n > 1 else pitch * t.shape[1],
+                            1 if on_stream else 0, stream)
+
+
 def import_tensors(ctx, pics, tensors, layout, pixel, bit_depth, chroma_format, chroma_down, chroma_loc, matrix, full_range, msb_aligned,
                    scale, bias, mean, std, size, on_stream):
     import torch
