@@ -249,6 +249,23 @@ int hmdec_picture_colour(libHMDec_picture* pic, int32_t out[5]);
 int hmdec_picture_chroma_loc(libHMDec_picture* pic, int32_t out[3]);
 int hmdec_hash_mismatches(libHMDec_context* ctx);                             /* pictures whose reconstruction disagreed with the hash SEI */
 int hmdec_pictures_decoded(libHMDec_context* ctx);
+/* Error concealment (DESIGN.md §9 "Damaged streams", §9v), for pictures started after the call: 0 off (the default: CTUs no slice
+ * delivered stay as they are, a picture without a decodable slice is dropped, a picture whose reference picture set names a missing
+ * picture as used is refused), 1 copy, 2 motion copy (hmgpu_pictures_conceal).  With 1 or 2:
+ *   - the CTUs of a picture that no slice delivered are filled, behind its loop filters, from the picture of the DPB closest in POC
+ *     (the smaller POC on a tie; with hmdec_set_devices: among the pictures the picture's own context holds; none: mid-grey);
+ *   - a picture none of whose slices could be decoded is not dropped: it is filled whole and stays what its header made it;
+ *   - a missing reference picture that an RPS names as used is replaced by a stand-in of that POC, filled whole, marked as a reference
+ *     (long-term if the entry is) and for output -- once the first IRAP picture of the stream has been started, and while a buffer is free.
+ * Mode 2 moves blocks only along the vectors of a source that was decoded (in the same device context); a stand-in, a picture filled
+ * whole or a copy transferred between contexts is copied as in mode 1.  A stand-in made for a picture that is refused after all
+ * (another used entry of its RPS cannot be replaced) leaves again.  An end of sequence ends the making of stand-ins until the next
+ * IRAP picture.  Concealed pictures are not checked against their hash SEI.  hmdec_picture_concealed: the CTUs of the picture that were concealed (all
+ * of them for a stand-in); hmdec_concealed_pictures / hmdec_concealed_ctus: the totals so far.  A parse-only decoder keeps the same books. */
+void hmdec_set_concealment(libHMDec_context* ctx, int mode);
+int hmdec_picture_concealed(libHMDec_picture* pic);
+int hmdec_concealed_pictures(libHMDec_context* ctx);
+long long hmdec_concealed_ctus(libHMDec_context* ctx);
 void hmdec_set_device_md5(libHMDec_context* ctx, int on);                     /* MD5 hash SEIs checked on the device (hmgpu_picture_hash_begin) (the default;
                                                                                   HMDEC_DEVICE_MD5=0 or 0 here: on the decoder's hash threads) */
 int hmdec_packed_pictures(libHMDec_context* ctx);                             /* pictures handed to the device as packed inputs so far */

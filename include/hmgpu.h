@@ -938,6 +938,53 @@ hmgpu_status hmgpu_import_yuvpack_source_check(hmgpu_ctx* ctx, int32_t n, const 
                                                const void* const src[3], const int64_t pitch_bytes[3],
                                                const int64_t batch_stride_bytes[3]);
 
+/* ------------------------------------------------------------------------------------------------ error concealment
+ * The CTUs of a picture that a damaged stream did not deliver, filled on the device from another picture of the context or with a
+ * constant: up to HMGPU_EXPORT_MAX_BATCH jobs and one kernel launch per call (plus the margin pass of the concealed
+ * pictures).  The library decides nothing: the caller names the destination, the source, the CTUs and the mode.
+ *
+ * A job writes the FINAL planes of dst -- the planes hmgpu_picture_download reads: the SAO planes when the picture went through SAO,
+ * else the reconstruction planes -- and reads the final planes of src.  Of a masked CTU (ctu_mask: bit (a & 7) of byte a >> 3 is CTU a
+ * in raster order; NULL: every CTU) every sample inside width x height is written, in every component the format has; nothing else
+ * is.  c: the component, w_c x h_c its plane, csx / csy its subsampling.
+ *   HMGPU_CONCEAL_COPY    sample (x, y) = sample (x, y) of src.
+ *   HMGPU_CONCEAL_MOTION  per 8x8 luma block of the CTU (its 4x4 / 4x8 / 8x8 chroma samples by format): look at the 4x4 block B of src
+ *                         at the block's top-left corner.  When src has side information (the rule of the motion export below) and
+ *                         list 0 is `used` in B by that export's rule, the slice-type term included, take mv and ref_poc of list 0;
+ *                         else the same of list 1.  With td = clip3(-128, 127, src_poc - ref_poc), tb = clip3(-128, 127, dst_poc -
+ *                         src_poc) (H.265 8.5.3.2.7): tx = (16384 + |td| / 2) / td (truncating), ds = clip3(-4096, 4095, (tb * tx + 32)
+ *                         >> 6), v = clip3(-32768, 32767, sign(ds * mv) * ((|ds * mv| + 127) >> 8)) per coordinate.  v = 0 when td = 0,
+ *                         no list is used, or src has no side information.  dx = (v.hor + 2) >> 2, dy = (v.ver + 2) >> 2 (arithmetic
+ *                         shifts); chroma dx >> csx, dy >> csy.  Sample (x, y) = sample (clamp(x + dx, 0, w_c - 1), clamp(y + dy, 0,
+ *                         h_c - 1)) of src: no vector leaves the plane, margins are never read.
+ *   src == HMGPU_NO_PIC   sample = fill[c], or 1 << (bit_depth_c - 1) where fill[c] < 0 (either mode).
+ *                         "Side information" is a property of the handle: the arrays decompress calls staged there since
+ *                         hmgpu_picture_acquire, hmgpu_picture_upload or hmgpu_picture_commit_received last cleared the record.  This
+ *                         call clears nothing, so a handle reused for a concealed picture without one of those calls still carries
+ *                         the arrays of the picture decoded there before: ask for HMGPU_CONCEAL_COPY from such a source.
+ * Afterwards the margins of dst are the replicated border of its final planes.  The side information of dst, its coverage and whether
+ * it went through SAO stay as they are: a concealed CTU keeps part_size == HMGPU_SIZE_NONE in the side exports.  The launch is not
+ * part of hmgpu_stats.
+ *
+ * The call is ordered on the context's stream: behind every earlier decompress / filter call, before every later one.  Masks are
+ * copied before it returns.  Everything is validated before anything is enqueued and a refused call changes nothing; HMGPU_EINVAL
+ * for: n outside 1 .. HMGPU_EXPORT_MAX_BATCH or jobs NULL; a dst that is no acquired picture; a src that is neither HMGPU_NO_PIC
+ * nor one; dst == src; a dst that is the dst or src of another job of the call; a mode outside the enum; mask bits at or beyond
+ * the number of CTUs set; fill[c] > 2^bit_depth_c - 1 (chroma of a 4:0:0 sequence is not looked at); a non-zero reserved word. */
+enum { HMGPU_CONCEAL_COPY = 0, HMGPU_CONCEAL_MOTION = 1 };
+typedef struct hmgpu_conceal_job {
+  hmgpu_pic dst, src;          /* src: HMGPU_NO_PIC = fill */
+  int32_t mode, dst_poc, src_poc;
+  int32_t fill[3];
+  const uint8_t* ctu_mask;     /* host; (num_ctus + 7) / 8 bytes; NULL = all CTUs */
+  int32_t reserved[4];         /* 0 */
+} hmgpu_conceal_job;
+/* the validation alone: host code, nothing is enqueued */
+hmgpu_status hmgpu_conceal_check(hmgpu_ctx* ctx, int32_t n, const hmgpu_conceal_job jobs[]);
+hmgpu_status hmgpu_pictures_conceal(hmgpu_ctx* ctx, int32_t n, const hmgpu_conceal_job jobs[]);
+/* the CTUs of the picture concealed by hmgpu_pictures_conceal since hmgpu_picture_acquire handed it out (a CTU counts once) */
+hmgpu_status hmgpu_picture_concealed_ctus(hmgpu_ctx* ctx, hmgpu_pic pic, int32_t* out);
+
 /* ------------------------------------------------------------------------------------------------ motion and block export
  * The side information of finished pictures -- motion vectors, reference pictures, prediction mode, CU size, partitioning and QP --
  * written on the device straight into caller-owned device memory: up to HMGPU_EXPORT_MAX_BATCH pictures and one

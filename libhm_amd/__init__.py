@@ -262,6 +262,9 @@ def lib():
                                                     C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
         L.hmgpu_import_yuvpack_source_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ImportDesc), C.POINTER(abi.ImportYuvPack),
                                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hmgpu_conceal_check.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ConcealJob)]
+        L.hmgpu_pictures_conceal.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.ConcealJob)]
+        L.hmgpu_picture_concealed_ctus.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.hmgpu_host_alloc.argtypes = [C.c_size_t]
         L.hmgpu_host_alloc.restype = C.c_void_p
         L.hmgpu_host_free.argtypes = [C.c_void_p]
@@ -1106,6 +1109,26 @@ class Context:
         """import_batch of one picture, its tensors without the batch dimension"""
         from . import imports
         self.import_batch([pic], imports.unsqueeze(tensors), **kw)
+
+    # ---- error concealment
+    def conceal_status(self, jobs, check_only=False):
+        """hmgpu_pictures_conceal (check_only: hmgpu_conceal_check, nothing enqueued), the status returned; jobs: abi.conceal_job_array"""
+        jobs = list(jobs)
+        arr, keep = abi.conceal_job_array(jobs, self.num_ctus)       # (keep: the masks live until the call has copied them)
+        f = lib().hmgpu_conceal_check if check_only else lib().hmgpu_pictures_conceal
+        return f(self._h, len(jobs), arr)
+
+    def conceal(self, jobs):
+        """Fill CTUs of up to 16 pictures from other pictures of the context, or with a constant (hmgpu_pictures_conceal: one launch).
+        jobs: dicts with dst, src (None: fill), mode ("copy" / "motion"), dst_poc, src_poc, fill, mask (None: every CTU) -- abi.conceal_job_array"""
+        jobs = list(jobs)
+        self._chk(self.conceal_status(jobs), "hmgpu_pictures_conceal")
+
+    def concealed_ctus(self, pic):
+        """hmgpu_picture_concealed_ctus: the CTUs of the picture concealed since it was acquired"""
+        n = C.c_int32(-1)
+        self._chk(lib().hmgpu_picture_concealed_ctus(self._h, pic, C.byref(n)), "hmgpu_picture_concealed_ctus")
+        return n.value
 
     def export_motion_into(self, pics, desc, ptrs, pitches, pstrides, bstrides, on_stream=0, stream=0, scale=None, windows=None):
         """hmgpu_pictures_export_motion into device memory the caller owns: ptrs / pitches / plane strides / batch strides (bytes) per

@@ -555,6 +555,50 @@ def make_export_desc(layout, bit_depth=(0, 0), bytes_per_sample=1, msb_aligned=0
     return d
 
 
+CONCEAL_COPY, CONCEAL_MOTION = 0, 1
+
+
+class ConcealJob(C.Structure):
+    _fields_ = [("dst", C.c_int32), ("src", C.c_int32), ("mode", C.c_int32), ("dst_poc", C.c_int32), ("src_poc", C.c_int32),
+                ("fill", C.c_int32 * 3), ("ctu_mask", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+def conceal_mask_bytes(mask, num_ctus):
+    """the ctu_mask bytes of a sequence of num_ctus truth values (CTU a: bit a & 7 of byte a >> 3); a uint8 array passes as it is"""
+    mask = np.asarray(mask)
+    if mask.dtype == np.uint8 and mask.ndim == 1 and mask.size == (num_ctus + 7) // 8:
+        return np.ascontiguousarray(mask)
+    return np.packbits(mask.astype(bool).reshape(num_ctus), bitorder="little")
+
+
+def conceal_job_array(jobs, num_ctus):
+    """the ConcealJob array of a sequence of jobs -- ConcealJob structures, or dicts with dst and, optionally, src (None: fill), mode
+    ("copy" / "motion" or CONCEAL_*), dst_poc, src_poc, fill (three values, negative: mid-grey), mask (None: every CTU; truth values per
+    CTU, or the packed bytes), reserved -- and the list that keeps the masks alive"""
+    jobs = list(jobs)
+    arr = (ConcealJob * max(len(jobs), 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        if isinstance(j, ConcealJob):
+            arr[i] = j
+            continue
+        q = arr[i]
+        q.dst = int(j["dst"])
+        q.src = NO_PIC if j.get("src") is None else int(j["src"])
+        mode = j.get("mode", CONCEAL_COPY)
+        q.mode = {"copy": CONCEAL_COPY, "motion": CONCEAL_MOTION}.get(mode, mode)
+        q.dst_poc, q.src_poc = int(j.get("dst_poc", 0)), int(j.get("src_poc", 0))
+        for k, v in enumerate(j.get("fill", (-1, -1, -1))):
+            q.fill[k] = int(v)
+        if j.get("mask") is not None:
+            m = conceal_mask_bytes(j["mask"], num_ctus)
+            keep.append(m)
+            q.ctu_mask = m.ctypes.data
+        for k, v in enumerate(j.get("reserved", ())):
+            q.reserved[k] = int(v)
+    return arr, keep
+
+
 # ------------------------------------------------------------------------------------------------ marshalling of the export calls
 def ref(x):
     """an optional struct argument: byref(x), or NULL for None"""

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libhmgpu.so")
-SOURCES = ["k_prep.hip", "k_mc.hip", "k_mc_cells.hip", "k_itx.hip", "k_intra.hip", "k_dbk.hip", "k_sao.hip", "k_filter.hip", "k_out.hip", "k_cfmt.hip", "k_unpack.hip", "k_export.hip", "k_export_scale.hip", "k_export_warp.hip", "k_export_fmt.hip", "k_export_yuvpack.hip", "k_motion.hip", "k_residual.hip", "k_transform.hip", "k_lfinfo.hip", "k_metrics.hip", "k_metrics_map.hip", "k_histogram.hip", "k_import.hip", "hmgpu_packed.hip", "hmgpu_api.hip", "hmgpu_input.hip", "hmgpu_output.hip", "hmgpu_export.hip", "hmgpu_side.hip", "hmgpu_analysis.hip", "hmgpu_import.hip"]
+SOURCES = ["k_prep.hip", "k_mc.hip", "k_mc_cells.hip", "k_itx.hip", "k_intra.hip", "k_dbk.hip", "k_sao.hip", "k_filter.hip", "k_out.hip", "k_cfmt.hip", "k_unpack.hip", "k_export.hip", "k_export_scale.hip", "k_export_warp.hip", "k_export_fmt.hip", "k_export_yuvpack.hip", "k_motion.hip", "k_residual.hip", "k_transform.hip", "k_lfinfo.hip", "k_metrics.hip", "k_metrics_map.hip", "k_histogram.hip", "k_import.hip", "k_conceal.hip", "hmgpu_packed.hip", "hmgpu_api.hip", "hmgpu_input.hip", "hmgpu_output.hip", "hmgpu_export.hip", "hmgpu_side.hip", "hmgpu_analysis.hip", "hmgpu_import.hip", "hmgpu_conceal.hip"]
 # Code objects for gfx950 with XNACK (retry on page fault) off, the mode these GPUs run in: with the mode known the compiler schedules loads
 # more freely than for "any" (k_mc_luma 0.213 -> 0.208 ms per launch of 16 pictures, measured A/B/A/B on one box).  A device that runs with
 # HSA_XNACK=1 does not load them: HMGPU_XNACK_ANY=1 in the environment of the build gives the mode-agnostic objects back.

@@ -17,9 +17,11 @@
 namespace hmgpu_host __attribute__((visibility("hidden"))) {
 
 // host -> device copy of a small structure on stream hs: through the context's page-locked ring (hmgpu_ctx::bounce) when it fits
-hipError_t h2d_small(hmgpu_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t hs) {
+hipError_t h2d_small(hmgpu_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t hs, bool* staged) {
   const size_t need = (bytes + 63) & ~(size_t)63;
+  if (staged) *staged = false;
   if (!c->bounce || need > hmgpu_ctx::kBounceSeg) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, hs);
+  if (staged) *staged = true;
   if (c->bounce_off + need > hmgpu_ctx::kBounceSeg) {
     hipStream_t streams[3] = {c->stream, c->copy_stream, c->copy_stream2};
     for (int k = 0; k < 3; k++) (void)hipEventRecord(c->bounce_ev[c->bounce_seg][k], streams[k]);
@@ -566,6 +568,7 @@ void hmgpu_destroy(hmgpu_ctx* c) {
   if (c->d_finals) hipFree(c->d_finals);
   if (c->plane_slab) hipFree(c->plane_slab);
   if (c->scratch) hipFree(c->scratch);
+  if (c->conceal_masks) hipFree(c->conceal_masks);
   if (c->d_ctu_order) hipFree(c->d_ctu_order);
   if (c->stream) hipStreamDestroy(c->stream);
   if (c->stream2) hipStreamDestroy(c->stream2);
@@ -635,6 +638,7 @@ hmgpu_status hmgpu_picture_acquire(hmgpu_ctx* c, hmgpu_pic* out) {
       p.extended = false;
       coverage_clear(p);
       filter_forget(p);
+      p.concealed.clear(); p.concealed_ctus = 0;
       p.dev.sao_applied = 0; p.dev.any_nofilt = 0;
       *out = (hmgpu_pic)i;
       hmgpu_status st = push_final(c, (int)i, c->stream);

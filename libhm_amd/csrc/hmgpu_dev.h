@@ -822,6 +822,28 @@ void launch_intra_chroma_422(const PicDev* pics, const Batch& b, hipStream_t s);
 void launch_deblock(const PicDev* pics, const Batch& b, int dir, int width, int height, hipStream_t s);
 void launch_sao(const PicDev* pics, const Batch& b, int width, int height, int csx, int csy, hipStream_t s);
 void launch_extend(const PicDev* pics, const Batch& b, int width, int height, int mx, int my, int csx, int csy, hipStream_t s);
+// error concealment (k_conceal.hip, hmgpu_pictures_conceal; include/hmgpu.h "error concealment"): everything by value, validated on the
+// host.  Per picture the FINAL planes of the destination and of the source (null: fill), the CTU mask in device memory, and -- motion
+// copy -- the source's HM arrays and slice table, read only where `side` says decompress calls staged them for the whole picture.
+struct ConcealPic {
+  int16_t* dst_y; int16_t* dst_c;              // sample (0, 0) of the luma plane / Cb of the pair plane
+  const int16_t* src_y; const int16_t* src_c;  // the same of the source; null: fill
+  const uint8_t* mask;                         // (num_ctus + 7) / 8 bytes, bit (a & 7) of byte a >> 3 = CTU a
+  const int8_t* part_size; const int8_t* pred_mode;
+  const int16_t* mv[2]; const int8_t* ref_idx[2];
+  const uint16_t* slice_idx; const SliceDev* slices;
+  int32_t mode, side;                          // HMGPU_CONCEAL_*; the source has side information
+  int32_t dst_poc, src_poc;
+  uint32_t fill_y, fill_c;                     // the luma sample; Cb | Cr << 16
+};
+struct ConcealArgs {
+  ConcealPic pic[kMaxBatch];
+  int32_t n, mono;                             // pictures; 4:0:0 (no chroma plane is written)
+  int32_t width, height, log2ctu, ctus_w, num_ctus, parts;
+  int32_t pitch_y, pitch_c;                    // int16 elements
+  int32_t csx, csy;
+};
+void launch_conceal(const ConcealArgs& a, hipStream_t s);
 // kernel-level seams for tests
 void launch_itx_flat(int log2size, int bit_depth, int n, const int16_t* levels, const int8_t* per, const int8_t* rem,
                      const uint8_t* flags, int16_t* resid, hipStream_t s);

@@ -1,5 +1,5 @@
 // hmgpu_host.h -- what the units of the host runtime (hmgpu_api.hip, hmgpu_input.hip, hmgpu_output.hip, hmgpu_export.hip,
-// hmgpu_side.hip, hmgpu_analysis.hip) share: the context and its pictures, the small tools every unit uses, and the helpers that
+// hmgpu_side.hip, hmgpu_analysis.hip, hmgpu_import.hip, hmgpu_conceal.hip) share: the context and its pictures, the small tools every unit uses, and the helpers that
 // more than one unit calls.  Internal: not installed, not included by any kernel file.
 #pragma once
 #include "hmgpu_dev.h"
@@ -52,6 +52,9 @@ struct Picture {
   // side information when all are); cleared by acquire, upload and hmgpu_picture_commit_received
   std::vector<bool> covered;
   int covered_ctus = 0;
+  // CTUs hmgpu_pictures_conceal has filled since the picture was acquired (hmgpu_picture_concealed_ctus)
+  std::vector<bool> concealed;
+  int concealed_ctus = 0;
 };
 
 struct EventPair { hipEvent_t a, b; int kind; };
@@ -172,6 +175,7 @@ struct hmgpu_ctx {
   std::vector<int> intra_launched;    // pictures whose intra kernel ran since the last fault check (k_intra's bounded spin)
   void* scratch = nullptr;            // device scratch of the output calls (packed download, picture hash): grown on demand, kept
   size_t scratch_bytes = 0;
+  uint8_t* conceal_masks = nullptr;   // device: the CTU masks of one hmgpu_pictures_conceal call, kMaxBatch of them (allocated when first used)
   hipEvent_t lane_ev[2] = {nullptr, nullptr};
   int replay_streams = 1;
   int32_t last_err = 0;
@@ -217,8 +221,9 @@ struct HostTimer {                      // adds the time between construction an
     }                                                        \
   } while (0)
 
-// host -> device copy of a small structure on stream hs: through the context's page-locked ring (hmgpu_ctx::bounce) when it fits
-hipError_t h2d_small(hmgpu_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t hs);
+// host -> device copy of a small structure on stream hs: through the context's page-locked ring (hmgpu_ctx::bounce) when it fits.
+// *staged (if asked for): the bytes were taken into the ring, so `src` is the caller's again on return; false: the copy reads `src` itself
+hipError_t h2d_small(hmgpu_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t hs, bool* staged = nullptr);
 
 size_t align_up(size_t v, size_t a);
 

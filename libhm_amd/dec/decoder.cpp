@@ -158,6 +158,7 @@ bool Decoder::push_unit(const uint8_t* d, size_t len, int max_tl, int* nal_type_
     case NAL_EOS:
       finish_picture();
       after_eos_ = true;
+      irap_seen_ = false;                    // (stand-ins again only behind the next IRAP picture)
       break;
     default: break;                        // AUD, EOB, filler data, reserved and unspecified types carry nothing to decode
   }
@@ -359,6 +360,7 @@ void Decoder::apply_rps(const SliceHeader& sh) {
   st_before_.clear();
   st_after_.clear();
   lt_curr_.clear();
+  stand_ins_made_.clear();
   if (is_irap(sh.nal_type) && no_rasl_output_)
     for (auto& p : pool_) if (p.get() != cur_) p->is_reference = p->is_long_term = false;
   if (is_idr(sh.nal_type)) return;
@@ -372,7 +374,9 @@ void Decoder::apply_rps(const SliceHeader& sh) {
     PicData* p = find_ref(poc, !sh.lt_msb_present[i], false);
     if (p) { keep.push_back(p); lt_all.push_back(p); }
     if (sh.lt_used[i]) {
-      if (!p) throw ParseError("long-term reference picture is missing from the decoded picture buffer");
+      // (only the LSBs are known: the stand-in takes the closest earlier POC that has them)
+      if (!p && (p = make_stand_in(sh.lt_msb_present[i] ? poc : cur_->poc - ((cur_->poc - poc) & (max_lsb - 1)), true))) { keep.push_back(p); lt_all.push_back(p); }
+      if (!p) { drop_stand_ins(); throw ParseError("long-term reference picture is missing from the decoded picture buffer"); }
       lt_curr_.push_back(p);
     }
   }
@@ -383,7 +387,8 @@ void Decoder::apply_rps(const SliceHeader& sh) {
       if (q.get() != cur_ && (q->decoded || q->in_flight) && q->is_reference && !q->is_long_term && q->poc == poc && std::find(lt_all.begin(), lt_all.end(), q.get()) == lt_all.end()) p = q.get();
     if (p) keep.push_back(p);
     if (sh.rps.used[i]) {
-      if (!p) throw ParseError("short-term reference picture is missing from the decoded picture buffer");
+      if (!p && (p = make_stand_in(poc, false))) keep.push_back(p);
+      if (!p) { drop_stand_ins(); throw ParseError("short-term reference picture is missing from the decoded picture buffer"); }
       (i < sh.rps.num_negative ? st_before_ : st_after_).push_back(p);
     }
   }
@@ -468,38 +473,134 @@ void Decoder::build_slice_params(const SliceHeader& sh, SliceInfo& si) {
   }
 }
 
-void Decoder::start_picture(const SliceHeader& sh) {
-  cur_ = acquire_buffer();
-  cur_->reset();
+// what a picture in a buffer of the pool takes from the active parameter sets
+void Decoder::init_picture(PicData* p, int poc, int nal_type, int temporal_id) {
+  p->reset();
   // levels in the compact form when one parser walks the picture from front to back (wavefront rows / tiles may be shared out among threads)
   // (4:2:2 / 4:4:4 pictures keep HM's dense layout: the lower square of a 4:2:2 chroma block has its place behind the upper one)
-  cur_->compact = gpu_ && cur_->stg && !pps_->entropy_coding_sync && !pps_->tiles_enabled && sps_->chroma_format_idc <= 1 && !getenv("HMDEC_DENSE_LEVELS");
-  cur_->chroma_format = sps_->chroma_format_idc;
-  cur_->poc = sh.poc;
-  cur_->nal_type = sh.nal_type;
-  cur_->temporal_id = sh.temporal_id;
-  cur_->sao_enabled = sps_->sao;
-  cur_->bit_depth[0] = sps_->bit_depth_luma; cur_->bit_depth[1] = sps_->bit_depth_chroma;
-  cur_->pcm_bit_depth[0] = sps_->pcm_bit_depth_luma; cur_->pcm_bit_depth[1] = sps_->pcm_bit_depth_chroma;
-  cur_->pcm_lf_disable = sps_->pcm && sps_->pcm_loop_filter_disabled;
-  cur_->strong_intra = sps_->strong_intra_smoothing;
-  cur_->range_ext_flags = sps_->range_ext_flags();
-  cur_->colour[0] = sps_->video_full_range; cur_->colour[1] = sps_->colour_primaries; cur_->colour[2] = sps_->transfer_characteristics;
-  cur_->colour[3] = sps_->matrix_coefficients; cur_->colour[4] = sps_->video_format;
-  cur_->chroma_loc[0] = sps_->chroma_loc_info_present; cur_->chroma_loc[1] = sps_->chroma_sample_loc_type_top_field;
-  cur_->chroma_loc[2] = sps_->chroma_sample_loc_type_bottom_field;
-  cur_->owner = this;
-  cur_->num_comps = sps_->chroma_format_idc == 0 ? 1 : 3;
-  cur_->sao_offset_shift[0] = pps_->sao_offset_shift[0]; cur_->sao_offset_shift[1] = pps_->sao_offset_shift[1];
-  cur_->lf_across_tiles = pps_->lf_across_tiles;
-  cur_->conf_window[0] = sps_->conf_left; cur_->conf_window[1] = sps_->conf_right; cur_->conf_window[2] = sps_->conf_top; cur_->conf_window[3] = sps_->conf_bottom;
-  cur_->is_reference = true;                 // "used for short-term reference" until a later RPS says otherwise (8.3.1 end)
-  cur_->is_long_term = false;
+  p->compact = gpu_ && p->stg && !pps_->entropy_coding_sync && !pps_->tiles_enabled && sps_->chroma_format_idc <= 1 && !getenv("HMDEC_DENSE_LEVELS");
+  p->chroma_format = sps_->chroma_format_idc;
+  p->poc = poc;
+  p->nal_type = nal_type;
+  p->temporal_id = temporal_id;
+  p->sao_enabled = sps_->sao;
+  p->bit_depth[0] = sps_->bit_depth_luma; p->bit_depth[1] = sps_->bit_depth_chroma;
+  p->pcm_bit_depth[0] = sps_->pcm_bit_depth_luma; p->pcm_bit_depth[1] = sps_->pcm_bit_depth_chroma;
+  p->pcm_lf_disable = sps_->pcm && sps_->pcm_loop_filter_disabled;
+  p->strong_intra = sps_->strong_intra_smoothing;
+  p->range_ext_flags = sps_->range_ext_flags();
+  p->colour[0] = sps_->video_full_range; p->colour[1] = sps_->colour_primaries; p->colour[2] = sps_->transfer_characteristics;
+  p->colour[3] = sps_->matrix_coefficients; p->colour[4] = sps_->video_format;
+  p->chroma_loc[0] = sps_->chroma_loc_info_present; p->chroma_loc[1] = sps_->chroma_sample_loc_type_top_field;
+  p->chroma_loc[2] = sps_->chroma_sample_loc_type_bottom_field;
+  p->owner = this;
+  p->num_comps = sps_->chroma_format_idc == 0 ? 1 : 3;
+  p->sao_offset_shift[0] = pps_->sao_offset_shift[0]; p->sao_offset_shift[1] = pps_->sao_offset_shift[1];
+  p->lf_across_tiles = pps_->lf_across_tiles;
+  p->conf_window[0] = sps_->conf_left; p->conf_window[1] = sps_->conf_right; p->conf_window[2] = sps_->conf_top; p->conf_window[3] = sps_->conf_bottom;
+  p->is_reference = true;                    // "used for short-term reference" until a later RPS says otherwise (8.3.1 end)
+  p->is_long_term = false;
+  p->needed_for_output = false;
+  p->conceal_mode = concealment_;
+}
+
+// ------------------------------------------------------------------------------------------------ error concealment
+// The picture a damaged picture (or a stand-in) of POC p->poc is filled from: among the pictures of the DPB -- decoded, stand-ins
+// included, and still a reference or waiting for output -- whose samples live in device context `home` (any context: home < 0; parse
+// only: no context is asked for), the closest in POC, the smaller POC on a tie.  Null: there is none.
+PicData* Decoder::conceal_source(const PicData* p, int home) const {
+  PicData* best = nullptr;
+  for (auto& q : pool_) {
+    if (q.get() == p || q.get() == cur_ || !q->decoded || !(q->is_reference || q->needed_for_output)) continue;
+    if (gpu_ && (!q->on_device || (home >= 0 && !((q->present >> home) & 1u)))) continue;
+    const long long d = std::llabs((long long)q->poc - p->poc), b = best ? std::llabs((long long)best->poc - p->poc) : 0;
+    if (!best || d < b || (d == b && q->poc < best->poc)) best = q.get();
+  }
+  return best;
+}
+
+// the totals, once the picture's concealment has been enqueued (parse only: decided)
+void Decoder::note_concealed(PicData* p) {
+  concealed_pictures_++;
+  concealed_ctus_ += p->concealed;
+}
+
+// Motion copy reads the source's motion arrays on the device, so it needs a source that was decoded in the very context the call
+// runs in.  A stand-in or a picture filled whole has none of its own -- the decoder reuses picture handles, and what the handle
+// holds there belongs to an older picture --, and a copy transferred from another context came without them: those are copied.
+int Decoder::conceal_job_mode(const PicData* p, const PicData* src, int home) const {
+  return p->conceal_mode == 2 && src && src->concealed != src->num_ctbs && src->home == home ? HMGPU_CONCEAL_MOTION : HMGPU_CONCEAL_COPY;
+}
+
+// every CTU of a picture that brings no device work of its own (a stand-in, a picture without a decodable slice): filled in the
+// context its source lives in, mid-grey when there is no source
+void Decoder::conceal_whole(PicData* p) {
+  p->concealed = p->num_ctbs;
+  if (!gpu_) { note_concealed(p); return; }
+  flush_batch();                             // (the source may still be waiting there)
+  const PicData* src = conceal_source(p, -1);
+  const int home = src ? src->home : 0;
+  hmgpu_conceal_job job;
+  memset(&job, 0, sizeof(job));
+  job.dst = p->handle; job.src = src ? src->handle : HMGPU_NO_PIC;
+  job.mode = conceal_job_mode(p, src, home);
+  job.dst_poc = p->poc; job.src_poc = src ? src->poc : 0;
+  job.fill[0] = job.fill[1] = job.fill[2] = -1;
+  const hmgpu_status st = hmgpu_pictures_conceal(gpus_[home], 1, &job);
+  if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_pictures_conceal: ") + hmgpu_status_string(st));
+  note_concealed(p);
+  p->home = home; p->present = 1u << home; p->on_device = true;
+}
+
+// A reference picture the RPS of the picture being started names as used is not in the DPB: a stand-in of that POC takes its place
+// (HM: TDecTop::xCreateLostPicture), a copy of the closest picture, marked as a reference and for output, its host arrays as
+// reset_ctu leaves them -- temporal motion vector prediction finds nothing there.  Null -- the caller refuses the picture as ever --
+// with concealment off, before the first IRAP picture of the stream, and when no buffer is free.
+PicData* Decoder::make_stand_in(int poc, bool long_term) {
+  if (!concealment_ || !irap_seen_) return nullptr;
+  // (parser threads: the pictures in front are all closed; the closest of them may still be in flight, and is a candidate once retired)
+  if (threaded()) retire_ready(true);
+  PicData* s = nullptr;
+  try { s = acquire_buffer(); } catch (const ParseError&) { return nullptr; }
+  init_picture(s, poc, NAL_TRAIL_R, 0);
+  s->compact = false;
+  for (int rs = 0; rs < s->num_ctbs; rs++) s->reset_ctu(rs);
+  s->is_long_term = long_term;
+  s->pic_output = true;
+  s->rows_done.store(s->ctbs_h, std::memory_order_release);
+  s->parse_done.store(true, std::memory_order_release);
+  s->in_flight = false;
+  s->decoded = s->filtered = true;
+  s->needed_for_output = true;               // (TDecTop.cpp:275)
+  fprintf(stderr, "hmdec: POC %d is missing: a stand-in takes its place\n", poc);
+  try {
+    conceal_whole(s);
+  } catch (...) {
+    s->decoded = s->is_reference = s->is_long_term = s->needed_for_output = false;
+    throw;
+  }
+  stand_ins_made_.push_back(s);
+  return s;
+}
+
+// the picture being started is refused after all: the stand-ins made for it leave the DPB again
+void Decoder::drop_stand_ins() {
+  for (PicData* s : stand_ins_made_) {
+    s->decoded = s->is_reference = s->is_long_term = s->needed_for_output = false;
+    concealed_pictures_--;
+    concealed_ctus_ -= s->concealed;
+  }
+  stand_ins_made_.clear();
+}
+
+void Decoder::start_picture(const SliceHeader& sh) {
+  cur_ = acquire_buffer();
+  init_picture(cur_, sh.poc, sh.nal_type, sh.temporal_id);
   cur_->pic_output = sh.pic_output && !(is_rasl(sh.nal_type) && skip_rasl_);
-  cur_->needed_for_output = false;
   parse_state_ = PicParseState();
   if (pending_hash_) pending_hash_ = false;  // a hash SEI ahead of its picture does not occur (suffix SEI)
   apply_rps(sh);
+  if (is_irap(sh.nal_type)) irap_seen_ = true;
   if (threaded()) {
     // at most threads_ pictures are parsed at once: wait for one of them before opening another
     for (;;) {
@@ -795,7 +896,7 @@ void Decoder::finish_picture() {
 }
 
 void Decoder::submit_picture(PicData* p, int parsed_ctbs) {
-  if (p->slices.empty()) {                 // no slice of the picture could be decoded: there is nothing to reconstruct or to show
+  if (p->slices.empty() && !p->conceal_mode) {   // no slice of the picture could be decoded: there is nothing to reconstruct or to show
     p->is_reference = p->is_long_term = p->needed_for_output = false;
     p->decoded = false;
     p->rows_done.store(p->ctbs_h, std::memory_order_release);
@@ -803,12 +904,21 @@ void Decoder::submit_picture(PicData* p, int parsed_ctbs) {
     return;
   }
   if (parsed_ctbs < p->num_ctbs) {
-    // slices were lost: HM conceals nothing either (TDecTop.cpp:560 "Warning: ... lost"); the missing CTUs stay as they are
-    fprintf(stderr, "hmdec: POC %d is incomplete (%d of %d CTUs)\n", p->poc, parsed_ctbs, p->num_ctbs);
+    // slices were lost: HM conceals nothing either (TDecTop.cpp:560 "Warning: ... lost").  Without hmdec_set_concealment the missing
+    // CTUs stay as they are; with it they are filled behind the picture's loop filters (flush_batch)
+    fprintf(stderr, "hmdec: POC %d is incomplete (%d of %d CTUs)%s\n", p->poc, parsed_ctbs, p->num_ctbs, p->conceal_mode ? ": concealed" : "");
   }
   p->rows_done.store(p->ctbs_h, std::memory_order_release);
-  for (int rs = 0; rs < p->num_ctbs; rs++) if (p->slice_addr[rs] < 0) p->reset_ctu(rs);     // CTUs no slice delivered
-  if (gpu_) {
+  int lost = 0;
+  for (int rs = 0; rs < p->num_ctbs; rs++) if (p->slice_addr[rs] < 0) { p->reset_ctu(rs); lost++; }     // CTUs no slice delivered
+  if (p->slices.empty()) {
+    // concealment is on: the picture is not dropped; it keeps what its header and NAL unit type made it and is filled whole
+    conceal_whole(p);
+  } else if (p->conceal_mode && lost) {
+    p->concealed = lost;                     // (counted when the fill has been enqueued: flush_batch)
+    if (!gpu_) note_concealed(p);
+  }
+  if (gpu_ && !p->slices.empty()) {
     // the picture joins the pictures retired with it if it predicts from none of them (the B pictures of one temporal level, pictures of
     // different sub-GOPs): one set of launches for all of them (hmgpu_decompress_pictures, TDecGop.cpp:105 / TDecTop.cpp:672 per picture)
     bool dependent = batch_.size() >= 16;
@@ -824,7 +934,7 @@ void Decoder::submit_picture(PicData* p, int parsed_ctbs) {
   p->needed_for_output = p->pic_output;
   last_decoded_ = p;
   pictures_decoded_++;
-  if (!gpu_ && check_hash_ && p->sei_hash_method) check_hash(p);
+  if (!gpu_ && check_hash_ && p->sei_hash_method && !p->concealed) check_hash(p);     // (a concealed picture is not what the SEI describes)
 }
 
 // the device work of the pictures retired together: reconstruction and loop filters of all of them in one batch of launches each
@@ -953,12 +1063,36 @@ void Decoder::flush_batch() {
     if (resync) (void)hmgpu_sync(gpus_[d]);                  // (the dense stand-in of a damaged picture is not page-locked staging: let its copies finish)
     st = hmgpu_filter_pictures(gpus_[d], (int32_t)df.size(), df.data());
     if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_filter_pictures: ") + hmgpu_status_string(st));
+    // error concealment: the CTUs no slice delivered, filled behind the loop filters from the closest picture this context holds --
+    // one call for the incomplete pictures of the batch, none when nothing was lost
+    std::vector<hmgpu_conceal_job> cj;
+    std::vector<std::vector<uint8_t>> cm;
+    for (size_t i = 0; i < n; i++) {
+      const PicData* p = pics[i];
+      if (where[i] != (int)d || !p->concealed) continue;
+      const PicData* src = conceal_source(p, (int)d);
+      cm.emplace_back((size_t)(p->num_ctbs + 7) / 8, (uint8_t)0);
+      for (int rs = 0; rs < p->num_ctbs; rs++) if (p->slice_addr[rs] < 0) cm.back()[(size_t)rs >> 3] |= (uint8_t)(1u << (rs & 7));
+      hmgpu_conceal_job job;
+      memset(&job, 0, sizeof(job));
+      job.dst = p->handle; job.src = src ? src->handle : HMGPU_NO_PIC;
+      job.mode = conceal_job_mode(p, src, (int)d);
+      job.dst_poc = p->poc; job.src_poc = src ? src->poc : 0;
+      job.fill[0] = job.fill[1] = job.fill[2] = -1;
+      job.ctu_mask = cm.back().data();
+      cj.push_back(job);
+    }
+    if (!cj.empty()) {
+      st = hmgpu_pictures_conceal(gpus_[d], (int32_t)cj.size(), cj.data());
+      if (st != HMGPU_OK) throw std::runtime_error(std::string("hmgpu_pictures_conceal: ") + hmgpu_status_string(st));
+      for (size_t i = 0; i < n; i++) if (where[i] == (int)d && pics[i]->concealed) note_concealed(pics[i]);
+    }
   }
   for (size_t i = 0; i < n; i++) { pics[i]->home = where[i]; pics[i]->present = 1u << where[i]; pics[i]->on_device = true; }
   ++submitted_seq_;
   batches_submitted_++;
   for (PicData* p : pics) p->submit_seq = submitted_seq_;
-  if (check_hash_) for (PicData* p : pics) if (p->sei_hash_method) check_hash(p);
+  if (check_hash_) for (PicData* p : pics) if (p->sei_hash_method && !p->concealed) check_hash(p);
 }
 
 bool Decoder::fetch_planes(PicData* pic) {

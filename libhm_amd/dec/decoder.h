@@ -50,6 +50,12 @@ class Decoder {
   // device output: pictures put out stay on the device (hmgpu_picture_export); their planes are downloaded only when asked for
   void set_device_output(bool v) { device_output_ = v; }
   bool device_output() const { return device_output_; }
+  // Error concealment (DESIGN.md §9 "Damaged streams"), for pictures started after the call: 0 off, 1 copy, 2 motion copy
+  // (hmgpu_pictures_conceal).  CTUs no slice delivered are filled from the closest picture in the DPB, a picture without a decodable
+  // slice is concealed whole instead of dropped, and a missing reference picture is replaced by a stand-in instead of refused.
+  void set_concealment(int mode) { concealment_ = mode < 0 || mode > 2 ? 0 : mode; }
+  int concealed_pictures() const { return concealed_pictures_; }
+  long long concealed_ctus() const { return concealed_ctus_; }
   void set_device(int ordinal) { device_ = ordinal; devices_.assign(1, ordinal); }
   // Several device contexts (one per GPU; the same ordinal twice gives two contexts on one GPU): the pictures retired together -- the B
   // pictures of one temporal level, TDecTop.cpp:672 per picture -- are placed round-robin on them, each reference picture is copied once to
@@ -149,6 +155,18 @@ class Decoder {
   template <int SLOTS, class Check, class Side, class Run>
   hmgpu_status export_side(int n, PicData* const* pics, const hmgpu_export_window* windows, void* const* dst, const int64_t* batch_stride_bytes,
                            Check check, Side side, Run run);
+  // error concealment
+  void init_picture(PicData* p, int poc, int nal_type, int temporal_id);   // what a picture takes from the active parameter sets
+  PicData* conceal_source(const PicData* p, int home) const;               // home < 0: in any context
+  void note_concealed(PicData* p);
+  int conceal_job_mode(const PicData* p, const PicData* src, int home) const;
+  void drop_stand_ins();
+  std::vector<PicData*> stand_ins_made_;                                   // by the apply_rps under way
+  void conceal_whole(PicData* p);                                          // every CTU of a picture that has no device work of its own
+  PicData* make_stand_in(int poc, bool long_term);                         // null: no buffer is free
+  int concealment_ = 0, concealed_pictures_ = 0;
+  long long concealed_ctus_ = 0;
+  bool irap_seen_ = false;                                                 // an IRAP picture of the stream has been started
   void close_current();
   void worker_main();
   static void hook_wait_rows(void* self, const PicData* pic, int rows);

@@ -478,6 +478,10 @@ int hmdec_picture_chroma_loc(libHMDec_picture* pic, int32_t out[3]) {
 void hmdec_set_packed_input(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_packed_input(on != 0); }
 int hmdec_hash_mismatches(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.hash_mismatches() : -1; }
 int hmdec_pictures_decoded(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.pictures_decoded() : -1; }
+void hmdec_set_concealment(libHMDec_context* ctx, int mode) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_concealment(mode); }
+int hmdec_picture_concealed(libHMDec_picture* pic) { return pic ? as_pic(pic)->concealed : -1; }
+int hmdec_concealed_pictures(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.concealed_pictures() : -1; }
+long long hmdec_concealed_ctus(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.concealed_ctus() : -1; }
 void hmdec_set_device_md5(libHMDec_context* ctx, int on) { if (ctx) static_cast<Wrapper*>(ctx)->dec.set_device_md5(on != 0); }
 int hmdec_device_batches(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.device_batches() : -1; }
 int hmdec_packed_pictures(libHMDec_context* ctx) { return ctx ? static_cast<Wrapper*>(ctx)->dec.packed_pictures() : -1; }

@@ -147,6 +147,9 @@ struct PicData {
   uint8_t sei_hash[3][16];
   int sei_hash_method = 0;           // 0 = none, 1 = MD5, 2 = CRC, 3 = checksum
   std::atomic<bool> hash_mismatch{false};
+  // error concealment (Decoder::set_concealment): the mode the picture was started under (0: off), and the CTUs that were concealed --
+  // num_ctbs for a stand-in of a missing reference picture or a picture none of whose slices could be decoded
+  int conceal_mode = 0, concealed = 0;
 
   PicData() { memset(&stg_meta, 0, sizeof(stg_meta)); memset(&stg_co, 0, sizeof(stg_co)); }
   PicData(const PicData&) = delete;
@@ -226,6 +229,7 @@ struct PicData {
     hash_mismatch = false;
     dl_ticket = 0;
     sei_hash_method = 0;
+    conceal_mode = concealed = 0;
   }
   void reset_ctu(int rs) {
     const size_t first = (size_t)rs * parts;

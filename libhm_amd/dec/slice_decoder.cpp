@@ -84,7 +84,9 @@ bool SliceDecoder::decode_segment(const SliceHeader& sh, int slice_idx, const ui
     for (int i = 0; i < sh.num_ref_idx[l]; i++) if (slice_->ref_poc[l][i] > pic_.poc) no_backward_pred_ = false;
   const int W = pic_.ctbs_w;
   ctb_ts_ = pps_.ctb_rs_to_ts[sh.segment_address];
-  if (ctb_ts_ != st_.next_ctb_ts) throw ParseError("slice segment does not continue where the previous one ended");
+  // (with error concealment a new slice may start behind CTUs that were lost: it depends on nothing in front of it, and the gap is filled later)
+  if (ctb_ts_ != st_.next_ctb_ts && !(pic_.conceal_mode && !sh.dependent && ctb_ts_ > st_.next_ctb_ts))
+    throw ParseError("slice segment does not continue where the previous one ended");
   if (!sh.dependent) st_.last_qp = sh.qp;           // first quantisation group in a slice: qPY_PREV = SliceQpY (8.6.1)
   cabac_.start(sh.data_bit_offset);
   bool first = true, done = false;

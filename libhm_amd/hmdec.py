@@ -49,6 +49,12 @@ def lib():
         L.hmdec_hash_mismatches.argtypes = [C.c_void_p]
         L.hmdec_pictures_decoded.argtypes = [C.c_void_p]
         L.hmdec_device_batches.argtypes = [C.c_void_p]
+        L.hmdec_set_concealment.argtypes = [C.c_void_p, C.c_int]
+        L.hmdec_set_concealment.restype = None
+        L.hmdec_picture_concealed.argtypes = [C.c_void_p]
+        L.hmdec_concealed_pictures.argtypes = [C.c_void_p]
+        L.hmdec_concealed_ctus.argtypes = [C.c_void_p]
+        L.hmdec_concealed_ctus.restype = C.c_longlong
         L.hmdec_picture_range_ext_flags.argtypes = [C.c_void_p]
         L.hmdec_picture_chroma_format.argtypes = [C.c_void_p]
         L.hmdec_picture_sao_offset_shift.argtypes = [C.c_void_p, C.c_int]
@@ -176,6 +182,12 @@ class Picture:
     @property
     def poc(self):
         return lib().libHMDEC_get_POC(self.h)
+
+    @property
+    def concealed(self):
+        """CTUs of the picture that were concealed (hmdec_picture_concealed): 0 for an undamaged picture, all of them for the
+        stand-in of a missing reference picture and for a picture none of whose slices could be decoded"""
+        return lib().hmdec_picture_concealed(self.h)
 
     def size(self, c=0):
         return lib().libHMDEC_get_picture_width(self.h, c), lib().libHMDEC_get_picture_height(self.h, c)
@@ -679,10 +691,15 @@ def _sdr_lut(ctx, src, depth):
     return _sdr_luts[key]
 
 
+CONCEALMENT = {None: 0, "copy": 1, "motion": 2}
+
+
 class Decoder:
     def __init__(self, parse_only=False, device=0, check_hash=True, max_temporal_layer=-1, threads=1, device_md5=None, devices=None,
-                 packed_input=False, device_output=False):
-        """devices: GPU ordinals of several device contexts (hmdec_set_devices; the same ordinal twice = two contexts on one GPU).
+                 packed_input=False, device_output=False, concealment=None):
+        """concealment: None (damaged streams as ever), "copy" or "motion" (hmdec_set_concealment): lost CTUs are filled from the
+        closest picture, a picture without a decodable slice is filled whole, a missing reference picture gets a stand-in.
+        devices: GPU ordinals of several device contexts (hmdec_set_devices; the same ordinal twice = two contexts on one GPU).
         packed_input: 4:0:0 / 4:2:0 pictures reach the device as packed inputs (hmdec_set_packed_input).
         device_output: pictures put out stay on the device (hmdec_set_device_output): Picture.export, planes downloaded lazily"""
         self.ctx = lib().libHMDec_new_decoder()
@@ -695,6 +712,11 @@ class Decoder:
         lib().hmdec_set_threads(self.ctx, threads)
         lib().hmdec_set_packed_input(self.ctx, 1 if packed_input else 0)
         lib().hmdec_set_device_output(self.ctx, 1 if device_output else 0)
+        if concealment not in CONCEALMENT:
+            lib().libHMDec_free_decoder(self.ctx)
+            self.ctx = None
+            raise ValueError("concealment: None, \"copy\" or \"motion\"")
+        lib().hmdec_set_concealment(self.ctx, CONCEALMENT[concealment])
         lib().libHMDec_set_SEI_Check(self.ctx, check_hash)
         lib().libHMDec_set_max_temporal_layer(self.ctx, max_temporal_layer)
         if device_md5 is not None:                 # MD5 hash SEIs checked on the device (default: the decoder's hash threads / HMDEC_DEVICE_MD5)
@@ -750,6 +772,14 @@ class Decoder:
     @property
     def pictures_decoded(self):
         return lib().hmdec_pictures_decoded(self.ctx)
+
+    def concealed_pictures(self):
+        """pictures concealed so far, whole or in part, stand-ins of missing reference pictures included (hmdec_concealed_pictures)"""
+        return lib().hmdec_concealed_pictures(self.ctx)
+
+    def concealed_ctus(self):
+        """CTUs concealed so far (hmdec_concealed_ctus)"""
+        return int(lib().hmdec_concealed_ctus(self.ctx))
 
     @property
     def packed_pictures(self):
